@@ -2,6 +2,14 @@
 """bench.py - merged-weight GB/s of the spectral-merge hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload llama3-70b-slice|llama3-8b|8192sq] [--k K]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the --steps steps and prints the headline (value, ms_per_step).
+--full adds everything else it measures: the same steps in the other norm mode, the per-kernel
+profile with the roofline (and its two rocprofv3 --pmc passes) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed: every merged tensor as
+DIR/merged_<i>.npy (float32; rank 0; a tensor larger than its share of a 48 MB budget is
+sampled at fixed, seeded positions), so that two builds can be compared output for output.
 
 Default workload = the configuration BASELINE.json's metric is quoted on: the Llama-3-70B
 3-finetune merge, this GPU's 1/8 slice of the block tensors (10 of 80 blocks), K = 3.
@@ -191,15 +199,18 @@ def make_inputs(shapes, k, device, seed, shared_base=None):
     return layers
 
 
-def run_step(engines, layers, k, norm_mode="exact"):
+def run_step(engines, layers, k, norm_mode="exact", sink=None):
     """One pass over the tensor list.  With more than one engine the tensors are merged
     concurrently, one worker thread + HIP stream + workspace per engine (the C calls release
-    the GIL); tensors are independent units, so this is the same job, pipelined."""
+    the GIL); tensors are independent units, so this is the same job, pipelined.
+    sink(i, out), if given, is called with every merged tensor on the stream that produced it."""
     if len(engines) == 1:
         outs = 0
-        for base, fts in layers:
+        for i, (base, fts) in enumerate(layers):
             out, rep = engines[0][0].merge_layer(fts, [base] * k, ALPHAS[:k], base, norm_mode=norm_mode)
             outs += out.numel()
+            if sink is not None:
+                sink(i, out)
         return outs
     import threading
     counts = [0] * len(engines)
@@ -223,6 +234,8 @@ def run_step(engines, layers, k, norm_mode="exact"):
                     base, fts = layers[i]
                     out, rep = eng.merge_layer(fts, [base] * k, ALPHAS[:k], base, norm_mode=norm_mode)
                     counts[w] += out.numel()
+                    if sink is not None:
+                        sink(i, out)
             stream.synchronize()
         except Exception as e:            # surface worker failures
             errors.append(e)
@@ -235,6 +248,40 @@ def run_step(engines, layers, k, norm_mode="exact"):
     if errors:
         raise errors[0]
     return sum(counts)
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: float32 bytes written in all
+DUMP_SEED = 20251015
+
+
+class OutputDump:
+    """--dump-outputs: a run_step sink that keeps, on the device, every merged tensor of one step as float32 - whole,
+    or at fixed positions (a seeded sample drawn once, the same in every run) when it is larger than its equal share
+    of DUMP_BUDGET_BYTES - and writes them as DIR/merged_<i>.npy."""
+
+    def __init__(self, shapes, device):
+        import numpy as np
+        share = DUMP_BUDGET_BYTES // 4 // max(len(shapes), 1)
+        self.index = []
+        for i, (r, c) in enumerate(shapes):
+            n = r * c
+            if n <= share:
+                self.index.append(None)
+            else:
+                pos = np.unique(np.random.default_rng([DUMP_SEED, i]).integers(0, n, size=share))
+                self.index.append(torch.from_numpy(pos).to(device))
+        self.got = {}
+
+    def __call__(self, i, out):
+        flat = out.reshape(-1)
+        self.got[i] = (flat if self.index[i] is None else flat.index_select(0, self.index[i])).float()
+
+    def write(self, out_dir):
+        import numpy as np
+        d = Path(out_dir)
+        d.mkdir(parents=True, exist_ok=True)
+        for i in range(len(self.index)):
+            np.save(d / f"merged_{i:03d}.npy", self.got[i].cpu().numpy())
 
 
 CPU_BASELINE_THREADS = 16      # capped: the sort-bound oracle gets SLOWER with hundreds of threads
@@ -418,7 +465,17 @@ def main():
                          "synthetic safetensors models under --product-root, N ranks partition ONE model (strong scaling), "
                          "base shards travel by broadcast, every rank writes its results into the output shards")
     ap.add_argument("--product-root", default="/dev/shm/smbench_product")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the steps in the other norm mode, the per-kernel profile "
+                         "and roofline (with its rocprofv3 --pmc passes) and the CPU baseline (the --no-* options still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/merged_<i>.npy (float32, rank 0; large tensors at "
+                         "fixed, seeded positions; at most 48 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.product_path:
+        ap.error("--dump-outputs measures the resident-tensor path, not --product-path")
     from shardmerge_amd.constants import tune_hip_queues
     tune_hip_queues()                   # 8 engines + their side streams: before the first GPU call (children inherit it)
 
@@ -483,6 +540,7 @@ def main():
             off += r * c
     layers = make_inputs(shapes, k, device, seed=1000 + 17 * rank, shared_base=shared)
     n_elems = sum(r * c for r, c in shapes)
+    dump = OutputDump(shapes, device) if args.dump_outputs and rank == 0 else None
 
     # the GPU of a fresh box idles at its lowest clocks and the first steps of a process also pay for code-object
     # loading and workspace growth: run untimed steps for --prewarm-seconds before the W warmup steps (one fresh
@@ -500,8 +558,8 @@ def main():
     if dist:
         dist.barrier()
     t0 = time.time()
-    for _ in range(args.steps):
-        run_step(engines, layers, k, args.norm_mode)
+    for step in range(args.steps):
+        run_step(engines, layers, k, args.norm_mode, sink=dump if step == args.steps - 1 else None)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -510,6 +568,8 @@ def main():
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if dump is not None:
+        dump.write(args.dump_outputs)
 
     out_bytes = 2.0 * n_elems * args.steps * world
     value = out_bytes / dt / 1e9
@@ -535,7 +595,7 @@ def main():
     hits = sum(eng.ctx.debug_query("spec_hits") for eng, _ in engines)
     result["cull_speculation"] = {"checked": checked, "confirmed": hits, "hit_rate": (hits / checked) if checked else None}
 
-    if not args.no_alt_mode:
+    if args.full and not args.no_alt_mode:
         # the same steps in the other norm mode, for comparison (the headline stays the conforming mode's)
         alt = "exact" if args.norm_mode == "reference_cpu" else "reference_cpu"
         run_step(engines, layers, k, alt)
@@ -556,7 +616,7 @@ def main():
         result["alt_norm_mode"] = {"norm_mode": alt, "value": out_bytes / dta / 1e9, "ms_per_step": dta / args.steps * 1e3,
                                    "pipeline_hbm_frac": alg_bytes_per_elem(k) * n_elems * args.steps / dta / HBM_PEAK}
 
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         # per-kernel device time: HIP events around every launch on the launch stream
         # (library profiling mode), one extra pass, single stream
         engine.ctx.profile(True)
@@ -597,7 +657,7 @@ def main():
             for name, (n, ms) in table.items() if kernel_alg_bytes_per_elem(name, k) > 0 and ms > 0}
         result["kernels"] = kern
         result["device_ms_profiled_step"] = round(tot_ms, 3)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(k)
     if rank == 0:
         print(json.dumps(result))

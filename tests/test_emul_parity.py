@@ -514,9 +514,16 @@ def test_reference_cpu_mode_follows_the_biased_norms_everywhere(engine):
     from oracle import spectral_oracle as so
     base, fts = so.synthetic_layer(2048, 2048, 2, seed=6048)
     tr, trx = so.LayerTrace(), so.LayerTrace()
-    so.merge_layer(fts, [base, base], so.ALPHAS[:2], base, trace=tr)
-    with so.exact_norms():
-        so.merge_layer(fts, [base, base], so.ALPHAS[:2], base, trace=trx)
+    # the oracle on ONE thread: on some hosts torch's multi-threaded CPU ifftn of a 2048 x 2048 complex64 tensor
+    # applies the 1/N scale twice (the oracle's merged delta comes out 2048^2 times too small); one thread is exact
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        so.merge_layer(fts, [base, base], so.ALPHAS[:2], base, trace=tr)
+        with so.exact_norms():
+            so.merge_layer(fts, [base, base], so.ALPHAS[:2], base, trace=trx)
+    finally:
+        torch.set_num_threads(threads)
     d_ref, d_exact = tr.steps[0].dot, trx.steps[0].dot
     assert abs(d_ref - d_exact) > 5e-6                      # the effect under test exists at this size
     got = {}

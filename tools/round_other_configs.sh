@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT
 cd $R
 for w in "8192sq --k 2 --blocks 8" "8192sq --k 3 --blocks 8" "llama3-8b --k 2 --blocks 8" "llama3-8b --k 4 --blocks 8"; do
-  timeout -k 10 300 python3 bench.py --workload $w --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python3 -c '
+  timeout -k 10 300 python3 bench.py --full --workload $w --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python3 -c '
 import json, sys
 r = json.loads(sys.stdin.read())
 a = r["alt_norm_mode"]

@@ -11,7 +11,9 @@ for s in "28672 8192 3" "8192 28672 3"; do
   python3 tools/pmc_summary.py gpurun_out/prof_pmcA gpurun_out/prof_pmcB > gpurun_out/${TAG}_pmc_sq_counters_$1x$2_k$3.txt
 done
 cd /tmp && export TMPDIR=/tmp
-rm -rf $R/gpurun_out/prof_bench1
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_bench1 -- python3 $R/bench.py --streams 1 --no-cpu-baseline --no-alt-mode --no-live-traffic > $R/gpurun_out/prof_bench1.log 2>&1 || exit 1
-cp $(find $R/gpurun_out/prof_bench1 -name "*kernel_stats.csv" | head -1) $R/gpurun_out/${TAG}_rocprofv3_kernel_stats_bench_streams1.csv
-tail -1 $R/gpurun_out/prof_bench1.log | cut -c1-400
+OUT=${OUT:-$R/profile_out}      # the bench's kernel-trace run (--full: its profiled pass gives roofline.avg_launch_ms)
+mkdir -p $OUT
+rm -rf $OUT/prof_bench1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench1 -- python3 $R/bench.py --full --streams 1 --no-cpu-baseline --no-alt-mode --no-live-traffic > $OUT/prof_bench1.log 2>&1 || exit 1
+cp $(find $OUT/prof_bench1 -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_rocprofv3_kernel_stats_bench_streams1.csv
+tail -1 $OUT/prof_bench1.log | cut -c1-400
