@@ -180,6 +180,17 @@ int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, s
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream);
 int smhip_div_scalar(smhip_ctx* ctx, const void* x, int dtype, size_t n, float s, void* out, void* stream);
 
+/* ---- LoRA: the finetune weight a LoRA adapter defines, W = base + scale * (lora_b @ lora_a).
+ *      out = round_dtype(base + scale * (lora_b @ lora_a)), all row-major: base/out [rows x cols] of `dtype`,
+ *      lora_a [rank x cols], lora_b [rows x rank] of `factor_dtype` (SMHIP_BF16/F16/F32); 1 <= rank <= 512;
+ *      out must not overlap an input.  Any rows, cols >= 1 (no transform plan involved).  The product is
+ *      accumulated in fp32 (16-bit factors on MFMA, products exact) and added as fma(scale, sum, base), rounded
+ *      once into `dtype`.  Pointers need only the alignment of their element type.  Profile names:
+ *      "lora_pack" (the factors copied k-contiguous into the workspace) and "lora_apply". ---- */
+int smhip_lora_apply(smhip_ctx* ctx, const void* base, int dtype, int rows, int cols,
+                     const void* lora_a, const void* lora_b, int factor_dtype, int rank, float scale,
+                     void* out, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device

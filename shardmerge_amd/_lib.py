@@ -103,6 +103,7 @@ class SmhipLibrary:
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]
         d.smhip_exact_norm.argtypes = [P, P, I, C.c_size_t, C.POINTER(D), P]
         d.smhip_div_scalar.argtypes = [P, P, I, C.c_size_t, C.c_float, P, P]
+        d.smhip_lora_apply.argtypes = [P, P, I, I, I, P, P, I, I, C.c_float, P, P]
         d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

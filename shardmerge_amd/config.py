@@ -19,6 +19,11 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
                                 # device="cpu" output) | exact (accurate norms: the reference's device="cuda" numerics)
       operator: fourier         # fourier (default: what the reference CLI hard-wires, __main__.py:22,67)
                                 # | addition | task_addition (shard/merge/addition.py, taskaddition.py)
+
+A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
+adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
+base + s * lora_B @ lora_A applied to its own `base` (shardmerge_amd/adapter.py).  Same keys;
+no new option.
 """
 from __future__ import annotations
 

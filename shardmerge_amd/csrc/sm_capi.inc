@@ -156,6 +156,23 @@ int smhip_div_scalar(smhip_ctx* ctx, const void* x, int dtype, size_t n, float s
     SM_FINISH(ctx, ctx->pipe.fn_div_scalar(x, dtype, n, s, out));
 }
 
+int smhip_lora_apply(smhip_ctx* ctx, const void* base, int dtype, int rows, int cols, const void* lora_a,
+                     const void* lora_b, int factor_dtype, int rank, float scale, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!base || !lora_a || !lora_b || !out || rows < 1 || cols < 1) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");
+    if (dtype < SMHIP_BF16 || dtype > SMHIP_F32 || factor_dtype < SMHIP_BF16 || factor_dtype > SMHIP_F32)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "bad dtype");
+    if (rank < 1 || rank > smhip::LORA_MAX_RANK) return ctx->pipe.fail(SMHIP_ERR_ARG, "rank out of range (1..512)");
+    const size_t bes = dtype == SMHIP_F32 ? 4 : 2, fes = factor_dtype == SMHIP_F32 ? 4 : 2;
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)rows * cols * bes;
+    auto overlaps = [&](const void* p, size_t bytes) { return (uintptr_t)p < o1 && o0 < (uintptr_t)p + bytes; };
+    if (overlaps(base, (size_t)rows * cols * bes) || overlaps(lora_a, (size_t)rank * cols * fes) ||
+        overlaps(lora_b, (size_t)rows * rank * fes))
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "lora_apply: out overlaps an input");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.lora_apply(base, dtype, rows, cols, lora_a, lora_b, factor_dtype, rank, scale, out));
+}
+
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
     SM_GUARD(ctx);
     if (!norm_out || (n > 0 && !x)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

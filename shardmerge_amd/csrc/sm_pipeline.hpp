@@ -15,6 +15,7 @@
 #include "sm_kernels.hpp"
 #include "sm_aten_norm.hpp"
 #include "sm_bluestein.hpp"
+#include "sm_lora.hpp"
 
 namespace smhip {
 
@@ -196,6 +197,11 @@ SM_KERNEL_TAG(KSpecRescale, SpecRescaleParams, "spec_rescale", k_spec_rescale(ex
 SM_KERNEL_TAG(KDftp, DftpParams, "dft_across_slices", k_dftp(ex, p))
 SM_KERNEL_TAG(KDftpPairs, DftpParams, "dft_across_slices", k_dftp_pairs(ex, p))
 SM_KERNEL_TAG(KTranspose, TransposeParams, "transpose", k_transpose(ex, p))
+// LoRA low-rank update (sm_lora.hpp): the factor packing and the MFMA product, one per factor dtype
+SM_KERNEL_TAG_LB(KLoraPack, LoraPackParams, "lora_pack", k_lora_pack(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KLoraBf16, LoraApplyParams, "lora_apply", k_lora_apply<DT_BF16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KLoraF16, LoraApplyParams, "lora_apply", k_lora_apply<DT_F16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KLoraF32, LoraApplyParams, "lora_apply", k_lora_apply<DT_F32>(ex, p), 256, 2)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -219,7 +225,7 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KSpecCheck) X(KSelect3) X(KReduceCand) X(KReduce) X(KSlerpConsts) X(KSumPartials) X(KClassEmf)
 #define SM_SIDE_KERNELS_2(X) X(KDeltaNorms) X(KSumPartialsN) X(KBlend) X(KCombine) X(KExpand) X(KPack) X(KSplit) X(KJoin) \
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
-    X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose)
+    X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32)
 #define SM_SIDE_GROUPS 7         // groups 3 - 6: the run-time planned (DynPlan) transform kernels
 
 // ---- FFT planner ---------------------------------------------------------------
@@ -342,7 +348,7 @@ class Pipeline {
     explicit Pipeline(int device) : be(device) {}
     ~Pipeline() {
         for (auto& kv : plans_) if (kv.second.dev.tw) be.free((void*)kv.second.dev.tw);
-        for (Buffer* b : {&cand_, &t1_, &small_, &tmpA_, &tmpB_, &tmpC_, &fullS_, &saveR_, &saveI_, &aten_, &emf_}) if (b->p) be.free(b->p);
+        for (Buffer* b : {&cand_, &t1_, &small_, &tmpA_, &tmpB_, &tmpC_, &fullS_, &saveR_, &saveI_, &aten_, &emf_, &lora_}) if (b->p) be.free(b->p);
         for (Buffer& b : pool_) if (b.p) be.free(b.p);
         if (mail_) be.free_host(mail_);
         for (Buffer& b : inter_) if (b.p) be.free(b.p);
@@ -402,7 +408,7 @@ class Pipeline {
         return SMHIP_OK;
     }
     size_t workspace_bytes() const {
-        size_t t = cand_.cap + t1_.cap + small_.cap + tmpA_.cap + tmpB_.cap + tmpC_.cap + fullS_.cap + saveR_.cap + saveI_.cap + aten_.cap + emf_.cap;
+        size_t t = cand_.cap + t1_.cap + small_.cap + tmpA_.cap + tmpB_.cap + tmpC_.cap + fullS_.cap + saveR_.cap + saveI_.cap + aten_.cap + emf_.cap + lora_.cap;
         for (const Buffer& b : inter_) t += b.cap;
         for (const Buffer& b : rowspec_) t += b.cap;
         for (const Buffer& b : pool_) t += b.cap;
@@ -2359,6 +2365,33 @@ class Pipeline {
         be.template launch<KDivScalar>(stream_grid(n, 256, q.chunks), 256, LDS_SCRATCH_FLOATS * 4, q, stream);
         return SMHIP_OK;
     }
+    // ---- LoRA: out = round(base + scale * (b @ a)) (sm_lora.hpp); arguments checked by smhip_lora_apply ----
+    int lora_apply(const void* base, int dtype, int rows, int cols, const void* a, const void* b, int fdtype, int rank,
+                   float scale, void* out) {
+        const size_t es = fdtype == DT_F32 ? 4 : 2, bes = dtype == DT_F32 ? 4 : 2;
+        if ((uintptr_t)a % es || (uintptr_t)b % es || (uintptr_t)base % bes || (uintptr_t)out % bes)
+            return fail(SMHIP_ERR_ARG, "lora_apply: a pointer is not aligned to its element size");
+        const int rp = (int)round_up((size_t)rank, LORA_KSTEP);
+        const size_t rows_pad = round_up((size_t)rows, LORA_TILE), cols_pad = round_up((size_t)cols, LORA_TILE);
+        const size_t tiles = (rows_pad / LORA_TILE) * (cols_pad / LORA_TILE);
+        const size_t pack_tiles = (rows_pad + cols_pad) / LORA_PACK_O * (size_t)(rp / LORA_KSTEP);
+        if (tiles > (size_t)1 << 30 || pack_tiles > (size_t)1 << 30) return fail(SMHIP_ERR_ARG, "lora_apply: tensor too large");
+        int rc;
+        if ((rc = ensure(lora_, (rows_pad + cols_pad) * (size_t)rp * es))) return rc;
+        LoraPackParams q;
+        q.a = a; q.b = b; q.bp = lora_.p; q.ap = (char*)lora_.p + rows_pad * (size_t)rp * es;
+        q.rows = rows; q.cols = cols; q.rank = rank; q.rp = rp; q.esize = (int)es;
+        q.b_tiles = (int)(rows_pad / LORA_PACK_O * (size_t)(rp / LORA_KSTEP));
+        be.template launch<KLoraPack>((int)pack_tiles, 256, LORA_PACK_O * (LORA_KSTEP + 1) * 4, q, stream);
+        LoraApplyParams l;
+        l.base = base; l.out = out; l.dtype = dtype; l.ap = q.ap; l.bp = q.bp;
+        l.rows = rows; l.cols = cols; l.rp = rp; l.tiles_j = (int)(cols_pad / LORA_TILE); l.scale = scale;
+        l.vec = cols % 4 == 0 && (uintptr_t)base % (4 * bes) == 0 && (uintptr_t)out % (4 * bes) == 0;
+        if (fdtype == DT_BF16) be.template launch<KLoraBf16>((int)tiles, 256, 0, l, stream);
+        else if (fdtype == DT_F16) be.template launch<KLoraF16>((int)tiles, 256, 0, l, stream);
+        else be.template launch<KLoraF32>((int)tiles, 256, 0, l, stream);
+        return SMHIP_OK;
+    }
     int fn_exact_norm(const void* x, int dtype, size_t n, double* norm_out) {
         *norm_out = 0.0;
         if (n == 0) return SMHIP_OK;
@@ -2501,6 +2534,7 @@ class Pipeline {
   private:
     std::map<int, HostPlan> plans_;
     Buffer t1_, small_, tmpA_, tmpB_, tmpC_, fullS_, saveR_, saveI_, cand_, aten_, emf_;
+    Buffer lora_;                       // packed LoRA factors (lora_apply)
     std::vector<Buffer> pool_ = std::vector<Buffer>(4);
     std::vector<char> pool_busy_ = std::vector<char>(4, 1);
     int pidx_[4] = {0, 1, 2, 3};

@@ -38,6 +38,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from .adapter import ADAPTER_CONFIG, ADAPTER_WEIGHTS, is_adapter_dir, read_header
 from .config import MergeConfig
 from .constants import DEFAULT_NORM_MODE, INPUT_LAYER, OUTPUT_LAYER
 from .index import LocalModelIndex
@@ -176,6 +177,14 @@ def config_stamp(config: MergeConfig) -> str:
            "finetune_merge": [asdict(m) for m in config.finetune_merge],
            "merge_options": dict(sorted((config.merge_options or {}).items())),
            "operator": getattr(config, "operator", "fourier"), "norm_mode": getattr(config, "norm_mode", None) or DEFAULT_NORM_MODE}
+    adapters = {}
+    for m in config.finetune_merge:
+        path = Path(config.storage_path) / m.model
+        if is_adapter_dir(path):            # a LoRA adapter's identity: its config and its tensors' header
+            adapters[m.model] = {"adapter_config": hashlib.sha256((path / ADAPTER_CONFIG).read_bytes()).hexdigest(),
+                                 "adapter_header": hashlib.sha256(read_header(path / ADAPTER_WEIGHTS)[0]).hexdigest()}
+    if adapters:
+        doc["adapters"] = adapters
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 
@@ -442,8 +451,8 @@ async def run_partitioned_merge(config: MergeConfig, index: LocalModelIndex, dev
         sl = ShardLayer(rank_of[name], s, name, False)
         if sl.layer_number >= 0 and fourier:
             models = [m for m in config.finetune_merge if m.use_layer_index(sl.layer_number)]
-            uris = [m.model for m in models] + [m.base for m in models if m.base != base_uri]
-            schedule.append([(u, name) for u in dict.fromkeys(uris)])
+            reqs = [r for m in models for r in merger._finetune_requests(m, name)] + [(m.base, name) for m in models]
+            schedule.append([r for r in dict.fromkeys(reqs) if r != (base_uri, name)])
         else:
             schedule.append(merger._layer_requests(sl))
     loader = None
@@ -595,14 +604,14 @@ async def _merge_block_tensor(merger: FourierMerge, engine, sl: ShardLayer, base
     if not models:
         raise ValueError(f"No finetune covers layer {number} ({sl.layer_name})")
     dev = str(engine.device)
-    loaded = {cfg.output_base_model: base_view}
+    loaded = {(cfg.output_base_model, sl.layer_name): base_view}
 
-    async def fetch(uri):
-        if uri not in loaded:
-            loaded[uri] = await merger._fetch(uri, sl.layer_name, dev)
-        return loaded[uri]
+    async def fetch(uri, tname=sl.layer_name):
+        if (uri, tname) not in loaded:
+            loaded[(uri, tname)] = await merger._fetch(uri, tname, dev)
+        return loaded[(uri, tname)]
 
-    fts = [await fetch(m.model) for m in models]
+    fts = [await merger.finetune_tensor(m, sl.layer_name, dev, fetch) for m in models]
     bases = [await fetch(m.base) for m in models]
     out, report = engine.merge_layer(fts, bases, [m.alpha for m in models], base_view,
                                      target_norm_offset=merger.target_norm_offset, cull_start_pct=merger.cull_start_pct,

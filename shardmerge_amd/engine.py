@@ -251,6 +251,28 @@ class Engine:
             norm = self.exact_norm(x)
         return (self.div_scalar(x, norm) if norm != 0 else self._dev(x, x.dtype if x.dtype in _DTYPE_CODE else torch.float32)), norm
 
+    # -- LoRA adapters ---------------------------------------------------------------------
+    def lora_apply(self, base: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float) -> torch.Tensor:
+        """the finetune weight a LoRA adapter defines: ``base + scale * (b @ a)`` accumulated in fp32 and rounded once
+        into base's dtype (``smhip_lora_apply``).  base [out, in], a = lora_A [r, in], b = lora_B [out, r]."""
+        if base.ndim != 2 or a.ndim != 2 or b.ndim != 2:
+            raise ValueError(f"lora_apply: 2-D tensors expected, got base {list(base.shape)}, a {list(a.shape)}, b {list(b.shape)}")
+        rows, cols = base.shape
+        rank = a.shape[0]
+        if a.shape[1] != cols or b.shape != (rows, rank):
+            raise ValueError(f"lora_apply: base {list(base.shape)} does not match lora_A {list(a.shape)} / lora_B {list(b.shape)}")
+        for name, t in (("base", base), ("lora_A", a), ("lora_B", b)):
+            if t.dtype not in _DTYPE_CODE:
+                raise ValueError(f"lora_apply: {name} is {t.dtype}; bf16, f16 or f32 expected")
+        fdtype = a.dtype if a.dtype == b.dtype else torch.promote_types(a.dtype, b.dtype)
+        bs = self._dev(base).contiguous()
+        av, bv = self._dev(a, fdtype).contiguous(), self._dev(b, fdtype).contiguous()
+        out = torch.empty_like(bs)
+        self._call(self.lib.dll.smhip_lora_apply(self.ctx.h, bs.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols, av.data_ptr(),
+                                                 bv.data_ptr(), _DTYPE_CODE[fdtype], rank, float(scale), out.data_ptr(),
+                                                 self._stream()))
+        return out
+
     # -- N3: AdditionMerge / TaskAdditionMerge ---------------------------------------------
     def addition_merge(self, finetunes: Sequence[torch.Tensor], base: torch.Tensor, sign_agreement: bool = False) -> torch.Tensor:
         """sum_i (finetune_i - base) in the tensors' dtype, optionally masked by the majority sign

@@ -21,6 +21,8 @@ from typing import Dict, List, Optional, Set
 import torch
 from safetensors import safe_open
 
+from .adapter import ADAPTER_BIN, AdapterError, LoraAdapter, is_adapter_dir, is_bin_only_adapter_dir
+
 logger = logging.getLogger(__name__)
 
 
@@ -63,11 +65,23 @@ class LocalModelIndex:
         self.download_manager = download_manager        # accepted for signature compatibility
         self.model_indexes: Dict[str, Dict] = {}
         self._ordered_weights: Dict[str, List[str]] = {}
+        self.adapters: Dict[str, LoraAdapter] = {}     # LoRA adapter directories (adapter.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
             return
         index_path = self.storage_path / model_uri / "model.safetensors.index.json"
+        if is_adapter_dir(self.storage_path / model_uri):
+            # a LoRA adapter: its factor tensors load through the same weight map as a model's tensors
+            adapter = LoraAdapter(model_uri, self.storage_path / model_uri)
+            self.adapters[model_uri] = adapter
+            self.model_indexes[model_uri] = {"metadata": {}, "weight_map": adapter.weight_map()}
+            self._ordered_weights[model_uri] = sorted(adapter.weight_map())
+            logger.info(f"Model {model_uri}: LoRA adapter, {len(adapter.pairs)} targeted tensors")
+            return
+        if is_bin_only_adapter_dir(self.storage_path / model_uri):
+            raise AdapterError(f"LoRA adapter {model_uri}: only {ADAPTER_BIN} found; adapters are read from "
+                               "adapter_model.safetensors")
         if not index_path.exists():
             raise FileNotFoundError(
                 f"{index_path} not found: this build reads models from storage_dir only (no network download)")
@@ -76,6 +90,10 @@ class LocalModelIndex:
         self.model_indexes[model_uri] = index
         self._ordered_weights[model_uri] = order_weights(list(index["weight_map"].keys()))
         logger.info(f"Model {model_uri}: {len(set(index['weight_map'].values()))} shards, {len(index['weight_map'])} tensors")
+
+    def adapter(self, model_uri: str) -> Optional[LoraAdapter]:
+        """the LoRA adapter registered under this uri, None for a full model"""
+        return self.adapters.get(model_uri)
 
     def _require(self, model_uri: str, tensor_name: Optional[str] = None) -> Dict:
         if model_uri not in self.model_indexes:

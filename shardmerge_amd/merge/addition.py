@@ -24,12 +24,6 @@ class AdditionMerge(MergeTensorsBase):
         super().__init__(*args, **kwargs)
         self._engine = engine
 
-    def engine(self, device):
-        if self._engine is None:
-            from ..engine import get_engine
-            self._engine = get_engine(device)
-        return self._engine
-
     def _loader_device(self, device: str) -> str:
         return str(self.engine(device).device)
 
@@ -39,14 +33,23 @@ class AdditionMerge(MergeTensorsBase):
                 f"This model was created by computing and combining the delta weights\n{self._how}\n")
 
     def _layer_requests(self, shard_layer: ShardLayer):
-        uris = [self.config.output_base_model] + [m.model for m in self.config.finetune_merge]
-        return [(u, shard_layer.layer_name) for u in dict.fromkeys(uris)]
+        name = shard_layer.layer_name
+        reqs = [(self.config.output_base_model, name)]
+        reqs += [r for m in self.config.finetune_merge for r in self._finetune_requests(m, name)]
+        return list(dict.fromkeys(reqs))
 
     async def _merge_layer(self, shard_layer: ShardLayer, device: str = "cuda") -> torch.Tensor:
         eng = self.engine(device)
         dev = str(eng.device)
         name = shard_layer.layer_name
         logger.info(f"Processing layer: {name}")
-        base = await self._fetch(self.config.output_base_model, name, dev)
-        fts = [await self._fetch(m.model, name, dev) for m in self.config.finetune_merge]
+        loaded = {}
+
+        async def fetch(uri, tname=name):
+            if (uri, tname) not in loaded:
+                loaded[(uri, tname)] = await self._fetch(uri, tname, dev)
+            return loaded[(uri, tname)]
+
+        base = await fetch(self.config.output_base_model)
+        fts = [await self.finetune_tensor(m, name, dev, fetch) for m in self.config.finetune_merge]
         return eng.addition_merge(fts, base, sign_agreement=self.sign_agreement)

@@ -38,6 +38,40 @@ class MergeTensorsBase(ABC):
         operators that list them get their inputs prefetched (loader.py), others load on demand."""
         return []
 
+    def engine(self, device):
+        if getattr(self, "_engine", None) is None:
+            from ..engine import get_engine
+            self._engine = get_engine(device)
+        return self._engine
+
+    def _finetune_requests(self, m: MergeModel, layer_name: str) -> List[Tuple[str, str]]:
+        """the (uri, tensor) reads `finetune_tensor` makes for entry m: the model's tensor, or for a LoRA adapter entry
+        its base's tensor and, when the adapter targets it, the two factors"""
+        adapter = self.index_manager.adapter(m.model)
+        if adapter is None:
+            return [(m.model, layer_name)]
+        pair = adapter.pairs.get(layer_name)
+        return [(m.base, layer_name)] + ([(m.model, pair.a_key), (m.model, pair.b_key)] if pair is not None else [])
+
+    async def finetune_tensor(self, m: MergeModel, layer_name: str, device: str, fetch=None) -> torch.Tensor:
+        """THE finetune tensor of entry m - every operator and the partitioned path resolve finetunes here.  A full
+        model's own tensor; for a LoRA adapter entry (adapter.py) base + s * B @ A rounded once into the base's dtype
+        on the engine, or the base tensor itself where the adapter does not target it.
+        fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
+        if fetch is None:
+            async def fetch(uri, tname):
+                return await self._fetch(uri, tname, device)
+        adapter = self.index_manager.adapter(m.model)
+        if adapter is None:
+            return await fetch(m.model, layer_name)
+        base = await fetch(m.base, layer_name)
+        pair = adapter.pairs.get(layer_name)
+        if pair is None:
+            return base
+        a = await fetch(m.model, pair.a_key)
+        b = await fetch(m.model, pair.b_key)
+        return self.engine(device).lora_apply(base, a, b, pair.scale)
+
     async def _fetch(self, model_uri: str, layer_name: str, device: str) -> torch.Tensor:
         if self._loader is not None:
             t = self._loader.take(model_uri, layer_name)
@@ -57,7 +91,7 @@ class MergeTensorsBase(ABC):
         for m in models:
             if m.base not in bases:
                 bases[m.base] = (await self._fetch(m.base, shard_layer.layer_name, device)).to(torch.float32)
-            ft = (await self._fetch(m.model, shard_layer.layer_name, device)).to(torch.float32)
+            ft = (await self.finetune_tensor(m, shard_layer.layer_name, device)).to(torch.float32)
             out.append((ft - bases[m.base]).detach() * (m.alpha if apply_alpha else 1))
         return out
 
@@ -70,7 +104,14 @@ class MergeTensorsBase(ABC):
             await self.index_manager.add_model(m.model)
         base_keys = self.index_manager.get_model_keys(cfg.output_base_model)
         for m in cfg.finetune_merge:
-            keys = self.index_manager.get_model_keys(m.model)
+            adapter = self.index_manager.adapter(m.model)
+            if adapter is not None:
+                # an adapter's finetune has its base's tensors: check the pairs against the base's shard headers
+                if self.index_manager.adapter(m.base) is not None:
+                    raise ValueError(f"{m.model}: the base of a LoRA adapter entry must be a full model, {m.base} is an adapter")
+                from ..adapter import base_tensor_meta
+                adapter.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
+            keys = self.index_manager.get_model_keys(m.base if adapter is not None else m.model)
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)

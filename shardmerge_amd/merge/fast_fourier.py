@@ -49,12 +49,6 @@ class FourierMerge(MergeTensorsBase):
         self._engine = engine
         self.last_report = None
 
-    def engine(self, device):
-        if self._engine is None:
-            from ..engine import get_engine
-            self._engine = get_engine(device)
-        return self._engine
-
     async def initialize(self):
         """reference base.py:139-162, plus a shape pre-flight: every block tensor's transform
         lengths are checked against the HIP library BEFORE any layer is merged (an unsupported
@@ -117,18 +111,21 @@ class FourierMerge(MergeTensorsBase):
         if number in (INPUT_LAYER, OUTPUT_LAYER):
             flag = "is_input" if number == INPUT_LAYER else "is_output"
             src = next((m for m in self.config.finetune_merge if getattr(m, flag)), None)
-            return [(src.model if src is not None else self.config.output_base_model, name)]
+            return self._finetune_requests(src, name) if src is not None else [(self.config.output_base_model, name)]
         models = [m for m in self.config.finetune_merge if m.use_layer_index(number)]
         if not models:
             return []
-        uris = [m.model for m in models] + [m.base for m in models] + [self.config.output_base_model]
-        return [(u, name) for u in dict.fromkeys(uris)]
+        reqs = [r for m in models for r in self._finetune_requests(m, name)]
+        reqs += [(m.base, name) for m in models] + [(self.config.output_base_model, name)]
+        return list(dict.fromkeys(reqs))
 
     async def _passthrough(self, flag: str, shard_layer: ShardLayer, device: str) -> torch.Tensor:
         src = next((m for m in self.config.finetune_merge if getattr(m, flag)), None)
         uri = src.model if src is not None else self.config.output_base_model
         logger.info(f"Passthrough - {shard_layer.layer_name} comes from {uri}")
-        return await self._fetch(uri, shard_layer.layer_name, device)
+        if src is None:
+            return await self._fetch(uri, shard_layer.layer_name, device)
+        return await self.finetune_tensor(src, shard_layer.layer_name, device)
 
     async def _merge_layer(self, shard_layer: ShardLayer, device: str) -> torch.Tensor:
         number = shard_layer.layer_number
@@ -144,15 +141,15 @@ class FourierMerge(MergeTensorsBase):
             # the reference indexes an empty stack here (IndexError); say what is wrong instead
             raise ValueError(f"No finetune covers layer {number} ({shard_layer.layer_name})")
         name = shard_layer.layer_name
-        await asyncio.gather(*(self.index_manager.preload_tensor(m.model, name) for m in models))
+        await asyncio.gather(*(self.index_manager.preload_tensor(u, t) for m in models for u, t in self._finetune_requests(m, name)))
         loaded = {}
 
-        async def fetch(uri):
-            if uri not in loaded:
-                loaded[uri] = await self._fetch(uri, name, dev)
-            return loaded[uri]
+        async def fetch(uri, tname=name):
+            if (uri, tname) not in loaded:
+                loaded[(uri, tname)] = await self._fetch(uri, tname, dev)
+            return loaded[(uri, tname)]
 
-        fts = [await fetch(m.model) for m in models]
+        fts = [await self.finetune_tensor(m, name, dev, fetch) for m in models]
         bases = [await fetch(m.base) for m in models]
         base_out = await fetch(self.config.output_base_model)
         with iostats.timed("merge", 2 * base_out.numel()):       # (the library syncs for its norms: ~ the layer's device time)

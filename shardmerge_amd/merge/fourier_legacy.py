@@ -47,12 +47,6 @@ class LegacyFourierMerge(MergeTensorsBase):
         self.cull_start_pct = cull_start_pct
         self._engine = engine
 
-    def engine(self, device):
-        if self._engine is None:
-            from ..engine import get_engine
-            self._engine = get_engine(device)
-        return self._engine
-
     def _loader_device(self, device: str) -> str:
         return str(self.engine(device).device)
 
@@ -65,9 +59,10 @@ class LegacyFourierMerge(MergeTensorsBase):
         if number in (INPUT_LAYER, OUTPUT_LAYER):
             flag = "is_input" if number == INPUT_LAYER else "is_output"
             src = next((m for m in self.config.finetune_merge if getattr(m, flag)), None)
-            return [(src.model, name)] if src is not None else []
-        uris = [self.config.output_base_model] + [m.model for m in self.config.finetune_merge if m.use_layer_index(number)]
-        return [(u, name) for u in dict.fromkeys(uris)]
+            return self._finetune_requests(src, name) if src is not None else []
+        reqs = [(self.config.output_base_model, name)]
+        reqs += [r for m in self.config.finetune_merge if m.use_layer_index(number) for r in self._finetune_requests(m, name)]
+        return list(dict.fromkeys(reqs))
 
     def _norm(self, eng, t: torch.Tensor) -> float:
         """`torch.norm(t).item()` as the reference's CPU run gets it: ATen's biased fp32 kernel, bit for bit
@@ -109,15 +104,22 @@ class LegacyFourierMerge(MergeTensorsBase):
             if src is None:
                 raise ValueError(f"No {what} model found")
             logger.info(f"Passthrough - {name} is an {what} layer, using {src.model} as {what}")
-            return await self._fetch(src.model, name, device)
+            return await self.finetune_tensor(src, name, device)
 
         eng = self.engine(device)
         dev = str(eng.device)
-        base = await self._fetch(self.config.output_base_model, name, dev)
+        loaded = {}
+
+        async def fetch(uri, tname=name):
+            if (uri, tname) not in loaded:
+                loaded[(uri, tname)] = await self._fetch(uri, tname, dev)
+            return loaded[(uri, tname)]
+
+        base = await fetch(self.config.output_base_model)
         used = [m for m in self.config.finetune_merge if m.use_layer_index(number)]
         layer_stack, add_stack, norms = [], [], []
         for i, m in enumerate(used):
-            ft = await self._fetch(m.model, name, dev)
+            ft = await self.finetune_tensor(m, name, dev, fetch)
             if ft.dtype != base.dtype:
                 raise ValueError(f"{name}: {m.model} is {ft.dtype}, the base {base.dtype} (the legacy operator subtracts in place)")
             delta = eng.addition_merge([ft], base)              # ft - base in the tensors' dtype, one rounding (fourier.py:113)

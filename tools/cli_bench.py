@@ -4,7 +4,10 @@ writes base + K finetunes with Llama-3-8B block shapes under a RAM-backed direct
 runs the CLI's merge with the prefetching loader on and off and prints one JSON line per run
 (wall time includes reading the safetensors shards, H2D, the merge, D2H and writing the output).
 
-    python tools/cli_bench.py [--blocks 4] [--k 2] [--root /dev/shm/smcli] [--device cuda]
+    python tools/cli_bench.py [--blocks 4] [--k 2] [--root /dev/shm/smcli] [--device cuda] [--lora-rank R]
+
+--lora-rank R writes every finetune as a LoRA adapter of rank R instead (adapter_config.json +
+adapter_model.safetensors, every 2-D block projection targeted); input_GB is then what the run reads.
 """
 import argparse
 import asyncio
@@ -33,8 +36,9 @@ BLOCK_70B = [("self_attn.q_proj.weight", 8192, 8192), ("self_attn.k_proj.weight"
 SIGMA = (0.002, 0.003, 0.0025, 0.004)
 
 
-def write_models(root: Path, blocks: int, k: int, gen_device: str, model: str = "llama3-8b"):
+def write_models(root: Path, blocks: int, k: int, gen_device: str, model: str = "llama3-8b", lora_rank: int = 0):
     storage = root / "storage"
+    factors = {i: {} for i in range(1, k + 1)}
     uris = ["org/base"] + [f"org/ft{i}" for i in range(1, k + 1)]
     g = torch.Generator(device=gen_device).manual_seed(1000)
     total = 0
@@ -57,6 +61,14 @@ def write_models(root: Path, blocks: int, k: int, gen_device: str, model: str = 
         for which, uri in enumerate(uris):
             d = storage / uri
             d.mkdir(parents=True, exist_ok=True)
+            if which and lora_rank:
+                for name, t in base.items():
+                    if ".layers." in name and t.ndim == 2:
+                        module = "base_model.model." + name[: -len(".weight")]
+                        sig = (SIGMA[which - 1] / 0.5 / lora_rank ** 0.5) ** 0.5    # s B A ~ SIGMA at s = 0.5
+                        factors[which][f"{module}.lora_A.weight"] = (torch.randn((lora_rank, t.shape[1]), generator=g, device=gen_device) * sig).to(torch.bfloat16).cpu()
+                        factors[which][f"{module}.lora_B.weight"] = (torch.randn((t.shape[0], lora_rank), generator=g, device=gen_device) * sig).to(torch.bfloat16).cpu()
+                continue
             if which == 0:
                 tens = {n: t.cpu() for n, t in base.items()}
             else:
@@ -69,6 +81,12 @@ def write_models(root: Path, blocks: int, k: int, gen_device: str, model: str = 
             json.dump(doc, open(idx_path, "w"))
             if which == 0:
                 total += sum(t.numel() for t in tens.values())
+    for which in factors if lora_rank else ():
+        d = storage / uris[which]
+        save_file(factors[which], str(d / "adapter_model.safetensors"), metadata={"format": "pt"})
+        json.dump({"peft_type": "LORA", "r": lora_rank, "lora_alpha": lora_rank / 2, "bias": "none",
+                   "target_modules": sorted({n.split(".")[-3] for n, _, _ in block if n.endswith("proj.weight")})},
+                  open(d / "adapter_config.json", "w"))
     cfg = {"output_base_model": "org/base",
            "finetune_merge": [{"model": f"org/ft{i}", "base": "org/base", "alpha": (0.3, 0.5, 0.2, 0.4)[i - 1], "is_input": i == 1}
                               for i in range(1, k + 1)],
@@ -89,6 +107,7 @@ def main():
     ap.add_argument("--model", default="llama3-8b", choices=["llama3-8b", "llama3-70b"],
                     help="block shapes; llama3-70b with --k 3 is the metric's configuration (1.7 GB of bf16 per block and model)")
     ap.add_argument("--runs", default="0,1,0,1", help="SHARDMERGE_PREFETCH value of each run")
+    ap.add_argument("--lora-rank", type=int, default=0, help="write the finetunes as LoRA adapters of this rank")
     args = ap.parse_args()
     from shardmerge_amd.constants import tune_hip_queues
     tune_hip_queues()
@@ -97,7 +116,9 @@ def main():
         shutil.rmtree(root)
     root.mkdir(parents=True)
     t0 = time.time()
-    cfg_path, n_params = write_models(root, args.blocks, args.k, args.device if torch.cuda.is_available() else "cpu", args.model)
+    cfg_path, n_params = write_models(root, args.blocks, args.k, args.device if torch.cuda.is_available() else "cpu", args.model,
+                                     args.lora_rank)
+    read_bytes = sum(f.stat().st_size for f in (root / "storage").rglob("*.safetensors"))
     print(f"# wrote {args.k + 1} models, {n_params / 1e6:.0f} M params each, in {time.time() - t0:.1f} s under {root}", file=sys.stderr)
 
     from shardmerge_amd.__main__ import run_merge
@@ -121,8 +142,8 @@ def main():
             torch.cuda.synchronize()
         dt = time.time() - t0
         st = iostats.snapshot(reset=True)
-        in_gb, out_gb = 2.0 * n_params * (args.k + 1) / 1e9, 2.0 * n_params / 1e9
-        rec = {"cli_merge": "end to end", "model": args.model, "prefetch": prefetch == "1", "inplace_shards": inplace, "blocks": args.blocks, "k": args.k,
+        in_gb, out_gb = read_bytes / 1e9, 2.0 * n_params / 1e9
+        rec = {"cli_merge": "end to end", "model": args.model, "lora_rank": args.lora_rank, "prefetch": prefetch == "1", "inplace_shards": inplace, "blocks": args.blocks, "k": args.k,
                "params": n_params, "seconds": round(dt, 3), "merged_GBps": round(out_gb / dt, 3), "input_GB": round(in_gb, 2),
                "stages": st}
         # what the PCIe link allows: every input byte crosses it once, every output byte once, at the H2D rate
