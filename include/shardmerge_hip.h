@@ -34,8 +34,10 @@ enum {
     SMHIP_ERR_INF_MERGED = 4,  /* "Inf in merged tensor for ..."  (fast_fourier.py:273-274) */
     SMHIP_ERR_ARG = 5,
     SMHIP_ERR_NOMEM = 6,
-    SMHIP_ERR_NONFINITE = 7    /* a delta norm is NaN/Inf (K >= 2): the reference's tournament loop
+    SMHIP_ERR_NONFINITE = 7,   /* a delta norm is NaN/Inf (K >= 2): the reference's tournament loop
                                   (fast_fourier.py:171-254) never terminates on such input */
+    SMHIP_ERR_ROW_NORM = 8     /* smhip_adapter_apply, DoRA: a row of base + scale * B @ A has a zero or non-finite
+                                  norm, or its magnitude is not finite (the message names the first such row) */
 };
 
 enum { SMHIP_BF16 = 0, SMHIP_F16 = 1, SMHIP_F32 = 2 };
@@ -190,6 +192,29 @@ int smhip_div_scalar(smhip_ctx* ctx, const void* x, int dtype, size_t n, float s
 int smhip_lora_apply(smhip_ctx* ctx, const void* base, int dtype, int rows, int cols,
                      const void* lora_a, const void* lora_b, int factor_dtype, int rank, float scale,
                      void* out, void* stream);
+
+/* ---- adapters: the finetune weight of a PEFT LoRA / DoRA / embedding-LoRA module, one descriptor.
+ *      LINEAR:    lora_a [rank x cols], lora_b [rows x rank]; out = round(base + scale * (lora_b @ lora_a)), exactly
+ *                 smhip_lora_apply's result when magnitude is NULL.
+ *      EMBEDDING: lora_a = lora_embedding_A [rank x rows], lora_b = lora_embedding_B [cols x rank];
+ *                 out = round(base + scale * (lora_a^T @ lora_b^T)), the same one-rounding contract.
+ *      magnitude (LINEAR only, NULL for plain LoRA): DoRA, [rows] of magnitude_dtype (SMHIP_BF16/F16/F32).  With
+ *                 v = base + scale * (lora_b @ lora_a) as the LoRA path forms it before rounding,
+ *                 out[i][:] = round(v[i][:] * f[i]), f[i] = magnitude[i] / ||v[i][:]||_2 in fp64 (row norm over cols).
+ *                 A row whose f is not finite (zero or non-finite norm, non-finite magnitude) fails the call with
+ *                 SMHIP_ERR_ROW_NORM naming the row; out is then unspecified.  The call synchronises the stream.
+ *      Same argument, alignment and overlap rules as smhip_lora_apply, the magnitude included; DoRA with EMBEDDING is
+ *      SMHIP_ERR_ARG.  Profile names: "lora_pack", "lora_apply"; DoRA: "dora_norm", "dora_scale", "dora_apply". ---- */
+enum { SMHIP_ADAPTER_LINEAR = 0, SMHIP_ADAPTER_EMBEDDING = 1 };
+typedef struct {
+    const void* base; int dtype; int rows, cols;
+    const void* lora_a; const void* lora_b; int factor_dtype; int rank; float scale;
+    int layout;                    /* SMHIP_ADAPTER_LINEAR / SMHIP_ADAPTER_EMBEDDING */
+    const void* magnitude;         /* NULL: plain LoRA; else DoRA (LINEAR only), [rows] of magnitude_dtype */
+    int magnitude_dtype;
+    void* out;
+} smhip_adapter_desc;
+int smhip_adapter_apply(smhip_ctx* ctx, const smhip_adapter_desc* d, void* stream);
 
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of

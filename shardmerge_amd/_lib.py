@@ -16,8 +16,9 @@ from typing import Optional
 MAX_MODELS = 16
 MAX_PAIRS = 32
 
-OK, ERR_HIP, ERR_SHAPE, ERR_INF_IFFT, ERR_INF_MERGED, ERR_ARG, ERR_NOMEM, ERR_NONFINITE = range(8)
+OK, ERR_HIP, ERR_SHAPE, ERR_INF_IFFT, ERR_INF_MERGED, ERR_ARG, ERR_NOMEM, ERR_NONFINITE, ERR_ROW_NORM = range(9)
 BF16, F16, F32 = 0, 1, 2
+ADAPTER_LINEAR, ADAPTER_EMBEDDING = 0, 1
 BRANCH_NAMES = {0: "add", 1: "arith", 2: "slerp", 3: "carry", 4: "early_v0", 5: "linear"}
 
 
@@ -27,6 +28,17 @@ class BlendInfo(C.Structure):
         ("dot", C.c_double), ("s00", C.c_double), ("s01", C.c_double), ("s11", C.c_double),
         ("n_slerp", C.c_uint64),
         ("t", C.c_double), ("cull_pct", C.c_double),
+    ]
+
+
+class AdapterDesc(C.Structure):
+    """smhip_adapter_desc"""
+    _fields_ = [
+        ("base", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
+        ("lora_a", C.c_void_p), ("lora_b", C.c_void_p), ("factor_dtype", C.c_int), ("rank", C.c_int),
+        ("scale", C.c_float), ("layout", C.c_int),
+        ("magnitude", C.c_void_p), ("magnitude_dtype", C.c_int),
+        ("out", C.c_void_p),
     ]
 
 
@@ -104,6 +116,7 @@ class SmhipLibrary:
         d.smhip_exact_norm.argtypes = [P, P, I, C.c_size_t, C.POINTER(D), P]
         d.smhip_div_scalar.argtypes = [P, P, I, C.c_size_t, C.c_float, P, P]
         d.smhip_lora_apply.argtypes = [P, P, I, I, I, P, P, I, I, C.c_float, P, P]
+        d.smhip_adapter_apply.argtypes = [P, C.POINTER(AdapterDesc), P]
         d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

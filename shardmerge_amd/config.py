@@ -22,8 +22,9 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
-base + s * lora_B @ lora_A applied to its own `base` (shardmerge_amd/adapter.py).  Same keys;
-no new option.
+base + s * lora_B @ lora_A applied to its own `base` (shardmerge_amd/adapter.py): embedding LoRA
+factors transposed, DoRA (use_dora) rows rescaled to their magnitude vector.  Same keys; no new
+option.
 """
 from __future__ import annotations
 

@@ -173,6 +173,33 @@ int smhip_lora_apply(smhip_ctx* ctx, const void* base, int dtype, int rows, int 
     SM_FINISH(ctx, ctx->pipe.lora_apply(base, dtype, rows, cols, lora_a, lora_b, factor_dtype, rank, scale, out));
 }
 
+int smhip_adapter_apply(smhip_ctx* ctx, const smhip_adapter_desc* d, void* stream) {
+    SM_GUARD(ctx);
+    if (!d || !d->base || !d->lora_a || !d->lora_b || !d->out || d->rows < 1 || d->cols < 1)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");
+    if (d->dtype < SMHIP_BF16 || d->dtype > SMHIP_F32 || d->factor_dtype < SMHIP_BF16 || d->factor_dtype > SMHIP_F32 ||
+        (d->magnitude && (d->magnitude_dtype < SMHIP_BF16 || d->magnitude_dtype > SMHIP_F32)))
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "bad dtype");
+    if (d->layout != SMHIP_ADAPTER_LINEAR && d->layout != SMHIP_ADAPTER_EMBEDDING)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "adapter_apply: bad layout");
+    if (d->magnitude && d->layout != SMHIP_ADAPTER_LINEAR)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "adapter_apply: DoRA (a magnitude) needs the LINEAR layout");
+    if (d->rank < 1 || d->rank > smhip::LORA_MAX_RANK) return ctx->pipe.fail(SMHIP_ERR_ARG, "rank out of range (1..512)");
+    const size_t bes = d->dtype == SMHIP_F32 ? 4 : 2, fes = d->factor_dtype == SMHIP_F32 ? 4 : 2;
+    const size_t mes = d->magnitude_dtype == SMHIP_F32 ? 4 : 2;
+    const bool emb = d->layout == SMHIP_ADAPTER_EMBEDDING;
+    const uintptr_t o0 = (uintptr_t)d->out, o1 = o0 + (size_t)d->rows * d->cols * bes;
+    auto overlaps = [&](const void* p, size_t bytes) { return (uintptr_t)p < o1 && o0 < (uintptr_t)p + bytes; };
+    if (overlaps(d->base, (size_t)d->rows * d->cols * bes) ||
+        overlaps(d->lora_a, (size_t)d->rank * (emb ? d->rows : d->cols) * fes) ||
+        overlaps(d->lora_b, (size_t)(emb ? d->cols : d->rows) * d->rank * fes) ||
+        (d->magnitude && overlaps(d->magnitude, (size_t)d->rows * mes)))
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "adapter_apply: out overlaps an input");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.adapter_apply(d->base, d->dtype, d->rows, d->cols, d->lora_a, d->lora_b, d->factor_dtype,
+                                           d->rank, d->scale, emb ? 1 : 0, d->magnitude, d->magnitude_dtype, d->out));
+}
+
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
     SM_GUARD(ctx);
     if (!norm_out || (n > 0 && !x)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

@@ -202,6 +202,14 @@ SM_KERNEL_TAG_LB(KLoraPack, LoraPackParams, "lora_pack", k_lora_pack(ex, p), 256
 SM_KERNEL_TAG_LB(KLoraBf16, LoraApplyParams, "lora_apply", k_lora_apply<DT_BF16>(ex, p), 256, 2)
 SM_KERNEL_TAG_LB(KLoraF16, LoraApplyParams, "lora_apply", k_lora_apply<DT_F16>(ex, p), 256, 2)
 SM_KERNEL_TAG_LB(KLoraF32, LoraApplyParams, "lora_apply", k_lora_apply<DT_F32>(ex, p), 256, 2)
+// DoRA (sm_lora.hpp): the row-norm pass, the row factors and the scaled apply pass
+SM_KERNEL_TAG_LB(KDoraNormBf16, LoraApplyParams, "dora_norm", k_dora_norm<DT_BF16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraNormF16, LoraApplyParams, "dora_norm", k_dora_norm<DT_F16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraNormF32, LoraApplyParams, "dora_norm", k_dora_norm<DT_F32>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraScale, DoraScaleParams, "dora_scale", k_dora_scale(ex, p), DORA_SCALE_THREADS, 4)
+SM_KERNEL_TAG_LB(KDoraApplyBf16, LoraApplyParams, "dora_apply", k_dora_apply<DT_BF16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraApplyF16, LoraApplyParams, "dora_apply", k_dora_apply<DT_F16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraApplyF32, LoraApplyParams, "dora_apply", k_dora_apply<DT_F32>(ex, p), 256, 2)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -225,7 +233,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KSpecCheck) X(KSelect3) X(KReduceCand) X(KReduce) X(KSlerpConsts) X(KSumPartials) X(KClassEmf)
 #define SM_SIDE_KERNELS_2(X) X(KDeltaNorms) X(KSumPartialsN) X(KBlend) X(KCombine) X(KExpand) X(KPack) X(KSplit) X(KJoin) \
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
-    X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32)
+    X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
+    X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
 #define SM_SIDE_GROUPS 7         // groups 3 - 6: the run-time planned (DynPlan) transform kernels
 
 // ---- FFT planner ---------------------------------------------------------------
@@ -348,7 +357,7 @@ class Pipeline {
     explicit Pipeline(int device) : be(device) {}
     ~Pipeline() {
         for (auto& kv : plans_) if (kv.second.dev.tw) be.free((void*)kv.second.dev.tw);
-        for (Buffer* b : {&cand_, &t1_, &small_, &tmpA_, &tmpB_, &tmpC_, &fullS_, &saveR_, &saveI_, &aten_, &emf_, &lora_}) if (b->p) be.free(b->p);
+        for (Buffer* b : {&cand_, &t1_, &small_, &tmpA_, &tmpB_, &tmpC_, &fullS_, &saveR_, &saveI_, &aten_, &emf_, &lora_, &dora_}) if (b->p) be.free(b->p);
         for (Buffer& b : pool_) if (b.p) be.free(b.p);
         if (mail_) be.free_host(mail_);
         for (Buffer& b : inter_) if (b.p) be.free(b.p);
@@ -408,7 +417,7 @@ class Pipeline {
         return SMHIP_OK;
     }
     size_t workspace_bytes() const {
-        size_t t = cand_.cap + t1_.cap + small_.cap + tmpA_.cap + tmpB_.cap + tmpC_.cap + fullS_.cap + saveR_.cap + saveI_.cap + aten_.cap + emf_.cap + lora_.cap;
+        size_t t = cand_.cap + t1_.cap + small_.cap + tmpA_.cap + tmpB_.cap + tmpC_.cap + fullS_.cap + saveR_.cap + saveI_.cap + aten_.cap + emf_.cap + lora_.cap + dora_.cap;
         for (const Buffer& b : inter_) t += b.cap;
         for (const Buffer& b : rowspec_) t += b.cap;
         for (const Buffer& b : pool_) t += b.cap;
@@ -2368,8 +2377,14 @@ class Pipeline {
     // ---- LoRA: out = round(base + scale * (b @ a)) (sm_lora.hpp); arguments checked by smhip_lora_apply ----
     int lora_apply(const void* base, int dtype, int rows, int cols, const void* a, const void* b, int fdtype, int rank,
                    float scale, void* out) {
-        const size_t es = fdtype == DT_F32 ? 4 : 2, bes = dtype == DT_F32 ? 4 : 2;
-        if ((uintptr_t)a % es || (uintptr_t)b % es || (uintptr_t)base % bes || (uintptr_t)out % bes)
+        return adapter_apply(base, dtype, rows, cols, a, b, fdtype, rank, scale, 0, nullptr, DT_F32, out);
+    }
+    // ---- adapters (sm_lora.hpp): LoRA, embedding LoRA (trans: a [rank x rows], b [cols x rank]) and DoRA (mag != null,
+    //      [rows] of mdtype); arguments checked by smhip_adapter_apply / smhip_lora_apply ----
+    int adapter_apply(const void* base, int dtype, int rows, int cols, const void* a, const void* b, int fdtype, int rank,
+                      float scale, int trans, const void* mag, int mdtype, void* out) {
+        const size_t es = fdtype == DT_F32 ? 4 : 2, bes = dtype == DT_F32 ? 4 : 2, mes = mdtype == DT_F32 ? 4 : 2;
+        if ((uintptr_t)a % es || (uintptr_t)b % es || (uintptr_t)base % bes || (uintptr_t)out % bes || (uintptr_t)mag % mes)
             return fail(SMHIP_ERR_ARG, "lora_apply: a pointer is not aligned to its element size");
         const int rp = (int)round_up((size_t)rank, LORA_KSTEP);
         const size_t rows_pad = round_up((size_t)rows, LORA_TILE), cols_pad = round_up((size_t)cols, LORA_TILE);
@@ -2382,14 +2397,50 @@ class Pipeline {
         q.a = a; q.b = b; q.bp = lora_.p; q.ap = (char*)lora_.p + rows_pad * (size_t)rp * es;
         q.rows = rows; q.cols = cols; q.rank = rank; q.rp = rp; q.esize = (int)es;
         q.b_tiles = (int)(rows_pad / LORA_PACK_O * (size_t)(rp / LORA_KSTEP));
+        q.trans = trans;
         be.template launch<KLoraPack>((int)pack_tiles, 256, LORA_PACK_O * (LORA_KSTEP + 1) * 4, q, stream);
         LoraApplyParams l;
         l.base = base; l.out = out; l.dtype = dtype; l.ap = q.ap; l.bp = q.bp;
         l.rows = rows; l.cols = cols; l.rp = rp; l.tiles_j = (int)(cols_pad / LORA_TILE); l.scale = scale;
         l.vec = cols % 4 == 0 && (uintptr_t)base % (4 * bes) == 0 && (uintptr_t)out % (4 * bes) == 0;
-        if (fdtype == DT_BF16) be.template launch<KLoraBf16>((int)tiles, 256, 0, l, stream);
-        else if (fdtype == DT_F16) be.template launch<KLoraF16>((int)tiles, 256, 0, l, stream);
-        else be.template launch<KLoraF32>((int)tiles, 256, 0, l, stream);
+        l.part = nullptr; l.fac = nullptr;
+        if (!mag) {
+            if (fdtype == DT_BF16) be.template launch<KLoraBf16>((int)tiles, 256, 0, l, stream);
+            else if (fdtype == DT_F16) be.template launch<KLoraF16>((int)tiles, 256, 0, l, stream);
+            else be.template launch<KLoraF32>((int)tiles, 256, 0, l, stream);
+            return SMHIP_OK;
+        }
+        // DoRA: [tiles_j x rows] partials | [rows] factors | [grid][2] bad-row counts
+        const int sgrid = (rows + DORA_SCALE_THREADS - 1) / DORA_SCALE_THREADS;
+        const size_t part_b = (size_t)l.tiles_j * rows * sizeof(double), fac_b = (size_t)rows * sizeof(double);
+        if ((rc = ensure(dora_, part_b + fac_b + (size_t)sgrid * 2 * sizeof(uint32_t)))) return rc;
+        l.part = (double*)dora_.p;
+        l.fac = (const double*)((char*)dora_.p + part_b);
+        const size_t norm_lds = 4 * 64 * sizeof(double);     // k_dora_norm's row sums per wave
+        if (fdtype == DT_BF16) be.template launch<KDoraNormBf16>((int)tiles, 256, norm_lds, l, stream);
+        else if (fdtype == DT_F16) be.template launch<KDoraNormF16>((int)tiles, 256, norm_lds, l, stream);
+        else be.template launch<KDoraNormF32>((int)tiles, 256, norm_lds, l, stream);
+        DoraScaleParams d;
+        d.part = l.part; d.mag = mag; d.mdtype = mdtype; d.fac = (double*)l.fac;
+        d.bad = (uint32_t*)((char*)dora_.p + part_b + fac_b); d.rows = rows; d.tiles_j = l.tiles_j;
+        be.template launch<KDoraScale>(sgrid, DORA_SCALE_THREADS, DORA_SCALE_THREADS * sizeof(uint32_t), d, stream);
+        if (fdtype == DT_BF16) be.template launch<KDoraApplyBf16>((int)tiles, 256, 0, l, stream);
+        else if (fdtype == DT_F16) be.template launch<KDoraApplyF16>((int)tiles, 256, 0, l, stream);
+        else be.template launch<KDoraApplyF32>((int)tiles, 256, 0, l, stream);
+        // the rows whose factor is not finite: read back after the apply pass (no bubble between the passes)
+        std::vector<uint32_t> h((size_t)sgrid * 2);
+        be.d2h(h.data(), d.bad, h.size() * sizeof(uint32_t), stream);
+        be.sync(stream);
+        size_t nbad = 0;
+        uint32_t first = ~0u;
+        for (int gi = 0; gi < sgrid; ++gi) {
+            nbad += h[2 * gi];
+            if (h[2 * gi] && first == ~0u) first = h[2 * gi + 1];
+        }
+        if (nbad)
+            return fail(SMHIP_ERR_ROW_NORM, "DoRA row " + std::to_string(first) + " has a zero or non-finite norm of " +
+                                                "base + scale * (B @ A), or a non-finite magnitude (" + std::to_string(nbad) +
+                                                " of " + std::to_string(rows) + " rows)");
         return SMHIP_OK;
     }
     int fn_exact_norm(const void* x, int dtype, size_t n, double* norm_out) {
@@ -2535,6 +2586,7 @@ class Pipeline {
     std::map<int, HostPlan> plans_;
     Buffer t1_, small_, tmpA_, tmpB_, tmpC_, fullS_, saveR_, saveI_, cand_, aten_, emf_;
     Buffer lora_;                       // packed LoRA factors (lora_apply)
+    Buffer dora_;                       // DoRA: row partials, row factors, per-work-group bad-row counts (adapter_apply)
     std::vector<Buffer> pool_ = std::vector<Buffer>(4);
     std::vector<char> pool_busy_ = std::vector<char>(4, 1);
     int pidx_[4] = {0, 1, 2, 3};

@@ -252,26 +252,61 @@ class Engine:
         return (self.div_scalar(x, norm) if norm != 0 else self._dev(x, x.dtype if x.dtype in _DTYPE_CODE else torch.float32)), norm
 
     # -- LoRA adapters ---------------------------------------------------------------------
-    def lora_apply(self, base: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float) -> torch.Tensor:
+    def lora_apply(self, base: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float, *,
+                   magnitude: Optional[torch.Tensor] = None, embedding: bool = False) -> torch.Tensor:
         """the finetune weight a LoRA adapter defines: ``base + scale * (b @ a)`` accumulated in fp32 and rounded once
-        into base's dtype (``smhip_lora_apply``).  base [out, in], a = lora_A [r, in], b = lora_B [out, r]."""
+        into base's dtype (``smhip_lora_apply``).  base [out, in], a = lora_A [r, in], b = lora_B [out, r].
+        embedding: a = lora_embedding_A [r, num_embeddings], b = lora_embedding_B [dim, r] of base [num_embeddings,
+        dim], ``base + scale * (a.T @ b.T)``.  magnitude [out] (DoRA, Linear only): each row of that sum scaled by
+        ``magnitude / ||row||`` before the one rounding; a zero or non-finite row norm or magnitude raises SmhipError
+        ERR_ROW_NORM naming the row (``smhip_adapter_apply``)."""
+        if magnitude is None and not embedding:
+            rows, cols, rank, bs, av, bv, fdtype = self._adapter_args(base, a, b, False)
+            out = torch.empty_like(bs)
+            self._call(self.lib.dll.smhip_lora_apply(self.ctx.h, bs.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols,
+                                                     av.data_ptr(), bv.data_ptr(), _DTYPE_CODE[fdtype], rank,
+                                                     float(scale), out.data_ptr(), self._stream()))
+            return out
+        return self.adapter_apply(base, a, b, scale, magnitude=magnitude, embedding=embedding)
+
+    def adapter_apply(self, base: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float, *,
+                      magnitude: Optional[torch.Tensor] = None, embedding: bool = False) -> torch.Tensor:
+        """``lora_apply`` through the descriptor entry point ``smhip_adapter_apply`` (also with neither keyword)"""
+        rows, cols, rank, bs, av, bv, fdtype = self._adapter_args(base, a, b, embedding)
+        mv = None
+        if magnitude is not None:
+            if embedding:
+                raise ValueError("lora_apply: DoRA (a magnitude) applies to Linear modules only, not embeddings")
+            if magnitude.ndim != 1 or magnitude.shape[0] != rows:
+                raise ValueError(f"lora_apply: magnitude {list(magnitude.shape)} does not match base {list(base.shape)}")
+            if magnitude.dtype not in _DTYPE_CODE:
+                raise ValueError(f"lora_apply: magnitude is {magnitude.dtype}; bf16, f16 or f32 expected")
+            mv = self._dev(magnitude).contiguous()
+        out = torch.empty_like(bs)
+        d = _lib.AdapterDesc(bs.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols, av.data_ptr(), bv.data_ptr(),
+                             _DTYPE_CODE[fdtype], rank, float(scale),
+                             _lib.ADAPTER_EMBEDDING if embedding else _lib.ADAPTER_LINEAR,
+                             mv.data_ptr() if mv is not None else None, _DTYPE_CODE[mv.dtype] if mv is not None else _lib.F32,
+                             out.data_ptr())
+        self._call(self.lib.dll.smhip_adapter_apply(self.ctx.h, C.byref(d), self._stream()))
+        return out
+
+    def _adapter_args(self, base, a, b, embedding: bool):
         if base.ndim != 2 or a.ndim != 2 or b.ndim != 2:
             raise ValueError(f"lora_apply: 2-D tensors expected, got base {list(base.shape)}, a {list(a.shape)}, b {list(b.shape)}")
         rows, cols = base.shape
         rank = a.shape[0]
-        if a.shape[1] != cols or b.shape != (rows, rank):
-            raise ValueError(f"lora_apply: base {list(base.shape)} does not match lora_A {list(a.shape)} / lora_B {list(b.shape)}")
+        want_a, want_b = ((rank, rows), (cols, rank)) if embedding else ((rank, cols), (rows, rank))
+        if tuple(a.shape) != want_a or tuple(b.shape) != want_b:
+            what = "lora_embedding_A / lora_embedding_B" if embedding else "lora_A / lora_B"
+            raise ValueError(f"lora_apply: base {list(base.shape)} does not match {what} {list(a.shape)} / {list(b.shape)}")
         for name, t in (("base", base), ("lora_A", a), ("lora_B", b)):
             if t.dtype not in _DTYPE_CODE:
                 raise ValueError(f"lora_apply: {name} is {t.dtype}; bf16, f16 or f32 expected")
         fdtype = a.dtype if a.dtype == b.dtype else torch.promote_types(a.dtype, b.dtype)
         bs = self._dev(base).contiguous()
         av, bv = self._dev(a, fdtype).contiguous(), self._dev(b, fdtype).contiguous()
-        out = torch.empty_like(bs)
-        self._call(self.lib.dll.smhip_lora_apply(self.ctx.h, bs.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols, av.data_ptr(),
-                                                 bv.data_ptr(), _DTYPE_CODE[fdtype], rank, float(scale), out.data_ptr(),
-                                                 self._stream()))
-        return out
+        return rows, cols, rank, bs, av, bv, fdtype
 
     # -- N3: AdditionMerge / TaskAdditionMerge ---------------------------------------------
     def addition_merge(self, finetunes: Sequence[torch.Tensor], base: torch.Tensor, sign_agreement: bool = False) -> torch.Tensor:

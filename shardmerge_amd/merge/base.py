@@ -51,12 +51,16 @@ class MergeTensorsBase(ABC):
         if adapter is None:
             return [(m.model, layer_name)]
         pair = adapter.pairs.get(layer_name)
-        return [(m.base, layer_name)] + ([(m.model, pair.a_key), (m.model, pair.b_key)] if pair is not None else [])
+        if pair is None:
+            return [(m.base, layer_name)]
+        return [(m.base, layer_name), (m.model, pair.a_key), (m.model, pair.b_key)] + \
+            ([(m.model, pair.m_key)] if pair.m_key is not None else [])
 
     async def finetune_tensor(self, m: MergeModel, layer_name: str, device: str, fetch=None) -> torch.Tensor:
         """THE finetune tensor of entry m - every operator and the partitioned path resolve finetunes here.  A full
         model's own tensor; for a LoRA adapter entry (adapter.py) base + s * B @ A rounded once into the base's dtype
-        on the engine, or the base tensor itself where the adapter does not target it.
+        on the engine (embedding factors transposed; DoRA rows scaled to their magnitudes, where a zero or non-finite
+        row norm raises AdapterError), or the base tensor itself where the adapter does not target it.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
@@ -70,7 +74,16 @@ class MergeTensorsBase(ABC):
             return base
         a = await fetch(m.model, pair.a_key)
         b = await fetch(m.model, pair.b_key)
-        return self.engine(device).lora_apply(base, a, b, pair.scale)
+        mag = await fetch(m.model, pair.m_key) if pair.m_key is not None else None
+        from .._lib import ERR_ROW_NORM, SmhipError
+        try:
+            return self.engine(device).lora_apply(base, a, b, pair.scale, magnitude=mag,
+                                                  embedding=pair.kind == "embedding")
+        except SmhipError as e:
+            if e.code != ERR_ROW_NORM:
+                raise
+            from ..adapter import AdapterError
+            raise AdapterError(f"LoRA adapter {m.model}: tensor {layer_name} (DoRA): {e.message}") from e
 
     async def _fetch(self, model_uri: str, layer_name: str, device: str) -> torch.Tensor:
         if self._loader is not None:
