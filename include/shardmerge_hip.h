@@ -35,7 +35,8 @@ enum {
     SMHIP_ERR_ARG = 5,
     SMHIP_ERR_NOMEM = 6,
     SMHIP_ERR_NONFINITE = 7,   /* a delta norm is NaN/Inf (K >= 2): the reference's tournament loop
-                                  (fast_fourier.py:171-254) never terminates on such input */
+                                  (fast_fourier.py:171-254) never terminates on such input; smhip_ties_merge:
+                                  a finetune's delta holds a NaN or an Inf */
     SMHIP_ERR_ROW_NORM = 8     /* smhip_adapter_apply, DoRA: a row of base + scale * B @ A has a zero or non-finite
                                   norm, or its magnitude is not finite (the message names the first such row) */
 };
@@ -167,6 +168,47 @@ int smhip_merge_layer(smhip_ctx* ctx, const smhip_layer_desc* desc, void* out_bf
  *      rounded to the dtype).  The base is NOT added back (the reference does not). ------------ */
 int smhip_addition_merge(smhip_ctx* ctx, int k, const void* const* finetunes, const void* base, int dtype, size_t n,
                          int sign_agreement, void* out, void* stream);
+
+/* ---- TIES merge (Yadav et al., "TIES-Merging", 2023).  The reference has no such operator; this section IS its
+ *      definition.  For one tensor of n elements (any shape, flat), finetunes i = 0..k-1 in order (1 <= k <= 16):
+ *        1. d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with SMHIP_ERR_NONFINITE
+ *           (the message lists the finetunes); out is then unspecified.
+ *        2. k_keep = n if density == 1, else (uint64) floor(density * n) in fp64.  tau_i = the k_keep-th largest |d_i|,
+ *           exact; +inf when k_keep == 0.  An element is KEPT iff |d_i| >= tau_i and d_i != 0.  TIE RULE: every element
+ *           that ties with the threshold is kept (kept[i] may exceed k_keep), so the result does not depend on any
+ *           traversal order - unlike a top-k, which keeps an arbitrary subset of the tied elements.
+ *        3. tv_i = fl32(d_i * fp32(alpha_i)) where kept, 0 elsewhere.
+ *        4. S = ((0 + tv_0) + tv_1) + ... in fp32; the elected sign is +1 if S >= 0, else -1.
+ *        5. m_i = [sign(tv_i) == elected sign] (a zero agrees with nothing); M = sum_i m_i tv_i, D = sum_i m_i fp32(alpha_i),
+ *           fp32, same order, from 0.
+ *        6. normalize: D := 1 where |D| < fp32(1e-8); M := M / D (IEEE fp32 division).
+ *        7. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M)): rounded product, rounded sum,
+ *           one round-to-nearest-even cast.
+ *      Every step is one correctly rounded fp32 operation or an exact order statistic: the result is defined bit for bit.
+ *      The selection is a radix select over the 31 magnitude bits (histogram passes, no sort, 64-bit counts) that forms
+ *      the deltas on the fly; thresholds stay on the device and the call synchronises the stream once, at its end, to
+ *      fetch the report.  Inputs may alias each other; out (and delta_out) must not overlap an input.  n == 0 is a
+ *      no-op.  Pointers need only the alignment of their element type (16-byte aligned ones take the fast path).
+ *      Profile names: "ties_hist", "ties_select", "ties_merge". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double density, lambda; int normalize;
+} smhip_ties_desc;
+typedef struct {
+    uint64_t k_keep;
+    float threshold[SMHIP_MAX_MODELS];      /* tau_i */
+    uint64_t kept[SMHIP_MAX_MODELS];        /* elements of finetune i that were kept (>= k_keep through ties, less
+                                               where the threshold is 0) */
+} smhip_ties_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * M).  report (optional): HOST. */
+int smhip_ties_merge(smhip_ctx* ctx, const smhip_ties_desc* desc, void* out, float* delta_out,
+                     smhip_ties_report* report, void* stream);
 
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector

@@ -19,6 +19,11 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
                                 # device="cpu" output) | exact (accurate norms: the reference's device="cuda" numerics)
       operator: fourier         # fourier (default: what the reference CLI hard-wires, __main__.py:22,67)
                                 # | addition | task_addition (shard/merge/addition.py, taskaddition.py)
+                                # | ties (TIES-Merging, Yadav et al. 2023; no counterpart in the reference)
+      density: 0.2              # operator ties only (and the spectral keys above and norm_mode are rejected with it):
+      ties_lambda: 1.0          #   each delta keeps its `density` largest magnitudes (0 < density <= 1; ties at the
+      ties_normalize: 1         #   threshold all kept), the merged delta is scaled by ties_lambda; ties_normalize = 1
+                                #   divides the sum of the agreeing entries by the sum of their alphas, 0 leaves the sum
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -44,7 +49,10 @@ _REQUIRED = ("output_base_model", "finetune_merge", "output_dir")
 MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.0, "target_norm_offset": 1e-10, "b": 0.1}
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
-OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy")
+OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties")
+# operator ties only: its three options and their defaults
+TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
+TIES_OPTION_RANGES = {"ties_lambda": (-1e6, 1e6)}                  # density: (0, 1]; ties_normalize: 0 or 1
 
 
 @dataclass
@@ -151,6 +159,13 @@ class MergeConfig:
         if operator not in OPERATORS:
             raise click.BadParameter(f"merge_options.operator must be one of {list(OPERATORS)}")
         raw["operator"] = operator
+        if operator == "ties":
+            if task_add:
+                raise click.BadParameter("merge_options.task_add_models is an option of operator fourier_legacy; operator 'ties' would ignore it")
+            raw["merge_options"] = cls._ties_options(opts, norm_mode)
+            return cls(**raw)
+        for key in sorted(set(opts) & set(TIES_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: ties (operator {operator!r} would ignore it)")
         unknown = set(opts) - set(MERGE_OPTION_DEFAULTS)
         if not isinstance(opts, dict) or unknown:
             raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known: {sorted(MERGE_OPTION_DEFAULTS) + ['norm_mode', 'operator']}")
@@ -160,3 +175,27 @@ class MergeConfig:
                 raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
         raw["merge_options"] = {k: float(v) for k, v in opts.items()}
         return cls(**raw)
+
+    @staticmethod
+    def _ties_options(opts: Dict[str, Any], norm_mode: str) -> Dict[str, float]:
+        """merge_options of operator ties: its own three keys only - an option it would ignore is an error that names it"""
+        for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator 'ties' would ignore it")
+        if norm_mode != DEFAULT_NORM_MODE:
+            raise click.BadParameter("merge_options.norm_mode is an option of the spectral operators; operator 'ties' takes no norm")
+        unknown = set(opts) - set(TIES_OPTION_DEFAULTS)
+        if unknown:
+            raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator ties: {sorted(TIES_OPTION_DEFAULTS) + ['operator']}")
+        for key, value in opts.items():
+            number = isinstance(value, (int, float)) and not isinstance(value, bool)
+            if key == "density":
+                if not number or not (0.0 < float(value) <= 1.0):
+                    raise click.BadParameter("merge_options.density must be a number in (0, 1]")
+            elif key == "ties_normalize":
+                if not number or float(value) not in (0.0, 1.0):
+                    raise click.BadParameter("merge_options.ties_normalize must be 0 or 1")
+            else:
+                lo, hi = TIES_OPTION_RANGES[key]
+                if not number or not (lo <= float(value) <= hi):
+                    raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
+        return {k: float(v) for k, v in opts.items()}

@@ -16,6 +16,7 @@
 #include "sm_aten_norm.hpp"
 #include "sm_bluestein.hpp"
 #include "sm_lora.hpp"
+#include "sm_ties.hpp"
 
 namespace smhip {
 
@@ -210,6 +211,10 @@ SM_KERNEL_TAG_LB(KDoraScale, DoraScaleParams, "dora_scale", k_dora_scale(ex, p),
 SM_KERNEL_TAG_LB(KDoraApplyBf16, LoraApplyParams, "dora_apply", k_dora_apply<DT_BF16>(ex, p), 256, 2)
 SM_KERNEL_TAG_LB(KDoraApplyF16, LoraApplyParams, "dora_apply", k_dora_apply<DT_F16>(ex, p), 256, 2)
 SM_KERNEL_TAG_LB(KDoraApplyF32, LoraApplyParams, "dora_apply", k_dora_apply<DT_F32>(ex, p), 256, 2)
+// TIES merge (sm_ties.hpp): one radix level of the magnitude selection, its scan, and the fused merge pass
+SM_KERNEL_TAG_LB(KTiesHist, TiesHistParams, "ties_hist", k_ties_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KTiesSelect, TiesSelectParams, "ties_select", k_ties_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KTiesMerge, TiesMergeParams, "ties_merge", k_ties_merge(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -235,7 +240,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
-#define SM_SIDE_GROUPS 7         // groups 3 - 6: the run-time planned (DynPlan) transform kernels
+#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -357,7 +363,7 @@ class Pipeline {
     explicit Pipeline(int device) : be(device) {}
     ~Pipeline() {
         for (auto& kv : plans_) if (kv.second.dev.tw) be.free((void*)kv.second.dev.tw);
-        for (Buffer* b : {&cand_, &t1_, &small_, &tmpA_, &tmpB_, &tmpC_, &fullS_, &saveR_, &saveI_, &aten_, &emf_, &lora_, &dora_}) if (b->p) be.free(b->p);
+        for (Buffer* b : {&cand_, &t1_, &small_, &tmpA_, &tmpB_, &tmpC_, &fullS_, &saveR_, &saveI_, &aten_, &emf_, &lora_, &dora_, &ties_}) if (b->p) be.free(b->p);
         for (Buffer& b : pool_) if (b.p) be.free(b.p);
         if (mail_) be.free_host(mail_);
         for (Buffer& b : inter_) if (b.p) be.free(b.p);
@@ -417,7 +423,7 @@ class Pipeline {
         return SMHIP_OK;
     }
     size_t workspace_bytes() const {
-        size_t t = cand_.cap + t1_.cap + small_.cap + tmpA_.cap + tmpB_.cap + tmpC_.cap + fullS_.cap + saveR_.cap + saveI_.cap + aten_.cap + emf_.cap + lora_.cap + dora_.cap;
+        size_t t = cand_.cap + t1_.cap + small_.cap + tmpA_.cap + tmpB_.cap + tmpC_.cap + fullS_.cap + saveR_.cap + saveI_.cap + aten_.cap + emf_.cap + lora_.cap + dora_.cap + ties_.cap;
         for (const Buffer& b : inter_) t += b.cap;
         for (const Buffer& b : rowspec_) t += b.cap;
         for (const Buffer& b : pool_) t += b.cap;
@@ -2336,6 +2342,84 @@ class Pipeline {
         return SMHIP_OK;
     }
 
+    // ---- TIES merge (sm_ties.hpp; the function is stated in shardmerge_hip.h); arguments checked by smhip_ties_merge ----
+    // workspace: the three levels' histograms [3][k][HIST1_BINS] | TiesState[k] | TiesReadback
+    struct TiesReadback { float threshold[TIES_MAX_MODELS]; unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
+    int ties_merge(const smhip_ties_desc& d, void* out, float* delta_out, smhip_ties_report* rep) {
+        const int k = d.k;
+        const size_t n = d.n;
+        const unsigned long long k_keep = d.density == 1.0 ? (unsigned long long)n : (unsigned long long)std::floor(d.density * (double)n);
+        if (rep) {
+            rep->k_keep = k_keep;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) { rep->threshold[i] = 0.f; rep->kept[i] = 0; }
+        }
+        if (n == 0) {                                    // k_keep == 0: the threshold is +inf by definition
+            if (rep) for (int i = 0; i < k; ++i) rep->threshold[i] = INFINITY;
+            return SMHIP_OK;
+        }
+        const size_t hist_level = (size_t)TIES_MAX_MODELS * HIST1_BINS * sizeof(unsigned long long);
+        const size_t off_state = 3 * hist_level, off_rb = off_state + TIES_MAX_MODELS * sizeof(TiesState);
+        const size_t ws = off_rb + sizeof(TiesReadback);
+        int rc;
+        if ((rc = ensure(ties_, ws))) return rc;
+        be.memset(ties_.p, 0, ws, stream);
+        TiesState* state = (TiesState*)((char*)ties_.p + off_state);
+        TiesReadback* rb = (TiesReadback*)((char*)ties_.p + off_rb);
+
+        TiesInputs in;
+        in.k = k; in.dtype = d.in_dtype; in.n = n;
+        bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) {
+            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
+            al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
+            shared = shared && in.base[i] == in.base[0];
+        }
+        in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
+        const size_t noct = (n + 7) / 8;
+
+        TiesHistParams h;
+        h.in = in; h.state = state; h.flags = rb->flags;
+        h.chunks = pick_chunks(noct, 256, 4, 5);
+        const int hgrid = stream_grid(noct, 256, h.chunks);
+        TiesSelectParams s;
+        s.k_keep = k_keep; s.state = state; s.threshold = rb->threshold; s.kept = rb->kept;
+        for (int level = 1; level <= 3; ++level) {
+            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * hist_level);
+            h.level = level; h.hist = hist;
+            const int nbins = level == 1 ? HIST1_BINS : HIST_LO_BINS;
+            // (k_keep == 0: the threshold is +inf whatever the data; level 1 still runs, it finds the non-finite deltas)
+            for (int first = 0; first < k && (level == 1 || k_keep > 0); first += TIES_GROUP) {
+                h.first = first; h.count = std::min(TIES_GROUP, k - first);
+                be.template launch<KTiesHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * nbins) * 4, h, stream);
+            }
+            s.level = level; s.hist = hist;
+            be.template launch<KTiesSelect>(k, TIES_SELECT_THREADS, LDS_SCRATCH_FLOATS * 4 + TIES_SELECT_THREADS * sizeof(unsigned long long), s, stream);
+        }
+
+        TiesMergeParams m;
+        m.in = in;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < k ? i : 0];
+        m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
+        m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
+        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0;
+        m.threshold = rb->threshold; m.out = out; m.delta_out = delta_out;
+        m.chunks = pick_chunks(noct, 256, 2, 8);
+        be.template launch<KTiesMerge>(stream_grid(noct, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+
+        TiesReadback host;
+        be.d2h(&host, rb, sizeof host, stream);          // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP)
+        if (host.flags[0]) {
+            std::string which;
+            for (int i = 0; i < k; ++i)
+                if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
+            return fail(SMHIP_ERR_NONFINITE, "ties_merge: NaN or Inf in finetune - base of finetune " + which);
+        }
+        if (rep)
+            for (int i = 0; i < k; ++i) { rep->threshold[i] = host.threshold[i]; rep->kept[i] = host.kept[i]; }
+        return SMHIP_OK;
+    }
+
     // ---- function level: slerp (functions.py:24-43), tensor / scalar and the exact norm (functions.py:75-88) ----
     int fn_slerp(const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out) {
         const size_t n = rows * cols;
@@ -2586,6 +2670,7 @@ class Pipeline {
     std::map<int, HostPlan> plans_;
     Buffer t1_, small_, tmpA_, tmpB_, tmpC_, fullS_, saveR_, saveI_, cand_, aten_, emf_;
     Buffer lora_;                       // packed LoRA factors (lora_apply)
+    Buffer ties_;                       // TIES: selection histograms, states and the report (ties_merge)
     Buffer dora_;                       // DoRA: row partials, row factors, per-work-group bad-row counts (adapter_apply)
     std::vector<Buffer> pool_ = std::vector<Buffer>(4);
     std::vector<char> pool_busy_ = std::vector<char>(4, 1);

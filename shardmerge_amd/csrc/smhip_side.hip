@@ -1,5 +1,5 @@
 // smhip_side.hip - explicit instantiation of one group of kernels, selected with -DSM_SIDE_GROUP=<g>
-// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths).
+// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: TIES).
 #include "smhip_device.hpp"
 
 namespace smhip {
@@ -18,7 +18,9 @@ SM_INST(KF2<DynPlan>) SM_INST(KF2Q<DynPlan>) SM_INST(KF2S<DynPlan>) SM_INST(KF2S
 SM_INST(KI1x1<DynPlan>) SM_INST(KI1x2<DynPlan>) SM_INST(KI1x1Q<DynPlan>) SM_INST(KI1x2Q<DynPlan>)
 #elif SM_SIDE_GROUP == 6
 SM_INST(KF1B<DynPlan>) SM_INST(KI2B<DynPlan>)
+#elif SM_SIDE_GROUP == 7
+SM_SIDE_KERNELS_7(SM_INST)
 #else
-#error "SM_SIDE_GROUP must be 0..6"
+#error "SM_SIDE_GROUP must be 0..7"
 #endif
 }  // namespace smhip

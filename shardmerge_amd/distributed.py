@@ -394,7 +394,7 @@ async def run_partitioned_merge(config: MergeConfig, index: LocalModelIndex, dev
                 cost = 0.02 + 2.0 * numel * (1 if fourier else len(config.finetune_merge) + 2) / 4.0e9   # a copy / one streaming pass
             else:
                 k = sum(1 for m in config.finetune_merge if m.use_layer_index(number))
-                cost = est_ms(shape, k)
+                cost = merger.block_cost_ms(shape, k) if hasattr(merger, "block_cost_ms") else est_ms(shape, k)
             names.append((s, name))
             costs.append(cost)
             groups.append(si)
@@ -613,9 +613,6 @@ async def _merge_block_tensor(merger: FourierMerge, engine, sl: ShardLayer, base
 
     fts = [await merger.finetune_tensor(m, sl.layer_name, dev, fetch) for m in models]
     bases = [await fetch(m.base) for m in models]
-    out, report = engine.merge_layer(fts, bases, [m.alpha for m in models], base_view,
-                                     target_norm_offset=merger.target_norm_offset, cull_start_pct=merger.cull_start_pct,
-                                     cutoff_pct=merger.cutoff_pct, t_sum=merger.t_sum, b=merger.b, norm_mode=merger.norm_mode,
-                                     layer_name=sl.layer_name)
+    out, report = merger.merge_block(engine, fts, bases, [m.alpha for m in models], base_view, sl.layer_name)
     merger.last_report = report
     return out

@@ -57,6 +57,13 @@ class BlendReport:
 
 
 @dataclass
+class TiesMergeReport:
+    k_keep: int = 0                                                  # elements each finetune was trimmed to
+    thresholds: List[float] = field(default_factory=list)            # tau_i: the k_keep-th largest |finetune_i - base_i|
+    kept: List[int] = field(default_factory=list)                    # elements kept (ties at tau_i included, zeros never)
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -329,6 +336,71 @@ class Engine:
         self._call(self.lib.dll.smhip_addition_merge(self.ctx.h, k, ptrs, bs.data_ptr(), _DTYPE_CODE[dtype], bs.numel(),
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
+
+    # -- TIES ------------------------------------------------------------------------------
+    def ties_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                   base_out: torch.Tensor, density: float = 0.2, lam: float = 1.0, normalize: bool = True,
+                   want_delta: bool = False, layer_name: str = "layer"):
+        """TIES merge of one tensor of any shape (``smhip_ties_merge``; the function is stated in
+        include/shardmerge_hip.h): each delta ``finetune_i - base_i`` trimmed to its ``density`` largest magnitudes
+        (ties at the threshold all kept), weighted by ``alpha_i``, a sign elected per element by the weighted sum, the
+        agreeing entries summed (``normalize``: divided by the sum of their weights), times ``lam``, added onto
+        ``base_out`` in its dtype.  Returns (out, TiesMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta
+        raises ValueError naming ``layer_name`` and the finetune."""
+        k = len(finetunes)
+        if k < 1 or k > _lib.MAX_MODELS:
+            raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
+        if len(bases) != k or len(alphas) != k:
+            raise ValueError(f"ties_merge: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
+        if not (0.0 < float(density) <= 1.0):
+            raise ValueError(f"ties_merge: density {density} is not in (0, 1]")
+        # one input dtype per call, mixed dtypes promoted to fp32 (as merge_layer does it)
+        dtypes = {t.dtype for t in list(finetunes) + list(bases)}
+        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
+        if in_dtype not in _DTYPE_CODE:
+            in_dtype = torch.float32
+        keep = []
+        desc = _lib.TiesDesc()
+        desc.k = k
+        seen: Dict[int, torch.Tensor] = {}
+        for i in range(k):
+            ft = self._dev(finetunes[i], in_dtype)
+            bkey = id(bases[i])
+            if bkey not in seen:
+                seen[bkey] = self._dev(bases[i], in_dtype)
+            bs = seen[bkey]
+            if ft.shape != base_out.shape or bs.shape != base_out.shape:
+                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
+            keep += [ft, bs]
+            desc.finetune[i] = ft.data_ptr()
+            desc.base[i] = bs.data_ptr()
+            desc.alpha[i] = float(alphas[i])
+        bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
+        bo = seen.get(id(base_out))
+        if bo is None or bo.dtype != bo_dtype:
+            bo = self._dev(base_out, bo_dtype)
+        keep.append(bo)
+        desc.in_dtype = _DTYPE_CODE[in_dtype]
+        desc.base_out = bo.data_ptr()
+        desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
+        desc.n = bo.numel()
+        desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
+        out = torch.empty(bo.shape, dtype=bo_dtype, device=self.device)
+        delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
+        rep = _lib.TiesReport()
+        try:
+            self.ctx.check(self.lib.dll.smhip_ties_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
+                                                         delta.data_ptr() if delta is not None else None,
+                                                         C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
+            raise
+        report = TiesMergeReport(k_keep=int(rep.k_keep), thresholds=[float(rep.threshold[i]) for i in range(k)],
+                                 kept=[int(rep.kept[i]) for i in range(k)])
+        if want_delta:
+            return out, report, delta
+        return out, report
 
     def correlate_pairs(self, tensors) -> torch.Tensor:
         """K x K matrix of mean column-wise cosine similarities (reference functions.py:304-314);

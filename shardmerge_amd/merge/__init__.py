@@ -15,4 +15,7 @@ def operator_class(name: str = "fourier"):
     if name == "fourier_legacy":
         from .fourier_legacy import LegacyFourierMerge
         return LegacyFourierMerge
+    if name == "ties":
+        from .ties import TiesMerge
+        return TiesMerge
     raise ValueError(f"unknown merge operator {name!r}")

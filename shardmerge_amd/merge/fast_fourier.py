@@ -153,10 +153,19 @@ class FourierMerge(MergeTensorsBase):
         bases = [await fetch(m.base) for m in models]
         base_out = await fetch(self.config.output_base_model)
         with iostats.timed("merge", 2 * base_out.numel()):       # (the library syncs for its norms: ~ the layer's device time)
-            out, report = eng.merge_layer(
-                fts, bases, [m.alpha for m in models], base_out,
-                target_norm_offset=self.target_norm_offset, cull_start_pct=self.cull_start_pct,
-                cutoff_pct=self.cutoff_pct, t_sum=self.t_sum, b=self.b, norm_mode=self.norm_mode, layer_name=name)
+            out, report = self.merge_block(eng, fts, bases, [m.alpha for m in models], base_out, name)
         self.last_report = report
-        logger.info(f"Merged {name}: {len(models)} model(s), branches {report.branches}, target norm {report.target_norm:.6g}")
+        self._log_block(name, len(models), report)
         return out
+
+    def merge_block(self, eng, fts, bases, alphas, base_out, name: str):
+        """(finetunes, their bases, alphas, output_base_model's tensor, layer name) -> (output tensor, report): THE
+        block-tensor merge of this operator.  _merge_layer above and the partitioned path (distributed.py,
+        _merge_block_tensor) both go through it; a subclass with another merge rule overrides it."""
+        return eng.merge_layer(
+            fts, bases, alphas, base_out,
+            target_norm_offset=self.target_norm_offset, cull_start_pct=self.cull_start_pct,
+            cutoff_pct=self.cutoff_pct, t_sum=self.t_sum, b=self.b, norm_mode=self.norm_mode, layer_name=name)
+
+    def _log_block(self, name: str, k: int, report):
+        logger.info(f"Merged {name}: {k} model(s), branches {report.branches}, target norm {report.target_norm:.6g}")
