@@ -35,8 +35,8 @@ enum {
     SMHIP_ERR_ARG = 5,
     SMHIP_ERR_NOMEM = 6,
     SMHIP_ERR_NONFINITE = 7,   /* a delta norm is NaN/Inf (K >= 2): the reference's tournament loop
-                                  (fast_fourier.py:171-254) never terminates on such input; smhip_ties_merge:
-                                  a finetune's delta holds a NaN or an Inf */
+                                  (fast_fourier.py:171-254) never terminates on such input; smhip_ties_merge,
+                                  smhip_dare_merge: a finetune's delta holds a NaN or an Inf */
     SMHIP_ERR_ROW_NORM = 8     /* smhip_adapter_apply, DoRA: a row of base + scale * B @ A has a zero or non-finite
                                   norm, or its magnitude is not finite (the message names the first such row) */
 };
@@ -209,6 +209,57 @@ typedef struct {
 /* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * M).  report (optional): HOST. */
 int smhip_ties_merge(smhip_ctx* ctx, const smhip_ties_desc* desc, void* out, float* delta_out,
                      smhip_ties_report* report, void* stream);
+
+/* ---- DARE merge (Yu et al., "Language Models are Super Mario", 2023): drop each delta entry at random with
+ *      probability 1 - density, rescale the survivors by 1 / density, then add the weighted deltas (dare_linear) or
+ *      elect a sign and merge the agreeing entries as TIES does (dare_ties).  The reference has no such operator; this
+ *      section IS its definition.  The random mask is a FUNCTION of (key, stream id, element index) - a counter-based
+ *      generator, no stream and no state - so the same call gives the same bytes whatever the grid, the traversal
+ *      order or the number of processes.  For one tensor of n elements (any shape, flat), finetunes i = 0..k-1 in
+ *      order (1 <= k <= 16):
+ *        1. d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with SMHIP_ERR_NONFINITE
+ *           (the message lists the finetunes); out is then unspecified.
+ *        2. T = 65536 if density == 1, else (uint32) floor(density * 65536) in fp64.  T == 0 (density < 2^-16) is
+ *           SMHIP_ERR_ARG.  The EFFECTIVE density is q = T / 65536: it is what the report carries and what the rescale
+ *           uses, so the expectation is unbiased for the mask actually drawn.
+ *        3. Mask.  For element index j (flat, 64-bit) of finetune i:
+ *             blk = Philox4x32-10(counter = (lo32(j >> 3), hi32(j >> 3), stream_id[i], 0), key = (lo32(key), hi32(key)))
+ *           (Salmon et al. 2011: multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten
+ *           rounds); w = blk[(j & 7) >> 1]; h = (j & 1) ? w >> 16 : w & 0xffff.  The element is KEPT iff h < T and
+ *           d_i != 0.  One block decides one octet of eight consecutive elements; the mask is monotone in T.
+ *        4. r = 1 if rescale == 0, else fp32(65536.0 / T) (fp64 division, one rounding).
+ *           tv_i = fl32(fl32(d_i * r) * fp32(alpha_i)) where kept, +0 elsewhere.
+ *        5. sign_election == 1 (dare_ties): steps 4-6 of smhip_ties_merge on these tv_i (S, the elected sign, M and D
+ *           over the agreeing entries, |D| < 1e-8 -> 1, M / D when normalize).
+ *           sign_election == 0 (dare_linear): M = ((0 + tv_0) + tv_1) + ... in fp32; D = ((0 + fp32(alpha_0)) + ...)
+ *           over ALL finetunes, kept or not; the same |D| < 1e-8 -> 1 and division when normalize.
+ *        6. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M)), delta_out = fl32(lambda * M):
+ *           step 7 of smhip_ties_merge.
+ *      Every step is an integer function or one correctly rounded fp32 operation: the result is defined bit for bit.
+ *      With density = 1 and sign_election = 1 the result equals smhip_ties_merge at density 1 for any key.  ONE kernel,
+ *      one pass over the inputs; the call synchronises the stream once, at its end, to fetch the report.  Aliasing,
+ *      alignment and n == 0: the rules of smhip_ties_merge.  Profile name: "dare_merge". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double density, lambda; int normalize;
+    uint64_t key;                           /* the generator's key: the same for every finetune of the tensor */
+    uint32_t stream_id[SMHIP_MAX_MODELS];   /* word 2 of finetune i's counter: what tells the finetunes' masks apart */
+    int rescale;                            /* 1: survivors times fp32(65536 / T); 0: left as they are */
+    int sign_election;                      /* 1: dare_ties; 0: dare_linear */
+} smhip_dare_desc;
+typedef struct {
+    uint32_t T;                             /* the keep threshold on the 16-bit draw; effective density T / 65536 */
+    uint64_t kept[SMHIP_MAX_MODELS];        /* elements of finetune i that were kept */
+} smhip_dare_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * M).  report (optional): HOST. */
+int smhip_dare_merge(smhip_ctx* ctx, const smhip_dare_desc* desc, void* out, float* delta_out,
+                     smhip_dare_report* report, void* stream);
 
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector

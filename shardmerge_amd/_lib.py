@@ -81,6 +81,28 @@ class TiesReport(C.Structure):
     _fields_ = [("k_keep", C.c_uint64), ("threshold", C.c_float * MAX_MODELS), ("kept", C.c_uint64 * MAX_MODELS)]
 
 
+class DareDesc(C.Structure):
+    """smhip_dare_desc"""
+    _fields_ = [
+        ("k", C.c_int),
+        ("finetune", C.c_void_p * MAX_MODELS),
+        ("base", C.c_void_p * MAX_MODELS),
+        ("alpha", C.c_double * MAX_MODELS),
+        ("in_dtype", C.c_int),
+        ("base_out", C.c_void_p), ("base_out_dtype", C.c_int),
+        ("n", C.c_size_t),
+        ("density", C.c_double), ("lam", C.c_double), ("normalize", C.c_int),
+        ("key", C.c_uint64),
+        ("stream_id", C.c_uint32 * MAX_MODELS),
+        ("rescale", C.c_int), ("sign_election", C.c_int),
+    ]
+
+
+class DareReport(C.Structure):
+    """smhip_dare_report"""
+    _fields_ = [("T", C.c_uint32), ("kept", C.c_uint64 * MAX_MODELS)]
+
+
 class LayerReport(C.Structure):
     _fields_ = [
         ("target_norm", C.c_double),
@@ -130,6 +152,7 @@ class SmhipLibrary:
         d.smhip_merge_layer.argtypes = [P, C.POINTER(LayerDesc), P, P, C.POINTER(LayerReport), P]
         d.smhip_addition_merge.argtypes = [P, I, C.POINTER(C.c_void_p), P, I, C.c_size_t, I, P, P]
         d.smhip_ties_merge.argtypes = [P, C.POINTER(TiesDesc), P, P, C.POINTER(TiesReport), P]
+        d.smhip_dare_merge.argtypes = [P, C.POINTER(DareDesc), P, P, C.POINTER(DareReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

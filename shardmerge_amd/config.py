@@ -24,6 +24,18 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       ties_lambda: 1.0          #   each delta keeps its `density` largest magnitudes (0 < density <= 1; ties at the
       ties_normalize: 1         #   threshold all kept), the merged delta is scaled by ties_lambda; ties_normalize = 1
                                 #   divides the sum of the agreeing entries by the sum of their alphas, 0 leaves the sum
+                                # | dare_ties | dare_linear (DARE, Yu et al. 2023; no counterpart in the reference): each
+                                #   delta entry is dropped at random with probability 1 - density, the survivors rescaled
+                                #   by 1 / density, then merged as ties merges (dare_ties) or added (dare_linear).  Keys,
+                                #   these operators only (the spectral keys, norm_mode and the ties_* keys are rejected):
+      # density: 0.2            #   2^-16 <= density <= 1; the mask draws 16 bits per element, so the density in effect
+                                #   is floor(density * 65536) / 65536 (the README of the output states it)
+      # dare_lambda: 1.0        #   scales the merged delta
+      # dare_normalize: 1       #   1: divide by the sum of the weights (dare_ties: of the agreeing entries), 0: plain sum
+      # dare_rescale: 1         #   1: survivors times 1 / effective density, 0: left as they are
+      # seed: 0                 #   an integer in [0, 2^63): with the tensor's name it keys the mask, which is a function
+                                #   of (seed, tensor name, position of the entry in finetune_merge, element index) - the
+                                #   same config gives the same bytes in one process, in place and on any number of ranks
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -36,7 +48,7 @@ from __future__ import annotations
 import dataclasses
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Union
 
 import click
 import torch
@@ -49,10 +61,15 @@ _REQUIRED = ("output_base_model", "finetune_merge", "output_dir")
 MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.0, "target_norm_offset": 1e-10, "b": 0.1}
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
-OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties")
+OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear")
 # operator ties only: its three options and their defaults
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
 TIES_OPTION_RANGES = {"ties_lambda": (-1e6, 1e6)}                  # density: (0, 1]; ties_normalize: 0 or 1
+# operators dare_ties / dare_linear only: their options and defaults (seed stays an int: it must survive exactly)
+DARE_OPERATORS = ("dare_ties", "dare_linear")
+DARE_OPTION_DEFAULTS = {"density": 0.2, "dare_lambda": 1.0, "dare_normalize": 1.0, "dare_rescale": 1.0, "seed": 0}
+DARE_OPTION_RANGES = {"dare_lambda": (-1e6, 1e6)}   # density: [2^-16, 1]; dare_normalize, dare_rescale: 0 or 1; seed: [0, 2^63)
+DARE_MIN_DENSITY = 2.0 ** -16                       # the mask draws 16 bits per element
 
 
 @dataclass
@@ -83,7 +100,7 @@ class MergeConfig:
     clean_cache: bool = False
     cache_dir: str = "cache"
     storage_dir: str = "storage"
-    merge_options: Dict[str, float] = field(default_factory=dict)
+    merge_options: Dict[str, Union[int, float]] = field(default_factory=dict)    # (an int: seed of the DARE operators)
     operator: str = "fourier"
     norm_mode: str = DEFAULT_NORM_MODE
     task_add_models: List[str] = field(default_factory=list)      # operator fourier_legacy only (reference fourier.py:39,115)
@@ -159,13 +176,20 @@ class MergeConfig:
         if operator not in OPERATORS:
             raise click.BadParameter(f"merge_options.operator must be one of {list(OPERATORS)}")
         raw["operator"] = operator
+        if operator in DARE_OPERATORS:
+            if task_add:
+                raise click.BadParameter(f"merge_options.task_add_models is an option of operator fourier_legacy; operator {operator!r} would ignore it")
+            raw["merge_options"] = cls._dare_options(opts, norm_mode, operator)
+            return cls(**raw)
+        for key in sorted((set(opts) & set(DARE_OPTION_DEFAULTS)) - set(TIES_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: dare_ties or dare_linear (operator {operator!r} would ignore it)")
         if operator == "ties":
             if task_add:
                 raise click.BadParameter("merge_options.task_add_models is an option of operator fourier_legacy; operator 'ties' would ignore it")
             raw["merge_options"] = cls._ties_options(opts, norm_mode)
             return cls(**raw)
         for key in sorted(set(opts) & set(TIES_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: ties (operator {operator!r} would ignore it)")
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: ties, dare_ties or dare_linear (operator {operator!r} would ignore it)")
         unknown = set(opts) - set(MERGE_OPTION_DEFAULTS)
         if not isinstance(opts, dict) or unknown:
             raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known: {sorted(MERGE_OPTION_DEFAULTS) + ['norm_mode', 'operator']}")
@@ -199,3 +223,37 @@ class MergeConfig:
                 if not number or not (lo <= float(value) <= hi):
                     raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
         return {k: float(v) for k, v in opts.items()}
+
+    @staticmethod
+    def _dare_options(opts: Dict[str, Any], norm_mode: str, operator: str) -> Dict[str, Union[int, float]]:
+        """merge_options of dare_ties / dare_linear: their own keys only - an option they would ignore is an error that names it"""
+        for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator {operator!r} would ignore it")
+        if norm_mode != DEFAULT_NORM_MODE:
+            raise click.BadParameter(f"merge_options.norm_mode is an option of the spectral operators; operator {operator!r} takes no norm")
+        for key in sorted((set(opts) & set(TIES_OPTION_DEFAULTS)) - set(DARE_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is an option of operator ties; operator {operator!r} would ignore it (its keys: dare_lambda, dare_normalize)")
+        unknown = set(opts) - set(DARE_OPTION_DEFAULTS)
+        if unknown:
+            raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator {operator}: {sorted(DARE_OPTION_DEFAULTS) + ['operator']}")
+        out: Dict[str, Union[int, float]] = {}
+        for key, value in opts.items():
+            number = isinstance(value, (int, float)) and not isinstance(value, bool)
+            if key == "seed":
+                if not isinstance(value, int) or isinstance(value, bool) or not (0 <= value < 2 ** 63):
+                    raise click.BadParameter("merge_options.seed must be an integer in [0, 2^63)")
+                out[key] = int(value)
+                continue
+            if key == "density":
+                if not number or not (DARE_MIN_DENSITY <= float(value) <= 1.0):
+                    raise click.BadParameter(f"merge_options.density must be a number in [2^-16 = {DARE_MIN_DENSITY}, 1] with operator {operator} "
+                                             "(the mask draws 16 bits per element)")
+            elif key in ("dare_normalize", "dare_rescale"):
+                if not number or float(value) not in (0.0, 1.0):
+                    raise click.BadParameter(f"merge_options.{key} must be 0 or 1")
+            else:
+                lo, hi = DARE_OPTION_RANGES[key]
+                if not number or not (lo <= float(value) <= hi):
+                    raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
+            out[key] = float(value)
+        return out

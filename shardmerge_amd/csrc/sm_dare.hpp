@@ -1,0 +1,179 @@
+// sm_dare.hpp - DARE merge (Yu et al. 2023: drop each delta entry at random, rescale the survivors, then add the
+// weighted deltas or elect a sign as TIES does), an operator the reference does not have.  The function is stated in
+// include/shardmerge_hip.h (smhip_dare_merge).  The drop mask is a FUNCTION of (key, stream id, element index): one
+// Philox4x32-10 block (Salmon et al. 2011) per octet of eight consecutive elements, 16 bits per element, computed in
+// registers - no tables, no LDS, no state in memory - so the result does not depend on the grid, the traversal order or
+// the number of processes, and every other step is one correctly rounded fp32 operation: the kernel equals a plain
+// restatement bit for bit.
+//
+//   dare_merge   the one fused streaming pass: per octet the base (once when shared), per finetune one 16-byte load,
+//                one Philox block, eight compares, the fp32 chain; out is written once.  Kept counts: a counter per
+//                thread and finetune in LDS, reduced per work-group, one 64-bit global atomic per finetune.
+#pragma once
+#include "sm_ties.hpp"
+
+namespace smhip {
+
+constexpr uint32_t DARE_T_ONE = 65536u;       // the threshold of density 1: every 16-bit draw is below it
+
+// (hi, lo) of the 64-bit product a * b
+SM_HD void philox_mulhilo(uint32_t a, uint32_t b, uint32_t& hi, uint32_t& lo) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    hi = __umulhi(a, b);
+    lo = a * b;
+#else
+    const uint64_t p = (uint64_t)a * (uint64_t)b;
+    hi = (uint32_t)(p >> 32);
+    lo = (uint32_t)p;
+#endif
+}
+
+// Philox4x32-10: counter c[4] -> c[4] under the key (k0, k1)
+SM_HD void philox4x32_10(uint32_t* c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        uint32_t hi0, lo0, hi1, lo1;
+        philox_mulhilo(0xD2511F53u, c[0], hi0, lo0);
+        philox_mulhilo(0xCD9E8D57u, c[2], hi1, lo1);
+        c[0] = hi1 ^ c[1] ^ k0;
+        c[1] = lo1;
+        c[2] = hi0 ^ c[3] ^ k1;
+        c[3] = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// THE mask: bit e of the result is set iff element 8 * (j >> 3) + e of the finetune with this stream id draws a 16-bit
+// value below T - the octet that holds element j, from one Philox block whose counter is (j >> 3, stream_id, 0).
+SM_HD uint32_t dare_mask8(uint64_t key, uint32_t stream_id, uint64_t j, uint32_t T) {
+#if defined(SM_DARE_NO_PHILOX)      // A/B measurement only (tools/dare_bench.py --ab-lib): no generator, every element kept
+    return 0xffu;
+#endif
+    const uint64_t oct = j >> 3;
+    uint32_t c[4] = {(uint32_t)oct, (uint32_t)(oct >> 32), stream_id, 0u};
+    philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
+    uint32_t m = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const uint32_t w = c[e >> 1];
+        const uint32_t h = (e & 1) ? (w >> 16) : (w & 0xffffu);
+        m |= (h < T ? 1u : 0u) << e;
+    }
+    return m;
+}
+
+struct DareMergeParams {
+    TiesInputs in;
+    float alpha[TIES_MAX_MODELS];
+    uint32_t stream_id[TIES_MAX_MODELS];
+    uint64_t key;
+    uint32_t T;                 // keep threshold on the 16-bit draw, 1 .. 65536
+    float rescale;              // 1 or fp32(65536 / T)
+    const void* base_out; int base_out_dtype;
+    int out_is_base0;           // base_out is base[0] in the same dtype and the bases are shared: loaded once
+    float lambda;
+    int normalize;
+    int sign_election;          // 1: dare_ties, 0: dare_linear
+    void* out;                  // base_out_dtype, [n]
+    float* delta_out;           // optional fp32 [n]: lambda * M
+    unsigned long long* kept;   // [k], device: elements kept per finetune
+    uint32_t* flags;            // [0]: bit i = finetune i has a non-finite delta
+    int chunks;                 // octets per thread
+};
+// dynamic LDS beyond the scratch: a kept counter per (finetune, thread), then the k work-group totals
+SM_HD size_t dare_lds_words(int k, int nthreads) { return (size_t)k * nthreads + TIES_MAX_MODELS; }
+
+template <class Ex>
+SM_HD void k_dare_merge(Ex& ex, const DareMergeParams& p) {
+    typename Ex::template State<EmptyState> st;
+    ex.init(st);
+    const int nt = ex.nthreads();
+    const int k = p.in.k;
+    uint32_t* lc = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [k][nt], then [TIES_MAX_MODELS] totals
+    uint32_t* tot = lc + (size_t)k * nt;
+    const size_t noct = (p.in.n + 7) / 8;
+    const float eps = 1e-8f;
+    ex.each(st, [&](int tid, EmptyState&) {
+        for (int i = 0; i < k; ++i) lc[i * nt + tid] = 0;
+        if (tid < TIES_MAX_MODELS) tot[tid] = 0;
+    });
+    ex.sync();
+    ex.each(st, [&](int tid, EmptyState&) {
+        const size_t start = (size_t)ex.bid() * p.chunks * nt;
+        uint32_t bad = 0;
+        float Dall = 0.f;                                          // dare_linear: the sum of ALL weights, kept or not
+        for (int i = 0; i < k; ++i) Dall = aten_fadd_(Dall, p.alpha[i]);
+        for (int q = 0; q < p.chunks; ++q) {
+            const size_t oi = start + (size_t)q * nt + tid;
+            if (oi >= noct) break;
+            const size_t i0 = 8 * oi;
+            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
+            const bool vec = p.in.aligned && cnt == 8;
+            float b[8], bo[8], S[8], P[8], N[8], DP[8], DN[8];
+            if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
+            if (p.out_is_base0) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) bo[e] = b[e];
+            } else {
+                ties_load8(p.base_out, p.base_out_dtype, i0, cnt, vec, bo);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { S[e] = 0.f; P[e] = 0.f; N[e] = 0.f; DP[e] = 0.f; DN[e] = 0.f; }
+            for (int i = 0; i < k; ++i) {
+                float f[8];
+                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);       // (elements past n load as 0: never kept)
+                if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                const uint32_t mask = dare_mask8(p.key, p.stream_id[i], (uint64_t)i0, p.T);
+                const float al = p.alpha[i];
+                uint32_t nkept = 0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float d = f[e] - b[e];
+                    const uint32_t mag = f2u(d) & 0x7fffffffu;
+                    if (mag >= TIES_KEY_INF) bad |= 1u << i;
+                    const bool kept = ((mask >> e) & 1u) != 0u && mag != 0u;
+                    nkept += kept ? 1u : 0u;
+                    const float tv = kept ? aten_fmul_(aten_fmul_(d, p.rescale), al) : 0.f;
+                    S[e] = aten_fadd_(S[e], tv);
+                    if (p.sign_election) {       // as ties_merge: the running sums of the positive and of the negative entries
+                        if (tv > 0.f) { P[e] = aten_fadd_(P[e], tv); DP[e] = aten_fadd_(DP[e], al); }
+                        if (tv < 0.f) { N[e] = aten_fadd_(N[e], tv); DN[e] = aten_fadd_(DN[e], al); }
+                    }
+                }
+                lc[i * nt + tid] += nkept;                                 // this thread's own slot
+            }
+            float r[8], dl[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const bool pos = S[e] >= 0.f;
+                float M = p.sign_election ? (pos ? P[e] : N[e]) : S[e];
+                if (p.normalize) {
+                    float D = p.sign_election ? (pos ? DP[e] : DN[e]) : Dall;
+                    if (fabsf(D) < eps) D = 1.f;
+                    M = M / D;
+                }
+                dl[e] = aten_fmul_(p.lambda, M);
+                r[e] = aten_fadd_(bo[e], dl[e]);
+            }
+            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, dl);
+        }
+        if (bad) ex.global_atomic_or_u32(p.flags, bad);
+    });
+    ex.sync();
+    // 16 threads per finetune add up its nt counters, one LDS atomic each; then one global atomic per finetune
+    ex.each(st, [&](int tid, EmptyState&) {
+        const int groups = nt >= 16 ? nt >> 4 : 1;
+        for (int i = tid >> 4; i < k; i += groups) {
+            uint32_t s = 0;
+            for (int t = tid & 15; t < nt; t += 16) s += lc[i * nt + t];
+            if (s) ex.lds_atomic_add(&tot[i], s);
+        }
+    });
+    ex.sync();
+    ex.each(st, [&](int tid, EmptyState&) {
+        if (tid < k && tot[tid]) ex.global_atomic_add(&p.kept[tid], (unsigned long long)tot[tid]);
+    });
+}
+
+}  // namespace smhip

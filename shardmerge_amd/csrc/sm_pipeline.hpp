@@ -17,6 +17,7 @@
 #include "sm_bluestein.hpp"
 #include "sm_lora.hpp"
 #include "sm_ties.hpp"
+#include "sm_dare.hpp"
 
 namespace smhip {
 
@@ -215,6 +216,8 @@ SM_KERNEL_TAG_LB(KDoraApplyF32, LoraApplyParams, "dora_apply", k_dora_apply<DT_F
 SM_KERNEL_TAG_LB(KTiesHist, TiesHistParams, "ties_hist", k_ties_hist(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KTiesSelect, TiesSelectParams, "ties_select", k_ties_select(ex, p), TIES_SELECT_THREADS, 4)
 SM_KERNEL_TAG_LB(KTiesMerge, TiesMergeParams, "ties_merge", k_ties_merge(ex, p), 256, 4)
+// DARE merge (sm_dare.hpp): the one fused pass, the drop mask from a Philox block per octet in registers
+SM_KERNEL_TAG_LB(KDareMerge, DareMergeParams, "dare_merge", k_dare_merge(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -240,8 +243,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
-#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES
+#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES and DARE
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2420,6 +2423,62 @@ class Pipeline {
         return SMHIP_OK;
     }
 
+    // ---- DARE merge (sm_dare.hpp; the function is stated in shardmerge_hip.h); arguments checked by smhip_dare_merge ----
+    // workspace (the TIES buffer, the two never run at once): DareReadback
+    struct DareReadback { unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
+    static uint32_t dare_threshold(double density) {
+        return density == 1.0 ? DARE_T_ONE : (uint32_t)std::floor(density * 65536.0);
+    }
+    int dare_merge(const smhip_dare_desc& d, void* out, float* delta_out, smhip_dare_report* rep) {
+        const int k = d.k;
+        const size_t n = d.n;
+        const uint32_t T = dare_threshold(d.density);
+        if (rep) {
+            rep->T = T;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
+        }
+        if (n == 0) return SMHIP_OK;
+        int rc;
+        if ((rc = ensure(ties_, sizeof(DareReadback)))) return rc;
+        be.memset(ties_.p, 0, sizeof(DareReadback), stream);
+        DareReadback* rb = (DareReadback*)ties_.p;
+
+        DareMergeParams m;
+        TiesInputs& in = m.in;
+        in.k = k; in.dtype = d.in_dtype; in.n = n;
+        bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) {
+            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
+            al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
+            shared = shared && in.base[i] == in.base[0];
+            m.alpha[i] = (float)d.alpha[i < k ? i : 0];
+            m.stream_id[i] = d.stream_id[i < k ? i : 0];
+        }
+        in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
+        m.key = d.key; m.T = T;
+        m.rescale = d.rescale ? (float)(65536.0 / (double)T) : 1.f;
+        m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
+        m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
+        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0; m.sign_election = d.sign_election ? 1 : 0;
+        m.out = out; m.delta_out = delta_out; m.kept = rb->kept; m.flags = rb->flags;
+        const size_t noct = (n + 7) / 8;
+        m.chunks = pick_chunks(noct, 256, 2, 8);
+        be.template launch<KDareMerge>(stream_grid(noct, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
+
+        DareReadback host;
+        be.d2h(&host, rb, sizeof host, stream);          // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP)
+        if (host.flags[0]) {
+            std::string which;
+            for (int i = 0; i < k; ++i)
+                if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
+            return fail(SMHIP_ERR_NONFINITE, "dare_merge: NaN or Inf in finetune - base of finetune " + which);
+        }
+        if (rep)
+            for (int i = 0; i < k; ++i) rep->kept[i] = host.kept[i];
+        return SMHIP_OK;
+    }
+
     // ---- function level: slerp (functions.py:24-43), tensor / scalar and the exact norm (functions.py:75-88) ----
     int fn_slerp(const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out) {
         const size_t n = rows * cols;
@@ -2670,7 +2729,7 @@ class Pipeline {
     std::map<int, HostPlan> plans_;
     Buffer t1_, small_, tmpA_, tmpB_, tmpC_, fullS_, saveR_, saveI_, cand_, aten_, emf_;
     Buffer lora_;                       // packed LoRA factors (lora_apply)
-    Buffer ties_;                       // TIES: selection histograms, states and the report (ties_merge)
+    Buffer ties_;                       // TIES: selection histograms, states and the report (ties_merge); DARE: its report
     Buffer dora_;                       // DoRA: row partials, row factors, per-work-group bad-row counts (adapter_apply)
     std::vector<Buffer> pool_ = std::vector<Buffer>(4);
     std::vector<char> pool_busy_ = std::vector<char>(4, 1);

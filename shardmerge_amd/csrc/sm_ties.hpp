@@ -173,6 +173,40 @@ SM_HD void k_ties_select(Ex& ex, const TiesSelectParams& p) {
     });
 }
 
+// the store tail of a fused merge pass (ties_merge, dare_merge): octet oi of out (r, rounded once to out_dtype) and of the
+// optional fp32 delta_out (dl); cnt of the 8 elements exist, vec: one 16-byte store per 8 x 16 bit / two per 8 x fp32
+SM_HD void ties_store8(void* out, int out_dtype, float* delta_out, size_t oi, int cnt, bool vec, const float* r, const float* dl) {
+    const size_t i0 = 8 * oi;
+    if (delta_out) {
+        if (vec) {
+            cf4 w0 = {dl[0], dl[1], dl[2], dl[3]}, w1 = {dl[4], dl[5], dl[6], dl[7]};
+            ((cf4*)delta_out)[i0 / 4] = w0; ((cf4*)delta_out)[i0 / 4 + 1] = w1;
+        } else {
+            for (int e = 0; e < cnt; ++e) delta_out[i0 + e] = dl[e];
+        }
+    }
+    if (out_dtype == DT_F32) {
+        if (vec) {
+            cf4 w0 = {r[0], r[1], r[2], r[3]}, w1 = {r[4], r[5], r[6], r[7]};
+            ((cf4*)out)[i0 / 4] = w0; ((cf4*)out)[i0 / 4 + 1] = w1;
+        } else {
+            for (int e = 0; e < cnt; ++e) ((float*)out)[i0 + e] = r[e];
+        }
+    } else {
+        uint16_t h[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) h[e] = out_dtype == DT_BF16 ? f_to_bf16_any(r[e]) : f_to_f16_any(r[e]);
+        if (vec) {
+            u32x4 w;
+            w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16); w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+            w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16); w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
+            ((u32x4*)out)[oi] = w;
+        } else {
+            for (int e = 0; e < cnt; ++e) ((uint16_t*)out)[i0 + e] = h[e];
+        }
+    }
+}
+
 struct TiesMergeParams {
     TiesInputs in;
     float alpha[TIES_MAX_MODELS];
@@ -242,34 +276,7 @@ SM_HD void k_ties_merge(Ex& ex, const TiesMergeParams& p) {
                 dl[e] = aten_fmul_(p.lambda, M);
                 r[e] = aten_fadd_(bo[e], dl[e]);
             }
-            if (p.delta_out) {
-                if (vec) {
-                    cf4 w0 = {dl[0], dl[1], dl[2], dl[3]}, w1 = {dl[4], dl[5], dl[6], dl[7]};
-                    ((cf4*)p.delta_out)[i0 / 4] = w0; ((cf4*)p.delta_out)[i0 / 4 + 1] = w1;
-                } else {
-                    for (int e = 0; e < cnt; ++e) p.delta_out[i0 + e] = dl[e];
-                }
-            }
-            if (p.base_out_dtype == DT_F32) {
-                if (vec) {
-                    cf4 w0 = {r[0], r[1], r[2], r[3]}, w1 = {r[4], r[5], r[6], r[7]};
-                    ((cf4*)p.out)[i0 / 4] = w0; ((cf4*)p.out)[i0 / 4 + 1] = w1;
-                } else {
-                    for (int e = 0; e < cnt; ++e) ((float*)p.out)[i0 + e] = r[e];
-                }
-            } else {
-                uint16_t h[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) h[e] = p.base_out_dtype == DT_BF16 ? f_to_bf16_any(r[e]) : f_to_f16_any(r[e]);
-                if (vec) {
-                    u32x4 w;
-                    w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16); w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-                    w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16); w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
-                    ((u32x4*)p.out)[oi] = w;
-                } else {
-                    for (int e = 0; e < cnt; ++e) ((uint16_t*)p.out)[i0 + e] = h[e];
-                }
-            }
+            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, dl);
         }
     });
 }

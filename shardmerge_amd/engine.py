@@ -64,6 +64,13 @@ class TiesMergeReport:
 
 
 @dataclass
+class DareMergeReport:
+    threshold: int = 0                                               # T: an element is kept iff its 16-bit draw is < T
+    density: float = 0.0                                             # the effective density T / 65536
+    kept: List[int] = field(default_factory=list)                    # elements kept per finetune (zero deltas never)
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -398,6 +405,83 @@ class Engine:
             raise
         report = TiesMergeReport(k_keep=int(rep.k_keep), thresholds=[float(rep.threshold[i]) for i in range(k)],
                                  kept=[int(rep.kept[i]) for i in range(k)])
+        if want_delta:
+            return out, report, delta
+        return out, report
+
+    # -- DARE ------------------------------------------------------------------------------
+    def dare_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                   base_out: torch.Tensor, *, density: float = 0.2, lam: float = 1.0, normalize: bool = True,
+                   rescale: bool = True, sign_election: bool = True, key: int = 0, stream_ids: Optional[Sequence[int]] = None,
+                   want_delta: bool = False, layer_name: Optional[str] = None):
+        """DARE merge of one tensor of any shape (``smhip_dare_merge``; the function is stated in
+        include/shardmerge_hip.h): each delta ``finetune_i - base_i`` keeps an element iff the 16-bit draw of the
+        counter-based mask (Philox4x32-10 under ``key``, stream ``stream_ids[i]``, indexed by the element) is below
+        ``floor(density * 65536)``, survivors are rescaled by the inverse effective density (``rescale``), weighted by
+        ``alpha_i`` and either summed (``sign_election=False``: dare_linear) or merged as TIES merges (dare_ties),
+        ``normalize``: divided by the weights, times ``lam``, added onto ``base_out`` in its dtype.  ``stream_ids``
+        defaults to 0..k-1.  Returns (out, DareMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta raises
+        ValueError naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        k = len(finetunes)
+        if k < 1 or k > _lib.MAX_MODELS:
+            raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
+        if len(bases) != k or len(alphas) != k:
+            raise ValueError(f"dare_merge: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
+        if not (0.0 < float(density) <= 1.0):
+            raise ValueError(f"dare_merge: density {density} is not in (0, 1]")
+        if float(density) < 2.0 ** -16:
+            raise ValueError(f"dare_merge: density {density} is below the smallest density 2^-16 = {2.0 ** -16}")
+        stream_ids = list(range(k)) if stream_ids is None else [int(s) for s in stream_ids]
+        if len(stream_ids) != k or any(not (0 <= s < 2 ** 32) for s in stream_ids):
+            raise ValueError(f"dare_merge: stream_ids must be {k} integers in [0, 2^32)")
+        if isinstance(key, bool) or not isinstance(key, int) or not (0 <= key < 2 ** 64):
+            raise ValueError("dare_merge: key must be an integer in [0, 2^64)")
+        # one input dtype per call, mixed dtypes promoted to fp32 (as merge_layer does it)
+        dtypes = {t.dtype for t in list(finetunes) + list(bases)}
+        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
+        if in_dtype not in _DTYPE_CODE:
+            in_dtype = torch.float32
+        keep = []
+        desc = _lib.DareDesc()
+        desc.k = k
+        seen: Dict[int, torch.Tensor] = {}
+        for i in range(k):
+            ft = self._dev(finetunes[i], in_dtype)
+            bkey = id(bases[i])
+            if bkey not in seen:
+                seen[bkey] = self._dev(bases[i], in_dtype)
+            bs = seen[bkey]
+            if ft.shape != base_out.shape or bs.shape != base_out.shape:
+                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
+            keep += [ft, bs]
+            desc.finetune[i] = ft.data_ptr()
+            desc.base[i] = bs.data_ptr()
+            desc.alpha[i] = float(alphas[i])
+            desc.stream_id[i] = stream_ids[i]
+        bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
+        bo = seen.get(id(base_out))
+        if bo is None or bo.dtype != bo_dtype:
+            bo = self._dev(base_out, bo_dtype)
+        keep.append(bo)
+        desc.in_dtype = _DTYPE_CODE[in_dtype]
+        desc.base_out = bo.data_ptr()
+        desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
+        desc.n = bo.numel()
+        desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
+        desc.key, desc.rescale, desc.sign_election = key, 1 if rescale else 0, 1 if sign_election else 0
+        out = torch.empty(bo.shape, dtype=bo_dtype, device=self.device)
+        delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
+        rep = _lib.DareReport()
+        try:
+            self.ctx.check(self.lib.dll.smhip_dare_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
+                                                         delta.data_ptr() if delta is not None else None,
+                                                         C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
+            raise
+        report = DareMergeReport(threshold=int(rep.T), density=int(rep.T) / 65536.0, kept=[int(rep.kept[i]) for i in range(k)])
         if want_delta:
             return out, report, delta
         return out, report

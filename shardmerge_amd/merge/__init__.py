@@ -18,4 +18,10 @@ def operator_class(name: str = "fourier"):
     if name == "ties":
         from .ties import TiesMerge
         return TiesMerge
+    if name == "dare_ties":
+        from .dare import DareTiesMerge
+        return DareTiesMerge
+    if name == "dare_linear":
+        from .dare import DareLinearMerge
+        return DareLinearMerge
     raise ValueError(f"unknown merge operator {name!r}")
