@@ -261,6 +261,60 @@ typedef struct {
 int smhip_dare_merge(smhip_ctx* ctx, const smhip_dare_desc* desc, void* out, float* delta_out,
                      smhip_dare_report* report, void* stream);
 
+/* ---- Model Breadcrumbs merge (Davari & Belilovsky, "Model Breadcrumbs", 2023): trim each finetune's delta at BOTH
+ *      ends - drop the smallest magnitudes, as TIES does, and also the few largest ones, the outliers - then add the
+ *      weighted masked deltas (breadcrumbs) or elect a sign and merge the agreeing entries as TIES does
+ *      (breadcrumbs_ties).  The reference has no such operator; this section IS its definition.  For one tensor of n
+ *      elements (any shape, flat), finetunes i = 0..k-1 in order (1 <= k <= 16):
+ *        1. d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with SMHIP_ERR_NONFINITE
+ *           (the message lists the finetunes); out is then unspecified.
+ *        2. k_keep = n if density == 1, else (uint64) floor(density * n) in fp64 (the rule of smhip_ties_merge).
+ *           n_top = min((uint64) floor(gamma * n), n - k_keep) in fp64: the number of largest magnitudes that may be
+ *           dropped.  Arguments: 0 < density <= 1, 0 <= gamma < 1, density + gamma <= 1 evaluated in fp64, else
+ *           SMHIP_ERR_ARG.
+ *        3. With the magnitudes ranked from the largest: tau_hi_i = the (n_top + 1)-th largest |d_i|, tau_lo_i = the
+ *           (n_top + k_keep)-th largest, both exact; both +inf when k_keep == 0.  An element is KEPT iff
+ *           tau_lo_i <= |d_i| <= tau_hi_i and d_i != 0.  TIE RULE: an element that ties with either threshold is kept,
+ *           so the result does not depend on any traversal order; at most n_top elements (those strictly above
+ *           tau_hi_i) are dropped at the top, and at least k_keep are kept unless tau_lo_i == 0 (zeros are never
+ *           kept).  With n_top == 0, tau_hi_i is the maximum and the upper test is vacuous - there is no special case.
+ *        4. tv_i = fl32(d_i * fp32(alpha_i)) where kept, +0 elsewhere.
+ *        5. sign_election == 1 (breadcrumbs_ties): steps 4-6 of smhip_ties_merge on these tv_i.
+ *           sign_election == 0 (breadcrumbs): M = ((0 + tv_0) + tv_1) + ... in fp32; D = ((0 + fp32(alpha_0)) + ...)
+ *           over ALL finetunes, kept or not; D := 1 where |D| < fp32(1e-8); M := M / D when normalize - step 5 of
+ *           smhip_dare_merge for dare_linear.
+ *        6. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M)), delta_out = fl32(lambda * M):
+ *           step 7 of smhip_ties_merge.
+ *      Every step is one correctly rounded fp32 operation or an exact order statistic: the result is defined bit for
+ *      bit.  Two identities follow: gamma == 0 with sign_election == 1 equals smhip_ties_merge with the same density,
+ *      lambda and normalize; gamma == 0, density == 1, sign_election == 0 equals smhip_dare_merge with density 1 and
+ *      sign_election 0 (any key, either rescale).  Both order statistics of a finetune are found in the same three
+ *      histogram passes that smhip_ties_merge spends on one, so the call moves the same 4k + 5 tensors (shared base).
+ *      Aliasing, alignment, n == 0 and the size limit: the rules of smhip_ties_merge; the call synchronises the stream
+ *      once, at its end, to fetch the report.  Profile names: "crumbs_hist", "crumbs_select", "crumbs_merge". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double density, lambda; int normalize;
+    double gamma;                           /* the share of largest magnitudes that may be dropped */
+    int sign_election;                      /* 1: breadcrumbs_ties; 0: breadcrumbs */
+} smhip_breadcrumbs_desc;
+typedef struct {
+    uint64_t k_keep, n_top;
+    float threshold_lo[SMHIP_MAX_MODELS];   /* tau_lo_i */
+    float threshold_hi[SMHIP_MAX_MODELS];   /* tau_hi_i */
+    uint64_t kept[SMHIP_MAX_MODELS];        /* elements of finetune i that were kept */
+    uint64_t dropped_top[SMHIP_MAX_MODELS]; /* elements strictly above tau_hi_i (<= n_top) */
+} smhip_breadcrumbs_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * M).  report (optional): HOST. */
+int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* desc, void* out, float* delta_out,
+                            smhip_breadcrumbs_report* report, void* stream);
+
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector
  *      v1 - v0 dot is normalised along the LAST dimension (F.normalize(dim=-1), eps 1e-12), out = v0 cos + rel sin.

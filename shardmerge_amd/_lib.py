@@ -103,6 +103,28 @@ class DareReport(C.Structure):
     _fields_ = [("T", C.c_uint32), ("kept", C.c_uint64 * MAX_MODELS)]
 
 
+class BreadcrumbsDesc(C.Structure):
+    """smhip_breadcrumbs_desc"""
+    _fields_ = [
+        ("k", C.c_int),
+        ("finetune", C.c_void_p * MAX_MODELS),
+        ("base", C.c_void_p * MAX_MODELS),
+        ("alpha", C.c_double * MAX_MODELS),
+        ("in_dtype", C.c_int),
+        ("base_out", C.c_void_p), ("base_out_dtype", C.c_int),
+        ("n", C.c_size_t),
+        ("density", C.c_double), ("lam", C.c_double), ("normalize", C.c_int),
+        ("gamma", C.c_double), ("sign_election", C.c_int),
+    ]
+
+
+class BreadcrumbsReport(C.Structure):
+    """smhip_breadcrumbs_report"""
+    _fields_ = [("k_keep", C.c_uint64), ("n_top", C.c_uint64),
+                ("threshold_lo", C.c_float * MAX_MODELS), ("threshold_hi", C.c_float * MAX_MODELS),
+                ("kept", C.c_uint64 * MAX_MODELS), ("dropped_top", C.c_uint64 * MAX_MODELS)]
+
+
 class LayerReport(C.Structure):
     _fields_ = [
         ("target_norm", C.c_double),
@@ -153,6 +175,7 @@ class SmhipLibrary:
         d.smhip_addition_merge.argtypes = [P, I, C.POINTER(C.c_void_p), P, I, C.c_size_t, I, P, P]
         d.smhip_ties_merge.argtypes = [P, C.POINTER(TiesDesc), P, P, C.POINTER(TiesReport), P]
         d.smhip_dare_merge.argtypes = [P, C.POINTER(DareDesc), P, P, C.POINTER(DareReport), P]
+        d.smhip_breadcrumbs_merge.argtypes = [P, C.POINTER(BreadcrumbsDesc), P, P, C.POINTER(BreadcrumbsReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

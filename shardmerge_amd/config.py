@@ -36,6 +36,16 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # seed: 0                 #   an integer in [0, 2^63): with the tensor's name it keys the mask, which is a function
                                 #   of (seed, tensor name, position of the entry in finetune_merge, element index) - the
                                 #   same config gives the same bytes in one process, in place and on any number of ranks
+                                # | breadcrumbs | breadcrumbs_ties (Model Breadcrumbs, Davari & Belilovsky 2023; no
+                                #   counterpart in the reference): each delta loses its `gamma` share of LARGEST magnitudes
+                                #   and keeps the next `density` share (the small rest is dropped as ties drops it; ties at
+                                #   either threshold all kept), then the weighted deltas are added (breadcrumbs) or merged
+                                #   as ties merges (breadcrumbs_ties).  Keys, these operators only (the spectral keys,
+                                #   norm_mode, task_add_models, ties_*, dare_* and seed are rejected):
+      # density: 0.9            #   0 < density <= 1
+      # gamma: 0.01             #   0 <= gamma < 1, density + gamma <= 1
+      # breadcrumbs_lambda: 1.0 #   scales the merged delta
+      # breadcrumbs_normalize: 1  # 1: divide by the sum of the weights (breadcrumbs_ties: of the agreeing entries), 0: plain sum
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -61,7 +71,7 @@ _REQUIRED = ("output_base_model", "finetune_merge", "output_dir")
 MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.0, "target_norm_offset": 1e-10, "b": 0.1}
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
-OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear")
+OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties")
 # operator ties only: its three options and their defaults
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
 TIES_OPTION_RANGES = {"ties_lambda": (-1e6, 1e6)}                  # density: (0, 1]; ties_normalize: 0 or 1
@@ -70,6 +80,10 @@ DARE_OPERATORS = ("dare_ties", "dare_linear")
 DARE_OPTION_DEFAULTS = {"density": 0.2, "dare_lambda": 1.0, "dare_normalize": 1.0, "dare_rescale": 1.0, "seed": 0}
 DARE_OPTION_RANGES = {"dare_lambda": (-1e6, 1e6)}   # density: [2^-16, 1]; dare_normalize, dare_rescale: 0 or 1; seed: [0, 2^63)
 DARE_MIN_DENSITY = 2.0 ** -16                       # the mask draws 16 bits per element
+# operators breadcrumbs / breadcrumbs_ties only: their options and defaults
+BREADCRUMBS_OPERATORS = ("breadcrumbs", "breadcrumbs_ties")
+BREADCRUMBS_OPTION_DEFAULTS = {"density": 0.9, "gamma": 0.01, "breadcrumbs_lambda": 1.0, "breadcrumbs_normalize": 1.0}
+BREADCRUMBS_OPTION_RANGES = {"breadcrumbs_lambda": (-1e6, 1e6)}    # density: (0, 1]; gamma: [0, 1), density + gamma <= 1; normalize: 0 or 1
 
 
 @dataclass
@@ -176,6 +190,13 @@ class MergeConfig:
         if operator not in OPERATORS:
             raise click.BadParameter(f"merge_options.operator must be one of {list(OPERATORS)}")
         raw["operator"] = operator
+        if operator in BREADCRUMBS_OPERATORS:
+            if task_add:
+                raise click.BadParameter(f"merge_options.task_add_models is an option of operator fourier_legacy; operator {operator!r} would ignore it")
+            raw["merge_options"] = cls._breadcrumbs_options(opts, norm_mode, operator)
+            return cls(**raw)
+        for key in sorted((set(opts) & set(BREADCRUMBS_OPTION_DEFAULTS)) - set(TIES_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: breadcrumbs or breadcrumbs_ties (operator {operator!r} would ignore it)")
         if operator in DARE_OPERATORS:
             if task_add:
                 raise click.BadParameter(f"merge_options.task_add_models is an option of operator fourier_legacy; operator {operator!r} would ignore it")
@@ -189,7 +210,7 @@ class MergeConfig:
             raw["merge_options"] = cls._ties_options(opts, norm_mode)
             return cls(**raw)
         for key in sorted(set(opts) & set(TIES_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: ties, dare_ties or dare_linear (operator {operator!r} would ignore it)")
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: ties, dare_ties, dare_linear, breadcrumbs or breadcrumbs_ties (operator {operator!r} would ignore it)")
         unknown = set(opts) - set(MERGE_OPTION_DEFAULTS)
         if not isinstance(opts, dict) or unknown:
             raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known: {sorted(MERGE_OPTION_DEFAULTS) + ['norm_mode', 'operator']}")
@@ -257,3 +278,42 @@ class MergeConfig:
                     raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
             out[key] = float(value)
         return out
+
+    @staticmethod
+    def _breadcrumbs_options(opts: Dict[str, Any], norm_mode: str, operator: str) -> Dict[str, float]:
+        """merge_options of breadcrumbs / breadcrumbs_ties: their own keys only - an option they would ignore is an error that names it"""
+        for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator {operator!r} would ignore it")
+        if norm_mode != DEFAULT_NORM_MODE:
+            raise click.BadParameter(f"merge_options.norm_mode is an option of the spectral operators; operator {operator!r} takes no norm")
+        for key in sorted((set(opts) & set(TIES_OPTION_DEFAULTS)) - set(BREADCRUMBS_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is an option of operator ties; operator {operator!r} would ignore it "
+                                     "(its keys: breadcrumbs_lambda, breadcrumbs_normalize)")
+        for key in sorted((set(opts) & set(DARE_OPTION_DEFAULTS)) - set(BREADCRUMBS_OPTION_DEFAULTS)):
+            raise click.BadParameter(f"merge_options.{key} is an option of operators dare_ties / dare_linear; operator {operator!r} would ignore it "
+                                     "(its trim is by magnitude, not random)")
+        unknown = set(opts) - set(BREADCRUMBS_OPTION_DEFAULTS)
+        if unknown:
+            raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator {operator}: "
+                                     f"{sorted(BREADCRUMBS_OPTION_DEFAULTS) + ['operator']}")
+        for key, value in opts.items():
+            number = isinstance(value, (int, float)) and not isinstance(value, bool)
+            if key == "density":
+                if not number or not (0.0 < float(value) <= 1.0):
+                    raise click.BadParameter("merge_options.density must be a number in (0, 1]")
+            elif key == "gamma":
+                if not number or not (0.0 <= float(value) < 1.0):
+                    raise click.BadParameter("merge_options.gamma must be a number in [0, 1)")
+            elif key == "breadcrumbs_normalize":
+                if not number or float(value) not in (0.0, 1.0):
+                    raise click.BadParameter("merge_options.breadcrumbs_normalize must be 0 or 1")
+            else:
+                lo, hi = BREADCRUMBS_OPTION_RANGES[key]
+                if not number or not (lo <= float(value) <= hi):
+                    raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
+        density = float(opts.get("density", BREADCRUMBS_OPTION_DEFAULTS["density"]))
+        gamma = float(opts.get("gamma", BREADCRUMBS_OPTION_DEFAULTS["gamma"]))
+        if not (density + gamma <= 1.0):
+            raise click.BadParameter(f"merge_options.density + merge_options.gamma must not exceed 1 (density {density:g}, gamma {gamma:g}): "
+                                     "the dropped top and the kept band cannot overlap")
+        return {k: float(v) for k, v in opts.items()}

@@ -217,6 +217,45 @@ int smhip_dare_merge(smhip_ctx* ctx, const smhip_dare_desc* d, void* out, float*
     SM_FINISH(ctx, ctx->pipe.dare_merge(*d, out, delta_out, report));
 }
 
+int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* d, void* out, float* delta_out,
+                            smhip_breadcrumbs_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: null descriptor");
+    if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: k out of range (1..16)");
+    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->base_out_dtype < SMHIP_BF16 || d->base_out_dtype > SMHIP_F32)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: bad dtype");
+    if (!(d->density > 0.0 && d->density <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: density must be in (0, 1]");
+    if (!(d->gamma >= 0.0 && d->gamma < 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: gamma must be in [0, 1)");
+    if (!(d->density + d->gamma <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: density + gamma must not exceed 1");
+    if (!std::isfinite(d->lambda)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: lambda is not finite");
+    for (int i = 0; i < d->k; ++i)
+        if (!std::isfinite(d->alpha[i])) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: an alpha is not finite");
+    if (d->n > 0) {
+        if (!out || !d->base_out) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: null out or base_out");
+        const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
+        if ((uintptr_t)out % oes || (uintptr_t)d->base_out % oes || (uintptr_t)delta_out % 4)
+            return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: a pointer is not aligned to its element size");
+        auto overlaps = [&](const void* o, size_t obytes, const void* p, size_t bytes) {
+            return o && (uintptr_t)p < (uintptr_t)o + obytes && (uintptr_t)o < (uintptr_t)p + bytes;
+        };
+        auto hits_output = [&](const void* p, size_t bytes) {
+            return overlaps(out, d->n * oes, p, bytes) || overlaps(delta_out, d->n * 4, p, bytes);
+        };
+        for (int i = 0; i < d->k; ++i) {
+            if (!d->finetune[i] || !d->base[i]) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: null model tensor");
+            if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies)
+                return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: a pointer is not aligned to its element size");
+            if (hits_output(d->finetune[i], d->n * ies) || hits_output(d->base[i], d->n * ies))
+                return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: out overlaps an input");
+        }
+        if (hits_output(d->base_out, d->n * oes) || overlaps(out, d->n * oes, delta_out, d->n * 4))
+            return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: out overlaps an input");
+        if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: tensor too large");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.breadcrumbs_merge(*d, out, delta_out, report));
+}
+
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {
     SM_GUARD(ctx);
     if (rows * cols > 0 && (!v0 || !v1 || !out)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

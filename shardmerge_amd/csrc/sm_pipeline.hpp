@@ -18,6 +18,7 @@
 #include "sm_lora.hpp"
 #include "sm_ties.hpp"
 #include "sm_dare.hpp"
+#include "sm_breadcrumbs.hpp"
 
 namespace smhip {
 
@@ -218,6 +219,10 @@ SM_KERNEL_TAG_LB(KTiesSelect, TiesSelectParams, "ties_select", k_ties_select(ex,
 SM_KERNEL_TAG_LB(KTiesMerge, TiesMergeParams, "ties_merge", k_ties_merge(ex, p), 256, 4)
 // DARE merge (sm_dare.hpp): the one fused pass, the drop mask from a Philox block per octet in registers
 SM_KERNEL_TAG_LB(KDareMerge, DareMergeParams, "dare_merge", k_dare_merge(ex, p), 256, 4)
+// Breadcrumbs merge (sm_breadcrumbs.hpp): the two-rank radix level, its scan, and the fused two-sided merge pass
+SM_KERNEL_TAG_LB(KCrumbsHist, CrumbsHistParams, "crumbs_hist", k_crumbs_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KCrumbsSelect, CrumbsSelectParams, "crumbs_select", k_crumbs_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KCrumbsMerge, CrumbsMergeParams, "crumbs_merge", k_crumbs_merge(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -243,8 +248,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
-#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES and DARE
+#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE and Breadcrumbs
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2479,6 +2484,95 @@ class Pipeline {
         return SMHIP_OK;
     }
 
+    // ---- Breadcrumbs merge (sm_breadcrumbs.hpp; the function is stated in shardmerge_hip.h); arguments checked by
+    // smhip_breadcrumbs_merge ----
+    // workspace (the TIES buffer, the operators never run at once): the three levels' histograms [3][k][HIST1_BINS] |
+    // CrumbsState[k][2] | CrumbsReadback
+    struct CrumbsReadback {
+        float threshold_lo[TIES_MAX_MODELS], threshold_hi[TIES_MAX_MODELS];
+        unsigned long long kept[TIES_MAX_MODELS], dropped_top[TIES_MAX_MODELS];
+        uint32_t flags[2];
+    };
+    int breadcrumbs_merge(const smhip_breadcrumbs_desc& d, void* out, float* delta_out, smhip_breadcrumbs_report* rep) {
+        const int k = d.k;
+        const size_t n = d.n;
+        const unsigned long long k_keep = d.density == 1.0 ? (unsigned long long)n : (unsigned long long)std::floor(d.density * (double)n);
+        const unsigned long long n_top = std::min((unsigned long long)std::floor(d.gamma * (double)n), (unsigned long long)n - k_keep);
+        if (rep) {
+            rep->k_keep = k_keep; rep->n_top = n_top;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) { rep->threshold_lo[i] = 0.f; rep->threshold_hi[i] = 0.f; rep->kept[i] = 0; rep->dropped_top[i] = 0; }
+        }
+        if (n == 0) {                                    // k_keep == 0: the thresholds are +inf by definition
+            if (rep) for (int i = 0; i < k; ++i) { rep->threshold_lo[i] = INFINITY; rep->threshold_hi[i] = INFINITY; }
+            return SMHIP_OK;
+        }
+        const size_t hist_level = (size_t)TIES_MAX_MODELS * HIST1_BINS * sizeof(unsigned long long);
+        const size_t off_state = 3 * hist_level, off_rb = off_state + 2 * TIES_MAX_MODELS * sizeof(CrumbsState);
+        const size_t ws = off_rb + sizeof(CrumbsReadback);
+        int rc;
+        if ((rc = ensure(ties_, ws))) return rc;
+        be.memset(ties_.p, 0, ws, stream);
+        CrumbsState* state = (CrumbsState*)((char*)ties_.p + off_state);
+        CrumbsReadback* rb = (CrumbsReadback*)((char*)ties_.p + off_rb);
+
+        TiesInputs in;
+        in.k = k; in.dtype = d.in_dtype; in.n = n;
+        bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) {
+            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
+            al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
+            shared = shared && in.base[i] == in.base[0];
+        }
+        in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
+        const size_t noct = (n + 7) / 8;
+
+        CrumbsHistParams h;
+        h.in = in; h.state = state; h.flags = rb->flags;
+        h.chunks = pick_chunks(noct, 256, 4, 5);
+        const int hgrid = stream_grid(noct, 256, h.chunks);
+        CrumbsSelectParams s;
+        s.k_keep = k_keep; s.rank[CRUMBS_HI] = n_top + 1; s.rank[CRUMBS_LO] = n_top + k_keep;
+        s.state = state; s.threshold_lo = rb->threshold_lo; s.threshold_hi = rb->threshold_hi;
+        s.kept = rb->kept; s.dropped_top = rb->dropped_top;
+        for (int level = 1; level <= 3; ++level) {
+            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * hist_level);
+            h.level = level; h.hist = hist;
+            // (k_keep == 0: the thresholds are +inf whatever the data; level 1 still runs, it finds the non-finite deltas)
+            for (int first = 0; first < k && (level == 1 || k_keep > 0); first += TIES_GROUP) {
+                h.first = first; h.count = std::min(TIES_GROUP, k - first);
+                be.template launch<KCrumbsHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * HIST1_BINS) * 4, h, stream);
+            }
+            s.level = level; s.hist = hist;
+            be.template launch<KCrumbsSelect>(k, TIES_SELECT_THREADS, CRUMBS_SELECT_LDS, s, stream);
+        }
+
+        CrumbsMergeParams m;
+        m.in = in;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < k ? i : 0];
+        m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
+        m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
+        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0; m.sign_election = d.sign_election ? 1 : 0;
+        m.threshold_lo = rb->threshold_lo; m.threshold_hi = rb->threshold_hi; m.out = out; m.delta_out = delta_out;
+        m.chunks = pick_chunks(noct, 256, 2, 8);
+        be.template launch<KCrumbsMerge>(stream_grid(noct, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+
+        CrumbsReadback host;
+        be.d2h(&host, rb, sizeof host, stream);          // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP)
+        if (host.flags[0]) {
+            std::string which;
+            for (int i = 0; i < k; ++i)
+                if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
+            return fail(SMHIP_ERR_NONFINITE, "breadcrumbs_merge: NaN or Inf in finetune - base of finetune " + which);
+        }
+        if (rep)
+            for (int i = 0; i < k; ++i) {
+                rep->threshold_lo[i] = host.threshold_lo[i]; rep->threshold_hi[i] = host.threshold_hi[i];
+                rep->kept[i] = host.kept[i]; rep->dropped_top[i] = host.dropped_top[i];
+            }
+        return SMHIP_OK;
+    }
+
     // ---- function level: slerp (functions.py:24-43), tensor / scalar and the exact norm (functions.py:75-88) ----
     int fn_slerp(const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out) {
         const size_t n = rows * cols;
@@ -2729,7 +2823,7 @@ class Pipeline {
     std::map<int, HostPlan> plans_;
     Buffer t1_, small_, tmpA_, tmpB_, tmpC_, fullS_, saveR_, saveI_, cand_, aten_, emf_;
     Buffer lora_;                       // packed LoRA factors (lora_apply)
-    Buffer ties_;                       // TIES: selection histograms, states and the report (ties_merge); DARE: its report
+    Buffer ties_;                       // TIES / Breadcrumbs: selection histograms, states and the report; DARE: its report
     Buffer dora_;                       // DoRA: row partials, row factors, per-work-group bad-row counts (adapter_apply)
     std::vector<Buffer> pool_ = std::vector<Buffer>(4);
     std::vector<char> pool_busy_ = std::vector<char>(4, 1);

@@ -71,6 +71,16 @@ class DareMergeReport:
 
 
 @dataclass
+class BreadcrumbsMergeReport:
+    k_keep: int = 0                                                  # elements each finetune was asked to keep
+    n_top: int = 0                                                   # largest magnitudes that may be dropped per finetune
+    thresholds_lo: List[float] = field(default_factory=list)         # tau_lo_i: the (n_top + k_keep)-th largest |delta_i|
+    thresholds_hi: List[float] = field(default_factory=list)         # tau_hi_i: the (n_top + 1)-th largest |delta_i|
+    kept: List[int] = field(default_factory=list)                    # elements kept (ties at either threshold included, zeros never)
+    dropped_top: List[int] = field(default_factory=list)             # elements strictly above tau_hi_i (<= n_top)
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -482,6 +492,82 @@ class Engine:
                 raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
             raise
         report = DareMergeReport(threshold=int(rep.T), density=int(rep.T) / 65536.0, kept=[int(rep.kept[i]) for i in range(k)])
+        if want_delta:
+            return out, report, delta
+        return out, report
+
+    # -- Model Breadcrumbs ---------------------------------------------------------------
+    def breadcrumbs_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                          base_out: torch.Tensor, density: float = 0.9, gamma: float = 0.01, lam: float = 1.0,
+                          normalize: bool = True, sign_election: bool = False, want_delta: bool = False,
+                          layer_name: Optional[str] = None):
+        """Model Breadcrumbs merge of one tensor of any shape (``smhip_breadcrumbs_merge``; the function is stated in
+        include/shardmerge_hip.h): each delta ``finetune_i - base_i`` loses its ``floor(gamma * n)`` largest magnitudes
+        and keeps the next ``floor(density * n)`` (ties at either threshold all kept), is weighted by ``alpha_i`` and
+        either summed (``sign_election=False``: breadcrumbs, ``normalize``: divided by the sum of all weights) or merged
+        as TIES merges (breadcrumbs_ties), times ``lam``, added onto ``base_out`` in its dtype.  Returns
+        (out, BreadcrumbsMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta raises ValueError naming
+        ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        k = len(finetunes)
+        if k < 1 or k > _lib.MAX_MODELS:
+            raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
+        if len(bases) != k or len(alphas) != k:
+            raise ValueError(f"breadcrumbs_merge: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
+        if not (0.0 < float(density) <= 1.0):
+            raise ValueError(f"breadcrumbs_merge: density {density} is not in (0, 1]")
+        if not (0.0 <= float(gamma) < 1.0):
+            raise ValueError(f"breadcrumbs_merge: gamma {gamma} is not in [0, 1)")
+        if not (float(density) + float(gamma) <= 1.0):
+            raise ValueError(f"breadcrumbs_merge: density {density} + gamma {gamma} exceeds 1")
+        # one input dtype per call, mixed dtypes promoted to fp32 (as merge_layer does it)
+        dtypes = {t.dtype for t in list(finetunes) + list(bases)}
+        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
+        if in_dtype not in _DTYPE_CODE:
+            in_dtype = torch.float32
+        keep = []
+        desc = _lib.BreadcrumbsDesc()
+        desc.k = k
+        seen: Dict[int, torch.Tensor] = {}
+        for i in range(k):
+            ft = self._dev(finetunes[i], in_dtype)
+            bkey = id(bases[i])
+            if bkey not in seen:
+                seen[bkey] = self._dev(bases[i], in_dtype)
+            bs = seen[bkey]
+            if ft.shape != base_out.shape or bs.shape != base_out.shape:
+                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
+            keep += [ft, bs]
+            desc.finetune[i] = ft.data_ptr()
+            desc.base[i] = bs.data_ptr()
+            desc.alpha[i] = float(alphas[i])
+        bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
+        bo = seen.get(id(base_out))
+        if bo is None or bo.dtype != bo_dtype:
+            bo = self._dev(base_out, bo_dtype)
+        keep.append(bo)
+        desc.in_dtype = _DTYPE_CODE[in_dtype]
+        desc.base_out = bo.data_ptr()
+        desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
+        desc.n = bo.numel()
+        desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
+        desc.gamma, desc.sign_election = float(gamma), 1 if sign_election else 0
+        out = torch.empty(bo.shape, dtype=bo_dtype, device=self.device)
+        delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
+        rep = _lib.BreadcrumbsReport()
+        try:
+            self.ctx.check(self.lib.dll.smhip_breadcrumbs_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
+                                                                delta.data_ptr() if delta is not None else None,
+                                                                C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
+            raise
+        report = BreadcrumbsMergeReport(k_keep=int(rep.k_keep), n_top=int(rep.n_top),
+                                        thresholds_lo=[float(rep.threshold_lo[i]) for i in range(k)],
+                                        thresholds_hi=[float(rep.threshold_hi[i]) for i in range(k)],
+                                        kept=[int(rep.kept[i]) for i in range(k)],
+                                        dropped_top=[int(rep.dropped_top[i]) for i in range(k)])
         if want_delta:
             return out, report, delta
         return out, report

@@ -24,4 +24,10 @@ def operator_class(name: str = "fourier"):
     if name == "dare_linear":
         from .dare import DareLinearMerge
         return DareLinearMerge
+    if name == "breadcrumbs":
+        from .breadcrumbs import BreadcrumbsMerge
+        return BreadcrumbsMerge
+    if name == "breadcrumbs_ties":
+        from .breadcrumbs import BreadcrumbsTiesMerge
+        return BreadcrumbsTiesMerge
     raise ValueError(f"unknown merge operator {name!r}")

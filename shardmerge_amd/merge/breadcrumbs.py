@@ -1,0 +1,60 @@
+"""BreadcrumbsMerge / BreadcrumbsTiesMerge: Model Breadcrumbs (Davari & Belilovsky, 2023) - trim each finetune's delta
+at BOTH ends: drop its ``gamma`` share of largest magnitudes (the outliers that dominate a merge of several finetunes)
+and keep the next ``density`` share, dropping the small rest as TIES does; then add the weighted masked deltas
+(``breadcrumbs``) or elect a sign and merge the agreeing entries as TIES does (``breadcrumbs_ties``), and add the result
+onto output_base_model.  The reference has no such operator; the function is defined in include/shardmerge_hip.h
+(``smhip_breadcrumbs_merge``) and runs in three HIP kernels (csrc/sm_breadcrumbs.hpp) behind
+``Engine.breadcrumbs_merge``: both thresholds of a finetune come out of the same three histogram passes TIES spends on
+its one.
+
+Tensor routing is FourierMerge's, as with TiesMerge: only the block-tensor merge (``merge_block``) differs."""
+from __future__ import annotations
+
+import logging
+
+from ..config import BREADCRUMBS_OPTION_DEFAULTS
+from .ties import TiesMerge
+
+logger = logging.getLogger(__name__)
+
+
+class BreadcrumbsMerge(TiesMerge):
+    sign_election = False
+    mode = "breadcrumbs"
+
+    def __init__(self, config, index_manager=None, engine=None, **kwargs):
+        self.gamma = BREADCRUMBS_OPTION_DEFAULTS["gamma"]
+        self.breadcrumbs_lambda = BREADCRUMBS_OPTION_DEFAULTS["breadcrumbs_lambda"]
+        self.breadcrumbs_normalize = BREADCRUMBS_OPTION_DEFAULTS["breadcrumbs_normalize"]
+        super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)     # (sets the YAML overrides)
+        if "density" not in (getattr(config, "merge_options", None) or {}):
+            self.density = BREADCRUMBS_OPTION_DEFAULTS["density"]                            # (not TIES's 0.2)
+
+    def get_readme(self) -> str:
+        models = "\n".join(f"- {m.model} (vs {m.base}, weight {m.alpha})" for m in self.config.finetune_merge)
+        how = "elect sign, merge the agreeing entries" if self.sign_election else "add the weighted deltas"
+        norm = ("normalized by the agreeing weights" if self.sign_election else "normalized by the sum of the weights") \
+            if self.breadcrumbs_normalize else "plain sum"
+        return (f"# Breadcrumbs Merged Model\nBase: {self.config.output_base_model}\n"
+                f"Method: Model Breadcrumbs ({self.mode}: drop the largest and the smallest magnitudes, {how}), "
+                f"density {self.density:g}, gamma {self.gamma:g}, lambda {self.breadcrumbs_lambda:g}, {norm}\n"
+                f"Models merged:\n{models}\n")
+
+    def merge_block(self, eng, fts, bases, alphas, base_out, name: str):
+        return eng.breadcrumbs_merge(fts, bases, alphas, base_out, density=self.density, gamma=self.gamma,
+                                     lam=self.breadcrumbs_lambda, normalize=bool(self.breadcrumbs_normalize),
+                                     sign_election=self.sign_election, layer_name=name)
+
+    def block_cost_ms(self, shape, k: int) -> float:
+        """the partitioned path's cost model: TIES's (the same tensor passes)"""
+        return TiesMerge.block_cost_ms(self, shape, k)
+
+    def _log_block(self, name: str, k: int, report):
+        logger.info(f"Merged {name}: {k} model(s), Breadcrumbs ({self.mode}) kept {report.kept} of {report.k_keep} asked, "
+                    f"dropped {report.dropped_top} of at most {report.n_top} at the top, thresholds "
+                    f"{[(float(f'{lo:.4g}'), float(f'{hi:.4g}')) for lo, hi in zip(report.thresholds_lo, report.thresholds_hi)]}")
+
+
+class BreadcrumbsTiesMerge(BreadcrumbsMerge):
+    sign_election = True
+    mode = "breadcrumbs_ties"
