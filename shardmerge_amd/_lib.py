@@ -62,18 +62,22 @@ class LayerDesc(C.Structure):
     ]
 
 
+# the leading fields that smhip_ties_desc, smhip_dare_desc and smhip_breadcrumbs_desc share
+_DELTA_DESC_FIELDS = [
+    ("k", C.c_int),
+    ("finetune", C.c_void_p * MAX_MODELS),
+    ("base", C.c_void_p * MAX_MODELS),
+    ("alpha", C.c_double * MAX_MODELS),
+    ("in_dtype", C.c_int),
+    ("base_out", C.c_void_p), ("base_out_dtype", C.c_int),
+    ("n", C.c_size_t),
+    ("density", C.c_double), ("lam", C.c_double), ("normalize", C.c_int),
+]
+
+
 class TiesDesc(C.Structure):
     """smhip_ties_desc"""
-    _fields_ = [
-        ("k", C.c_int),
-        ("finetune", C.c_void_p * MAX_MODELS),
-        ("base", C.c_void_p * MAX_MODELS),
-        ("alpha", C.c_double * MAX_MODELS),
-        ("in_dtype", C.c_int),
-        ("base_out", C.c_void_p), ("base_out_dtype", C.c_int),
-        ("n", C.c_size_t),
-        ("density", C.c_double), ("lam", C.c_double), ("normalize", C.c_int),
-    ]
+    _fields_ = _DELTA_DESC_FIELDS
 
 
 class TiesReport(C.Structure):
@@ -83,15 +87,7 @@ class TiesReport(C.Structure):
 
 class DareDesc(C.Structure):
     """smhip_dare_desc"""
-    _fields_ = [
-        ("k", C.c_int),
-        ("finetune", C.c_void_p * MAX_MODELS),
-        ("base", C.c_void_p * MAX_MODELS),
-        ("alpha", C.c_double * MAX_MODELS),
-        ("in_dtype", C.c_int),
-        ("base_out", C.c_void_p), ("base_out_dtype", C.c_int),
-        ("n", C.c_size_t),
-        ("density", C.c_double), ("lam", C.c_double), ("normalize", C.c_int),
+    _fields_ = _DELTA_DESC_FIELDS + [
         ("key", C.c_uint64),
         ("stream_id", C.c_uint32 * MAX_MODELS),
         ("rescale", C.c_int), ("sign_election", C.c_int),
@@ -105,15 +101,7 @@ class DareReport(C.Structure):
 
 class BreadcrumbsDesc(C.Structure):
     """smhip_breadcrumbs_desc"""
-    _fields_ = [
-        ("k", C.c_int),
-        ("finetune", C.c_void_p * MAX_MODELS),
-        ("base", C.c_void_p * MAX_MODELS),
-        ("alpha", C.c_double * MAX_MODELS),
-        ("in_dtype", C.c_int),
-        ("base_out", C.c_void_p), ("base_out_dtype", C.c_int),
-        ("n", C.c_size_t),
-        ("density", C.c_double), ("lam", C.c_double), ("normalize", C.c_int),
+    _fields_ = _DELTA_DESC_FIELDS + [
         ("gamma", C.c_double), ("sign_election", C.c_int),
     ]
 

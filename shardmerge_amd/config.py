@@ -58,7 +58,7 @@ from __future__ import annotations
 import dataclasses
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Union
+from typing import Any, Callable, Dict, List, Optional, Union
 
 import click
 import torch
@@ -72,18 +72,97 @@ MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties")
-# operator ties only: its three options and their defaults
+# The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
+# (all of them take `density`), seed stays an int (it must survive exactly), every other value becomes a float.
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
-TIES_OPTION_RANGES = {"ties_lambda": (-1e6, 1e6)}                  # density: (0, 1]; ties_normalize: 0 or 1
-# operators dare_ties / dare_linear only: their options and defaults (seed stays an int: it must survive exactly)
 DARE_OPERATORS = ("dare_ties", "dare_linear")
 DARE_OPTION_DEFAULTS = {"density": 0.2, "dare_lambda": 1.0, "dare_normalize": 1.0, "dare_rescale": 1.0, "seed": 0}
-DARE_OPTION_RANGES = {"dare_lambda": (-1e6, 1e6)}   # density: [2^-16, 1]; dare_normalize, dare_rescale: 0 or 1; seed: [0, 2^63)
 DARE_MIN_DENSITY = 2.0 ** -16                       # the mask draws 16 bits per element
-# operators breadcrumbs / breadcrumbs_ties only: their options and defaults
 BREADCRUMBS_OPERATORS = ("breadcrumbs", "breadcrumbs_ties")
 BREADCRUMBS_OPTION_DEFAULTS = {"density": 0.9, "gamma": 0.01, "breadcrumbs_lambda": 1.0, "breadcrumbs_normalize": 1.0}
-BREADCRUMBS_OPTION_RANGES = {"breadcrumbs_lambda": (-1e6, 1e6)}    # density: (0, 1]; gamma: [0, 1), density + gamma <= 1; normalize: 0 or 1
+
+
+def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
+    density = float(opts.get("density", BREADCRUMBS_OPTION_DEFAULTS["density"]))
+    gamma = float(opts.get("gamma", BREADCRUMBS_OPTION_DEFAULTS["gamma"]))
+    if not (density + gamma <= 1.0):
+        raise click.BadParameter(f"merge_options.density + merge_options.gamma must not exceed 1 (density {density:g}, gamma {gamma:g}): "
+                                 "the dropped top and the kept band cannot overlap")
+
+
+@dataclass(frozen=True)
+class _OptionFamily:
+    """One family's merge_options.  rules: key -> "flag" (0 or 1), "seed" (an exact integer in [0, 2^63)) or a range
+    (lo, hi, brackets[, the message's own wording of the range]).  earlier: what the message says after a key of an
+    earlier family, by that family's first operator.  check: a rule over several keys."""
+    operators: tuple
+    defaults: Dict[str, Union[int, float]]
+    rules: Dict[str, Any]
+    earlier: Dict[str, str] = field(default_factory=dict)
+    check: Optional[Callable[[Dict[str, Any]], None]] = None
+
+
+_DENSITY, _LAMBDA = (0, 1, "(]"), (-1e6, 1e6, "[]")
+_OPTION_FAMILIES = (                                # in the order they were added: a later family knows the earlier ones
+    _OptionFamily(("ties",), TIES_OPTION_DEFAULTS, {"density": _DENSITY, "ties_lambda": _LAMBDA, "ties_normalize": "flag"}),
+    _OptionFamily(DARE_OPERATORS, DARE_OPTION_DEFAULTS,
+                  {"density": (DARE_MIN_DENSITY, 1, "[]", f"[2^-16 = {DARE_MIN_DENSITY}, 1] with operator {{operator}} (the mask draws 16 bits per element)"),
+                   "dare_lambda": _LAMBDA, "dare_normalize": "flag", "dare_rescale": "flag", "seed": "seed"},
+                  earlier={"ties": "(its keys: dare_lambda, dare_normalize)"}),
+    _OptionFamily(BREADCRUMBS_OPERATORS, BREADCRUMBS_OPTION_DEFAULTS,
+                  {"density": _DENSITY, "gamma": (0, 1, "[)"), "breadcrumbs_lambda": _LAMBDA, "breadcrumbs_normalize": "flag"},
+                  earlier={"ties": "(its keys: breadcrumbs_lambda, breadcrumbs_normalize)", "dare_ties": "(its trim is by magnitude, not random)"},
+                  check=_breadcrumbs_band),
+)
+
+
+def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], operator: str) -> Optional[Dict[str, Union[int, float]]]:
+    """merge_options of a delta-merge operator: its family's keys only - an option the operator would ignore is an
+    error that names it.  None for an operator of no family, once the families' keys are ruled out."""
+    own = next((i for i, f in enumerate(_OPTION_FAMILIES) if operator in f.operators), -1)
+    for i in reversed(range(own + 1, len(_OPTION_FAMILIES))):          # the families added after the operator's, the latest first
+        new = set(_OPTION_FAMILIES[i].defaults).difference(*(e.defaults for e in _OPTION_FAMILIES[:i]))    # the keys it brought
+        for key in sorted(set(opts) & new):
+            names = [op for f in _OPTION_FAMILIES if new & set(f.defaults) for op in f.operators]
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: {', '.join(names[:-1])} or {names[-1]} "
+                                     f"(operator {operator!r} would ignore it)")
+    if own < 0:
+        return None
+    fam = _OPTION_FAMILIES[own]
+    if task_add:
+        raise click.BadParameter(f"merge_options.task_add_models is an option of operator fourier_legacy; operator {operator!r} would ignore it")
+    for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
+        raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator {operator!r} would ignore it")
+    if norm_mode != DEFAULT_NORM_MODE:
+        raise click.BadParameter(f"merge_options.norm_mode is an option of the spectral operators; operator {operator!r} takes no norm")
+    for e in _OPTION_FAMILIES[:own]:
+        for key in sorted((set(opts) & set(e.defaults)) - set(fam.defaults)):
+            raise click.BadParameter(f"merge_options.{key} is an option of operator{'s' if len(e.operators) > 1 else ''} {' / '.join(e.operators)}; "
+                                     f"operator {operator!r} would ignore it {fam.earlier[e.operators[0]]}")
+    unknown = set(opts) - set(fam.defaults)
+    if unknown:
+        raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator {operator}: {sorted(fam.defaults) + ['operator']}")
+    out: Dict[str, Union[int, float]] = {}
+    for key, value in opts.items():
+        rule = fam.rules[key]
+        number = isinstance(value, (int, float)) and not isinstance(value, bool)
+        if rule == "seed":
+            if not isinstance(value, int) or isinstance(value, bool) or not (0 <= value < 2 ** 63):
+                raise click.BadParameter(f"merge_options.{key} must be an integer in [0, 2^63)")
+            out[key] = int(value)
+            continue
+        if rule == "flag":
+            if not number or float(value) not in (0.0, 1.0):
+                raise click.BadParameter(f"merge_options.{key} must be 0 or 1")
+        else:
+            lo, hi, (left, right) = rule[:3]
+            text = rule[3].format(operator=operator) if len(rule) > 3 else f"{left}{lo}, {hi}{right}"
+            if not number or not (lo <= float(value) <= hi) or (left == "(" and value == lo) or (right == ")" and value == hi):
+                raise click.BadParameter(f"merge_options.{key} must be a number in {text}")
+        out[key] = float(value)
+    if fam.check:
+        fam.check(opts)
+    return out
 
 
 @dataclass
@@ -190,27 +269,10 @@ class MergeConfig:
         if operator not in OPERATORS:
             raise click.BadParameter(f"merge_options.operator must be one of {list(OPERATORS)}")
         raw["operator"] = operator
-        if operator in BREADCRUMBS_OPERATORS:
-            if task_add:
-                raise click.BadParameter(f"merge_options.task_add_models is an option of operator fourier_legacy; operator {operator!r} would ignore it")
-            raw["merge_options"] = cls._breadcrumbs_options(opts, norm_mode, operator)
+        family_options = _family_options(opts, norm_mode, task_add, operator)
+        if family_options is not None:
+            raw["merge_options"] = family_options
             return cls(**raw)
-        for key in sorted((set(opts) & set(BREADCRUMBS_OPTION_DEFAULTS)) - set(TIES_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: breadcrumbs or breadcrumbs_ties (operator {operator!r} would ignore it)")
-        if operator in DARE_OPERATORS:
-            if task_add:
-                raise click.BadParameter(f"merge_options.task_add_models is an option of operator fourier_legacy; operator {operator!r} would ignore it")
-            raw["merge_options"] = cls._dare_options(opts, norm_mode, operator)
-            return cls(**raw)
-        for key in sorted((set(opts) & set(DARE_OPTION_DEFAULTS)) - set(TIES_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: dare_ties or dare_linear (operator {operator!r} would ignore it)")
-        if operator == "ties":
-            if task_add:
-                raise click.BadParameter("merge_options.task_add_models is an option of operator fourier_legacy; operator 'ties' would ignore it")
-            raw["merge_options"] = cls._ties_options(opts, norm_mode)
-            return cls(**raw)
-        for key in sorted(set(opts) & set(TIES_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: ties, dare_ties, dare_linear, breadcrumbs or breadcrumbs_ties (operator {operator!r} would ignore it)")
         unknown = set(opts) - set(MERGE_OPTION_DEFAULTS)
         if not isinstance(opts, dict) or unknown:
             raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known: {sorted(MERGE_OPTION_DEFAULTS) + ['norm_mode', 'operator']}")
@@ -220,100 +282,3 @@ class MergeConfig:
                 raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
         raw["merge_options"] = {k: float(v) for k, v in opts.items()}
         return cls(**raw)
-
-    @staticmethod
-    def _ties_options(opts: Dict[str, Any], norm_mode: str) -> Dict[str, float]:
-        """merge_options of operator ties: its own three keys only - an option it would ignore is an error that names it"""
-        for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator 'ties' would ignore it")
-        if norm_mode != DEFAULT_NORM_MODE:
-            raise click.BadParameter("merge_options.norm_mode is an option of the spectral operators; operator 'ties' takes no norm")
-        unknown = set(opts) - set(TIES_OPTION_DEFAULTS)
-        if unknown:
-            raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator ties: {sorted(TIES_OPTION_DEFAULTS) + ['operator']}")
-        for key, value in opts.items():
-            number = isinstance(value, (int, float)) and not isinstance(value, bool)
-            if key == "density":
-                if not number or not (0.0 < float(value) <= 1.0):
-                    raise click.BadParameter("merge_options.density must be a number in (0, 1]")
-            elif key == "ties_normalize":
-                if not number or float(value) not in (0.0, 1.0):
-                    raise click.BadParameter("merge_options.ties_normalize must be 0 or 1")
-            else:
-                lo, hi = TIES_OPTION_RANGES[key]
-                if not number or not (lo <= float(value) <= hi):
-                    raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
-        return {k: float(v) for k, v in opts.items()}
-
-    @staticmethod
-    def _dare_options(opts: Dict[str, Any], norm_mode: str, operator: str) -> Dict[str, Union[int, float]]:
-        """merge_options of dare_ties / dare_linear: their own keys only - an option they would ignore is an error that names it"""
-        for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator {operator!r} would ignore it")
-        if norm_mode != DEFAULT_NORM_MODE:
-            raise click.BadParameter(f"merge_options.norm_mode is an option of the spectral operators; operator {operator!r} takes no norm")
-        for key in sorted((set(opts) & set(TIES_OPTION_DEFAULTS)) - set(DARE_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is an option of operator ties; operator {operator!r} would ignore it (its keys: dare_lambda, dare_normalize)")
-        unknown = set(opts) - set(DARE_OPTION_DEFAULTS)
-        if unknown:
-            raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator {operator}: {sorted(DARE_OPTION_DEFAULTS) + ['operator']}")
-        out: Dict[str, Union[int, float]] = {}
-        for key, value in opts.items():
-            number = isinstance(value, (int, float)) and not isinstance(value, bool)
-            if key == "seed":
-                if not isinstance(value, int) or isinstance(value, bool) or not (0 <= value < 2 ** 63):
-                    raise click.BadParameter("merge_options.seed must be an integer in [0, 2^63)")
-                out[key] = int(value)
-                continue
-            if key == "density":
-                if not number or not (DARE_MIN_DENSITY <= float(value) <= 1.0):
-                    raise click.BadParameter(f"merge_options.density must be a number in [2^-16 = {DARE_MIN_DENSITY}, 1] with operator {operator} "
-                                             "(the mask draws 16 bits per element)")
-            elif key in ("dare_normalize", "dare_rescale"):
-                if not number or float(value) not in (0.0, 1.0):
-                    raise click.BadParameter(f"merge_options.{key} must be 0 or 1")
-            else:
-                lo, hi = DARE_OPTION_RANGES[key]
-                if not number or not (lo <= float(value) <= hi):
-                    raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
-            out[key] = float(value)
-        return out
-
-    @staticmethod
-    def _breadcrumbs_options(opts: Dict[str, Any], norm_mode: str, operator: str) -> Dict[str, float]:
-        """merge_options of breadcrumbs / breadcrumbs_ties: their own keys only - an option they would ignore is an error that names it"""
-        for key in sorted(set(opts) & set(MERGE_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is an option of the spectral operators; operator {operator!r} would ignore it")
-        if norm_mode != DEFAULT_NORM_MODE:
-            raise click.BadParameter(f"merge_options.norm_mode is an option of the spectral operators; operator {operator!r} takes no norm")
-        for key in sorted((set(opts) & set(TIES_OPTION_DEFAULTS)) - set(BREADCRUMBS_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is an option of operator ties; operator {operator!r} would ignore it "
-                                     "(its keys: breadcrumbs_lambda, breadcrumbs_normalize)")
-        for key in sorted((set(opts) & set(DARE_OPTION_DEFAULTS)) - set(BREADCRUMBS_OPTION_DEFAULTS)):
-            raise click.BadParameter(f"merge_options.{key} is an option of operators dare_ties / dare_linear; operator {operator!r} would ignore it "
-                                     "(its trim is by magnitude, not random)")
-        unknown = set(opts) - set(BREADCRUMBS_OPTION_DEFAULTS)
-        if unknown:
-            raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator {operator}: "
-                                     f"{sorted(BREADCRUMBS_OPTION_DEFAULTS) + ['operator']}")
-        for key, value in opts.items():
-            number = isinstance(value, (int, float)) and not isinstance(value, bool)
-            if key == "density":
-                if not number or not (0.0 < float(value) <= 1.0):
-                    raise click.BadParameter("merge_options.density must be a number in (0, 1]")
-            elif key == "gamma":
-                if not number or not (0.0 <= float(value) < 1.0):
-                    raise click.BadParameter("merge_options.gamma must be a number in [0, 1)")
-            elif key == "breadcrumbs_normalize":
-                if not number or float(value) not in (0.0, 1.0):
-                    raise click.BadParameter("merge_options.breadcrumbs_normalize must be 0 or 1")
-            else:
-                lo, hi = BREADCRUMBS_OPTION_RANGES[key]
-                if not number or not (lo <= float(value) <= hi):
-                    raise click.BadParameter(f"merge_options.{key} must be a number in [{lo}, {hi}]")
-        density = float(opts.get("density", BREADCRUMBS_OPTION_DEFAULTS["density"]))
-        gamma = float(opts.get("gamma", BREADCRUMBS_OPTION_DEFAULTS["gamma"]))
-        if not (density + gamma <= 1.0):
-            raise click.BadParameter(f"merge_options.density + merge_options.gamma must not exceed 1 (density {density:g}, gamma {gamma:g}): "
-                                     "the dropped top and the kept band cannot overlap")
-        return {k: float(v) for k, v in opts.items()}

@@ -22,6 +22,42 @@ struct smhip_ctx {
         return rc__;                                                              \
     } while (0)
 
+// The argument checks that smhip_ties_merge, smhip_dare_merge and smhip_breadcrumbs_merge share: their descriptors have
+// the same leading fields (k .. normalize), hence the template.  `op` names the entry point in the messages.
+template <class Desc>
+static int delta_merge_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out) {
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + what); };
+    if (!d) return bad("null descriptor");
+    if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return bad("k out of range (1..16)");
+    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->base_out_dtype < SMHIP_BF16 || d->base_out_dtype > SMHIP_F32)
+        return bad("bad dtype");
+    if (!(d->density > 0.0 && d->density <= 1.0)) return bad("density must be in (0, 1]");
+    if (!std::isfinite(d->lambda)) return bad("lambda is not finite");
+    for (int i = 0; i < d->k; ++i)
+        if (!std::isfinite(d->alpha[i])) return bad("an alpha is not finite");
+    if (d->n == 0) return SMHIP_OK;
+    if (!out || !d->base_out) return bad("null out or base_out");
+    const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
+    if ((uintptr_t)out % oes || (uintptr_t)d->base_out % oes || (uintptr_t)delta_out % 4)
+        return bad("a pointer is not aligned to its element size");
+    auto overlaps = [&](const void* o, size_t obytes, const void* p, size_t bytes) {
+        return o && (uintptr_t)p < (uintptr_t)o + obytes && (uintptr_t)o < (uintptr_t)p + bytes;
+    };
+    auto hits_output = [&](const void* p, size_t bytes) {
+        return overlaps(out, d->n * oes, p, bytes) || overlaps(delta_out, d->n * 4, p, bytes);
+    };
+    bool hit = hits_output(d->base_out, d->n * oes) || overlaps(out, d->n * oes, delta_out, d->n * 4);
+    for (int i = 0; i < d->k; ++i) {
+        if (!d->finetune[i] || !d->base[i]) return bad("null model tensor");
+        if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies)
+            return bad("a pointer is not aligned to its element size");
+        hit = hit || hits_output(d->finetune[i], d->n * ies) || hits_output(d->base[i], d->n * ies);
+    }
+    if (hit) return bad("out overlaps an input");
+    if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return bad("tensor too large");
+    return SMHIP_OK;
+}
+
 extern "C" {
 
 const char* smhip_version(void) { return SM_VERSION_STRING; }
@@ -144,36 +180,7 @@ int smhip_addition_merge(smhip_ctx* ctx, int k, const void* const* finetunes, co
 int smhip_ties_merge(smhip_ctx* ctx, const smhip_ties_desc* d, void* out, float* delta_out, smhip_ties_report* report,
                      void* stream) {
     SM_GUARD(ctx);
-    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: null descriptor");
-    if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: k out of range (1..16)");
-    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->base_out_dtype < SMHIP_BF16 || d->base_out_dtype > SMHIP_F32)
-        return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: bad dtype");
-    if (!(d->density > 0.0 && d->density <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: density must be in (0, 1]");
-    if (!std::isfinite(d->lambda)) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: lambda is not finite");
-    for (int i = 0; i < d->k; ++i)
-        if (!std::isfinite(d->alpha[i])) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: an alpha is not finite");
-    if (d->n > 0) {
-        if (!out || !d->base_out) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: null out or base_out");
-        const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
-        if ((uintptr_t)out % oes || (uintptr_t)d->base_out % oes || (uintptr_t)delta_out % 4)
-            return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: a pointer is not aligned to its element size");
-        auto overlaps = [&](const void* o, size_t obytes, const void* p, size_t bytes) {
-            return o && (uintptr_t)p < (uintptr_t)o + obytes && (uintptr_t)o < (uintptr_t)p + bytes;
-        };
-        auto hits_output = [&](const void* p, size_t bytes) {
-            return overlaps(out, d->n * oes, p, bytes) || overlaps(delta_out, d->n * 4, p, bytes);
-        };
-        for (int i = 0; i < d->k; ++i) {
-            if (!d->finetune[i] || !d->base[i]) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: null model tensor");
-            if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies)
-                return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: a pointer is not aligned to its element size");
-            if (hits_output(d->finetune[i], d->n * ies) || hits_output(d->base[i], d->n * ies))
-                return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: out overlaps an input");
-        }
-        if (hits_output(d->base_out, d->n * oes) || overlaps(out, d->n * oes, delta_out, d->n * 4))
-            return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: out overlaps an input");
-        if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return ctx->pipe.fail(SMHIP_ERR_ARG, "ties_merge: tensor too large");
-    }
+    if (int rc = delta_merge_check(ctx, "ties_merge", d, out, delta_out)) return rc;
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.ties_merge(*d, out, delta_out, report));
 }
@@ -181,38 +188,9 @@ int smhip_ties_merge(smhip_ctx* ctx, const smhip_ties_desc* d, void* out, float*
 int smhip_dare_merge(smhip_ctx* ctx, const smhip_dare_desc* d, void* out, float* delta_out, smhip_dare_report* report,
                      void* stream) {
     SM_GUARD(ctx);
-    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: null descriptor");
-    if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: k out of range (1..16)");
-    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->base_out_dtype < SMHIP_BF16 || d->base_out_dtype > SMHIP_F32)
-        return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: bad dtype");
-    if (!(d->density > 0.0 && d->density <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: density must be in (0, 1]");
+    if (int rc = delta_merge_check(ctx, "dare_merge", d, out, delta_out)) return rc;
     if (ctx->pipe.dare_threshold(d->density) == 0)
         return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: density is below the smallest density, 2^-16 = 1.52587890625e-05 (the mask draws 16 bits per element)");
-    if (!std::isfinite(d->lambda)) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: lambda is not finite");
-    for (int i = 0; i < d->k; ++i)
-        if (!std::isfinite(d->alpha[i])) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: an alpha is not finite");
-    if (d->n > 0) {
-        if (!out || !d->base_out) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: null out or base_out");
-        const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
-        if ((uintptr_t)out % oes || (uintptr_t)d->base_out % oes || (uintptr_t)delta_out % 4)
-            return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: a pointer is not aligned to its element size");
-        auto overlaps = [&](const void* o, size_t obytes, const void* p, size_t bytes) {
-            return o && (uintptr_t)p < (uintptr_t)o + obytes && (uintptr_t)o < (uintptr_t)p + bytes;
-        };
-        auto hits_output = [&](const void* p, size_t bytes) {
-            return overlaps(out, d->n * oes, p, bytes) || overlaps(delta_out, d->n * 4, p, bytes);
-        };
-        for (int i = 0; i < d->k; ++i) {
-            if (!d->finetune[i] || !d->base[i]) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: null model tensor");
-            if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies)
-                return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: a pointer is not aligned to its element size");
-            if (hits_output(d->finetune[i], d->n * ies) || hits_output(d->base[i], d->n * ies))
-                return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: out overlaps an input");
-        }
-        if (hits_output(d->base_out, d->n * oes) || overlaps(out, d->n * oes, delta_out, d->n * 4))
-            return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: out overlaps an input");
-        if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: tensor too large");
-    }
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.dare_merge(*d, out, delta_out, report));
 }
@@ -220,38 +198,9 @@ int smhip_dare_merge(smhip_ctx* ctx, const smhip_dare_desc* d, void* out, float*
 int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* d, void* out, float* delta_out,
                             smhip_breadcrumbs_report* report, void* stream) {
     SM_GUARD(ctx);
-    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: null descriptor");
-    if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: k out of range (1..16)");
-    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->base_out_dtype < SMHIP_BF16 || d->base_out_dtype > SMHIP_F32)
-        return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: bad dtype");
-    if (!(d->density > 0.0 && d->density <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: density must be in (0, 1]");
+    if (int rc = delta_merge_check(ctx, "breadcrumbs_merge", d, out, delta_out)) return rc;
     if (!(d->gamma >= 0.0 && d->gamma < 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: gamma must be in [0, 1)");
     if (!(d->density + d->gamma <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: density + gamma must not exceed 1");
-    if (!std::isfinite(d->lambda)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: lambda is not finite");
-    for (int i = 0; i < d->k; ++i)
-        if (!std::isfinite(d->alpha[i])) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: an alpha is not finite");
-    if (d->n > 0) {
-        if (!out || !d->base_out) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: null out or base_out");
-        const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
-        if ((uintptr_t)out % oes || (uintptr_t)d->base_out % oes || (uintptr_t)delta_out % 4)
-            return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: a pointer is not aligned to its element size");
-        auto overlaps = [&](const void* o, size_t obytes, const void* p, size_t bytes) {
-            return o && (uintptr_t)p < (uintptr_t)o + obytes && (uintptr_t)o < (uintptr_t)p + bytes;
-        };
-        auto hits_output = [&](const void* p, size_t bytes) {
-            return overlaps(out, d->n * oes, p, bytes) || overlaps(delta_out, d->n * 4, p, bytes);
-        };
-        for (int i = 0; i < d->k; ++i) {
-            if (!d->finetune[i] || !d->base[i]) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: null model tensor");
-            if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies)
-                return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: a pointer is not aligned to its element size");
-            if (hits_output(d->finetune[i], d->n * ies) || hits_output(d->base[i], d->n * ies))
-                return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: out overlaps an input");
-        }
-        if (hits_output(d->base_out, d->n * oes) || overlaps(out, d->n * oes, delta_out, d->n * 4))
-            return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: out overlaps an input");
-        if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: tensor too large");
-    }
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.breadcrumbs_merge(*d, out, delta_out, report));
 }

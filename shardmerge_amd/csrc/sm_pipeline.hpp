@@ -2350,144 +2350,149 @@ class Pipeline {
         return SMHIP_OK;
     }
 
-    // ---- TIES merge (sm_ties.hpp; the function is stated in shardmerge_hip.h); arguments checked by smhip_ties_merge ----
-    // workspace: the three levels' histograms [3][k][HIST1_BINS] | TiesState[k] | TiesReadback
-    struct TiesReadback { float threshold[TIES_MAX_MODELS]; unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
-    int ties_merge(const smhip_ties_desc& d, void* out, float* delta_out, smhip_ties_report* rep) {
-        const int k = d.k;
-        const size_t n = d.n;
-        const unsigned long long k_keep = d.density == 1.0 ? (unsigned long long)n : (unsigned long long)std::floor(d.density * (double)n);
-        if (rep) {
-            rep->k_keep = k_keep;
-            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) { rep->threshold[i] = 0.f; rep->kept[i] = 0; }
-        }
-        if (n == 0) {                                    // k_keep == 0: the threshold is +inf by definition
-            if (rep) for (int i = 0; i < k; ++i) rep->threshold[i] = INFINITY;
-            return SMHIP_OK;
-        }
-        const size_t hist_level = (size_t)TIES_MAX_MODELS * HIST1_BINS * sizeof(unsigned long long);
-        const size_t off_state = 3 * hist_level, off_rb = off_state + TIES_MAX_MODELS * sizeof(TiesState);
-        const size_t ws = off_rb + sizeof(TiesReadback);
-        int rc;
-        if ((rc = ensure(ties_, ws))) return rc;
-        be.memset(ties_.p, 0, ws, stream);
-        TiesState* state = (TiesState*)((char*)ties_.p + off_state);
-        TiesReadback* rb = (TiesReadback*)((char*)ties_.p + off_rb);
-
-        TiesInputs in;
-        in.k = k; in.dtype = d.in_dtype; in.n = n;
-        bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
-        for (int i = 0; i < TIES_MAX_MODELS; ++i) {
-            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
-            al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
-            shared = shared && in.base[i] == in.base[0];
-        }
-        in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
-        const size_t noct = (n + 7) / 8;
-
-        TiesHistParams h;
-        h.in = in; h.state = state; h.flags = rb->flags;
-        h.chunks = pick_chunks(noct, 256, 4, 5);
-        const int hgrid = stream_grid(noct, 256, h.chunks);
-        TiesSelectParams s;
-        s.k_keep = k_keep; s.state = state; s.threshold = rb->threshold; s.kept = rb->kept;
-        for (int level = 1; level <= 3; ++level) {
-            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * hist_level);
-            h.level = level; h.hist = hist;
-            const int nbins = level == 1 ? HIST1_BINS : HIST_LO_BINS;
-            // (k_keep == 0: the threshold is +inf whatever the data; level 1 still runs, it finds the non-finite deltas)
-            for (int first = 0; first < k && (level == 1 || k_keep > 0); first += TIES_GROUP) {
-                h.first = first; h.count = std::min(TIES_GROUP, k - first);
-                be.template launch<KTiesHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * nbins) * 4, h, stream);
-            }
-            s.level = level; s.hist = hist;
-            be.template launch<KTiesSelect>(k, TIES_SELECT_THREADS, LDS_SCRATCH_FLOATS * 4 + TIES_SELECT_THREADS * sizeof(unsigned long long), s, stream);
-        }
-
-        TiesMergeParams m;
-        m.in = in;
-        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < k ? i : 0];
-        m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
-        m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
-        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0;
-        m.threshold = rb->threshold; m.out = out; m.delta_out = delta_out;
-        m.chunks = pick_chunks(noct, 256, 2, 8);
-        be.template launch<KTiesMerge>(stream_grid(noct, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
-
-        TiesReadback host;
-        be.d2h(&host, rb, sizeof host, stream);          // the call's one synchronisation
-        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP)
-        if (host.flags[0]) {
-            std::string which;
-            for (int i = 0; i < k; ++i)
-                if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
-            return fail(SMHIP_ERR_NONFINITE, "ties_merge: NaN or Inf in finetune - base of finetune " + which);
-        }
-        if (rep)
-            for (int i = 0; i < k; ++i) { rep->threshold[i] = host.threshold[i]; rep->kept[i] = host.kept[i]; }
-        return SMHIP_OK;
+    // ---- the delta-merge family: TIES, DARE, Breadcrumbs (sm_ties.hpp, sm_dare.hpp, sm_breadcrumbs.hpp; the functions are
+    // stated in shardmerge_hip.h; arguments checked by delta_merge_check, sm_capi.inc).  The descriptors share their leading
+    // fields and the *MergeParams their common ones, so what the three host paths share is written once, as templates. ----
+    static unsigned long long delta_k_keep(double density, size_t n) {
+        return density == 1.0 ? (unsigned long long)n : (unsigned long long)std::floor(density * (double)n);
     }
-
-    // ---- DARE merge (sm_dare.hpp; the function is stated in shardmerge_hip.h); arguments checked by smhip_dare_merge ----
-    // workspace (the TIES buffer, the two never run at once): DareReadback
-    struct DareReadback { unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
-    static uint32_t dare_threshold(double density) {
-        return density == 1.0 ? DARE_T_ONE : (uint32_t)std::floor(density * 65536.0);
-    }
-    int dare_merge(const smhip_dare_desc& d, void* out, float* delta_out, smhip_dare_report* rep) {
+    // the common fields of a *MergeParams: the inputs (padded with finetune 0), alignment, shared base, add-back, chunks
+    template <class Desc, class MergeParams>
+    void delta_merge_params(const Desc& d, void* out, float* delta_out, MergeParams& m) {
         const int k = d.k;
-        const size_t n = d.n;
-        const uint32_t T = dare_threshold(d.density);
-        if (rep) {
-            rep->T = T;
-            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
-        }
-        if (n == 0) return SMHIP_OK;
-        int rc;
-        if ((rc = ensure(ties_, sizeof(DareReadback)))) return rc;
-        be.memset(ties_.p, 0, sizeof(DareReadback), stream);
-        DareReadback* rb = (DareReadback*)ties_.p;
-
-        DareMergeParams m;
         TiesInputs& in = m.in;
-        in.k = k; in.dtype = d.in_dtype; in.n = n;
+        in.k = k; in.dtype = d.in_dtype; in.n = d.n;
         bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
         for (int i = 0; i < TIES_MAX_MODELS; ++i) {
             in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
             al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
             shared = shared && in.base[i] == in.base[0];
             m.alpha[i] = (float)d.alpha[i < k ? i : 0];
-            m.stream_id[i] = d.stream_id[i < k ? i : 0];
         }
         in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
-        m.key = d.key; m.T = T;
-        m.rescale = d.rescale ? (float)(65536.0 / (double)T) : 1.f;
         m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
         m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
-        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0; m.sign_election = d.sign_election ? 1 : 0;
-        m.out = out; m.delta_out = delta_out; m.kept = rb->kept; m.flags = rb->flags;
-        const size_t noct = (n + 7) / 8;
-        m.chunks = pick_chunks(noct, 256, 2, 8);
-        be.template launch<KDareMerge>(stream_grid(noct, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
+        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0;
+        m.out = out; m.delta_out = delta_out;
+        m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+    }
+    // the call's one synchronisation: fetch the readback and fail on a non-finite delta (flags[0]: one bit per finetune)
+    template <class Readback>
+    int delta_readback(const char* op, int k, const Readback* rb, Readback& host) {
+        be.d2h(&host, rb, sizeof host, stream);
+        if (!be.ok()) { host = Readback{}; return SMHIP_OK; }   // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
+        if (!host.flags[0]) return SMHIP_OK;
+        std::string which;
+        for (int i = 0; i < k; ++i)
+            if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
+        return fail(SMHIP_ERR_NONFINITE, std::string(op) + ": NaN or Inf in finetune - base of finetune " + which);
+    }
+    // the zeroed workspace of a radix select: the three levels' histograms [3][k][HIST1_BINS] | State[states] | Readback
+    static constexpr size_t SELECT_HIST_LEVEL = (size_t)TIES_MAX_MODELS * HIST1_BINS * sizeof(unsigned long long);
+    template <class State, class Readback>
+    int select_workspace(size_t states, State*& state, Readback*& rb) {
+        const size_t off_state = 3 * SELECT_HIST_LEVEL, off_rb = off_state + states * sizeof(State);
+        const size_t ws = off_rb + sizeof(Readback);
+        int rc;
+        if ((rc = ensure(ties_, ws))) return rc;
+        be.memset(ties_.p, 0, ws, stream);
+        state = (State*)((char*)ties_.p + off_state);
+        rb = (Readback*)((char*)ties_.p + off_rb);
+        return SMHIP_OK;
+    }
+    // the three levels of a radix select: hist launches in groups of TIES_GROUP finetunes, then one select launch.
+    // The caller has filled h and s but for level, hist, first, count and h.chunks; hist_bins: LDS bins per finetune and level.
+    template <class KHist, class KSelect, class HistParams, class SelectParams>
+    void select_levels(HistParams& h, SelectParams& s, const int (&hist_bins)[3], size_t select_lds) {
+        const int k = h.in.k;
+        const size_t noct = (h.in.n + 7) / 8;
+        h.chunks = pick_chunks(noct, 256, 4, 5);
+        const int hgrid = stream_grid(noct, 256, h.chunks);
+        for (int level = 1; level <= 3; ++level) {
+            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * SELECT_HIST_LEVEL);
+            h.level = level; h.hist = hist;
+            // (k_keep == 0: the thresholds are +inf whatever the data; level 1 still runs, it finds the non-finite deltas)
+            for (int first = 0; first < k && (level == 1 || s.k_keep > 0); first += TIES_GROUP) {
+                h.first = first; h.count = std::min(TIES_GROUP, k - first);
+                be.template launch<KHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * hist_bins[level - 1]) * 4, h, stream);
+            }
+            s.level = level; s.hist = hist;
+            be.template launch<KSelect>(k, TIES_SELECT_THREADS, select_lds, s, stream);
+        }
+    }
+
+    // ---- TIES merge: one rank per finetune; levels 2 and 3 need only the low bins in LDS ----
+    struct TiesReadback { float threshold[TIES_MAX_MODELS]; unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
+    int ties_merge(const smhip_ties_desc& d, void* out, float* delta_out, smhip_ties_report* rep) {
+        const int k = d.k;
+        const unsigned long long k_keep = delta_k_keep(d.density, d.n);
+        if (rep) {
+            rep->k_keep = k_keep;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) { rep->threshold[i] = 0.f; rep->kept[i] = 0; }
+        }
+        if (d.n == 0) {                                  // k_keep == 0: the threshold is +inf by definition
+            if (rep) for (int i = 0; i < k; ++i) rep->threshold[i] = INFINITY;
+            return SMHIP_OK;
+        }
+        TiesState* state;
+        TiesReadback* rb;
+        int rc;
+        if ((rc = select_workspace(TIES_MAX_MODELS, state, rb))) return rc;
+
+        TiesMergeParams m;
+        delta_merge_params(d, out, delta_out, m);
+        m.threshold = rb->threshold;
+
+        TiesHistParams h;
+        h.in = m.in; h.state = state; h.flags = rb->flags;
+        TiesSelectParams s;
+        s.k_keep = k_keep; s.state = state; s.threshold = rb->threshold; s.kept = rb->kept;
+        select_levels<KTiesHist, KTiesSelect>(h, s, {HIST1_BINS, HIST_LO_BINS, HIST_LO_BINS},
+                                              LDS_SCRATCH_FLOATS * 4 + TIES_SELECT_THREADS * sizeof(unsigned long long));
+        be.template launch<KTiesMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+
+        TiesReadback host;
+        if ((rc = delta_readback("ties_merge", k, rb, host))) return rc;
+        if (rep)
+            for (int i = 0; i < k; ++i) { rep->threshold[i] = host.threshold[i]; rep->kept[i] = host.kept[i]; }
+        return SMHIP_OK;
+    }
+
+    // ---- DARE merge: no select, one kernel; workspace (the TIES buffer, the operators never run at once): DareReadback ----
+    struct DareReadback { unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
+    static uint32_t dare_threshold(double density) {
+        return density == 1.0 ? DARE_T_ONE : (uint32_t)std::floor(density * 65536.0);
+    }
+    int dare_merge(const smhip_dare_desc& d, void* out, float* delta_out, smhip_dare_report* rep) {
+        const int k = d.k;
+        const uint32_t T = dare_threshold(d.density);
+        if (rep) {
+            rep->T = T;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
+        }
+        if (d.n == 0) return SMHIP_OK;
+        int rc;
+        if ((rc = ensure(ties_, sizeof(DareReadback)))) return rc;
+        be.memset(ties_.p, 0, sizeof(DareReadback), stream);
+        DareReadback* rb = (DareReadback*)ties_.p;
+
+        DareMergeParams m;
+        delta_merge_params(d, out, delta_out, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.stream_id[i] = d.stream_id[i < k ? i : 0];
+        m.key = d.key; m.T = T;
+        m.rescale = d.rescale ? (float)(65536.0 / (double)T) : 1.f;
+        m.sign_election = d.sign_election ? 1 : 0;
+        m.kept = rb->kept; m.flags = rb->flags;
+        be.template launch<KDareMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
 
         DareReadback host;
-        be.d2h(&host, rb, sizeof host, stream);          // the call's one synchronisation
-        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP)
-        if (host.flags[0]) {
-            std::string which;
-            for (int i = 0; i < k; ++i)
-                if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
-            return fail(SMHIP_ERR_NONFINITE, "dare_merge: NaN or Inf in finetune - base of finetune " + which);
-        }
+        if ((rc = delta_readback("dare_merge", k, rb, host))) return rc;
         if (rep)
             for (int i = 0; i < k; ++i) rep->kept[i] = host.kept[i];
         return SMHIP_OK;
     }
 
-    // ---- Breadcrumbs merge (sm_breadcrumbs.hpp; the function is stated in shardmerge_hip.h); arguments checked by
-    // smhip_breadcrumbs_merge ----
-    // workspace (the TIES buffer, the operators never run at once): the three levels' histograms [3][k][HIST1_BINS] |
-    // CrumbsState[k][2] | CrumbsReadback
+    // ---- Breadcrumbs merge: two ranks per finetune (CrumbsState[k][2]), found in the same three histogram passes ----
     struct CrumbsReadback {
         float threshold_lo[TIES_MAX_MODELS], threshold_hi[TIES_MAX_MODELS];
         unsigned long long kept[TIES_MAX_MODELS], dropped_top[TIES_MAX_MODELS];
@@ -2495,76 +2500,37 @@ class Pipeline {
     };
     int breadcrumbs_merge(const smhip_breadcrumbs_desc& d, void* out, float* delta_out, smhip_breadcrumbs_report* rep) {
         const int k = d.k;
-        const size_t n = d.n;
-        const unsigned long long k_keep = d.density == 1.0 ? (unsigned long long)n : (unsigned long long)std::floor(d.density * (double)n);
-        const unsigned long long n_top = std::min((unsigned long long)std::floor(d.gamma * (double)n), (unsigned long long)n - k_keep);
+        const unsigned long long k_keep = delta_k_keep(d.density, d.n);
+        const unsigned long long n_top = std::min((unsigned long long)std::floor(d.gamma * (double)d.n), (unsigned long long)d.n - k_keep);
         if (rep) {
             rep->k_keep = k_keep; rep->n_top = n_top;
             for (int i = 0; i < SMHIP_MAX_MODELS; ++i) { rep->threshold_lo[i] = 0.f; rep->threshold_hi[i] = 0.f; rep->kept[i] = 0; rep->dropped_top[i] = 0; }
         }
-        if (n == 0) {                                    // k_keep == 0: the thresholds are +inf by definition
+        if (d.n == 0) {                                  // k_keep == 0: the thresholds are +inf by definition
             if (rep) for (int i = 0; i < k; ++i) { rep->threshold_lo[i] = INFINITY; rep->threshold_hi[i] = INFINITY; }
             return SMHIP_OK;
         }
-        const size_t hist_level = (size_t)TIES_MAX_MODELS * HIST1_BINS * sizeof(unsigned long long);
-        const size_t off_state = 3 * hist_level, off_rb = off_state + 2 * TIES_MAX_MODELS * sizeof(CrumbsState);
-        const size_t ws = off_rb + sizeof(CrumbsReadback);
+        CrumbsState* state;
+        CrumbsReadback* rb;
         int rc;
-        if ((rc = ensure(ties_, ws))) return rc;
-        be.memset(ties_.p, 0, ws, stream);
-        CrumbsState* state = (CrumbsState*)((char*)ties_.p + off_state);
-        CrumbsReadback* rb = (CrumbsReadback*)((char*)ties_.p + off_rb);
+        if ((rc = select_workspace(2 * TIES_MAX_MODELS, state, rb))) return rc;
 
-        TiesInputs in;
-        in.k = k; in.dtype = d.in_dtype; in.n = n;
-        bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
-        for (int i = 0; i < TIES_MAX_MODELS; ++i) {
-            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
-            al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
-            shared = shared && in.base[i] == in.base[0];
-        }
-        in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
-        const size_t noct = (n + 7) / 8;
+        CrumbsMergeParams m;
+        delta_merge_params(d, out, delta_out, m);
+        m.sign_election = d.sign_election ? 1 : 0;
+        m.threshold_lo = rb->threshold_lo; m.threshold_hi = rb->threshold_hi;
 
         CrumbsHistParams h;
-        h.in = in; h.state = state; h.flags = rb->flags;
-        h.chunks = pick_chunks(noct, 256, 4, 5);
-        const int hgrid = stream_grid(noct, 256, h.chunks);
+        h.in = m.in; h.state = state; h.flags = rb->flags;
         CrumbsSelectParams s;
         s.k_keep = k_keep; s.rank[CRUMBS_HI] = n_top + 1; s.rank[CRUMBS_LO] = n_top + k_keep;
         s.state = state; s.threshold_lo = rb->threshold_lo; s.threshold_hi = rb->threshold_hi;
         s.kept = rb->kept; s.dropped_top = rb->dropped_top;
-        for (int level = 1; level <= 3; ++level) {
-            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * hist_level);
-            h.level = level; h.hist = hist;
-            // (k_keep == 0: the thresholds are +inf whatever the data; level 1 still runs, it finds the non-finite deltas)
-            for (int first = 0; first < k && (level == 1 || k_keep > 0); first += TIES_GROUP) {
-                h.first = first; h.count = std::min(TIES_GROUP, k - first);
-                be.template launch<KCrumbsHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * HIST1_BINS) * 4, h, stream);
-            }
-            s.level = level; s.hist = hist;
-            be.template launch<KCrumbsSelect>(k, TIES_SELECT_THREADS, CRUMBS_SELECT_LDS, s, stream);
-        }
-
-        CrumbsMergeParams m;
-        m.in = in;
-        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < k ? i : 0];
-        m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
-        m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
-        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0; m.sign_election = d.sign_election ? 1 : 0;
-        m.threshold_lo = rb->threshold_lo; m.threshold_hi = rb->threshold_hi; m.out = out; m.delta_out = delta_out;
-        m.chunks = pick_chunks(noct, 256, 2, 8);
-        be.template launch<KCrumbsMerge>(stream_grid(noct, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+        select_levels<KCrumbsHist, KCrumbsSelect>(h, s, {HIST1_BINS, HIST1_BINS, HIST1_BINS}, CRUMBS_SELECT_LDS);
+        be.template launch<KCrumbsMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
 
         CrumbsReadback host;
-        be.d2h(&host, rb, sizeof host, stream);          // the call's one synchronisation
-        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP)
-        if (host.flags[0]) {
-            std::string which;
-            for (int i = 0; i < k; ++i)
-                if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
-            return fail(SMHIP_ERR_NONFINITE, "breadcrumbs_merge: NaN or Inf in finetune - base of finetune " + which);
-        }
+        if ((rc = delta_readback("breadcrumbs_merge", k, rb, host))) return rc;
         if (rep)
             for (int i = 0; i < k; ++i) {
                 rep->threshold_lo[i] = host.threshold_lo[i]; rep->threshold_hi[i] = host.threshold_hi[i];

@@ -354,30 +354,26 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- TIES ------------------------------------------------------------------------------
-    def ties_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
-                   base_out: torch.Tensor, density: float = 0.2, lam: float = 1.0, normalize: bool = True,
-                   want_delta: bool = False, layer_name: str = "layer"):
-        """TIES merge of one tensor of any shape (``smhip_ties_merge``; the function is stated in
-        include/shardmerge_hip.h): each delta ``finetune_i - base_i`` trimmed to its ``density`` largest magnitudes
-        (ties at the threshold all kept), weighted by ``alpha_i``, a sign elected per element by the weighted sum, the
-        agreeing entries summed (``normalize``: divided by the sum of their weights), times ``lam``, added onto
-        ``base_out`` in its dtype.  Returns (out, TiesMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta
-        raises ValueError naming ``layer_name`` and the finetune."""
+    # -- the delta merges (TIES, DARE, Breadcrumbs; merge_layer stages its inputs the same way) ---------
+    def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
+                           op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
+        """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
+        in_dtype, base_out, base_out_dtype) and the outputs.  ``op`` names the operator in the check that every
+        finetune has a base and an alpha (merge_layer makes none).  Returns (keep, bo, out, delta): ``keep`` holds the
+        copies alive until the call returns, ``bo`` is base_out on the device, ``out`` is of ``out_dtype`` (default: bo's)."""
         k = len(finetunes)
         if k < 1 or k > _lib.MAX_MODELS:
             raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
-        if len(bases) != k or len(alphas) != k:
-            raise ValueError(f"ties_merge: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
-        if not (0.0 < float(density) <= 1.0):
-            raise ValueError(f"ties_merge: density {density} is not in (0, 1]")
-        # one input dtype per call, mixed dtypes promoted to fp32 (as merge_layer does it)
+        if op is not None and (len(bases) != k or len(alphas) != k):
+            raise ValueError(f"{op}: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
+        # one input dtype per call (the descriptors' in_dtype).  Mixed dtypes are PROMOTED to
+        # fp32, never demoted: the reference upcasts every tensor to fp32 before subtracting
+        # (base.py:128-131), so an fp32 base next to bf16 finetunes must keep its low bits
         dtypes = {t.dtype for t in list(finetunes) + list(bases)}
         in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
         if in_dtype not in _DTYPE_CODE:
             in_dtype = torch.float32
-        keep = []
-        desc = _lib.TiesDesc()
+        keep = []           # keep device copies alive until the call returns
         desc.k = k
         seen: Dict[int, torch.Tensor] = {}
         for i in range(k):
@@ -400,24 +396,40 @@ class Engine:
         desc.in_dtype = _DTYPE_CODE[in_dtype]
         desc.base_out = bo.data_ptr()
         desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
-        desc.n = bo.numel()
-        desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
-        out = torch.empty(bo.shape, dtype=bo_dtype, device=self.device)
+        out = torch.empty(bo.shape, dtype=out_dtype or bo_dtype, device=self.device)
         delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
-        rep = _lib.TiesReport()
+        return keep, bo, out, delta
+
+    def _run_delta_merge(self, fn, desc, rep, out, delta, layer_name: str):
+        """one smhip_*_merge call of the family; a NaN or Inf in a delta becomes the ValueError naming the layer"""
         try:
-            self.ctx.check(self.lib.dll.smhip_ties_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
-                                                         delta.data_ptr() if delta is not None else None,
-                                                         C.byref(rep), self._stream()))
+            self.ctx.check(fn(self.ctx.h, C.byref(desc), out.data_ptr(), delta.data_ptr() if delta is not None else None,
+                              C.byref(rep), self._stream()))
         except SmhipError as e:
             if e.code == _lib.ERR_NONFINITE:
                 raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
             raise
+
+    # -- TIES ------------------------------------------------------------------------------
+    def ties_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                   base_out: torch.Tensor, density: float = 0.2, lam: float = 1.0, normalize: bool = True,
+                   want_delta: bool = False, layer_name: str = "layer"):
+        """TIES merge of one tensor of any shape (``smhip_ties_merge``; the function is stated in
+        include/shardmerge_hip.h): each delta ``finetune_i - base_i`` trimmed to its ``density`` largest magnitudes
+        (ties at the threshold all kept), weighted by ``alpha_i``, a sign elected per element by the weighted sum, the
+        agreeing entries summed (``normalize``: divided by the sum of their weights), times ``lam``, added onto
+        ``base_out`` in its dtype.  Returns (out, TiesMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta
+        raises ValueError naming ``layer_name`` and the finetune."""
+        if not (0.0 < float(density) <= 1.0):
+            raise ValueError(f"ties_merge: density {density} is not in (0, 1]")
+        desc, rep, k = _lib.TiesDesc(), _lib.TiesReport(), len(finetunes)
+        desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "ties_merge")
+        desc.n = bo.numel()
+        self._run_delta_merge(self.lib.dll.smhip_ties_merge, desc, rep, out, delta, layer_name)
         report = TiesMergeReport(k_keep=int(rep.k_keep), thresholds=[float(rep.threshold[i]) for i in range(k)],
                                  kept=[int(rep.kept[i]) for i in range(k)])
-        if want_delta:
-            return out, report, delta
-        return out, report
+        return (out, report, delta) if want_delta else (out, report)
 
     # -- DARE ------------------------------------------------------------------------------
     def dare_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
@@ -434,10 +446,6 @@ class Engine:
         ValueError naming ``layer_name`` and the finetune."""
         layer_name = layer_name or "layer"
         k = len(finetunes)
-        if k < 1 or k > _lib.MAX_MODELS:
-            raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
-        if len(bases) != k or len(alphas) != k:
-            raise ValueError(f"dare_merge: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
         if not (0.0 < float(density) <= 1.0):
             raise ValueError(f"dare_merge: density {density} is not in (0, 1]")
         if float(density) < 2.0 ** -16:
@@ -447,54 +455,15 @@ class Engine:
             raise ValueError(f"dare_merge: stream_ids must be {k} integers in [0, 2^32)")
         if isinstance(key, bool) or not isinstance(key, int) or not (0 <= key < 2 ** 64):
             raise ValueError("dare_merge: key must be an integer in [0, 2^64)")
-        # one input dtype per call, mixed dtypes promoted to fp32 (as merge_layer does it)
-        dtypes = {t.dtype for t in list(finetunes) + list(bases)}
-        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
-        if in_dtype not in _DTYPE_CODE:
-            in_dtype = torch.float32
-        keep = []
-        desc = _lib.DareDesc()
-        desc.k = k
-        seen: Dict[int, torch.Tensor] = {}
-        for i in range(k):
-            ft = self._dev(finetunes[i], in_dtype)
-            bkey = id(bases[i])
-            if bkey not in seen:
-                seen[bkey] = self._dev(bases[i], in_dtype)
-            bs = seen[bkey]
-            if ft.shape != base_out.shape or bs.shape != base_out.shape:
-                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
-            keep += [ft, bs]
-            desc.finetune[i] = ft.data_ptr()
-            desc.base[i] = bs.data_ptr()
-            desc.alpha[i] = float(alphas[i])
-            desc.stream_id[i] = stream_ids[i]
-        bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
-        bo = seen.get(id(base_out))
-        if bo is None or bo.dtype != bo_dtype:
-            bo = self._dev(base_out, bo_dtype)
-        keep.append(bo)
-        desc.in_dtype = _DTYPE_CODE[in_dtype]
-        desc.base_out = bo.data_ptr()
-        desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
-        desc.n = bo.numel()
+        desc, rep = _lib.DareDesc(), _lib.DareReport()
         desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
         desc.key, desc.rescale, desc.sign_election = key, 1 if rescale else 0, 1 if sign_election else 0
-        out = torch.empty(bo.shape, dtype=bo_dtype, device=self.device)
-        delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
-        rep = _lib.DareReport()
-        try:
-            self.ctx.check(self.lib.dll.smhip_dare_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
-                                                         delta.data_ptr() if delta is not None else None,
-                                                         C.byref(rep), self._stream()))
-        except SmhipError as e:
-            if e.code == _lib.ERR_NONFINITE:
-                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
-            raise
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "dare_merge")
+        desc.n = bo.numel()
+        desc.stream_id[:k] = stream_ids
+        self._run_delta_merge(self.lib.dll.smhip_dare_merge, desc, rep, out, delta, layer_name)
         report = DareMergeReport(threshold=int(rep.T), density=int(rep.T) / 65536.0, kept=[int(rep.kept[i]) for i in range(k)])
-        if want_delta:
-            return out, report, delta
-        return out, report
+        return (out, report, delta) if want_delta else (out, report)
 
     # -- Model Breadcrumbs ---------------------------------------------------------------
     def breadcrumbs_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
@@ -509,68 +478,24 @@ class Engine:
         (out, BreadcrumbsMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta raises ValueError naming
         ``layer_name`` and the finetune."""
         layer_name = layer_name or "layer"
-        k = len(finetunes)
-        if k < 1 or k > _lib.MAX_MODELS:
-            raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
-        if len(bases) != k or len(alphas) != k:
-            raise ValueError(f"breadcrumbs_merge: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
         if not (0.0 < float(density) <= 1.0):
             raise ValueError(f"breadcrumbs_merge: density {density} is not in (0, 1]")
         if not (0.0 <= float(gamma) < 1.0):
             raise ValueError(f"breadcrumbs_merge: gamma {gamma} is not in [0, 1)")
         if not (float(density) + float(gamma) <= 1.0):
             raise ValueError(f"breadcrumbs_merge: density {density} + gamma {gamma} exceeds 1")
-        # one input dtype per call, mixed dtypes promoted to fp32 (as merge_layer does it)
-        dtypes = {t.dtype for t in list(finetunes) + list(bases)}
-        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
-        if in_dtype not in _DTYPE_CODE:
-            in_dtype = torch.float32
-        keep = []
-        desc = _lib.BreadcrumbsDesc()
-        desc.k = k
-        seen: Dict[int, torch.Tensor] = {}
-        for i in range(k):
-            ft = self._dev(finetunes[i], in_dtype)
-            bkey = id(bases[i])
-            if bkey not in seen:
-                seen[bkey] = self._dev(bases[i], in_dtype)
-            bs = seen[bkey]
-            if ft.shape != base_out.shape or bs.shape != base_out.shape:
-                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
-            keep += [ft, bs]
-            desc.finetune[i] = ft.data_ptr()
-            desc.base[i] = bs.data_ptr()
-            desc.alpha[i] = float(alphas[i])
-        bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
-        bo = seen.get(id(base_out))
-        if bo is None or bo.dtype != bo_dtype:
-            bo = self._dev(base_out, bo_dtype)
-        keep.append(bo)
-        desc.in_dtype = _DTYPE_CODE[in_dtype]
-        desc.base_out = bo.data_ptr()
-        desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
-        desc.n = bo.numel()
+        desc, rep, k = _lib.BreadcrumbsDesc(), _lib.BreadcrumbsReport(), len(finetunes)
         desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
         desc.gamma, desc.sign_election = float(gamma), 1 if sign_election else 0
-        out = torch.empty(bo.shape, dtype=bo_dtype, device=self.device)
-        delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
-        rep = _lib.BreadcrumbsReport()
-        try:
-            self.ctx.check(self.lib.dll.smhip_breadcrumbs_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
-                                                                delta.data_ptr() if delta is not None else None,
-                                                                C.byref(rep), self._stream()))
-        except SmhipError as e:
-            if e.code == _lib.ERR_NONFINITE:
-                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
-            raise
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "breadcrumbs_merge")
+        desc.n = bo.numel()
+        self._run_delta_merge(self.lib.dll.smhip_breadcrumbs_merge, desc, rep, out, delta, layer_name)
         report = BreadcrumbsMergeReport(k_keep=int(rep.k_keep), n_top=int(rep.n_top),
                                         thresholds_lo=[float(rep.threshold_lo[i]) for i in range(k)],
                                         thresholds_hi=[float(rep.threshold_hi[i]) for i in range(k)],
                                         kept=[int(rep.kept[i]) for i in range(k)],
                                         dropped_top=[int(rep.dropped_top[i]) for i in range(k)])
-        if want_delta:
-            return out, report, delta
-        return out, report
+        return (out, report, delta) if want_delta else (out, report)
 
     def correlate_pairs(self, tensors) -> torch.Tensor:
         """K x K matrix of mean column-wise cosine similarities (reference functions.py:304-314);
@@ -593,41 +518,10 @@ class Engine:
                     base_out: torch.Tensor, target_norm_offset: float = 1e-10, cull_start_pct: float = 0.20,
                     cutoff_pct: float = 0.08, t_sum: float = 1.0, want_delta: bool = False,
                     layer_name: str = "layer", b: float = 0.1, norm_mode: Optional[str] = None):
-        k = len(finetunes)
-        if k < 1 or k > _lib.MAX_MODELS:
-            raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
-        # one input dtype per call (smhip_layer_desc.in_dtype).  Mixed dtypes are PROMOTED to
-        # fp32, never demoted: the reference upcasts every tensor to fp32 before subtracting
-        # (base.py:128-131), so an fp32 base next to bf16 finetunes must keep its low bits
-        dtypes = {t.dtype for t in list(finetunes) + list(bases)}
-        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
-        if in_dtype not in _DTYPE_CODE:
-            in_dtype = torch.float32
-        keep = []           # keep device copies alive until the call returns
-        desc = LayerDesc()
-        desc.k = k
-        seen: Dict[int, torch.Tensor] = {}
-        for i in range(k):
-            ft = self._dev(finetunes[i], in_dtype)
-            bkey = id(bases[i])
-            if bkey not in seen:
-                seen[bkey] = self._dev(bases[i], in_dtype)
-            bs = seen[bkey]
-            if ft.shape != base_out.shape or bs.shape != base_out.shape:
-                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
-            keep += [ft, bs]
-            desc.finetune[i] = ft.data_ptr()
-            desc.base[i] = bs.data_ptr()
-            desc.alpha[i] = float(alphas[i])
-        bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
-        bo = seen.get(id(base_out))
-        if bo is None or bo.dtype != bo_dtype:
-            bo = self._dev(base_out, bo_dtype)
-        keep.append(bo)
+        desc, k = LayerDesc(), len(finetunes)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta,
+                                                       out_dtype=torch.bfloat16)
         nb, r, c = _shape3d(bo)
-        desc.in_dtype = _DTYPE_CODE[in_dtype]
-        desc.base_out = bo.data_ptr()
-        desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
         desc.rows, desc.cols = r, c
         desc.target_norm_offset = float(target_norm_offset)
         desc.cull_start_pct = float(cull_start_pct)
@@ -640,8 +534,6 @@ class Engine:
             raise ValueError(f"norm_mode {norm_mode!r}: 'exact' or 'reference_cpu'")
         desc.norm_mode = 1 if norm_mode == "reference_cpu" else 0
         desc.batch = nb
-        out = torch.empty(bo.shape, dtype=torch.bfloat16, device=self.device)
-        delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
         rep = LayerReport()
         self._call(self.lib.dll.smhip_merge_layer(self.ctx.h, C.byref(desc), out.data_ptr(),
                                                   delta.data_ptr() if delta is not None else None,

@@ -1,33 +1,23 @@
 """Merge operators behind the reference's MergeTensorsBase interface."""
+from importlib import import_module
+
+# merge_options.operator -> (module, class); the module is imported when the operator is asked for
+_OPERATOR_CLASSES = {
+    "fourier": ("fast_fourier", "FourierMerge"),
+    "addition": ("addition", "AdditionMerge"),
+    "task_addition": ("taskaddition", "TaskAdditionMerge"),
+    "fourier_legacy": ("fourier_legacy", "LegacyFourierMerge"),
+    "ties": ("ties", "TiesMerge"),
+    "dare_ties": ("dare", "DareTiesMerge"),
+    "dare_linear": ("dare", "DareLinearMerge"),
+    "breadcrumbs": ("breadcrumbs", "BreadcrumbsMerge"),
+    "breadcrumbs_ties": ("breadcrumbs", "BreadcrumbsTiesMerge"),
+}
 
 
 def operator_class(name: str = "fourier"):
     """merge_options.operator -> class (the reference CLI hard-wires FourierMerge, __main__.py:22,67)."""
-    if name == "fourier":
-        from .fast_fourier import FourierMerge
-        return FourierMerge
-    if name == "addition":
-        from .addition import AdditionMerge
-        return AdditionMerge
-    if name == "task_addition":
-        from .taskaddition import TaskAdditionMerge
-        return TaskAdditionMerge
-    if name == "fourier_legacy":
-        from .fourier_legacy import LegacyFourierMerge
-        return LegacyFourierMerge
-    if name == "ties":
-        from .ties import TiesMerge
-        return TiesMerge
-    if name == "dare_ties":
-        from .dare import DareTiesMerge
-        return DareTiesMerge
-    if name == "dare_linear":
-        from .dare import DareLinearMerge
-        return DareLinearMerge
-    if name == "breadcrumbs":
-        from .breadcrumbs import BreadcrumbsMerge
-        return BreadcrumbsMerge
-    if name == "breadcrumbs_ties":
-        from .breadcrumbs import BreadcrumbsTiesMerge
-        return BreadcrumbsTiesMerge
-    raise ValueError(f"unknown merge operator {name!r}")
+    if name not in _OPERATOR_CLASSES:
+        raise ValueError(f"unknown merge operator {name!r}")
+    module, cls = _OPERATOR_CLASSES[name]
+    return getattr(import_module(f".{module}", __name__), cls)

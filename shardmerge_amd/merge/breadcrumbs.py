@@ -22,32 +22,17 @@ class BreadcrumbsMerge(TiesMerge):
     sign_election = False
     mode = "breadcrumbs"
 
-    def __init__(self, config, index_manager=None, engine=None, **kwargs):
-        self.gamma = BREADCRUMBS_OPTION_DEFAULTS["gamma"]
-        self.breadcrumbs_lambda = BREADCRUMBS_OPTION_DEFAULTS["breadcrumbs_lambda"]
-        self.breadcrumbs_normalize = BREADCRUMBS_OPTION_DEFAULTS["breadcrumbs_normalize"]
-        super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)     # (sets the YAML overrides)
-        if "density" not in (getattr(config, "merge_options", None) or {}):
-            self.density = BREADCRUMBS_OPTION_DEFAULTS["density"]                            # (not TIES's 0.2)
+    option_defaults = BREADCRUMBS_OPTION_DEFAULTS                # (density 0.9, not TIES's 0.2; TIES's passes over the tensor)
 
     def get_readme(self) -> str:
-        models = "\n".join(f"- {m.model} (vs {m.base}, weight {m.alpha})" for m in self.config.finetune_merge)
-        how = "elect sign, merge the agreeing entries" if self.sign_election else "add the weighted deltas"
-        norm = ("normalized by the agreeing weights" if self.sign_election else "normalized by the sum of the weights") \
-            if self.breadcrumbs_normalize else "plain sum"
-        return (f"# Breadcrumbs Merged Model\nBase: {self.config.output_base_model}\n"
-                f"Method: Model Breadcrumbs ({self.mode}: drop the largest and the smallest magnitudes, {how}), "
-                f"density {self.density:g}, gamma {self.gamma:g}, lambda {self.breadcrumbs_lambda:g}, {norm}\n"
-                f"Models merged:\n{models}\n")
+        how, norm = self._how_and_norm(self.breadcrumbs_normalize)
+        return self._readme("Breadcrumbs", f"Model Breadcrumbs ({self.mode}: drop the largest and the smallest magnitudes, {how}), "
+                                           f"density {self.density:g}, gamma {self.gamma:g}, lambda {self.breadcrumbs_lambda:g}, {norm}")
 
     def merge_block(self, eng, fts, bases, alphas, base_out, name: str):
         return eng.breadcrumbs_merge(fts, bases, alphas, base_out, density=self.density, gamma=self.gamma,
                                      lam=self.breadcrumbs_lambda, normalize=bool(self.breadcrumbs_normalize),
                                      sign_election=self.sign_election, layer_name=name)
-
-    def block_cost_ms(self, shape, k: int) -> float:
-        """the partitioned path's cost model: TIES's (the same tensor passes)"""
-        return TiesMerge.block_cost_ms(self, shape, k)
 
     def _log_block(self, name: str, k: int, report):
         logger.info(f"Merged {name}: {k} model(s), Breadcrumbs ({self.mode}) kept {report.kept} of {report.k_keep} asked, "

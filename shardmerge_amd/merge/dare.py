@@ -37,23 +37,18 @@ class DareTiesMerge(TiesMerge):
     sign_election = True
     mode = "dare_ties"
 
+    option_defaults = DARE_OPTION_DEFAULTS
+
     def __init__(self, config, index_manager=None, engine=None, **kwargs):
-        self.dare_lambda = DARE_OPTION_DEFAULTS["dare_lambda"]
-        self.dare_normalize = DARE_OPTION_DEFAULTS["dare_normalize"]
-        self.dare_rescale = DARE_OPTION_DEFAULTS["dare_rescale"]
-        super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)     # (sets the YAML overrides, as floats)
+        super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)
         self.seed = int((getattr(config, "merge_options", None) or {}).get("seed", DARE_OPTION_DEFAULTS["seed"]))   # exactly
 
     def get_readme(self) -> str:
-        models = "\n".join(f"- {m.model} (vs {m.base}, weight {m.alpha})" for m in self.config.finetune_merge)
         T = effective_threshold(self.density)
-        how = "elect sign, merge the agreeing entries" if self.sign_election else "add the weighted deltas"
-        norm = ("normalized by the agreeing weights" if self.sign_election else "normalized by the sum of the weights") \
-            if self.dare_normalize else "plain sum"
-        return (f"# DARE Merged Model\nBase: {self.config.output_base_model}\n"
-                f"Method: DARE ({self.mode}: drop at random, {'rescale' if self.dare_rescale else 'no rescale'}, {how}), "
-                f"density {self.density:g} (effective {T}/65536 = {T / 65536.0:.6g}), lambda {self.dare_lambda:g}, seed {self.seed}, {norm}\n"
-                f"Models merged:\n{models}\n")
+        how, norm = self._how_and_norm(self.dare_normalize)
+        return self._readme("DARE", f"DARE ({self.mode}: drop at random, {'rescale' if self.dare_rescale else 'no rescale'}, {how}), "
+                                    f"density {self.density:g} (effective {T}/65536 = {T / 65536.0:.6g}), lambda {self.dare_lambda:g}, "
+                                    f"seed {self.seed}, {norm}")
 
     def stream_ids(self, name: str, k: int):
         """positions in config.finetune_merge of the entries that cover the tensor's layer: the mask's streams"""
@@ -69,12 +64,8 @@ class DareTiesMerge(TiesMerge):
                               sign_election=self.sign_election, key=tensor_key(self.seed, name),
                               stream_ids=self.stream_ids(name, len(fts)), layer_name=name)
 
-    def block_cost_ms(self, shape, k: int) -> float:
-        """the partitioned path's cost model: (k + 2) streaming passes over the tensor"""
-        numel = 1
-        for d in shape:
-            numel *= int(d)
-        return 0.02 + 2.0 * numel * (k + 2) / 4.0e9
+    def tensor_passes(self, k: int) -> int:
+        return k + 2
 
     def _log_block(self, name: str, k: int, report):
         logger.info(f"Merged {name}: {k} model(s), DARE ({self.mode}) kept {report.kept} at effective density "

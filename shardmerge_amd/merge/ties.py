@@ -10,6 +10,7 @@ takes every shape and rank."""
 from __future__ import annotations
 
 import logging
+import math
 
 from ..config import TIES_OPTION_DEFAULTS
 from .base import MergeTensorsBase
@@ -19,32 +20,43 @@ logger = logging.getLogger(__name__)
 
 
 class TiesMerge(FourierMerge):
+    """Also the base of the other delta-merge operators (dare.py, breadcrumbs.py): they name their option_defaults and
+    tensor_passes and state their own readme method line, merge_block and log line."""
+    option_defaults = TIES_OPTION_DEFAULTS
+
     def __init__(self, config, index_manager=None, engine=None, **kwargs):
-        self.density = TIES_OPTION_DEFAULTS["density"]
-        self.ties_lambda = TIES_OPTION_DEFAULTS["ties_lambda"]
-        self.ties_normalize = TIES_OPTION_DEFAULTS["ties_normalize"]
-        super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)     # (sets the YAML overrides)
+        for key, value in {**TIES_OPTION_DEFAULTS, **self.option_defaults}.items():
+            setattr(self, key, value)
+        super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)     # (sets the YAML overrides, as floats)
 
     async def initialize(self):
         await MergeTensorsBase.initialize(self)          # no transform lengths to check
 
-    def get_readme(self) -> str:
+    def _readme(self, title: str, method: str) -> str:
         models = "\n".join(f"- {m.model} (vs {m.base}, weight {m.alpha})" for m in self.config.finetune_merge)
-        return (f"# TIES Merged Model\nBase: {self.config.output_base_model}\n"
-                f"Method: TIES (trim, elect sign, merge), density {self.density:g}, lambda {self.ties_lambda:g}, "
-                f"{'normalized by the agreeing weights' if self.ties_normalize else 'plain sum'}\n"
-                f"Models merged:\n{models}\n")
+        return f"# {title} Merged Model\nBase: {self.config.output_base_model}\nMethod: {method}\nModels merged:\n{models}\n"
+
+    def _how_and_norm(self, normalize):
+        """the readme's words for sign_election and a normalize option (operators with the two modes)"""
+        how = "elect sign, merge the agreeing entries" if self.sign_election else "add the weighted deltas"
+        norm = ("normalized by the agreeing weights" if self.sign_election else "normalized by the sum of the weights") \
+            if normalize else "plain sum"
+        return how, norm
+
+    def get_readme(self) -> str:
+        return self._readme("TIES", f"TIES (trim, elect sign, merge), density {self.density:g}, lambda {self.ties_lambda:g}, "
+                                    f"{'normalized by the agreeing weights' if self.ties_normalize else 'plain sum'}")
 
     def merge_block(self, eng, fts, bases, alphas, base_out, name: str):
         return eng.ties_merge(fts, bases, alphas, base_out, density=self.density, lam=self.ties_lambda,
                               normalize=bool(self.ties_normalize), layer_name=name)
 
+    def tensor_passes(self, k: int) -> int:
+        return 2 * k + 3
+
     def block_cost_ms(self, shape, k: int) -> float:
-        """the partitioned path's cost model: (2k + 3) streaming passes over the tensor"""
-        numel = 1
-        for d in shape:
-            numel *= int(d)
-        return 0.02 + 2.0 * numel * (2 * k + 3) / 4.0e9
+        """the partitioned path's cost model: tensor_passes(k) streaming passes over the tensor"""
+        return 0.02 + 2.0 * math.prod(int(d) for d in shape) * self.tensor_passes(k) / 4.0e9
 
     def _log_block(self, name: str, k: int, report):
         logger.info(f"Merged {name}: {k} model(s), TIES kept {report.kept} of {report.k_keep} asked, thresholds "

@@ -22,34 +22,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 
-DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
-HBM_PEAK_GBPS = 8000.0
-
-
-def window(fn, reps: int) -> float:
-    """mean ms per call over `reps` back-to-back calls"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def alternate(contenders, seconds: float, rounds: int, warmup: int = 5):
-    """{name: [ms per round]}: every round times each contender once, in turn"""
-    reps = {}
-    for name, fn in contenders.items():
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        reps[name] = max(10, int(seconds * 1e3 / rounds / max(window(fn, 3), 1e-3)))
-    times = {name: [] for name in contenders}
-    for _ in range(rounds):
-        for name, fn in contenders.items():
-            times[name].append(window(fn, reps[name]))
-    return times
+from delta_bench_common import ALPHAS as alphas, DT, HBM_PEAK_GBPS, alternate, append_lines, cases
 
 
 def main():
@@ -70,53 +43,38 @@ def main():
     from shardmerge_amd.engine import get_engine
     eng = get_engine("cuda:0")
     dev = eng.device
-    g = torch.Generator(device=dev).manual_seed(0)
-    dtype = DT[args.dtype]
-    alphas = [0.5, 0.3, 0.4, 0.25, 0.6, 0.1, 0.35, 0.45, 0.2, 0.15, 0.55, 0.05, 0.7, 0.3, 0.5, 0.4]
     lines = []
-    for shape in args.shapes.split(","):
-        rows, cols = (int(v) for v in shape.split("x"))
-        base = (torch.randn(rows, cols, generator=g, device=dev) * 0.02).to(dtype)
-        for k in (int(v) for v in args.ks.split(",")):
-            fts = [(base.float() + torch.randn(rows, cols, generator=g, device=dev) * 3e-3).to(dtype) for _ in range(k)]
-            bases = [base] * k
-            nbytes = (2 * k + 3) * base.numel() * base.element_size()
-            blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-            crumbs = lambda se: (lambda: eng.breadcrumbs_merge(fts, bases, alphas[:k], base, density=args.density, gamma=args.gamma,
-                                                               sign_election=se))
-            contenders = {"breadcrumbs_ties": crumbs(True), "breadcrumbs": crumbs(False),
-                          "ties": lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density),
-                          "clone": lambda: blob.clone()}
-            times = alternate(contenders, args.seconds, args.rounds)
-            _, rep = eng.breadcrumbs_merge(fts, bases, alphas[:k], base, density=args.density, gamma=args.gamma, sign_election=True)
-            rec = {"breadcrumbs_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "density": args.density, "gamma": args.gamma,
-                   "kept_share": [round(c / base.numel(), 6) for c in rep.kept],
-                   "dropped_top_share": [round(c / base.numel(), 6) for c in rep.dropped_top],
-                   "bytes": nbytes, "rounds": args.rounds}
-            med = {name: statistics.median(t) for name, t in times.items()}
-            for name, t in times.items():
-                rec[f"{name}_ms"] = round(med[name], 4)
-                rec[f"{name}_spread_ms"] = round(max(t) - min(t), 4)
-                rec[f"{name}_rounds_ms"] = [round(v, 4) for v in t]
-            for mode in ("breadcrumbs_ties", "breadcrumbs"):
-                rec[f"{mode}_GBps"] = round(nbytes / med[mode] / 1e6, 1)
-                rec[f"{mode}_share_of_8TBps"] = round(nbytes / med[mode] / 1e6 / HBM_PEAK_GBPS, 3)
-                rec[f"{mode}_ratio_to_clone"] = round(med[mode] / med["clone"], 3)
-                rec[f"{mode}_ratio_to_ties"] = round(med[mode] / med["ties"], 4)
-            bound = med["ties"] + 2.0 * (max(times["ties"]) - min(times["ties"]))
-            rec["acceptance_bound_ms"] = round(bound, 4)
-            rec["within_ties_noise"] = bool(med["breadcrumbs_ties"] <= bound)
-            print(json.dumps(rec), flush=True)
-            lines.append(rec)
-            del fts, blob
-            torch.cuda.empty_cache()
-        del base
-        torch.cuda.empty_cache()
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        with open(args.out, "a") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+    for rows, cols, k, base, fts, bases in cases(args.shapes, args.ks, DT[args.dtype], dev):
+        nbytes = (2 * k + 3) * base.numel() * base.element_size()
+        blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+        crumbs = lambda se: (lambda: eng.breadcrumbs_merge(fts, bases, alphas[:k], base, density=args.density, gamma=args.gamma,
+                                                           sign_election=se))
+        contenders = {"breadcrumbs_ties": crumbs(True), "breadcrumbs": crumbs(False),
+                      "ties": lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density),
+                      "clone": lambda: blob.clone()}
+        times = alternate(contenders, args.seconds, args.rounds)
+        _, rep = eng.breadcrumbs_merge(fts, bases, alphas[:k], base, density=args.density, gamma=args.gamma, sign_election=True)
+        rec = {"breadcrumbs_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "density": args.density, "gamma": args.gamma,
+               "kept_share": [round(c / base.numel(), 6) for c in rep.kept],
+               "dropped_top_share": [round(c / base.numel(), 6) for c in rep.dropped_top],
+               "bytes": nbytes, "rounds": args.rounds}
+        med = {name: statistics.median(t) for name, t in times.items()}
+        for name, t in times.items():
+            rec[f"{name}_ms"] = round(med[name], 4)
+            rec[f"{name}_spread_ms"] = round(max(t) - min(t), 4)
+            rec[f"{name}_rounds_ms"] = [round(v, 4) for v in t]
+        for mode in ("breadcrumbs_ties", "breadcrumbs"):
+            rec[f"{mode}_GBps"] = round(nbytes / med[mode] / 1e6, 1)
+            rec[f"{mode}_share_of_8TBps"] = round(nbytes / med[mode] / 1e6 / HBM_PEAK_GBPS, 3)
+            rec[f"{mode}_ratio_to_clone"] = round(med[mode] / med["clone"], 3)
+            rec[f"{mode}_ratio_to_ties"] = round(med[mode] / med["ties"], 4)
+        bound = med["ties"] + 2.0 * (max(times["ties"]) - min(times["ties"]))
+        rec["acceptance_bound_ms"] = round(bound, 4)
+        rec["within_ties_noise"] = bool(med["breadcrumbs_ties"] <= bound)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        del blob
+    append_lines(lines, args.out)
     if not all(rec["within_ties_noise"] for rec in lines):
         sys.exit("breadcrumbs_ties took longer than ties plus twice the spread of ties in at least one case")
 

@@ -22,34 +22,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 
-DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
-HBM_PEAK_GBPS = 8000.0
-
-
-def window(fn, reps: int) -> float:
-    """mean ms per call over `reps` back-to-back calls"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def alternate(contenders, seconds: float, rounds: int, warmup: int = 5):
-    """{name: (median ms, spread)}: every round times each contender once, in turn"""
-    reps = {}
-    for name, fn in contenders.items():
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        reps[name] = max(10, int(seconds * 1e3 / rounds / max(window(fn, 3), 1e-3)))
-    times = {name: [] for name in contenders}
-    for _ in range(rounds):
-        for name, fn in contenders.items():
-            times[name].append(window(fn, reps[name]))
-    return {name: (statistics.median(t), (max(t) - min(t)) / statistics.median(t)) for name, t in times.items()}
+from delta_bench_common import ALPHAS as alphas, DT, HBM_PEAK_GBPS, alternate, append_lines, cases
 
 
 def main():
@@ -72,54 +45,40 @@ def main():
     if args.ab_lib:
         from shardmerge_amd._lib import SmhipLibrary
         variant = Engine(lib=SmhipLibrary(Path(args.ab_lib)), device=dev)
-    g = torch.Generator(device=dev).manual_seed(0)
-    dtype = DT[args.dtype]
-    alphas = [0.5, 0.3, 0.4, 0.25, 0.6, 0.1, 0.35, 0.45, 0.2, 0.15, 0.55, 0.05, 0.7, 0.3, 0.5, 0.4]
     key = 0x0123456789ABCDEF
     lines = []
-    for shape in args.shapes.split(","):
-        rows, cols = (int(v) for v in shape.split("x"))
-        base = (torch.randn(rows, cols, generator=g, device=dev) * 0.02).to(dtype)
-        for k in (int(v) for v in args.ks.split(",")):
-            fts = [(base.float() + torch.randn(rows, cols, generator=g, device=dev) * 3e-3).to(dtype) for _ in range(k)]
-            bases = [base] * k
-            nbytes = (k + 2) * base.numel() * base.element_size()
-            blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-            dare = lambda e, se: (lambda: e.dare_merge(fts, bases, alphas[:k], base, density=args.density, sign_election=se, key=key))
-            contenders = {"dare_ties": dare(eng, True), "dare_linear": dare(eng, False),
-                          "ties": lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density),
-                          "clone": lambda: blob.clone()}
+    for rows, cols, k, base, fts, bases in cases(args.shapes, args.ks, DT[args.dtype], dev):
+        nbytes = (k + 2) * base.numel() * base.element_size()
+        blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+        dare = lambda e, se: (lambda: e.dare_merge(fts, bases, alphas[:k], base, density=args.density, sign_election=se, key=key))
+        contenders = {"dare_ties": dare(eng, True), "dare_linear": dare(eng, False),
+                      "ties": lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density),
+                      "clone": lambda: blob.clone()}
+        if variant is not None:
+            contenders["dare_ties_no_philox"] = dare(variant, True)
+            contenders["dare_linear_no_philox"] = dare(variant, False)
+        res = {name: (statistics.median(t), (max(t) - min(t)) / statistics.median(t))
+               for name, t in alternate(contenders, args.seconds, args.rounds).items()}
+        _, rep = eng.dare_merge(fts, bases, alphas[:k], base, density=args.density, key=key)
+        rec = {"dare_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "density": args.density,
+               "effective_density": rep.density, "kept_share": [round(c / base.numel(), 6) for c in rep.kept],
+               "bytes": nbytes, "rounds": args.rounds}
+        for name, (ms, spread) in res.items():
+            rec[f"{name}_ms"] = round(ms, 4)
+            rec[f"{name}_spread"] = round(spread, 4)
+        for mode in ("dare_ties", "dare_linear"):
+            ms = res[mode][0]
+            rec[f"{mode}_GBps"] = round(nbytes / ms / 1e6, 1)
+            rec[f"{mode}_share_of_8TBps"] = round(nbytes / ms / 1e6 / HBM_PEAK_GBPS, 3)
+            rec[f"{mode}_ratio_to_clone"] = round(ms / res["clone"][0], 3)
+            rec[f"{mode}_speedup_over_ties"] = round(res["ties"][0] / ms, 2)
             if variant is not None:
-                contenders["dare_ties_no_philox"] = dare(variant, True)
-                contenders["dare_linear_no_philox"] = dare(variant, False)
-            res = alternate(contenders, args.seconds, args.rounds)
-            _, rep = eng.dare_merge(fts, bases, alphas[:k], base, density=args.density, key=key)
-            rec = {"dare_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "density": args.density,
-                   "effective_density": rep.density, "kept_share": [round(c / base.numel(), 6) for c in rep.kept],
-                   "bytes": nbytes, "rounds": args.rounds}
-            for name, (ms, spread) in res.items():
-                rec[f"{name}_ms"] = round(ms, 4)
-                rec[f"{name}_spread"] = round(spread, 4)
-            for mode in ("dare_ties", "dare_linear"):
-                ms = res[mode][0]
-                rec[f"{mode}_GBps"] = round(nbytes / ms / 1e6, 1)
-                rec[f"{mode}_share_of_8TBps"] = round(nbytes / ms / 1e6 / HBM_PEAK_GBPS, 3)
-                rec[f"{mode}_ratio_to_clone"] = round(ms / res["clone"][0], 3)
-                rec[f"{mode}_speedup_over_ties"] = round(res["ties"][0] / ms, 2)
-                if variant is not None:
-                    rec[f"{mode}_philox_cost"] = round(ms / res[f"{mode}_no_philox"][0] - 1.0, 4)
-            rec["faster_than_ties"] = bool(max(res["dare_ties"][0], res["dare_linear"][0]) < res["ties"][0])
-            print(json.dumps(rec), flush=True)
-            lines.append(rec)
-            del fts, blob
-            torch.cuda.empty_cache()
-        del base
-        torch.cuda.empty_cache()
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        with open(args.out, "a") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+                rec[f"{mode}_philox_cost"] = round(ms / res[f"{mode}_no_philox"][0] - 1.0, 4)
+        rec["faster_than_ties"] = bool(max(res["dare_ties"][0], res["dare_linear"][0]) < res["ties"][0])
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        del blob
+    append_lines(lines, args.out)
     if not all(rec["faster_than_ties"] for rec in lines):
         sys.exit("dare_merge was not faster than ties_merge in at least one case")
 

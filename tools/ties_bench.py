@@ -18,8 +18,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 
-DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
-HBM_PEAK_GBPS = 8000.0
+from delta_bench_common import ALPHAS as alphas, DT, HBM_PEAK_GBPS, append_lines, cases
 
 
 def timed(fn, seconds: float, warmup: int = 5, min_reps: int = 10) -> float:
@@ -84,47 +83,31 @@ def main():
     from shardmerge_amd.engine import get_engine
     eng = get_engine("cuda:0")
     dev = eng.device
-    g = torch.Generator(device=dev).manual_seed(0)
-    dtype = DT[args.dtype]
-    alphas = [0.5, 0.3, 0.4, 0.25, 0.6, 0.1, 0.35, 0.45, 0.2, 0.15, 0.55, 0.05, 0.7, 0.3, 0.5, 0.4]
     lines = []
-    for shape in args.shapes.split(","):
-        rows, cols = (int(v) for v in shape.split("x"))
-        base = (torch.randn(rows, cols, generator=g, device=dev) * 0.02).to(dtype)
-        for k in (int(v) for v in args.ks.split(",")):
-            fts = [(base.float() + torch.randn(rows, cols, generator=g, device=dev) * 3e-3).to(dtype) for _ in range(k)]
-            bases = [base] * k
-            nbytes = (2 * k + 3) * base.numel() * base.element_size()
-            ms = timed(lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density), args.seconds)
-            eng.ctx.profile(True)
-            eng.ctx.profile_reset()
-            _, rep = eng.ties_merge(fts, bases, alphas[:k], base, density=args.density)
-            table = eng.ctx.profile_table()
-            eng.ctx.profile(False)
-            blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-            clone_ms = timed(lambda: blob.clone(), args.seconds)
-            del blob
-            how = torch_ties(fts, base, alphas[:k], args.density, 1.0, True)[1]
-            torch_ms = timed(lambda: torch_ties(fts, base, alphas[:k], args.density, 1.0, True), args.seconds, warmup=1, min_reps=3)
-            rec = {"ties_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "density": args.density,
-                   "ms": round(ms, 4), "GBps": round(nbytes / ms / 1e6, 1), "share_of_8TBps": round(nbytes / ms / 1e6 / HBM_PEAK_GBPS, 3),
-                   "kernel_ms": {n: round(v[1], 4) for n, v in sorted(table.items())},
-                   "kept_over_asked": [round(c / max(rep.k_keep, 1), 4) for c in rep.kept],
-                   "clone_ms": round(clone_ms, 4), "clone_GBps": round(nbytes / clone_ms / 1e6, 1),
-                   "ratio_to_clone": round(ms / clone_ms, 3),
-                   "torch_ms": round(torch_ms, 3), "torch_select": how, "speedup_over_torch": round(torch_ms / ms, 2),
-                   "faster_than_torch": bool(ms < torch_ms)}
-            print(json.dumps(rec), flush=True)
-            lines.append(rec)
-            del fts
-            torch.cuda.empty_cache()
-        del base
-        torch.cuda.empty_cache()
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        with open(args.out, "a") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+    for rows, cols, k, base, fts, bases in cases(args.shapes, args.ks, DT[args.dtype], dev):
+        nbytes = (2 * k + 3) * base.numel() * base.element_size()
+        ms = timed(lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density), args.seconds)
+        eng.ctx.profile(True)
+        eng.ctx.profile_reset()
+        _, rep = eng.ties_merge(fts, bases, alphas[:k], base, density=args.density)
+        table = eng.ctx.profile_table()
+        eng.ctx.profile(False)
+        blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+        clone_ms = timed(lambda: blob.clone(), args.seconds)
+        del blob
+        how = torch_ties(fts, base, alphas[:k], args.density, 1.0, True)[1]
+        torch_ms = timed(lambda: torch_ties(fts, base, alphas[:k], args.density, 1.0, True), args.seconds, warmup=1, min_reps=3)
+        rec = {"ties_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "density": args.density,
+               "ms": round(ms, 4), "GBps": round(nbytes / ms / 1e6, 1), "share_of_8TBps": round(nbytes / ms / 1e6 / HBM_PEAK_GBPS, 3),
+               "kernel_ms": {n: round(v[1], 4) for n, v in sorted(table.items())},
+               "kept_over_asked": [round(c / max(rep.k_keep, 1), 4) for c in rep.kept],
+               "clone_ms": round(clone_ms, 4), "clone_GBps": round(nbytes / clone_ms / 1e6, 1),
+               "ratio_to_clone": round(ms / clone_ms, 3),
+               "torch_ms": round(torch_ms, 3), "torch_select": how, "speedup_over_torch": round(torch_ms / ms, 2),
+               "faster_than_torch": bool(ms < torch_ms)}
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    append_lines(lines, args.out)
     if not all(rec["faster_than_torch"] for rec in lines):
         sys.exit("ties_merge lost to the torch restatement in at least one case")
 
