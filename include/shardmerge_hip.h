@@ -315,6 +315,79 @@ typedef struct {
 int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* desc, void* out, float* delta_out,
                             smhip_breadcrumbs_report* report, void* stream);
 
+/* ---- Geometric merges: Model Stock (Jang et al., "Model Stock: All we need is just a few fine-tuned models", 2024),
+ *      SLERP and NuSLERP.  The coefficients come from the geometry of the vectors - their norms and the angles between
+ *      them - not from a per-element decision.  The reference has no such operators; this section IS their definition.
+ *      One tensor of n elements viewed as R x C: R = `rows` (the first dimension, 1 for a 1-D tensor), C = n / R.
+ *      Finetunes i = 0..k-1 in order, 1 <= k <= 16.
+ *        1. Vectors.  Delta space (mode MODEL_STOCK, NUSLERP): x_i = fl32(fp32(finetune_i) - fp32(base_i)).  Weight
+ *           space (mode SLERP): x_i = fp32(finetune_i); base_i and base_out are not read (they may be NULL).  A NaN or
+ *           Inf in any x_i fails the call with SMHIP_ERR_NONFINITE (the message lists the finetunes); out is then
+ *           unspecified.
+ *        2. Gram.  G[i][j] = sum_e (double) x_i[e] * (double) x_j[e], i <= j, over the whole tensor (rowwise == 0) or
+ *           over each row (rowwise == 1, MODEL_STOCK only).  A product of two fp32 values is exact in fp64; every
+ *           addition is one correctly rounded fp64 addition, in THIS order:
+ *             - the elements are cut into SEGMENTS: whole tensor, segment s = elements [32768 s, min(n, 32768 (s + 1)));
+ *               row-wise, segment s = row s (C elements);
+ *             - inside a segment, the element with segment-local index c belongs to octet o = c / 8 and to LANE
+ *               t = o % 256.  A lane starts from +0 and adds the products of its elements in ascending index order:
+ *               p_t = (...((0 + x_i[c_0] x_j[c_0]) + x_i[c_1] x_j[c_1]) + ...), c_0 < c_1 < ...; a lane without
+ *               elements is +0;
+ *             - the 256 lanes are reduced by a binary tree: for s = 128, 64, 32, 16, 8, 4, 2, 1 in turn,
+ *               p_t = p_t + p_(t+s) for every t < s; the segment's value is p_0;
+ *             - whole tensor: G = (...((0 + S_0) + S_1) + ...) over the segments' values in ascending index order;
+ *               row-wise: the Gram of row r is S_r.
+ *           The order is a function of n alone (of C alone for a row): it does not depend on the device, the grid, the
+ *           stream or the number of processes, and no floating-point atomic takes part.
+ *        3. Coefficients, in fp64, every operation one IEEE operation (no fused multiply-add), each coefficient rounded
+ *           once to fp32.  n_i = sqrt(G[i][i]); cos_ij = clamp(G[i][j] / (n_i * n_j), -1, 1), or 0 when n_i * n_j is 0
+ *           or not finite (two parallel vectors reach +-1 only up to the rounding of the two square roots).
+ *           MODEL_STOCK: k == 1: t = 1.  Else cos = (((0 + cos_01) + cos_02) + ... over i < j, lexicographic)
+ *             / (double)(k (k - 1) / 2); den = 1 + (k - 1) * cos; t = (k * cos) / den when den > 0 and the quotient is
+ *             finite, else 0.  A = ((0 + alpha_0) + alpha_1) + ..., A := 1 where |A| < 1e-8.
+ *             c_i = fp32((t * alpha_i) / A).  Equal alphas: the plain average of the finetunes, interpolated towards
+ *             the base by t, as in the paper.  Row-wise: cos, t and c_i exist per row (computed on the device; the
+ *             formulas need + - * / sqrt only).
+ *           NUSLERP, SLERP: k <= 2, rowwise == 0.  k == 1: c_0 = 1.  k == 2: both alphas >= 0 and their sum > 0, else
+ *             SMHIP_ERR_ARG; tau = alpha_1 / (alpha_0 + alpha_1).  LINEAR case (n_0 == 0, n_1 == 0 or
+ *             |cos_01| > 0.9995): s_0 = 1 - tau, s_1 = tau.  Else Omega = acos(cos_01), s_0 = sin((1 - tau) * Omega)
+ *             / sin(Omega), s_1 = sin(tau * Omega) / sin(Omega), with the C library's acos and sin in double.
+ *             SLERP (the classic form, on the weights): c_i = fp32(s_i).
+ *             NUSLERP (the direction is slerped between the unit vectors, the length interpolated linearly):
+ *             N = (1 - tau) * n_0 + tau * n_1, c_i = fp32((s_i * N) / n_i); in the linear case c_i = fp32(s_i).
+ *        4. Combine.  M = ((0 + fl32(c_0 * x_0)) + fl32(c_1 * x_1)) + ... in fp32, product and sum rounded separately.
+ *           Delta space: out = round_to(base_out_dtype, fp32(base_out) + M).  Weight space: out =
+ *           round_to(base_out_dtype, M).  delta_out (optional) = M.
+ *      Aliasing, alignment, n == 0, dtypes and the size limit: the rules of smhip_ties_merge (n > 0 needs rows >= 1
+ *      that divides n).  Whole-tensor calls synchronise the stream once, after the Gram, to fetch it and compute the
+ *      coefficients on the host; row-wise calls once, at their end.  Profile names: "geo_gram", "geo_gram_fold" (whole
+ *      tensor), "geo_coef" (row-wise), "geo_combine". ---- */
+enum { SMHIP_GEO_MODEL_STOCK = 0, SMHIP_GEO_NUSLERP = 1, SMHIP_GEO_SLERP = 2 };
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base (SLERP: not read) */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;   /* (SLERP: base_out is not read, base_out_dtype is out's dtype) */
+    size_t n;
+    int mode;                               /* SMHIP_GEO_* */
+    int rowwise;                            /* 1: a Gram, a t and coefficients per row (MODEL_STOCK only) */
+    size_t rows;                            /* R */
+} smhip_geo_desc;
+typedef struct {
+    double G[SMHIP_MAX_MODELS][SMHIP_MAX_MODELS];   /* whole tensor: the Gram, both triangles */
+    double cos;                             /* whole tensor: MODEL_STOCK the mean cosine, else cos_01 (0 when k == 1) */
+    double t;                               /* whole tensor: MODEL_STOCK t, else tau */
+    double omega;                           /* NUSLERP / SLERP: Omega, 0 in the linear case */
+    int linear;                             /* NUSLERP / SLERP: 1 in the linear case (and when k == 1) */
+    float c[SMHIP_MAX_MODELS];              /* whole tensor: the coefficients */
+    double t_min, t_max, t_mean;            /* row-wise: over the rows' t; the mean is (((0 + t_0) + t_1) + ...) / R */
+} smhip_geo_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], M.  report (optional): HOST. */
+int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* desc, void* out, float* delta_out,
+                    smhip_geo_report* report, void* stream);
+
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector
  *      v1 - v0 dot is normalised along the LAST dimension (F.normalize(dim=-1), eps 1e-12), out = v0 cos + rel sin.

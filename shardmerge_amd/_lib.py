@@ -113,6 +113,21 @@ class BreadcrumbsReport(C.Structure):
                 ("kept", C.c_uint64 * MAX_MODELS), ("dropped_top", C.c_uint64 * MAX_MODELS)]
 
 
+GEO_MODEL_STOCK, GEO_NUSLERP, GEO_SLERP = 0, 1, 2
+
+
+class GeoDesc(C.Structure):
+    """smhip_geo_desc"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("mode", C.c_int), ("rowwise", C.c_int), ("rows", C.c_size_t)]
+
+
+class GeoReport(C.Structure):
+    """smhip_geo_report"""
+    _fields_ = [("G", (C.c_double * MAX_MODELS) * MAX_MODELS), ("cos", C.c_double), ("t", C.c_double), ("omega", C.c_double),
+                ("linear", C.c_int), ("c", C.c_float * MAX_MODELS),
+                ("t_min", C.c_double), ("t_max", C.c_double), ("t_mean", C.c_double)]
+
+
 class LayerReport(C.Structure):
     _fields_ = [
         ("target_norm", C.c_double),
@@ -164,6 +179,7 @@ class SmhipLibrary:
         d.smhip_ties_merge.argtypes = [P, C.POINTER(TiesDesc), P, P, C.POINTER(TiesReport), P]
         d.smhip_dare_merge.argtypes = [P, C.POINTER(DareDesc), P, P, C.POINTER(DareReport), P]
         d.smhip_breadcrumbs_merge.argtypes = [P, C.POINTER(BreadcrumbsDesc), P, P, C.POINTER(BreadcrumbsReport), P]
+        d.smhip_geo_merge.argtypes = [P, C.POINTER(GeoDesc), P, P, C.POINTER(GeoReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

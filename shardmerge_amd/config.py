@@ -46,6 +46,15 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # gamma: 0.01             #   0 <= gamma < 1, density + gamma <= 1
       # breadcrumbs_lambda: 1.0 #   scales the merged delta
       # breadcrumbs_normalize: 1  # 1: divide by the sum of the weights (breadcrumbs_ties: of the agreeing entries), 0: plain sum
+                                # | model_stock | nuslerp | slerp (the geometric operators; no counterpart in the reference):
+                                #   the coefficients come from the norms of the deltas and the angles between them, summed in
+                                #   fp64 in a fixed order.  model_stock (Jang et al. 2024): the alpha-weighted average of the
+                                #   deltas, pulled towards the base by t = k cos / (1 + (k - 1) cos), cos the mean cosine
+                                #   between them.  nuslerp: exactly two finetune_merge entries, alphas >= 0 with a sum > 0; the
+                                #   deltas' directions are interpolated on the sphere at alpha_1 / (alpha_0 + alpha_1), their
+                                #   lengths linearly.  slerp: the same interpolation of the two models' WEIGHTS (the bases and
+                                #   output_base_model do not enter a block tensor).  Every key above is rejected; the one key:
+      # stock_filter_wise: 0    #   operator model_stock only - 1: one cosine, one t per ROW of each tensor, 0: per tensor
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -71,7 +80,8 @@ _REQUIRED = ("output_base_model", "finetune_merge", "output_dir")
 MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.0, "target_norm_offset": 1e-10, "b": 0.1}
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
-OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties")
+OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
+             "model_stock", "nuslerp", "slerp")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them take `density`), seed stays an int (it must survive exactly), every other value becomes a float.
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
@@ -80,6 +90,9 @@ DARE_OPTION_DEFAULTS = {"density": 0.2, "dare_lambda": 1.0, "dare_normalize": 1.
 DARE_MIN_DENSITY = 2.0 ** -16                       # the mask draws 16 bits per element
 BREADCRUMBS_OPERATORS = ("breadcrumbs", "breadcrumbs_ties")
 BREADCRUMBS_OPTION_DEFAULTS = {"density": 0.9, "gamma": 0.01, "breadcrumbs_lambda": 1.0, "breadcrumbs_normalize": 1.0}
+GEO_OPERATORS = ("model_stock", "nuslerp", "slerp")      # the geometric family: coefficients from norms and angles
+GEO_PAIR_OPERATORS = ("nuslerp", "slerp")                # ... of exactly two finetune_merge entries
+GEO_OPTION_DEFAULTS = {"stock_filter_wise": 0.0}
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -94,11 +107,12 @@ def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
 class _OptionFamily:
     """One family's merge_options.  rules: key -> "flag" (0 or 1), "seed" (an exact integer in [0, 2^63)) or a range
     (lo, hi, brackets[, the message's own wording of the range]).  earlier: what the message says after a key of an
-    earlier family, by that family's first operator.  check: a rule over several keys."""
+    earlier family, by that family's first operator.  only: a key that not every operator of the family takes.  check: a rule over several keys."""
     operators: tuple
     defaults: Dict[str, Union[int, float]]
     rules: Dict[str, Any]
     earlier: Dict[str, str] = field(default_factory=dict)
+    only: Dict[str, tuple] = field(default_factory=dict)        # key -> the operators of the family that take it (default: all)
     check: Optional[Callable[[Dict[str, Any]], None]] = None
 
 
@@ -113,7 +127,15 @@ _OPTION_FAMILIES = (                                # in the order they were add
                   {"density": _DENSITY, "gamma": (0, 1, "[)"), "breadcrumbs_lambda": _LAMBDA, "breadcrumbs_normalize": "flag"},
                   earlier={"ties": "(its keys: breadcrumbs_lambda, breadcrumbs_normalize)", "dare_ties": "(its trim is by magnitude, not random)"},
                   check=_breadcrumbs_band),
+    _OptionFamily(GEO_OPERATORS, GEO_OPTION_DEFAULTS, {"stock_filter_wise": "flag"},
+                  earlier={"ties": "(it trims nothing and scales by the deltas' geometry)", "dare_ties": "(it drops nothing)",
+                           "breadcrumbs": "(it trims nothing)"},
+                  only={"stock_filter_wise": ("model_stock",)}),
 )
+
+
+def _one_of(names) -> str:
+    return names[0] if len(names) == 1 else f"{', '.join(names[:-1])} or {names[-1]}"
 
 
 def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], operator: str) -> Optional[Dict[str, Union[int, float]]]:
@@ -123,8 +145,8 @@ def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], o
     for i in reversed(range(own + 1, len(_OPTION_FAMILIES))):          # the families added after the operator's, the latest first
         new = set(_OPTION_FAMILIES[i].defaults).difference(*(e.defaults for e in _OPTION_FAMILIES[:i]))    # the keys it brought
         for key in sorted(set(opts) & new):
-            names = [op for f in _OPTION_FAMILIES if new & set(f.defaults) for op in f.operators]
-            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: {', '.join(names[:-1])} or {names[-1]} "
+            names = [op for f in _OPTION_FAMILIES if new & set(f.defaults) for op in f.only.get(key, f.operators)]
+            raise click.BadParameter(f"merge_options.{key} is accepted only with operator: {_one_of(names)} "
                                      f"(operator {operator!r} would ignore it)")
     if own < 0:
         return None
@@ -139,6 +161,9 @@ def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], o
         for key in sorted((set(opts) & set(e.defaults)) - set(fam.defaults)):
             raise click.BadParameter(f"merge_options.{key} is an option of operator{'s' if len(e.operators) > 1 else ''} {' / '.join(e.operators)}; "
                                      f"operator {operator!r} would ignore it {fam.earlier[e.operators[0]]}")
+    for key in sorted(k for k in set(opts) & set(fam.only) if operator not in fam.only[k]):
+        raise click.BadParameter(f"merge_options.{key} is accepted only with operator: {_one_of(fam.only[key])} "
+                                 f"(operator {operator!r} would ignore it)")
     unknown = set(opts) - set(fam.defaults)
     if unknown:
         raise click.BadParameter(f"merge_options: unknown keys {sorted(unknown)}; known with operator {operator}: {sorted(fam.defaults) + ['operator']}")
@@ -270,6 +295,14 @@ class MergeConfig:
             raise click.BadParameter(f"merge_options.operator must be one of {list(OPERATORS)}")
         raw["operator"] = operator
         family_options = _family_options(opts, norm_mode, task_add, operator)
+        if operator in GEO_PAIR_OPERATORS:
+            entries = raw["finetune_merge"]
+            if len(entries) != 2:
+                raise click.BadParameter(f"operator {operator} interpolates between exactly two finetune_merge entries, not {len(entries)}")
+            alphas = [m.alpha for m in entries]
+            if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
+                raise click.BadParameter(f"operator {operator} needs finetune_merge alphas >= 0 with a sum > 0 (the interpolation "
+                                         f"point is alpha_1 / (alpha_0 + alpha_1)), not {alphas}")
         if family_options is not None:
             raw["merge_options"] = family_options
             return cls(**raw)

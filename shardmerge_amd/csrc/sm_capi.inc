@@ -24,19 +24,21 @@ struct smhip_ctx {
 
 // The argument checks that smhip_ties_merge, smhip_dare_merge and smhip_breadcrumbs_merge share: their descriptors have
 // the same leading fields (k .. normalize), hence the template.  `op` names the entry point in the messages.
-template <class Desc>
-static int delta_merge_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out) {
+// smhip_geo_merge shares all of it but the scalars (`scalars`: the operator's own checks, after k and the dtypes) and,
+// in weight space, the bases (`need_base` = false: they are not read and may be NULL).
+template <class Desc, class Scalars>
+static int delta_tensor_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out,
+                              bool need_base, Scalars scalars) {
     auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + what); };
     if (!d) return bad("null descriptor");
     if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return bad("k out of range (1..16)");
     if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->base_out_dtype < SMHIP_BF16 || d->base_out_dtype > SMHIP_F32)
         return bad("bad dtype");
-    if (!(d->density > 0.0 && d->density <= 1.0)) return bad("density must be in (0, 1]");
-    if (!std::isfinite(d->lambda)) return bad("lambda is not finite");
+    if (const char* what = scalars()) return bad(what);
     for (int i = 0; i < d->k; ++i)
         if (!std::isfinite(d->alpha[i])) return bad("an alpha is not finite");
     if (d->n == 0) return SMHIP_OK;
-    if (!out || !d->base_out) return bad("null out or base_out");
+    if (!out || (need_base && !d->base_out)) return bad("null out or base_out");
     const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
     if ((uintptr_t)out % oes || (uintptr_t)d->base_out % oes || (uintptr_t)delta_out % 4)
         return bad("a pointer is not aligned to its element size");
@@ -46,16 +48,24 @@ static int delta_merge_check(smhip_ctx* ctx, const char* op, const Desc* d, cons
     auto hits_output = [&](const void* p, size_t bytes) {
         return overlaps(out, d->n * oes, p, bytes) || overlaps(delta_out, d->n * 4, p, bytes);
     };
-    bool hit = hits_output(d->base_out, d->n * oes) || overlaps(out, d->n * oes, delta_out, d->n * 4);
+    bool hit = (need_base && hits_output(d->base_out, d->n * oes)) || overlaps(out, d->n * oes, delta_out, d->n * 4);
     for (int i = 0; i < d->k; ++i) {
-        if (!d->finetune[i] || !d->base[i]) return bad("null model tensor");
-        if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies)
+        if (!d->finetune[i] || (need_base && !d->base[i])) return bad("null model tensor");
+        if ((uintptr_t)d->finetune[i] % ies || (need_base && (uintptr_t)d->base[i] % ies))
             return bad("a pointer is not aligned to its element size");
-        hit = hit || hits_output(d->finetune[i], d->n * ies) || hits_output(d->base[i], d->n * ies);
+        hit = hit || hits_output(d->finetune[i], d->n * ies) || (need_base && hits_output(d->base[i], d->n * ies));
     }
     if (hit) return bad("out overlaps an input");
     if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return bad("tensor too large");
     return SMHIP_OK;
+}
+template <class Desc>
+static int delta_merge_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out) {
+    return delta_tensor_check(ctx, op, d, out, delta_out, true, [&]() -> const char* {
+        if (!(d->density > 0.0 && d->density <= 1.0)) return "density must be in (0, 1]";
+        if (!std::isfinite(d->lambda)) return "lambda is not finite";
+        return nullptr;
+    });
 }
 
 extern "C" {
@@ -203,6 +213,26 @@ int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* d, voi
     if (!(d->density + d->gamma <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: density + gamma must not exceed 1");
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.breadcrumbs_merge(*d, out, delta_out, report));
+}
+
+int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* d, void* out, float* delta_out, smhip_geo_report* report,
+                    void* stream) {
+    SM_GUARD(ctx);
+    const bool weight = d && d->mode == SMHIP_GEO_SLERP;
+    if (int rc = delta_tensor_check(ctx, "geo_merge", d, out, delta_out, !weight, [&]() -> const char* {
+            if (d->mode < SMHIP_GEO_MODEL_STOCK || d->mode > SMHIP_GEO_SLERP) return "bad mode";
+            if (d->mode == SMHIP_GEO_MODEL_STOCK) return nullptr;
+            if (d->rowwise) return "rowwise is an option of mode MODEL_STOCK";
+            if (d->k > 2) return "modes NUSLERP and SLERP take k <= 2";
+            if (d->k == 2 && !(d->alpha[0] >= 0.0 && d->alpha[1] >= 0.0 && d->alpha[0] + d->alpha[1] > 0.0 &&
+                               std::isfinite(d->alpha[0] + d->alpha[1])))
+                return "modes NUSLERP and SLERP need alphas >= 0 with a sum > 0";
+            return nullptr;
+        }))
+        return rc;
+    if (d->n > 0 && (d->rows < 1 || d->n % d->rows)) return ctx->pipe.fail(SMHIP_ERR_ARG, "geo_merge: rows must divide n");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.geo_merge(*d, out, delta_out, report));
 }
 
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {

@@ -19,6 +19,7 @@
 #include "sm_ties.hpp"
 #include "sm_dare.hpp"
 #include "sm_breadcrumbs.hpp"
+#include "sm_geo.hpp"
 
 namespace smhip {
 
@@ -223,6 +224,12 @@ SM_KERNEL_TAG_LB(KDareMerge, DareMergeParams, "dare_merge", k_dare_merge(ex, p),
 SM_KERNEL_TAG_LB(KCrumbsHist, CrumbsHistParams, "crumbs_hist", k_crumbs_hist(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KCrumbsSelect, CrumbsSelectParams, "crumbs_select", k_crumbs_select(ex, p), TIES_SELECT_THREADS, 4)
 SM_KERNEL_TAG_LB(KCrumbsMerge, CrumbsMergeParams, "crumbs_merge", k_crumbs_merge(ex, p), 256, 4)
+// Geometric merges (sm_geo.hpp): the ordered fp64 Gram pass, its fold over the segments, the row-wise coefficients, the combine pass
+SM_KERNEL_TAG_LB(KGeoGram, GeoGramParams, "geo_gram", k_geo_gram<false>(ex, p), GEO_THREADS, 4)       // k <= 4: one tile of pairs
+SM_KERNEL_TAG_LB(KGeoGramTiled, GeoGramParams, "geo_gram", k_geo_gram<true>(ex, p), GEO_THREADS, 2)
+SM_KERNEL_TAG_LB(KGeoFold, GeoFoldParams, "geo_gram_fold", k_geo_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KGeoCoef, GeoCoefParams, "geo_coef", k_geo_coef(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KGeoCombine, GeoCombineParams, "geo_combine", k_geo_combine(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -248,8 +255,9 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
-#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE and Breadcrumbs
+#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
+    X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs and the geometric merges
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2536,6 +2544,137 @@ class Pipeline {
                 rep->threshold_lo[i] = host.threshold_lo[i]; rep->threshold_hi[i] = host.threshold_hi[i];
                 rep->kept[i] = host.kept[i]; rep->dropped_top[i] = host.dropped_top[i];
             }
+        return SMHIP_OK;
+    }
+
+    // ---- Geometric merges (sm_geo.hpp; the function is stated in shardmerge_hip.h, smhip_geo_merge): the Gram pass, then
+    // whole tensor: fold, ONE readback, the coefficients on the host, the combine pass; row-wise: coefficients on the
+    // device, the combine pass, one readback at the end.  Workspace (the TIES buffer): flags | G | partials or row data ----
+    struct GeoHead { uint32_t flags[2]; double G[TIES_MAX_MODELS * (TIES_MAX_MODELS + 1) / 2]; };
+    int geo_nonfinite(int k, uint32_t flags) {
+        std::string which;
+        for (int i = 0; i < k; ++i)
+            if (flags & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
+        return fail(SMHIP_ERR_NONFINITE, "geo_merge: NaN or Inf in the vector (finetune - base, or the finetune) of finetune " + which);
+    }
+    int geo_merge(const smhip_geo_desc& d, void* out, float* delta_out, smhip_geo_report* rep) {
+        const int k = d.k, np = geo_pairs(k);
+        const bool weight = d.mode == SMHIP_GEO_SLERP, rowwise = d.rowwise != 0;
+        if (rep) *rep = smhip_geo_report{};
+        // the scalars that need no data
+        double A = 0.0;
+        for (int i = 0; i < k; ++i) A = geo_dadd(A, d.alpha[i]);
+        if (std::fabs(A) < 1e-8) A = 1.0;
+        const double tau = (d.mode != SMHIP_GEO_MODEL_STOCK && k == 2) ? geo_ddiv(d.alpha[1], geo_dadd(d.alpha[0], d.alpha[1])) : 0.0;
+        if (d.n == 0) return SMHIP_OK;
+
+        GeoCombineParams m;
+        {   // (a smhip_geo_desc has the leading fields of the delta-merge descriptors but for density, lambda, normalize)
+            TiesInputs& in = m.in;
+            in.k = k; in.dtype = d.in_dtype; in.n = d.n;
+            bool al = aligned16(out) && aligned16(delta_out) && (weight || aligned16(d.base_out)), shared = true;
+            for (int i = 0; i < TIES_MAX_MODELS; ++i) {
+                in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = weight ? nullptr : d.base[i < k ? i : 0];
+                al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
+                shared = shared && in.base[i] == in.base[0];
+                m.c[i] = 0.f;
+            }
+            in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
+            m.weight_space = weight ? 1 : 0;
+            m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
+            m.out_is_base0 = (!weight && shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
+            m.out = out; m.delta_out = delta_out;
+            m.rowcoef = nullptr; m.C = d.n / d.rows;
+            m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+        }
+        GeoGramParams g;
+        g.in = m.in; g.weight_space = m.weight_space;
+        g.seg_len = rowwise ? m.C : GEO_SEG_ELEMS;
+        g.nseg = (d.n + g.seg_len - 1) / g.seg_len;
+        g.seg_vec = (m.in.aligned && g.seg_len % 8 == 0) ? 1 : 0;
+        const size_t ggrid = g.nseg * (size_t)geo_tiles(k);
+        if (ggrid > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "geo_merge: tensor too large");
+
+        const size_t off_part = round_up(sizeof(GeoHead), 256), part_bytes = round_up(g.nseg * np * sizeof(double), 256);
+        const size_t off_coef = off_part + part_bytes, coef_bytes = rowwise ? round_up(g.nseg * k * sizeof(float), 256) : 0;
+        const size_t off_t = off_coef + coef_bytes, t_bytes = rowwise ? g.nseg * sizeof(double) : 0;
+        int rc;
+        if ((rc = ensure(ties_, off_t + t_bytes))) return rc;
+        GeoHead* head = (GeoHead*)ties_.p;
+        be.memset(head, 0, sizeof(GeoHead), stream);
+        g.part = (double*)((char*)ties_.p + off_part);
+        g.flags = head->flags;
+        if (k <= GEO_TILE) be.template launch<KGeoGram>((int)ggrid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+        else be.template launch<KGeoGramTiled>((int)ggrid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+
+        const int cgrid = stream_grid((d.n + 7) / 8, 256, m.chunks);
+        if (rowwise) {
+            GeoCoefParams c;
+            c.k = k; c.rows = g.nseg; c.A = A; c.G = g.part;
+            for (int i = 0; i < TIES_MAX_MODELS; ++i) c.alpha[i] = d.alpha[i < k ? i : 0];
+            c.coef = (float*)((char*)ties_.p + off_coef); c.t = (double*)((char*)ties_.p + off_t);
+            be.template launch<KGeoCoef>((int)((g.nseg + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, c, stream);
+            m.rowcoef = c.coef;
+            be.template launch<KGeoCombine>(cgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+            GeoHead host;
+            std::vector<double> t(g.nseg);
+            be.d2h(t.data(), c.t, t_bytes, stream);          // (the call's one synchronisation; the head follows on the drained stream)
+            be.d2h(&host, head, sizeof host, stream);
+            if (!be.ok()) return SMHIP_OK;
+            if (host.flags[0]) return geo_nonfinite(k, host.flags[0]);
+            if (rep) {
+                double sum = 0.0, lo = t[0], hi = t[0];
+                for (double v : t) { sum = geo_dadd(sum, v); lo = std::min(lo, v); hi = std::max(hi, v); }
+                rep->t_min = lo; rep->t_max = hi; rep->t_mean = geo_ddiv(sum, (double)g.nseg);
+            }
+            return SMHIP_OK;
+        }
+
+        GeoFoldParams f;
+        f.np = np; f.nseg = g.nseg; f.part = g.part; f.G = head->G;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        GeoHead host;
+        be.d2h(&host, head, sizeof host, stream);            // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0]) return geo_nonfinite(k, host.flags[0]);
+        const double* G = host.G;
+        double cosv = 0.0, tv = 0.0, omega = 0.0;
+        int linear = 0;
+        if (d.mode == SMHIP_GEO_MODEL_STOCK) {
+            tv = geo_stock_t(G, k, &cosv);
+            for (int i = 0; i < k; ++i) m.c[i] = geo_stock_coef(tv, d.alpha[i], A);
+        } else if (k == 1) {
+            m.c[0] = 1.f; linear = 1;
+        } else {
+            const double n0 = geo_dsqrt(G[geo_pair_index(0, 0, 2)]), n1 = geo_dsqrt(G[geo_pair_index(1, 1, 2)]);
+            cosv = geo_cos(G[geo_pair_index(0, 1, 2)], n0, n1);
+            tv = tau;
+            double s0, s1;
+            const double one_tau = geo_dadd(1.0, -tau);
+            linear = (n0 == 0.0 || n1 == 0.0 || std::fabs(cosv) > 0.9995) ? 1 : 0;
+            if (linear) {
+                s0 = one_tau; s1 = tau;
+            } else {
+                omega = std::acos(cosv);
+                const double so = std::sin(omega);
+                s0 = geo_ddiv(std::sin(geo_dmul(one_tau, omega)), so);
+                s1 = geo_ddiv(std::sin(geo_dmul(tau, omega)), so);
+            }
+            if (d.mode == SMHIP_GEO_NUSLERP && !linear) {
+                const double N = geo_dadd(geo_dmul(one_tau, n0), geo_dmul(tau, n1));
+                m.c[0] = (float)geo_ddiv(geo_dmul(s0, N), n0);
+                m.c[1] = (float)geo_ddiv(geo_dmul(s1, N), n1);
+            } else {
+                m.c[0] = (float)s0; m.c[1] = (float)s1;
+            }
+        }
+        if (rep) {
+            for (int i = 0; i < k; ++i)
+                for (int j = i; j < k; ++j) rep->G[i][j] = rep->G[j][i] = G[geo_pair_index(i, j, k)];
+            rep->cos = cosv; rep->t = tv; rep->omega = omega; rep->linear = linear;
+            for (int i = 0; i < k; ++i) rep->c[i] = m.c[i];
+        }
+        be.template launch<KGeoCombine>(cgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
         return SMHIP_OK;
     }
 

@@ -81,6 +81,21 @@ class BreadcrumbsMergeReport:
 
 
 @dataclass
+class GeoMergeReport:
+    mode: str = "model_stock"
+    rowwise: bool = False
+    gram: List[List[float]] = field(default_factory=list)            # whole tensor: G[i][j], the fp64 Gram of the k vectors
+    cos: float = 0.0                                                 # model_stock: the mean pairwise cosine; else cos_01
+    t: float = 0.0                                                   # model_stock: the interpolation ratio t; else tau
+    omega: float = 0.0                                               # nuslerp / slerp: the angle (0 in the linear case)
+    linear: bool = False                                             # nuslerp / slerp: the linear case was taken
+    coefficients: List[float] = field(default_factory=list)          # whole tensor: c_i (fp32)
+    t_min: float = 0.0                                               # row-wise: over the rows' t
+    t_max: float = 0.0
+    t_mean: float = 0.0
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -354,7 +369,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -495,6 +510,44 @@ class Engine:
                                         thresholds_hi=[float(rep.threshold_hi[i]) for i in range(k)],
                                         kept=[int(rep.kept[i]) for i in range(k)],
                                         dropped_top=[int(rep.dropped_top[i]) for i in range(k)])
+        return (out, report, delta) if want_delta else (out, report)
+
+    # -- Model Stock, NuSLERP, SLERP -------------------------------------------------------
+    GEO_MODES = {"model_stock": _lib.GEO_MODEL_STOCK, "nuslerp": _lib.GEO_NUSLERP, "slerp": _lib.GEO_SLERP}
+
+    def geo_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                  base_out: torch.Tensor, *, mode: str = "model_stock", rowwise: bool = False, want_delta: bool = False,
+                  layer_name: Optional[str] = None):
+        """Geometric merge of one tensor of any shape (``smhip_geo_merge``; the function is stated in
+        include/shardmerge_hip.h).  The fp64 Gram matrix of the vectors (the deltas ``finetune_i - base_i``; the
+        finetunes themselves for ``slerp``) is summed in an order that depends on the element count only, the
+        coefficients follow from it - ``model_stock``: the ratio t from the mean cosine, ``rowwise``: per row of the
+        first dimension; ``nuslerp`` / ``slerp``: the spherical interpolation of two vectors at
+        ``alpha_1 / (alpha_0 + alpha_1)`` - and one pass writes ``base_out + sum c_i x_i`` (``slerp``: ``sum c_i x_i``)
+        in base_out's dtype.  Returns (out, GeoMergeReport[, the fp32 combination M]).  A NaN or Inf in a vector raises
+        ValueError naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if mode not in self.GEO_MODES:
+            raise ValueError(f"geo_merge: mode {mode!r} is not one of {sorted(self.GEO_MODES)}")
+        k = len(finetunes)
+        if mode != "model_stock":
+            if rowwise:
+                raise ValueError(f"geo_merge: rowwise is an option of mode model_stock, not of {mode}")
+            if k > 2:
+                raise ValueError(f"geo_merge: mode {mode} merges at most 2 models, not {k}")
+            if k == 2 and len(alphas) == 2 and not (float(alphas[0]) >= 0 and float(alphas[1]) >= 0 and float(alphas[0]) + float(alphas[1]) > 0):
+                raise ValueError(f"geo_merge: mode {mode} needs alphas >= 0 with a sum > 0, not {list(alphas)}")
+        desc, rep = _lib.GeoDesc(), _lib.GeoReport()
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "geo_merge")
+        desc.n = bo.numel()
+        desc.mode, desc.rowwise = self.GEO_MODES[mode], 1 if rowwise else 0
+        desc.rows = (bo.shape[0] if bo.ndim > 1 else 1) or 1
+        self._run_delta_merge(self.lib.dll.smhip_geo_merge, desc, rep, out, delta, layer_name)
+        report = GeoMergeReport(mode=mode, rowwise=bool(rowwise), cos=float(rep.cos), t=float(rep.t), omega=float(rep.omega),
+                                linear=bool(rep.linear), t_min=float(rep.t_min), t_max=float(rep.t_max), t_mean=float(rep.t_mean))
+        if not rowwise:
+            report.gram = [[float(rep.G[i][j]) for j in range(k)] for i in range(k)]
+            report.coefficients = [float(rep.c[i]) for i in range(k)]
         return (out, report, delta) if want_delta else (out, report)
 
     def correlate_pairs(self, tensors) -> torch.Tensor:

@@ -12,6 +12,9 @@ _OPERATOR_CLASSES = {
     "dare_linear": ("dare", "DareLinearMerge"),
     "breadcrumbs": ("breadcrumbs", "BreadcrumbsMerge"),
     "breadcrumbs_ties": ("breadcrumbs", "BreadcrumbsTiesMerge"),
+    "model_stock": ("geometric", "ModelStockMerge"),
+    "nuslerp": ("geometric", "NuSlerpMerge"),
+    "slerp": ("geometric", "SlerpMerge"),
 }
 
 
