@@ -388,6 +388,69 @@ typedef struct {
 int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* desc, void* out, float* delta_out,
                     smhip_geo_report* report, void* stream);
 
+/* ---- SCE merge (Wan et al., "FuseChat: Knowledge Fusion of Chat Models", 2024; mergekit's merge_method sce with
+ *      select_topk): SELECT the parameters whose deltas vary most across the finetunes, CALCULATE a weight per finetune
+ *      from the energy of what it kept, ERASE the entries whose sign disagrees with the majority.  The reference has no
+ *      such operator; this section IS its definition.  For one tensor of n elements (any shape, flat), finetunes
+ *      i = 0..k-1 in order (1 <= k <= 16):
+ *        1. Deltas.  d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with
+ *           SMHIP_ERR_NONFINITE (the message lists the finetunes); out is then unspecified.  Arguments:
+ *           0 < select_topk <= 1, every alpha_i >= 0 and finite, their fp64 sum ((0 + alpha_0) + ...) > 0 and finite,
+ *           lambda finite, else SMHIP_ERR_ARG.
+ *        2. Select.  SKIPPED - every element is selected - when select_topk == 1 or k == 1; the report then carries
+ *           nz = k_keep = selected = n and a threshold of 0.  Else the score of an element is the sum of squared
+ *           deviations across the finetunes, every operation one rounded fp32 operation, no fused multiply-add:
+ *             s = ((0 + d_0) + d_1) + ...;  mean = s / fp32(k) (IEEE division);  e_i = d_i - mean;
+ *             q = ((0 + fl32(e_0 * e_0)) + fl32(e_1 * e_1)) + ...
+ *           q is never NaN for finite deltas; a q that overflowed to +inf is an ordinary value that sorts above all
+ *           others.  nz = the number of elements with q > 0.  k_keep = (uint64) floor(select_topk * nz) in fp64 (one
+ *           multiplication, one truncation).  tau = the k_keep-th largest q, exact.  An element is SELECTED iff
+ *           k_keep > 0, q >= tau and q > 0.  TIE RULE: every element that ties with tau is selected (selected >= k_keep),
+ *           so the result does not depend on any traversal order.  k_keep == 0 selects nothing; the report's threshold
+ *           is then +inf.  Counting by nz follows mergekit, which takes the top share of the NONZERO variances.
+ *           k == 1 deviates from mergekit on purpose: a single model has zero variance everywhere and mergekit keeps
+ *           nothing; here a layer that a window leaves with one entry takes that entry, as the geometric operators do.
+ *        3. Calculate.  x_i = d_i where selected, +0 elsewhere (the mask is Select's only; it is applied before Erase,
+ *           as in mergekit).  E_i = sum_e (double) x_i[e] * (double) x_i[e] over the whole tensor, accumulated in
+ *           exactly the order of step 2 of smhip_geo_merge: 32768-element segments, octet o to lane o % 256, ascending
+ *           index inside a lane, the binary tree over the 256 lanes, the segments added in index order.  In fp64, one
+ *           IEEE operation each: P_i = alpha_i * E_i, Z = ((0 + P_0) + P_1) + ...; w_i = fp32(P_i / Z) when Z > 0 and
+ *           finite, else w_i = fp32(1.0 / k).  Equal alphas of any value give the paper's weights: alpha is a prior on
+ *           the weight, not a scale of the delta.
+ *        4. Erase and merge, each operation one rounded fp32 operation.  S = ((0 + x_0) + x_1) + ..., unweighted as in the
+ *           paper; the elected sign is +1 if S >= 0, else -1.  m_i = [sign(x_i) == elected sign] (a zero agrees with
+ *           nothing).  M = sum_i m_i fl32(x_i * w_i), D = sum_i m_i w_i, both from 0 in order.  D := 1 where
+ *           |D| < fp32(1e-8); M := M / D (IEEE fp32 division).
+ *        5. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M)), delta_out = fl32(lambda * M):
+ *           step 7 of smhip_ties_merge.
+ *      Every step is one correctly rounded operation or an exact order statistic in a stated order: the result is
+ *      defined bit for bit.  The selection is ONE radix select over the 31 bits of q (11 + 10 + 10, 64-bit counts)
+ *      whatever k; nz, k_keep, tau and the selected count stay on the device.  With a shared base the call moves 5k + 6
+ *      tensors (three levels of k + 1, the energy pass k + 1, the merge k + 2), 2k + 3 when the selection is skipped.
+ *      Aliasing, alignment, n == 0, dtypes and the size limit: the rules of smhip_ties_merge.  The call synchronises
+ *      the stream once, after the energies, to fetch them with the selection's results and compute the weights on the
+ *      host.  Profile names: "sce_hist", "sce_select" (three launches each, none when the selection is skipped),
+ *      "sce_energy", "sce_energy_fold", "sce_merge". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double select_topk, lambda;
+} smhip_sce_desc;
+typedef struct {
+    uint64_t nz, k_keep, selected;
+    float threshold;                        /* tau; +inf when k_keep == 0; 0 when the selection was skipped */
+    double energy[SMHIP_MAX_MODELS];        /* E_i */
+    float weight[SMHIP_MAX_MODELS];         /* w_i */
+} smhip_sce_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * M).  report (optional): HOST. */
+int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* desc, void* out, float* delta_out,
+                    smhip_sce_report* report, void* stream);
+
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector
  *      v1 - v0 dot is normalised along the LAST dimension (F.normalize(dim=-1), eps 1e-12), out = v0 cos + rel sin.

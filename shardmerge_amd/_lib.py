@@ -128,6 +128,17 @@ class GeoReport(C.Structure):
                 ("t_min", C.c_double), ("t_max", C.c_double), ("t_mean", C.c_double)]
 
 
+class SceDesc(C.Structure):
+    """smhip_sce_desc"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("select_topk", C.c_double), ("lam", C.c_double)]
+
+
+class SceReport(C.Structure):
+    """smhip_sce_report"""
+    _fields_ = [("nz", C.c_uint64), ("k_keep", C.c_uint64), ("selected", C.c_uint64), ("threshold", C.c_float),
+                ("energy", C.c_double * MAX_MODELS), ("weight", C.c_float * MAX_MODELS)]
+
+
 class LayerReport(C.Structure):
     _fields_ = [
         ("target_norm", C.c_double),
@@ -180,6 +191,7 @@ class SmhipLibrary:
         d.smhip_dare_merge.argtypes = [P, C.POINTER(DareDesc), P, P, C.POINTER(DareReport), P]
         d.smhip_breadcrumbs_merge.argtypes = [P, C.POINTER(BreadcrumbsDesc), P, P, C.POINTER(BreadcrumbsReport), P]
         d.smhip_geo_merge.argtypes = [P, C.POINTER(GeoDesc), P, P, C.POINTER(GeoReport), P]
+        d.smhip_sce_merge.argtypes = [P, C.POINTER(SceDesc), P, P, C.POINTER(SceReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

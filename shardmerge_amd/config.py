@@ -55,6 +55,15 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
                                 #   lengths linearly.  slerp: the same interpolation of the two models' WEIGHTS (the bases and
                                 #   output_base_model do not enter a block tensor).  Every key above is rejected; the one key:
       # stock_filter_wise: 0    #   operator model_stock only - 1: one cosine, one t per ROW of each tensor, 0: per tensor
+                                # | sce (SCE, Wan et al. 2024, mergekit's merge_method sce; no counterpart in the reference):
+                                #   per tensor, the parameters whose deltas vary most across the finetunes are selected, each
+                                #   finetune is weighted by alpha times the energy (sum of squares) of its selected entries,
+                                #   normalised over the finetunes, and the entries whose sign disagrees with the majority are
+                                #   erased.  alphas >= 0 with a sum > 0 (an alpha is a prior on the weight, not a scale of
+                                #   the delta).  Every key above is rejected; its keys, this operator only:
+      # select_topk: 1.0        #   0 < select_topk <= 1: the share of the nonzero variances that is selected (ties at the
+                                #   threshold all kept); 1: everything (mergekit's name and default)
+      # sce_lambda: 1.0         #   scales the merged delta
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -81,7 +90,7 @@ MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
-             "model_stock", "nuslerp", "slerp")
+             "model_stock", "nuslerp", "slerp", "sce")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them take `density`), seed stays an int (it must survive exactly), every other value becomes a float.
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
@@ -93,6 +102,7 @@ BREADCRUMBS_OPTION_DEFAULTS = {"density": 0.9, "gamma": 0.01, "breadcrumbs_lambd
 GEO_OPERATORS = ("model_stock", "nuslerp", "slerp")      # the geometric family: coefficients from norms and angles
 GEO_PAIR_OPERATORS = ("nuslerp", "slerp")                # ... of exactly two finetune_merge entries
 GEO_OPTION_DEFAULTS = {"stock_filter_wise": 0.0}
+SCE_OPTION_DEFAULTS = {"select_topk": 1.0, "sce_lambda": 1.0}
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -131,6 +141,10 @@ _OPTION_FAMILIES = (                                # in the order they were add
                   earlier={"ties": "(it trims nothing and scales by the deltas' geometry)", "dare_ties": "(it drops nothing)",
                            "breadcrumbs": "(it trims nothing)"},
                   only={"stock_filter_wise": ("model_stock",)}),
+    _OptionFamily(("sce",), SCE_OPTION_DEFAULTS, {"select_topk": (0, 1, "(]"), "sce_lambda": _LAMBDA},
+                  earlier={"ties": "(its keys: select_topk, sce_lambda)", "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it selects by the variance across the finetunes, not by magnitude)",
+                           "model_stock": "(its weights come from the energies, per tensor)"}),
 )
 
 
@@ -303,6 +317,11 @@ class MergeConfig:
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
                 raise click.BadParameter(f"operator {operator} needs finetune_merge alphas >= 0 with a sum > 0 (the interpolation "
                                          f"point is alpha_1 / (alpha_0 + alpha_1)), not {alphas}")
+        if operator == "sce":
+            alphas = [m.alpha for m in raw["finetune_merge"]]
+            if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
+                raise click.BadParameter(f"operator sce needs finetune_merge alphas >= 0 with a sum > 0 (an alpha is a prior on the "
+                                         f"finetune's weight), not {alphas}")
         if family_options is not None:
             raw["merge_options"] = family_options
             return cls(**raw)

@@ -25,7 +25,7 @@ struct smhip_ctx {
 // The argument checks that smhip_ties_merge, smhip_dare_merge and smhip_breadcrumbs_merge share: their descriptors have
 // the same leading fields (k .. normalize), hence the template.  `op` names the entry point in the messages.
 // smhip_geo_merge shares all of it but the scalars (`scalars`: the operator's own checks, after k and the dtypes) and,
-// in weight space, the bases (`need_base` = false: they are not read and may be NULL).
+// in weight space, the bases (`need_base` = false: they are not read and may be NULL); smhip_sce_merge all but the scalars.
 template <class Desc, class Scalars>
 static int delta_tensor_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out,
                               bool need_base, Scalars scalars) {
@@ -233,6 +233,25 @@ int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* d, void* out, float* d
     if (d->n > 0 && (d->rows < 1 || d->n % d->rows)) return ctx->pipe.fail(SMHIP_ERR_ARG, "geo_merge: rows must divide n");
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.geo_merge(*d, out, delta_out, report));
+}
+
+int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* d, void* out, float* delta_out, smhip_sce_report* report,
+                    void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "sce_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!(d->select_topk > 0.0 && d->select_topk <= 1.0)) return "select_topk must be in (0, 1]";
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            double sum = 0.0;
+            for (int i = 0; i < d->k; ++i) {
+                if (!(d->alpha[i] >= 0.0) || !std::isfinite(d->alpha[i])) return "every alpha must be >= 0 and finite";
+                sum += d->alpha[i];
+            }
+            if (!(sum > 0.0) || !std::isfinite(sum)) return "the alphas need a sum > 0";
+            return nullptr;
+        }))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.sce_merge(*d, out, delta_out, report));
 }
 
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {

@@ -20,6 +20,7 @@
 #include "sm_dare.hpp"
 #include "sm_breadcrumbs.hpp"
 #include "sm_geo.hpp"
+#include "sm_sce.hpp"
 
 namespace smhip {
 
@@ -230,6 +231,16 @@ SM_KERNEL_TAG_LB(KGeoGramTiled, GeoGramParams, "geo_gram", k_geo_gram<true>(ex, 
 SM_KERNEL_TAG_LB(KGeoFold, GeoFoldParams, "geo_gram_fold", k_geo_fold(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KGeoCoef, GeoCoefParams, "geo_coef", k_geo_coef(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KGeoCombine, GeoCombineParams, "geo_combine", k_geo_combine(ex, p), 256, 4)
+// SCE merge (sm_sce.hpp): the one-stream radix level over the variance scores, its scan, the masked ordered fp64 energies
+// and their fold, the fused merge pass; k <= 4 deltas per octet in registers, or up to 16
+SM_KERNEL_TAG_LB(KSceHist, SceHistParams, "sce_hist", k_sce_hist<SCE_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KSceHistAny, SceHistParams, "sce_hist", k_sce_hist<TIES_MAX_MODELS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KSceSelect, SceSelectParams, "sce_select", k_sce_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KSceEnergy, SceEnergyParams, "sce_energy", k_sce_energy<SCE_REG_SMALL>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KSceEnergyAny, SceEnergyParams, "sce_energy", k_sce_energy<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 2)
+SM_KERNEL_TAG_LB(KSceFold, SceFoldParams, "sce_energy_fold", k_sce_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KSceMerge, SceMergeParams, "sce_merge", k_sce_merge<SCE_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KSceMergeAny, SceMergeParams, "sce_merge", k_sce_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -256,8 +267,9 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
-    X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs and the geometric merges
+    X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) \
+    X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges and SCE
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2675,6 +2687,99 @@ class Pipeline {
             for (int i = 0; i < k; ++i) rep->c[i] = m.c[i];
         }
         be.template launch<KGeoCombine>(cgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+        return SMHIP_OK;
+    }
+
+    // ---- SCE merge (sm_sce.hpp; the function is stated in shardmerge_hip.h, smhip_sce_merge): the three levels of the ONE
+    // selection stream (skipped when select_topk == 1 or k == 1), the energy pass and its fold, ONE readback (flags, the
+    // selection's results, the energies), the weights on the host, the merge pass.  Workspace (the TIES buffer):
+    // the three levels' histograms [3][HIST1_BINS] | SceHead | the segments' sums [nseg][k] ----
+    struct SceHead { uint32_t flags[2]; SceState sel; double E[TIES_MAX_MODELS]; };
+    int sce_merge(const smhip_sce_desc& d, void* out, float* delta_out, smhip_sce_report* rep) {
+        const int k = d.k;
+        const bool select = !(d.select_topk == 1.0 || k == 1);
+        smhip_sce_report r{};
+        auto weights = [&](const double* E, float* w) {           // step 3 on the host: one IEEE fp64 operation each
+            double P[TIES_MAX_MODELS], Z = 0.0;
+            for (int i = 0; i < k; ++i) { P[i] = geo_dmul(d.alpha[i], E[i]); Z = geo_dadd(Z, P[i]); }
+            for (int i = 0; i < k; ++i) w[i] = (Z > 0.0 && geo_finite(Z)) ? (float)geo_ddiv(P[i], Z) : (float)geo_ddiv(1.0, (double)k);
+        };
+        if (d.n == 0) {                                  // nothing selected (k_keep == 0: the threshold is +inf), no energy
+            r.threshold = select ? INFINITY : 0.f;
+            weights(r.energy, r.weight);
+            if (rep) *rep = r;
+            return SMHIP_OK;
+        }
+        if (rep) *rep = r;
+        SceMergeParams m;
+        {   // (a smhip_sce_desc has the leading fields of the delta-merge descriptors but for density and normalize)
+            TiesInputs& in = m.in;
+            in.k = k; in.dtype = d.in_dtype; in.n = d.n;
+            bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
+            for (int i = 0; i < TIES_MAX_MODELS; ++i) {
+                in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
+                al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
+                shared = shared && in.base[i] == in.base[0];
+                m.w[i] = 0.f;
+            }
+            in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
+            m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
+            m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
+            m.lambda = (float)d.lambda;
+            m.out = out; m.delta_out = delta_out;
+            m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+        }
+        const bool small = k <= SCE_REG_SMALL;
+        const size_t nseg = (d.n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
+        const size_t hist_bytes = (size_t)3 * HIST1_BINS * sizeof(unsigned long long);
+        const size_t off_head = hist_bytes, off_part = round_up(off_head + sizeof(SceHead), 256);
+        int rc;
+        if ((rc = ensure(ties_, off_part + nseg * k * sizeof(double)))) return rc;
+        be.memset(ties_.p, 0, off_head + sizeof(SceHead), stream);
+        SceHead* head = (SceHead*)((char*)ties_.p + off_head);
+        m.select = select ? 1 : 0; m.state = &head->sel;
+
+        if (select) {
+            const size_t noct = (d.n + 7) / 8;
+            SceHistParams h;
+            h.in = m.in; h.state = &head->sel; h.flags = head->flags;
+            h.chunks = pick_chunks(noct, 256, 4, 5);
+            const int hgrid = stream_grid(noct, 256, h.chunks);
+            SceSelectParams s;
+            s.n = d.n; s.select_topk = d.select_topk; s.state = &head->sel;
+            for (int level = 1; level <= 3; ++level) {
+                h.level = level; h.hist = (unsigned long long*)ties_.p + (size_t)(level - 1) * HIST1_BINS;
+                const size_t hlds = (LDS_SCRATCH_FLOATS + (size_t)(level == 1 ? HIST1_BINS : HIST_LO_BINS) + 1) * 4;
+                if (small) be.template launch<KSceHist>(hgrid, 256, hlds, h, stream);
+                else be.template launch<KSceHistAny>(hgrid, 256, hlds, h, stream);
+                s.level = level; s.hist = h.hist;
+                be.template launch<KSceSelect>(1, TIES_SELECT_THREADS, LDS_SCRATCH_FLOATS * 4 + TIES_SELECT_THREADS * sizeof(unsigned long long), s, stream);
+            }
+        }
+        SceEnergyParams e;
+        e.in = m.in; e.select = m.select; e.state = m.state; e.nseg = nseg; e.seg_vec = m.in.aligned;
+        e.part = (double*)((char*)ties_.p + off_part); e.flags = head->flags;
+        if (small) be.template launch<KSceEnergy>((int)nseg, GEO_THREADS, sce_energy_lds_floats<SCE_REG_SMALL>() * 4, e, stream);
+        else be.template launch<KSceEnergyAny>((int)nseg, GEO_THREADS, sce_energy_lds_floats<TIES_MAX_MODELS>() * 4, e, stream);
+        SceFoldParams f;
+        f.k = k; f.nseg = nseg; f.part = e.part; f.E = head->E;
+        be.template launch<KSceFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+
+        SceHead host;
+        if ((rc = delta_readback("sce_merge", k, head, host))) return rc;     // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                        // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
+        if (select) {
+            r.nz = d.n - host.sel.zeros; r.k_keep = host.sel.k_keep; r.selected = host.sel.selected; r.threshold = host.sel.threshold;
+        } else {                                             // every element is selected: every q >= +0 reaches a threshold of 0
+            r.nz = r.k_keep = r.selected = d.n; r.threshold = 0.f;
+        }
+        for (int i = 0; i < k; ++i) r.energy[i] = host.E[i];
+        weights(r.energy, r.weight);
+        for (int i = 0; i < k; ++i) m.w[i] = r.weight[i];
+        if (rep) *rep = r;
+        const int mgrid = stream_grid((d.n + 7) / 8, 256, m.chunks);
+        if (small) be.template launch<KSceMerge>(mgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+        else be.template launch<KSceMergeAny>(mgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
         return SMHIP_OK;
     }
 

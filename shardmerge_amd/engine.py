@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -93,6 +94,16 @@ class GeoMergeReport:
     t_min: float = 0.0                                               # row-wise: over the rows' t
     t_max: float = 0.0
     t_mean: float = 0.0
+
+
+@dataclass
+class SceMergeReport:
+    nz: int = 0                                                      # elements whose variance score q is > 0
+    k_keep: int = 0                                                  # floor(select_topk * nz): elements asked for
+    selected: int = 0                                                # elements selected (ties at the threshold included)
+    threshold: float = 0.0                                           # tau: the k_keep-th largest q (+inf: nothing selected)
+    energies: List[float] = field(default_factory=list)              # E_i: the fp64 sum of squares of what finetune i kept
+    weights: List[float] = field(default_factory=list)               # w_i (fp32)
 
 
 @dataclass
@@ -369,7 +380,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -548,6 +559,39 @@ class Engine:
         if not rowwise:
             report.gram = [[float(rep.G[i][j]) for j in range(k)] for i in range(k)]
             report.coefficients = [float(rep.c[i]) for i in range(k)]
+        return (out, report, delta) if want_delta else (out, report)
+
+    # -- SCE ------------------------------------------------------------------------------
+    def sce_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                  base_out: torch.Tensor, *, select_topk: float = 1.0, lam: float = 1.0, want_delta: bool = False,
+                  layer_name: Optional[str] = None):
+        """SCE merge of one tensor of any shape (``smhip_sce_merge``; the function is stated in
+        include/shardmerge_hip.h): the elements whose deltas ``finetune_i - base_i`` vary most across the finetunes are
+        selected (the ``select_topk`` share of the nonzero variances, ties at the threshold all kept; everything when
+        ``select_topk`` is 1 or there is one finetune), each finetune is weighted by ``alpha_i`` times the fp64 energy of
+        its selected entries, normalised over the finetunes, a sign is elected per element by the unweighted sum, the
+        agreeing entries are summed and divided by the sum of their weights, times ``lam``, added onto ``base_out`` in
+        its dtype.  Returns (out, SceMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta raises ValueError
+        naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if not (0.0 < float(select_topk) <= 1.0):
+            raise ValueError(f"sce_merge: select_topk {select_topk} is not in (0, 1]")
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"sce_merge: lam {lam} is not finite")
+        total = 0.0
+        for a in alphas:
+            if not (float(a) >= 0.0) or not math.isfinite(float(a)):
+                raise ValueError(f"sce_merge: the alphas must be >= 0 and finite, not {list(alphas)}")
+            total += float(a)
+        if len(alphas) and not (0.0 < total < math.inf):
+            raise ValueError(f"sce_merge: the alphas need a sum > 0, not {list(alphas)}")
+        desc, rep, k = _lib.SceDesc(), _lib.SceReport(), len(finetunes)
+        desc.select_topk, desc.lam = float(select_topk), float(lam)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "sce_merge")
+        desc.n = bo.numel()
+        self._run_delta_merge(self.lib.dll.smhip_sce_merge, desc, rep, out, delta, layer_name)
+        report = SceMergeReport(nz=int(rep.nz), k_keep=int(rep.k_keep), selected=int(rep.selected), threshold=float(rep.threshold),
+                                energies=[float(rep.energy[i]) for i in range(k)], weights=[float(rep.weight[i]) for i in range(k)])
         return (out, report, delta) if want_delta else (out, report)
 
     def correlate_pairs(self, tensors) -> torch.Tensor:

@@ -15,6 +15,7 @@ _OPERATOR_CLASSES = {
     "model_stock": ("geometric", "ModelStockMerge"),
     "nuslerp": ("geometric", "NuSlerpMerge"),
     "slerp": ("geometric", "SlerpMerge"),
+    "sce": ("sce", "SceMerge"),
 }
 
 
