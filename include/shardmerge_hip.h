@@ -451,6 +451,65 @@ typedef struct {
 int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* desc, void* out, float* delta_out,
                     smhip_sce_report* report, void* stream);
 
+/* ---- DELLA merge (Deep et al., "DELLA-Merging", 2024; mergekit's della and della_linear): DARE whose keep probability
+ *      rises with the rank of each entry's magnitude WITHIN ITS ROW, from density - epsilon for the smallest magnitude
+ *      of a row to density + epsilon for the largest, then merged as dare_ties (della) or dare_linear (della_linear)
+ *      merges.  The reference has no such operator; this section IS its definition.  For one tensor of n elements seen as
+ *      R = rows rows of c elements (n = R * c), finetunes i = 0..k-1 in order (1 <= k <= 16):
+ *        1. Deltas.  d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with
+ *           SMHIP_ERR_NONFINITE (the message lists the finetunes); out is then unspecified.
+ *        2. Arguments.  0 < density <= 1 and 0 <= epsilon; density == 1 requires epsilon == 0; otherwise
+ *           density + epsilon < 1 and floor((density - epsilon) * 65536) >= 1, evaluated in fp64; rows >= 1 divides n;
+ *           anything else is SMHIP_ERR_ARG.  c > 32768 with epsilon > 0 is SMHIP_ERR_SHAPE (the message gives c and
+ *           the limit): a row is sorted in the 160 KiB LDS of one compute unit.
+ *        3. Rank.  For element j in row rho of finetune i, r_ij is the number of elements of that row of d_i whose
+ *           magnitude is STRICTLY SMALLER than |d_ij|: 0 <= r_ij <= c - 1.  The comparison is on the 31 magnitude bits as
+ *           unsigned integers (-0 == +0).  TIE RULE: equal magnitudes share a rank, so the result does not depend on
+ *           any traversal or sort order - unlike an argsort, which ranks tied elements arbitrarily.
+ *        4. Threshold, in fp64, each operation rounded once, in this order: p_lo = density - epsilon; w = 2 * epsilon;
+ *           p_ij = p_lo + (w * (double) r_ij) / (double)(c - 1), or p_lo when c == 1;
+ *           T_ij = min((uint32) floor(p_ij * 65536), 65535).  density == 1: T_ij = 65536.  epsilon == 0:
+ *           T_ij = floor(density * 65536) for every element and no ranking runs.
+ *        5. Mask.  The draw h of smhip_dare_merge step 3, unchanged: Philox4x32-10, counter (j >> 3, stream_id[i], 0)
+ *           under key, j the element's FLAT index in the whole tensor.  The element is KEPT iff h < T_ij and d_ij != 0.
+ *        6. s_ij = 1 if rescale == 0, else fp32(65536.0 / T_ij) (fp64 division, rounded once, then to fp32);
+ *           tv_ij = fl32(fl32(d_ij * s_ij) * fp32(alpha_i)) where kept, +0 elsewhere.
+ *        7. Steps 5 and 6 of smhip_dare_merge, unchanged: sign_election == 1 is della, 0 is della_linear; normalize,
+ *           lambda, out and delta_out as there.
+ *      Every step is an integer function, an exact count or one correctly rounded operation: the result is defined bit
+ *      for bit.  IDENTITY: with epsilon == 0 the call equals smhip_dare_merge with the same remaining arguments, for
+ *      either sign_election and any key; it then runs that kernel and ranks nothing (so does density == 1).  Otherwise
+ *      the tensor is processed in slabs of whole rows (at most 2^26 elements per finetune): one work-group per finetune
+ *      and row sorts the row's magnitude keys in LDS and writes T_ij as uint16 to a workspace of 2 k bytes per slab
+ *      element, then one fused pass merges the slab.  threshold_out (optional, a debugging output in the spirit of
+ *      delta_out): device uint16 [k][n], receives T_ij; written only when density < 1.  Aliasing, alignment, n == 0 and
+ *      the one synchronisation at the end of the call: the rules of smhip_ties_merge.  Profile names: "della_table"
+ *      (T as a function of the rank, once per call), "della_rank" and "della_merge" (once per slab each). ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double density, lambda; int normalize;
+    uint64_t key;
+    uint32_t stream_id[SMHIP_MAX_MODELS];
+    int rescale;                            /* 1: a survivor times fp32(65536 / T_ij); 0: left as it is */
+    int sign_election;                      /* 1: della; 0: della_linear */
+    double epsilon;                         /* half the width of the keep-probability window */
+    size_t rows;                            /* R: the rows the ranks are taken in, c = n / rows */
+} smhip_della_desc;
+typedef struct {
+    uint32_t T_lo, T_hi;                    /* the thresholds of rank 0 and of rank c - 1 */
+    uint64_t kept[SMHIP_MAX_MODELS];        /* elements of finetune i that were kept */
+} smhip_della_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n].  threshold_out (optional): device uint16
+ * [k][n].  report (optional): HOST. */
+int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* desc, void* out, float* delta_out, uint16_t* threshold_out,
+                      smhip_della_report* report, void* stream);
+
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector
  *      v1 - v0 dot is normalised along the LAST dimension (F.normalize(dim=-1), eps 1e-12), out = v0 cos + rel sin.
@@ -535,7 +594,9 @@ int smhip_reference_cpu_norm(smhip_ctx* ctx, const void* x, const void* base, in
  *      receive (another realisation of the same statistics; default 0);
  *      "spectral_intermediates" = 0 makes a K >= 3 tournament materialise every intermediate
  *      (inverse transform to fp32, forward again) as round 1 of this library did, instead of
- *      keeping it in the spectral domain (default 1). ----------------------------------- */
+ *      keeping it in the spectral domain (default 1);
+ *      "della_slab_rows" = r makes smhip_della_merge rank and merge r rows at a time (0, the default: as many whole
+ *      rows as hold at most 2^26 elements per finetune); the result does not depend on it. ------- */
 int smhip_debug_option(smhip_ctx* ctx, const char* key, long value);
 /* test hook, read side: "spec_hit" = 1 if the last speculative blend's guess was confirmed, 0 if it was voided;
  * "spec_checked" / "spec_hits": how many speculations this context has checked / confirmed since it was created;

@@ -139,6 +139,19 @@ class SceReport(C.Structure):
                 ("energy", C.c_double * MAX_MODELS), ("weight", C.c_float * MAX_MODELS)]
 
 
+class DellaDesc(C.Structure):
+    """smhip_della_desc: smhip_dare_desc, then epsilon and rows"""
+    _fields_ = DareDesc._fields_ + [("epsilon", C.c_double), ("rows", C.c_size_t)]
+
+
+class DellaReport(C.Structure):
+    """smhip_della_report"""
+    _fields_ = [("T_lo", C.c_uint32), ("T_hi", C.c_uint32), ("kept", C.c_uint64 * MAX_MODELS)]
+
+
+DELLA_MAX_COLS = 32768          # the longest row smhip_della_merge ranks (a row is sorted in LDS)
+
+
 class LayerReport(C.Structure):
     _fields_ = [
         ("target_norm", C.c_double),
@@ -192,6 +205,7 @@ class SmhipLibrary:
         d.smhip_breadcrumbs_merge.argtypes = [P, C.POINTER(BreadcrumbsDesc), P, P, C.POINTER(BreadcrumbsReport), P]
         d.smhip_geo_merge.argtypes = [P, C.POINTER(GeoDesc), P, P, C.POINTER(GeoReport), P]
         d.smhip_sce_merge.argtypes = [P, C.POINTER(SceDesc), P, P, C.POINTER(SceReport), P]
+        d.smhip_della_merge.argtypes = [P, C.POINTER(DellaDesc), P, P, P, C.POINTER(DellaReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

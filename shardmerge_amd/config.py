@@ -64,6 +64,20 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # select_topk: 1.0        #   0 < select_topk <= 1: the share of the nonzero variances that is selected (ties at the
                                 #   threshold all kept); 1: everything (mergekit's name and default)
       # sce_lambda: 1.0         #   scales the merged delta
+                                # | della | della_linear (DELLA, Deep et al. 2024, mergekit's della / della_linear; no
+                                #   counterpart in the reference): dare_ties / dare_linear whose keep probability rises
+                                #   with the rank of the entry's magnitude within its row (the tensor's last dimension), from
+                                #   density - epsilon for the smallest to density + epsilon for the largest; equal
+                                #   magnitudes share a rank; a survivor is rescaled by the inverse of its own probability.
+                                #   Rows of more than 32768 elements are an error.  The spectral keys, norm_mode,
+                                #   task_add_models and every other family's keys are rejected; its keys:
+      # density: 0.5            #   0 < density <= 1; density 1 requires epsilon 0
+      # epsilon: 0.15           #   >= 0, density + epsilon < 1 and floor((density - epsilon) * 65536) >= 1 (the mask draws
+                                #   16 bits per element); 0: dare_ties / dare_linear bit for bit
+      # della_lambda: 1.0       #   scales the merged delta
+      # della_normalize: 1      #   1: divide by the sum of the weights (della: of the agreeing entries), 0: plain sum
+      # della_rescale: 1        #   1: survivors times 1 / their effective probability, 0: left as they are
+      # seed: 0                 #   as with dare_ties: an integer in [0, 2^63)
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -90,7 +104,7 @@ MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
-             "model_stock", "nuslerp", "slerp", "sce")
+             "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them take `density`), seed stays an int (it must survive exactly), every other value becomes a float.
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
@@ -103,6 +117,8 @@ GEO_OPERATORS = ("model_stock", "nuslerp", "slerp")      # the geometric family:
 GEO_PAIR_OPERATORS = ("nuslerp", "slerp")                # ... of exactly two finetune_merge entries
 GEO_OPTION_DEFAULTS = {"stock_filter_wise": 0.0}
 SCE_OPTION_DEFAULTS = {"select_topk": 1.0, "sce_lambda": 1.0}
+DELLA_OPERATORS = ("della", "della_linear")
+DELLA_OPTION_DEFAULTS = {"density": 0.5, "epsilon": 0.15, "della_lambda": 1.0, "della_normalize": 1.0, "della_rescale": 1.0, "seed": 0}
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -111,6 +127,33 @@ def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
     if not (density + gamma <= 1.0):
         raise click.BadParameter(f"merge_options.density + merge_options.gamma must not exceed 1 (density {density:g}, gamma {gamma:g}): "
                                  "the dropped top and the kept band cannot overlap")
+
+
+def della_thresholds(density: float, epsilon: float, cols: int = 2):
+    """(T_lo, T_hi) of smhip_della_merge, step 4 in fp64: the thresholds of rank 0 and of rank cols - 1"""
+    if density == 1:
+        return 65536, 65536
+    if epsilon == 0:
+        return (int(float(density) * 65536.0),) * 2
+    p_lo, w = float(density) - float(epsilon), 2.0 * float(epsilon)
+    t = lambda r: min(int((p_lo + (w * float(r)) / float(cols - 1) if cols > 1 else p_lo) * 65536.0), 65535)
+    return t(0), t(cols - 1)
+
+
+def _della_window(opts: Dict[str, Any]) -> None:
+    """the argument rules of smhip_della_merge (include/shardmerge_hip.h, step 2), in fp64"""
+    density = float(opts.get("density", DELLA_OPTION_DEFAULTS["density"]))
+    epsilon = float(opts.get("epsilon", DELLA_OPTION_DEFAULTS["epsilon"]))
+    if density == 1.0:
+        if epsilon != 0.0:
+            raise click.BadParameter(f"merge_options.density 1 keeps everything and requires merge_options.epsilon 0 (epsilon {epsilon:g})")
+        return
+    if not (density + epsilon < 1.0):
+        raise click.BadParameter(f"merge_options.density + merge_options.epsilon must be below 1 (density {density:g}, epsilon {epsilon:g}): "
+                                 "the largest magnitude of a row is kept with probability density + epsilon")
+    if not (int((density - epsilon) * 65536.0) >= 1):
+        raise click.BadParameter(f"floor((merge_options.density - merge_options.epsilon) * 65536) must be at least 1 (density {density:g}, "
+                                 f"epsilon {epsilon:g}): the mask draws 16 bits per element")
 
 
 @dataclass(frozen=True)
@@ -145,6 +188,13 @@ _OPTION_FAMILIES = (                                # in the order they were add
                   earlier={"ties": "(its keys: select_topk, sce_lambda)", "dare_ties": "(it drops nothing at random)",
                            "breadcrumbs": "(it selects by the variance across the finetunes, not by magnitude)",
                            "model_stock": "(its weights come from the energies, per tensor)"}),
+    _OptionFamily(DELLA_OPERATORS, DELLA_OPTION_DEFAULTS,
+                  {"density": _DENSITY, "epsilon": (0, 1, "[)"), "della_lambda": _LAMBDA, "della_normalize": "flag", "della_rescale": "flag",
+                   "seed": "seed"},
+                  earlier={"ties": "(its keys: della_lambda, della_normalize)", "dare_ties": "(its keys: della_lambda, della_normalize, della_rescale)",
+                           "breadcrumbs": "(its drop is random, by the rank of the magnitude within the row)",
+                           "model_stock": "(it drops at random and weights by alpha)", "sce": "(it selects nothing by variance)"},
+                  check=_della_window),
 )
 
 

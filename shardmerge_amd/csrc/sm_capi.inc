@@ -254,6 +254,40 @@ int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* d, void* out, float* d
     SM_FINISH(ctx, ctx->pipe.sce_merge(*d, out, delta_out, report));
 }
 
+int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* d, void* out, float* delta_out, uint16_t* threshold_out,
+                      smhip_della_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "della_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!(d->density > 0.0 && d->density <= 1.0)) return "density must be in (0, 1]";
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            if (!(d->epsilon >= 0.0)) return "epsilon must be >= 0";
+            if (d->density == 1.0) return d->epsilon == 0.0 ? nullptr : "density 1 keeps everything: it requires epsilon 0";
+            if (d->epsilon == 0.0)
+                return ctx->pipe.dare_threshold(d->density) >= 1 ? nullptr : "density is below the smallest density, 2^-16 = 1.52587890625e-05 (the mask draws 16 bits per element)";
+            if (!(d->density + d->epsilon < 1.0)) return "density + epsilon must be below 1";
+            if (!(std::floor((d->density - d->epsilon) * 65536.0) >= 1.0)) return "floor((density - epsilon) * 65536) must be at least 1 (the mask draws 16 bits per element)";
+            return nullptr;
+        }))
+        return rc;
+    if (d->n > 0) {
+        if (d->rows < 1 || d->n % d->rows) return ctx->pipe.fail(SMHIP_ERR_ARG, "della_merge: rows must divide n");
+        const size_t c = d->n / d->rows;
+        if (d->epsilon > 0.0 && c > (size_t)smhip::DELLA_MAX_COLS)
+            return ctx->pipe.fail(SMHIP_ERR_SHAPE, "della_merge: rows of c = " + std::to_string(c) + " elements exceed the limit of " +
+                                                       std::to_string(smhip::DELLA_MAX_COLS) + " (a row is sorted in the LDS of one compute unit)");
+        if (threshold_out) {
+            const uintptr_t t0 = (uintptr_t)threshold_out, t1 = t0 + (size_t)d->k * d->n * 2;
+            const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
+            auto hits = [&](const void* p, size_t bytes) { return p && (uintptr_t)p < t1 && t0 < (uintptr_t)p + bytes; };
+            bool hit = t0 % 2 != 0 || hits(out, d->n * oes) || hits(delta_out, d->n * 4) || hits(d->base_out, d->n * oes);
+            for (int i = 0; i < d->k; ++i) hit = hit || hits(d->finetune[i], d->n * ies) || hits(d->base[i], d->n * ies);
+            if (hit) return ctx->pipe.fail(SMHIP_ERR_ARG, "della_merge: threshold_out is misaligned or overlaps another tensor");
+        }
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.della_merge(*d, out, delta_out, threshold_out, report));
+}
+
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {
     SM_GUARD(ctx);
     if (rows * cols > 0 && (!v0 || !v1 || !out)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");
@@ -371,6 +405,7 @@ int smhip_debug_option(smhip_ctx* ctx, const char* key, long value) {
     if (key && std::string(key) == "force_bluestein") { ctx->pipe.debug_force_bluestein = value != 0; return SMHIP_OK; }
     if (key && std::string(key) == "force_split") { ctx->pipe.debug_force_split = value > 1 && value <= smhip::DFTP_MAX_P ? (int)value : 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_columns") { ctx->pipe.fold_enabled = value != 0; return SMHIP_OK; }
+    if (key && std::string(key) == "della_slab_rows") { ctx->pipe.della_slab_rows = value > 0 ? (size_t)value : 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_min_rows") { ctx->pipe.fold_min_rows = value > 0 ? (int)value : SM_FOLD_MIN_ROWS; return SMHIP_OK; }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug option");
 }

@@ -21,6 +21,7 @@
 #include "sm_breadcrumbs.hpp"
 #include "sm_geo.hpp"
 #include "sm_sce.hpp"
+#include "sm_della.hpp"
 
 namespace smhip {
 
@@ -241,6 +242,11 @@ SM_KERNEL_TAG_LB(KSceEnergyAny, SceEnergyParams, "sce_energy", k_sce_energy<TIES
 SM_KERNEL_TAG_LB(KSceFold, SceFoldParams, "sce_energy_fold", k_sce_fold(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KSceMerge, SceMergeParams, "sce_merge", k_sce_merge<SCE_REG_SMALL>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KSceMergeAny, SceMergeParams, "sce_merge", k_sce_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
+// DELLA merge (sm_della.hpp): T as a function of the rank, the whole-row sort in LDS (one work-group per finetune and row,
+// up to 1024 threads), the fused pass with a threshold per element
+SM_KERNEL_TAG_LB(KDellaTable, DellaTableParams, "della_table", k_della_table(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KDellaRank, DellaRankParams, "della_rank", k_della_rank(ex, p), 1024, 4)
+SM_KERNEL_TAG_LB(KDellaMerge, DellaMergeParams, "della_merge", k_della_merge(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -268,8 +274,9 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) \
-    X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges and SCE
+    X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny) \
+    X(KDellaTable) X(KDellaRank) X(KDellaMerge)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE and DELLA
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2507,6 +2514,91 @@ class Pipeline {
 
         DareReadback host;
         if ((rc = delta_readback("dare_merge", k, rb, host))) return rc;
+        if (rep)
+            for (int i = 0; i < k; ++i) rep->kept[i] = host.kept[i];
+        return SMHIP_OK;
+    }
+
+    // ---- DELLA merge (sm_della.hpp; the function is stated in shardmerge_hip.h, smhip_della_merge).  epsilon == 0 or
+    // density == 1: the uniform threshold, dare_merge itself.  Otherwise slabs of whole rows: rank all k finetunes of a slab
+    // into the workspace, merge the slab; the mask index stays the flat index in the tensor.  Workspace (the TIES buffer):
+    // DareReadback | the table T(rank) [c] | uint16 [k][stride] ----
+    size_t della_slab_rows = 0;               // test hook "della_slab_rows": rows per slab (0: at most 2^26 elements per finetune)
+    static constexpr size_t DELLA_SLAB_ELEMS = (size_t)1 << 26;
+    int della_merge(const smhip_della_desc& d, void* out, float* delta_out, uint16_t* threshold_out, smhip_della_report* rep) {
+        const int k = d.k;
+        const bool uniform = d.epsilon == 0.0 || d.density == 1.0;
+        const double p_lo = d.density - d.epsilon, w = 2.0 * d.epsilon;
+        const size_t c = d.n ? d.n / d.rows : 1;
+        const uint32_t T_lo = uniform ? dare_threshold(d.density) : della_threshold(p_lo, w, 0u, (uint32_t)c);
+        const uint32_t T_hi = uniform ? T_lo : della_threshold(p_lo, w, (uint32_t)(c - 1), (uint32_t)c);
+        if (rep) {
+            rep->T_lo = T_lo; rep->T_hi = T_hi;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
+        }
+        if (d.n == 0) return SMHIP_OK;
+        int rc;
+        if (uniform) {
+            smhip_dare_desc dd;
+            dd.k = k;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) {
+                dd.finetune[i] = d.finetune[i]; dd.base[i] = d.base[i]; dd.alpha[i] = d.alpha[i]; dd.stream_id[i] = d.stream_id[i];
+            }
+            dd.in_dtype = d.in_dtype; dd.base_out = d.base_out; dd.base_out_dtype = d.base_out_dtype; dd.n = d.n;
+            dd.density = d.density; dd.lambda = d.lambda; dd.normalize = d.normalize;
+            dd.key = d.key; dd.rescale = d.rescale; dd.sign_election = d.sign_election;
+            if (threshold_out && d.density < 1.0) {
+                DellaTableParams t;
+                t.out = threshold_out; t.count = (size_t)k * d.n; t.c = 1; t.p_lo = 0.0; t.w = 0.0; t.fill = T_lo;
+                if ((t.count + 255) / 256 > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "della_merge: tensor too large for threshold_out");
+                be.template launch<KDellaTable>((int)((t.count + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, t, stream);
+            }
+            smhip_dare_report dr;
+            if ((rc = dare_merge(dd, out, delta_out, &dr))) {
+                if (rc == SMHIP_ERR_NONFINITE) err.replace(0, 4, "della");      // "dare_merge: ..." names this entry point
+                return rc;
+            }
+            if (rep)
+                for (int i = 0; i < k; ++i) rep->kept[i] = dr.kept[i];
+            return SMHIP_OK;
+        }
+        const size_t R = d.rows;
+        size_t slab_rows = della_slab_rows ? della_slab_rows : std::max<size_t>(1, DELLA_SLAB_ELEMS / c);
+        slab_rows = std::min(slab_rows, std::min<size_t>(R, (size_t)0x7fffffff / TIES_MAX_MODELS));
+        const size_t stride = round_up(7 + slab_rows * c, 8);
+        const size_t off_table = round_up(sizeof(DareReadback), 256), off_ws = off_table + round_up(c * sizeof(uint16_t), 256);
+        if ((rc = ensure(ties_, off_ws + (size_t)k * stride * sizeof(uint16_t)))) return rc;
+        be.memset(ties_.p, 0, sizeof(DareReadback), stream);
+        DareReadback* rb = (DareReadback*)ties_.p;
+
+        DellaTableParams t;
+        t.out = (uint16_t*)((char*)ties_.p + off_table); t.count = c; t.c = (uint32_t)c; t.p_lo = p_lo; t.w = w; t.fill = 0;
+        be.template launch<KDellaTable>((int)((c + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, t, stream);
+
+        DellaMergeParams m;
+        delta_merge_params(d, out, delta_out, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.stream_id[i] = d.stream_id[i < k ? i : 0];
+        m.key = d.key; m.rescale = d.rescale ? 1 : 0;
+        m.sign_election = d.sign_election ? 1 : 0;
+        m.kept = rb->kept; m.flags = rb->flags;
+        DellaRankParams r;
+        r.in = m.in; r.c = (int)c; r.table = t.out; r.threshold_out = threshold_out; r.flags = rb->flags;
+        r.P = 8;
+        while ((size_t)r.P < c) r.P <<= 1;
+        const int rank_threads = std::min(1024, std::max(64, r.P / 8));
+        for (size_t r0 = 0; r0 < R; r0 += slab_rows) {
+            const size_t rows = std::min(slab_rows, R - r0);
+            DellaSlab s;
+            s.e0 = r0 * c; s.len = rows * c; s.stride = stride; s.ws = (uint16_t*)((char*)ties_.p + off_ws);
+            r.slab = s; r.rows = (int)rows;
+            be.template launch<KDellaRank>((int)(rows * k), rank_threads, (LDS_SCRATCH_FLOATS + (size_t)r.P) * 4, r, stream);
+            m.slab = s;
+            const size_t noct = ((s.e0 + s.len + 7) >> 3) - (s.e0 >> 3);
+            m.chunks = pick_chunks(noct, 256, 2, 8);
+            be.template launch<KDellaMerge>(stream_grid(noct, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
+        }
+        DareReadback host;
+        if ((rc = delta_readback("della_merge", k, rb, host))) return rc;
         if (rep)
             for (int i = 0; i < k; ++i) rep->kept[i] = host.kept[i];
         return SMHIP_OK;

@@ -72,6 +72,13 @@ class DareMergeReport:
 
 
 @dataclass
+class DellaMergeReport:
+    threshold_lo: int = 0                                            # T of rank 0, the smallest magnitude of a row
+    threshold_hi: int = 0                                            # T of rank c - 1
+    kept: List[int] = field(default_factory=list)                    # elements kept per finetune (zero deltas never)
+
+
+@dataclass
 class BreadcrumbsMergeReport:
     k_keep: int = 0                                                  # elements each finetune was asked to keep
     n_top: int = 0                                                   # largest magnitudes that may be dropped per finetune
@@ -491,6 +498,55 @@ class Engine:
         report = DareMergeReport(threshold=int(rep.T), density=int(rep.T) / 65536.0, kept=[int(rep.kept[i]) for i in range(k)])
         return (out, report, delta) if want_delta else (out, report)
 
+    # -- DELLA -----------------------------------------------------------------------------
+    def della_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                    base_out: torch.Tensor, *, density: float = 0.5, epsilon: float = 0.15, lam: float = 1.0, normalize: bool = True,
+                    rescale: bool = True, sign_election: bool = True, key: int = 0, stream_ids: Optional[Sequence[int]] = None,
+                    want_delta: bool = False, want_thresholds: bool = False, layer_name: Optional[str] = None):
+        """DELLA merge of one tensor (``smhip_della_merge``; the function is stated in include/shardmerge_hip.h): DARE
+        whose keep threshold rises with the rank of the entry's magnitude within its row (the last dimension; a 1-D
+        tensor is one row) from ``density - epsilon`` to ``density + epsilon``; equal magnitudes share a rank.  The
+        mask, ``key`` and ``stream_ids`` are those of ``dare_merge``, a survivor is rescaled by the inverse of ITS
+        threshold (``rescale``), and the deltas are merged as dare_ties (``sign_election``: della) or dare_linear
+        (della_linear) merges them.  ``epsilon=0`` is ``dare_merge`` bit for bit.  Returns (out, DellaMergeReport[, the
+        fp32 merged delta][, the uint16 thresholds [k, *shape]]).  A NaN or Inf in a delta raises ValueError naming
+        ``layer_name`` and the finetune; so does a row longer than 32768 when ``epsilon > 0``."""
+        layer_name = layer_name or "layer"
+        k = len(finetunes)
+        density, epsilon = float(density), float(epsilon)
+        della_arguments(density, epsilon, "della_merge")
+        stream_ids = list(range(k)) if stream_ids is None else [int(s) for s in stream_ids]
+        if len(stream_ids) != k or any(not (0 <= s < 2 ** 32) for s in stream_ids):
+            raise ValueError(f"della_merge: stream_ids must be {k} integers in [0, 2^32)")
+        if isinstance(key, bool) or not isinstance(key, int) or not (0 <= key < 2 ** 64):
+            raise ValueError("della_merge: key must be an integer in [0, 2^64)")
+        desc, rep = _lib.DellaDesc(), _lib.DellaReport()
+        desc.density, desc.lam, desc.normalize = density, float(lam), 1 if normalize else 0
+        desc.key, desc.rescale, desc.sign_election = key, 1 if rescale else 0, 1 if sign_election else 0
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "della_merge")
+        desc.n = bo.numel()
+        cols = int(bo.shape[-1]) if bo.ndim >= 1 else 1
+        if epsilon > 0.0 and cols > _lib.DELLA_MAX_COLS:
+            raise ValueError(f"della_merge: the rows of {layer_name} have c = {cols} elements, above the limit of {_lib.DELLA_MAX_COLS} "
+                             f"(a row is ranked in the LDS of one compute unit)")
+        desc.epsilon, desc.rows = epsilon, (desc.n // cols if cols else 1) or 1
+        desc.stream_id[:k] = stream_ids
+        thresholds = torch.zeros((k,) + tuple(bo.shape), dtype=torch.int16, device=self.device) if want_thresholds else None
+        try:
+            self.ctx.check(self.lib.dll.smhip_della_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
+                                                          delta.data_ptr() if delta is not None else None,
+                                                          thresholds.data_ptr() if thresholds is not None else None,
+                                                          C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
+            raise
+        report = DellaMergeReport(threshold_lo=int(rep.T_lo), threshold_hi=int(rep.T_hi), kept=[int(rep.kept[i]) for i in range(k)])
+        res = (out, report) + ((delta,) if want_delta else ())
+        if want_thresholds:     # (uint16 values in an int16 tensor: widened here, 65536 of density 1 does not fit and is never written)
+            res += (thresholds.to(torch.int32) & 0xFFFF if density < 1.0 else torch.full_like(thresholds, 65536, dtype=torch.int32),)
+        return res
+
     # -- Model Breadcrumbs ---------------------------------------------------------------
     def breadcrumbs_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
                           base_out: torch.Tensor, density: float = 0.9, gamma: float = 0.01, lam: float = 1.0,
@@ -646,6 +702,23 @@ class Engine:
         if want_delta:
             return out, report, delta
         return out, report
+
+
+def della_arguments(density: float, epsilon: float, what: str) -> None:
+    """the argument rules of smhip_della_merge (step 2), in fp64; ``what`` names the caller in the message"""
+    if not (0.0 < density <= 1.0):
+        raise ValueError(f"{what}: density {density} is not in (0, 1]")
+    if not (epsilon >= 0.0):
+        raise ValueError(f"{what}: epsilon {epsilon} must be >= 0")
+    if density == 1.0:
+        if epsilon != 0.0:
+            raise ValueError(f"{what}: density 1 keeps everything and requires epsilon 0, not epsilon {epsilon}")
+        return
+    if not (density + epsilon < 1.0):
+        raise ValueError(f"{what}: density {density} + epsilon {epsilon} must be below 1")
+    if not (math.floor((density - epsilon) * 65536.0) >= 1):
+        raise ValueError(f"{what}: floor((density - epsilon) * 65536) must be at least 1 (the mask draws 16 bits per element), "
+                    f"not density {density}, epsilon {epsilon}")
 
 
 _engines: Dict[str, Engine] = {}

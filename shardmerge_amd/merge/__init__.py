@@ -16,6 +16,8 @@ _OPERATOR_CLASSES = {
     "nuslerp": ("geometric", "NuSlerpMerge"),
     "slerp": ("geometric", "SlerpMerge"),
     "sce": ("sce", "SceMerge"),
+    "della": ("della", "DellaMerge"),
+    "della_linear": ("della", "DellaLinearMerge"),
 }
 
 
