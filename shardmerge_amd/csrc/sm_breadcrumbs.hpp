@@ -17,6 +17,7 @@
 //                  kept = (above_lo + count at tau_lo) - above_hi and dropped_top = above_hi are final.
 //   crumbs_merge   the fused streaming pass of ties_merge with the two-sided test tau_lo <= key <= tau_hi && key != 0
 //                  and the sign_election switch (0: the linear sum of dare_merge).
+// The walk, the loader, the election and the radix step are sm_delta.hpp's; here are the two prefixes and the two-sided test.
 // Tensor passes: 3 (K + 1) for the selection + (K + 2) for the merge when the base is shared - TIES's 4K + 5.
 #pragma once
 #include "sm_ties.hpp"
@@ -25,19 +26,11 @@ namespace smhip {
 
 constexpr int CRUMBS_HI = 0, CRUMBS_LO = 1;   // the two ranks of a finetune: its state is state[2 * i + which]
 
-// selection state of one rank of one finetune (device memory)
-struct CrumbsState {
-    unsigned long long rank;    // 1-based rank (from the largest) wanted among the keys that share `prefix`
-    unsigned long long above;   // keys known to be larger than every key with this prefix
-    uint32_t prefix;            // key bits decided so far (11, 21, then all 31: the threshold)
-    uint32_t pad;
-};
-
 struct CrumbsHistParams {
     TiesInputs in;
     int first, count;           // the finetunes of this launch: first .. first + count - 1, count <= TIES_GROUP
     int level;                  // 1, 2 or 3
-    const CrumbsState* state;   // [k][2]
+    const RadixState* state;    // [k][2]
     unsigned long long* hist;   // [k][HIST1_BINS] of this level (levels 2, 3: [k][2][HIST_LO_BINS])
     uint32_t* flags;            // [0]: bit i = finetune i has a non-finite delta
     int chunks;                 // octets per thread
@@ -47,66 +40,47 @@ SM_HD void k_crumbs_hist(Ex& ex, const CrumbsHistParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
     uint32_t* lh = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [count][HIST1_BINS] at every level
-    const int nt = ex.nthreads();
-    const size_t noct = (p.in.n + 7) / 8;
-    ex.each(st, [&](int tid, EmptyState&) { for (int b = tid; b < HIST1_BINS * p.count; b += nt) lh[b] = 0; });
-    ex.sync();
+    hist_zero(ex, st, lh, HIST1_BINS * p.count);
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         uint32_t bad = 0;
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oi = start + (size_t)q * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
             float b[8];
-            if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
+            delta_base8(p.in, o, b);
             for (int j = 0; j < p.count; ++j) {
                 const int i = p.first + j;
                 float f[8];
-                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);
-                if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                delta_load8(p.in, i, o, b, f);
                 const uint32_t phi = p.level == 1 ? 0u : p.state[2 * i + CRUMBS_HI].prefix;
                 const uint32_t plo = p.level == 1 ? 0u : p.state[2 * i + CRUMBS_LO].prefix;
                 uint32_t* h0 = lh + j * HIST1_BINS;
                 uint32_t* h1 = h0 + HIST_LO_BINS;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    if (e < cnt) {
-                        const uint32_t key = f2u(f[e] - b[e]) & 0x7fffffffu;
-                        if (p.level == 1) {
-                            if (key >= TIES_KEY_INF) bad |= 1u << i;
-                            ex.lds_atomic_add(&h0[key >> 20], 1u);
-                        } else {
-                            // equal prefixes: the first test takes every such key, [1] stays empty (the shared histogram)
-                            const uint32_t top = p.level == 2 ? key >> 20 : key >> 10;
-                            const uint32_t bin = p.level == 2 ? (key >> 10) & 1023u : key & 1023u;
-                            if (top == phi) ex.lds_atomic_add(&h0[bin], 1u);
-                            else if (top == plo) ex.lds_atomic_add(&h1[bin], 1u);
-                        }
+                    if (e < o.cnt) {
+                        const uint32_t key = delta_key(f[e] - b[e]);
+                        if (p.level == 1 && key >= TIES_KEY_INF) bad |= 1u << i;
+                        // equal prefixes: the first test takes every such key, [1] stays empty (the shared histogram)
+                        const int b0 = radix_bin(p.level, key, phi), b1 = radix_bin(p.level, key, plo);
+                        if (b0 >= 0) ex.lds_atomic_add(&h0[b0], 1u);
+                        else if (b1 >= 0) ex.lds_atomic_add(&h1[b1], 1u);
                     }
                 }
             }
         }
         if (bad) ex.global_atomic_or_u32(p.flags, bad);
     });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        for (int b = tid; b < HIST1_BINS * p.count; b += nt) {
-            const uint32_t v = lh[b];
-            if (v) ex.global_atomic_add(&p.hist[(size_t)p.first * HIST1_BINS + b], (unsigned long long)v);
-        }
-    });
+    hist_flush(ex, st, lh, HIST1_BINS * p.count, [&](int b) { return &p.hist[(size_t)p.first * HIST1_BINS + b]; });
 }
 
-// one work-group of TIES_SELECT_THREADS per finetune, both ranks; thread t owns TIES_SELECT_PER consecutive bins
+// one work-group of TIES_SELECT_THREADS per finetune, both ranks
 struct CrumbsSelectParams {
     int level;                       // 1, 2 or 3
     unsigned long long k_keep;       // elements to keep per finetune (0: both thresholds are +inf)
     unsigned long long rank[2];      // level 1: n_top + 1 (CRUMBS_HI), n_top + k_keep (CRUMBS_LO)
     const unsigned long long* hist;  // [k][HIST1_BINS] of this level
-    CrumbsState* state;              // [k][2]
+    RadixState* state;               // [k][2]
     float* threshold_lo;             // [k], written after level 3
     float* threshold_hi;             // [k]
     unsigned long long* kept;        // [k]
@@ -120,53 +94,26 @@ SM_HD void k_crumbs_select(Ex& ex, const CrumbsSelectParams& p) {
     unsigned long long* part = (unsigned long long*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [2][TIES_SELECT_THREADS]
     unsigned long long* fin = part + 2 * TIES_SELECT_THREADS;                            // [2][2]: above, count at the threshold
     const int m = ex.bid();
-    const int nbins = p.level == 1 ? HIST1_BINS : HIST_LO_BINS;
-    CrumbsState* s = p.state + 2 * m;
-    unsigned long long rank[2], above0[2];
-    uint32_t prefix0[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        rank[r] = p.level == 1 ? p.rank[r] : s[r].rank;
-        above0[r] = p.level == 1 ? 0ull : s[r].above;
-        prefix0[r] = p.level == 1 ? 0u : s[r].prefix;
-    }
+    const int nbins = radix_bins(p.level);
+    RadixState* s = p.state + 2 * m;
+    const RadixState s0[2] = {radix_start(p.level, p.rank[0], s[0]), radix_start(p.level, p.rank[1], s[1])};
     // level 1, or equal prefixes so far: both ranks read histogram [0] (crumbs_hist left [1] empty)
     const unsigned long long* h[2];
     h[0] = p.hist + (size_t)m * HIST1_BINS;
-    h[1] = (p.level == 1 || prefix0[0] == prefix0[1]) ? h[0] : h[0] + HIST_LO_BINS;
+    h[1] = (p.level == 1 || s0[0].prefix == s0[1].prefix) ? h[0] : h[0] + HIST_LO_BINS;
     ex.each(st, [&](int tid, CrumbsSelectState& t) {
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            unsigned long long a = 0;
-            for (int q = 0; q < TIES_SELECT_PER; ++q) {
-                const int b = tid * TIES_SELECT_PER + q;
-                if (b < nbins) a += h[r][b];
-            }
-            t.own[r] = a;
-            part[r * TIES_SELECT_THREADS + tid] = a;
-        }
+        for (int r = 0; r < 2; ++r) part[r * TIES_SELECT_THREADS + tid] = t.own[r] = radix_own_sum(h[r], nbins, tid);
     });
     ex.sync();      // (every thread has read its copy of the state above: the writes below cannot reach those reads)
     ex.each(st, [&](int tid, CrumbsSelectState& t) {
         if (p.k_keep == 0) return;    // nothing is kept: no finite magnitude reaches +inf
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            unsigned long long higher = 0;                      // keys in the bins of the threads after this one
-            for (int q = tid + 1; q < TIES_SELECT_THREADS; ++q) higher += part[r * TIES_SELECT_THREADS + q];
-            if (!(higher < rank[r] && rank[r] <= higher + t.own[r])) continue;
-            // the bin that holds the rank-th largest key is one of this thread's
-            for (int q = TIES_SELECT_PER - 1; q >= 0; --q) {
-                const int b = tid * TIES_SELECT_PER + q;
-                const unsigned long long c = b < nbins ? h[r][b] : 0ull;
-                if (rank[r] <= higher + c) {
-                    s[r].prefix = (prefix0[r] << (p.level == 1 ? 0 : 10)) | (uint32_t)b;
-                    s[r].rank = rank[r] - higher;
-                    s[r].above = above0[r] + higher;
-                    if (p.level == 3) { fin[2 * r] = above0[r] + higher; fin[2 * r + 1] = c; }
-                    break;
-                }
-                higher += c;
-            }
+            const RadixFound f = radix_select_step(h[r], nbins, part + r * TIES_SELECT_THREADS, t.own[r], s0[r].rank, tid);
+            if (!f.found) continue;
+            const RadixState s1 = s[r] = radix_advance(p.level, s0[r], f);
+            if (p.level == 3) { fin[2 * r] = s1.above; fin[2 * r + 1] = f.c; }
         }
     });
     if (p.level != 3) return;
@@ -206,62 +153,32 @@ template <class Ex>
 SM_HD void k_crumbs_merge(Ex& ex, const CrumbsMergeParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
-    const int nt = ex.nthreads();
-    const size_t noct = (p.in.n + 7) / 8;
-    const float eps = 1e-8f;
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
-        float Dall = 0.f;                                          // breadcrumbs: the sum of ALL weights, kept or not
-        for (int i = 0; i < p.in.k; ++i) Dall = aten_fadd_(Dall, p.alpha[i]);
+        const float Dall = delta_weight_sum(p.alpha, p.in.k);
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oi = start + (size_t)q * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
-            float b[8], bo[8], S[8], P[8], N[8], DP[8], DN[8];
-            if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
-            if (p.out_is_base0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bo[e] = b[e];
-            } else {
-                ties_load8(p.base_out, p.base_out_dtype, i0, cnt, vec, bo);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { S[e] = 0.f; P[e] = 0.f; N[e] = 0.f; DP[e] = 0.f; DN[e] = 0.f; }
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
+            float b[8], bo[8];
+            delta_base8(p.in, o, b);
+            delta_base_out8(p, o, b, bo);
+            Election el;
+            el.clear();
             for (int i = 0; i < p.in.k; ++i) {
                 float f[8];
-                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);
-                if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                delta_load8(p.in, i, o, b, f);
                 const uint32_t tau_lo = f2u(p.threshold_lo[i]), tau_hi = f2u(p.threshold_hi[i]);
                 const float al = p.alpha[i];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float d = f[e] - b[e];
-                    const uint32_t key = f2u(d) & 0x7fffffffu;
+                    const uint32_t key = delta_key(d);
                     const bool kept = key >= tau_lo && key <= tau_hi && key != 0u;
-                    const float tv = kept ? aten_fmul_(d, al) : 0.f;
-                    S[e] = aten_fadd_(S[e], tv);
-                    if (p.sign_election) {       // as ties_merge: the running sums of the positive and of the negative entries
-                        if (tv > 0.f) { P[e] = aten_fadd_(P[e], tv); DP[e] = aten_fadd_(DP[e], al); }
-                        if (tv < 0.f) { N[e] = aten_fadd_(N[e], tv); DN[e] = aten_fadd_(DN[e], al); }
-                    }
+                    el.add(e, kept ? aten_fmul_(d, al) : 0.f, al, p.sign_election);
                 }
             }
             float r[8], dl[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool pos = S[e] >= 0.f;
-                float M = p.sign_election ? (pos ? P[e] : N[e]) : S[e];
-                if (p.normalize) {
-                    float D = p.sign_election ? (pos ? DP[e] : DN[e]) : Dall;
-                    if (fabsf(D) < eps) D = 1.f;
-                    M = M / D;
-                }
-                dl[e] = aten_fmul_(p.lambda, M);
-                r[e] = aten_fadd_(bo[e], dl[e]);
-            }
-            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, dl);
+            el.finish(p.sign_election, p.normalize, Dall, p.lambda, bo, r, dl);
+            delta_store8(p, o, r, dl);
         }
     });
 }

@@ -10,7 +10,7 @@
 //                one Philox block, eight compares, the fp32 chain; out is written once.  Kept counts: a counter per
 //                thread and finetune in LDS, reduced per work-group, one 64-bit global atomic per finetune.
 #pragma once
-#include "sm_ties.hpp"
+#include "sm_delta.hpp"
 
 namespace smhip {
 
@@ -44,22 +44,27 @@ SM_HD void philox4x32_10(uint32_t* c, uint32_t k0, uint32_t k1) {
     }
 }
 
-// THE mask: bit e of the result is set iff element 8 * (j >> 3) + e of the finetune with this stream id draws a 16-bit
-// value below T - the octet that holds element j, from one Philox block whose counter is (j >> 3, stream_id, 0).
+// The eight 16-bit draws h of the octet that holds element j of the finetune with this stream id: one Philox block whose
+// counter is (j >> 3, stream_id, 0).
+SM_HD void dare_draws8(uint64_t key, uint32_t stream_id, uint64_t j, uint32_t* h) {
+    const uint64_t oct = j >> 3;
+    uint32_t c[4] = {(uint32_t)oct, (uint32_t)(oct >> 32), stream_id, 0u};
+    philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const uint32_t w = c[e >> 1];
+        h[e] = (e & 1) ? (w >> 16) : (w & 0xffffu);
+    }
+}
+// THE mask: bit e of the result is set iff element 8 * (j >> 3) + e draws a value below T.
 SM_HD uint32_t dare_mask8(uint64_t key, uint32_t stream_id, uint64_t j, uint32_t T) {
 #if defined(SM_DARE_NO_PHILOX)      // A/B measurement only (tools/dare_bench.py --ab-lib): no generator, every element kept
     return 0xffu;
 #endif
-    const uint64_t oct = j >> 3;
-    uint32_t c[4] = {(uint32_t)oct, (uint32_t)(oct >> 32), stream_id, 0u};
-    philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
-    uint32_t m = 0;
+    uint32_t h[8], m = 0;
+    dare_draws8(key, stream_id, j, h);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint32_t w = c[e >> 1];
-        const uint32_t h = (e & 1) ? (w >> 16) : (w & 0xffffu);
-        m |= (h < T ? 1u : 0u) << e;
-    }
+    for (int e = 0; e < 8; ++e) m |= (h[e] < T ? 1u : 0u) << e;
     return m;
 }
 
@@ -81,8 +86,6 @@ struct DareMergeParams {
     uint32_t* flags;            // [0]: bit i = finetune i has a non-finite delta
     int chunks;                 // octets per thread
 };
-// dynamic LDS beyond the scratch: a kept counter per (finetune, thread), then the k work-group totals
-SM_HD size_t dare_lds_words(int k, int nthreads) { return (size_t)k * nthreads + TIES_MAX_MODELS; }
 
 template <class Ex>
 SM_HD void k_dare_merge(Ex& ex, const DareMergeParams& p) {
@@ -90,90 +93,43 @@ SM_HD void k_dare_merge(Ex& ex, const DareMergeParams& p) {
     ex.init(st);
     const int nt = ex.nthreads();
     const int k = p.in.k;
-    uint32_t* lc = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [k][nt], then [TIES_MAX_MODELS] totals
-    uint32_t* tot = lc + (size_t)k * nt;
-    const size_t noct = (p.in.n + 7) / 8;
-    const float eps = 1e-8f;
+    uint32_t* lc = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [k][nt], then the totals (dare_lds_words)
+    kept_zero(ex, st, lc, k);
     ex.each(st, [&](int tid, EmptyState&) {
-        for (int i = 0; i < k; ++i) lc[i * nt + tid] = 0;
-        if (tid < TIES_MAX_MODELS) tot[tid] = 0;
-    });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         uint32_t bad = 0;
-        float Dall = 0.f;                                          // dare_linear: the sum of ALL weights, kept or not
-        for (int i = 0; i < k; ++i) Dall = aten_fadd_(Dall, p.alpha[i]);
+        const float Dall = delta_weight_sum(p.alpha, k);
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oi = start + (size_t)q * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
-            float b[8], bo[8], S[8], P[8], N[8], DP[8], DN[8];
-            if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
-            if (p.out_is_base0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bo[e] = b[e];
-            } else {
-                ties_load8(p.base_out, p.base_out_dtype, i0, cnt, vec, bo);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { S[e] = 0.f; P[e] = 0.f; N[e] = 0.f; DP[e] = 0.f; DN[e] = 0.f; }
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), nt, p.chunks, tid, q, o)) break;
+            float b[8], bo[8];
+            delta_base8(p.in, o, b);
+            delta_base_out8(p, o, b, bo);
+            Election el;
+            el.clear();
             for (int i = 0; i < k; ++i) {
                 float f[8];
-                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);       // (elements past n load as 0: never kept)
-                if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
-                const uint32_t mask = dare_mask8(p.key, p.stream_id[i], (uint64_t)i0, p.T);
+                delta_load8(p.in, i, o, b, f);                             // (elements past n load as 0: never kept)
+                const uint32_t mask = dare_mask8(p.key, p.stream_id[i], (uint64_t)o.i0, p.T);
                 const float al = p.alpha[i];
                 uint32_t nkept = 0;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float d = f[e] - b[e];
-                    const uint32_t mag = f2u(d) & 0x7fffffffu;
+                    const uint32_t mag = delta_key(d);
                     if (mag >= TIES_KEY_INF) bad |= 1u << i;
                     const bool kept = ((mask >> e) & 1u) != 0u && mag != 0u;
                     nkept += kept ? 1u : 0u;
-                    const float tv = kept ? aten_fmul_(aten_fmul_(d, p.rescale), al) : 0.f;
-                    S[e] = aten_fadd_(S[e], tv);
-                    if (p.sign_election) {       // as ties_merge: the running sums of the positive and of the negative entries
-                        if (tv > 0.f) { P[e] = aten_fadd_(P[e], tv); DP[e] = aten_fadd_(DP[e], al); }
-                        if (tv < 0.f) { N[e] = aten_fadd_(N[e], tv); DN[e] = aten_fadd_(DN[e], al); }
-                    }
+                    el.add(e, kept ? aten_fmul_(aten_fmul_(d, p.rescale), al) : 0.f, al, p.sign_election);
                 }
                 lc[i * nt + tid] += nkept;                                 // this thread's own slot
             }
             float r[8], dl[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool pos = S[e] >= 0.f;
-                float M = p.sign_election ? (pos ? P[e] : N[e]) : S[e];
-                if (p.normalize) {
-                    float D = p.sign_election ? (pos ? DP[e] : DN[e]) : Dall;
-                    if (fabsf(D) < eps) D = 1.f;
-                    M = M / D;
-                }
-                dl[e] = aten_fmul_(p.lambda, M);
-                r[e] = aten_fadd_(bo[e], dl[e]);
-            }
-            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, dl);
+            el.finish(p.sign_election, p.normalize, Dall, p.lambda, bo, r, dl);
+            delta_store8(p, o, r, dl);
         }
         if (bad) ex.global_atomic_or_u32(p.flags, bad);
     });
-    ex.sync();
-    // 16 threads per finetune add up its nt counters, one LDS atomic each; then one global atomic per finetune
-    ex.each(st, [&](int tid, EmptyState&) {
-        const int groups = nt >= 16 ? nt >> 4 : 1;
-        for (int i = tid >> 4; i < k; i += groups) {
-            uint32_t s = 0;
-            for (int t = tid & 15; t < nt; t += 16) s += lc[i * nt + t];
-            if (s) ex.lds_atomic_add(&tot[i], s);
-        }
-    });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        if (tid < k && tot[tid]) ex.global_atomic_add(&p.kept[tid], (unsigned long long)tot[tid]);
-    });
+    kept_fold(ex, st, lc, k, p.kept);
 }
 
 }  // namespace smhip

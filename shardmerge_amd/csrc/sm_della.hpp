@@ -10,7 +10,8 @@
 //                of two with all-ones keys), an in-place bitonic network sorts them, and each element's rank is the
 //                lower bound of its key in the sorted row; T = table[rank] goes to the workspace as uint16.
 //   della_merge  the fused streaming pass of dare_merge with a threshold and a rescale per element: per octet and
-//                finetune one 16-byte load of eight T from the workspace, one Philox block, the fp32 chain.
+//                finetune one 16-byte load of eight T from the workspace, one Philox block, the fp32 chain.  The walk
+//                (over the slab's octets of the flat index), the loader, the election, the kept counters: sm_delta.hpp.
 // The sort: the strides 4, 2, 1 of every merge step run in registers (a thread owns 8 consecutive keys: two 16-byte LDS
 // accesses each way), the strides from 8 up two at a time (4 keys per thread), so a 32768-key row is 55 passes over
 // LDS instead of 120.
@@ -226,18 +227,6 @@ SM_HD void k_della_rank(Ex& ex, const DellaRankParams& p) {
     });
 }
 
-// the eight 16-bit draws of the octet that holds element j: h of smhip_dare_merge step 3 (dare_mask8 compares them with one T)
-SM_HD void della_draws8(uint64_t key, uint32_t stream_id, uint64_t j, uint32_t* h) {
-    const uint64_t oct = j >> 3;
-    uint32_t c[4] = {(uint32_t)oct, (uint32_t)(oct >> 32), stream_id, 0u};
-    philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint32_t w = c[e >> 1];
-        h[e] = (e & 1) ? (w >> 16) : (w & 0xffffu);
-    }
-}
-
 struct DellaMergeParams {
     TiesInputs in;              // the whole tensor
     DellaSlab slab;
@@ -263,114 +252,55 @@ SM_HD void k_della_merge(Ex& ex, const DellaMergeParams& p) {
     ex.init(st);
     const int nt = ex.nthreads();
     const int k = p.in.k;
-    uint32_t* lc = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [k][nt], then [TIES_MAX_MODELS] totals (dare_lds_words)
-    uint32_t* tot = lc + (size_t)k * nt;
+    uint32_t* lc = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [k][nt], then the totals (dare_lds_words)
     const size_t lo = p.slab.e0, hi = p.slab.e0 + p.slab.len;      // the slab's elements; its octets are those of the FLAT index
-    const size_t oct0 = lo >> 3, noct = ((hi + 7) >> 3) - oct0;
     const uint16_t* ws0 = p.slab.ws - (lo & ~(size_t)7);
-    const float eps = 1e-8f;
+    kept_zero(ex, st, lc, k);
     ex.each(st, [&](int tid, EmptyState&) {
-        for (int i = 0; i < k; ++i) lc[i * nt + tid] = 0;
-        if (tid < TIES_MAX_MODELS) tot[tid] = 0;
-    });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         uint32_t bad = 0;
-        float Dall = 0.f;
-        for (int i = 0; i < k; ++i) Dall = aten_fadd_(Dall, p.alpha[i]);
+        const float Dall = delta_weight_sum(p.alpha, k);
+        // (an octet cut by the slab's edge: its elements below o.lo are the slab's before - loaded, never kept or stored)
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oq = start + (size_t)q * nt + tid;
-            if (oq >= noct) break;
-            const size_t oi = oct0 + oq, i0 = 8 * oi;
-            const int e_lo = i0 < lo ? (int)(lo - i0) : 0, e_hi = (hi - i0) < 8 ? (int)(hi - i0) : 8;   // live: e_lo <= e < e_hi
-            const bool whole = e_lo == 0 && e_hi == 8;
-            const bool vec = p.in.aligned && whole;
-            float b[8], bo[8], S[8], P[8], N[8], DP[8], DN[8];
-            // (an octet cut by the slab's edge: element by element, the dead ones as 0 and never stored)
-            auto load8 = [&](const void* src, int dtype, float* dst) {
-                if (vec) { load_elem8(src, dtype, i0, dst); return; }
-                for (int e = 0; e < 8; ++e) dst[e] = (e >= e_lo && e < e_hi) ? load_elem(src, dtype, i0 + e) : 0.f;
-            };
-            if (p.in.shared_base) load8(p.in.base[0], p.in.dtype, b);
-            if (p.out_is_base0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bo[e] = b[e];
-            } else {
-                load8(p.base_out, p.base_out_dtype, bo);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { S[e] = 0.f; P[e] = 0.f; N[e] = 0.f; DP[e] = 0.f; DN[e] = 0.f; }
+            Octet o;
+            if (!octet_at(lo, hi, p.in.aligned, ex.bid(), nt, p.chunks, tid, q, o)) break;
+            float b[8], bo[8];
+            delta_base8(p.in, o, b);
+            delta_base_out8(p, o, b, bo);
+            Election el;
+            el.clear();
             for (int i = 0; i < k; ++i) {
                 float f[8];
-                load8(p.in.ft[i], p.in.dtype, f);
-                if (!p.in.shared_base) load8(p.in.base[i], p.in.dtype, b);
-                const u32x4 tw = *(const u32x4*)(ws0 + (size_t)i * p.slab.stride + i0);     // eight T: one 16-byte load
+                delta_load8(p.in, i, o, b, f);
+                const u32x4 tw = *(const u32x4*)(ws0 + (size_t)i * p.slab.stride + o.i0);   // eight T: one 16-byte load
                 const uint32_t tws[4] = {tw.x, tw.y, tw.z, tw.w};
                 uint32_t h[8];
-                della_draws8(p.key, p.stream_id[i], (uint64_t)i0, h);
+                dare_draws8(p.key, p.stream_id[i], (uint64_t)o.i0, h);
                 const float al = p.alpha[i];
                 uint32_t nkept = 0;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const uint32_t T = (e & 1) ? (tws[e >> 1] >> 16) : (tws[e >> 1] & 0xffffu);
                     const float d = f[e] - b[e];
-                    const uint32_t mag = f2u(d) & 0x7fffffffu;
+                    const uint32_t mag = delta_key(d);
                     if (mag >= TIES_KEY_INF) bad |= 1u << i;
-                    const bool live = whole || (e >= e_lo && e < e_hi);
-                    const bool kept = live && h[e] < T && mag != 0u;
+                    const bool kept = e >= o.lo && h[e] < T && mag != 0u;
                     nkept += kept ? 1u : 0u;
                     float tv = 0.f;
                     if (kept) {
                         const float s = p.rescale ? (float)(65536.0 / (double)T) : 1.f;
                         tv = aten_fmul_(aten_fmul_(d, s), al);
                     }
-                    S[e] = aten_fadd_(S[e], tv);
-                    if (p.sign_election) {
-                        if (tv > 0.f) { P[e] = aten_fadd_(P[e], tv); DP[e] = aten_fadd_(DP[e], al); }
-                        if (tv < 0.f) { N[e] = aten_fadd_(N[e], tv); DN[e] = aten_fadd_(DN[e], al); }
-                    }
+                    el.add(e, tv, al, p.sign_election);
                 }
                 lc[i * nt + tid] += nkept;
             }
             float r[8], dl[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool pos = S[e] >= 0.f;
-                float M = p.sign_election ? (pos ? P[e] : N[e]) : S[e];
-                if (p.normalize) {
-                    float D = p.sign_election ? (pos ? DP[e] : DN[e]) : Dall;
-                    if (fabsf(D) < eps) D = 1.f;
-                    M = M / D;
-                }
-                dl[e] = aten_fmul_(p.lambda, M);
-                r[e] = aten_fadd_(bo[e], dl[e]);
-            }
-            if (e_lo == 0) {
-                ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, e_hi, vec, r, dl);
-            } else {
-                for (int e = e_lo; e < e_hi; ++e) {
-                    if (p.delta_out) p.delta_out[i0 + e] = dl[e];
-                    if (p.base_out_dtype == DT_F32) ((float*)p.out)[i0 + e] = r[e];
-                    else ((uint16_t*)p.out)[i0 + e] = p.base_out_dtype == DT_BF16 ? f_to_bf16_any(r[e]) : f_to_f16_any(r[e]);
-                }
-            }
+            el.finish(p.sign_election, p.normalize, Dall, p.lambda, bo, r, dl);
+            delta_store8(p, o, r, dl);
         }
         if (bad) ex.global_atomic_or_u32(p.flags, bad);
     });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        const int groups = nt >= 16 ? nt >> 4 : 1;
-        for (int i = tid >> 4; i < k; i += groups) {
-            uint32_t s = 0;
-            for (int t = tid & 15; t < nt; t += 16) s += lc[i * nt + t];
-            if (s) ex.lds_atomic_add(&tot[i], s);
-        }
-    });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        if (tid < k && tot[tid]) ex.global_atomic_add(&p.kept[tid], (unsigned long long)tot[tid]);
-    });
+    kept_fold(ex, st, lc, k, p.kept);
 }
 
 }  // namespace smhip

@@ -15,7 +15,7 @@
 //   geo_combine    one streaming pass: out = base_out + sum_i c_i x_i (delta space) or sum_i c_i x_i (weight space),
 //                  the coefficients from the kernel arguments or from the [R][k] array of geo_coef.
 #pragma once
-#include "sm_ties.hpp"
+#include "sm_delta.hpp"
 
 namespace smhip {
 
@@ -117,7 +117,6 @@ SM_HD void k_geo_gram(Ex& ex, const GeoGramParams& p) {
     double* red = (double*)(ex.lds() + LDS_SCRATCH_FLOATS);        // [GEO_TILE * GEO_TILE][nt] (LDS_SCRATCH_FLOATS is even)
     const size_t start = seg * p.seg_len;
     const size_t len = p.in.n - start < p.seg_len ? p.in.n - start : p.seg_len;
-    const size_t noct = (len + 7) / 8;
     ex.each(st, [&](int tid, EmptyState&) {
         double acc[GEO_TILE][GEO_TILE];
 #pragma unroll
@@ -125,27 +124,23 @@ SM_HD void k_geo_gram(Ex& ex, const GeoGramParams& p) {
 #pragma unroll
             for (int jb = 0; jb < GEO_TILE; ++jb) acc[ia][jb] = 0.0;
         uint32_t bad = 0;
-        for (size_t o = tid; o < noct; o += nt) {
-            const size_t i0 = start + 8 * o;
-            const int cnt = (int)((len - 8 * o) < 8 ? (len - 8 * o) : 8);
-            const bool vec = p.seg_vec && cnt == 8;
+        for (size_t q = tid; q < segment_octets(len); q += nt) {
+            const Octet o = segment_octet(start, len, p.seg_vec, q);
             float b[8], xa[GEO_TILE][8], xb[TILED ? GEO_TILE : 1][8];
-            if (!p.weight_space && p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
+            if (!p.weight_space) delta_base8(p.in, o, b);
             // the vectors of one side of the tile: 8 elements each (elements past the segment's end load as +0)
             auto load_side = [&](int m0, int nm, float (*x)[8]) {
 #pragma unroll
                 for (int m = 0; m < GEO_TILE; ++m) {
                     if (m < nm) {
                         const int i = m0 + m;
-                        ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, x[m]);
-                        if (!p.weight_space) {
-                            if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                        if (p.weight_space) ties_load8(p.in.ft[i], p.in.dtype, o.i0, o.cnt, o.vec, x[m]);
+                        else delta_load8(p.in, i, o, b, x[m]);
 #pragma unroll
-                            for (int e = 0; e < 8; ++e) x[m][e] = x[m][e] - b[e];
+                        for (int e = 0; e < 8; ++e) {
+                            if (!p.weight_space) x[m][e] = x[m][e] - b[e];
+                            if (delta_key(x[m][e]) >= TIES_KEY_INF) bad |= 1u << i;
                         }
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            if ((f2u(x[m][e]) & 0x7fffffffu) >= TIES_KEY_INF) bad |= 1u << i;
                     }
                 }
             };
@@ -250,53 +245,42 @@ template <class Ex>
 SM_HD void k_geo_combine(Ex& ex, const GeoCombineParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
-    const int nt = ex.nthreads();
     const int k = p.in.k;
-    const size_t noct = (p.in.n + 7) / 8;
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oi = start + (size_t)q * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
             float b[8], bo[8], M[8];
             if (!p.weight_space) {
-                if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
-                if (p.out_is_base0) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) bo[e] = b[e];
-                } else {
-                    ties_load8(p.base_out, p.base_out_dtype, i0, cnt, vec, bo);
-                }
+                delta_base8(p.in, o, b);
+                delta_base_out8(p, o, b, bo);
             }
             // row-wise: the row of element i0, and whether the whole octet lies in it (always when C % 8 == 0)
             size_t row = 0;
             bool one_row = true;
             if (p.rowcoef) {
-                row = i0 / p.C;
-                one_row = i0 - row * p.C + 8 <= p.C;
+                row = o.i0 / p.C;
+                one_row = o.i0 - row * p.C + 8 <= p.C;
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) M[e] = 0.f;
             for (int i = 0; i < k; ++i) {
                 float f[8];
-                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);
-                if (!p.weight_space && !p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                if (p.weight_space) ties_load8(p.in.ft[i], p.in.dtype, o.i0, o.cnt, o.vec, f);
+                else delta_load8(p.in, i, o, b, f);
                 const float ci = p.rowcoef ? p.rowcoef[row * k + i] : p.c[i];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float x = p.weight_space ? f[e] : f[e] - b[e];
                     float ce = ci;
-                    if (!one_row && e < cnt) ce = p.rowcoef[((i0 + e) / p.C) * k + i];
+                    if (!one_row && e < o.cnt) ce = p.rowcoef[((o.i0 + e) / p.C) * k + i];
                     M[e] = aten_fadd_(M[e], aten_fmul_(ce, x));
                 }
             }
             float r[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) r[e] = p.weight_space ? M[e] : aten_fadd_(bo[e], M[e]);
-            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, M);
+            delta_store8(p, o, r, M);
         }
     });
 }

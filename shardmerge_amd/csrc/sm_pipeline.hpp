@@ -2377,31 +2377,45 @@ class Pipeline {
         return SMHIP_OK;
     }
 
-    // ---- the delta-merge family: TIES, DARE, Breadcrumbs (sm_ties.hpp, sm_dare.hpp, sm_breadcrumbs.hpp; the functions are
-    // stated in shardmerge_hip.h; arguments checked by delta_merge_check, sm_capi.inc).  The descriptors share their leading
-    // fields and the *MergeParams their common ones, so what the three host paths share is written once, as templates. ----
+    // ---- the delta-merge family: TIES, DARE, DELLA, Breadcrumbs, the geometric merges, SCE (sm_delta.hpp and the operators'
+    // headers; the functions are stated in shardmerge_hip.h; arguments checked by delta_merge_check, sm_capi.inc).  The
+    // descriptors share their leading fields and the *MergeParams their common ones, so what the host paths share is
+    // written once, as templates. ----
     static unsigned long long delta_k_keep(double density, size_t n) {
         return density == 1.0 ? (unsigned long long)n : (unsigned long long)std::floor(density * (double)n);
     }
-    // the common fields of a *MergeParams: the inputs (padded with finetune 0), alignment, shared base, add-back, chunks
-    template <class Desc, class MergeParams>
-    void delta_merge_params(const Desc& d, void* out, float* delta_out, MergeParams& m) {
+    // what every descriptor has: the inputs (padded with finetune 0), alignment, shared base, add-back, chunks.
+    // weight_space (geo's SLERP): the vectors are the finetunes themselves, no base is read and base_out need not be aligned
+    template <class Desc, class Params>
+    void delta_inputs(const Desc& d, void* out, float* delta_out, bool weight_space, Params& m) {
         const int k = d.k;
         TiesInputs& in = m.in;
         in.k = k; in.dtype = d.in_dtype; in.n = d.n;
-        bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
+        bool al = aligned16(out) && aligned16(delta_out) && (weight_space || aligned16(d.base_out)), shared = true;
         for (int i = 0; i < TIES_MAX_MODELS; ++i) {
-            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
+            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = weight_space ? nullptr : d.base[i < k ? i : 0];
             al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
             shared = shared && in.base[i] == in.base[0];
-            m.alpha[i] = (float)d.alpha[i < k ? i : 0];
         }
         in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
         m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
-        m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
-        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0;
+        m.out_is_base0 = (!weight_space && shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
         m.out = out; m.delta_out = delta_out;
         m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+    }
+    // ... and what the descriptors of the election operators add: the weights, lambda, normalize
+    template <class Desc, class MergeParams>
+    void delta_merge_params(const Desc& d, void* out, float* delta_out, MergeParams& m) {
+        delta_inputs(d, out, delta_out, false, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < d.k ? i : 0];
+        m.lambda = (float)d.lambda; m.normalize = d.normalize ? 1 : 0;
+    }
+    // a non-finite vector fails the call: `what` and the finetunes whose bit is set in flags
+    int delta_nonfinite(const std::string& what, int k, uint32_t flags) {
+        std::string which;
+        for (int i = 0; i < k; ++i)
+            if (flags & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
+        return fail(SMHIP_ERR_NONFINITE, what + which);
     }
     // the call's one synchronisation: fetch the readback and fail on a non-finite delta (flags[0]: one bit per finetune)
     template <class Readback>
@@ -2409,47 +2423,53 @@ class Pipeline {
         be.d2h(&host, rb, sizeof host, stream);
         if (!be.ok()) { host = Readback{}; return SMHIP_OK; }   // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
         if (!host.flags[0]) return SMHIP_OK;
-        std::string which;
-        for (int i = 0; i < k; ++i)
-            if (host.flags[0] & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
-        return fail(SMHIP_ERR_NONFINITE, std::string(op) + ": NaN or Inf in finetune - base of finetune " + which);
+        return delta_nonfinite(std::string(op) + ": NaN or Inf in finetune - base of finetune ", k, host.flags[0]);
     }
-    // the zeroed workspace of a radix select: the three levels' histograms [3][k][HIST1_BINS] | State[states] | Readback
-    static constexpr size_t SELECT_HIST_LEVEL = (size_t)TIES_MAX_MODELS * HIST1_BINS * sizeof(unsigned long long);
-    template <class State, class Readback>
-    int select_workspace(size_t states, State*& state, Readback*& rb) {
-        const size_t off_state = 3 * SELECT_HIST_LEVEL, off_rb = off_state + states * sizeof(State);
-        const size_t ws = off_rb + sizeof(Readback);
+    // the workspace of a radix select: the three levels' histograms [3][streams][HIST1_BINS] | Tail, zeroed; then, from
+    // the next multiple of 256 bytes (*off_more) on, `more` bytes that are not
+    static size_t select_hist_level(int streams) { return (size_t)streams * HIST1_BINS * sizeof(unsigned long long); }
+    template <class Tail>
+    int select_workspace(int streams, Tail*& tail, size_t more = 0, size_t* off_more = nullptr) {
+        const size_t off_tail = 3 * select_hist_level(streams), zeroed = off_tail + sizeof(Tail), off = round_up(zeroed, 256);
         int rc;
-        if ((rc = ensure(ties_, ws))) return rc;
-        be.memset(ties_.p, 0, ws, stream);
-        state = (State*)((char*)ties_.p + off_state);
-        rb = (Readback*)((char*)ties_.p + off_rb);
+        if ((rc = ensure(ties_, more ? off + more : zeroed))) return rc;
+        be.memset(ties_.p, 0, zeroed, stream);
+        tail = (Tail*)((char*)ties_.p + off_tail);
+        if (off_more) *off_more = off;
         return SMHIP_OK;
     }
-    // the three levels of a radix select: hist launches in groups of TIES_GROUP finetunes, then one select launch.
-    // The caller has filled h and s but for level, hist, first, count and h.chunks; hist_bins: LDS bins per finetune and level.
+    // the three levels of a radix select: launch_hist(level, hist) fills the level's histograms, then one select launch
+    // of a work-group per stream.  The caller has filled s but for level and hist.
+    template <class KSelect, class SelectParams, class LaunchHist>
+    void select_levels(int streams, int grid, SelectParams& s, size_t select_lds, LaunchHist&& launch_hist) {
+        for (int level = 1; level <= 3; ++level) {
+            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * select_hist_level(streams));
+            launch_hist(level, hist);
+            s.level = level; s.hist = hist;
+            be.template launch<KSelect>(grid, TIES_SELECT_THREADS, select_lds, s, stream);
+        }
+    }
+    // ... with a stream per finetune: hist launches in groups of TIES_GROUP finetunes.  The caller has filled h but for
+    // level, hist, first, count and chunks; hist_bins: LDS bins per finetune and level.
     template <class KHist, class KSelect, class HistParams, class SelectParams>
-    void select_levels(HistParams& h, SelectParams& s, const int (&hist_bins)[3], size_t select_lds) {
+    void select_levels_per_finetune(HistParams& h, SelectParams& s, const int (&hist_bins)[3], size_t select_lds) {
         const int k = h.in.k;
         const size_t noct = (h.in.n + 7) / 8;
         h.chunks = pick_chunks(noct, 256, 4, 5);
         const int hgrid = stream_grid(noct, 256, h.chunks);
-        for (int level = 1; level <= 3; ++level) {
-            unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * SELECT_HIST_LEVEL);
+        select_levels<KSelect>(TIES_MAX_MODELS, k, s, select_lds, [&](int level, unsigned long long* hist) {
             h.level = level; h.hist = hist;
             // (k_keep == 0: the thresholds are +inf whatever the data; level 1 still runs, it finds the non-finite deltas)
             for (int first = 0; first < k && (level == 1 || s.k_keep > 0); first += TIES_GROUP) {
                 h.first = first; h.count = std::min(TIES_GROUP, k - first);
                 be.template launch<KHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * hist_bins[level - 1]) * 4, h, stream);
             }
-            s.level = level; s.hist = hist;
-            be.template launch<KSelect>(k, TIES_SELECT_THREADS, select_lds, s, stream);
-        }
+        });
     }
 
     // ---- TIES merge: one rank per finetune; levels 2 and 3 need only the low bins in LDS ----
     struct TiesReadback { float threshold[TIES_MAX_MODELS]; unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
+    struct TiesWork { RadixState state[TIES_MAX_MODELS]; TiesReadback rb; };
     int ties_merge(const smhip_ties_desc& d, void* out, float* delta_out, smhip_ties_report* rep) {
         const int k = d.k;
         const unsigned long long k_keep = delta_k_keep(d.density, d.n);
@@ -2461,43 +2481,51 @@ class Pipeline {
             if (rep) for (int i = 0; i < k; ++i) rep->threshold[i] = INFINITY;
             return SMHIP_OK;
         }
-        TiesState* state;
-        TiesReadback* rb;
+        TiesWork* w;
         int rc;
-        if ((rc = select_workspace(TIES_MAX_MODELS, state, rb))) return rc;
+        if ((rc = select_workspace(TIES_MAX_MODELS, w))) return rc;
 
         TiesMergeParams m;
         delta_merge_params(d, out, delta_out, m);
-        m.threshold = rb->threshold;
+        m.threshold = w->rb.threshold;
 
         TiesHistParams h;
-        h.in = m.in; h.state = state; h.flags = rb->flags;
+        h.in = m.in; h.state = w->state; h.flags = w->rb.flags;
         TiesSelectParams s;
-        s.k_keep = k_keep; s.state = state; s.threshold = rb->threshold; s.kept = rb->kept;
-        select_levels<KTiesHist, KTiesSelect>(h, s, {HIST1_BINS, HIST_LO_BINS, HIST_LO_BINS},
-                                              LDS_SCRATCH_FLOATS * 4 + TIES_SELECT_THREADS * sizeof(unsigned long long));
+        s.k_keep = k_keep; s.state = w->state; s.threshold = w->rb.threshold; s.kept = w->rb.kept;
+        select_levels_per_finetune<KTiesHist, KTiesSelect>(h, s, {HIST1_BINS, HIST_LO_BINS, HIST_LO_BINS}, TIES_SELECT_LDS);
         be.template launch<KTiesMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
 
         TiesReadback host;
-        if ((rc = delta_readback("ties_merge", k, rb, host))) return rc;
+        if ((rc = delta_readback("ties_merge", k, &w->rb, host))) return rc;
         if (rep)
             for (int i = 0; i < k; ++i) { rep->threshold[i] = host.threshold[i]; rep->kept[i] = host.kept[i]; }
         return SMHIP_OK;
     }
 
-    // ---- DARE merge: no select, one kernel; workspace (the TIES buffer, the operators never run at once): DareReadback ----
+    // ---- DARE merge: no select, one kernel; workspace (the TIES buffer, the operators never run at once): DareReadback.
+    // dare_pass is the call for any descriptor with DARE's fields (smhip_dare_desc; smhip_della_desc with a uniform
+    // threshold); op names the entry point in the error text ----
     struct DareReadback { unsigned long long kept[TIES_MAX_MODELS]; uint32_t flags[2]; };
     static uint32_t dare_threshold(double density) {
         return density == 1.0 ? DARE_T_ONE : (uint32_t)std::floor(density * 65536.0);
     }
-    int dare_merge(const smhip_dare_desc& d, void* out, float* delta_out, smhip_dare_report* rep) {
-        const int k = d.k;
-        const uint32_t T = dare_threshold(d.density);
-        if (rep) {
-            rep->T = T;
-            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
-        }
-        if (d.n == 0) return SMHIP_OK;
+    template <class Desc, class MergeParams>
+    void dare_fields(const Desc& d, DareReadback* rb, MergeParams& m) {
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.stream_id[i] = d.stream_id[i < d.k ? i : 0];
+        m.key = d.key; m.sign_election = d.sign_election ? 1 : 0;
+        m.kept = rb->kept; m.flags = rb->flags;
+    }
+    int dare_readback(const char* op, int k, const DareReadback* rb, uint64_t* kept) {
+        DareReadback host;
+        int rc;
+        if ((rc = delta_readback(op, k, rb, host))) return rc;
+        if (kept)
+            for (int i = 0; i < k; ++i) kept[i] = host.kept[i];
+        return SMHIP_OK;
+    }
+    template <class Desc>
+    int dare_pass(const char* op, const Desc& d, uint32_t T, void* out, float* delta_out, uint64_t* kept) {
         int rc;
         if ((rc = ensure(ties_, sizeof(DareReadback)))) return rc;
         be.memset(ties_.p, 0, sizeof(DareReadback), stream);
@@ -2505,22 +2533,24 @@ class Pipeline {
 
         DareMergeParams m;
         delta_merge_params(d, out, delta_out, m);
-        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.stream_id[i] = d.stream_id[i < k ? i : 0];
-        m.key = d.key; m.T = T;
+        dare_fields(d, rb, m);
+        m.T = T;
         m.rescale = d.rescale ? (float)(65536.0 / (double)T) : 1.f;
-        m.sign_election = d.sign_election ? 1 : 0;
-        m.kept = rb->kept; m.flags = rb->flags;
-        be.template launch<KDareMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
-
-        DareReadback host;
-        if ((rc = delta_readback("dare_merge", k, rb, host))) return rc;
-        if (rep)
-            for (int i = 0; i < k; ++i) rep->kept[i] = host.kept[i];
-        return SMHIP_OK;
+        be.template launch<KDareMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(d.k, 256)) * 4, m, stream);
+        return dare_readback(op, d.k, rb, kept);
+    }
+    int dare_merge(const smhip_dare_desc& d, void* out, float* delta_out, smhip_dare_report* rep) {
+        const uint32_t T = dare_threshold(d.density);
+        if (rep) {
+            rep->T = T;
+            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
+        }
+        if (d.n == 0) return SMHIP_OK;
+        return dare_pass("dare_merge", d, T, out, delta_out, rep ? rep->kept : nullptr);
     }
 
     // ---- DELLA merge (sm_della.hpp; the function is stated in shardmerge_hip.h, smhip_della_merge).  epsilon == 0 or
-    // density == 1: the uniform threshold, dare_merge itself.  Otherwise slabs of whole rows: rank all k finetunes of a slab
+    // density == 1: the uniform threshold, dare_pass itself.  Otherwise slabs of whole rows: rank all k finetunes of a slab
     // into the workspace, merge the slab; the mask index stays the flat index in the tensor.  Workspace (the TIES buffer):
     // DareReadback | the table T(rank) [c] | uint16 [k][stride] ----
     size_t della_slab_rows = 0;               // test hook "della_slab_rows": rows per slab (0: at most 2^26 elements per finetune)
@@ -2537,30 +2567,16 @@ class Pipeline {
             for (int i = 0; i < SMHIP_MAX_MODELS; ++i) rep->kept[i] = 0;
         }
         if (d.n == 0) return SMHIP_OK;
+        uint64_t* kept = rep ? rep->kept : nullptr;
         int rc;
         if (uniform) {
-            smhip_dare_desc dd;
-            dd.k = k;
-            for (int i = 0; i < SMHIP_MAX_MODELS; ++i) {
-                dd.finetune[i] = d.finetune[i]; dd.base[i] = d.base[i]; dd.alpha[i] = d.alpha[i]; dd.stream_id[i] = d.stream_id[i];
-            }
-            dd.in_dtype = d.in_dtype; dd.base_out = d.base_out; dd.base_out_dtype = d.base_out_dtype; dd.n = d.n;
-            dd.density = d.density; dd.lambda = d.lambda; dd.normalize = d.normalize;
-            dd.key = d.key; dd.rescale = d.rescale; dd.sign_election = d.sign_election;
             if (threshold_out && d.density < 1.0) {
                 DellaTableParams t;
                 t.out = threshold_out; t.count = (size_t)k * d.n; t.c = 1; t.p_lo = 0.0; t.w = 0.0; t.fill = T_lo;
                 if ((t.count + 255) / 256 > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "della_merge: tensor too large for threshold_out");
                 be.template launch<KDellaTable>((int)((t.count + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, t, stream);
             }
-            smhip_dare_report dr;
-            if ((rc = dare_merge(dd, out, delta_out, &dr))) {
-                if (rc == SMHIP_ERR_NONFINITE) err.replace(0, 4, "della");      // "dare_merge: ..." names this entry point
-                return rc;
-            }
-            if (rep)
-                for (int i = 0; i < k; ++i) rep->kept[i] = dr.kept[i];
-            return SMHIP_OK;
+            return dare_pass("della_merge", d, T_lo, out, delta_out, kept);
         }
         const size_t R = d.rows;
         size_t slab_rows = della_slab_rows ? della_slab_rows : std::max<size_t>(1, DELLA_SLAB_ELEMS / c);
@@ -2577,10 +2593,8 @@ class Pipeline {
 
         DellaMergeParams m;
         delta_merge_params(d, out, delta_out, m);
-        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.stream_id[i] = d.stream_id[i < k ? i : 0];
-        m.key = d.key; m.rescale = d.rescale ? 1 : 0;
-        m.sign_election = d.sign_election ? 1 : 0;
-        m.kept = rb->kept; m.flags = rb->flags;
+        dare_fields(d, rb, m);
+        m.rescale = d.rescale ? 1 : 0;
         DellaRankParams r;
         r.in = m.in; r.c = (int)c; r.table = t.out; r.threshold_out = threshold_out; r.flags = rb->flags;
         r.P = 8;
@@ -2597,19 +2611,16 @@ class Pipeline {
             m.chunks = pick_chunks(noct, 256, 2, 8);
             be.template launch<KDellaMerge>(stream_grid(noct, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
         }
-        DareReadback host;
-        if ((rc = delta_readback("della_merge", k, rb, host))) return rc;
-        if (rep)
-            for (int i = 0; i < k; ++i) rep->kept[i] = host.kept[i];
-        return SMHIP_OK;
+        return dare_readback("della_merge", k, rb, kept);
     }
 
-    // ---- Breadcrumbs merge: two ranks per finetune (CrumbsState[k][2]), found in the same three histogram passes ----
+    // ---- Breadcrumbs merge: two ranks per finetune (RadixState[k][2]), found in the same three histogram passes ----
     struct CrumbsReadback {
         float threshold_lo[TIES_MAX_MODELS], threshold_hi[TIES_MAX_MODELS];
         unsigned long long kept[TIES_MAX_MODELS], dropped_top[TIES_MAX_MODELS];
         uint32_t flags[2];
     };
+    struct CrumbsWork { RadixState state[2 * TIES_MAX_MODELS]; CrumbsReadback rb; };
     int breadcrumbs_merge(const smhip_breadcrumbs_desc& d, void* out, float* delta_out, smhip_breadcrumbs_report* rep) {
         const int k = d.k;
         const unsigned long long k_keep = delta_k_keep(d.density, d.n);
@@ -2622,27 +2633,26 @@ class Pipeline {
             if (rep) for (int i = 0; i < k; ++i) { rep->threshold_lo[i] = INFINITY; rep->threshold_hi[i] = INFINITY; }
             return SMHIP_OK;
         }
-        CrumbsState* state;
-        CrumbsReadback* rb;
+        CrumbsWork* w;
         int rc;
-        if ((rc = select_workspace(2 * TIES_MAX_MODELS, state, rb))) return rc;
+        if ((rc = select_workspace(TIES_MAX_MODELS, w))) return rc;
 
         CrumbsMergeParams m;
         delta_merge_params(d, out, delta_out, m);
         m.sign_election = d.sign_election ? 1 : 0;
-        m.threshold_lo = rb->threshold_lo; m.threshold_hi = rb->threshold_hi;
+        m.threshold_lo = w->rb.threshold_lo; m.threshold_hi = w->rb.threshold_hi;
 
         CrumbsHistParams h;
-        h.in = m.in; h.state = state; h.flags = rb->flags;
+        h.in = m.in; h.state = w->state; h.flags = w->rb.flags;
         CrumbsSelectParams s;
         s.k_keep = k_keep; s.rank[CRUMBS_HI] = n_top + 1; s.rank[CRUMBS_LO] = n_top + k_keep;
-        s.state = state; s.threshold_lo = rb->threshold_lo; s.threshold_hi = rb->threshold_hi;
-        s.kept = rb->kept; s.dropped_top = rb->dropped_top;
-        select_levels<KCrumbsHist, KCrumbsSelect>(h, s, {HIST1_BINS, HIST1_BINS, HIST1_BINS}, CRUMBS_SELECT_LDS);
+        s.state = w->state; s.threshold_lo = w->rb.threshold_lo; s.threshold_hi = w->rb.threshold_hi;
+        s.kept = w->rb.kept; s.dropped_top = w->rb.dropped_top;
+        select_levels_per_finetune<KCrumbsHist, KCrumbsSelect>(h, s, {HIST1_BINS, HIST1_BINS, HIST1_BINS}, CRUMBS_SELECT_LDS);
         be.template launch<KCrumbsMerge>(stream_grid((d.n + 7) / 8, 256, m.chunks), 256, LDS_SCRATCH_FLOATS * 4, m, stream);
 
         CrumbsReadback host;
-        if ((rc = delta_readback("breadcrumbs_merge", k, rb, host))) return rc;
+        if ((rc = delta_readback("breadcrumbs_merge", k, &w->rb, host))) return rc;
         if (rep)
             for (int i = 0; i < k; ++i) {
                 rep->threshold_lo[i] = host.threshold_lo[i]; rep->threshold_hi[i] = host.threshold_hi[i];
@@ -2656,10 +2666,7 @@ class Pipeline {
     // device, the combine pass, one readback at the end.  Workspace (the TIES buffer): flags | G | partials or row data ----
     struct GeoHead { uint32_t flags[2]; double G[TIES_MAX_MODELS * (TIES_MAX_MODELS + 1) / 2]; };
     int geo_nonfinite(int k, uint32_t flags) {
-        std::string which;
-        for (int i = 0; i < k; ++i)
-            if (flags & (1u << i)) which += (which.empty() ? "" : ", ") + std::to_string(i);
-        return fail(SMHIP_ERR_NONFINITE, "geo_merge: NaN or Inf in the vector (finetune - base, or the finetune) of finetune " + which);
+        return delta_nonfinite("geo_merge: NaN or Inf in the vector (finetune - base, or the finetune) of finetune ", k, flags);
     }
     int geo_merge(const smhip_geo_desc& d, void* out, float* delta_out, smhip_geo_report* rep) {
         const int k = d.k, np = geo_pairs(k);
@@ -2673,24 +2680,10 @@ class Pipeline {
         if (d.n == 0) return SMHIP_OK;
 
         GeoCombineParams m;
-        {   // (a smhip_geo_desc has the leading fields of the delta-merge descriptors but for density, lambda, normalize)
-            TiesInputs& in = m.in;
-            in.k = k; in.dtype = d.in_dtype; in.n = d.n;
-            bool al = aligned16(out) && aligned16(delta_out) && (weight || aligned16(d.base_out)), shared = true;
-            for (int i = 0; i < TIES_MAX_MODELS; ++i) {
-                in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = weight ? nullptr : d.base[i < k ? i : 0];
-                al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
-                shared = shared && in.base[i] == in.base[0];
-                m.c[i] = 0.f;
-            }
-            in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
-            m.weight_space = weight ? 1 : 0;
-            m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
-            m.out_is_base0 = (!weight && shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
-            m.out = out; m.delta_out = delta_out;
-            m.rowcoef = nullptr; m.C = d.n / d.rows;
-            m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
-        }
+        delta_inputs(d, out, delta_out, weight, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.c[i] = 0.f;
+        m.weight_space = weight ? 1 : 0;
+        m.rowcoef = nullptr; m.C = d.n / d.rows;
         GeoGramParams g;
         g.in = m.in; g.weight_space = m.weight_space;
         g.seg_len = rowwise ? m.C : GEO_SEG_ELEMS;
@@ -2785,7 +2778,7 @@ class Pipeline {
     // ---- SCE merge (sm_sce.hpp; the function is stated in shardmerge_hip.h, smhip_sce_merge): the three levels of the ONE
     // selection stream (skipped when select_topk == 1 or k == 1), the energy pass and its fold, ONE readback (flags, the
     // selection's results, the energies), the weights on the host, the merge pass.  Workspace (the TIES buffer):
-    // the three levels' histograms [3][HIST1_BINS] | SceHead | the segments' sums [nseg][k] ----
+    // select_workspace of one stream with SceHead as its tail, then the segments' sums [nseg][k] ----
     struct SceHead { uint32_t flags[2]; SceState sel; double E[TIES_MAX_MODELS]; };
     int sce_merge(const smhip_sce_desc& d, void* out, float* delta_out, smhip_sce_report* rep) {
         const int k = d.k;
@@ -2804,31 +2797,15 @@ class Pipeline {
         }
         if (rep) *rep = r;
         SceMergeParams m;
-        {   // (a smhip_sce_desc has the leading fields of the delta-merge descriptors but for density and normalize)
-            TiesInputs& in = m.in;
-            in.k = k; in.dtype = d.in_dtype; in.n = d.n;
-            bool al = aligned16(d.base_out) && aligned16(out) && aligned16(delta_out), shared = true;
-            for (int i = 0; i < TIES_MAX_MODELS; ++i) {
-                in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
-                al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
-                shared = shared && in.base[i] == in.base[0];
-                m.w[i] = 0.f;
-            }
-            in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
-            m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
-            m.out_is_base0 = (shared && d.base_out == in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
-            m.lambda = (float)d.lambda;
-            m.out = out; m.delta_out = delta_out;
-            m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
-        }
+        delta_inputs(d, out, delta_out, false, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.w[i] = 0.f;
+        m.lambda = (float)d.lambda;
         const bool small = k <= SCE_REG_SMALL;
         const size_t nseg = (d.n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
-        const size_t hist_bytes = (size_t)3 * HIST1_BINS * sizeof(unsigned long long);
-        const size_t off_head = hist_bytes, off_part = round_up(off_head + sizeof(SceHead), 256);
+        SceHead* head;
+        size_t off_part;
         int rc;
-        if ((rc = ensure(ties_, off_part + nseg * k * sizeof(double)))) return rc;
-        be.memset(ties_.p, 0, off_head + sizeof(SceHead), stream);
-        SceHead* head = (SceHead*)((char*)ties_.p + off_head);
+        if ((rc = select_workspace(1, head, nseg * k * sizeof(double), &off_part))) return rc;
         m.select = select ? 1 : 0; m.state = &head->sel;
 
         if (select) {
@@ -2839,14 +2816,12 @@ class Pipeline {
             const int hgrid = stream_grid(noct, 256, h.chunks);
             SceSelectParams s;
             s.n = d.n; s.select_topk = d.select_topk; s.state = &head->sel;
-            for (int level = 1; level <= 3; ++level) {
-                h.level = level; h.hist = (unsigned long long*)ties_.p + (size_t)(level - 1) * HIST1_BINS;
-                const size_t hlds = (LDS_SCRATCH_FLOATS + (size_t)(level == 1 ? HIST1_BINS : HIST_LO_BINS) + 1) * 4;
+            select_levels<KSceSelect>(1, 1, s, TIES_SELECT_LDS, [&](int level, unsigned long long* hist) {
+                h.level = level; h.hist = hist;
+                const size_t hlds = (LDS_SCRATCH_FLOATS + (size_t)radix_bins(level) + 1) * 4;     // (+ 1: the count of q == 0)
                 if (small) be.template launch<KSceHist>(hgrid, 256, hlds, h, stream);
                 else be.template launch<KSceHistAny>(hgrid, 256, hlds, h, stream);
-                s.level = level; s.hist = h.hist;
-                be.template launch<KSceSelect>(1, TIES_SELECT_THREADS, LDS_SCRATCH_FLOATS * 4 + TIES_SELECT_THREADS * sizeof(unsigned long long), s, stream);
-            }
+            });
         }
         SceEnergyParams e;
         e.in = m.in; e.select = m.select; e.state = m.state; e.nseg = nseg; e.seg_vec = m.in.aligned;

@@ -1,6 +1,6 @@
 // sm_sce.hpp - SCE merge (Wan et al., FuseChat: select, calculate, erase), an operator the reference does not have.
 // The function is stated in include/shardmerge_hip.h (smhip_sce_merge).  It is the first operator that needs both the
-// exact radix select of sm_ties.hpp and the ordered fp64 accumulation of sm_geo.hpp in one call; every step of it is
+// exact radix select of sm_delta.hpp and the ordered fp64 accumulation of sm_geo.hpp in one call; every step of it is
 // one correctly rounded operation or an exact order statistic in a stated order, so these kernels equal a plain
 // restatement of it bit for bit.
 //
@@ -10,7 +10,7 @@
 //                    11 + 10 + 10 bits as in ties_hist.  ONE selection stream whatever k: one LDS histogram per
 //                    work-group.  Level 1 also raises a flag bit per finetune whose delta holds a NaN or an Inf and
 //                    counts the elements with q == 0, so that nz is known.
-//   sce_select       the walk of ties_select on that stream; level 1 first turns nz into k_keep on the device.  After
+//   sce_select       the radix step of ties_select (sm_delta.hpp) on that stream; level 1 first turns nz into k_keep on the device.  After
 //                    level 3 the threshold and the selected count are final and stay on the device.
 //   sce_energy       E_i = sum of x_i^2 in fp64 over the selected elements, in the order of geo_gram: a work-group of
 //                    256 per 32768-element segment, octet o to lane o % 256, the binary tree through LDS.
@@ -29,32 +29,28 @@ constexpr uint32_t SCE_KEY_NONE = 0xffffffffu; // a threshold key that no score 
 
 // selection state and results (device memory, zeroed before a call)
 struct SceState {
-    unsigned long long rank;    // 1-based rank (from the largest) wanted among the keys that share `prefix`
-    unsigned long long above;   // keys known to be larger than every key with this prefix
+    RadixState sel;             // the one selection stream
     unsigned long long zeros;   // elements with q == 0 (level 1)
     unsigned long long k_keep;  // floor(select_topk * nz), from level 1 on
     unsigned long long selected;// elements with q >= tau and q > 0, after level 3
-    uint32_t prefix;            // key bits decided so far (11, 21, then all 31)
     uint32_t tau_key;           // after level 3: the bits of tau, SCE_KEY_NONE when k_keep == 0
     float threshold;            // after level 3: tau, +inf when k_keep == 0
-    uint32_t pad;
 };
 
-// the deltas of 8 elements from i0 on (cnt of them exist, the others are +0): d[i][e] for i < k <= KR; `bad` gains
-// bit i where d_i holds a NaN or an Inf
+// the deltas of octet o (the elements past its cnt are +0): d[i][e] for i < k <= KR; `bad` gains bit i where d_i holds
+// a NaN or an Inf
 template <int KR>
-SM_HD void sce_delta8(const TiesInputs& in, size_t i0, int cnt, bool vec, float (*d)[8], uint32_t& bad) {
+SM_HD void sce_delta8(const TiesInputs& in, const Octet& o, float (*d)[8], uint32_t& bad) {
     float b[8];
-    if (in.shared_base) ties_load8(in.base[0], in.dtype, i0, cnt, vec, b);
+    delta_base8(in, o, b);
 #pragma unroll
     for (int i = 0; i < KR; ++i) {
         if (i < in.k) {
-            ties_load8(in.ft[i], in.dtype, i0, cnt, vec, d[i]);
-            if (!in.shared_base) ties_load8(in.base[i], in.dtype, i0, cnt, vec, b);
+            delta_load8(in, i, o, b, d[i]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 d[i][e] = d[i][e] - b[e];
-                if ((f2u(d[i][e]) & 0x7fffffffu) >= TIES_KEY_INF) bad |= 1u << i;
+                if (delta_key(d[i][e]) >= TIES_KEY_INF) bad |= 1u << i;
             }
         }
     }
@@ -97,52 +93,36 @@ SM_HD void k_sce_hist(Ex& ex, const SceHistParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
     uint32_t* lh = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [nbins] and, level 1, the count of q == 0 after them
-    const int nt = ex.nthreads();
-    const int nbins = p.level == 1 ? HIST1_BINS : HIST_LO_BINS;
-    const size_t noct = (p.in.n + 7) / 8;
-    const uint32_t prefix = p.level == 1 ? 0u : p.state->prefix;
-    ex.each(st, [&](int tid, EmptyState&) { for (int b = tid; b < nbins + 1; b += nt) lh[b] = 0; });
-    ex.sync();
+    const int nbins = radix_bins(p.level);
+    const uint32_t prefix = p.level == 1 ? 0u : p.state->sel.prefix;
+    hist_zero(ex, st, lh, nbins + 1);
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         uint32_t bad = 0;
-        for (int c = 0; c < p.chunks; ++c) {
-            const size_t oi = start + (size_t)c * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
+        for (int q = 0; q < p.chunks; ++q) {
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
             float d[KR][8];
             uint32_t key[8];
-            sce_delta8<KR>(p.in, i0, cnt, vec, d, bad);
+            sce_delta8<KR>(p.in, o, d, bad);
             sce_key8<KR>(p.in.k, d, key);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                if (e < cnt) {
-                    if (p.level == 1) {
-                        ex.lds_atomic_add(&lh[key[e] >> 20], 1u);
-                        if (key[e] == 0u) ex.lds_atomic_add(&lh[nbins], 1u);
-                    } else if (p.level == 2) {
-                        if ((key[e] >> 20) == prefix) ex.lds_atomic_add(&lh[(key[e] >> 10) & 1023u], 1u);
-                    } else {
-                        if ((key[e] >> 10) == prefix) ex.lds_atomic_add(&lh[key[e] & 1023u], 1u);
-                    }
+                if (e < o.cnt) {
+                    const int bin = radix_bin(p.level, key[e], prefix);
+                    if (bin >= 0) ex.lds_atomic_add(&lh[bin], 1u);
+                    if (p.level == 1 && key[e] == 0u) ex.lds_atomic_add(&lh[nbins], 1u);
                 }
             }
         }
         if (bad && p.level == 1) ex.global_atomic_or_u32(p.flags, bad);
     });
-    ex.sync();
+    hist_flush(ex, st, lh, nbins, [&](int b) { return &p.hist[b]; });
     ex.each(st, [&](int tid, EmptyState&) {
-        for (int b = tid; b < nbins; b += nt) {
-            const uint32_t v = lh[b];
-            if (v) ex.global_atomic_add(&p.hist[b], (unsigned long long)v);
-        }
         if (tid == 0 && p.level == 1 && lh[nbins]) ex.global_atomic_add(&p.state->zeros, (unsigned long long)lh[nbins]);
     });
 }
 
-// one work-group of TIES_SELECT_THREADS; thread t owns TIES_SELECT_PER consecutive bins
+// one work-group of TIES_SELECT_THREADS
 struct SceSelectParams {
     int level;                       // 1, 2 or 3
     unsigned long long n;            // elements of the tensor
@@ -155,24 +135,14 @@ SM_HD void k_sce_select(Ex& ex, const SceSelectParams& p) {
     typename Ex::template State<TiesSelectState> st;
     ex.init(st);
     unsigned long long* part = (unsigned long long*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [TIES_SELECT_THREADS]
-    const int nbins = p.level == 1 ? HIST1_BINS : HIST_LO_BINS;
+    const int nbins = radix_bins(p.level);
     const unsigned long long* h = p.hist;
     SceState* s = p.state;
     // level 1: k_keep = floor(select_topk * nz) - one fp64 multiply and a truncation; every thread reads the same state
     // before the barrier below, the one thread that owns the rank writes it after
     const unsigned long long k_keep = p.level == 1 ? (unsigned long long)geo_dmul(p.select_topk, (double)(p.n - s->zeros)) : s->k_keep;
-    const unsigned long long rank = p.level == 1 ? k_keep : s->rank;
-    const unsigned long long above0 = p.level == 1 ? 0ull : s->above;
-    const uint32_t prefix0 = p.level == 1 ? 0u : s->prefix;
-    ex.each(st, [&](int tid, TiesSelectState& t) {
-        unsigned long long a = 0;
-        for (int q = 0; q < TIES_SELECT_PER; ++q) {
-            const int b = tid * TIES_SELECT_PER + q;
-            if (b < nbins) a += h[b];
-        }
-        t.own = a;
-        part[tid] = a;
-    });
+    const RadixState s0 = radix_start(p.level, k_keep, s->sel);
+    ex.each(st, [&](int tid, TiesSelectState& t) { part[tid] = t.own = radix_own_sum(h, nbins, tid); });
     ex.sync();
     ex.each(st, [&](int tid, TiesSelectState& t) {
         if (k_keep == 0) {            // nothing is selected: the threshold is +inf and no key reaches SCE_KEY_NONE
@@ -180,27 +150,14 @@ SM_HD void k_sce_select(Ex& ex, const SceSelectParams& p) {
             if (tid == 0 && p.level == 3) { s->tau_key = SCE_KEY_NONE; s->threshold = u2f(TIES_KEY_INF); s->selected = 0; }
             return;
         }
-        unsigned long long higher = 0;                       // keys in the bins of the threads after this one
-        for (int q = tid + 1; q < TIES_SELECT_THREADS; ++q) higher += part[q];
-        if (!(higher < rank && rank <= higher + t.own)) return;
-        // the bin that holds the rank-th largest key is one of this thread's
-        for (int q = TIES_SELECT_PER - 1; q >= 0; --q) {
-            const int b = tid * TIES_SELECT_PER + q;
-            const unsigned long long c = b < nbins ? h[b] : 0ull;
-            if (rank <= higher + c) {
-                const uint32_t prefix = (prefix0 << (p.level == 1 ? 0 : 10)) | (uint32_t)b;
-                s->prefix = prefix;
-                s->rank = rank - higher;
-                s->above = above0 + higher;
-                if (p.level == 1) s->k_keep = k_keep;
-                if (p.level == 3) {                          // the bin is one key: tau; ties at it are all selected
-                    s->tau_key = prefix;
-                    s->threshold = u2f(prefix);
-                    s->selected = above0 + higher + (prefix != 0u ? c : 0ull);   // (k_keep <= nz: tau > 0 always)
-                }
-                return;
-            }
-            higher += c;
+        const RadixFound f = radix_select_step(h, nbins, part, t.own, s0.rank, tid);
+        if (!f.found) return;
+        const RadixState s1 = s->sel = radix_advance(p.level, s0, f);
+        if (p.level == 1) s->k_keep = k_keep;
+        if (p.level == 3) {                                  // the bin is one key: tau; ties at it are all selected
+            s->tau_key = s1.prefix;
+            s->threshold = u2f(s1.prefix);
+            s->selected = s1.above + (s1.prefix != 0u ? f.c : 0ull);     // (k_keep <= nz: tau > 0 always)
         }
     });
 }
@@ -226,20 +183,17 @@ SM_HD void k_sce_energy(Ex& ex, const SceEnergyParams& p) {
     double* red = (double*)(ex.lds() + LDS_SCRATCH_FLOATS);        // [KR][nt] (LDS_SCRATCH_FLOATS is even)
     const size_t start = seg * GEO_SEG_ELEMS;
     const size_t len = p.in.n - start < GEO_SEG_ELEMS ? p.in.n - start : GEO_SEG_ELEMS;
-    const size_t noct = (len + 7) / 8;
     const uint32_t tau = p.select ? p.state->tau_key : 0u;
     ex.each(st, [&](int tid, EmptyState&) {
         double acc[KR];
 #pragma unroll
         for (int i = 0; i < KR; ++i) acc[i] = 0.0;
         uint32_t bad = 0;
-        for (size_t o = tid; o < noct; o += nt) {
-            const size_t i0 = start + 8 * o;
-            const int cnt = (int)((len - 8 * o) < 8 ? (len - 8 * o) : 8);
-            const bool vec = p.seg_vec && cnt == 8;
+        for (size_t q = tid; q < segment_octets(len); q += nt) {
+            const Octet o = segment_octet(start, len, p.seg_vec, q);
             float d[KR][8];
             uint32_t key[8];
-            sce_delta8<KR>(p.in, i0, cnt, vec, d, bad);
+            sce_delta8<KR>(p.in, o, d, bad);
             if (p.select) sce_key8<KR>(k, d, key);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -307,31 +261,25 @@ template <int KR, class Ex>
 SM_HD void k_sce_merge(Ex& ex, const SceMergeParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
-    const int nt = ex.nthreads();
     const int k = p.in.k;
-    const size_t noct = (p.in.n + 7) / 8;
     const float eps = 1e-8f;
     const uint32_t tau = p.select ? p.state->tau_key : 0u;
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
-        for (int c = 0; c < p.chunks; ++c) {
-            const size_t oi = start + (size_t)c * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
+        for (int q = 0; q < p.chunks; ++q) {
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
             float d[KR][8], bo[8];
             uint32_t key[8], bad = 0;
-            sce_delta8<KR>(p.in, i0, cnt, vec, d, bad);
+            sce_delta8<KR>(p.in, o, d, bad);
             if (p.select) sce_key8<KR>(k, d, key);
-            // (base_out last: when it is the shared base the line is still in cache from sce_delta8)
-            ties_load8(p.out_is_base0 ? p.in.base[0] : p.base_out, p.out_is_base0 ? p.in.dtype : p.base_out_dtype, i0, cnt, vec, bo);
+            // (base_out last and, where it is the shared base, loaded again - the line is still in cache from sce_delta8 -
+            // instead of delta_base_out8's copy: the k deltas leave no registers to hold the base that long)
+            ties_load8(p.out_is_base0 ? p.in.base[0] : p.base_out, p.out_is_base0 ? p.in.dtype : p.base_out_dtype, o.i0, o.cnt, o.vec, bo);
             float r[8], dl[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const bool sel = !p.select || (key[e] >= tau && key[e] != 0u);
-                // The sums over the agreeing entries equal the running sums of the positive (elected +1) or of the
-                // negative (elected -1) entries: the skipped terms are +0 and x + 0 = x.  Both are kept, the election picks.
+                // SCE's own election (not sm_delta.hpp's Election): the sum S is unweighted, the weights act on P / N alone
                 float S = 0.f, P = 0.f, N = 0.f, DP = 0.f, DN = 0.f;
 #pragma unroll
                 for (int i = 0; i < KR; ++i) {
@@ -350,7 +298,7 @@ SM_HD void k_sce_merge(Ex& ex, const SceMergeParams& p) {
                 dl[e] = aten_fmul_(p.lambda, M);
                 r[e] = aten_fadd_(bo[e], dl[e]);
             }
-            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, dl);
+            delta_store8(p, o, r, dl);
         }
     });
 }

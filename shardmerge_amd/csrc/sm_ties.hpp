@@ -14,44 +14,18 @@
 //   ties_merge   the fused streaming pass: K finetunes, their bases and base_out are loaded once, trim / weights /
 //                sign election / masked sums / division / add-back happen in registers, out is written once.
 // Every level re-reads the inputs (no candidate lists): selection reads 3 (K + 1) tensors when the base is shared.
+// The octet walk, the loader, the election and the radix step are sm_delta.hpp's; here are the keep test key >= tau and
+// what ties_select writes.
 #pragma once
-#include "sm_kernels.hpp"
+#include "sm_delta.hpp"
 
 namespace smhip {
-
-constexpr int TIES_MAX_MODELS = 16;
-constexpr int TIES_GROUP = 4;                 // finetunes per ties_hist launch (an LDS histogram each)
-constexpr uint32_t TIES_KEY_INF = 0x7f800000u;
-
-// selection state of one finetune (device memory)
-struct TiesState {
-    unsigned long long rank;    // 1-based rank (from the largest) wanted among the keys that share `prefix`
-    unsigned long long above;   // keys known to be larger than every key with this prefix
-    uint32_t prefix;            // key bits decided so far (11, 21, then all 31: the threshold)
-    uint32_t pad;
-};
-
-struct TiesInputs {
-    int k;
-    const void* ft[TIES_MAX_MODELS];
-    const void* base[TIES_MAX_MODELS];
-    int dtype;                  // finetunes and their bases
-    size_t n;
-    int aligned;                // every pointer (out included) is 16-byte aligned: full octets use 16-byte accesses
-    int shared_base;            // every base[i] is base[0]
-};
-
-// 8 elements from i0 on (cnt of them exist)
-SM_HD void ties_load8(const void* src, int dtype, size_t i0, int cnt, bool vec, float* dst) {
-    if (vec) { load_elem8(src, dtype, i0, dst); return; }
-    for (int e = 0; e < 8; ++e) dst[e] = e < cnt ? load_elem(src, dtype, i0 + e) : 0.f;
-}
 
 struct TiesHistParams {
     TiesInputs in;
     int first, count;           // the finetunes of this launch: first .. first + count - 1, count <= TIES_GROUP
     int level;                  // 1, 2 or 3
-    const TiesState* state;     // [k]
+    const RadixState* state;    // [k]
     unsigned long long* hist;   // [k][HIST1_BINS] of this level
     uint32_t* flags;            // [0]: bit i = finetune i has a non-finite delta
     int chunks;                 // octets per thread
@@ -61,64 +35,42 @@ SM_HD void k_ties_hist(Ex& ex, const TiesHistParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
     uint32_t* lh = (uint32_t*)(ex.lds() + LDS_SCRATCH_FLOATS);
-    const int nt = ex.nthreads();
-    const int nbins = p.level == 1 ? HIST1_BINS : HIST_LO_BINS;
-    const size_t noct = (p.in.n + 7) / 8;
-    ex.each(st, [&](int tid, EmptyState&) { for (int b = tid; b < nbins * p.count; b += nt) lh[b] = 0; });
-    ex.sync();
+    const int nbins = radix_bins(p.level);
+    hist_zero(ex, st, lh, nbins * p.count);
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         uint32_t bad = 0;
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oi = start + (size_t)q * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
             float b[8];
-            if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
+            delta_base8(p.in, o, b);
             for (int j = 0; j < p.count; ++j) {
                 const int i = p.first + j;
                 float f[8];
-                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);
-                if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                delta_load8(p.in, i, o, b, f);
                 const uint32_t prefix = p.level == 1 ? 0u : p.state[i].prefix;
                 uint32_t* h = lh + j * nbins;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    if (e < cnt) {
-                        const uint32_t key = f2u(f[e] - b[e]) & 0x7fffffffu;
-                        if (p.level == 1) {
-                            if (key >= TIES_KEY_INF) bad |= 1u << i;
-                            ex.lds_atomic_add(&h[key >> 20], 1u);
-                        } else if (p.level == 2) {
-                            if ((key >> 20) == prefix) ex.lds_atomic_add(&h[(key >> 10) & 1023u], 1u);
-                        } else {
-                            if ((key >> 10) == prefix) ex.lds_atomic_add(&h[key & 1023u], 1u);
-                        }
+                    if (e < o.cnt) {
+                        const uint32_t key = delta_key(f[e] - b[e]);
+                        if (p.level == 1 && key >= TIES_KEY_INF) bad |= 1u << i;
+                        const int bin = radix_bin(p.level, key, prefix);
+                        if (bin >= 0) ex.lds_atomic_add(&h[bin], 1u);
                     }
                 }
             }
         }
         if (bad) ex.global_atomic_or_u32(p.flags, bad);
     });
-    ex.sync();
-    ex.each(st, [&](int tid, EmptyState&) {
-        for (int b = tid; b < nbins * p.count; b += nt) {
-            const uint32_t v = lh[b];
-            if (v) ex.global_atomic_add(&p.hist[(size_t)(p.first + b / nbins) * HIST1_BINS + (b % nbins)], (unsigned long long)v);
-        }
-    });
+    hist_flush(ex, st, lh, nbins * p.count, [&](int b) { return &p.hist[(size_t)(p.first + b / nbins) * HIST1_BINS + (b % nbins)]; });
 }
 
-// one work-group of TIES_SELECT_THREADS per finetune; thread t owns TIES_SELECT_PER consecutive bins
-constexpr int TIES_SELECT_THREADS = 256;
-constexpr int TIES_SELECT_PER = HIST1_BINS / TIES_SELECT_THREADS;
 struct TiesSelectParams {
     int level;                       // 1, 2 or 3
     unsigned long long k_keep;       // elements to keep per finetune (0: the threshold is +inf)
     const unsigned long long* hist;  // [k][HIST1_BINS] of this level
-    TiesState* state;                // [k]
+    RadixState* state;               // [k]
     float* threshold;                // [k], written after level 3
     unsigned long long* kept;        // [k], written after level 3
 };
@@ -129,82 +81,25 @@ SM_HD void k_ties_select(Ex& ex, const TiesSelectParams& p) {
     ex.init(st);
     unsigned long long* part = (unsigned long long*)(ex.lds() + LDS_SCRATCH_FLOATS);     // [TIES_SELECT_THREADS]
     const int m = ex.bid();
-    const int nbins = p.level == 1 ? HIST1_BINS : HIST_LO_BINS;
+    const int nbins = radix_bins(p.level);
     const unsigned long long* h = p.hist + (size_t)m * HIST1_BINS;
-    TiesState* s = p.state + m;
-    const unsigned long long rank = p.level == 1 ? p.k_keep : s->rank;
-    const unsigned long long above0 = p.level == 1 ? 0ull : s->above;
-    const uint32_t prefix0 = p.level == 1 ? 0u : s->prefix;
-    ex.each(st, [&](int tid, TiesSelectState& t) {
-        unsigned long long a = 0;
-        for (int q = 0; q < TIES_SELECT_PER; ++q) {
-            const int b = tid * TIES_SELECT_PER + q;
-            if (b < nbins) a += h[b];
-        }
-        t.own = a;
-        part[tid] = a;
-    });
+    RadixState* s = p.state + m;
+    const RadixState s0 = radix_start(p.level, p.k_keep, *s);
+    ex.each(st, [&](int tid, TiesSelectState& t) { part[tid] = t.own = radix_own_sum(h, nbins, tid); });
     ex.sync();
     ex.each(st, [&](int tid, TiesSelectState& t) {
         if (p.k_keep == 0) {          // nothing is kept: no finite magnitude reaches +inf
             if (tid == 0 && p.level == 3) { p.threshold[m] = u2f(TIES_KEY_INF); p.kept[m] = 0; }
             return;
         }
-        unsigned long long higher = 0;                       // keys in the bins of the threads after this one
-        for (int q = tid + 1; q < TIES_SELECT_THREADS; ++q) higher += part[q];
-        if (!(higher < rank && rank <= higher + t.own)) return;
-        // the bin that holds the rank-th largest key is one of this thread's
-        for (int q = TIES_SELECT_PER - 1; q >= 0; --q) {
-            const int b = tid * TIES_SELECT_PER + q;
-            const unsigned long long c = b < nbins ? h[b] : 0ull;
-            if (rank <= higher + c) {
-                const uint32_t prefix = (prefix0 << (p.level == 1 ? 0 : 10)) | (uint32_t)b;
-                s->prefix = prefix;
-                s->rank = rank - higher;
-                s->above = above0 + higher;
-                if (p.level == 3) {                          // the bin is one key: the threshold; ties at it are all kept
-                    p.threshold[m] = u2f(prefix);
-                    p.kept[m] = above0 + higher + (prefix != 0u ? c : 0ull);     // a zero delta is never kept
-                }
-                return;
-            }
-            higher += c;
+        const RadixFound f = radix_select_step(h, nbins, part, t.own, s0.rank, tid);
+        if (!f.found) return;
+        const RadixState s1 = *s = radix_advance(p.level, s0, f);
+        if (p.level == 3) {                                  // the bin is one key: the threshold; ties at it are all kept
+            p.threshold[m] = u2f(s1.prefix);
+            p.kept[m] = s1.above + (s1.prefix != 0u ? f.c : 0ull);       // a zero delta is never kept
         }
     });
-}
-
-// the store tail of a fused merge pass (ties_merge, dare_merge): octet oi of out (r, rounded once to out_dtype) and of the
-// optional fp32 delta_out (dl); cnt of the 8 elements exist, vec: one 16-byte store per 8 x 16 bit / two per 8 x fp32
-SM_HD void ties_store8(void* out, int out_dtype, float* delta_out, size_t oi, int cnt, bool vec, const float* r, const float* dl) {
-    const size_t i0 = 8 * oi;
-    if (delta_out) {
-        if (vec) {
-            cf4 w0 = {dl[0], dl[1], dl[2], dl[3]}, w1 = {dl[4], dl[5], dl[6], dl[7]};
-            ((cf4*)delta_out)[i0 / 4] = w0; ((cf4*)delta_out)[i0 / 4 + 1] = w1;
-        } else {
-            for (int e = 0; e < cnt; ++e) delta_out[i0 + e] = dl[e];
-        }
-    }
-    if (out_dtype == DT_F32) {
-        if (vec) {
-            cf4 w0 = {r[0], r[1], r[2], r[3]}, w1 = {r[4], r[5], r[6], r[7]};
-            ((cf4*)out)[i0 / 4] = w0; ((cf4*)out)[i0 / 4 + 1] = w1;
-        } else {
-            for (int e = 0; e < cnt; ++e) ((float*)out)[i0 + e] = r[e];
-        }
-    } else {
-        uint16_t h[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = out_dtype == DT_BF16 ? f_to_bf16_any(r[e]) : f_to_f16_any(r[e]);
-        if (vec) {
-            u32x4 w;
-            w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16); w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-            w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16); w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
-            ((u32x4*)out)[oi] = w;
-        } else {
-            for (int e = 0; e < cnt; ++e) ((uint16_t*)out)[i0 + e] = h[e];
-        }
-    }
 }
 
 struct TiesMergeParams {
@@ -223,60 +118,31 @@ template <class Ex>
 SM_HD void k_ties_merge(Ex& ex, const TiesMergeParams& p) {
     typename Ex::template State<EmptyState> st;
     ex.init(st);
-    const int nt = ex.nthreads();
-    const size_t noct = (p.in.n + 7) / 8;
-    const float eps = 1e-8f;
     ex.each(st, [&](int tid, EmptyState&) {
-        const size_t start = (size_t)ex.bid() * p.chunks * nt;
         for (int q = 0; q < p.chunks; ++q) {
-            const size_t oi = start + (size_t)q * nt + tid;
-            if (oi >= noct) break;
-            const size_t i0 = 8 * oi;
-            const int cnt = (int)((p.in.n - i0) < 8 ? (p.in.n - i0) : 8);
-            const bool vec = p.in.aligned && cnt == 8;
-            float b[8], bo[8], S[8], P[8], N[8], DP[8], DN[8];
-            if (p.in.shared_base) ties_load8(p.in.base[0], p.in.dtype, i0, cnt, vec, b);
-            if (p.out_is_base0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bo[e] = b[e];
-            } else {
-                ties_load8(p.base_out, p.base_out_dtype, i0, cnt, vec, bo);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { S[e] = 0.f; P[e] = 0.f; N[e] = 0.f; DP[e] = 0.f; DN[e] = 0.f; }
-            // The sum over the agreeing entries equals the running sum of the positive (elected +1) or of the negative
-            // (elected -1) weighted deltas: the skipped terms are +0 and x + 0 = x.  Both are kept, the election picks.
+            Octet o;
+            if (!octet_at(p.in, ex.bid(), ex.nthreads(), p.chunks, tid, q, o)) break;
+            float b[8], bo[8];
+            delta_base8(p.in, o, b);
+            delta_base_out8(p, o, b, bo);
+            Election el;
+            el.clear();
             for (int i = 0; i < p.in.k; ++i) {
                 float f[8];
-                ties_load8(p.in.ft[i], p.in.dtype, i0, cnt, vec, f);
-                if (!p.in.shared_base) ties_load8(p.in.base[i], p.in.dtype, i0, cnt, vec, b);
+                delta_load8(p.in, i, o, b, f);
                 const uint32_t tau = f2u(p.threshold[i]);
                 const float al = p.alpha[i];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float d = f[e] - b[e];
-                    const uint32_t key = f2u(d) & 0x7fffffffu;
+                    const uint32_t key = delta_key(d);
                     const bool kept = key >= tau && key != 0u;
-                    const float tv = kept ? aten_fmul_(d, al) : 0.f;
-                    S[e] = aten_fadd_(S[e], tv);
-                    if (tv > 0.f) { P[e] = aten_fadd_(P[e], tv); DP[e] = aten_fadd_(DP[e], al); }
-                    if (tv < 0.f) { N[e] = aten_fadd_(N[e], tv); DN[e] = aten_fadd_(DN[e], al); }
+                    el.add(e, kept ? aten_fmul_(d, al) : 0.f, al, 1);
                 }
             }
             float r[8], dl[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool pos = S[e] >= 0.f;
-                float M = pos ? P[e] : N[e];
-                if (p.normalize) {
-                    float D = pos ? DP[e] : DN[e];
-                    if (fabsf(D) < eps) D = 1.f;
-                    M = M / D;
-                }
-                dl[e] = aten_fmul_(p.lambda, M);
-                r[e] = aten_fadd_(bo[e], dl[e]);
-            }
-            ties_store8(p.out, p.base_out_dtype, p.delta_out, oi, cnt, vec, r, dl);
+            el.finish(1, p.normalize, 0.f, p.lambda, bo, r, dl);
+            delta_store8(p, o, r, dl);
         }
     });
 }

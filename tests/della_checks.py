@@ -171,8 +171,10 @@ def check_nonfinite(engine, device="cpu"):
             fts, bases, bo = make_inputs(SMALL, 3, seed=80, device=device)
             fts[1] = fts[1].clone()
             fts[1].view(-1)[4321] = poison
-            with pytest.raises(ValueError, match=r"model\.layers\.7\.mlp\.up_proj\.weight.*finetune 1\b"):
+            with pytest.raises(ValueError, match=r"model\.layers\.7\.mlp\.up_proj\.weight.*finetune 1\b") as err:
                 engine.della_merge(fts, bases, ALPHAS[:3], bo, epsilon=epsilon, layer_name="model.layers.7.mlp.up_proj.weight")
+            # (epsilon == 0 runs DARE's pass: the text still names this entry point)
+            assert str(err.value).endswith(": della_merge: NaN or Inf in finetune - base of finetune 1"), err.value
         fts, bases, bo = make_inputs(SMALL, 3, seed=81, device=device)
         check(engine, fts, bases, ALPHAS[:3], bo, label="after an error")
     fts, bases, bo = make_inputs(SMALL, 2, torch.float32, seed=82, own_bases=True, device=device)
