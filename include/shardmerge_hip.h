@@ -510,6 +510,67 @@ typedef struct {
 int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* desc, void* out, float* delta_out, uint16_t* threshold_out,
                       smhip_della_report* report, void* stream);
 
+/* ---- Consensus merge (Wang et al., "Localizing Task Information for Improved Model Merging and Compression", ICML
+ *      2024): per finetune a TALL mask marks where its own entry outweighs what the other tasks did to the same weight,
+ *      and an element of the multi-task vector survives only where at least consensus_k of those masks agree - the
+ *      "selfish" weights that serve one task and the "catastrophic" ones that serve none are dropped.  Two flavours: on
+ *      top of task arithmetic (ties == 0, consensus_ta) and on top of TIES (ties == 1, consensus_ties).  The reference
+ *      has no such operator; this section IS its definition.  For one tensor of n elements (any shape, flat), finetunes
+ *      i = 0..k-1 in order (1 <= k <= 16):
+ *        1. d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with SMHIP_ERR_NONFINITE
+ *           (the message lists the finetunes), detected as smhip_dare_merge detects it; out is then unspecified.
+ *        2. tv_i = fl32(d_i * fp32(alpha_i)), for EVERY element: the trim of ties == 1 does not touch tv_i.
+ *        3. The multi-task vector U.
+ *           ties == 0: U = ((0 + tv_0) + tv_1) + ... in fp32, in order.
+ *           ties == 1: U = M of smhip_ties_merge steps 2-6 at `density`, `normalize` as given: the same tie rule, thresholds,
+ *           election, division by the agreeing weights and |D| < 1e-8 -> 1.
+ *        4. m_i = [ |tv_i| >= fl32(fp32(mask_lambda) * |fl32(U - tv_i)|) ], an IEEE comparison: a NaN on the right
+ *           (0 * inf) compares false.  An element whose deltas are all zero has every mask set (0 >= 0): it changes
+ *           nothing in the output, but it does count in masked[] and in agree[k].
+ *        5. c = sum_i m_i, an integer.  The element is SELECTED iff c >= min(consensus_k, k): a tensor that a layer
+ *           window leaves with fewer entries than consensus_k needs all of them to agree, so one entry is taken as it
+ *           is (ties == 0: U - tv_0 = 0 and its mask always holds) - the convention of the other operators.
+ *        6. ties == 0: M = U / D when normalize, D = ((0 + fp32(alpha_0)) + ...) over all finetunes, D := 1 where
+ *           |D| < fp32(1e-8) (the linear variants' divisor); M = U otherwise.  ties == 1: M = U.
+ *           M := +0 where the element is not selected.
+ *        7. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M)), delta_out = fl32(lambda * M):
+ *           step 7 of smhip_ties_merge.
+ *      Every step is one correctly rounded fp32 operation, a comparison, an integer count or (ties == 1) an exact order
+ *      statistic: the result is defined bit for bit.  With mask_lambda = 0 and consensus_k = 1 every finite element is
+ *      selected: ties == 0 then equals smhip_dare_merge (sign_election 0) at density 1, ties == 1 equals
+ *      smhip_ties_merge at the same density.  The selected sets are nested in consensus_k.  ties == 0 is ONE kernel, one
+ *      pass over the inputs (k + 2 tensor passes); ties == 1 adds the three selection levels of TIES (4k + 5).  The k
+ *      entries of an element stay in registers between the sum and the masks: no finetune is read twice by the kernel.
+ *      Counters are integers (LDS, then one global atomic per counter and work-group), no floating-point atomics; the
+ *      call synchronises the stream once, at its end.  Aliasing, alignment, n == 0, dtypes and the size limit: the
+ *      rules of smhip_ties_merge.  SMHIP_ERR_ARG: k or consensus_k outside 1..16, mask_lambda negative, NaN or above
+ *      1e6, density outside (0, 1] when ties, lambda or an alpha not finite, out overlapping an input, a bad dtype, a
+ *      null descriptor.  Profile names: "consensus_merge" and, ties == 1, "ties_hist" / "ties_select". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double density, lambda; int normalize;  /* density: ties == 1 only */
+    double mask_lambda;                     /* lambda of the TALL mask, 0 <= mask_lambda <= 1e6 */
+    int consensus_k;                        /* masks that must agree, 1..16 (min(consensus_k, k) in effect) */
+    int ties;                               /* 1: consensus_ties; 0: consensus_ta */
+} smhip_consensus_desc;
+typedef struct {
+    uint64_t k_keep;                        /* ties == 1: as smhip_ties_report; zero otherwise, as threshold and kept */
+    float threshold[SMHIP_MAX_MODELS];
+    uint64_t kept[SMHIP_MAX_MODELS];
+    uint64_t masked[SMHIP_MAX_MODELS];      /* elements with m_i set */
+    uint64_t agree[SMHIP_MAX_MODELS + 1];   /* elements with exactly c masks set; they sum to n */
+    uint64_t selected;                      /* elements with c >= min(consensus_k, k) */
+} smhip_consensus_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * M).  report (optional): HOST. */
+int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* desc, void* out, float* delta_out,
+                          smhip_consensus_report* report, void* stream);
+
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector
  *      v1 - v0 dot is normalised along the LAST dimension (F.normalize(dim=-1), eps 1e-12), out = v0 cos + rel sin.

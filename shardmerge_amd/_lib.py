@@ -149,6 +149,17 @@ class DellaReport(C.Structure):
     _fields_ = [("T_lo", C.c_uint32), ("T_hi", C.c_uint32), ("kept", C.c_uint64 * MAX_MODELS)]
 
 
+class ConsensusDesc(C.Structure):
+    """smhip_consensus_desc: smhip_ties_desc, then mask_lambda, consensus_k and ties"""
+    _fields_ = _DELTA_DESC_FIELDS + [("mask_lambda", C.c_double), ("consensus_k", C.c_int), ("ties", C.c_int)]
+
+
+class ConsensusReport(C.Structure):
+    """smhip_consensus_report"""
+    _fields_ = [("k_keep", C.c_uint64), ("threshold", C.c_float * MAX_MODELS), ("kept", C.c_uint64 * MAX_MODELS),
+                ("masked", C.c_uint64 * MAX_MODELS), ("agree", C.c_uint64 * (MAX_MODELS + 1)), ("selected", C.c_uint64)]
+
+
 DELLA_MAX_COLS = 32768          # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -206,6 +217,7 @@ class SmhipLibrary:
         d.smhip_geo_merge.argtypes = [P, C.POINTER(GeoDesc), P, P, C.POINTER(GeoReport), P]
         d.smhip_sce_merge.argtypes = [P, C.POINTER(SceDesc), P, P, C.POINTER(SceReport), P]
         d.smhip_della_merge.argtypes = [P, C.POINTER(DellaDesc), P, P, P, C.POINTER(DellaReport), P]
+        d.smhip_consensus_merge.argtypes = [P, C.POINTER(ConsensusDesc), P, P, C.POINTER(ConsensusReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

@@ -78,6 +78,17 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # della_normalize: 1      #   1: divide by the sum of the weights (della: of the agreeing entries), 0: plain sum
       # della_rescale: 1        #   1: survivors times 1 / their effective probability, 0: left as they are
       # seed: 0                 #   as with dare_ties: an integer in [0, 2^63)
+                                # | consensus_ta | consensus_ties (Consensus Merging with TALL masks, Wang et al. 2024; no
+                                #   counterpart in the reference): the weighted deltas are added (consensus_ta) or merged as
+                                #   ties merges (consensus_ties) into a multi-task vector; a finetune's mask is set where its
+                                #   own weighted entry is at least mask_lambda times what the others did to the same weight;
+                                #   an element of the multi-task vector is kept where at least consensus_k masks are set.  The
+                                #   spectral keys, norm_mode, task_add_models and every other family's keys are rejected; keys:
+      # mask_lambda: 0.4        #   0 <= mask_lambda <= 1e6; 0 sets every mask
+      # consensus_k: 2          #   an integer in 1..16: masks that must agree (all of them where fewer finetunes cover a tensor)
+      # consensus_lambda: 1.0   #   scales the merged delta
+      # consensus_normalize: 1  #   1: divide by the sum of the weights (consensus_ties: of the agreeing entries), 0: plain sum
+      # density: 0.2            #   operator consensus_ties only: the trim of ties, 0 < density <= 1
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -104,9 +115,10 @@ MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
-             "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear")
+             "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
-# (all of them take `density`), seed stays an int (it must survive exactly), every other value becomes a float.
+# (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
+# other value becomes a float.
 TIES_OPTION_DEFAULTS = {"density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1.0}
 DARE_OPERATORS = ("dare_ties", "dare_linear")
 DARE_OPTION_DEFAULTS = {"density": 0.2, "dare_lambda": 1.0, "dare_normalize": 1.0, "dare_rescale": 1.0, "seed": 0}
@@ -119,6 +131,8 @@ GEO_OPTION_DEFAULTS = {"stock_filter_wise": 0.0}
 SCE_OPTION_DEFAULTS = {"select_topk": 1.0, "sce_lambda": 1.0}
 DELLA_OPERATORS = ("della", "della_linear")
 DELLA_OPTION_DEFAULTS = {"density": 0.5, "epsilon": 0.15, "della_lambda": 1.0, "della_normalize": 1.0, "della_rescale": 1.0, "seed": 0}
+CONSENSUS_OPERATORS = ("consensus_ta", "consensus_ties")
+CONSENSUS_OPTION_DEFAULTS = {"density": 0.2, "mask_lambda": 0.4, "consensus_k": 2, "consensus_lambda": 1.0, "consensus_normalize": 1.0}
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -158,9 +172,10 @@ def _della_window(opts: Dict[str, Any]) -> None:
 
 @dataclass(frozen=True)
 class _OptionFamily:
-    """One family's merge_options.  rules: key -> "flag" (0 or 1), "seed" (an exact integer in [0, 2^63)) or a range
-    (lo, hi, brackets[, the message's own wording of the range]).  earlier: what the message says after a key of an
-    earlier family, by that family's first operator.  only: a key that not every operator of the family takes.  check: a rule over several keys."""
+    """One family's merge_options.  rules: key -> "flag" (0 or 1), "seed" (an exact integer in [0, 2^63)), ("int", lo, hi)
+    (an exact integer in lo..hi, kept an int) or a range (lo, hi, brackets[, the message's own wording of the range]).
+    earlier: what the message says after a key of an earlier family, by that family's first operator.  only: a key that
+    not every operator of the family takes.  check: a rule over several keys."""
     operators: tuple
     defaults: Dict[str, Union[int, float]]
     rules: Dict[str, Any]
@@ -195,6 +210,15 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "breadcrumbs": "(its drop is random, by the rank of the magnitude within the row)",
                            "model_stock": "(it drops at random and weights by alpha)", "sce": "(it selects nothing by variance)"},
                   check=_della_window),
+    _OptionFamily(CONSENSUS_OPERATORS, CONSENSUS_OPTION_DEFAULTS,
+                  {"density": _DENSITY, "mask_lambda": (0, 1e6, "[]"), "consensus_k": ("int", 1, 16), "consensus_lambda": _LAMBDA,
+                   "consensus_normalize": "flag"},
+                  earlier={"ties": "(its keys: consensus_lambda, consensus_normalize)", "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it drops by the agreement of the masks, not by magnitude)",
+                           "model_stock": "(it weights by alpha and drops by the agreement of the masks)",
+                           "sce": "(it selects by the agreement of the masks, not by variance)",
+                           "della": "(it drops nothing at random)"},
+                  only={"density": ("consensus_ties",)}),
 )
 
 
@@ -238,6 +262,11 @@ def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], o
         if rule == "seed":
             if not isinstance(value, int) or isinstance(value, bool) or not (0 <= value < 2 ** 63):
                 raise click.BadParameter(f"merge_options.{key} must be an integer in [0, 2^63)")
+            out[key] = int(value)
+            continue
+        if rule[0] == "int":
+            if not isinstance(value, int) or isinstance(value, bool) or not (rule[1] <= value <= rule[2]):
+                raise click.BadParameter(f"merge_options.{key} must be an integer in {rule[1]}..{rule[2]}")
             out[key] = int(value)
             continue
         if rule == "flag":

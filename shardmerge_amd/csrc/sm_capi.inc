@@ -25,7 +25,8 @@ struct smhip_ctx {
 // The argument checks that smhip_ties_merge, smhip_dare_merge and smhip_breadcrumbs_merge share: their descriptors have
 // the same leading fields (k .. normalize), hence the template.  `op` names the entry point in the messages.
 // smhip_geo_merge shares all of it but the scalars (`scalars`: the operator's own checks, after k and the dtypes) and,
-// in weight space, the bases (`need_base` = false: they are not read and may be NULL); smhip_sce_merge all but the scalars.
+// in weight space, the bases (`need_base` = false: they are not read and may be NULL); smhip_sce_merge, smhip_della_merge and
+// smhip_consensus_merge all but the scalars.
 template <class Desc, class Scalars>
 static int delta_tensor_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out,
                               bool need_base, Scalars scalars) {
@@ -286,6 +287,21 @@ int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* d, void* out, floa
     }
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.della_merge(*d, out, delta_out, threshold_out, report));
+}
+
+int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* d, void* out, float* delta_out,
+                          smhip_consensus_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "consensus_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (d->consensus_k < 1 || d->consensus_k > SMHIP_MAX_MODELS) return "consensus_k out of range (1..16)";
+            if (!(d->mask_lambda >= 0.0 && d->mask_lambda <= 1e6)) return "mask_lambda must be in [0, 1e6]";
+            if (d->ties && !(d->density > 0.0 && d->density <= 1.0)) return "density must be in (0, 1]";
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            return nullptr;
+        }))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.consensus_merge(*d, out, delta_out, report));
 }
 
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {

@@ -1,10 +1,10 @@
 // sm_delta.hpp - what the delta-merge operators (sm_ties.hpp, sm_dare.hpp, sm_breadcrumbs.hpp, sm_geo.hpp, sm_sce.hpp,
-// sm_della.hpp) share on the device, written once:
+// sm_della.hpp, sm_consensus.hpp) share on the device, written once:
 //
 //   Octet, octet_at, segment_octet    block / chunk / thread -> the 8 elements a thread works on
 //   ties_load8, delta_base8, delta_load8, delta_base_out8, delta_store8
 //                                     the operands of an octet's deltas (the base once when shared), base_out, the store
-//   Election                          S / P / N / DP / DN of the TIES sign election: clear, add, finish
+//   Election                          S / P / N / DP / DN of the TIES sign election: clear, add, merged, finish
 //   kept_zero, kept_fold              the kept counters of a drop mask: [k][nt] in LDS -> one global atomic per finetune
 //   RadixState, radix_start, radix_own_sum, radix_select_step, radix_advance
 //                                     one level of the exact select of the rank-th largest 31-bit key
@@ -151,18 +151,23 @@ struct Election {
             if (tv < 0.f) { N[e] = aten_fadd_(N[e], tv); DN[e] = aten_fadd_(DN[e], al); }
         }
     }
+    // M of element e: the elected (or the plain) sum, over its divisor when normalize
+    SM_HD float merged(int e, int elect, int normalize, float Dall) const {
+        const float eps = 1e-8f;
+        const bool pos = S[e] >= 0.f;
+        float M = elect ? (pos ? P[e] : N[e]) : S[e];
+        if (normalize) {
+            float D = elect ? (pos ? DP[e] : DN[e]) : Dall;
+            if (fabsf(D) < eps) D = 1.f;
+            M = M / D;
+        }
+        return M;
+    }
     // dl = lambda * M, r = bo + dl
     SM_HD void finish(int elect, int normalize, float Dall, float lambda, const float* bo, float* r, float* dl) const {
-        const float eps = 1e-8f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const bool pos = S[e] >= 0.f;
-            float M = elect ? (pos ? P[e] : N[e]) : S[e];
-            if (normalize) {
-                float D = elect ? (pos ? DP[e] : DN[e]) : Dall;
-                if (fabsf(D) < eps) D = 1.f;
-                M = M / D;
-            }
+            const float M = merged(e, elect, normalize, Dall);
             dl[e] = aten_fmul_(lambda, M);
             r[e] = aten_fadd_(bo[e], dl[e]);
         }

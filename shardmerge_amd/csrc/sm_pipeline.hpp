@@ -22,6 +22,7 @@
 #include "sm_geo.hpp"
 #include "sm_sce.hpp"
 #include "sm_della.hpp"
+#include "sm_consensus.hpp"
 
 namespace smhip {
 
@@ -247,6 +248,10 @@ SM_KERNEL_TAG_LB(KSceMergeAny, SceMergeParams, "sce_merge", k_sce_merge<TIES_MAX
 SM_KERNEL_TAG_LB(KDellaTable, DellaTableParams, "della_table", k_della_table(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KDellaRank, DellaRankParams, "della_rank", k_della_rank(ex, p), 1024, 4)
 SM_KERNEL_TAG_LB(KDellaMerge, DellaMergeParams, "della_merge", k_della_merge(ex, p), 256, 4)
+// Consensus merge (sm_consensus.hpp): the one fused pass with the k weighted entries of an octet in registers across the
+// sum / election; k <= 4 at dare_merge's residency, or up to 16
+SM_KERNEL_TAG_LB(KConsensusMerge, ConsensusMergeParams, "consensus_merge", k_consensus_merge<CONSENSUS_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KConsensusMergeAny, ConsensusMergeParams, "consensus_merge", k_consensus_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -275,8 +280,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) \
     X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny) \
-    X(KDellaTable) X(KDellaRank) X(KDellaMerge)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE and DELLA
+    X(KDellaTable) X(KDellaRank) X(KDellaMerge) X(KConsensusMerge) X(KConsensusMergeAny)
+#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2612,6 +2617,68 @@ class Pipeline {
             be.template launch<KDellaMerge>(stream_grid(noct, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
         }
         return dare_readback("della_merge", k, rb, kept);
+    }
+
+    // ---- Consensus merge (sm_consensus.hpp; the function is stated in shardmerge_hip.h, smhip_consensus_merge).  ties == 0:
+    // no select, one kernel, the workspace is ConsensusWork alone.  ties == 1: the thresholds of TIES through the same
+    // hist / select launches (select_workspace with ConsensusWork as its tail), then the one kernel ----
+    struct ConsensusReadback {
+        float threshold[TIES_MAX_MODELS];
+        unsigned long long kept[TIES_MAX_MODELS], masked[TIES_MAX_MODELS], counts[CONSENSUS_COUNTS];
+        uint32_t flags[2];
+    };
+    struct ConsensusWork { RadixState state[TIES_MAX_MODELS]; ConsensusReadback rb; };
+    int consensus_merge(const smhip_consensus_desc& d, void* out, float* delta_out, smhip_consensus_report* rep) {
+        const int k = d.k;
+        const bool ties = d.ties != 0;
+        const unsigned long long k_keep = ties ? delta_k_keep(d.density, d.n) : 0ull;
+        if (rep) {
+            *rep = smhip_consensus_report{};
+            rep->k_keep = k_keep;
+        }
+        if (d.n == 0) {                                  // (ties, k_keep == 0: the threshold is +inf by definition)
+            if (rep && ties) for (int i = 0; i < k; ++i) rep->threshold[i] = INFINITY;
+            return SMHIP_OK;
+        }
+        ConsensusWork* w;
+        int rc;
+        if (ties) {
+            if ((rc = select_workspace(TIES_MAX_MODELS, w))) return rc;
+        } else {
+            if ((rc = ensure(ties_, sizeof(ConsensusWork)))) return rc;
+            be.memset(ties_.p, 0, sizeof(ConsensusWork), stream);
+            w = (ConsensusWork*)ties_.p;
+        }
+
+        ConsensusMergeParams m;
+        delta_merge_params(d, out, delta_out, m);
+        m.ties = ties ? 1 : 0; m.threshold = w->rb.threshold;
+        m.mask_lambda = (float)d.mask_lambda; m.need = (uint32_t)std::min(d.consensus_k, k);
+        m.masked = w->rb.masked; m.counts = w->rb.counts; m.flags = w->rb.flags;
+
+        if (ties) {
+            TiesHistParams h;
+            h.in = m.in; h.state = w->state; h.flags = w->rb.flags;
+            TiesSelectParams s;
+            s.k_keep = k_keep; s.state = w->state; s.threshold = w->rb.threshold; s.kept = w->rb.kept;
+            select_levels_per_finetune<KTiesHist, KTiesSelect>(h, s, {HIST1_BINS, HIST_LO_BINS, HIST_LO_BINS}, TIES_SELECT_LDS);
+        }
+        const int grid = stream_grid((d.n + 7) / 8, 256, m.chunks);
+        const size_t lds = (LDS_SCRATCH_FLOATS + consensus_lds_words(k, 256)) * 4;
+        if (k <= CONSENSUS_REG_SMALL) be.template launch<KConsensusMerge>(grid, 256, lds, m, stream);
+        else be.template launch<KConsensusMergeAny>(grid, 256, lds, m, stream);
+
+        ConsensusReadback host;
+        if ((rc = delta_readback("consensus_merge", k, &w->rb, host))) return rc;     // the call's one synchronisation
+        if (rep) {
+            for (int i = 0; i < k; ++i) {
+                if (ties) { rep->threshold[i] = host.threshold[i]; rep->kept[i] = host.kept[i]; }
+                rep->masked[i] = host.masked[i];
+            }
+            for (int c = 0; c <= TIES_MAX_MODELS; ++c) rep->agree[c] = host.counts[c];
+            rep->selected = host.counts[TIES_MAX_MODELS + 1];
+        }
+        return SMHIP_OK;
     }
 
     // ---- Breadcrumbs merge: two ranks per finetune (RadixState[k][2]), found in the same three histogram passes ----

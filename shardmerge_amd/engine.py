@@ -114,6 +114,18 @@ class SceMergeReport:
 
 
 @dataclass
+class ConsensusMergeReport:
+    ties: bool = False                                               # consensus_ties (else consensus_ta)
+    k_keep: int = 0                                                  # consensus_ties: as TiesMergeReport; 0 / empty otherwise
+    thresholds: List[float] = field(default_factory=list)
+    kept: List[int] = field(default_factory=list)
+    masked: List[int] = field(default_factory=list)                  # elements where finetune i's TALL mask is set
+    agree: List[int] = field(default_factory=list)                   # agree[c], c = 0..k: elements with exactly c masks set
+    selected: int = 0                                                # elements with at least min(consensus_k, k) masks set
+    n: int = 0                                                       # elements of the tensor (the sum of agree)
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -387,7 +399,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -648,6 +660,41 @@ class Engine:
         self._run_delta_merge(self.lib.dll.smhip_sce_merge, desc, rep, out, delta, layer_name)
         report = SceMergeReport(nz=int(rep.nz), k_keep=int(rep.k_keep), selected=int(rep.selected), threshold=float(rep.threshold),
                                 energies=[float(rep.energy[i]) for i in range(k)], weights=[float(rep.weight[i]) for i in range(k)])
+        return (out, report, delta) if want_delta else (out, report)
+
+    # -- Consensus (TALL masks) ---------------------------------------------------------------
+    def consensus_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                        base_out: torch.Tensor, *, ties: bool = False, density: float = 0.2, mask_lambda: float = 0.4,
+                        consensus_k: int = 2, lam: float = 1.0, normalize: bool = True, want_delta: bool = False,
+                        layer_name: Optional[str] = None):
+        """Consensus merge of one tensor of any shape (``smhip_consensus_merge``; the function is stated in
+        include/shardmerge_hip.h): the weighted entries ``tv_i = (finetune_i - base_i) * alpha_i`` are summed
+        (``ties=False``: consensus_ta) or merged as TIES merges them at ``density`` (``ties=True``: consensus_ties) into
+        the multi-task vector U; finetune i's TALL mask is set where ``|tv_i| >= mask_lambda * |U - tv_i|``; an element
+        of U is kept where at least ``min(consensus_k, k)`` masks are set and zeroed elsewhere; ``normalize``: divided
+        by the weights (consensus_ties: inside the TIES merge), times ``lam``, added onto ``base_out`` in its dtype.
+        Returns (out, ConsensusMergeReport[, the fp32 merged delta]).  A NaN or Inf in a delta raises ValueError naming
+        ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if ties and not (0.0 < float(density) <= 1.0):
+            raise ValueError(f"consensus_merge: density {density} is not in (0, 1]")
+        if not (0.0 <= float(mask_lambda) <= 1e6):
+            raise ValueError(f"consensus_merge: mask_lambda {mask_lambda} is not in [0, 1e6]")
+        if isinstance(consensus_k, bool) or not isinstance(consensus_k, int) or not (1 <= consensus_k <= _lib.MAX_MODELS):
+            raise ValueError(f"consensus_merge: consensus_k must be an integer in 1..{_lib.MAX_MODELS}, not {consensus_k!r}")
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"consensus_merge: lam {lam} is not finite")
+        desc, rep, k = _lib.ConsensusDesc(), _lib.ConsensusReport(), len(finetunes)
+        desc.density, desc.lam, desc.normalize = float(density), float(lam), 1 if normalize else 0
+        desc.mask_lambda, desc.consensus_k, desc.ties = float(mask_lambda), consensus_k, 1 if ties else 0
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "consensus_merge")
+        desc.n = bo.numel()
+        self._run_delta_merge(self.lib.dll.smhip_consensus_merge, desc, rep, out, delta, layer_name)
+        report = ConsensusMergeReport(ties=bool(ties), k_keep=int(rep.k_keep),
+                                      thresholds=[float(rep.threshold[i]) for i in range(k)] if ties else [],
+                                      kept=[int(rep.kept[i]) for i in range(k)] if ties else [],
+                                      masked=[int(rep.masked[i]) for i in range(k)],
+                                      agree=[int(rep.agree[c]) for c in range(k + 1)], selected=int(rep.selected), n=int(desc.n))
         return (out, report, delta) if want_delta else (out, report)
 
     def correlate_pairs(self, tensors) -> torch.Tensor:

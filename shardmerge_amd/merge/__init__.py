@@ -18,6 +18,8 @@ _OPERATOR_CLASSES = {
     "sce": ("sce", "SceMerge"),
     "della": ("della", "DellaMerge"),
     "della_linear": ("della", "DellaLinearMerge"),
+    "consensus_ta": ("consensus", "ConsensusTaMerge"),
+    "consensus_ties": ("consensus", "ConsensusTiesMerge"),
 }
 
 
