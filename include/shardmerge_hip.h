@@ -388,6 +388,93 @@ typedef struct {
 int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* desc, void* out, float* delta_out,
                     smhip_geo_report* report, void* stream);
 
+/* ---- Karcher-mean merges (operators karcher and multislerp): the DIRECTIONS of k vectors are averaged on the unit sphere
+ *      - the weighted Karcher (Frechet) mean, found by iterating the log map - and their LENGTHS linearly.  They
+ *      generalise NuSLERP (weight_space == 0), and its rule applied to the weights themselves (weight_space == 1), from
+ *      two vectors to 1 <= k <= 16; with k == 2 the first iteration lands on the SLERP direction, so the coefficients are
+ *      NUSLERP's c_i = s_i * N / n_i - and SLERP's c_i = s_i where the two norms are equal (SLERP leaves the length to its
+ *      two sines).  The reference has no such operators; this section IS their definition.  The mean of k unit vectors lies in their span, so every inner product the iteration takes is a
+ *      combination of Gram entries: the iteration runs on k coefficients and reads no tensor.
+ *        1. Vectors, 2. Gram, 4. Combine: steps 1, 2 and 4 of smhip_geo_merge with x_i in delta space (weight_space == 0)
+ *           or weight space (weight_space == 1; base_i and base_out are not read), the Gram over the whole tensor
+ *           (rowwise == 0) or over each of the R rows (rowwise == 1), the combination with the coefficients of step 3
+ *           (one set per row when rowwise == 1).
+ *        3. Coefficients.  Every operation below is ONE IEEE fp64 operation (no fused multiply-add); every sum runs in
+ *           ascending index order starting from +0; "v^T H v" is sum_i v_i * (sum_j H_ij * v_j).
+ *           Weights.  Every alpha must be >= 0 and A = ((0 + alpha_0) + alpha_1) + ... > 0, else SMHIP_ERR_ARG.
+ *             n_i = sqrt(G_ii), w_i = alpha_i / A.  Vector i is ACTIVE when n_i > 0 and w_i > 0; W = the sum of the active
+ *             w_i; w_i := w_i / W for an active vector and 0 for an inactive one.  N = sum_i w_i * n_i.
+ *           Normalised Gram.  H_ij = cos_ij of smhip_geo_merge (clamp(G_ij / (n_i * n_j), -1, 1), 0 when n_i * n_j is 0
+ *             or not finite) for i != j, H_ii = 1.  a is the coefficient vector of the current point m = sum a_i u_i,
+ *             u_i = x_i / n_i.
+ *           Start.  a = w.  With no active vector or one, c_i = fp32(a_i) (all 0, or a single 1): no iteration,
+ *             converged.  Else q = a^T H a; q <= 1e-16 (or not finite) is the LINEAR case: the unit vectors cancel,
+ *             c_i = fp32(w_i), no iteration.  Else a_i = a_i / sqrt(q).
+ *           Iterations it = 0 .. max_iter - 1 (`iterations` counts how often tau was evaluated):
+ *             d_j = clamp(sum_i a_i * H_ij, -1, 1); theta_j = sm_acos(d_j);
+ *             f_j = 1 when theta_j < 1e-8; else f_j = 0 when sm_sin(theta_j) < 1e-8 (antipodal: the log map is
+ *             undefined), else f_j = theta_j / sm_sin(theta_j);
+ *             p_j = w_j * f_j; g = sum_j p_j * d_j; t_i = p_i - a_i * g;
+ *             tau = sqrt(max(t^T H t, 0)), at most fp64(pi); tau < tol: converged, stop;
+ *             a_i = sm_cos(tau) * a_i + s * t_i with s = 1 when tau < 1e-8, else sm_sin(tau) / tau;
+ *             q = a^T H a, a_i = a_i / sqrt(q).
+ *             A t^T H t that is not finite, or a q that is <= 1e-16 or not finite, ends the iteration in the LINEAR
+ *             case: c_i = fp32(w_i).  Not converging within max_iter is no error: the report says so.  (Two antipodal
+ *             vectors reach H_ij = -1 only up to the rounding of the two square roots: with equal weights their q is 0
+ *             or a few 1e-16, on either side of the threshold.  Past it the iteration runs on a direction that is
+ *             rounding noise, as the mean of antipodal points is any point of their equator; the combination stays
+ *             bounded by N.)
+ *           Coefficients.  c_i = fp32((a_i * N) / n_i) for an active vector, 0 for an inactive one.
+ *           sm_acos on [-1, 1], sm_sin and sm_cos on [0, pi] are DEFINED in csrc/sm_sphere.hpp: Horner evaluations of
+ *           truncated Taylor series (asin to degree 47 on [-1/2, 1/2] behind the half-angle reduction; sin to degree 23
+ *           and cos to degree 24 on [0, pi/2] behind the reflection at pi/2) over the four operations + * / sqrt, the
+ *           coefficients written as hex floats, so that every implementation gives the same bits.  Their absolute error
+ *           is below 2^-40 (measured: below 2^-50).  Row-wise, step 3 runs per row on the device; rows stop
+ *           independently.
+ *      Arguments: 1 <= max_iter <= 100, 0 <= tol < 1.  Aliasing, alignment, n == 0, dtypes, SMHIP_ERR_NONFINITE and the
+ *      size limit: the rules of smhip_geo_merge (n > 0 needs rows >= 1 that divides n).  One synchronisation per call,
+ *      as there.  Profile names: "geo_gram", "geo_gram_fold" (whole tensor), "sphere_coef" (row-wise), "geo_combine",
+ *      each ONE launch per call. ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base (weight space: not read) */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;   /* (weight space: base_out is not read, base_out_dtype is out's dtype) */
+    size_t n;
+    int weight_space;                       /* 1: karcher (x_i = finetune_i), 0: multislerp (x_i = finetune_i - base_i) */
+    int rowwise;                            /* 1: a Gram, an iteration and coefficients per row */
+    size_t rows;                            /* R */
+    int max_iter;                           /* 1..100 */
+    double tol;                             /* [0, 1): the iteration stops when tau < tol */
+    float* row_coef;                        /* row-wise, optional, HOST: [R][k] coefficients */
+    int32_t* row_iters;                     /* row-wise, optional, HOST: [R] iterations */
+    int32_t* row_flags;                     /* row-wise, optional, HOST: [R], bit 0 converged, bit 1 linear */
+} smhip_sphere_desc;
+typedef struct {
+    double G[SMHIP_MAX_MODELS][SMHIP_MAX_MODELS];   /* whole tensor: the Gram, both triangles */
+    double H[SMHIP_MAX_MODELS][SMHIP_MAX_MODELS];   /* whole tensor: the normalised Gram */
+    double w[SMHIP_MAX_MODELS];             /* whole tensor: the renormalised weights */
+    double a[SMHIP_MAX_MODELS];             /* whole tensor: the final coefficient vector of the mean direction */
+    double N;                               /* whole tensor: the length, sum w_i n_i */
+    float c[SMHIP_MAX_MODELS];              /* whole tensor: the coefficients */
+    int iterations;                         /* whole tensor: how often tau was evaluated */
+    double tau;                             /* whole tensor: the last tau evaluated (0 when none was) */
+    int converged, linear;                  /* whole tensor: tau < tol was reached (or nothing to iterate) / the LINEAR case */
+    int iters_max;                          /* row-wise: the largest iteration count of a row */
+    uint64_t rows_unconverged, rows_linear; /* row-wise: rows that did not converge / that took the LINEAR case */
+    double csum_min, csum_max, csum_mean;   /* row-wise: over s_r = ((0 + c_r0) + c_r1) + ... in fp64; the mean is
+                                               (((0 + s_0) + s_1) + ...) / R */
+} smhip_sphere_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], M.  report (optional): HOST. */
+int smhip_sphere_merge(smhip_ctx* ctx, const smhip_sphere_desc* desc, void* out, float* delta_out,
+                       smhip_sphere_report* report, void* stream);
+/* The probe of the three defined functions: y[i] = sm_acos / sm_sin / sm_cos (x[i]), i < n.  on_device == 0: x and y
+ * are HOST arrays, evaluated on the host; 1: DEVICE arrays, evaluated by a kernel ("sphere_fn") on the stream. */
+enum { SMHIP_SPHERE_ACOS = 0, SMHIP_SPHERE_SIN = 1, SMHIP_SPHERE_COS = 2 };
+int smhip_sphere_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream);
+
 /* ---- SCE merge (Wan et al., "FuseChat: Knowledge Fusion of Chat Models", 2024; mergekit's merge_method sce with
  *      select_topk): SELECT the parameters whose deltas vary most across the finetunes, CALCULATE a weight per finetune
  *      from the energy of what it kept, ERASE the entries whose sign disagrees with the majority.  The reference has no

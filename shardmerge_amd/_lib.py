@@ -128,6 +128,26 @@ class GeoReport(C.Structure):
                 ("t_min", C.c_double), ("t_max", C.c_double), ("t_mean", C.c_double)]
 
 
+SPHERE_ACOS, SPHERE_SIN, SPHERE_COS = 0, 1, 2
+SPHERE_CONVERGED, SPHERE_LINEAR = 1, 2                # a row's flags
+
+
+class SphereDesc(C.Structure):
+    """smhip_sphere_desc"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("weight_space", C.c_int), ("rowwise", C.c_int), ("rows", C.c_size_t),
+                                         ("max_iter", C.c_int), ("tol", C.c_double),
+                                         ("row_coef", C.c_void_p), ("row_iters", C.c_void_p), ("row_flags", C.c_void_p)]
+
+
+class SphereReport(C.Structure):
+    """smhip_sphere_report"""
+    _fields_ = [("G", (C.c_double * MAX_MODELS) * MAX_MODELS), ("H", (C.c_double * MAX_MODELS) * MAX_MODELS),
+                ("w", C.c_double * MAX_MODELS), ("a", C.c_double * MAX_MODELS), ("N", C.c_double), ("c", C.c_float * MAX_MODELS),
+                ("iterations", C.c_int), ("tau", C.c_double), ("converged", C.c_int), ("linear", C.c_int),
+                ("iters_max", C.c_int), ("rows_unconverged", C.c_uint64), ("rows_linear", C.c_uint64),
+                ("csum_min", C.c_double), ("csum_max", C.c_double), ("csum_mean", C.c_double)]
+
+
 class SceDesc(C.Structure):
     """smhip_sce_desc"""
     _fields_ = _DELTA_DESC_FIELDS[:8] + [("select_topk", C.c_double), ("lam", C.c_double)]
@@ -215,6 +235,8 @@ class SmhipLibrary:
         d.smhip_dare_merge.argtypes = [P, C.POINTER(DareDesc), P, P, C.POINTER(DareReport), P]
         d.smhip_breadcrumbs_merge.argtypes = [P, C.POINTER(BreadcrumbsDesc), P, P, C.POINTER(BreadcrumbsReport), P]
         d.smhip_geo_merge.argtypes = [P, C.POINTER(GeoDesc), P, P, C.POINTER(GeoReport), P]
+        d.smhip_sphere_merge.argtypes = [P, C.POINTER(SphereDesc), P, P, C.POINTER(SphereReport), P]
+        d.smhip_sphere_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
         d.smhip_sce_merge.argtypes = [P, C.POINTER(SceDesc), P, P, C.POINTER(SceReport), P]
         d.smhip_della_merge.argtypes = [P, C.POINTER(DellaDesc), P, P, P, C.POINTER(DellaReport), P]
         d.smhip_consensus_merge.argtypes = [P, C.POINTER(ConsensusDesc), P, P, C.POINTER(ConsensusReport), P]

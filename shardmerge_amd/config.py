@@ -89,6 +89,15 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # consensus_lambda: 1.0   #   scales the merged delta
       # consensus_normalize: 1  #   1: divide by the sum of the weights (consensus_ties: of the agreeing entries), 0: plain sum
       # density: 0.2            #   operator consensus_ties only: the trim of ties, 0 < density <= 1
+                                # | karcher | multislerp (Karcher means; no counterpart in the reference): slerp / nuslerp for
+                                #   any number of finetune_merge entries (1..16).  The DIRECTIONS of the vectors - karcher: the
+                                #   models' weights, as slerp; multislerp: the deltas, as nuslerp - are averaged on the sphere
+                                #   with the weights alpha_i / sum alpha (the log map iterated to its fixed point, on the fp64
+                                #   Gram matrix), their LENGTHS linearly.  alphas >= 0 with a sum > 0.  The spectral keys,
+                                #   norm_mode, task_add_models and every other family's keys are rejected; keys:
+      # karcher_max_iter: 10    #   an integer in 1..100: iterations at most (two entries need one)
+      # karcher_tol: 1.0e-5     #   0 <= karcher_tol < 1: the iteration stops when its step on the sphere is shorter
+      # sphere_row_wise: 0      #   1: one mean per ROW of each tensor (multislerp with two entries: row-wise nuslerp), 0: per tensor
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -115,7 +124,8 @@ MERGE_OPTION_DEFAULTS = {"cutoff_pct": 0.08, "cull_start_pct": 0.20, "t_sum": 1.
 MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "t_sum": (-1e6, 1e6), "target_norm_offset": (0.0, 1e6),
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
-             "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties")
+             "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
+             "karcher", "multislerp")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -133,6 +143,8 @@ DELLA_OPERATORS = ("della", "della_linear")
 DELLA_OPTION_DEFAULTS = {"density": 0.5, "epsilon": 0.15, "della_lambda": 1.0, "della_normalize": 1.0, "della_rescale": 1.0, "seed": 0}
 CONSENSUS_OPERATORS = ("consensus_ta", "consensus_ties")
 CONSENSUS_OPTION_DEFAULTS = {"density": 0.2, "mask_lambda": 0.4, "consensus_k": 2, "consensus_lambda": 1.0, "consensus_normalize": 1.0}
+SPHERE_OPERATORS = ("karcher", "multislerp")             # Karcher means: slerp / nuslerp for any number of entries
+SPHERE_OPTION_DEFAULTS = {"karcher_max_iter": 10, "karcher_tol": 1e-5, "sphere_row_wise": 0.0}
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -219,6 +231,14 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "sce": "(it selects by the agreement of the masks, not by variance)",
                            "della": "(it drops nothing at random)"},
                   only={"density": ("consensus_ties",)}),
+    _OptionFamily(SPHERE_OPERATORS, SPHERE_OPTION_DEFAULTS,
+                  {"karcher_max_iter": ("int", 1, 100), "karcher_tol": (0, 1, "[)"), "sphere_row_wise": "flag"},
+                  earlier={"ties": "(it trims nothing and averages directions on the sphere)", "dare_ties": "(it drops nothing)",
+                           "breadcrumbs": "(it trims nothing)",
+                           "model_stock": "(its granularity key is sphere_row_wise)",
+                           "sce": "(its weights are the alphas, not energies)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it masks nothing)"}),
 )
 
 
@@ -396,6 +416,12 @@ class MergeConfig:
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
                 raise click.BadParameter(f"operator {operator} needs finetune_merge alphas >= 0 with a sum > 0 (the interpolation "
                                          f"point is alpha_1 / (alpha_0 + alpha_1)), not {alphas}")
+        if operator in SPHERE_OPERATORS:
+            alphas = [m.alpha for m in raw["finetune_merge"]]
+            if not alphas or any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) \
+                    or not (0 < sum(alphas) < float("inf")):
+                raise click.BadParameter(f"operator {operator} needs finetune_merge alphas >= 0 with a sum > 0 (the weight of a "
+                                         f"direction on the sphere is alpha_i / sum alpha), not {alphas}")
         if operator == "sce":
             alphas = [m.alpha for m in raw["finetune_merge"]]
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):

@@ -236,6 +236,37 @@ int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* d, void* out, float* d
     SM_FINISH(ctx, ctx->pipe.geo_merge(*d, out, delta_out, report));
 }
 
+int smhip_sphere_merge(smhip_ctx* ctx, const smhip_sphere_desc* d, void* out, float* delta_out, smhip_sphere_report* report,
+                       void* stream) {
+    SM_GUARD(ctx);
+    const bool weight = d && d->weight_space;
+    if (int rc = delta_tensor_check(ctx, "sphere_merge", d, out, delta_out, !weight, [&]() -> const char* {
+            double sum = 0.0;
+            for (int i = 0; i < d->k; ++i) {
+                if (!(d->alpha[i] >= 0.0) || !std::isfinite(d->alpha[i])) return "needs alphas >= 0 with a sum > 0";
+                sum += d->alpha[i];
+            }
+            if (!(sum > 0.0) || !std::isfinite(sum)) return "needs alphas >= 0 with a sum > 0";
+            if (d->max_iter < 1 || d->max_iter > 100) return "max_iter must be in 1..100";
+            if (!(d->tol >= 0.0 && d->tol < 1.0)) return "tol must be in [0, 1)";
+            return nullptr;
+        }))
+        return rc;
+    if (d->n > 0 && (d->rows < 1 || d->n % d->rows)) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_merge: rows must divide n");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.sphere_merge(*d, out, delta_out, report));
+}
+
+int smhip_sphere_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream) {
+    SM_GUARD(ctx);
+    if (op < SMHIP_SPHERE_ACOS || op > SMHIP_SPHERE_COS) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_fn: bad op");
+    if (n > 0 && (!x || !y)) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_fn: null array");
+    if ((uintptr_t)x % 8 || (uintptr_t)y % 8) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_fn: a pointer is not aligned to 8 bytes");
+    if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_fn: array too large");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.sphere_fn_array(op, x, y, n, on_device != 0));
+}
+
 int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* d, void* out, float* delta_out, smhip_sce_report* report,
                     void* stream) {
     SM_GUARD(ctx);

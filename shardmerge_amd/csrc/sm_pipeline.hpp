@@ -20,6 +20,7 @@
 #include "sm_dare.hpp"
 #include "sm_breadcrumbs.hpp"
 #include "sm_geo.hpp"
+#include "sm_sphere.hpp"
 #include "sm_sce.hpp"
 #include "sm_della.hpp"
 #include "sm_consensus.hpp"
@@ -233,6 +234,11 @@ SM_KERNEL_TAG_LB(KGeoGramTiled, GeoGramParams, "geo_gram", k_geo_gram<true>(ex, 
 SM_KERNEL_TAG_LB(KGeoFold, GeoFoldParams, "geo_gram_fold", k_geo_fold(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KGeoCoef, GeoCoefParams, "geo_coef", k_geo_coef(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KGeoCombine, GeoCombineParams, "geo_combine", k_geo_combine(ex, p), 256, 4)
+// Karcher-mean merges (sm_sphere.hpp): the row-wise coefficient iteration, k <= 4 in registers or up to 16 in LDS, and the
+// probe of the three defined functions
+SM_KERNEL_TAG_LB(KSphereCoef, SphereCoefParams, "sphere_coef", k_sphere_coef<false>(ex, p), SPH_REG_THREADS, 2)
+SM_KERNEL_TAG_LB(KSphereCoefLds, SphereCoefParams, "sphere_coef", k_sphere_coef<true>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KSphereFn, SphereFnParams, "sphere_fn", k_sphere_fn(ex, p), 256, 4)
 // SCE merge (sm_sce.hpp): the one-stream radix level over the variance scores, its scan, the masked ordered fp64 energies
 // and their fold, the fused merge pass; k <= 4 deltas per octet in registers, or up to 16
 SM_KERNEL_TAG_LB(KSceHist, SceHistParams, "sce_hist", k_sce_hist<SCE_REG_SMALL>(ex, p), 256, 4)
@@ -278,7 +284,7 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
-    X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) \
+    X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
     X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny) \
     X(KDellaTable) X(KDellaRank) X(KDellaMerge) X(KConsensusMerge) X(KConsensusMergeAny)
 #define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus
@@ -2839,6 +2845,124 @@ class Pipeline {
             for (int i = 0; i < k; ++i) rep->c[i] = m.c[i];
         }
         be.template launch<KGeoCombine>(cgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+        return SMHIP_OK;
+    }
+
+    // ---- Karcher-mean merges (sm_sphere.hpp; the function is stated in shardmerge_hip.h, smhip_sphere_merge): the Gram pass of
+    // geo_merge, then whole tensor: fold, ONE readback, sphere_coefficients on the host, the combine pass; row-wise:
+    // sphere_coef on the device, the combine pass through its row-coefficient path, one readback at the end.
+    // Workspace (the TIES buffer): GeoHead | partials or row Grams | row coefficients | row iterations | row flags ----
+    int sphere_merge(const smhip_sphere_desc& d, void* out, float* delta_out, smhip_sphere_report* rep) {
+        const int k = d.k, np = geo_pairs(k);
+        const bool weight = d.weight_space != 0, rowwise = d.rowwise != 0;
+        if (rep) *rep = smhip_sphere_report{};
+        double A = 0.0;
+        for (int i = 0; i < k; ++i) A = geo_dadd(A, d.alpha[i]);
+        if (d.n == 0) return SMHIP_OK;
+
+        GeoCombineParams m;
+        delta_inputs(d, out, delta_out, weight, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.c[i] = 0.f;
+        m.weight_space = weight ? 1 : 0;
+        m.rowcoef = nullptr; m.C = d.n / d.rows;
+        GeoGramParams g;
+        g.in = m.in; g.weight_space = m.weight_space;
+        g.seg_len = rowwise ? m.C : GEO_SEG_ELEMS;
+        g.nseg = (d.n + g.seg_len - 1) / g.seg_len;
+        g.seg_vec = (m.in.aligned && g.seg_len % 8 == 0) ? 1 : 0;
+        const size_t ggrid = g.nseg * (size_t)geo_tiles(k);
+        if (ggrid > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "sphere_merge: tensor too large");
+
+        const size_t off_part = round_up(sizeof(GeoHead), 256), part_bytes = round_up(g.nseg * np * sizeof(double), 256);
+        const size_t off_coef = off_part + part_bytes, coef_bytes = rowwise ? round_up(g.nseg * k * sizeof(float), 256) : 0;
+        const size_t off_iters = off_coef + coef_bytes, int_bytes = rowwise ? round_up(g.nseg * sizeof(int), 256) : 0;
+        const size_t off_flags = off_iters + int_bytes;
+        int rc;
+        if ((rc = ensure(ties_, off_flags + int_bytes))) return rc;
+        GeoHead* head = (GeoHead*)ties_.p;
+        be.memset(head, 0, sizeof(GeoHead), stream);
+        g.part = (double*)((char*)ties_.p + off_part);
+        g.flags = head->flags;
+        if (k <= GEO_TILE) be.template launch<KGeoGram>((int)ggrid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+        else be.template launch<KGeoGramTiled>((int)ggrid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+        auto nonfinite = [&](uint32_t flags) {
+            return delta_nonfinite("sphere_merge: NaN or Inf in the vector (finetune - base, or the finetune) of finetune ", k, flags);
+        };
+
+        const int cgrid = stream_grid((d.n + 7) / 8, 256, m.chunks);
+        if (rowwise) {
+            const size_t R = g.nseg;
+            SphereCoefParams c;
+            c.k = k; c.max_iter = d.max_iter; c.rows = R; c.tol = d.tol; c.A = A; c.G = g.part;
+            for (int i = 0; i < TIES_MAX_MODELS; ++i) c.alpha[i] = d.alpha[i < k ? i : 0];
+            c.coef = (float*)((char*)ties_.p + off_coef);
+            c.iters = (int*)((char*)ties_.p + off_iters); c.flags = (int*)((char*)ties_.p + off_flags);
+            const int nt = sphere_coef_threads(k);
+            if (k <= SPH_REG_SMALL) be.template launch<KSphereCoef>((int)((R + nt - 1) / nt), nt, sphere_coef_lds_floats(k) * 4, c, stream);
+            else be.template launch<KSphereCoefLds>((int)((R + nt - 1) / nt), nt, sphere_coef_lds_floats(k) * 4, c, stream);
+            m.rowcoef = c.coef;
+            be.template launch<KGeoCombine>(cgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+            GeoHead host;
+            std::vector<float> coef(R * k);
+            std::vector<int> iters(R), flags(R);
+            be.d2h(coef.data(), c.coef, R * k * sizeof(float), stream);     // (the call's one synchronisation; the rest follows on the drained stream)
+            be.d2h(iters.data(), c.iters, R * sizeof(int), stream);
+            be.d2h(flags.data(), c.flags, R * sizeof(int), stream);
+            be.d2h(&host, head, sizeof host, stream);
+            if (!be.ok()) return SMHIP_OK;
+            if (host.flags[0]) return nonfinite(host.flags[0]);
+            if (d.row_coef) std::copy(coef.begin(), coef.end(), d.row_coef);
+            if (d.row_iters) std::copy(iters.begin(), iters.end(), d.row_iters);
+            if (d.row_flags) std::copy(flags.begin(), flags.end(), d.row_flags);
+            if (rep) {
+                double sum = 0.0, lo = 0.0, hi = 0.0;
+                for (size_t r = 0; r < R; ++r) {
+                    double sr = 0.0;
+                    for (int i = 0; i < k; ++i) sr = geo_dadd(sr, (double)coef[r * k + i]);
+                    sum = geo_dadd(sum, sr);
+                    lo = r ? std::min(lo, sr) : sr; hi = r ? std::max(hi, sr) : sr;
+                    rep->iters_max = std::max(rep->iters_max, iters[r]);
+                    rep->rows_unconverged += (flags[r] & SPH_CONVERGED) ? 0 : 1;
+                    rep->rows_linear += (flags[r] & SPH_LINEAR) ? 1 : 0;
+                }
+                rep->csum_min = lo; rep->csum_max = hi; rep->csum_mean = geo_ddiv(sum, (double)R);
+            }
+            return SMHIP_OK;
+        }
+
+        GeoFoldParams f;
+        f.np = np; f.nseg = g.nseg; f.part = g.part; f.G = head->G;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        GeoHead host;
+        be.d2h(&host, head, sizeof host, stream);            // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0]) return nonfinite(host.flags[0]);
+        SphereRegs<TIES_MAX_MODELS> s;
+        SphereOut o;
+        sphere_coefficients<TIES_MAX_MODELS, false>(s, host.G, d.alpha, A, k, d.max_iter, d.tol, m.c, o);
+        if (rep) {
+            for (int i = 0; i < k; ++i) {
+                for (int j = i; j < k; ++j) {
+                    rep->G[i][j] = rep->G[j][i] = host.G[geo_pair_index(i, j, k)];
+                    rep->H[i][j] = rep->H[j][i] = s.H(i, j);
+                }
+                rep->w[i] = s.w(i); rep->a[i] = s.a(i); rep->c[i] = m.c[i];
+            }
+            rep->N = o.N; rep->iterations = o.iterations; rep->tau = o.tau;
+            rep->converged = (o.flags & SPH_CONVERGED) ? 1 : 0; rep->linear = (o.flags & SPH_LINEAR) ? 1 : 0;
+        }
+        be.template launch<KGeoCombine>(cgrid, 256, LDS_SCRATCH_FLOATS * 4, m, stream);
+        return SMHIP_OK;
+    }
+    // the probe of sm_acos / sm_sin / sm_cos: on the host, or one thread per argument on the device
+    int sphere_fn_array(int op, const double* x, double* y, size_t n, bool on_device) {
+        if (!on_device) {
+            for (size_t i = 0; i < n; ++i) y[i] = sphere_fn(op, x[i]);
+            return SMHIP_OK;
+        }
+        SphereFnParams p;
+        p.op = op; p.n = n; p.x = x; p.y = y;
+        if (n) be.template launch<KSphereFn>((int)((n + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         return SMHIP_OK;
     }
 

@@ -104,6 +104,33 @@ class GeoMergeReport:
 
 
 @dataclass
+class SphereMergeReport:
+    mode: str = "karcher"
+    rowwise: bool = False
+    max_iter: int = 10
+    tol: float = 1e-5
+    gram: List[List[float]] = field(default_factory=list)            # whole tensor: G[i][j], the fp64 Gram of the k vectors
+    cosines: List[List[float]] = field(default_factory=list)         # whole tensor: H[i][j], the normalised Gram
+    weights: List[float] = field(default_factory=list)               # whole tensor: w_i, renormalised over the active vectors
+    a: List[float] = field(default_factory=list)                     # whole tensor: the mean direction's coefficients
+    length: float = 0.0                                              # whole tensor: N = sum w_i n_i
+    coefficients: List[float] = field(default_factory=list)          # whole tensor: c_i (fp32)
+    iterations: int = 0                                              # whole tensor: how often tau was evaluated
+    tau: float = 0.0                                                 # whole tensor: the last tau
+    converged: bool = False
+    linear: bool = False                                             # the unit vectors cancel: c_i = w_i
+    iters_max: int = 0                                               # row-wise: over the rows
+    rows_unconverged: int = 0
+    rows_linear: int = 0
+    csum_min: float = 0.0                                            # row-wise: over the rows' sum of coefficients
+    csum_max: float = 0.0
+    csum_mean: float = 0.0
+    row_coefficients: Optional[torch.Tensor] = None                  # row-wise: fp32 [R, k] (CPU)
+    row_iterations: Optional[torch.Tensor] = None                    # row-wise: int32 [R]
+    row_flags: Optional[torch.Tensor] = None                         # row-wise: int32 [R], bit 0 converged, bit 1 linear
+
+
+@dataclass
 class SceMergeReport:
     nz: int = 0                                                      # elements whose variance score q is > 0
     k_keep: int = 0                                                  # floor(select_topk * nz): elements asked for
@@ -628,6 +655,74 @@ class Engine:
             report.gram = [[float(rep.G[i][j]) for j in range(k)] for i in range(k)]
             report.coefficients = [float(rep.c[i]) for i in range(k)]
         return (out, report, delta) if want_delta else (out, report)
+
+    # -- Karcher means: karcher, multislerp -----------------------------------------------
+    SPHERE_MODES = {"karcher": 1, "multislerp": 0}                # mode -> weight_space
+    SPHERE_FNS = {"acos": _lib.SPHERE_ACOS, "sin": _lib.SPHERE_SIN, "cos": _lib.SPHERE_COS}
+
+    def sphere_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                     base_out: torch.Tensor, *, mode: str = "karcher", rowwise: bool = False, max_iter: int = 10, tol: float = 1e-5,
+                     want_delta: bool = False, layer_name: Optional[str] = None):
+        """Karcher-mean merge of one tensor of any shape (``smhip_sphere_merge``; the function is stated in
+        include/shardmerge_hip.h).  The directions of the k vectors (``karcher``: the finetunes themselves;
+        ``multislerp``: the deltas ``finetune_i - base_i``) are averaged on the sphere with the weights
+        ``alpha_i / sum alpha`` - the log map iterated at most ``max_iter`` times, until the step is below ``tol``, on k
+        coefficients against the fp64 Gram matrix - and their lengths linearly; ``rowwise``: one mean per row of the
+        first dimension.  One pass writes ``sum c_i x_i`` (``multislerp``: ``base_out + sum c_i x_i``) in base_out's
+        dtype.  Returns (out, SphereMergeReport[, the fp32 combination M]).  A NaN or Inf in a vector raises ValueError
+        naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if mode not in self.SPHERE_MODES:
+            raise ValueError(f"sphere_merge: mode {mode!r} is not one of {sorted(self.SPHERE_MODES)}")
+        k = len(finetunes)
+        if len(alphas) == k and not (all(float(a) >= 0 for a in alphas) and 0 < sum(float(a) for a in alphas) < float("inf")):
+            raise ValueError(f"sphere_merge: mode {mode} needs alphas >= 0 with a sum > 0, not {list(alphas)}")
+        if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not (1 <= max_iter <= 100):
+            raise ValueError(f"sphere_merge: max_iter {max_iter!r} is not an integer in 1..100")
+        if not (0.0 <= float(tol) < 1.0):
+            raise ValueError(f"sphere_merge: tol {tol} is not in [0, 1)")
+        desc, rep = _lib.SphereDesc(), _lib.SphereReport()
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "sphere_merge")
+        desc.n = bo.numel()
+        desc.weight_space, desc.rowwise = self.SPHERE_MODES[mode], 1 if rowwise else 0
+        desc.rows = (bo.shape[0] if bo.ndim > 1 else 1) or 1
+        desc.max_iter, desc.tol = int(max_iter), float(tol)
+        report = SphereMergeReport(mode=mode, rowwise=bool(rowwise), max_iter=int(max_iter), tol=float(tol))
+        if rowwise and desc.n:
+            R = int(desc.rows)
+            report.row_coefficients = torch.zeros(R, k, dtype=torch.float32)
+            report.row_iterations = torch.zeros(R, dtype=torch.int32)
+            report.row_flags = torch.zeros(R, dtype=torch.int32)
+            desc.row_coef, desc.row_iters, desc.row_flags = (report.row_coefficients.data_ptr(), report.row_iterations.data_ptr(),
+                                                             report.row_flags.data_ptr())
+        self._run_delta_merge(self.lib.dll.smhip_sphere_merge, desc, rep, out, delta, layer_name)
+        if rowwise:
+            report.iters_max, report.rows_unconverged, report.rows_linear = int(rep.iters_max), int(rep.rows_unconverged), int(rep.rows_linear)
+            report.csum_min, report.csum_max, report.csum_mean = float(rep.csum_min), float(rep.csum_max), float(rep.csum_mean)
+        else:
+            report.gram = [[float(rep.G[i][j]) for j in range(k)] for i in range(k)]
+            report.cosines = [[float(rep.H[i][j]) for j in range(k)] for i in range(k)]
+            report.weights = [float(rep.w[i]) for i in range(k)]
+            report.a = [float(rep.a[i]) for i in range(k)]
+            report.length = float(rep.N)
+            report.coefficients = [float(rep.c[i]) for i in range(k)]
+            report.iterations, report.tau = int(rep.iterations), float(rep.tau)
+            report.converged, report.linear = bool(rep.converged), bool(rep.linear)
+        return (out, report, delta) if want_delta else (out, report)
+
+    def sphere_fn(self, op: str, x: torch.Tensor, on_device: bool = True) -> torch.Tensor:
+        """``sm_acos`` / ``sm_sin`` / ``sm_cos`` of csrc/sm_sphere.hpp over an fp64 array (``smhip_sphere_fn``): by a
+        kernel on the engine's device, or on the host.  Returns an fp64 CPU tensor."""
+        if op not in self.SPHERE_FNS:
+            raise ValueError(f"sphere_fn: op {op!r} is not one of {sorted(self.SPHERE_FNS)}")
+        x = x.detach().to(torch.float64).contiguous().reshape(-1)
+        x = x.to(self.device) if on_device else x.cpu()
+        y = torch.empty_like(x)
+        self.ctx.check(self.lib.dll.smhip_sphere_fn(self.ctx.h, self.SPHERE_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
+                                                    1 if on_device else 0, self._stream() if on_device else None))
+        if on_device and self.device.type != "cpu":
+            torch.cuda.synchronize(self.device)
+        return y.cpu()
 
     # -- SCE ------------------------------------------------------------------------------
     def sce_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],

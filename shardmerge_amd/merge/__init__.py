@@ -20,6 +20,8 @@ _OPERATOR_CLASSES = {
     "della_linear": ("della", "DellaLinearMerge"),
     "consensus_ta": ("consensus", "ConsensusTaMerge"),
     "consensus_ties": ("consensus", "ConsensusTiesMerge"),
+    "karcher": ("spherical", "KarcherMerge"),
+    "multislerp": ("spherical", "MultiSlerpMerge"),
 }
 
 
