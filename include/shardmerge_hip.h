@@ -658,6 +658,66 @@ typedef struct {
 int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* desc, void* out, float* delta_out,
                           smhip_consensus_report* report, void* stream);
 
+/* ---- Task-vector statistics: what the knobs of the delta merges (density above all) would do to THESE finetunes,
+ *      before a merge has run.  No output tensor: for one tensor of n elements (any shape, flat), finetunes i = 0..k-1
+ *      (1 <= k <= 16) and candidate densities rho_q, q = 0..m-1 (1 <= m <= SMHIP_STATS_MAX_DENSITIES, each in (0, 1],
+ *      any order, duplicates allowed), the report holds:
+ *        1. d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with SMHIP_ERR_NONFINITE
+ *           (the message lists the finetunes, as smhip_ties_merge does).  nonzero[i] = #{d_i != 0}.
+ *        2. G[i][j] (symmetric): step 2 of smhip_geo_merge in delta space over the whole tensor - segments of 32768
+ *           elements, octet o to lane o % 256, the binary tree over the lanes, the segments added in index order.
+ *        3. k_keep[q] = n if rho_q == 1, else (uint64) floor(rho_q * n) in fp64.  tau[q][i] = the k_keep[q]-th largest
+ *           |d_i|, exact; +inf when k_keep[q] == 0.  Entry (q, i) of an element is KEPT iff |d_i| >= tau[q][i] and
+ *           d_i != 0: step 2 of smhip_ties_merge with its tie rule.  kept[q][i] counts the kept entries.
+ *        4. energy[q][i] = sum over the elements of (double) x * (double) x, x = d_i where kept and +0 elsewhere, summed
+ *           in the order of 2 (how smhip_sce_merge step 3 sums, with this step's mask).
+ *        5. For every q, each operation one rounded fp32 operation: tv_i = fl32(d_i * fp32(alpha_i)) where kept, +0
+ *           elsewhere; S = ((0 + tv_0) + tv_1) + ...; the elected sign is + when S >= 0; m_i = [sign(tv_i) == elected
+ *           sign], a zero agrees with nothing (steps 3-5 of smhip_ties_merge; Yadav et al. 2023).  Then, all uint64:
+ *             opposed[q][i]  #{kept and m_i == 0}: what TIES at this density discards of finetune i
+ *             alone[q][i]    #{kept by i and by no other finetune}
+ *             cover[q][c]    c = 0..k: elements that exactly c finetunes keep
+ *             conflict[q]    elements with a kept tv > 0 and a kept tv < 0
+ *      Every value is an integer, an exact order statistic or an fp64 sum in a stated order: the report is defined bit
+ *      for bit, the same on any grid.  Identities: tau[q][i] and kept[q][i] equal smhip_ties_merge's report at density
+ *      rho_q; energy[q][i] at rho_q == 1 equals G[i][i] bit for bit (a zero adds +0); G equals the Gram that
+ *      smhip_geo_merge (MODEL_STOCK) reports on the same inputs; sum_c cover[q][c] == n;
+ *      sum_c c * cover[q][c] == sum_i kept[q][i]; sum_i alone[q][i] == cover[q][1].
+ *      Passes: the radix select finds all m thresholds of a finetune in the same three levels (a 2048-bin histogram per
+ *      finetune at level 1, a 1024-bin histogram per distinct prefix at levels 2 and 3), then the Gram pass, then ONE
+ *      fused pass for everything else: with a shared base and k <= 4 the call reads 5 (k + 1) tensors, whatever m
+ *      (k > 4: the Gram pass re-reads per tile of pairs, as in smhip_geo_merge).  Counters are integers (LDS, then one
+ *      global atomic per counter and work-group), no floating-point atomics; the stream is synchronised once, at the
+ *      end.  Aliasing, alignment, dtypes and the size limit: the rules of smhip_ties_merge's inputs.  n == 0: the report
+ *      is all zeros and tau is +inf.  SMHIP_ERR_ARG: k outside 1..16, m outside 1..4, a density outside (0, 1], an alpha
+ *      not finite, a bad dtype, a null descriptor, report or tensor.
+ *      Profile names: "stats_hist", "stats_select", "geo_gram", "geo_gram_fold", "stats_pass", "stats_fold". ---- */
+#define SMHIP_STATS_MAX_DENSITIES 4
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];         /* the election's weights (step 5 only) */
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    size_t n;
+    int m;                                  /* densities, 1..SMHIP_STATS_MAX_DENSITIES */
+    double density[SMHIP_STATS_MAX_DENSITIES];
+} smhip_stats_desc;
+typedef struct {
+    uint64_t nonzero[SMHIP_MAX_MODELS];
+    double G[SMHIP_MAX_MODELS][SMHIP_MAX_MODELS];
+    uint64_t k_keep[SMHIP_STATS_MAX_DENSITIES];
+    float tau[SMHIP_STATS_MAX_DENSITIES][SMHIP_MAX_MODELS];
+    uint64_t kept[SMHIP_STATS_MAX_DENSITIES][SMHIP_MAX_MODELS];
+    double energy[SMHIP_STATS_MAX_DENSITIES][SMHIP_MAX_MODELS];
+    uint64_t opposed[SMHIP_STATS_MAX_DENSITIES][SMHIP_MAX_MODELS];
+    uint64_t alone[SMHIP_STATS_MAX_DENSITIES][SMHIP_MAX_MODELS];
+    uint64_t cover[SMHIP_STATS_MAX_DENSITIES][SMHIP_MAX_MODELS + 1];
+    uint64_t conflict[SMHIP_STATS_MAX_DENSITIES];
+} smhip_stats_report;
+/* report: HOST, required. */
+int smhip_delta_stats(smhip_ctx* ctx, const smhip_stats_desc* desc, smhip_stats_report* report, void* stream);
+
 /* ---- slerp (reference shard/tensor/functions.py:24-43) on fp32 device tensors of rows x cols elements (1-D:
  *      rows = 1): the cosine is taken between the UN-normalised vectors over the whole tensor, the relative vector
  *      v1 - v0 dot is normalised along the LAST dimension (F.normalize(dim=-1), eps 1e-12), out = v0 cos + rel sin.

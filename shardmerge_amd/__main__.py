@@ -1,6 +1,8 @@
 """`python -m shardmerge_amd merge CONFIG` (and `python -m shard merge CONFIG`
 through the alias package): the merge entry point of the reference CLI
-(shard/__main__.py:78-158) with the same arguments and options."""
+(shard/__main__.py:78-158) with the same arguments and options; and `analyze CONFIG`,
+the per-tensor task-vector statistics of the same config (merge/analyze.py), which
+writes no tensor."""
 from __future__ import annotations
 
 import asyncio
@@ -72,6 +74,50 @@ def merge_command(config_file: Path, cache_dir: Optional[Path], verbose: bool, *
         logging.error(f"Error during merge: {exc}", exc_info=verbose)
         traceback.print_exc()
         raise click.Abort()
+
+
+def _densities_option(ctx, param, value):
+    from .merge.analyze import parse_densities
+    try:
+        return parse_densities(value)
+    except ValueError as exc:
+        raise click.BadParameter(str(exc))
+
+
+@cli.command("analyze")
+@click.argument("config_file", type=click.Path(exists=True, path_type=Path))
+@click.option("--densities", default="0.05,0.1,0.2,0.5", callback=_densities_option,
+              help="Up to four candidate densities in (0, 1], comma-separated")
+@click.option("--report", type=click.Path(path_type=Path), default=None, help="Where the JSON goes (default: <output_dir>/analysis.json)")
+@click.option("--device", type=str, default=None, help="Device to perform tensor operations on (cuda/cpu)")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def analyze_command(config_file: Path, densities, report: Optional[Path], device: Optional[str], verbose: bool):
+    """Task-vector statistics of every block tensor a merge of CONFIG_FILE would touch, no tensor written.
+
+    Per finetune: norm, cosines, and at each candidate density what a trim keeps (elements, energy), how the kept sets
+    overlap and what the TIES sign election would discard.  The full per-tensor report goes to a JSON file.
+    """
+    setup_logging(verbose)
+    from . import distributed
+    if distributed.world_size() > 1:
+        raise click.ClickException("analyze runs in a single process: a partitioned analysis is not supported (run it without torchrun)")
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        config = MergeConfig.from_yaml(config_file)
+        if device is not None:
+            config.device = device
+        from .merge.analyze import format_tables, run_analysis
+        path = report if report is not None else config.output_path / "analysis.json"
+        result = asyncio.run(run_analysis(config, config.device, densities, path))
+    except click.ClickException:
+        raise
+    except Exception as exc:
+        logging.error(f"Error during analyze: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_tables(result))
+    click.echo(f"report: {path}")
 
 
 if __name__ == "__main__":

@@ -180,6 +180,29 @@ class ConsensusReport(C.Structure):
                 ("masked", C.c_uint64 * MAX_MODELS), ("agree", C.c_uint64 * (MAX_MODELS + 1)), ("selected", C.c_uint64)]
 
 
+STATS_MAX_DENSITIES = 4         # SMHIP_STATS_MAX_DENSITIES
+
+
+class StatsDesc(C.Structure):
+    """smhip_stats_desc"""
+    _fields_ = [("k", C.c_int), ("finetune", C.c_void_p * MAX_MODELS), ("base", C.c_void_p * MAX_MODELS),
+                ("alpha", C.c_double * MAX_MODELS), ("in_dtype", C.c_int), ("n", C.c_size_t),
+                ("m", C.c_int), ("density", C.c_double * STATS_MAX_DENSITIES)]
+
+
+class StatsReport(C.Structure):
+    """smhip_stats_report"""
+    _fields_ = [("nonzero", C.c_uint64 * MAX_MODELS), ("G", (C.c_double * MAX_MODELS) * MAX_MODELS),
+                ("k_keep", C.c_uint64 * STATS_MAX_DENSITIES),
+                ("tau", (C.c_float * MAX_MODELS) * STATS_MAX_DENSITIES),
+                ("kept", (C.c_uint64 * MAX_MODELS) * STATS_MAX_DENSITIES),
+                ("energy", (C.c_double * MAX_MODELS) * STATS_MAX_DENSITIES),
+                ("opposed", (C.c_uint64 * MAX_MODELS) * STATS_MAX_DENSITIES),
+                ("alone", (C.c_uint64 * MAX_MODELS) * STATS_MAX_DENSITIES),
+                ("cover", (C.c_uint64 * (MAX_MODELS + 1)) * STATS_MAX_DENSITIES),
+                ("conflict", C.c_uint64 * STATS_MAX_DENSITIES)]
+
+
 DELLA_MAX_COLS = 32768          # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -240,6 +263,7 @@ class SmhipLibrary:
         d.smhip_sce_merge.argtypes = [P, C.POINTER(SceDesc), P, P, C.POINTER(SceReport), P]
         d.smhip_della_merge.argtypes = [P, C.POINTER(DellaDesc), P, P, P, C.POINTER(DellaReport), P]
         d.smhip_consensus_merge.argtypes = [P, C.POINTER(ConsensusDesc), P, P, C.POINTER(ConsensusReport), P]
+        d.smhip_delta_stats.argtypes = [P, C.POINTER(StatsDesc), C.POINTER(StatsReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

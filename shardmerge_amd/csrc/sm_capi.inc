@@ -335,6 +335,28 @@ int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* d, void* o
     SM_FINISH(ctx, ctx->pipe.consensus_merge(*d, out, delta_out, report));
 }
 
+int smhip_delta_stats(smhip_ctx* ctx, const smhip_stats_desc* d, smhip_stats_report* report, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("delta_stats: ") + what); };
+    if (!d) return bad("null descriptor");
+    if (!report) return bad("null report");
+    if (d->k < 1 || d->k > SMHIP_MAX_MODELS) return bad("k out of range (1..16)");
+    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32) return bad("bad dtype");
+    if (d->m < 1 || d->m > SMHIP_STATS_MAX_DENSITIES) return bad("m out of range (1..4)");
+    for (int q = 0; q < d->m; ++q)
+        if (!(d->density[q] > 0.0 && d->density[q] <= 1.0)) return bad("density must be in (0, 1]");
+    for (int i = 0; i < d->k; ++i)
+        if (!std::isfinite(d->alpha[i])) return bad("an alpha is not finite");
+    const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2;
+    for (int i = 0; i < d->k && d->n > 0; ++i) {
+        if (!d->finetune[i] || !d->base[i]) return bad("null model tensor");
+        if ((uintptr_t)d->finetune[i] % ies || (uintptr_t)d->base[i] % ies) return bad("a pointer is not aligned to its element size");
+    }
+    if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return bad("tensor too large");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta_stats(*d, report));
+}
+
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {
     SM_GUARD(ctx);
     if (rows * cols > 0 && (!v0 || !v1 || !out)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

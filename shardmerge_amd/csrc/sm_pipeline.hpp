@@ -24,6 +24,7 @@
 #include "sm_sce.hpp"
 #include "sm_della.hpp"
 #include "sm_consensus.hpp"
+#include "sm_stats.hpp"
 
 namespace smhip {
 
@@ -258,6 +259,13 @@ SM_KERNEL_TAG_LB(KDellaMerge, DellaMergeParams, "della_merge", k_della_merge(ex,
 // sum / election; k <= 4 at dare_merge's residency, or up to 16
 SM_KERNEL_TAG_LB(KConsensusMerge, ConsensusMergeParams, "consensus_merge", k_consensus_merge<CONSENSUS_REG_SMALL>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KConsensusMergeAny, ConsensusMergeParams, "consensus_merge", k_consensus_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
+// Task-vector statistics (sm_stats.hpp): the m-rank radix level and its scan, the one fused pass over the k deltas of an
+// octet (k <= 4 with every density in registers, or up to 16 with the densities tiled), the fold of its energies
+SM_KERNEL_TAG_LB(KStatsHist, StatsHistParams, "stats_hist", k_stats_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KStatsSelect, StatsSelectParams, "stats_select", k_stats_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KStatsPass, StatsPassParams, "stats_pass", k_stats_pass<STATS_REG_SMALL>(ex, p), GEO_THREADS, 2)
+SM_KERNEL_TAG_LB(KStatsPassAny, StatsPassParams, "stats_pass", k_stats_pass<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 1)
+SM_KERNEL_TAG_LB(KStatsFold, StatsFoldParams, "stats_fold", k_stats_fold(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -287,7 +295,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
     X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny) \
     X(KDellaTable) X(KDellaRank) X(KDellaMerge) X(KConsensusMerge) X(KConsensusMergeAny)
-#define SM_SIDE_GROUPS 8         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus
+#define SM_SIDE_KERNELS_8(X) X(KStatsHist) X(KStatsSelect) X(KStatsPass) X(KStatsPassAny) X(KStatsFold)
+#define SM_SIDE_GROUPS 9         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2683,6 +2692,103 @@ class Pipeline {
             }
             for (int c = 0; c <= TIES_MAX_MODELS; ++c) rep->agree[c] = host.counts[c];
             rep->selected = host.counts[TIES_MAX_MODELS + 1];
+        }
+        return SMHIP_OK;
+    }
+
+    // ---- Task-vector statistics (sm_stats.hpp; the function is stated in shardmerge_hip.h, smhip_delta_stats): the three
+    // selection levels for every density at once, the Gram through geo_gram / geo_gram_fold as geo_merge launches them,
+    // the one fused pass and its fold, ONE readback.  Workspace (the TIES buffer): the histograms [3][32][HIST1_BINS]
+    // (STATS_HIST_STRIDE words per finetune) | StatsWork | the Gram's partials | the energies' partials ----
+    struct StatsReadback {
+        float tau[STATS_MAX_RANKS * TIES_MAX_MODELS];
+        unsigned long long kept[STATS_MAX_RANKS * TIES_MAX_MODELS];
+        double energy[STATS_MAX_RANKS * TIES_MAX_MODELS];
+        double G[TIES_MAX_MODELS * (TIES_MAX_MODELS + 1) / 2];
+        unsigned long long counts[STATS_COUNTS];
+        uint32_t flags[2];
+    };
+    struct StatsWork { RadixState state[STATS_MAX_RANKS * TIES_MAX_MODELS]; StatsReadback rb; };
+    int delta_stats(const smhip_stats_desc& d, smhip_stats_report* rep) {
+        const int k = d.k, m = d.m, np = geo_pairs(k);
+        *rep = smhip_stats_report{};
+        for (int q = 0; q < m; ++q) {
+            rep->k_keep[q] = delta_k_keep(d.density[q], d.n);
+            if (d.n == 0) for (int i = 0; i < k; ++i) rep->tau[q][i] = INFINITY;     // k_keep == 0: +inf by definition
+        }
+        if (d.n == 0) return SMHIP_OK;
+
+        TiesInputs in;
+        in.k = k; in.dtype = d.in_dtype; in.n = d.n;
+        bool al = true, shared = true;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) {
+            in.ft[i] = d.finetune[i < k ? i : 0]; in.base[i] = d.base[i < k ? i : 0];
+            al = al && aligned16(in.ft[i]) && aligned16(in.base[i]);
+            shared = shared && in.base[i] == in.base[0];
+        }
+        in.aligned = al ? 1 : 0; in.shared_base = shared ? 1 : 0;
+
+        const size_t nseg = (d.n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
+        const size_t ggrid = nseg * (size_t)geo_tiles(k);
+        if (ggrid > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "delta_stats: tensor too large");
+        const size_t gram_bytes = round_up(nseg * np * sizeof(double), 256);
+        StatsWork* w;
+        size_t off_part;
+        int rc;
+        if ((rc = select_workspace(2 * TIES_MAX_MODELS, w, gram_bytes + nseg * m * k * sizeof(double), &off_part))) return rc;
+
+        StatsHistParams h;
+        h.in = in; h.m = m; h.state = w->state; h.flags = w->rb.flags;
+        StatsSelectParams s;
+        s.m = m; s.state = w->state; s.tau = w->rb.tau; s.kept = w->rb.kept;
+        for (int q = 0; q < STATS_MAX_RANKS; ++q) s.rank[q] = rep->k_keep[q < m ? q : 0];
+        const size_t noct = (d.n + 7) / 8;
+        h.chunks = pick_chunks(noct, 256, 4, 5);
+        const int hgrid = stream_grid(noct, 256, h.chunks);
+        select_levels<KStatsSelect>(2 * TIES_MAX_MODELS, k, s, STATS_SELECT_LDS, [&](int level, unsigned long long* hist) {
+            h.level = level; h.hist = hist;
+            for (int first = 0; first < k; first += TIES_GROUP) {
+                h.first = first; h.count = std::min(TIES_GROUP, k - first);
+                be.template launch<KStatsHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)h.count * stats_hist_words(level, m)) * 4, h, stream);
+            }
+        });
+
+        GeoGramParams g;
+        g.in = in; g.weight_space = 0;
+        g.seg_len = GEO_SEG_ELEMS; g.nseg = nseg; g.seg_vec = in.aligned;
+        g.part = (double*)((char*)ties_.p + off_part); g.flags = w->rb.flags;
+        if (k <= GEO_TILE) be.template launch<KGeoGram>((int)ggrid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+        else be.template launch<KGeoGramTiled>((int)ggrid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+        GeoFoldParams gf;
+        gf.np = np; gf.nseg = nseg; gf.part = g.part; gf.G = w->rb.G;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, gf, stream);
+
+        StatsPassParams sp;
+        sp.in = in; sp.m = m; sp.tau = w->rb.tau; sp.nseg = nseg; sp.seg_vec = in.aligned;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) sp.alpha[i] = (float)d.alpha[i < k ? i : 0];
+        sp.part = (double*)((char*)ties_.p + off_part + gram_bytes); sp.counts = w->rb.counts;
+        if (k <= STATS_REG_SMALL) be.template launch<KStatsPass>((int)nseg, GEO_THREADS, stats_pass_lds_floats(m, k) * 4, sp, stream);
+        else be.template launch<KStatsPassAny>((int)nseg, GEO_THREADS, stats_pass_lds_floats(m, k) * 4, sp, stream);
+        StatsFoldParams sf;
+        sf.m = m; sf.k = k; sf.nseg = nseg; sf.part = sp.part; sf.energy = w->rb.energy;
+        be.template launch<KStatsFold>(1, 256, LDS_SCRATCH_FLOATS * 4, sf, stream);
+
+        StatsReadback host;
+        if ((rc = delta_readback("delta_stats", k, &w->rb, host))) return rc;       // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        const unsigned long long* c = host.counts;
+        for (int i = 0; i < k; ++i) {
+            rep->nonzero[i] = c[STATS_NONZERO + i];
+            for (int j = i; j < k; ++j) rep->G[i][j] = rep->G[j][i] = host.G[geo_pair_index(i, j, k)];
+        }
+        for (int q = 0; q < m; ++q) {
+            for (int i = 0; i < k; ++i) {
+                const int qi = q * TIES_MAX_MODELS + i;
+                rep->tau[q][i] = host.tau[qi]; rep->kept[q][i] = host.kept[qi]; rep->energy[q][i] = host.energy[qi];
+                rep->opposed[q][i] = c[STATS_OPPOSED + qi]; rep->alone[q][i] = c[STATS_ALONE + qi];
+            }
+            for (int cc = 0; cc <= k; ++cc) rep->cover[q][cc] = c[STATS_COVER + q * (TIES_MAX_MODELS + 1) + cc];
+            rep->conflict[q] = c[STATS_CONFLICT + q];
         }
         return SMHIP_OK;
     }

@@ -153,6 +153,22 @@ class ConsensusMergeReport:
 
 
 @dataclass
+class DeltaStatsReport:
+    n: int = 0                                                       # elements of the tensor
+    densities: List[float] = field(default_factory=list)             # rho_q, as given
+    nonzero: List[int] = field(default_factory=list)                 # [i]: elements where finetune i differs from its base
+    gram: List[List[float]] = field(default_factory=list)            # G[i][j], the fp64 Gram of the k deltas
+    k_keep: List[int] = field(default_factory=list)                  # [q]: elements a trim at rho_q asks for
+    thresholds: List[List[float]] = field(default_factory=list)      # [q][i]: tau, the k_keep-th largest |delta_i| (+inf: none)
+    kept: List[List[int]] = field(default_factory=list)              # [q][i]: entries kept (ties at tau included, zeros never)
+    energy: List[List[float]] = field(default_factory=list)          # [q][i]: the fp64 sum of squares of what is kept
+    opposed: List[List[int]] = field(default_factory=list)           # [q][i]: kept entries the TIES election would discard
+    alone: List[List[int]] = field(default_factory=list)             # [q][i]: kept by finetune i and by no other
+    cover: List[List[int]] = field(default_factory=list)             # [q][c], c = 0..k: elements that exactly c finetunes keep
+    conflict: List[int] = field(default_factory=list)                # [q]: elements with kept entries of both signs
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -791,6 +807,58 @@ class Engine:
                                       masked=[int(rep.masked[i]) for i in range(k)],
                                       agree=[int(rep.agree[c]) for c in range(k + 1)], selected=int(rep.selected), n=int(desc.n))
         return (out, report, delta) if want_delta else (out, report)
+
+    # -- task-vector statistics ----------------------------------------------------------------
+    def delta_stats(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                    densities: Sequence[float], layer_name: Optional[str] = None) -> DeltaStatsReport:
+        """Statistics of the deltas ``finetune_i - base_i`` of one tensor of any shape (``smhip_delta_stats``; the
+        function is stated in include/shardmerge_hip.h), no tensor is written: their fp64 Gram and, for up to four
+        candidate ``densities`` at once, every finetune's exact trim threshold, what that trim keeps in elements and
+        in energy, how the kept sets overlap (``alone``, ``cover``) and what the TIES election under ``alphas`` would
+        discard (``opposed``, ``conflict``).  A NaN or Inf in a delta raises ValueError naming ``layer_name`` and the
+        finetune."""
+        layer_name = layer_name or "layer"
+        k, dens = len(finetunes), [float(x) for x in densities]
+        if k < 1 or k > _lib.MAX_MODELS:
+            raise ValueError(f"{k} models to analyse: supported range is 1..{_lib.MAX_MODELS}")
+        if len(bases) != k or len(alphas) != k:
+            raise ValueError(f"delta_stats: {k} finetunes, {len(bases)} bases, {len(alphas)} alphas")
+        if not (1 <= len(dens) <= _lib.STATS_MAX_DENSITIES):
+            raise ValueError(f"delta_stats: {len(dens)} densities, supported range is 1..{_lib.STATS_MAX_DENSITIES}")
+        for rho in dens:
+            if not (0.0 < rho <= 1.0):
+                raise ValueError(f"delta_stats: density {rho} is not in (0, 1]")
+        dtypes = {t.dtype for t in list(finetunes) + list(bases)}        # (mixed dtypes are promoted, as _stage_delta_merge does)
+        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
+        if in_dtype not in _DTYPE_CODE:
+            in_dtype = torch.float32
+        desc, rep, m = _lib.StatsDesc(), _lib.StatsReport(), len(dens)
+        keep, seen = [], {}
+        for i in range(k):
+            ft = self._dev(finetunes[i], in_dtype)
+            if id(bases[i]) not in seen:
+                seen[id(bases[i])] = self._dev(bases[i], in_dtype)
+            bs = seen[id(bases[i])]
+            if ft.shape != bs.shape or ft.shape != finetunes[0].shape:
+                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(finetunes[0].shape)}")
+            keep += [ft, bs]
+            desc.finetune[i], desc.base[i], desc.alpha[i] = ft.data_ptr(), bs.data_ptr(), float(alphas[i])
+        desc.k, desc.in_dtype, desc.n, desc.m = k, _DTYPE_CODE[in_dtype], keep[0].numel(), m
+        for q in range(m):
+            desc.density[q] = dens[q]
+        try:
+            self.ctx.check(self.lib.dll.smhip_delta_stats(self.ctx.h, C.byref(desc), C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
+            raise
+        per = lambda a, cast, cols=k: [[cast(a[q][i]) for i in range(cols)] for q in range(m)]
+        return DeltaStatsReport(
+            n=int(desc.n), densities=dens, nonzero=[int(rep.nonzero[i]) for i in range(k)],
+            gram=[[float(rep.G[i][j]) for j in range(k)] for i in range(k)],
+            k_keep=[int(rep.k_keep[q]) for q in range(m)], thresholds=per(rep.tau, float), kept=per(rep.kept, int),
+            energy=per(rep.energy, float), opposed=per(rep.opposed, int), alone=per(rep.alone, int),
+            cover=per(rep.cover, int, k + 1), conflict=[int(rep.conflict[q]) for q in range(m)])
 
     def correlate_pairs(self, tensors) -> torch.Tensor:
         """K x K matrix of mean column-wise cosine similarities (reference functions.py:304-314);
