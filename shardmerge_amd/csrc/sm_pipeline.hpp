@@ -1603,22 +1603,80 @@ class Pipeline {
         double post = 1.0;              // spatial values = post * ifft(R)   (target_norm)
         int rows_id = -1;               // >= 0: rowspec_[rows_id] holds this raw delta's row spectra (row-pair layout)
     };
-    // spectral -> spatial fp32 (the branches that need spatial inputs: add, Arithmetic-FFT, early-out)
-    int materialise(const Geo& g, Slot& s, std::vector<char>& inter_busy) {
-        if (!s.spectral) return SMHIP_OK;
-        const size_t n = (size_t)g.R * g.C;
+    static constexpr SigDesc NO_SIG{nullptr, nullptr, DT_F32, 1.f};      // the absent second input of a pass
+
+    // The state of ONE merge_layer_once call: everything that lives longer than one pair merge.  It is built afresh at
+    // the top of every call and nothing in it outlives the call (begin_layer_run() resets the pipeline members beside it).
+    struct LayerRun {
+        const smhip_layer_desc& d;
+        void* out;                      // the bf16 result
+        float* delta_out;               // the fp32 merged delta, when wanted
+        smhip_layer_report& rp;
+        int R = 0, C = 0, batch = 1, rough = 1;
+        size_t n = 0;                   // elements: R * C * batch
+        Geo g;
+        bool all_aligned = false, ref_norms = false, spectral_ok = false;
+        std::vector<Slot> stack;
+        std::vector<float> norms32;     // the deltas' fp32 norms, as the reference lists them (Q1)
+        double target_norm = 0;
+        double cull_pct = 0;            // of the current round: halves with every round
+        int step = 0;                   // report entry (pair merges and carries)
+        int round_idx = 0;              // tournament round: the cull fraction goes with it
+        int pair_idx = 0;               // pair merge of this layer, in order: its speculation slot (one guess per
+                                        // (round, position): two pairs of one round have different thresholds - with
+                                        // one guess per round a K = 4 layer missed 22 % of its speculations)
+        bool f1_ready = false;          // K = 2: the row pass that took the norms left the pair's T1
+        PairOut fin;                    // the layer's output: base_out + merged delta, bf16
+        std::vector<char> inter_busy;   // per inter_ buffer
+        int deferred_step = -1;         // >= 0: this step's blend info is read with the flags at the end of the layer
+        bool deferred_cut = false, deferred_cull = false;
+        LayerRun(const smhip_layer_desc& d_, void* out_, float* delta_out_, smhip_layer_report& rp_)
+            : d(d_), out(out_), delta_out(delta_out_), rp(rp_) {}
+    };
+    // one pair merge of a round (the reference's merge_tensors_fft2_slerp / task_arithmetic call and what surrounds it)
+    struct PairRun {
+        int x = -1, y = -1;             // positions in the stack, in pairing order
+        bool last_round = false;
+        Slot A, Bs;                     // the inputs by role: "a" has the larger norm
+        double a_w = 0, b_w = 0;        // Q4: not swapped
+        double na = 0, nb = 0;          // their fp32 norms
+        bool swapped = false, slerp_proper = false;
+        PairOut po;                     // where the merged pair goes: the layer's output or ...
+        float* inter = nullptr;         // ... an fp32 intermediate (neither: the result stays spectral)
+        int branch = 0;
+        int inv_grid = -1;              // >= 0: work-groups of the inverse row pass that left norm partials
+        smhip_blend_info info;
+        bool out_spectral = false;
+        Slot spec_slot;
+        // the SLERP branch
+        double t = 0;
+        bool fused1d = false;           // 1-D: the whole pair merge is one launch
+        int im_parts = -1, sel_parts = 0;
+        bool have_cull = false, fused_norm = false;
+    };
+    // a free fp32 intermediate of the layer's size (a new one when all are taken)
+    int acquire_inter(LayerRun& L, float*& buf) {
         int id = -1;
-        for (size_t q = 0; q < inter_.size(); ++q) if (!inter_busy[q]) { id = (int)q; break; }
-        if (id < 0) { inter_.emplace_back(); inter_busy.push_back(0); id = (int)inter_.size() - 1; }
-        int rc = ensure(inter_[id], n * sizeof(float));
+        for (size_t q = 0; q < inter_.size(); ++q) if (!L.inter_busy[q]) { id = (int)q; break; }
+        if (id < 0) { inter_.emplace_back(); L.inter_busy.push_back(0); id = (int)inter_.size() - 1; }
+        const int rc = ensure(inter_[id], L.n * sizeof(float));
         if (rc) return rc;
-        inter_busy[id] = 1;
+        L.inter_busy[id] = 1;
+        buf = (float*)inter_[id].p;
+        return SMHIP_OK;
+    }
+    // spectral -> spatial fp32 (the branches that need spatial inputs: add, Arithmetic-FFT, early-out)
+    int materialise(LayerRun& L, Slot& s) {
+        if (!s.spectral) return SMHIP_OK;
+        float* buf = nullptr;
+        int rc = acquire_inter(L, buf);
+        if (rc) return rc;
         PairOut po;
-        po.out = inter_[id].p; po.out_mode = OUT_F32; po.post = (float)s.post;
-        if ((rc = run_inverse(g, (const float*)pool_[s.re_id].p, (const float*)pool_[s.im_id].p, nullptr, po, nullptr, s.thr))) return rc;
+        po.out = buf; po.out_mode = OUT_F32; po.post = (float)s.post;
+        if ((rc = run_inverse(L.g, (const float*)pool_[s.re_id].p, (const float*)pool_[s.im_id].p, nullptr, po, nullptr, s.thr))) return rc;
         pool_release(s.re_id); pool_release(s.im_id);
         s.spectral = false; s.re_id = s.im_id = -1;
-        s.sig = SigDesc{inter_[id].p, nullptr, DT_F32, 1.f};
+        s.sig = SigDesc{buf, nullptr, DT_F32, 1.f};
         return SMHIP_OK;
     }
 
@@ -1971,15 +2029,53 @@ class Pipeline {
         if (delta_out) run_transpose(dt, delta_out, d.cols, d.rows, 4);
         return SMHIP_OK;
     }
+    // The layer merge is a sequence of stages over one LayerRun: setup, K = 1, delta norms, target norm, the
+    // tournament rounds (each a loop over pair merges), finish.
     int merge_layer_once(const smhip_layer_desc& d, void* out_bf16, float* delta_out, smhip_layer_report* rep) {
+        smhip_layer_report local;
+        LayerRun L(d, out_bf16, delta_out, rep ? *rep : local);
+        struct RefModeGuard { bool& f; ~RefModeGuard() { f = false; } } ref_guard{ref_mode_};
+        int rc;
+        if ((rc = layer_setup(L))) return rc;
+        begin_layer_run(L);
+        if (d.k == 1) return layer_single(L);
+        if ((rc = reserve(L.g.R, L.C, false, L.g.batch))) return rc;
+        if ((rc = layer_delta_norms(L))) return rc;
+        if ((rc = layer_target_norm(L))) return rc;
+        bool last_round = false;
+        while (L.stack.size() > 1 && !last_round)
+            if ((rc = layer_round(L, last_round))) return rc;
+        return layer_finish(L);
+    }
+
+    // the per-call resets of pipeline members, all of them: a retried call (with_select_retry) or the call after an
+    // aborted one starts from here
+    void begin_layer_run(LayerRun& L) {
+        clear_flags();
+        ref_mode_ = L.ref_norms;                 // (merge_layer_once's guard takes it back)
+        fused_done_ = false;
+        fused_.armed = false;
+        noise_seed_ = noise_seed_base;           // the noise model is a function of (layer step, bin): runs repeat bit for bit
+        for (size_t q = 0; q < pool_.size(); ++q) {          // planes an aborted call left detached
+            bool working = false;
+            for (int i = 0; i < 4; ++i) working = working || pidx_[i] == (int)q;
+            pool_busy_[q] = working ? 1 : 0;
+        }
+        L.inter_busy.assign(inter_.size(), 0);
+    }
+
+    // argument checks, the rough / forced column split, the geometry, the report and the layer stack
+    int layer_setup(LayerRun& L) {
+        const smhip_layer_desc& d = L.d;
         if (d.k < 1 || d.k > SMHIP_MAX_MODELS) return fail(SMHIP_ERR_ARG, "k out of range");
-        const int R = d.rows, C = d.cols;
+        const int R = L.R = d.rows, C = L.C = d.cols;
         if (R < 1 || C < 1) return fail(SMHIP_ERR_ARG, "bad shape");
-        const int batch = d.batch > 1 ? d.batch : 1;          // rank > 2: `batch` slices [R x C], statistics over all of them
+        const int batch = L.batch = d.batch > 1 ? d.batch : 1;          // rank > 2: `batch` slices [R x C], statistics over all of them
         if (batch > 1 && R < 2) return fail(SMHIP_ERR_ARG, "a batch of 1-D slices: pass it as a 2-D tensor");
-        const size_t n = (size_t)R * C * batch;
-        bool all_aligned = aligned16(d.base_out) && aligned16(out_bf16) && aligned16(delta_out);
+        L.n = (size_t)R * C * batch;
+        bool all_aligned = aligned16(d.base_out) && aligned16(L.out) && aligned16(L.delta_out);
         for (int i = 0; i < d.k; ++i) all_aligned = all_aligned && aligned16(d.finetune[i]) && aligned16(d.base[i]);
+        L.all_aligned = all_aligned;
         // a column length without a plan: `rough` row blocks of Rs rows, combined by k_dftp
         int rough = 1, Rs = R;
         if (d.k > 1 && R > 1) {
@@ -1995,391 +2091,417 @@ class Pipeline {
             const int M = R / debug_force_split;
             if (M % 2 == 0 && plan_shape(M, T, rad)) { rough = debug_force_split; Rs = M; }
         }
-        Geo g = geo(Rs, C, false, all_aligned && rough == 1, rough > 1 ? rough : batch);
-        g.rough = rough;
+        L.rough = rough;
+        L.g = geo(Rs, C, false, all_aligned && rough == 1, rough > 1 ? rough : batch);
+        L.g.rough = rough;
         int rc;
         if (!small_.p && (rc = reserve(1, 1))) return rc;
-        clear_flags();
-        smhip_layer_report local;
-        smhip_layer_report& rp = rep ? *rep : local;
-        memset(&rp, 0, sizeof rp);
-        rp.merged_delta_norm = -1;
+        memset(&L.rp, 0, sizeof L.rp);
+        L.rp.merged_delta_norm = -1;
 
-        const bool ref_norms = d.norm_mode == 1;       // torch's CPU norm kernel emulated for every norm the reference takes
-        struct RefModeGuard { bool& f; ~RefModeGuard() { f = false; } } ref_guard{ref_mode_};
-        ref_mode_ = ref_norms;
-        const bool spectral_ok = spectral_inter && (Rs % 2 == 0) && Rs >= 2;
-        std::vector<Slot> stack(d.k);
+        L.ref_norms = d.norm_mode == 1;       // torch's CPU norm kernel emulated for every norm the reference takes
+        L.spectral_ok = spectral_inter && (Rs % 2 == 0) && Rs >= 2;
+        L.stack.resize(d.k);
         for (int i = 0; i < d.k; ++i) {
-            stack[i].sig = SigDesc{d.finetune[i], d.base[i], d.in_dtype, 1.f};
-            stack[i].weight = d.alpha[i];
-            stack[i].norm = -1;
+            L.stack[i].sig = SigDesc{d.finetune[i], d.base[i], d.in_dtype, 1.f};
+            L.stack[i].weight = d.alpha[i];
+            L.stack[i].norm = -1;
         }
-        PairOut fin;
-        fin.out = out_bf16; fin.out_mode = OUT_BF16; fin.base = d.base_out; fin.base_dtype = d.base_out_dtype; fin.post = 1.f;
+        L.fin.out = L.out; L.fin.out_mode = OUT_BF16; L.fin.base = d.base_out; L.fin.base_dtype = d.base_out_dtype; L.fin.post = 1.f;
+        L.cull_pct = d.cull_start_pct;
+        return SMHIP_OK;
+    }
 
-        // K = 1: result = base_out + (ft - base)        (tournament loop is skipped)
-        if (d.k == 1) {
-            SigDesc none{nullptr, nullptr, DT_F32, 1.f};
-            int grid;
-            run_combine(stack[0].sig, none, 1.f, 0.f, n, delta_out, &fin, true, &grid);
-            double na, nb;
-            read_norms(grid, na, nb);
-            rp.delta_norm[0] = na; rp.target_norm = (double)(float)na + d.target_norm_offset; rp.merged_delta_norm = na;
-            return check_flags(false, true, &rp.nan_ifft, &rp.nan_final);
-        }
-        if ((rc = reserve(g.R, C, false, g.batch))) return rc;
+    // K = 1: result = base_out + (ft - base)        (no tournament)
+    int layer_single(LayerRun& L) {
+        double na, nb;
+        combine_norms(L.stack[0].sig, NO_SIG, 1.f, 0.f, L.n, L.delta_out, &L.fin, na, nb);
+        L.rp.delta_norm[0] = na; L.rp.target_norm = (double)(float)na + L.d.target_norm_offset; L.rp.merged_delta_norm = na;
+        return check_flags(false, true, &L.rp.nan_ifft, &L.rp.nan_final);
+    }
 
-        // norms of every delta.  K == 2: fused into the (speculative) F1 of the only pair.
-        std::vector<float> norms32(d.k);
-        int f1_grid = -1;
-        bool f1_ready = false;
+    // run_combine with the norms of its two inputs read back (one sync)
+    void combine_norms(const SigDesc& a, const SigDesc& b, float ca, float cb, size_t n, float* out_f32, const PairOut* fin,
+                       double& na, double& nb) {
+        int grid;
+        run_combine(a, b, ca, cb, n, out_f32, fin, true, &grid);
+        read_norms(grid, na, nb);
+    }
+    // ||x||_2 of an fp32 buffer (grid >= 0: that many work-groups of an earlier pass left the partial sums already)
+    double f32_norm(const float* x, size_t n, int grid = -1) {
+        double nm, dummy;
+        if (grid >= 0) read_norms(grid, nm, dummy);
+        else combine_norms(SigDesc{x, nullptr, DT_F32, 1.f}, NO_SIG, 0.f, 0.f, n, nullptr, nullptr, nm, dummy);
+        return nm;
+    }
+
+    // norms of every delta -> stack[i].norm.  K == 2: fused into the (speculative) F1 of the only pair.
+    int layer_delta_norms(LayerRun& L) {
+        const smhip_layer_desc& d = L.d;
+        const Geo& g = L.g;
+        std::vector<Slot>& stack = L.stack;
         bool ref_started = false;          // reference_cpu: the deltas' torch.norm emulation runs beside the row passes
-        fused_done_ = false;
-        fused_.armed = false;
         if (d.k == 2) {
             // reference_cpu: the row pass summarises its deltas for the torch.norm emulation when its plan can
             // (begin_fused_norms), else the separate summary pass runs in front of it with the walker beside it
-            const bool fusing = ref_norms && begin_fused_norms(g, stack, n);
-            if (ref_norms && !fusing) ref_started = begin_delta_ref_norms(stack, n);
-            rc = run_f1(g, stack[0].sig, stack[1].sig, f1_grid);
+            const bool fusing = L.ref_norms && begin_fused_norms(g, stack, L.n);
+            if (L.ref_norms && !fusing) ref_started = begin_delta_ref_norms(stack, L.n);
+            int f1_grid = -1;
+            const int rc = run_f1(g, stack[0].sig, stack[1].sig, f1_grid);
             if (fusing) ref_started = finish_fused_norms();
             end_delta_ref_norms();
             if (rc) return rc;
             double na, nb;
             read_norms(f1_grid, na, nb);
             stack[0].norm = na; stack[1].norm = nb;
-            f1_ready = true;
-        } else if (spectral_ok && all_aligned && (C % 8 == 0) && (size_t)d.k * 2 * (size_t)(g.R / 2 + 8) * g.batch <= PART_DOUBLES &&
-                   ((ref_started = ref_norms && !begin_fused_norms(g, stack, n) && begin_delta_ref_norms(stack, n)),
-                    rows_first(g, stack) == SMHIP_OK)) {
-            if (fused_done_) ref_started = true;        // (the row passes took the summaries with them; rows_first has synced)
+            L.f1_ready = true;
+        } else {
             // K >= 3: every delta's ROWS are transformed up front, one signal at a time (row pairs);
             // the norms come with it (no separate pass over the inputs), and whichever deltas the
             // pairing puts together only need their column passes afterwards
-        } else {
-            if (!run_delta_norms(d, n, stack)) {
-                SigDesc none{nullptr, nullptr, DT_F32, 1.f};
-                for (int i = 0; i < d.k; i += 2) {
-                    int grid;
-                    const bool two = i + 1 < d.k;
-                    run_combine(stack[i].sig, two ? stack[i + 1].sig : none, 0.f, 0.f, n, nullptr, nullptr, true, &grid);
-                    double na, nb;
-                    read_norms(grid, na, nb);
-                    stack[i].norm = na;
-                    if (two) stack[i + 1].norm = nb;
-                }
+            bool rows = L.spectral_ok && L.all_aligned && (L.C % 8 == 0) &&
+                        (size_t)d.k * 2 * (size_t)(g.R / 2 + 8) * g.batch <= PART_DOUBLES;
+            if (rows) {
+                ref_started = L.ref_norms && !begin_fused_norms(g, stack, L.n) && begin_delta_ref_norms(stack, L.n);
+                rows = rows_first(g, stack) == SMHIP_OK;
             }
+            if (rows && fused_done_) ref_started = true;        // (the row passes took the summaries with them; rows_first has synced)
+            if (!rows) streamed_delta_norms(L);
         }
         fused_.armed = false;
         if (ref_started && d.k != 2 && !fused_done_) { end_delta_ref_norms(); be.sync(stream); }      // (K = 2: joined in front of read_norms' sync)
         if (ref_started) {
             for (int i = 0; i < d.k; ++i) stack[i].norm = (double)mail_->snorm[i];
-        } else if (ref_norms) {
+        } else if (L.ref_norms) {
             SigDesc sg[16];
             double nr[16];
             for (int i = 0; i < d.k; ++i) sg[i] = stack[i].sig;
             // (never a silent fall-back to accurate norms: the caller asked for the reference's device="cpu" numerics)
-            if (!run_serial_norms(sg, d.k, n, nr))
+            if (!run_serial_norms(sg, d.k, L.n, nr))
                 return fail(SMHIP_ERR_ARG, "norm_mode = reference_cpu: the torch.norm emulation does not apply to these inputs");
             for (int i = 0; i < d.k; ++i) stack[i].norm = nr[i];
         }
-        double mean = 0;
+        return SMHIP_OK;
+    }
+    // one pass over the inputs for all norms (run_delta_norms), else a pass per two deltas
+    void streamed_delta_norms(LayerRun& L) {
+        std::vector<Slot>& stack = L.stack;
+        if (run_delta_norms(L.d, L.n, stack)) return;
+        for (int i = 0; i < L.d.k; i += 2) {
+            const bool two = i + 1 < L.d.k;
+            double na, nb;
+            combine_norms(stack[i].sig, two ? stack[i + 1].sig : NO_SIG, 0.f, 0.f, L.n, nullptr, nullptr, na, nb);
+            stack[i].norm = na;
+            if (two) stack[i + 1].norm = nb;
+        }
+    }
+
+    // the fp32 norm list, its non-finite check, and the target norm: the fp32 mean of the list plus the offset
+    int layer_target_norm(LayerRun& L) {
+        const smhip_layer_desc& d = L.d;
+        L.norms32.resize(d.k);
         for (int i = 0; i < d.k; ++i) {
-            norms32[i] = (float)stack[i].norm;           // torch.norm of an fp32 tensor is fp32
-            rp.delta_norm[i] = norms32[i];
+            L.norms32[i] = (float)L.stack[i].norm;           // torch.norm of an fp32 tensor is fp32
+            L.rp.delta_norm[i] = L.norms32[i];
         }
         // A NaN/Inf norm (NaN or Inf element in a finetune or base) makes the pairing find no
-        // pair, every slot is carried and the loop below would never end - the reference does
+        // pair, every slot is carried and the rounds would never end - the reference does
         // spin there.  Deviation: a loud error.
         for (int i = 0; i < d.k; ++i) {
-            if (!std::isfinite(norms32[i])) {
+            if (!std::isfinite(L.norms32[i])) {
                 char buf[96];
-                snprintf(buf, sizeof buf, "||finetune[%d] - base[%d]|| = %g", i, i, (double)norms32[i]);
+                snprintf(buf, sizeof buf, "||finetune[%d] - base[%d]|| = %g", i, i, (double)L.norms32[i]);
                 check_flags(false, false);
                 return fail(SMHIP_ERR_NONFINITE, buf);
             }
         }
-        {   // torch.tensor(layer_norms).mean(): fp32 mean
-            float acc = 0.f;
-            for (int i = 0; i < d.k; ++i) acc += norms32[i];
-            mean = (double)(acc / (float)d.k);
-        }
-        const double target_norm = mean + d.target_norm_offset;
-        rp.target_norm = target_norm;
-        double cull_pct = d.cull_start_pct;
+        float acc = 0.f;                                     // torch.tensor(layer_norms).mean(): fp32 mean
+        for (int i = 0; i < d.k; ++i) acc += L.norms32[i];
+        L.target_norm = (double)(acc / (float)d.k) + d.target_norm_offset;
+        L.rp.target_norm = L.target_norm;
+        return SMHIP_OK;
+    }
 
-        std::vector<char> inter_busy(inter_.size(), 0);
-        for (size_t q = 0; q < pool_.size(); ++q) {          // planes an aborted call left detached
-            bool working = false;
-            for (int i = 0; i < 4; ++i) working = working || pidx_[i] == (int)q;
-            pool_busy_[q] = working ? 1 : 0;
-        }
-        noise_seed_ = noise_seed_base;           // the noise model is a function of (layer step, bin): runs repeat bit for bit
-        int step = 0;
-        int round_idx = 0;                       // tournament round: the cull fraction goes with it
-        int pair_idx = 0;                        // pair merge of this layer, in order: its speculation slot (one guess per
-                                                 // (round, position): two pairs of one round have different thresholds - with
-                                                 // one guess per round a K = 4 layer missed 22 % of its speculations)
-        int deferred_step = -1;
-        bool deferred_cut = false, deferred_cull = false;
-        while (stack.size() > 1) {
-            const int m = (int)stack.size();
-            std::vector<std::pair<int, int>> pairs;
-            correlated_pairs_least(norms32, m, pairs);   // Q1: first m entries of the ORIGINAL norm list
-            std::vector<Slot> next;
-            const bool last_round = (pairs.size() == 1 && pairs[0].second >= 0);
-            bool any_pair = false;
-            for (auto& pr : pairs) any_pair = any_pair || pr.second >= 0;
-            if (!any_pair) { check_flags(false, false); return fail(SMHIP_ERR_NONFINITE, "no pair can be formed (non-finite norms)"); }
-            for (auto& pr : pairs) {
-                const int x = pr.first, y = pr.second;
-                if (step < SMHIP_MAX_PAIRS) { rp.step_x[step] = x; rp.step_y[step] = y; }
-                if (y < 0) {
-                    next.push_back(stack[x]);
-                    if (step < SMHIP_MAX_PAIRS) rp.step_branch[step] = SMHIP_BRANCH_CARRY;
-                    ++step;
-                    continue;
-                }
-                Slot A = stack[x], Bs = stack[y];
-                const double a_w = stack[x].weight, b_w = stack[y].weight;   // Q4: not swapped
-                if (A.norm < 0 || Bs.norm < 0) return fail(SMHIP_ERR_ARG, "internal: norm unknown");
-                double na = (double)(float)A.norm, nb = (double)(float)Bs.norm;
-                bool swapped = false;
-                if (std::fabs(na) < std::fabs(nb)) { std::swap(A, Bs); std::swap(na, nb); swapped = true; }
-                const double ca = std::fabs(na / target_norm), cb = std::fabs(nb / target_norm);
-                const double ratio = cb / (ca + 1e-10);
-                // destination: final output when this is the last merge, else an fp32 intermediate
-                PairOut po;
-                float* inter = nullptr;
-                // merge_tensors_fft2_slerp's own ratio test (functions.py:196-202): linear blend below b
-                const bool linear = (nb / (na + 1e-10)) < d.b;
-                const bool slerp_proper = !(ca < 1e-6) && !(cb < 1e-6 || ratio < 0.1) && !(nb < 1e-4 || na < 1e-4) && !linear;
-                if (last_round) {
-                    po = fin;
-                } else if (slerp_proper && spectral_ok) {
-                    // the result stays in the spectral domain: no fp32 buffer
-                } else {
-                    int id = -1;
-                    for (size_t q = 0; q < inter_.size(); ++q) if (!inter_busy[q]) { id = (int)q; break; }
-                    if (id < 0) { inter_.emplace_back(); inter_busy.push_back(0); id = (int)inter_.size() - 1; }
-                    Buffer* bb = &inter_[id];
-                    if ((rc = ensure(*bb, n * sizeof(float)))) return rc;
-                    inter_busy[id] = 1;
-                    inter = (float*)bb->p;
-                    po.out = inter; po.out_mode = OUT_F32; po.post = 1.f;
-                }
-                int branch;
-                int inv_grid = -1;      // >= 0: work-groups of the inverse row pass that left norm partials
-                smhip_blend_info info;
-                memset(&info, 0, sizeof info);
-                double out_norm = -1;
-                Slot spec_slot;
-                if (!slerp_proper && (A.spectral || Bs.spectral)) {
-                    // these branches work on spatial values
-                    if ((rc = materialise(g, stack[x], inter_busy))) return rc;
-                    if ((rc = materialise(g, stack[y], inter_busy))) return rc;
-                    A = swapped ? stack[y] : stack[x]; Bs = swapped ? stack[x] : stack[y];
-                }
-                bool out_spectral = false;
-                if (ca < 1e-6) {
-                    branch = SMHIP_BRANCH_ADD;                       // merged = a + b
-                    int grid;
-                    if (last_round) run_combine(A.sig, Bs.sig, 1.f, 1.f, n, delta_out, &po, false, &grid);
-                    else run_combine(A.sig, Bs.sig, 1.f, 1.f, n, inter, nullptr, false, &grid);
-                } else if (cb < 1e-6 || ratio < 0.1) {
-                    branch = SMHIP_BRANCH_ARITH;
-                    const double s = target_norm / na;
-                    const double w = b_w / (a_w + 1e-10);
-                    PairOut pa = po;
-                    float* dtmp = nullptr;
-                    if (last_round && delta_out) { pa = PairOut(); pa.out = delta_out; dtmp = delta_out; }
-                    pa.ifft_policy = 0;
-                    if ((rc = pair_arith(A.sig, Bs.sig, R, C, (float)s, (float)(w * s), 1.0, 1, pa, na, nb, &g))) return rc;
-                    if (dtmp) {     // add-back from the fp32 delta
-                        SigDesc ds{dtmp, nullptr, DT_F32, 1.f}, none{nullptr, nullptr, DT_F32, 1.f};
-                        run_combine(ds, none, 1.f, 0.f, n, nullptr, &fin, false);
-                    }
-                    f1_ready = false;
-                } else {
-                    branch = SMHIP_BRANCH_SLERP;
-                    const double t = a_w / (a_w + b_w);
-                    // merge_tensors_fft2_slerp early-outs on the fp32 norms (functions.py:184-190)
-                    if (nb < 1e-4 || na < 1e-4) {
-                        SigDesc none{nullptr, nullptr, DT_F32, 1.f};
-                        const float sc = (float)(target_norm / na);
-                        if (last_round) run_combine(A.sig, none, sc, 0.f, n, delta_out, &po, false);
-                        else run_combine(A.sig, none, sc, 0.f, n, inter, nullptr, false);
-                        branch = SMHIP_BRANCH_EARLY_V0;
-                    } else if (linear) {
-                        // R = Fa + t Fb on the normalised spectra, Im included; then * target_norm
-                        branch = SMHIP_BRANCH_LINEAR;
-                        int grid;
-                        if ((rc = run_f1(g, A.sig, Bs.sig, grid))) return rc;          // a in slot 0
-                        f1_ready = false;
-                        if ((rc = run_f2_linear(g, (float)(1.0 / na), (float)(1.0 / nb), (float)t))) return rc;
-                        PairOut ps = po;
-                        ps.post = (float)target_norm;
-                        float* dtmp = nullptr;
-                        if (last_round && delta_out) { ps = PairOut(); ps.out = delta_out; ps.post = (float)target_norm; dtmp = delta_out; }
-                        if ((rc = run_inverse(g, plane(g, P_RER), plane(g, P_IMA), nullptr, ps, last_round ? nullptr : &inv_grid))) return rc;
-                        if (dtmp) {
-                            SigDesc ds{dtmp, nullptr, DT_F32, 1.f}, none{nullptr, nullptr, DT_F32, 1.f};
-                            run_combine(ds, none, 1.f, 0.f, n, nullptr, &fin, false);
-                        }
-                    } else {
-                        int im_parts = -1;
-                        const bool any_spec = stack[x].spectral || stack[y].spectral ||
-                                              (stack[x].rows_id >= 0 && stack[y].rows_id >= 0);
-                        const bool fused1d = !any_spec && pair1d_ok(g);       // 1-D: the whole pair merge is one launch
-                        if (fused1d) {
-                            f1_ready = false;
-                        } else if (!any_spec) {
-                            if (!(f1_ready && d.k == 2)) {
-                                int grid;
-                                if ((rc = run_f1(g, stack[x].sig, stack[y].sig, grid))) return rc;
-                            }
-                            f1_ready = false;
-                            // T1 slot 0 holds stack[x], slot 1 holds stack[y]; role "a" is the larger norm
-                            const float s0 = (float)(1.0 / (double)(float)stack[x].norm);
-                            const float s1 = (float)(1.0 / (double)(float)stack[y].norm);
-                            if ((rc = run_f2(g, s0, s1, swapped ? 1 : 0, d.cutoff_pct > 0))) return rc;
-                        } else {
-                            // at least one input stayed in the spectral domain: bring each input's
-                            // planes in on its own (the level-1 histogram accumulates over both)
-                            f1_ready = false;
-                            int* imp = (!last_round && spectral_ok && fuse_spec_norm) ? &im_parts : nullptr;
-                            // both inputs raw with their rows done: ONE column-pass launch for the two of them
-                            // (measured on one box, per layer: 1024x8192 -19 %, 14336x4096 -6 %, 8192^2 -2 %, 8192x28672 -0.6 %,
-                            //  the folded 28672x8192 +1 %: the launch boundary it saves matters for short passes only)
-                            if (f2s_pair && g.batch == 1 && g.fold == 1 && (size_t)g.Cb * g.R <= f2s_pair_max_bins &&
-                                !stack[x].spectral && !stack[y].spectral &&
-                                stack[x].rows_id >= 0 && stack[y].rows_id >= 0) {
-                                const bool xa = !swapped;
-                                F2SSecond sec{rowspec_[stack[y].rows_id].p, !xa, (float)(1.0 / (double)(float)stack[y].norm)};
-                                if ((rc = run_f2s(g, xa, (float)(1.0 / (double)(float)stack[x].norm), d.cutoff_pct > 0,
-                                                  rowspec_[stack[x].rows_id].p, imp, &sec))) return rc;
-                            } else
-                            for (int side = 0; side < 2; ++side) {
-                                const Slot& in = side == 0 ? stack[x] : stack[y];
-                                const bool role_a = (side == 0) != swapped;
-                                int* ip = role_a ? imp : nullptr;
-                                if (in.spectral) {
-                                    run_spec_rescale(g, (const float*)pool_[in.re_id].p, (const float*)pool_[in.im_id].p, in.thr,
-                                                     (float)in.spec_scale, role_a, d.cutoff_pct > 0, ip);
-                                } else if (in.rows_id >= 0) {
-                                    if ((rc = run_f2s(g, role_a, (float)(1.0 / (double)(float)in.norm), d.cutoff_pct > 0,
-                                                      rowspec_[in.rows_id].p, ip))) return rc;
-                                } else {
-                                    if ((rc = run_f1_rowpairs(g, in.sig))) return rc;
-                                    if ((rc = run_f2s(g, role_a, (float)(1.0 / (double)(float)in.norm), d.cutoff_pct > 0, nullptr, ip))) return rc;
-                                }
-                            }
-                        }
-                        bool have_cull;
-                        int sel_parts = 0;
-                        const bool fused_norm = im_parts > 0 && !safe_select && cull_pct > 0;
-                        if (fused1d) have_cull = cull_pct > 0;
-                        else spectral_blend(g, BLEND_SLERP, t, d.t_sum, d.cutoff_pct, cull_pct, 1, true, have_cull,
-                                            fused_norm ? &sel_parts : nullptr, std::min(pair_idx++, 6));
-                        for (int side = 0; side < 2; ++side) {          // consumed spectral inputs give their planes back
-                            Slot& in = side == 0 ? stack[x] : stack[y];
-                            if (in.spectral) { pool_release(in.re_id); pool_release(in.im_id); in.re_id = in.im_id = -1; }
-                        }
-                        if (!last_round && spectral_ok) {
-                            // the result stays spectral: its norm by Parseval, its planes detached
-                            double sre, sim;
-                            if (fused_norm && sel_parts > 0) run_spec_norm_fused(sel_parts, im_parts, sre, sim);
-                            else run_spec_norm(g, plane(g, P_RER), plane(g, P_IMA), have_cull ? d_thr(1) : nullptr, sre, sim);
-                            read_blend_info(&info, d.cutoff_pct > 0, have_cull, true, /*published=*/true);
-                            const double ssum = (sre + sim) / ((double)R * (double)C);     // Parseval per [R x C] transform (slices add up)
-                            out_spectral = true;
-                            spec_slot = Slot();
-                            spec_slot.spectral = true;
-                            spec_slot.re_id = pidx_[P_RER]; spec_slot.im_id = pidx_[P_IMA];
-                            spec_slot.thr = have_cull ? mail_->thr[1] : 0.f;
-                            // reference_cpu: the reference takes torch.norm of the materialised tensor
-                            // (fast_fourier.py:209-210, functions.py:85); here the tensor does not exist - its norm
-                            // is modelled from its exact one (aten_gauss_norm_ratio: the values are Gaussian-like)
-                            const double nrm_exact = target_norm * std::sqrt(ssum);
-                            const double bias = ref_norms ? aten_gauss_norm_ratio((double)n, nrm_exact / std::sqrt((double)n)) : 1.0;
-                            spec_slot.spec_scale = ssum > 0 ? 1.0 / (std::sqrt(ssum) * bias) : 1.0;
-                            spec_slot.post = target_norm;
-                            spec_slot.norm = nrm_exact * bias;
-                            spec_slot.sig = SigDesc{nullptr, nullptr, DT_F32, 1.f};
-                            const int r1 = pool_acquire(g.plane_floats * sizeof(float));
-                            const int r2 = pool_acquire(g.plane_floats * sizeof(float));
-                            if (r1 < 0 || r2 < 0) return SMHIP_ERR_NOMEM;
-                            pidx_[P_RER] = r1; pidx_[P_IMA] = r2;
-                        } else {
-                        PairOut ps = po;
-                        ps.post = (float)target_norm;                       // merged * target_norm (fast_fourier.py:243)
-                        float* dtmp = nullptr;
-                        if (last_round && delta_out) { ps = PairOut(); ps.out = delta_out; ps.post = (float)target_norm; dtmp = delta_out; }
-                        if (fused1d) {
-                            if ((rc = run_pair1d(g, A.sig, Bs.sig, na, nb, t, d.t_sum, d.cutoff_pct, cull_pct, ps,
-                                                 last_round ? nullptr : &inv_grid))) return rc;
-                        } else
-                        if ((rc = run_inverse(g, plane(g, P_RER), plane(g, P_IMA), have_cull ? d_thr(1) : nullptr, ps,
-                                              last_round ? nullptr : &inv_grid))) return rc;
-                        if (dtmp) {
-                            SigDesc ds{dtmp, nullptr, DT_F32, 1.f}, none{nullptr, nullptr, DT_F32, 1.f};
-                            run_combine(ds, none, 1.f, 0.f, n, nullptr, &fin, false);
-                        }
-                        if (last_round) {      // read with the flags at the end of the layer: one sync less
-                            deferred_step = step; deferred_cut = d.cutoff_pct > 0; deferred_cull = have_cull;
-                        } else {
-                            read_blend_info(&info, d.cutoff_pct > 0, have_cull, true);
-                        }
-                        }
-                    }
-                }
-                if (branch == SMHIP_BRANCH_SLERP || branch == SMHIP_BRANCH_LINEAR) { info.t = a_w / (a_w + b_w); info.cull_pct = cull_pct; }
-                if (step < SMHIP_MAX_PAIRS) { rp.step_branch[step] = branch; rp.step_info[step] = info; }
-                ++step;
-                for (size_t q = 0; q < inter_.size(); ++q)     // inputs that were intermediates are dead now
-                    if (inter_[q].p && (inter_[q].p == stack[x].sig.x || inter_[q].p == stack[y].sig.x)) inter_busy[q] = 0;
-                if (!last_round && out_spectral) {
-                    spec_slot.weight = (a_w + b_w) / 2.0;
-                    next.push_back(spec_slot);
-                } else if (!last_round) {
-                    // the next round needs ||merged|| (fast_fourier.py:209-210)
-                    SigDesc ms{inter, nullptr, DT_F32, 1.f}, none{nullptr, nullptr, DT_F32, 1.f};
-                    int grid = inv_grid;             // the inverse row pass summed the squares it stored
-                    if (grid < 0) run_combine(ms, none, 0.f, 0.f, n, nullptr, nullptr, true, &grid);
-                    double nm, dummy;
-                    read_norms(grid, nm, dummy);
-                    if (ref_norms) {
-                        double nr;
-                        if (!run_serial_norms(&ms, 1, n, &nr))
-                            return fail(SMHIP_ERR_ARG, "norm_mode = reference_cpu: the torch.norm emulation does not apply to an intermediate");
-                        nm = nr;
-                    }
-                    out_norm = nm;
-                    Slot s;
-                    s.sig = ms; s.weight = (a_w + b_w) / 2.0; s.norm = out_norm;
-                    next.push_back(s);
-                }
+    // one tournament round: pair the stack up, merge every pair, carry the odd one
+    int layer_round(LayerRun& L, bool& last_round) {
+        smhip_layer_report& rp = L.rp;
+        const int m = (int)L.stack.size();
+        std::vector<std::pair<int, int>> pairs;
+        correlated_pairs_least(L.norms32, m, pairs);   // Q1: first m entries of the ORIGINAL norm list
+        std::vector<Slot> next;
+        last_round = (pairs.size() == 1 && pairs[0].second >= 0);
+        bool any_pair = false;
+        for (auto& pr : pairs) any_pair = any_pair || pr.second >= 0;
+        if (!any_pair) { check_flags(false, false); return fail(SMHIP_ERR_NONFINITE, "no pair can be formed (non-finite norms)"); }
+        for (auto& pr : pairs) {
+            const int x = pr.first, y = pr.second;
+            if (L.step < SMHIP_MAX_PAIRS) { rp.step_x[L.step] = x; rp.step_y[L.step] = y; }
+            if (y < 0) {
+                next.push_back(L.stack[x]);
+                if (L.step < SMHIP_MAX_PAIRS) rp.step_branch[L.step] = SMHIP_BRANCH_CARRY;
+                ++L.step;
+                continue;
             }
-            stack.swap(next);
-            cull_pct = cull_pct / 2.0;
-            ++round_idx;
-            if (last_round) break;
+            const int rc = layer_pair(L, x, y, last_round, next);
+            if (rc) return rc;
         }
-        rp.n_steps = std::min(step, (int)SMHIP_MAX_PAIRS);
-        if (delta_out) {
-            SigDesc ds{delta_out, nullptr, DT_F32, 1.f}, none{nullptr, nullptr, DT_F32, 1.f};
+        L.stack.swap(next);
+        L.cull_pct = L.cull_pct / 2.0;
+        ++L.round_idx;
+        return SMHIP_OK;
+    }
+
+    // one pair merge: roles and ratios, the destination, the branch, the next round's slot
+    int layer_pair(LayerRun& L, int x, int y, bool last_round, std::vector<Slot>& next) {
+        const smhip_layer_desc& d = L.d;
+        std::vector<Slot>& stack = L.stack;
+        PairRun P;
+        P.x = x; P.y = y; P.last_round = last_round;
+        P.A = stack[x]; P.Bs = stack[y];
+        P.a_w = stack[x].weight; P.b_w = stack[y].weight;   // Q4: not swapped
+        if (P.A.norm < 0 || P.Bs.norm < 0) return fail(SMHIP_ERR_ARG, "internal: norm unknown");
+        P.na = (double)(float)P.A.norm; P.nb = (double)(float)P.Bs.norm;
+        if (std::fabs(P.na) < std::fabs(P.nb)) { std::swap(P.A, P.Bs); std::swap(P.na, P.nb); P.swapped = true; }
+        const double na = P.na, nb = P.nb;
+        const double ca = std::fabs(na / L.target_norm), cb = std::fabs(nb / L.target_norm);
+        const double ratio = cb / (ca + 1e-10);
+        // merge_tensors_fft2_slerp's own ratio test (functions.py:196-202): linear blend below b
+        const bool linear = (nb / (na + 1e-10)) < d.b;
+        P.slerp_proper = !(ca < 1e-6) && !(cb < 1e-6 || ratio < 0.1) && !(nb < 1e-4 || na < 1e-4) && !linear;
+        // destination: final output when this is the last merge, else an fp32 intermediate
+        int rc;
+        if (last_round) {
+            P.po = L.fin;
+        } else if (P.slerp_proper && L.spectral_ok) {
+            // the result stays in the spectral domain: no fp32 buffer
+        } else {
+            if ((rc = acquire_inter(L, P.inter))) return rc;
+            P.po.out = P.inter; P.po.out_mode = OUT_F32; P.po.post = 1.f;
+        }
+        memset(&P.info, 0, sizeof P.info);
+        if (!P.slerp_proper && (P.A.spectral || P.Bs.spectral)) {
+            // these branches work on spatial values
+            if ((rc = materialise(L, stack[x]))) return rc;
+            if ((rc = materialise(L, stack[y]))) return rc;
+            P.A = P.swapped ? stack[y] : stack[x]; P.Bs = P.swapped ? stack[x] : stack[y];
+        }
+        if (ca < 1e-6) rc = pair_add(L, P);
+        else if (cb < 1e-6 || ratio < 0.1) rc = pair_arith_branch(L, P);
+        // merge_tensors_fft2_slerp early-outs on the fp32 norms (functions.py:184-190)
+        else if (nb < 1e-4 || na < 1e-4) rc = pair_early_v0(L, P);
+        else if (linear) rc = pair_linear(L, P);
+        else rc = pair_slerp(L, P);
+        if (rc) return rc;
+        return pair_done(L, P, next);
+    }
+
+    // the last merge of a layer whose fp32 delta is wanted writes the delta (pair_dest) and adds the base to it in a
+    // second pass (add_back); every other merge writes where the pair was sent
+    PairOut pair_dest(const LayerRun& L, const PairRun& P, float post) {
+        PairOut o = P.po;
+        if (P.last_round && L.delta_out) { o = PairOut(); o.out = L.delta_out; }
+        o.post = post;
+        return o;
+    }
+    void add_back(LayerRun& L, const PairRun& P) {
+        if (!(P.last_round && L.delta_out)) return;
+        run_combine(SigDesc{L.delta_out, nullptr, DT_F32, 1.f}, NO_SIG, 1.f, 0.f, L.n, nullptr, &L.fin, false);
+    }
+
+    int pair_add(LayerRun& L, PairRun& P) {
+        P.branch = SMHIP_BRANCH_ADD;                       // merged = a + b
+        if (P.last_round) run_combine(P.A.sig, P.Bs.sig, 1.f, 1.f, L.n, L.delta_out, &P.po, false);
+        else run_combine(P.A.sig, P.Bs.sig, 1.f, 1.f, L.n, P.inter, nullptr, false);
+        return SMHIP_OK;
+    }
+    int pair_arith_branch(LayerRun& L, PairRun& P) {
+        P.branch = SMHIP_BRANCH_ARITH;
+        const double s = L.target_norm / P.na;
+        const double w = P.b_w / (P.a_w + 1e-10);
+        PairOut pa = pair_dest(L, P, P.po.post);
+        pa.ifft_policy = 0;
+        const int rc = pair_arith(P.A.sig, P.Bs.sig, L.R, L.C, (float)s, (float)(w * s), 1.0, 1, pa, P.na, P.nb, &L.g);
+        if (rc) return rc;
+        add_back(L, P);     // from the fp32 delta
+        L.f1_ready = false;
+        return SMHIP_OK;
+    }
+    int pair_early_v0(LayerRun& L, PairRun& P) {
+        P.branch = SMHIP_BRANCH_EARLY_V0;
+        const float sc = (float)(L.target_norm / P.na);
+        if (P.last_round) run_combine(P.A.sig, NO_SIG, sc, 0.f, L.n, L.delta_out, &P.po, false);
+        else run_combine(P.A.sig, NO_SIG, sc, 0.f, L.n, P.inter, nullptr, false);
+        return SMHIP_OK;
+    }
+    int pair_linear(LayerRun& L, PairRun& P) {
+        // R = Fa + t Fb on the normalised spectra, Im included; then * target_norm
+        P.branch = SMHIP_BRANCH_LINEAR;
+        const Geo& g = L.g;
+        const double t = P.a_w / (P.a_w + P.b_w);
+        int rc, grid;
+        if ((rc = run_f1(g, P.A.sig, P.Bs.sig, grid))) return rc;          // a in slot 0
+        L.f1_ready = false;
+        if ((rc = run_f2_linear(g, (float)(1.0 / P.na), (float)(1.0 / P.nb), (float)t))) return rc;
+        const PairOut ps = pair_dest(L, P, (float)L.target_norm);
+        if ((rc = run_inverse(g, plane(g, P_RER), plane(g, P_IMA), nullptr, ps, P.last_round ? nullptr : &P.inv_grid))) return rc;
+        add_back(L, P);
+        return SMHIP_OK;
+    }
+
+    // SLERP proper: the inputs' spectra into the working planes, the blend, then the result either stays spectral
+    // (a later round takes it up) or is transformed back
+    int pair_slerp(LayerRun& L, PairRun& P) {
+        P.branch = SMHIP_BRANCH_SLERP;
+        P.t = P.a_w / (P.a_w + P.b_w);
+        int rc;
+        if ((rc = slerp_inputs(L, P))) return rc;
+        slerp_blend(L, P);
+        if (!P.last_round && L.spectral_ok) return slerp_keep_spectral(L, P);
+        return slerp_inverse(L, P);
+    }
+    int slerp_inputs(LayerRun& L, PairRun& P) {
+        const smhip_layer_desc& d = L.d;
+        const Geo& g = L.g;
+        const Slot& sx = L.stack[P.x];
+        const Slot& sy = L.stack[P.y];
+        const bool hist = d.cutoff_pct > 0;
+        int rc;
+        const bool any_spec = sx.spectral || sy.spectral || (sx.rows_id >= 0 && sy.rows_id >= 0);
+        P.fused1d = !any_spec && pair1d_ok(g);       // 1-D: the whole pair merge is one launch
+        if (!P.fused1d && !any_spec && !(L.f1_ready && d.k == 2)) {
             int grid;
-            run_combine(ds, none, 0.f, 0.f, n, nullptr, nullptr, true, &grid);
-            double nm, dummy;
-            read_norms(grid, nm, dummy);
-            rp.merged_delta_norm = nm;
+            if ((rc = run_f1(g, sx.sig, sy.sig, grid))) return rc;
         }
-        rc = check_flags(true, true, &rp.nan_ifft, &rp.nan_final);
-        if (deferred_step >= 0 && deferred_step < SMHIP_MAX_PAIRS) {
-            const double t_keep = rp.step_info[deferred_step].t, c_keep = rp.step_info[deferred_step].cull_pct;
-            read_blend_info(&rp.step_info[deferred_step], deferred_cut, deferred_cull, true, /*published=*/true);
-            rp.step_info[deferred_step].t = t_keep; rp.step_info[deferred_step].cull_pct = c_keep;
+        L.f1_ready = false;
+        if (P.fused1d) return SMHIP_OK;
+        if (!any_spec) {
+            // T1 slot 0 holds stack[x], slot 1 holds stack[y]; role "a" is the larger norm
+            const float s0 = (float)(1.0 / (double)(float)sx.norm);
+            const float s1 = (float)(1.0 / (double)(float)sy.norm);
+            return run_f2(g, s0, s1, P.swapped ? 1 : 0, hist);
+        }
+        // at least one input stayed in the spectral domain: bring each input's
+        // planes in on its own (the level-1 histogram accumulates over both)
+        int* imp = (!P.last_round && L.spectral_ok && fuse_spec_norm) ? &P.im_parts : nullptr;
+        // both inputs raw with their rows done: ONE column-pass launch for the two of them
+        // (measured on one box, per layer: 1024x8192 -19 %, 14336x4096 -6 %, 8192^2 -2 %, 8192x28672 -0.6 %,
+        //  the folded 28672x8192 +1 %: the launch boundary it saves matters for short passes only)
+        if (f2s_pair && g.batch == 1 && g.fold == 1 && (size_t)g.Cb * g.R <= f2s_pair_max_bins &&
+            !sx.spectral && !sy.spectral && sx.rows_id >= 0 && sy.rows_id >= 0) {
+            const bool xa = !P.swapped;
+            F2SSecond sec{rowspec_[sy.rows_id].p, !xa, (float)(1.0 / (double)(float)sy.norm)};
+            return run_f2s(g, xa, (float)(1.0 / (double)(float)sx.norm), hist, rowspec_[sx.rows_id].p, imp, &sec);
+        }
+        for (int side = 0; side < 2; ++side) {
+            const Slot& in = side == 0 ? sx : sy;
+            const bool role_a = (side == 0) != P.swapped;
+            int* ip = role_a ? imp : nullptr;
+            if (in.spectral) {
+                run_spec_rescale(g, (const float*)pool_[in.re_id].p, (const float*)pool_[in.im_id].p, in.thr,
+                                 (float)in.spec_scale, role_a, hist, ip);
+                continue;
+            }
+            if (in.rows_id < 0 && (rc = run_f1_rowpairs(g, in.sig))) return rc;
+            if ((rc = run_f2s(g, role_a, (float)(1.0 / (double)(float)in.norm), hist,
+                              in.rows_id >= 0 ? rowspec_[in.rows_id].p : nullptr, ip))) return rc;
+        }
+        return SMHIP_OK;
+    }
+    void slerp_blend(LayerRun& L, PairRun& P) {
+        const smhip_layer_desc& d = L.d;
+        P.fused_norm = P.im_parts > 0 && !safe_select && L.cull_pct > 0;
+        if (P.fused1d) P.have_cull = L.cull_pct > 0;
+        else spectral_blend(L.g, BLEND_SLERP, P.t, d.t_sum, d.cutoff_pct, L.cull_pct, 1, true, P.have_cull,
+                            P.fused_norm ? &P.sel_parts : nullptr, std::min(L.pair_idx++, 6));
+        for (int side = 0; side < 2; ++side) {          // consumed spectral inputs give their planes back
+            Slot& in = side == 0 ? L.stack[P.x] : L.stack[P.y];
+            if (in.spectral) { pool_release(in.re_id); pool_release(in.im_id); in.re_id = in.im_id = -1; }
+        }
+    }
+    // the result stays spectral: its norm by Parseval, its planes detached
+    int slerp_keep_spectral(LayerRun& L, PairRun& P) {
+        const smhip_layer_desc& d = L.d;
+        const Geo& g = L.g;
+        double sre, sim;
+        if (P.fused_norm && P.sel_parts > 0) run_spec_norm_fused(P.sel_parts, P.im_parts, sre, sim);
+        else run_spec_norm(g, plane(g, P_RER), plane(g, P_IMA), P.have_cull ? d_thr(1) : nullptr, sre, sim);
+        read_blend_info(&P.info, d.cutoff_pct > 0, P.have_cull, true, /*published=*/true);
+        const double ssum = (sre + sim) / ((double)L.R * (double)L.C);     // Parseval per [R x C] transform (slices add up)
+        P.out_spectral = true;
+        Slot& s = P.spec_slot;
+        s = Slot();
+        s.spectral = true;
+        s.re_id = pidx_[P_RER]; s.im_id = pidx_[P_IMA];
+        s.thr = P.have_cull ? mail_->thr[1] : 0.f;
+        // reference_cpu: the reference takes torch.norm of the materialised tensor
+        // (fast_fourier.py:209-210, functions.py:85); here the tensor does not exist - its norm
+        // is modelled from its exact one (aten_gauss_norm_ratio: the values are Gaussian-like)
+        const double nrm_exact = L.target_norm * std::sqrt(ssum);
+        const double bias = L.ref_norms ? aten_gauss_norm_ratio((double)L.n, nrm_exact / std::sqrt((double)L.n)) : 1.0;
+        s.spec_scale = ssum > 0 ? 1.0 / (std::sqrt(ssum) * bias) : 1.0;
+        s.post = L.target_norm;
+        s.norm = nrm_exact * bias;
+        s.sig = NO_SIG;
+        const int r1 = pool_acquire(g.plane_floats * sizeof(float));
+        const int r2 = pool_acquire(g.plane_floats * sizeof(float));
+        if (r1 < 0 || r2 < 0) return SMHIP_ERR_NOMEM;
+        pidx_[P_RER] = r1; pidx_[P_IMA] = r2;
+        return SMHIP_OK;
+    }
+    int slerp_inverse(LayerRun& L, PairRun& P) {
+        const smhip_layer_desc& d = L.d;
+        const Geo& g = L.g;
+        const PairOut ps = pair_dest(L, P, (float)L.target_norm);      // merged * target_norm (fast_fourier.py:243)
+        int* inv_grid = P.last_round ? nullptr : &P.inv_grid;
+        int rc;
+        if (P.fused1d) rc = run_pair1d(g, P.A.sig, P.Bs.sig, P.na, P.nb, P.t, d.t_sum, d.cutoff_pct, L.cull_pct, ps, inv_grid);
+        else rc = run_inverse(g, plane(g, P_RER), plane(g, P_IMA), P.have_cull ? d_thr(1) : nullptr, ps, inv_grid);
+        if (rc) return rc;
+        add_back(L, P);
+        if (P.last_round) {      // read with the flags at the end of the layer: one sync less
+            L.deferred_step = L.step; L.deferred_cut = d.cutoff_pct > 0; L.deferred_cull = P.have_cull;
+        } else {
+            read_blend_info(&P.info, d.cutoff_pct > 0, P.have_cull, true);
+        }
+        return SMHIP_OK;
+    }
+
+    // after a pair: its report entry, its dead inputs, the next round's slot with its norm
+    int pair_done(LayerRun& L, PairRun& P, std::vector<Slot>& next) {
+        const Slot& sx = L.stack[P.x];
+        const Slot& sy = L.stack[P.y];
+        if (P.branch == SMHIP_BRANCH_SLERP || P.branch == SMHIP_BRANCH_LINEAR) { P.info.t = P.a_w / (P.a_w + P.b_w); P.info.cull_pct = L.cull_pct; }
+        if (L.step < SMHIP_MAX_PAIRS) { L.rp.step_branch[L.step] = P.branch; L.rp.step_info[L.step] = P.info; }
+        ++L.step;
+        for (size_t q = 0; q < inter_.size(); ++q)     // inputs that were intermediates are dead now
+            if (inter_[q].p && (inter_[q].p == sx.sig.x || inter_[q].p == sy.sig.x)) L.inter_busy[q] = 0;
+        if (P.last_round) return SMHIP_OK;
+        if (P.out_spectral) {
+            P.spec_slot.weight = (P.a_w + P.b_w) / 2.0;
+            next.push_back(P.spec_slot);
+            return SMHIP_OK;
+        }
+        // the next round needs ||merged|| (fast_fourier.py:209-210); the inverse row pass summed the squares it stored
+        Slot s;
+        s.sig = SigDesc{P.inter, nullptr, DT_F32, 1.f}; s.weight = (P.a_w + P.b_w) / 2.0;
+        s.norm = f32_norm(P.inter, L.n, P.inv_grid);
+        if (L.ref_norms && !run_serial_norms(&s.sig, 1, L.n, &s.norm))
+            return fail(SMHIP_ERR_ARG, "norm_mode = reference_cpu: the torch.norm emulation does not apply to an intermediate");
+        next.push_back(s);
+        return SMHIP_OK;
+    }
+
+    // the merged delta's norm, the NaN / Inf flags, the blend info of the last pair
+    int layer_finish(LayerRun& L) {
+        smhip_layer_report& rp = L.rp;
+        rp.n_steps = std::min(L.step, (int)SMHIP_MAX_PAIRS);
+        if (L.delta_out) rp.merged_delta_norm = f32_norm(L.delta_out, L.n);
+        const int rc = check_flags(true, true, &rp.nan_ifft, &rp.nan_final);
+        if (L.deferred_step >= 0 && L.deferred_step < SMHIP_MAX_PAIRS) {
+            smhip_blend_info& info = rp.step_info[L.deferred_step];
+            const double t_keep = info.t, c_keep = info.cull_pct;
+            read_blend_info(&info, L.deferred_cut, L.deferred_cull, true, /*published=*/true);
+            info.t = t_keep; info.cull_pct = c_keep;
         }
         return rc;
     }

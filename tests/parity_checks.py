@@ -21,7 +21,9 @@ that come back from its ifft->fft round trip as rounding noise (see
 oracle/chaos_probe.py): there the bar is the reference's own reproducibility
 floor, measured when the goldens were generated (manifest "layer_self_floor").
 """
+import json
 import math
+from pathlib import Path
 
 import torch
 
@@ -427,3 +429,178 @@ def check_fn_normalize(engine):
     z = torch.zeros(16)
     out, norm = engine.normalize_tensor(z)
     assert norm == 0.0 and torch.equal(out.cpu(), z)
+
+
+# ---- the host sequence of the spectral layer merge, pinned (tests/golden/layer_launches.json) -----------------------
+# What a layer merge launches and which pairs it merges in which branch, recorded ONCE (python -m tests.parity_checks,
+# on the commit before the host sequence was split into stages) and compared for equality ever since: integers and
+# names only, nothing a machine's libm could move.
+LAUNCH_GOLDEN = Path(__file__).resolve().parent / "golden" / "layer_launches.json"
+
+
+def random_layer(shape, k, seed):
+    """bf16 base + k finetunes with deltas of comparable norms (every pair merge takes the SLERP branch)"""
+    g = torch.Generator().manual_seed(seed)
+    base = (torch.randn(shape, generator=g) * 0.02).to(torch.bfloat16)
+    sig = (0.002, 0.003, 0.0025, 0.0035)
+    fts = [(base.float() + torch.randn(shape, generator=g) * sig[i % 4]).to(torch.bfloat16) for i in range(k)]
+    return base, fts
+
+
+def early_v0_inputs(dtype):
+    """two deltas of comparable norms below merge_tensors_fft2_slerp's 1e-4 early-out (functions.py:184-190)"""
+    torch.manual_seed(7)
+    base = torch.zeros(64, 64)
+    ft0 = 1e-7 * torch.randn(64, 64)
+    ft1 = 0.7e-7 * torch.randn(64, 64)
+    return base.to(dtype), [ft0.to(dtype), ft1.to(dtype)]
+
+
+def _early_v0_args(dtype):
+    base, fts = early_v0_inputs(dtype)
+    return dict(finetunes=fts, bases=[base, base], alphas=[0.5, 0.3], base_out=base)
+
+
+def _golden_layer_args(cid):
+    case = [c for c in gi.LAYER_CASES if c["id"] == cid][0]
+    tensors, use, cfg, lname = models_in_window(case)
+    return dict(finetunes=[tensors[m["model"]] for m in use], bases=[tensors[m["base"]] for m in use],
+                alphas=[m["alpha"] for m in use], base_out=tensors[cfg["output_base_model"]], layer_name=lname)
+
+
+def _synthetic_args(base, fts, **kw):
+    k = len(fts)
+    return dict(finetunes=fts, bases=[base] * k, alphas=[so.ALPHAS[i % len(so.ALPHAS)] for i in range(k)], base_out=base, **kw)
+
+
+def _launch_cases():
+    """(id, builder of Engine.merge_layer's arguments, {debug option: (value, value to restore)})"""
+    cases = []
+    for c in gi.LAYER_CASES:
+        for mode in ("reference_cpu", "exact"):
+            cases.append((f"{c['id']}-{mode}", (lambda cid=c["id"], mode=mode: dict(_golden_layer_args(cid), norm_mode=mode)), {}))
+    cases.append(("linear", lambda: _synthetic_args(*so.synthetic_layer(128, 256, 2, seed=61, sigmas=(0.004, 0.001)), b=0.5), {}))
+    for dt, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+        for mode in ("reference_cpu", "exact"):
+            cases.append((f"early_v0-{tag}-{mode}",
+                          (lambda dt=dt, mode=mode: dict(_early_v0_args(dt), norm_mode=mode)), {}))
+    for k in (5, 16):
+        cases.append((f"k{k}_32x64", lambda k=k: _synthetic_args(*random_layer((32, 64), k, 500 + k)), {}))
+    for k in (2, 3):
+        cases.append((f"rank3_k{k}", lambda k=k: _synthetic_args(*random_layer((3, 64, 128), k, 40 + k)), {}))
+        cases.append((f"rough_column_34x64_k{k}", lambda k=k: _synthetic_args(*random_layer((34, 64), k, 100 + k)), {}))
+    cases.append(("rough_row_64x34_k2", lambda: _synthetic_args(*random_layer((64, 34), 2, 300)), {}))
+    cases.append(("layer_k3-force_split2", lambda: _golden_layer_args("layer_k3"), {"force_split": (2, 0)}))
+    cases.append(("layer_k4-materialised", lambda: _golden_layer_args("layer_k4"), {"spectral_intermediates": (0, 1)}))
+    cases.append(("layer_k3-separate_spec_norm", lambda: _golden_layer_args("layer_k3"), {"fuse_spec_norm": (0, 1)}))
+    cases.append(("layer_k3-single_f2s", lambda: _golden_layer_args("layer_k3"), {"f2s_pair": (0, 1)}))
+    cases.append(("layer_k2-cand_cap7", lambda: _golden_layer_args("layer_k2"), {"cand_cap": (7, 0)}))
+    cases.append(("folded_8192x1024_k3", lambda: _synthetic_args(*so.synthetic_layer(8192, 1024, 3, seed=77)),
+                  {"fold_min_rows": (8192, 0)}))
+    return cases
+
+
+LAUNCH_CASES = _launch_cases()
+LAUNCH_CASE_IDS = [c[0] for c in LAUNCH_CASES]
+# 7-14 s in the work-group emulator, instant on the device: the emulator tier leaves it out
+LAUNCH_CASES_DEVICE_ONLY = ("folded_8192x1024_k3",)
+
+
+def record_layer_launches(engine, cid):
+    """one LAUNCH_CASES entry through Engine.merge_layer with profiling on -> {"launches": {kernel: count}, "steps": [...]}"""
+    _, build, options = [c for c in LAUNCH_CASES if c[0] == cid][0]
+    args = build()
+    fts, bases, alphas, base_out = (args.pop(key) for key in ("finetunes", "bases", "alphas", "base_out"))
+    for key, (value, _) in options.items():
+        engine.ctx.debug_option(key, value)
+    engine.ctx.profile(True)
+    engine.ctx.profile_reset()
+    try:
+        out, rep, delta = engine.merge_layer(fts, bases, alphas, base_out, want_delta=True, **args)
+        table = engine.ctx.profile_table()
+    finally:
+        engine.ctx.profile(False)
+        for key, (_, restore) in options.items():
+            engine.ctx.debug_option(key, restore)
+    return {"launches": {name: table[name][0] for name in sorted(table) if table[name][0]},
+            "steps": [[int(x), int(y), str(b)] for x, y, b in rep.steps]}
+
+
+def launch_golden(tier):
+    """the recorded tables for `tier` ("emulator" / "device"): the device's are the emulator's except where the file
+    holds an entry of its own"""
+    rec = json.loads(LAUNCH_GOLDEN.read_text())
+    table = dict(rec["emulator"])
+    if tier == "device":
+        table.update(rec.get("device", {}))
+    return table
+
+
+def check_layer_launches(engine, cid, tier):
+    want = launch_golden(tier)[cid]
+    got = record_layer_launches(engine, cid)
+    assert got["steps"] == want["steps"], (cid, got["steps"], want["steps"])
+    assert got["launches"] == want["launches"], (cid, got["launches"], want["launches"])
+
+
+def check_early_v0(engine, dtype, norm_mode):
+    """SMHIP_BRANCH_EARLY_V0: both fp32 norms below 1e-4 and comparable -> merged = a * (target_norm / ||a||), a the
+    larger-norm delta, without any transform after the row pass that took the norms"""
+    base, fts = early_v0_inputs(dtype)
+    engine.ctx.profile(True)
+    engine.ctx.profile_reset()
+    try:
+        out, rep, delta = engine.merge_layer(fts, [base, base], [0.5, 0.3], base, want_delta=True, norm_mode=norm_mode)
+        table = engine.ctx.profile_table()
+    finally:
+        engine.ctx.profile(False)
+    out, delta = out.cpu(), delta.cpu()
+    assert rep.branches == ["early_v0"]
+    norms = [torch.tensor(v, dtype=torch.float64).float() for v in rep.delta_norms]
+    ia = 0 if abs(float(norms[0])) >= abs(float(norms[1])) else 1
+    a = fts[ia].float() - base.float()
+    sc = (torch.tensor(rep.target_norm, dtype=torch.float64) / norms[ia].double()).float()
+    want = sc * a                                            # one fp32 multiplication per element
+    assert delta.dtype == torch.float32 and torch.equal(delta, want)
+    assert out.dtype == torch.bfloat16 and torch.equal(out, (base.float() + want).to(torch.bfloat16))
+    ran = {name for name, (count, _) in table.items() if count}
+    assert not ran & {"f2_cols_fwd", "blend", "i1_cols_inv", "i2_rows_inv"}, sorted(ran)
+
+
+def check_materialised_rank3_intermediate(engine):
+    """K = 3 on a rank-3 tensor with b = 0.5: round 1 leaves a spectral intermediate, round 2 takes the linear branch,
+    which works on spatial values - the intermediate is transformed back into an fp32 buffer of ALL its slices"""
+    shape = (3, 64, 128)
+    g = torch.Generator().manual_seed(21)
+    base = (torch.randn(shape, generator=g) * 0.02).to(torch.bfloat16)
+    fts = [(base.float() + torch.randn(shape, generator=g) * s_).to(torch.bfloat16) for s_ in (0.002, 0.002, 0.02)]
+    tr = so.LayerTrace()
+    ref = so.merge_layer(fts, [base] * 3, so.ALPHAS[:3], base, trace=tr, ratio_b=0.5)
+    out, rep, delta = engine.merge_layer(fts, [base] * 3, so.ALPHAS[:3], base, want_delta=True, b=0.5)
+    assert rep.branches == tr.branches == ["slerp", "carry", "linear"]
+    assert [(s[0], s[1]) for s in rep.steps] == tr.pairs
+    # the K = 3 bars of the rank-3 test: the reference's own chaos floor (DESIGN 6.2)
+    assert so.rel_err(out.cpu().float(), ref.float()) < 5e-3 and so.rel_err(delta.cpu(), tr.merged_delta) < 3e-2
+
+
+if __name__ == "__main__":
+    # the recorder: python -m tests.parity_checks [--device cuda] [--lib PATH] [--out FILE]
+    import argparse
+    ap = argparse.ArgumentParser(description="record the launch table and the steps of every LAUNCH_CASES entry")
+    ap.add_argument("--device", default="cpu", help="cpu: the work-group emulator; cuda: the HIP library")
+    ap.add_argument("--lib", default=None, help="another build of the library (default: the in-tree one)")
+    ap.add_argument("--out", default=str(LAUNCH_GOLDEN))
+    ns = ap.parse_args()
+    from shardmerge_amd._lib import SmhipLibrary
+    from shardmerge_amd.engine import Engine, get_engine
+    if ns.device == "cpu":
+        from tests.emul import loader
+        eng = Engine(lib=SmhipLibrary(ns.lib or loader.build()), device=torch.device("cpu"))
+    else:
+        eng = Engine(lib=SmhipLibrary(ns.lib), device=torch.device("cuda", 0)) if ns.lib else get_engine("cuda")
+    tier = "emulator" if ns.device == "cpu" else "device"
+    rec = {tier: {cid: record_layer_launches(eng, cid) for cid in LAUNCH_CASE_IDS}}
+    with open(ns.out, "w") as f:
+        json.dump(rec, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{len(rec[tier])} cases -> {ns.out}")

@@ -1052,3 +1052,21 @@ def test_row_pass_summarises_its_deltas_for_the_norm_emulation(engine, k, shape,
 def test_legacy_fourier_operator(engine, golden, case):
     """the reference's older FourierMerge class (shard/merge/fourier.py:35-205) behind the same boundary"""
     print(pc.check_legacy(engine, golden, case))
+
+
+# ---- the host sequence of the layer merge (Pipeline::merge_layer_once and its stages) -------------------------------
+@pytest.mark.parametrize("norm_mode", ["reference_cpu", "exact"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_early_out_branch_scales_the_larger_delta(engine, dtype, norm_mode):
+    pc.check_early_v0(engine, dtype, norm_mode)
+
+
+@pytest.mark.parametrize("cid", [c for c in pc.LAUNCH_CASE_IDS if c not in pc.LAUNCH_CASES_DEVICE_ONLY])
+def test_layer_launch_table_and_steps_are_the_recorded_ones(engine, cid):
+    """tests/golden/layer_launches.json, recorded before the sequence was split into stages (the folded column pass
+    takes 7-14 s in the emulator: the device tier runs it)"""
+    pc.check_layer_launches(engine, cid, "emulator")
+
+
+def test_spectral_intermediate_of_a_rank3_tensor_is_materialised_whole(engine):
+    pc.check_materialised_rank3_intermediate(engine)

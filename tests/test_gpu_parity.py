@@ -894,3 +894,18 @@ def test_1d_policies_through_the_one_launch_kernel_on_device(engine):
 def test_legacy_fourier_operator_on_device(engine, golden, case):
     """the reference's older FourierMerge class (shard/merge/fourier.py:35-205) behind the same boundary"""
     print(pc.check_legacy(engine, golden, case))
+
+
+@pytest.mark.parametrize("norm_mode", ["reference_cpu", "exact"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_early_out_branch_scales_the_larger_delta_on_device(engine, dtype, norm_mode):
+    pc.check_early_v0(engine, dtype, norm_mode)
+
+
+@pytest.mark.parametrize("cid", pc.LAUNCH_CASE_IDS)
+def test_layer_launch_table_and_steps_are_the_recorded_ones_on_device(engine, cid):
+    pc.check_layer_launches(engine, cid, "device")
+
+
+def test_spectral_intermediate_of_a_rank3_tensor_is_materialised_whole_on_device(engine):
+    pc.check_materialised_rank3_intermediate(engine)
