@@ -766,6 +766,85 @@ typedef struct {
 } smhip_adapter_desc;
 int smhip_adapter_apply(smhip_ctx* ctx, const smhip_adapter_desc* d, void* stream);
 
+/* ---- extract-lora: the other direction - a rank-r adapter (A [r x cols], B [rows x r], lora_alpha = r, scale 1) from one
+ *      2-D finetune and its base, D = fp32(finetune) - fp32(base) (one fp32 subtraction), B A ~ D.  A randomized subspace
+ *      iteration (Halko, Martinsson, Tropp 2011) with a Gram-space orthonormalisation: the small algebra runs on L x L
+ *      matrices, no tensor-sized matrix is factorised, and every value is defined step by step (csrc/sm_extract.hpp).
+ *      1 <= r <= 256, power iterations 0 <= q <= 4, L = min(ceil16(r + 8), ceil16(min(rows, cols))) <= 272.
+ *        1. Sketch.  Omega [cols x L] fp32: entry e = i * L + j is +1 when bit (e & 31) of word ((e >> 5) & 3) of the
+ *           Philox4x32-10 block with counter (lo32(e >> 7), hi32(e >> 7), 0, 0) under `key` is 0, else -1.
+ *        2. Y = D Omega [rows x L].
+ *        3. q times: Q = orth(Y); Z = D^T Q [cols x L]; Q' = orth(Z); Y = D Q'.
+ *        4. Q = orth(Y); C = D^T Q [cols x L].
+ *        5. G_C = gram(C) = V diag(lambda) V^T (eig below), sigma_i = sqrt(max(lambda_i, 0)).  With n = min(r, L):
+ *           rho = #{i < n : lambda_i > 1e-12 * lambda_0}.  s_i = sqrt(sigma_i);  Tb[k][i] = fp32(V[k][i] * s_i),
+ *           Ta[k][i] = fp32(V[k][i] / s_i) for i < rho, zero columns for rho <= i < r;  B = round(pmm(Q, Tb)),
+ *           A = round(pmm(C, Ta))^T, each rounded once into factor_dtype; rows / columns i >= rho are exact zeros.
+ *        6. orth(Y): G = gram(Y) = V diag(lambda) V^T; T[:, i] = fp32(V[:, i] / sqrt(lambda_i)) where
+ *           lambda_i > 1e-12 * lambda_0, else a zero column; Q = pmm(Y, T).  The kept rank of every call is reported.
+ *           (Symmetric orthonormalisation with truncation: a finetune that is a merged low-rank adapter has a singular Gram.)
+ *        7. delta_sq = ||D||_F^2: step 2 of smhip_geo_merge in delta space with k = 1.  share = (((0 + sigma_0^2) + ...
+ *           + sigma_{n-1}^2) / delta_sq with sigma_i^2 = max(lambda_i, 0), 0 when delta_sq == 0.
+ *      The products.  D X and D^T X run on v_mfma_f32_16x16x4_f32, bit for bit a k-ordered fp32 fma chain.  The reduction
+ *      index is cut into segments of 512; within a segment every output element is ONE fma chain from +0, the segments'
+ *      results are added in index order in fp32 (((0 + p_0) + p_1) + ...).  D^T X: the chain runs k = 512 s, 512 s + 1,
+ *      ..., padded with products of two +0 to a multiple of 4.  D X: inside every block of 32 consecutive k the chain
+ *      visits k0 + 8 g + j in the order j = 0..7 (outer), g = 0..3 (inner) - a lane's 16-byte load feeds one k of eight
+ *      instructions - and the segment is padded with products of two +0 to a multiple of 32.
+ *      gram(P) [L x L], fp64 (products of fp32 values are exact): rows in segments of 256; within a segment
+ *      s_c = the sum over rows c, c + 4, ... in order (c = 0..3), the segment's value (s_0 + s_2) + (s_1 + s_3); segments
+ *      added in index order.  pmm(P, T)[m][j] = the fp32 fma chain over k = 0..L-1 of P[m][k] * T[k][j] from +0.
+ *      eig: cyclic Jacobi in fp64, one rounded operation at a time, fixed sweep order, stopping rule, descending order and
+ *      sign convention as stated at xl_sym_eig in csrc/sm_extract.hpp.
+ *      A NaN or Inf in D reaches the first panel and fails the call with SMHIP_ERR_NONFINITE.  The workspace is the
+ *      caller's: DEVICE memory, 256-byte aligned, at least smhip_lora_extract_workspace(rows, cols, rank) bytes, else
+ *      SMHIP_ERR_ARG; as are a null pointer, r outside 1..256, q outside 0..4, a bad dtype, rows or cols < 1, a pointer
+ *      not aligned to its element.  Passes: 2 q + 2 delta products, each reading finetune and base once (L <= 80; one more
+ *      read per further 80 columns).  The stream is synchronised once per orth and once at the end.
+ *      Profile names and launches per call: "xl_fill" 1, "xl_delta_mm" and "xl_fold" 2 q + 2 each, "xl_gram" and
+ *      "xl_gram_fold" 2 q + 2 each, "xl_panel_mm" 2 q + 3, "geo_gram" and "geo_gram_fold" 1 each. ---- */
+#define SMHIP_EXTRACT_MAX_L 272
+#define SMHIP_EXTRACT_MAX_ORTH 9
+typedef struct {
+    const void* finetune; const void* base; /* device, in_dtype, [rows x cols] */
+    int in_dtype;
+    int rows, cols;
+    int rank;                               /* r, 1..256 */
+    int power_iters;                        /* q, 0..4 */
+    uint64_t key;
+    int factor_dtype;                       /* of A and B */
+    void* workspace; size_t workspace_bytes;
+} smhip_extract_desc;
+typedef struct {
+    int L;                                  /* the panel width */
+    int rho;                                /* the effective rank, <= min(r, L) */
+    int n_orth;                             /* orth calls: 2 q + 1 */
+    int orth_rank[SMHIP_EXTRACT_MAX_ORTH];  /* the rank each kept */
+    double sigma[SMHIP_EXTRACT_MAX_L];      /* sigma[0 .. L) */
+    double delta_sq;                        /* ||D||_F^2 */
+    double share;                           /* the captured energy share */
+} smhip_extract_report;
+size_t smhip_lora_extract_workspace(int rows, int cols, int rank);
+/* a_out [rank x cols], b_out [rows x rank]: device, factor_dtype.  report: HOST, required. */
+int smhip_lora_extract(smhip_ctx* ctx, const smhip_extract_desc* desc, void* a_out, void* b_out,
+                       smhip_extract_report* report, void* stream);
+/* TEST ABI, not part of the stable surface and free to change with the kernels: the probe of the primitives, one per
+ * call.  FILL y = the Rademacher panel [rows x L] under key; DELTA_MM
+ * y [M x L] = D X or D^T X (trans) with its fold, x [K x L]; GRAM y = gram(x), x [rows x L] fp32, y fp64 [L x L];
+ * PANEL_MM y = pmm(x [rows x L], t [L x L2]) in out_dtype, stored transposed when trans; x, t, y DEVICE.
+ * SYM_EIG: x HOST fp64 [L x L], y HOST fp64 [L + L * L]: lambda, then V row-major.  The workspace as above (for L). */
+enum { SMHIP_XL_FILL = 0, SMHIP_XL_DELTA_MM = 1, SMHIP_XL_GRAM = 2, SMHIP_XL_PANEL_MM = 3, SMHIP_XL_SYM_EIG = 4 };
+typedef struct {
+    int op;
+    const void* finetune; const void* base; int in_dtype;
+    int rows, cols, L, L2, trans;
+    uint64_t key;
+    const void* x; const float* t; void* y; int out_dtype;
+    void* workspace; size_t workspace_bytes;
+} smhip_xl_probe_desc;
+size_t smhip_xl_probe_workspace(int rows, int cols, int L);    /* DELTA_MM: (rows, cols, L); GRAM: (rows, 1, L) */
+int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* desc, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device

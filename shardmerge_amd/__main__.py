@@ -2,7 +2,8 @@
 through the alias package): the merge entry point of the reference CLI
 (shard/__main__.py:78-158) with the same arguments and options; and `analyze CONFIG`,
 the per-tensor task-vector statistics of the same config (merge/analyze.py), which
-writes no tensor."""
+writes no tensor; and `extract-lora MODEL --base BASE --rank R --out DIR`, a PEFT LoRA adapter
+from a full finetune (merge/extract.py)."""
 from __future__ import annotations
 
 import asyncio
@@ -118,6 +119,40 @@ def analyze_command(config_file: Path, densities, report: Optional[Path], device
         raise click.Abort()
     click.echo(format_tables(result))
     click.echo(f"report: {path}")
+
+
+@cli.command("extract-lora")
+@click.argument("model", type=str)
+@click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")
+@click.option("--rank", required=True, type=int, help="The adapter's rank r, 1..256")
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the adapter is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL and BASE live")
+@click.option("--modules", type=str, default=None, help="Only the modules whose name ends in one of these, comma-separated (q_proj,k_proj,...)")
+@click.option("--power-iters", type=int, default=2, help="Power iterations of the subspace iteration, 0..4")
+@click.option("--dtype", "dtype_name", type=click.Choice(["bf16", "fp16", "fp32"]), default="bf16", help="The factors' dtype")
+@click.option("--seed", type=int, default=0, help="Seed of the sketch")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def extract_lora_command(model: str, base: str, rank: int, out_dir: Path, storage_dir: Path, modules: Optional[str], power_iters: int,
+                         dtype_name: str, seed: int, device: str, verbose: bool):
+    """A PEFT LoRA adapter of rank RANK from the full finetune MODEL and its base: every Linear weight that differs.
+
+    DIR receives adapter_model.safetensors, adapter_config.json and extraction.json (per tensor the singular values, the
+    effective rank and the captured energy share); it can be named as a finetune_merge entry of `merge`.
+    """
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.extract import DTYPES, format_table, parse_modules, run_extraction
+        result = asyncio.run(run_extraction(model, base, rank, out_dir, storage_dir, parse_modules(modules), power_iters,
+                                            DTYPES[dtype_name], seed, device))
+    except Exception as exc:
+        logging.error(f"Error during extract-lora: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"adapter: {out_dir}")
 
 
 if __name__ == "__main__":

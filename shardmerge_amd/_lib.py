@@ -203,6 +203,31 @@ class StatsReport(C.Structure):
                 ("conflict", C.c_uint64 * STATS_MAX_DENSITIES)]
 
 
+EXTRACT_MAX_RANK, EXTRACT_MAX_L, EXTRACT_MAX_ORTH, EXTRACT_MAX_POWER = 256, 272, 9, 4
+XL_FILL, XL_DELTA_MM, XL_GRAM, XL_PANEL_MM, XL_SYM_EIG = range(5)
+
+
+class ExtractDesc(C.Structure):
+    """smhip_extract_desc"""
+    _fields_ = [("finetune", C.c_void_p), ("base", C.c_void_p), ("in_dtype", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
+                ("rank", C.c_int), ("power_iters", C.c_int), ("key", C.c_uint64), ("factor_dtype", C.c_int),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class ExtractReport(C.Structure):
+    """smhip_extract_report"""
+    _fields_ = [("L", C.c_int), ("rho", C.c_int), ("n_orth", C.c_int), ("orth_rank", C.c_int * EXTRACT_MAX_ORTH),
+                ("sigma", C.c_double * EXTRACT_MAX_L), ("delta_sq", C.c_double), ("share", C.c_double)]
+
+
+class XlProbeDesc(C.Structure):
+    """smhip_xl_probe_desc"""
+    _fields_ = [("op", C.c_int), ("finetune", C.c_void_p), ("base", C.c_void_p), ("in_dtype", C.c_int),
+                ("rows", C.c_int), ("cols", C.c_int), ("L", C.c_int), ("L2", C.c_int), ("trans", C.c_int),
+                ("key", C.c_uint64), ("x", C.c_void_p), ("t", C.c_void_p), ("y", C.c_void_p), ("out_dtype", C.c_int),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 DELLA_MAX_COLS = 32768          # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -271,6 +296,12 @@ class SmhipLibrary:
         d.smhip_div_scalar.argtypes = [P, P, I, C.c_size_t, C.c_float, P, P]
         d.smhip_lora_apply.argtypes = [P, P, I, I, I, P, P, I, I, C.c_float, P, P]
         d.smhip_adapter_apply.argtypes = [P, C.POINTER(AdapterDesc), P]
+        d.smhip_lora_extract_workspace.argtypes = [I, I, I]
+        d.smhip_lora_extract_workspace.restype = C.c_size_t
+        d.smhip_lora_extract.argtypes = [P, C.POINTER(ExtractDesc), P, P, C.POINTER(ExtractReport), P]
+        d.smhip_xl_probe_workspace.argtypes = [I, I, I]
+        d.smhip_xl_probe_workspace.restype = C.c_size_t
+        d.smhip_xl_probe.argtypes = [P, C.POINTER(XlProbeDesc), P]
         d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

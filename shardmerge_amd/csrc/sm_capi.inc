@@ -416,6 +416,57 @@ int smhip_adapter_apply(smhip_ctx* ctx, const smhip_adapter_desc* d, void* strea
                                            d->rank, d->scale, emb ? 1 : 0, d->magnitude, d->magnitude_dtype, d->out));
 }
 
+size_t smhip_lora_extract_workspace(int rows, int cols, int rank) {
+    if (rows < 1 || cols < 1 || rank < 1 || rank > smhip::XL_MAX_RANK) return 0;
+    return smhip::Pipeline<SM_BACKEND>::xl_layout(rows, cols, rank).total;
+}
+size_t smhip_xl_probe_workspace(int rows, int cols, int L) {
+    if (rows < 1 || cols < 1 || L < 16 || L > smhip::XL_MAX_L || L % 16) return 0;
+    return smhip::Pipeline<SM_BACKEND>::xl_layout_L(rows, cols, L, L).total;
+}
+
+int smhip_lora_extract(smhip_ctx* ctx, const smhip_extract_desc* d, void* a_out, void* b_out,
+                       smhip_extract_report* report, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("lora_extract: ") + what); };
+    if (!d || !report || !a_out || !b_out) return bad("null descriptor, report or output");
+    if (!d->finetune || !d->base) return bad("null model tensor");
+    if (d->rows < 1 || d->cols < 1) return bad("rows and cols must be >= 1");
+    if (d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32 || d->factor_dtype < SMHIP_BF16 || d->factor_dtype > SMHIP_F32)
+        return bad("bad dtype");
+    if (d->rank < 1 || d->rank > smhip::XL_MAX_RANK) return bad("rank out of range (1..256)");
+    if (d->power_iters < 0 || d->power_iters > smhip::XL_MAX_POWER) return bad("power_iters out of range (0..4)");
+    const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, fes = d->factor_dtype == SMHIP_F32 ? 4 : 2;
+    if ((uintptr_t)d->finetune % ies || (uintptr_t)d->base % ies || (uintptr_t)a_out % fes || (uintptr_t)b_out % fes)
+        return bad("a pointer is not aligned to its element size");
+    if ((size_t)d->rows * d->cols / smhip::GEO_SEG_ELEMS > (size_t)1 << 30) return bad("tensor too large");
+    if (!d->workspace || (uintptr_t)d->workspace % 256 || d->workspace_bytes < smhip_lora_extract_workspace(d->rows, d->cols, d->rank))
+        return bad("the workspace is null, not 256-byte aligned or too small (smhip_lora_extract_workspace)");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.lora_extract(*d, a_out, b_out, report));
+}
+
+int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* d, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("xl_probe: ") + what); };
+    if (!d || !d->y) return bad("null descriptor or output");
+    if (d->op < SMHIP_XL_FILL || d->op > SMHIP_XL_SYM_EIG) return bad("bad op");
+    if (d->op == SMHIP_XL_SYM_EIG) {
+        if (!d->x || d->L < 1 || d->L > smhip::XL_MAX_L) return bad("bad argument");
+    } else {
+        if (d->L < 16 || d->L > smhip::XL_MAX_L || d->L % 16 || d->rows < 1) return bad("bad shape");
+        if (d->op != SMHIP_XL_FILL && !d->x) return bad("null panel");
+        if (d->op == SMHIP_XL_DELTA_MM && (!d->finetune || !d->base || d->cols < 1 || d->in_dtype < SMHIP_BF16 || d->in_dtype > SMHIP_F32))
+            return bad("bad delta");
+        if (d->op == SMHIP_XL_GRAM && d->cols != 1) return bad("gram: cols must be 1");
+        if (d->op == SMHIP_XL_PANEL_MM && (!d->t || d->L2 < 1 || d->out_dtype < SMHIP_BF16 || d->out_dtype > SMHIP_F32))
+            return bad("bad panel product");
+        if ((d->op == SMHIP_XL_DELTA_MM || d->op == SMHIP_XL_GRAM) && (uintptr_t)d->workspace % 256) return bad("the workspace is not 256-byte aligned");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.xl_probe(*d));
+}
+
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
     SM_GUARD(ctx);
     if (!norm_out || (n > 0 && !x)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

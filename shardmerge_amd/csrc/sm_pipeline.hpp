@@ -25,6 +25,7 @@
 #include "sm_della.hpp"
 #include "sm_consensus.hpp"
 #include "sm_stats.hpp"
+#include "sm_extract.hpp"
 
 namespace smhip {
 
@@ -266,6 +267,14 @@ SM_KERNEL_TAG_LB(KStatsSelect, StatsSelectParams, "stats_select", k_stats_select
 SM_KERNEL_TAG_LB(KStatsPass, StatsPassParams, "stats_pass", k_stats_pass<STATS_REG_SMALL>(ex, p), GEO_THREADS, 2)
 SM_KERNEL_TAG_LB(KStatsPassAny, StatsPassParams, "stats_pass", k_stats_pass<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 1)
 SM_KERNEL_TAG_LB(KStatsFold, StatsFoldParams, "stats_fold", k_stats_fold(ex, p), 256, 4)
+// Low-rank extraction (sm_extract.hpp): the Rademacher panel, the delta product on fp32 MFMA (one wave per work-group: 40
+// or 160 accumulator registers) and its fold, the ordered fp64 Gram of a panel and its fold, panel x small matrix
+SM_KERNEL_TAG_LB(KXlFill, XlFillParams, "xl_fill", k_xl_fill(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlDeltaMm, XlMmParams, "xl_delta_mm", k_xl_delta_mm(ex, p), 64, 2)
+SM_KERNEL_TAG_LB(KXlFold, XlFoldParams, "xl_fold", k_xl_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlGram, XlGramParams, "xl_gram", k_xl_gram(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlGramFold, XlGramFoldParams, "xl_gram_fold", k_xl_gram_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlPanelMm, XlPanelMmParams, "xl_panel_mm", k_xl_panel_mm(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -296,7 +305,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny) \
     X(KDellaTable) X(KDellaRank) X(KDellaMerge) X(KConsensusMerge) X(KConsensusMergeAny)
 #define SM_SIDE_KERNELS_8(X) X(KStatsHist) X(KStatsSelect) X(KStatsPass) X(KStatsPassAny) X(KStatsFold)
-#define SM_SIDE_GROUPS 9         // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics
+#define SM_SIDE_KERNELS_9(X) X(KXlFill) X(KXlDeltaMm) X(KXlFold) X(KXlGram) X(KXlGramFold) X(KXlPanelMm)
+#define SM_SIDE_GROUPS 10        // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics; 9: the low-rank extraction
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2915,6 +2925,212 @@ class Pipeline {
         return SMHIP_OK;
     }
 
+    // ---- Low-rank extraction (sm_extract.hpp; the function is stated in shardmerge_hip.h, smhip_lora_extract).  The
+    // caller's workspace: two panels [max(rows, cols) x L] | the delta product's partials | the Gram's partials | G | T |
+    // the energy's partials | its sum and the flags ----
+    struct XlLayout {
+        int L;
+        size_t pan, part, gpart, G, T, epart, tail, total;      // byte offsets; pan: the size of one panel
+        size_t eseg;
+    };
+    static XlLayout xl_layout_L(int rows, int cols, int L_, int tcols) {
+        XlLayout y;
+        y.L = L_;
+        const size_t mx = (size_t)std::max(rows, cols), L = (size_t)y.L;
+        auto nseg = [](int K) { return (size_t)(K + XL_SEG - 1) / XL_SEG; };
+        y.pan = round_up(mx * L * 4, 256);
+        const size_t part = std::max(nseg(cols) * (size_t)rows, nseg(rows) * (size_t)cols) * L * 4;
+        const size_t gpart = (mx + XL_GSEG - 1) / XL_GSEG * L * L * 8;
+        y.eseg = ((size_t)rows * cols + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
+        y.part = 2 * y.pan;
+        y.gpart = y.part + round_up(part, 256);
+        y.G = y.gpart + round_up(gpart, 256);
+        y.T = y.G + round_up(L * L * 8, 256);
+        y.epart = y.T + round_up(2 * L * (size_t)std::max(y.L, tcols) * 4, 256);     // T [L x L], or Tb and Ta [L x r]
+        y.tail = y.epart + round_up(y.eseg * 8, 256);
+        y.total = y.tail + 256;
+        return y;
+    }
+    static XlLayout xl_layout(int rows, int cols, int rank) { return xl_layout_L(rows, cols, xl_panel_width(rows, cols, rank), rank); }
+    void xl_delta_mm(const void* ft, const void* base, int dtype, int rows, int cols, int trans, int L, const float* x,
+                     float* out, void* ws, const XlLayout& y) {
+        const int M = trans ? cols : rows, K = trans ? rows : cols, MT = trans ? XL_MT1 : XL_MT0;
+        XlMmParams m;
+        m.ft = ft; m.base = base; m.dtype = dtype; m.rows = rows; m.cols = cols; m.trans = trans; m.L = L; m.x = x;
+        m.part = (float*)((char*)ws + y.part);
+        m.nseg = (K + XL_SEG - 1) / XL_SEG; m.nchunk = (L / 16 + XL_CT - 1) / XL_CT;
+        m.vec = (aligned16(ft) && aligned16(base) && cols % 8 == 0) ? 1 : 0;
+        const size_t grid = (size_t)((M + MT - 1) / MT) * m.nseg * m.nchunk;
+        be.template launch<KXlDeltaMm>((int)grid, 64, 0, m, stream);
+        XlFoldParams f;
+        f.part = m.part; f.out = out; f.n = (size_t)M * L; f.nseg = m.nseg; f.flags = (uint32_t*)((char*)ws + y.tail) + 2;
+        be.template launch<KXlFold>((int)((f.n + 255) / 256), 256, 0, f, stream);
+    }
+    void xl_gram(const float* pan, int m, int L, void* ws, const XlLayout& y) {
+        XlGramParams g;
+        g.pan = pan; g.m = m; g.L = L; g.part = (double*)((char*)ws + y.gpart);
+        const int nseg = (m + XL_GSEG - 1) / XL_GSEG;
+        be.template launch<KXlGram>(nseg * xl_gram_tiles(L), 256, 256 * sizeof(double), g, stream);
+        XlGramFoldParams f;
+        f.part = g.part; f.G = (double*)((char*)ws + y.G); f.L = L; f.nseg = nseg;
+        be.template launch<KXlGramFold>((L * L + 255) / 256, 256, 0, f, stream);
+    }
+    void xl_panel_mm(const float* pan, int m, int L, const float* t, int L2, void* out, int out_dtype, int store_trans) {
+        XlPanelMmParams q;
+        q.pan = pan; q.t = t; q.out = out; q.m = m; q.L = L; q.L2 = L2; q.out_dtype = out_dtype; q.store_trans = store_trans;
+        be.template launch<KXlPanelMm>((int)(((size_t)m * L2 + 255) / 256), 256, 0, q, stream);
+    }
+    // reads the flags and the Gram back (one synchronisation) and decomposes it; false: the panel or its Gram held a NaN
+    // or an Inf (lam and V are then zeros)
+    bool xl_eig_readback(int L, void* ws, const XlLayout& y, std::vector<double>& lam, std::vector<double>& V) {
+        lam.assign(L, 0.0); V.assign((size_t)L * L, 0.0);
+        uint32_t flags[4];
+        be.d2h(flags, (char*)ws + y.tail, sizeof flags, stream);
+        if (!be.ok()) return true;                              // (reported by the caller as SMHIP_ERR_HIP)
+        if (flags[2]) return false;
+        std::vector<double> G((size_t)L * L);
+        be.d2h(G.data(), (char*)ws + y.G, G.size() * 8, stream);
+        if (!be.ok()) return true;
+        for (double v : G) if (!geo_finite(v)) return false;
+        xl_sym_eig(L, G.data(), lam.data(), V.data());
+        return true;
+    }
+    // Q = orth(Y) (step 6): y_pan -> q_pan, both [m x L]; returns the kept rank, -1: not finite
+    int xl_orth(const float* y_pan, float* q_pan, int m, int L, void* ws, const XlLayout& y) {
+        xl_gram(y_pan, m, L, ws, y);
+        std::vector<double> lam, V;
+        if (!xl_eig_readback(L, ws, y, lam, V)) return -1;
+        std::vector<float> T((size_t)L * L, 0.f);
+        const double cut = geo_dmul(1e-12, lam[0]);
+        int kept = 0;
+        for (int i = 0; i < L; ++i) {
+            if (!(lam[i] > cut)) continue;
+            ++kept;
+            const double s = geo_dsqrt(lam[i]);
+            for (int k = 0; k < L; ++k) T[(size_t)k * L + i] = (float)geo_ddiv(V[(size_t)k * L + i], s);
+        }
+        float* dT = (float*)((char*)ws + y.T);
+        be.h2d(dT, T.data(), T.size() * 4, stream);
+        xl_panel_mm(y_pan, m, L, dT, L, q_pan, DT_F32, 0);
+        return kept;
+    }
+    int lora_extract(const smhip_extract_desc& d, void* a_out, void* b_out, smhip_extract_report* rep) {
+        const XlLayout y = xl_layout(d.rows, d.cols, d.rank);
+        const int L = y.L, rows = d.rows, cols = d.cols, r = d.rank;
+        *rep = smhip_extract_report{};
+        rep->L = L;
+        void* ws = d.workspace;
+        float* p0 = (float*)ws;
+        float* p1 = (float*)((char*)ws + y.pan);
+        uint32_t* flags = (uint32_t*)((char*)ws + y.tail);          // [0..1]: geo_gram's, [2]: xl_fold's
+        double* E = (double*)((char*)ws + y.tail + 16);
+        be.memset(flags, 0, 32, stream);
+        auto nonfinite = [&]() { return fail(SMHIP_ERR_NONFINITE, "lora_extract: NaN or Inf in finetune - base"); };
+
+        // ||D||_F^2: geo_gram with k = 1, as delta_stats launches it
+        TiesInputs in;
+        in.k = 1; in.dtype = d.in_dtype; in.n = (size_t)rows * cols;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) { in.ft[i] = d.finetune; in.base[i] = d.base; }
+        in.aligned = (aligned16(d.finetune) && aligned16(d.base)) ? 1 : 0; in.shared_base = 1;
+        GeoGramParams g;
+        g.in = in; g.weight_space = 0; g.seg_len = GEO_SEG_ELEMS; g.nseg = y.eseg; g.seg_vec = in.aligned;
+        g.part = (double*)((char*)ws + y.epart); g.flags = flags;
+        be.template launch<KGeoGram>((int)y.eseg, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
+        GeoFoldParams gf;
+        gf.np = 1; gf.nseg = y.eseg; gf.part = g.part; gf.G = E;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, gf, stream);
+
+        XlFillParams f;
+        f.out = p0; f.n = (size_t)cols * L; f.key = d.key;
+        be.template launch<KXlFill>((int)(((f.n + 31) / 32 + 255) / 256), 256, 0, f, stream);
+        auto mm = [&](int trans, const float* x, float* out) {
+            xl_delta_mm(d.finetune, d.base, d.in_dtype, rows, cols, trans, L, x, out, ws, y);
+        };
+        mm(0, p0, p1);                                              // Y
+        int n_orth = 0;
+        auto orth = [&](int m) {                                    // p1 -> p0
+            const int kept = xl_orth(p1, p0, m, L, ws, y);
+            if (kept >= 0) rep->orth_rank[n_orth++] = kept;
+            return kept >= 0;
+        };
+        for (int it = 0; it < d.power_iters; ++it) {
+            if (!orth(rows)) return nonfinite();
+            mm(1, p0, p1);                                          // Z
+            if (!orth(cols)) return nonfinite();
+            mm(0, p0, p1);                                          // Y
+        }
+        if (!orth(rows)) return nonfinite();                        // Q in p0
+        mm(1, p0, p1);                                              // C in p1
+        rep->n_orth = n_orth;
+        xl_gram(p1, cols, L, ws, y);
+        std::vector<double> lam, V;
+        const bool finite = xl_eig_readback(L, ws, y, lam, V);
+        if (!be.ok()) return SMHIP_OK;
+        if (!finite) return nonfinite();
+        const int n = r < L ? r : L;
+        const double cut = geo_dmul(1e-12, lam[0]);
+        double sum = 0.0;
+        int rho = 0;
+        for (int i = 0; i < L; ++i) rep->sigma[i] = geo_dsqrt(lam[i] > 0.0 ? lam[i] : 0.0);
+        for (int i = 0; i < n; ++i) {
+            if (lam[i] > cut) ++rho;
+            sum = geo_dadd(sum, lam[i] > 0.0 ? lam[i] : 0.0);
+        }
+        rep->rho = rho;
+        std::vector<float> T((size_t)2 * L * r, 0.f);               // Tb, then Ta, [L x r] each
+        for (int i = 0; i < n; ++i) {
+            if (!(lam[i] > cut)) continue;
+            const double s = geo_dsqrt(rep->sigma[i]);
+            for (int k = 0; k < L; ++k) {
+                T[(size_t)k * r + i] = (float)geo_dmul(V[(size_t)k * L + i], s);
+                T[(size_t)L * r + (size_t)k * r + i] = (float)geo_ddiv(V[(size_t)k * L + i], s);
+            }
+        }
+        float* dT = (float*)((char*)ws + y.T);
+        be.h2d(dT, T.data(), T.size() * 4, stream);
+        xl_panel_mm(p0, rows, L, dT, r, b_out, d.factor_dtype, 0);
+        xl_panel_mm(p1, cols, L, dT + (size_t)L * r, r, a_out, d.factor_dtype, 1);
+        double e_host[1];
+        uint32_t fl[4];
+        be.d2h(e_host, E, 8, stream);
+        be.d2h(fl, flags, sizeof fl, stream);                       // the call's last synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (fl[0] || fl[2]) return nonfinite();
+        rep->delta_sq = e_host[0];
+        rep->share = e_host[0] > 0.0 ? geo_ddiv(sum, e_host[0]) : 0.0;
+        return SMHIP_OK;
+    }
+    int xl_probe(const smhip_xl_probe_desc& d) {
+        const int L = d.L;
+        if (d.op == SMHIP_XL_SYM_EIG) {
+            std::vector<double> a((const double*)d.x, (const double*)d.x + (size_t)L * L);
+            xl_sym_eig(L, a.data(), (double*)d.y, (double*)d.y + L);
+            return SMHIP_OK;
+        }
+        if (d.op == SMHIP_XL_FILL) {
+            XlFillParams f;
+            f.out = (float*)d.y; f.n = (size_t)d.rows * L; f.key = d.key;
+            be.template launch<KXlFill>((int)(((f.n + 31) / 32 + 255) / 256), 256, 0, f, stream);
+            return SMHIP_OK;
+        }
+        if (d.op == SMHIP_XL_PANEL_MM) {
+            xl_panel_mm((const float*)d.x, d.rows, L, d.t, d.L2, d.y, d.out_dtype, d.trans);
+            return SMHIP_OK;
+        }
+        const XlLayout y = xl_layout_L(d.rows, d.cols, L, L);
+        if (!d.workspace || d.workspace_bytes < y.total) return fail(SMHIP_ERR_ARG, "xl_probe: the workspace is too small");
+        if (d.op == SMHIP_XL_GRAM) {
+            xl_gram((const float*)d.x, d.rows, L, d.workspace, y);
+            std::vector<double> G((size_t)L * L);
+            be.d2h(G.data(), (char*)d.workspace + y.G, G.size() * 8, stream);
+            be.h2d(d.y, G.data(), G.size() * 8, stream);
+            return SMHIP_OK;
+        }
+        be.memset((char*)d.workspace + y.tail, 0, 32, stream);
+        xl_delta_mm(d.finetune, d.base, d.in_dtype, d.rows, d.cols, d.trans, L, (const float*)d.x, (float*)d.y, d.workspace, y);
+        be.sync(stream);
+        return SMHIP_OK;
+    }
     // ---- Breadcrumbs merge: two ranks per finetune (RadixState[k][2]), found in the same three histogram passes ----
     struct CrumbsReadback {
         float threshold_lo[TIES_MAX_MODELS], threshold_hi[TIES_MAX_MODELS];

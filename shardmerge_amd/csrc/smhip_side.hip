@@ -1,5 +1,5 @@
 // smhip_side.hip - explicit instantiation of one group of kernels, selected with -DSM_SIDE_GROUP=<g>
-// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics).
+// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction).
 #include "smhip_device.hpp"
 
 namespace smhip {
@@ -22,7 +22,9 @@ SM_INST(KF1B<DynPlan>) SM_INST(KI2B<DynPlan>)
 SM_SIDE_KERNELS_7(SM_INST)
 #elif SM_SIDE_GROUP == 8
 SM_SIDE_KERNELS_8(SM_INST)
+#elif SM_SIDE_GROUP == 9
+SM_SIDE_KERNELS_9(SM_INST)
 #else
-#error "SM_SIDE_GROUP must be 0..8"
+#error "SM_SIDE_GROUP must be 0..9"
 #endif
 }  // namespace smhip

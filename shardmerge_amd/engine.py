@@ -169,6 +169,25 @@ class DeltaStatsReport:
 
 
 @dataclass
+class LoraExtractReport:
+    rows: int = 0
+    cols: int = 0
+    rank: int = 0                                                    # r, as asked for
+    power_iters: int = 0
+    width: int = 0                                                   # L, the panel width
+    effective_rank: int = 0                                          # rho: factor rows / columns from here on are zeros
+    orth_ranks: List[int] = field(default_factory=list)              # the rank every orthonormalisation kept
+    sigma: List[float] = field(default_factory=list)                 # sigma[0 .. L), the singular values of the projection
+    delta_sq: float = 0.0                                            # ||finetune - base||_F^2 (fp64, ordered)
+    share: float = 0.0                                               # sum_{i < r} sigma_i^2 / delta_sq
+
+    @property
+    def residual_bound(self) -> float:
+        """the relative residual ||D - B A||_F / ||D||_F of the exact-arithmetic factors: sqrt(1 - share)"""
+        return math.sqrt(max(0.0, 1.0 - self.share))
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -419,6 +438,86 @@ class Engine:
         bs = self._dev(base).contiguous()
         av, bv = self._dev(a, fdtype).contiguous(), self._dev(b, fdtype).contiguous()
         return rows, cols, rank, bs, av, bv, fdtype
+
+    # -- extract-lora ------------------------------------------------------------------------
+    def lora_extract(self, finetune: torch.Tensor, base: torch.Tensor, rank: int, *, power_iters: int = 2,
+                     factor_dtype: Optional[torch.dtype] = None, seed: int = 0, name: str = ""):
+        """A rank-``rank`` adapter of one 2-D tensor: ``(A [rank, cols], B [rows, rank], LoraExtractReport)`` with
+        ``B @ A`` the randomized rank-``rank`` approximation of ``finetune - base`` (``smhip_lora_extract``; the function
+        is stated in include/shardmerge_hip.h), ``lora_alpha = rank``.  The sketch is keyed as the DARE mask is: the
+        first 8 bytes of ``sha256(f"{seed}\\n{name}")``.  factor_dtype: of A and B, default the inputs' dtype.  A NaN or
+        Inf in the delta raises ValueError naming ``name``."""
+        import hashlib
+        if finetune.ndim != 2 or finetune.shape != base.shape:
+            raise ValueError(f"lora_extract: two 2-D tensors of one shape expected, got {list(finetune.shape)} / {list(base.shape)}")
+        if isinstance(rank, bool) or not isinstance(rank, int) or not (1 <= rank <= _lib.EXTRACT_MAX_RANK):
+            raise ValueError(f"lora_extract: rank must be an integer in 1..{_lib.EXTRACT_MAX_RANK}, not {rank!r}")
+        if isinstance(power_iters, bool) or not isinstance(power_iters, int) or not (0 <= power_iters <= _lib.EXTRACT_MAX_POWER):
+            raise ValueError(f"lora_extract: power_iters must be an integer in 0..{_lib.EXTRACT_MAX_POWER}, not {power_iters!r}")
+        in_dtype = finetune.dtype if finetune.dtype == base.dtype and finetune.dtype in _DTYPE_CODE else torch.float32
+        factor_dtype = factor_dtype or in_dtype
+        if factor_dtype not in _DTYPE_CODE:
+            raise ValueError(f"lora_extract: factor dtype {factor_dtype}; bf16, f16 or f32 expected")
+        ft, bs = self._dev(finetune, in_dtype), self._dev(base, in_dtype)
+        rows, cols = ft.shape
+        a = torch.empty((rank, cols), dtype=factor_dtype, device=self.device)
+        b = torch.empty((rows, rank), dtype=factor_dtype, device=self.device)
+        ws = self._xl_workspace(int(self.lib.dll.smhip_lora_extract_workspace(rows, cols, rank)))
+        key = int.from_bytes(hashlib.sha256(f"{seed}\n{name}".encode()).digest()[:8], "little")
+        desc = _lib.ExtractDesc(ft.data_ptr(), bs.data_ptr(), _DTYPE_CODE[in_dtype], rows, cols, rank, power_iters, key,
+                                _DTYPE_CODE[factor_dtype], ws.data_ptr(), ws.numel())
+        rep = _lib.ExtractReport()
+        self._call(self.lib.dll.smhip_lora_extract(self.ctx.h, C.byref(desc), a.data_ptr(), b.data_ptr(), C.byref(rep),
+                                                   self._stream()), name or "tensor")
+        return a, b, LoraExtractReport(rows=rows, cols=cols, rank=rank, power_iters=power_iters, width=int(rep.L),
+                                       effective_rank=int(rep.rho), orth_ranks=[int(rep.orth_rank[i]) for i in range(rep.n_orth)],
+                                       sigma=[float(rep.sigma[i]) for i in range(rep.L)], delta_sq=float(rep.delta_sq),
+                                       share=float(rep.share))
+
+    def _xl_workspace(self, nbytes: int) -> torch.Tensor:
+        """a 256-byte aligned device buffer of at least nbytes (kept and regrown: the walk calls per tensor)"""
+        ws = getattr(self, "_xl_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            off = (-raw.data_ptr()) % 256
+            ws = self._xl_ws = raw[off:off + nbytes]
+        return ws
+
+    def xl_probe(self, op: int, *, rows: int, L: int, cols: int = 1, L2: int = 0, trans: int = 0, key: int = 0,
+                 finetune: Optional[torch.Tensor] = None, base: Optional[torch.Tensor] = None,
+                 x: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None,
+                 out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """one primitive of ``lora_extract`` (``smhip_xl_probe``; tests): the Rademacher panel, a delta product with its
+        fold, a panel's Gram, a panel product, or - on host arrays - the eigensolver (returns [L + L * L] fp64)"""
+        d = _lib.XlProbeDesc()
+        d.op, d.rows, d.cols, d.L, d.L2, d.trans, d.key, d.out_dtype = op, rows, cols, L, L2, trans, key, _DTYPE_CODE[out_dtype]
+        keep = []
+        if op == _lib.XL_SYM_EIG:
+            xin = x.to(torch.float64).cpu().contiguous()
+            y = torch.empty(L + L * L, dtype=torch.float64)
+            d.x, d.y = xin.data_ptr(), y.data_ptr()
+            self._call(self.lib.dll.smhip_xl_probe(self.ctx.h, C.byref(d), self._stream()))
+            return y
+        if op == _lib.XL_FILL:
+            y = torch.empty((rows, L), dtype=torch.float32, device=self.device)
+        elif op == _lib.XL_DELTA_MM:
+            keep = [self._dev(finetune), self._dev(base), self._dev(x, torch.float32)]
+            d.finetune, d.base, d.in_dtype, d.x = keep[0].data_ptr(), keep[1].data_ptr(), _DTYPE_CODE[keep[0].dtype], keep[2].data_ptr()
+            y = torch.empty((cols if trans else rows, L), dtype=torch.float32, device=self.device)
+        elif op == _lib.XL_GRAM:
+            keep = [self._dev(x, torch.float32)]
+            d.x = keep[0].data_ptr()
+            y = torch.empty((L, L), dtype=torch.float64, device=self.device)
+        else:
+            keep = [self._dev(x, torch.float32), self._dev(t, torch.float32)]
+            d.x, d.t = keep[0].data_ptr(), keep[1].data_ptr()
+            y = torch.empty((L2, rows) if trans else (rows, L2), dtype=out_dtype, device=self.device)
+        if op in (_lib.XL_DELTA_MM, _lib.XL_GRAM):
+            ws = self._xl_workspace(int(self.lib.dll.smhip_xl_probe_workspace(rows, cols, L)))
+            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+        d.y = y.data_ptr()
+        self._call(self.lib.dll.smhip_xl_probe(self.ctx.h, C.byref(d), self._stream()))
+        return y
 
     # -- N3: AdditionMerge / TaskAdditionMerge ---------------------------------------------
     def addition_merge(self, finetunes: Sequence[torch.Tensor], base: torch.Tensor, sign_agreement: bool = False) -> torch.Tensor:
