@@ -658,6 +658,79 @@ typedef struct {
 int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* desc, void* out, float* delta_out,
                           smhip_consensus_report* report, void* stream);
 
+/* ---- Pairwise fusion: ONE finetune grafted onto a base, element by element (the operators arcee_fusion and nearswap;
+ *      both after mergekit's methods of those names, as recalled - PAPERS.md).  ARCEE takes only the updates an importance
+ *      score marks as outliers, NEARSWAP limits how far any weight may move.  The reference has no such operator; this
+ *      section IS their definition.  One tensor of n elements viewed as R x C: R = rows, C = n / rows (the caller passes
+ *      the last dimension as C; a 1-D tensor is one row).  k must be 1 and alpha[0] is not read: the operators take no
+ *      weight.  Both modes: d = fp32(finetune) - fp32(base).
+ *      NEARSWAP.  t32 = fp32(t), t > 0 and finite, else SMHIP_ERR_ARG.  M = min(max(d, -t32), t32) (d where
+ *      |d| <= t32, +-t32 beyond).  out = round_to(base_out_dtype, fp32(base_out) + M), delta_out = M.  clipped counts
+ *      |d| > t32.  A NaN or Inf in d fails the call with SMHIP_ERR_NONFINITE.  One kernel, one pass: 4 tensor passes.
+ *      mergekit writes lweight = clamp(t / |v0 - v1|, 0, 1) and interpolates; in exact arithmetic that is this clamp.
+ *      ARCEE.  A NaN or Inf in the finetune or the base fails the call (the weights themselves enter the softmax), as
+ *      does one in d.
+ *        1. Row KL, in fp64: every operation below is ONE rounded IEEE operation, never an fma.  For row r, with
+ *           x = fp32(finetune), y = fp32(base): mx = max_j x_j, my = max_j y_j, a_j = fp64(x_j) - fp64(mx),
+ *           b_j = fp64(y_j) - fp64(my), ea_j = sm_exp(a_j), eb_j = sm_exp(b_j), S_a = sum ea_j, S_b = sum eb_j,
+ *           U = sum ea_j * (a_j - b_j).  The three sums run in the row order of smhip_geo_merge step 2: octet o of the
+ *           row (elements 8 o .. 8 o + 7 from the row's start) goes to lane o % 256, each lane adds in ascending index
+ *           from +0, the 256 lanes are reduced by the binary tree p[t] += p[t + s], s = 128 .. 1.
+ *           kl = U / S_a - (sm_log(S_a) - sm_log(S_b)); kappa_r = fp32(kl) where kl > 0, +0 elsewhere.
+ *           This is KL(softmax(finetune row) || softmax(base row)) written through log-softmax: nothing takes the log of
+ *           a probability, so the +1e-8 guard of mergekit's formula is not needed (and not part of this definition).
+ *           A row equal in finetune and base gives kappa = 0 EXACTLY: every a_j - b_j is +0, so U = +0 and U / S_a = +0;
+ *           S_a and S_b are the same bits, so the difference of their logarithms is +0.
+ *        2. Score: s_e = fl32(|d_e| * kappa_row(e)), one fp32 multiplication.
+ *        3. Quartiles: rho_q = floor(q (n - 1)) for q = 1/4, 1/2, 3/4; Q1, Q2, Q3 are the rho_q-th smallest scores
+ *           (0-based), exact: no interpolation, no subsampling.  thr = fl32(Q2 + fl32(fp32(iqr_mult) * fl32(Q3 - Q1))).
+ *        4. Gate: an element is selected iff s_e > thr, an IEEE fp32 comparison - strict, so ties with the threshold all
+ *           go the same way and the result does not depend on order.  M = d where selected, +0 elsewhere; out and
+ *           delta_out as in NEARSWAP.
+ *      sm_exp and sm_log (csrc/sm_fusion.hpp) are DEFINED there: sm_exp on (-inf, 0], +0 below -45 (e^-45 < 2^-64
+ *      against sums that are at least 1); sm_log on [1, 2^40).  Both: an argument reduction with a two-part ln 2, a Horner
+ *      evaluation of a truncated Taylor series, the scale by a power of two, one rounded operation at a time - the
+ *      host, the device, the emulator and a numpy restatement give the same bits; smhip_fusion_fn exposes them.
+ *      Every value is one correctly rounded operation, an exact order statistic or an integer count in a stated order:
+ *      the result is defined bit for bit.  Identities: NEARSWAP with t >= max |d|, and ARCEE with thr < 0, equal
+ *      smhip_dare_merge (sign_election 0, normalize 1) at density 1 with alpha 1 (a delta of -0, which that sum turns into +0,
+ *      aside); ARCEE's selected sets are nested in
+ *      iqr_mult when Q3 >= Q1.  Passes (ARCEE): "fusion_rowkl" once (a work-group per row; 2 tensor passes, the second
+ *      read of a row from L2), "fusion_hist" / "fusion_select" three times (all three ranks in the same 11 + 10 + 10 bit
+ *      levels, the scores formed on the fly: 3 x 2), "fusion_merge" once (4): 12 tensor passes.  Counters are integers
+ *      (LDS, then one global atomic per work-group), no floating-point atomics; the stream is synchronised once, at
+ *      the end.  Aliasing, alignment, n == 0 (a no-op, the report all zeros), dtypes and the size limit: the rules of
+ *      smhip_ties_merge.  SMHIP_ERR_ARG: k != 1, a bad mode, rows < 1 or not dividing n, t <= 0 or not finite
+ *      (NEARSWAP), iqr_mult not finite (ARCEE), a null pointer, kl_out misaligned or overlapping an output. ---- */
+enum { SMHIP_FUSION_ARCEE = 0, SMHIP_FUSION_NEARSWAP = 1 };
+typedef struct {
+    int k;                                  /* must be 1 */
+    const void* finetune[SMHIP_MAX_MODELS]; /* [0]: device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* [0]: device, in_dtype */
+    double alpha[SMHIP_MAX_MODELS];         /* not read */
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, the finetune and the base */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    int mode;                               /* SMHIP_FUSION_ARCEE / SMHIP_FUSION_NEARSWAP */
+    size_t rows;                            /* R: C = n / rows is the row of step 1 */
+    double iqr_mult;                        /* ARCEE */
+    double t;                               /* NEARSWAP */
+    float* kl_out;                          /* ARCEE, optional: device float [rows], kappa_r */
+} smhip_fusion_desc;
+typedef struct {
+    float q1, q2, q3, threshold;            /* ARCEE */
+    uint64_t selected;                      /* ARCEE: elements with s_e > thr */
+    uint64_t clipped;                       /* NEARSWAP: elements with |d| > t32 */
+    float kl_min, kl_max;                   /* ARCEE: over the rows */
+} smhip_fusion_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], M.  report (optional): HOST. */
+int smhip_fusion_merge(smhip_ctx* ctx, const smhip_fusion_desc* desc, void* out, float* delta_out,
+                       smhip_fusion_report* report, void* stream);
+/* y[i] = sm_exp(x[i]) (op SMHIP_FUSION_EXP) or sm_log(x[i]) (SMHIP_FUSION_LOG) for n doubles.  on_device = 0: x and y
+ * are HOST arrays, evaluated on the host; 1: DEVICE arrays, evaluated by a kernel ("fusion_fn") on the stream. */
+enum { SMHIP_FUSION_EXP = 0, SMHIP_FUSION_LOG = 1 };
+int smhip_fusion_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream);
+
 /* ---- Task-vector statistics: what the knobs of the delta merges (density above all) would do to THESE finetunes,
  *      before a merge has run.  No output tensor: for one tensor of n elements (any shape, flat), finetunes i = 0..k-1
  *      (1 <= k <= 16) and candidate densities rho_q, q = 0..m-1 (1 <= m <= SMHIP_STATS_MAX_DENSITIES, each in (0, 1],

@@ -180,6 +180,23 @@ class ConsensusReport(C.Structure):
                 ("masked", C.c_uint64 * MAX_MODELS), ("agree", C.c_uint64 * (MAX_MODELS + 1)), ("selected", C.c_uint64)]
 
 
+FUSION_ARCEE, FUSION_NEARSWAP = 0, 1
+FUSION_EXP, FUSION_LOG = 0, 1
+FUSION_EXP_CUTOFF = -45.0       # sm_exp is +0 below it (csrc/sm_fusion.hpp)
+
+
+class FusionDesc(C.Structure):
+    """smhip_fusion_desc: the leading fields of the delta merges (k must be 1), then mode, rows, iqr_mult, t, kl_out"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("mode", C.c_int), ("rows", C.c_size_t), ("iqr_mult", C.c_double), ("t", C.c_double),
+                                         ("kl_out", C.c_void_p)]
+
+
+class FusionReport(C.Structure):
+    """smhip_fusion_report"""
+    _fields_ = [("q1", C.c_float), ("q2", C.c_float), ("q3", C.c_float), ("threshold", C.c_float),
+                ("selected", C.c_uint64), ("clipped", C.c_uint64), ("kl_min", C.c_float), ("kl_max", C.c_float)]
+
+
 STATS_MAX_DENSITIES = 4         # SMHIP_STATS_MAX_DENSITIES
 
 
@@ -288,6 +305,8 @@ class SmhipLibrary:
         d.smhip_sce_merge.argtypes = [P, C.POINTER(SceDesc), P, P, C.POINTER(SceReport), P]
         d.smhip_della_merge.argtypes = [P, C.POINTER(DellaDesc), P, P, P, C.POINTER(DellaReport), P]
         d.smhip_consensus_merge.argtypes = [P, C.POINTER(ConsensusDesc), P, P, C.POINTER(ConsensusReport), P]
+        d.smhip_fusion_merge.argtypes = [P, C.POINTER(FusionDesc), P, P, C.POINTER(FusionReport), P]
+        d.smhip_fusion_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
         d.smhip_delta_stats.argtypes = [P, C.POINTER(StatsDesc), C.POINTER(StatsReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]

@@ -98,6 +98,19 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # karcher_max_iter: 10    #   an integer in 1..100: iterations at most (two entries need one)
       # karcher_tol: 1.0e-5     #   0 <= karcher_tol < 1: the iteration stops when its step on the sphere is shorter
       # sphere_row_wise: 0      #   1: one mean per ROW of each tensor (multislerp with two entries: row-wise nuslerp), 0: per tensor
+                                # | arcee_fusion | nearswap (the pairwise operators, after mergekit's methods of those names; no
+                                #   counterpart in the reference): ONE model is grafted onto its base, element by element, so
+                                #   every block tensor must be covered by EXACTLY ONE finetune_merge entry (entries with
+                                #   disjoint layer windows fuse different models into different layers; two entries on one
+                                #   layer are an error before anything is written).  They take no weight: an entry alpha other
+                                #   than 1 is rejected.  arcee_fusion: a row of a tensor (its last dimension) is scored by the
+                                #   KL divergence of its softmax in the model from its softmax in the base, an element by
+                                #   |delta| times its row's score, and the delta is taken only where that exceeds
+                                #   median + fusion_iqr * (Q3 - Q1) of the tensor's scores.  nearswap: the delta is clamped to
+                                #   [-nearswap_t, nearswap_t].  The spectral keys, norm_mode, task_add_models and every other
+                                #   family's keys are rejected; keys:
+      # fusion_iqr: 1.5         #   operator arcee_fusion only: -1e6 <= fusion_iqr <= 1e6 (mergekit's 1.5)
+      # nearswap_t: 0.001       #   operator nearswap only, REQUIRED: 0 < nearswap_t <= 1e6
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -125,7 +138,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp")
+             "karcher", "multislerp", "arcee_fusion", "nearswap")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -145,6 +158,8 @@ CONSENSUS_OPERATORS = ("consensus_ta", "consensus_ties")
 CONSENSUS_OPTION_DEFAULTS = {"density": 0.2, "mask_lambda": 0.4, "consensus_k": 2, "consensus_lambda": 1.0, "consensus_normalize": 1.0}
 SPHERE_OPERATORS = ("karcher", "multislerp")             # Karcher means: slerp / nuslerp for any number of entries
 SPHERE_OPTION_DEFAULTS = {"karcher_max_iter": 10, "karcher_tol": 1e-5, "sphere_row_wise": 0.0}
+FUSION_OPERATORS = ("arcee_fusion", "nearswap")          # the pairwise family: one model onto its base, no weights
+FUSION_OPTION_DEFAULTS = {"fusion_iqr": 1.5, "nearswap_t": None}      # nearswap_t has no default: it is required
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -187,12 +202,13 @@ class _OptionFamily:
     """One family's merge_options.  rules: key -> "flag" (0 or 1), "seed" (an exact integer in [0, 2^63)), ("int", lo, hi)
     (an exact integer in lo..hi, kept an int) or a range (lo, hi, brackets[, the message's own wording of the range]).
     earlier: what the message says after a key of an earlier family, by that family's first operator.  only: a key that
-    not every operator of the family takes.  check: a rule over several keys."""
+    not every operator of the family takes.  required: keys that have no default.  check: a rule over several keys."""
     operators: tuple
     defaults: Dict[str, Union[int, float]]
     rules: Dict[str, Any]
     earlier: Dict[str, str] = field(default_factory=dict)
     only: Dict[str, tuple] = field(default_factory=dict)        # key -> the operators of the family that take it (default: all)
+    required: tuple = ()                                        # keys without a default: the operators that take them must give them
     check: Optional[Callable[[Dict[str, Any]], None]] = None
 
 
@@ -239,6 +255,15 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "sce": "(its weights are the alphas, not energies)",
                            "della": "(it drops nothing at random)",
                            "consensus_ta": "(it masks nothing)"}),
+    _OptionFamily(FUSION_OPERATORS, FUSION_OPTION_DEFAULTS,
+                  {"fusion_iqr": (-1e6, 1e6, "[]"), "nearswap_t": (0, 1e6, "(]")},
+                  earlier={"ties": "(it trims by an importance score or clamps, and takes no weight)", "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it trims by an importance score or clamps)",
+                           "model_stock": "(it fuses one model, row scores come from the softmax)",
+                           "sce": "(it fuses one model: nothing varies across finetunes)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it fuses one model: no masks to agree)"},
+                  only={"fusion_iqr": ("arcee_fusion",), "nearswap_t": ("nearswap",)}, required=("nearswap_t",)),
 )
 
 
@@ -267,6 +292,9 @@ def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], o
         raise click.BadParameter(f"merge_options.norm_mode is an option of the spectral operators; operator {operator!r} takes no norm")
     for e in _OPTION_FAMILIES[:own]:
         for key in sorted((set(opts) & set(e.defaults)) - set(fam.defaults)):
+            if e.operators[0] not in fam.earlier:          # no remark of this family on that one: the plain wording
+                raise click.BadParameter(f"merge_options.{key} is accepted only with operator: {_one_of(e.only.get(key, e.operators))} "
+                                         f"(operator {operator!r} would ignore it)")
             raise click.BadParameter(f"merge_options.{key} is an option of operator{'s' if len(e.operators) > 1 else ''} {' / '.join(e.operators)}; "
                                      f"operator {operator!r} would ignore it {fam.earlier[e.operators[0]]}")
     for key in sorted(k for k in set(opts) & set(fam.only) if operator not in fam.only[k]):
@@ -298,6 +326,9 @@ def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], o
             if not number or not (lo <= float(value) <= hi) or (left == "(" and value == lo) or (right == ")" and value == hi):
                 raise click.BadParameter(f"merge_options.{key} must be a number in {text}")
         out[key] = float(value)
+    for key in fam.required:
+        if operator in fam.only.get(key, fam.operators) and key not in opts:
+            raise click.BadParameter(f"merge_options.{key} is required with operator {operator} (it has no default)")
     if fam.check:
         fam.check(opts)
     return out
@@ -427,6 +458,11 @@ class MergeConfig:
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
                 raise click.BadParameter(f"operator sce needs finetune_merge alphas >= 0 with a sum > 0 (an alpha is a prior on the "
                                          f"finetune's weight), not {alphas}")
+        if operator in FUSION_OPERATORS:
+            for m in raw["finetune_merge"]:
+                if isinstance(m.alpha, bool) or not isinstance(m.alpha, (int, float)) or m.alpha != 1:
+                    raise click.BadParameter(f"operator {operator} takes no weight: finetune_merge alpha of {m.model} must be 1 "
+                                             f"(or absent), not {m.alpha!r} - the operator would ignore it")
         if family_options is not None:
             raw["merge_options"] = family_options
             return cls(**raw)

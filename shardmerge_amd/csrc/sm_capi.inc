@@ -26,7 +26,7 @@ struct smhip_ctx {
 // the same leading fields (k .. normalize), hence the template.  `op` names the entry point in the messages.
 // smhip_geo_merge shares all of it but the scalars (`scalars`: the operator's own checks, after k and the dtypes) and,
 // in weight space, the bases (`need_base` = false: they are not read and may be NULL); smhip_sce_merge, smhip_della_merge and
-// smhip_consensus_merge all but the scalars.
+// smhip_consensus_merge all but the scalars; smhip_fusion_merge too (k == 1).
 template <class Desc, class Scalars>
 static int delta_tensor_check(smhip_ctx* ctx, const char* op, const Desc* d, const void* out, const float* delta_out,
                               bool need_base, Scalars scalars) {
@@ -333,6 +333,43 @@ int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* d, void* o
         return rc;
     ctx->pipe.stream = stream;
     SM_FINISH(ctx, ctx->pipe.consensus_merge(*d, out, delta_out, report));
+}
+
+int smhip_fusion_merge(smhip_ctx* ctx, const smhip_fusion_desc* d, void* out, float* delta_out, smhip_fusion_report* report,
+                       void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "fusion_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (d->k != 1) return "k must be 1 (one finetune and its base)";
+            if (d->mode != SMHIP_FUSION_ARCEE && d->mode != SMHIP_FUSION_NEARSWAP) return "bad mode";
+            if (d->mode == SMHIP_FUSION_NEARSWAP && !(d->t > 0.0 && std::isfinite(d->t) && (float)d->t > 0.f && std::isfinite((float)d->t)))
+                return "t must be > 0 and finite";
+            if (d->mode == SMHIP_FUSION_ARCEE && !std::isfinite((float)d->iqr_mult)) return "iqr_mult is not finite";
+            return nullptr;
+        }))
+        return rc;
+    if (d->n > 0) {
+        if (d->rows < 1 || d->n % d->rows) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_merge: rows must divide n");
+        if (d->mode == SMHIP_FUSION_ARCEE && d->kl_out) {
+            const uintptr_t k0 = (uintptr_t)d->kl_out, k1 = k0 + d->rows * 4;
+            const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
+            auto hits = [&](const void* p, size_t bytes) { return p && (uintptr_t)p < k1 && k0 < (uintptr_t)p + bytes; };
+            if (k0 % 4 || hits(out, d->n * oes) || hits(delta_out, d->n * 4) || hits(d->base_out, d->n * oes) ||
+                hits(d->finetune[0], d->n * ies) || hits(d->base[0], d->n * ies))
+                return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_merge: kl_out is misaligned or overlaps another tensor");
+        }
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.fusion_merge(*d, out, delta_out, report));
+}
+
+int smhip_fusion_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream) {
+    SM_GUARD(ctx);
+    if (op != SMHIP_FUSION_EXP && op != SMHIP_FUSION_LOG) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_fn: bad op");
+    if (n > 0 && (!x || !y)) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_fn: null array");
+    if ((uintptr_t)x % 8 || (uintptr_t)y % 8) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_fn: a pointer is not aligned to 8 bytes");
+    if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_fn: array too large");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.fusion_fn_array(op, x, y, n, on_device != 0));
 }
 
 int smhip_delta_stats(smhip_ctx* ctx, const smhip_stats_desc* d, smhip_stats_report* report, void* stream) {

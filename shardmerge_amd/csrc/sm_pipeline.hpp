@@ -26,6 +26,7 @@
 #include "sm_consensus.hpp"
 #include "sm_stats.hpp"
 #include "sm_extract.hpp"
+#include "sm_fusion.hpp"
 
 namespace smhip {
 
@@ -275,6 +276,15 @@ SM_KERNEL_TAG_LB(KXlFold, XlFoldParams, "xl_fold", k_xl_fold(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KXlGram, XlGramParams, "xl_gram", k_xl_gram(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KXlGramFold, XlGramFoldParams, "xl_gram_fold", k_xl_gram_fold(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KXlPanelMm, XlPanelMmParams, "xl_panel_mm", k_xl_panel_mm(ex, p), 256, 4)
+// Pairwise fusion (sm_fusion.hpp): the row KL through sm_exp / sm_log (54 VGPRs: the fp64
+// Horner chains run one element after another), the three-rank radix level over the score stream and its scan, the
+// fused gate pass - which with FUS_NEARSWAP is the whole of nearswap - and the probe of the two defined functions
+SM_KERNEL_TAG_LB(KFusionRowKl, FusionRowKlParams, "fusion_rowkl", k_fusion_rowkl(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KFusionHist, FusionHistParams, "fusion_hist", k_fusion_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KFusionSelect, FusionSelectParams, "fusion_select", k_fusion_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KFusionMergeArcee, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_ARCEE>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KFusionMergeNear, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_NEARSWAP>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KFusionFn, FusionFnParams, "fusion_fn", k_fusion_fn(ex, p), 256, 4)
 // (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
 SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
@@ -306,7 +316,8 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KDellaTable) X(KDellaRank) X(KDellaMerge) X(KConsensusMerge) X(KConsensusMergeAny)
 #define SM_SIDE_KERNELS_8(X) X(KStatsHist) X(KStatsSelect) X(KStatsPass) X(KStatsPassAny) X(KStatsFold)
 #define SM_SIDE_KERNELS_9(X) X(KXlFill) X(KXlDeltaMm) X(KXlFold) X(KXlGram) X(KXlGramFold) X(KXlPanelMm)
-#define SM_SIDE_GROUPS 10        // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics; 9: the low-rank extraction
+#define SM_SIDE_KERNELS_10(X) X(KFusionRowKl) X(KFusionHist) X(KFusionSelect) X(KFusionMergeArcee) X(KFusionMergeNear) X(KFusionFn)
+#define SM_SIDE_GROUPS 11        // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics; 9: the low-rank extraction; 10: the pairwise fusion
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {
@@ -2922,6 +2933,106 @@ class Pipeline {
             for (int cc = 0; cc <= k; ++cc) rep->cover[q][cc] = c[STATS_COVER + q * (TIES_MAX_MODELS + 1) + cc];
             rep->conflict[q] = c[STATS_CONFLICT + q];
         }
+        return SMHIP_OK;
+    }
+
+    // ---- Pairwise fusion (sm_fusion.hpp; the function is stated in shardmerge_hip.h, smhip_fusion_merge).  NEARSWAP: one
+    // kernel, the workspace is FusionWork alone.  ARCEE: the row KL, the three levels of the three-rank select over the
+    // score stream, the gate pass, ONE readback.  Workspace (the TIES buffer): the histograms [3][STATS_HIST_STRIDE] |
+    // FusionWork | kappa [R] when the caller gives no kl_out ----
+    struct FusionReadback {
+        float tau[STATS_MAX_RANKS * TIES_MAX_MODELS];                  // stats_select's layout: Q_q at [q * TIES_MAX_MODELS]
+        unsigned long long kept[STATS_MAX_RANKS * TIES_MAX_MODELS];    // (stats_select's kept counts: not reported)
+        unsigned long long count;                                      // selected / clipped
+        float threshold;
+        uint32_t kl_minmax[2];
+        uint32_t flags[2];
+    };
+    struct FusionWork { RadixState state[STATS_MAX_RANKS]; FusionReadback rb; };
+    int fusion_nonfinite(uint32_t flags) {
+        std::string which;
+        if (flags & FUS_BAD_FT) which = "the finetune";
+        if (flags & FUS_BAD_BASE) which += std::string(which.empty() ? "" : " and ") + "the base";
+        if (which.empty()) which = "finetune - base";
+        return fail(SMHIP_ERR_NONFINITE, "fusion_merge: NaN or Inf in " + which);
+    }
+    int fusion_merge(const smhip_fusion_desc& d, void* out, float* delta_out, smhip_fusion_report* rep) {
+        const bool arcee = d.mode == SMHIP_FUSION_ARCEE;
+        if (rep) *rep = smhip_fusion_report{};
+        if (d.n == 0) return SMHIP_OK;
+        const size_t n = d.n, R = d.rows, C = n / R;
+        if (arcee && R > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "fusion_merge: too many rows");
+        FusionMergeParams m;
+        delta_inputs(d, out, delta_out, false, m);
+        m.C = C; m.kl = nullptr; m.quart = nullptr; m.threshold = nullptr;
+        m.iqr_mult = (float)d.iqr_mult; m.t = (float)d.t;
+        const int grid = stream_grid((n + 7) / 8, 256, m.chunks);
+        const size_t merge_lds = (LDS_SCRATCH_FLOATS + 4) * 4;
+        FusionWork* w;
+        int rc;
+        if (!arcee) {
+            if ((rc = ensure(ties_, sizeof(FusionWork)))) return rc;
+            be.memset(ties_.p, 0, sizeof(FusionWork), stream);
+            w = (FusionWork*)ties_.p;
+            m.count = &w->rb.count; m.flags = w->rb.flags;
+            be.template launch<KFusionMergeNear>(grid, 256, merge_lds, m, stream);
+        } else {
+            size_t off_kl = 0;
+            if ((rc = select_workspace(2, w, d.kl_out ? 0 : R * sizeof(float), &off_kl))) return rc;
+            float* kl = d.kl_out ? d.kl_out : (float*)((char*)ties_.p + off_kl);
+            FusionRowKlParams k;
+            k.ft = m.in.ft[0]; k.base = m.in.base[0]; k.dtype = m.in.dtype; k.C = C;
+            k.seg_vec = (aligned16(k.ft) && aligned16(k.base) && C % 8 == 0) ? 1 : 0;
+            k.kl = kl; k.flags = w->rb.flags;
+            be.template launch<KFusionRowKl>((int)R, GEO_THREADS, fusion_rowkl_lds_floats() * 4, k, stream);
+
+            FusionHistParams h;
+            h.in = m.in; h.C = C; h.kl = kl; h.state = w->state;
+            const size_t noct = (n + 7) / 8;
+            h.chunks = pick_chunks(noct, 256, 4, 5);
+            const int hgrid = stream_grid(noct, 256, h.chunks);
+            FusionSelectParams s;
+            s.sel.m = FUS_RANKS; s.sel.state = w->state; s.sel.tau = w->rb.tau; s.sel.kept = w->rb.kept;
+            // rho_q = floor(q (n - 1)), q = 1/4, 1/2, 3/4, in integers; the rho-th smallest is the (n - rho)-th largest
+            const unsigned long long n1 = (unsigned long long)n - 1;
+            const unsigned long long rho[FUS_RANKS] = {n1 / 4, n1 / 2, 3 * n1 / 4};      // (n <= 2^41: delta_tensor_check)
+            for (int q = 0; q < STATS_MAX_RANKS; ++q) s.sel.rank[q] = (unsigned long long)n - rho[q < FUS_RANKS ? q : 0];
+            s.rows = R; s.kl = kl; s.kl_minmax = w->rb.kl_minmax;
+            for (int level = 1; level <= 3; ++level) {
+                unsigned long long* hist = (unsigned long long*)((char*)ties_.p + (size_t)(level - 1) * select_hist_level(2));
+                h.level = level; h.hist = hist;
+                be.template launch<KFusionHist>(hgrid, 256, (LDS_SCRATCH_FLOATS + (size_t)fusion_hist_words(level)) * 4, h, stream);
+                s.sel.level = level; s.sel.hist = hist;
+                be.template launch<KFusionSelect>(1, TIES_SELECT_THREADS, FUSION_SELECT_LDS, s, stream);
+            }
+            m.kl = kl; m.quart = w->rb.tau; m.threshold = &w->rb.threshold;
+            m.count = &w->rb.count; m.flags = w->rb.flags;
+            be.template launch<KFusionMergeArcee>(grid, 256, merge_lds, m, stream);
+        }
+        FusionReadback host;
+        be.d2h(&host, &w->rb, sizeof host, stream);      // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0]) return fusion_nonfinite(host.flags[0]);
+        if (rep) {
+            if (arcee) {
+                rep->q1 = host.tau[0]; rep->q2 = host.tau[TIES_MAX_MODELS]; rep->q3 = host.tau[2 * TIES_MAX_MODELS];
+                rep->threshold = host.threshold; rep->selected = host.count;
+                rep->kl_min = u2f(host.kl_minmax[0]); rep->kl_max = u2f(host.kl_minmax[1]);
+            } else {
+                rep->clipped = host.count;
+            }
+        }
+        return SMHIP_OK;
+    }
+    // the probe of sm_exp / sm_log: on the host, or one thread per argument on the device
+    int fusion_fn_array(int op, const double* x, double* y, size_t n, bool on_device) {
+        if (!on_device) {
+            for (size_t i = 0; i < n; ++i) y[i] = fusion_fn(op, x[i]);
+            return SMHIP_OK;
+        }
+        FusionFnParams p;
+        p.op = op; p.n = n; p.x = x; p.y = y;
+        if (n) be.template launch<KFusionFn>((int)((n + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         return SMHIP_OK;
     }
 

@@ -1,5 +1,5 @@
 // smhip_side.hip - explicit instantiation of one group of kernels, selected with -DSM_SIDE_GROUP=<g>
-// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction).
+// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction, 10: the pairwise fusion).
 #include "smhip_device.hpp"
 
 namespace smhip {
@@ -24,7 +24,9 @@ SM_SIDE_KERNELS_7(SM_INST)
 SM_SIDE_KERNELS_8(SM_INST)
 #elif SM_SIDE_GROUP == 9
 SM_SIDE_KERNELS_9(SM_INST)
+#elif SM_SIDE_GROUP == 10
+SM_SIDE_KERNELS_10(SM_INST)
 #else
-#error "SM_SIDE_GROUP must be 0..9"
+#error "SM_SIDE_GROUP must be 0..10"
 #endif
 }  // namespace smhip

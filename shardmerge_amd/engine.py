@@ -153,6 +153,21 @@ class ConsensusMergeReport:
 
 
 @dataclass
+class FusionMergeReport:
+    mode: str = "arcee"                                              # "arcee" (arcee_fusion) or "nearswap"
+    n: int = 0                                                       # elements of the tensor
+    q1: float = 0.0                                                  # arcee: the quartiles of the scores |d| * kappa_row,
+    q2: float = 0.0                                                  #   exact order statistics (no interpolation)
+    q3: float = 0.0
+    threshold: float = 0.0                                           # arcee: fl32(q2 + fl32(iqr_mult * fl32(q3 - q1)))
+    selected: int = 0                                                # arcee: elements with a score above the threshold
+    kl_min: float = 0.0                                              # arcee: the smallest and the largest row KL
+    kl_max: float = 0.0
+    kl: Optional[torch.Tensor] = None                                # arcee, want_kl: fp32 [rows], the row KLs
+    clipped: int = 0                                                 # nearswap: elements with |d| > t
+
+
+@dataclass
 class DeltaStatsReport:
     n: int = 0                                                       # elements of the tensor
     densities: List[float] = field(default_factory=list)             # rho_q, as given
@@ -541,7 +556,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -906,6 +921,62 @@ class Engine:
                                       masked=[int(rep.masked[i]) for i in range(k)],
                                       agree=[int(rep.agree[c]) for c in range(k + 1)], selected=int(rep.selected), n=int(desc.n))
         return (out, report, delta) if want_delta else (out, report)
+
+    # -- pairwise fusion: arcee_fusion, nearswap --------------------------------------------------
+    FUSION_MODES = {"arcee": _lib.FUSION_ARCEE, "nearswap": _lib.FUSION_NEARSWAP}
+    FUSION_FNS = {"exp": _lib.FUSION_EXP, "log": _lib.FUSION_LOG}
+
+    def fusion_merge(self, ft: torch.Tensor, base: torch.Tensor, base_out: torch.Tensor, *, mode: str, iqr_mult: float = 1.5,
+                     t: Optional[float] = None, want_delta: bool = False, want_kl: bool = False, layer_name: Optional[str] = None):
+        """Pairwise fusion of ONE finetune onto a base, one tensor of any shape (``smhip_fusion_merge``; the function is
+        stated in include/shardmerge_hip.h).  ``arcee``: a row of the last dimension (a 1-D tensor is one row) gets the
+        fp64 KL divergence of its softmax in the finetune from its softmax in the base, an element's score is
+        ``|finetune - base|`` times its row's KL, and the delta is taken where the score exceeds
+        ``median + iqr_mult * (Q3 - Q1)`` of all scores (exact quartiles), dropped elsewhere.  ``nearswap``: the delta
+        is clamped to ``[-t, t]``.  The gated delta is added onto ``base_out`` in its dtype.  Returns (out,
+        FusionMergeReport[, the fp32 gated delta]); ``want_kl`` puts the row KLs into the report.  A NaN or Inf in
+        the finetune, the base or their difference raises ValueError naming ``layer_name`` and the tensor."""
+        layer_name = layer_name or "layer"
+        if mode not in self.FUSION_MODES:
+            raise ValueError(f"fusion_merge: mode {mode!r} is not one of {sorted(self.FUSION_MODES)}")
+        arcee = mode == "arcee"
+        if arcee and not math.isfinite(float(iqr_mult)):
+            raise ValueError(f"fusion_merge: iqr_mult {iqr_mult} is not finite")
+        if not arcee and (t is None or not (0.0 < float(t) < math.inf)):
+            raise ValueError(f"fusion_merge: mode nearswap needs t > 0 and finite, not {t!r}")
+        desc, rep = _lib.FusionDesc(), _lib.FusionReport()
+        keep, bo, out, delta = self._stage_delta_merge(desc, [ft], [base], [1.0], base_out, layer_name, want_delta, "fusion_merge")
+        desc.n = bo.numel()
+        desc.mode = self.FUSION_MODES[mode]
+        cols = bo.shape[-1] if bo.ndim >= 1 else 1
+        desc.rows = (desc.n // cols if cols else 1) or 1
+        desc.iqr_mult, desc.t = float(iqr_mult), float(t) if t is not None else 0.0
+        kl = None
+        if arcee and want_kl:
+            kl = torch.zeros(int(desc.rows) if desc.n else 0, dtype=torch.float32, device=self.device)
+            desc.kl_out = kl.data_ptr() if kl.numel() else None
+        self._run_delta_merge(self.lib.dll.smhip_fusion_merge, desc, rep, out, delta, layer_name)
+        report = FusionMergeReport(mode=mode, n=int(desc.n))
+        if arcee:
+            report.q1, report.q2, report.q3, report.threshold = float(rep.q1), float(rep.q2), float(rep.q3), float(rep.threshold)
+            report.selected, report.kl_min, report.kl_max, report.kl = int(rep.selected), float(rep.kl_min), float(rep.kl_max), kl
+        else:
+            report.clipped = int(rep.clipped)
+        return (out, report, delta) if want_delta else (out, report)
+
+    def fusion_fn(self, op: str, x: torch.Tensor, on_device: bool = True) -> torch.Tensor:
+        """``sm_exp`` / ``sm_log`` of csrc/sm_fusion.hpp over an fp64 array (``smhip_fusion_fn``): by a kernel on the
+        engine's device, or on the host.  Returns an fp64 CPU tensor."""
+        if op not in self.FUSION_FNS:
+            raise ValueError(f"fusion_fn: op {op!r} is not one of {sorted(self.FUSION_FNS)}")
+        x = x.detach().to(torch.float64).contiguous().reshape(-1)
+        x = x.to(self.device) if on_device else x.cpu()
+        y = torch.empty_like(x)
+        self.ctx.check(self.lib.dll.smhip_fusion_fn(self.ctx.h, self.FUSION_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
+                                                    1 if on_device else 0, self._stream() if on_device else None))
+        if on_device and self.device.type != "cpu":
+            torch.cuda.synchronize(self.device)
+        return y.cpu()
 
     # -- task-vector statistics ----------------------------------------------------------------
     def delta_stats(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],

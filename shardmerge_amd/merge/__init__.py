@@ -22,6 +22,8 @@ _OPERATOR_CLASSES = {
     "consensus_ties": ("consensus", "ConsensusTiesMerge"),
     "karcher": ("spherical", "KarcherMerge"),
     "multislerp": ("spherical", "MultiSlerpMerge"),
+    "arcee_fusion": ("fusion", "ArceeFusionMerge"),
+    "nearswap": ("fusion", "NearSwapMerge"),
 }
 
 
