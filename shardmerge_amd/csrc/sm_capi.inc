@@ -2,7 +2,7 @@
 // and included by the HIP build (smhip_hip.hip) and by the CPU work-group
 // emulator (tests/emul/smhip_emul.cpp) after they define SM_BACKEND.
 //
-// struct smhip_ctx wraps Pipeline<SM_BACKEND>.
+// struct smhip_ctx wraps Pipeline<SM_BACKEND>; the delta operators are its member `delta` (sm_delta_host.hpp).
 
 struct smhip_ctx {
     smhip::Pipeline<SM_BACKEND> pipe;
@@ -193,17 +193,17 @@ int smhip_ties_merge(smhip_ctx* ctx, const smhip_ties_desc* d, void* out, float*
     SM_GUARD(ctx);
     if (int rc = delta_merge_check(ctx, "ties_merge", d, out, delta_out)) return rc;
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.ties_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.ties_merge(*d, out, delta_out, report));
 }
 
 int smhip_dare_merge(smhip_ctx* ctx, const smhip_dare_desc* d, void* out, float* delta_out, smhip_dare_report* report,
                      void* stream) {
     SM_GUARD(ctx);
     if (int rc = delta_merge_check(ctx, "dare_merge", d, out, delta_out)) return rc;
-    if (ctx->pipe.dare_threshold(d->density) == 0)
+    if (ctx->pipe.delta.dare_threshold(d->density) == 0)
         return ctx->pipe.fail(SMHIP_ERR_ARG, "dare_merge: density is below the smallest density, 2^-16 = 1.52587890625e-05 (the mask draws 16 bits per element)");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.dare_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.dare_merge(*d, out, delta_out, report));
 }
 
 int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* d, void* out, float* delta_out,
@@ -213,7 +213,7 @@ int smhip_breadcrumbs_merge(smhip_ctx* ctx, const smhip_breadcrumbs_desc* d, voi
     if (!(d->gamma >= 0.0 && d->gamma < 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: gamma must be in [0, 1)");
     if (!(d->density + d->gamma <= 1.0)) return ctx->pipe.fail(SMHIP_ERR_ARG, "breadcrumbs_merge: density + gamma must not exceed 1");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.breadcrumbs_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.breadcrumbs_merge(*d, out, delta_out, report));
 }
 
 int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* d, void* out, float* delta_out, smhip_geo_report* report,
@@ -233,7 +233,7 @@ int smhip_geo_merge(smhip_ctx* ctx, const smhip_geo_desc* d, void* out, float* d
         return rc;
     if (d->n > 0 && (d->rows < 1 || d->n % d->rows)) return ctx->pipe.fail(SMHIP_ERR_ARG, "geo_merge: rows must divide n");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.geo_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.geo_merge(*d, out, delta_out, report));
 }
 
 int smhip_sphere_merge(smhip_ctx* ctx, const smhip_sphere_desc* d, void* out, float* delta_out, smhip_sphere_report* report,
@@ -254,7 +254,7 @@ int smhip_sphere_merge(smhip_ctx* ctx, const smhip_sphere_desc* d, void* out, fl
         return rc;
     if (d->n > 0 && (d->rows < 1 || d->n % d->rows)) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_merge: rows must divide n");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.sphere_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.sphere_merge(*d, out, delta_out, report));
 }
 
 int smhip_sphere_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream) {
@@ -264,7 +264,7 @@ int smhip_sphere_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n
     if ((uintptr_t)x % 8 || (uintptr_t)y % 8) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_fn: a pointer is not aligned to 8 bytes");
     if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "sphere_fn: array too large");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.sphere_fn_array(op, x, y, n, on_device != 0));
+    SM_FINISH(ctx, ctx->pipe.delta.sphere_fn_array(op, x, y, n, on_device != 0));
 }
 
 int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* d, void* out, float* delta_out, smhip_sce_report* report,
@@ -283,7 +283,7 @@ int smhip_sce_merge(smhip_ctx* ctx, const smhip_sce_desc* d, void* out, float* d
         }))
         return rc;
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.sce_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.sce_merge(*d, out, delta_out, report));
 }
 
 int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* d, void* out, float* delta_out, uint16_t* threshold_out,
@@ -295,7 +295,7 @@ int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* d, void* out, floa
             if (!(d->epsilon >= 0.0)) return "epsilon must be >= 0";
             if (d->density == 1.0) return d->epsilon == 0.0 ? nullptr : "density 1 keeps everything: it requires epsilon 0";
             if (d->epsilon == 0.0)
-                return ctx->pipe.dare_threshold(d->density) >= 1 ? nullptr : "density is below the smallest density, 2^-16 = 1.52587890625e-05 (the mask draws 16 bits per element)";
+                return ctx->pipe.delta.dare_threshold(d->density) >= 1 ? nullptr : "density is below the smallest density, 2^-16 = 1.52587890625e-05 (the mask draws 16 bits per element)";
             if (!(d->density + d->epsilon < 1.0)) return "density + epsilon must be below 1";
             if (!(std::floor((d->density - d->epsilon) * 65536.0) >= 1.0)) return "floor((density - epsilon) * 65536) must be at least 1 (the mask draws 16 bits per element)";
             return nullptr;
@@ -317,7 +317,7 @@ int smhip_della_merge(smhip_ctx* ctx, const smhip_della_desc* d, void* out, floa
         }
     }
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.della_merge(*d, out, delta_out, threshold_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.della_merge(*d, out, delta_out, threshold_out, report));
 }
 
 int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* d, void* out, float* delta_out,
@@ -332,7 +332,7 @@ int smhip_consensus_merge(smhip_ctx* ctx, const smhip_consensus_desc* d, void* o
         }))
         return rc;
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.consensus_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.consensus_merge(*d, out, delta_out, report));
 }
 
 int smhip_fusion_merge(smhip_ctx* ctx, const smhip_fusion_desc* d, void* out, float* delta_out, smhip_fusion_report* report,
@@ -359,7 +359,7 @@ int smhip_fusion_merge(smhip_ctx* ctx, const smhip_fusion_desc* d, void* out, fl
         }
     }
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.fusion_merge(*d, out, delta_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.fusion_merge(*d, out, delta_out, report));
 }
 
 int smhip_fusion_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream) {
@@ -369,7 +369,7 @@ int smhip_fusion_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n
     if ((uintptr_t)x % 8 || (uintptr_t)y % 8) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_fn: a pointer is not aligned to 8 bytes");
     if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "fusion_fn: array too large");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.fusion_fn_array(op, x, y, n, on_device != 0));
+    SM_FINISH(ctx, ctx->pipe.delta.fusion_fn_array(op, x, y, n, on_device != 0));
 }
 
 int smhip_delta_stats(smhip_ctx* ctx, const smhip_stats_desc* d, smhip_stats_report* report, void* stream) {
@@ -391,7 +391,7 @@ int smhip_delta_stats(smhip_ctx* ctx, const smhip_stats_desc* d, smhip_stats_rep
     }
     if ((d->n + 7) / 8 / 256 > (size_t)1 << 30) return bad("tensor too large");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.delta_stats(*d, report));
+    SM_FINISH(ctx, ctx->pipe.delta.delta_stats(*d, report));
 }
 
 int smhip_slerp(smhip_ctx* ctx, const float* v0, const float* v1, size_t rows, size_t cols, float t, float* out, void* stream) {
@@ -455,11 +455,11 @@ int smhip_adapter_apply(smhip_ctx* ctx, const smhip_adapter_desc* d, void* strea
 
 size_t smhip_lora_extract_workspace(int rows, int cols, int rank) {
     if (rows < 1 || cols < 1 || rank < 1 || rank > smhip::XL_MAX_RANK) return 0;
-    return smhip::Pipeline<SM_BACKEND>::xl_layout(rows, cols, rank).total;
+    return smhip::DeltaHost<SM_BACKEND>::xl_layout(rows, cols, rank).total;
 }
 size_t smhip_xl_probe_workspace(int rows, int cols, int L) {
     if (rows < 1 || cols < 1 || L < 16 || L > smhip::XL_MAX_L || L % 16) return 0;
-    return smhip::Pipeline<SM_BACKEND>::xl_layout_L(rows, cols, L, L).total;
+    return smhip::DeltaHost<SM_BACKEND>::xl_layout_L(rows, cols, L, L).total;
 }
 
 int smhip_lora_extract(smhip_ctx* ctx, const smhip_extract_desc* d, void* a_out, void* b_out,
@@ -480,7 +480,7 @@ int smhip_lora_extract(smhip_ctx* ctx, const smhip_extract_desc* d, void* a_out,
     if (!d->workspace || (uintptr_t)d->workspace % 256 || d->workspace_bytes < smhip_lora_extract_workspace(d->rows, d->cols, d->rank))
         return bad("the workspace is null, not 256-byte aligned or too small (smhip_lora_extract_workspace)");
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.lora_extract(*d, a_out, b_out, report));
+    SM_FINISH(ctx, ctx->pipe.delta.lora_extract(*d, a_out, b_out, report));
 }
 
 int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* d, void* stream) {
@@ -501,7 +501,7 @@ int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* d, void* stream) {
         if ((d->op == SMHIP_XL_DELTA_MM || d->op == SMHIP_XL_GRAM) && (uintptr_t)d->workspace % 256) return bad("the workspace is not 256-byte aligned");
     }
     ctx->pipe.stream = stream;
-    SM_FINISH(ctx, ctx->pipe.xl_probe(*d));
+    SM_FINISH(ctx, ctx->pipe.delta.xl_probe(*d));
 }
 
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
@@ -562,7 +562,7 @@ int smhip_debug_option(smhip_ctx* ctx, const char* key, long value) {
     if (key && std::string(key) == "force_bluestein") { ctx->pipe.debug_force_bluestein = value != 0; return SMHIP_OK; }
     if (key && std::string(key) == "force_split") { ctx->pipe.debug_force_split = value > 1 && value <= smhip::DFTP_MAX_P ? (int)value : 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_columns") { ctx->pipe.fold_enabled = value != 0; return SMHIP_OK; }
-    if (key && std::string(key) == "della_slab_rows") { ctx->pipe.della_slab_rows = value > 0 ? (size_t)value : 0; return SMHIP_OK; }
+    if (key && std::string(key) == "della_slab_rows") { ctx->pipe.delta.della_slab_rows = value > 0 ? (size_t)value : 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_min_rows") { ctx->pipe.fold_min_rows = value > 0 ? (int)value : SM_FOLD_MIN_ROWS; return SMHIP_OK; }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug option");
 }

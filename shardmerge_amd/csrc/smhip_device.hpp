@@ -1,5 +1,7 @@
 // smhip_device.hpp - DeviceExec (one real gfx950 work-group per block) and the
-// generic __global__ entry point; shared by smhip_hip.hip and smhip_inst.hip.
+// generic __global__ entry point; shared by smhip_hip.hip, smhip_side.hip and smhip_inst.hip.
+// The kernel tags and the lists of what each translation unit instantiates: sm_pipeline.hpp
+// (the spectral pipeline, SM_STATIC_PLANS) and sm_delta_host.hpp (the delta operators).
 #pragma once
 #include <hip/hip_runtime.h>
 

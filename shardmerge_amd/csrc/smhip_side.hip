@@ -1,5 +1,5 @@
 // smhip_side.hip - explicit instantiation of one group of kernels, selected with -DSM_SIDE_GROUP=<g>
-// (SM_SIDE_KERNELS_<g> in sm_pipeline.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction, 10: the pairwise fusion).
+// (SM_SIDE_KERNELS_<g>: groups 0..2 in sm_pipeline.hpp, 7..10 in sm_delta_host.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction, 10: the pairwise fusion).
 #include "smhip_device.hpp"
 
 namespace smhip {

@@ -562,7 +562,8 @@ class Engine:
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
         in_dtype, base_out, base_out_dtype) and the outputs.  ``op`` names the operator in the check that every
         finetune has a base and an alpha (merge_layer makes none).  Returns (keep, bo, out, delta): ``keep`` holds the
-        copies alive until the call returns, ``bo`` is base_out on the device, ``out`` is of ``out_dtype`` (default: bo's)."""
+        copies alive until the call returns, ``bo`` is base_out on the device, ``out`` is of ``out_dtype`` (default: bo's).
+        ``base_out`` None (delta_stats writes no tensor): the shapes are held to finetune 0's and only ``keep`` is returned."""
         k = len(finetunes)
         if k < 1 or k > _lib.MAX_MODELS:
             raise ValueError(f"{k} models to merge: supported range is 1..{_lib.MAX_MODELS}")
@@ -577,6 +578,7 @@ class Engine:
             in_dtype = torch.float32
         keep = []           # keep device copies alive until the call returns
         desc.k = k
+        shape = finetunes[0].shape if base_out is None else base_out.shape
         seen: Dict[int, torch.Tensor] = {}
         for i in range(k):
             ft = self._dev(finetunes[i], in_dtype)
@@ -584,29 +586,32 @@ class Engine:
             if bkey not in seen:
                 seen[bkey] = self._dev(bases[i], in_dtype)
             bs = seen[bkey]
-            if ft.shape != base_out.shape or bs.shape != base_out.shape:
-                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(base_out.shape)}")
+            if ft.shape != shape or bs.shape != shape:
+                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(shape)}")
             keep += [ft, bs]
             desc.finetune[i] = ft.data_ptr()
             desc.base[i] = bs.data_ptr()
             desc.alpha[i] = float(alphas[i])
+        desc.in_dtype = _DTYPE_CODE[in_dtype]
+        if base_out is None:
+            return keep, None, None, None
         bo_dtype = base_out.dtype if base_out.dtype in _DTYPE_CODE else torch.float32
         bo = seen.get(id(base_out))
         if bo is None or bo.dtype != bo_dtype:
             bo = self._dev(base_out, bo_dtype)
         keep.append(bo)
-        desc.in_dtype = _DTYPE_CODE[in_dtype]
         desc.base_out = bo.data_ptr()
         desc.base_out_dtype = _DTYPE_CODE[bo_dtype]
         out = torch.empty(bo.shape, dtype=out_dtype or bo_dtype, device=self.device)
         delta = torch.empty(bo.shape, dtype=torch.float32, device=self.device) if want_delta else None
         return keep, bo, out, delta
 
-    def _run_delta_merge(self, fn, desc, rep, out, delta, layer_name: str):
-        """one smhip_*_merge call of the family; a NaN or Inf in a delta becomes the ValueError naming the layer"""
+    def _run_delta_merge(self, fn, desc, rep, out, delta, layer_name: str, *more):
+        """one smhip_*_merge call of the family (``more``: the operator's own arguments between delta_out and the report);
+        a NaN or Inf in a delta becomes the ValueError naming the layer"""
         try:
             self.ctx.check(fn(self.ctx.h, C.byref(desc), out.data_ptr(), delta.data_ptr() if delta is not None else None,
-                              C.byref(rep), self._stream()))
+                              *more, C.byref(rep), self._stream()))
         except SmhipError as e:
             if e.code == _lib.ERR_NONFINITE:
                 raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
@@ -701,15 +706,8 @@ class Engine:
         desc.epsilon, desc.rows = epsilon, (desc.n // cols if cols else 1) or 1
         desc.stream_id[:k] = stream_ids
         thresholds = torch.zeros((k,) + tuple(bo.shape), dtype=torch.int16, device=self.device) if want_thresholds else None
-        try:
-            self.ctx.check(self.lib.dll.smhip_della_merge(self.ctx.h, C.byref(desc), out.data_ptr(),
-                                                          delta.data_ptr() if delta is not None else None,
-                                                          thresholds.data_ptr() if thresholds is not None else None,
-                                                          C.byref(rep), self._stream()))
-        except SmhipError as e:
-            if e.code == _lib.ERR_NONFINITE:
-                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
-            raise
+        self._run_delta_merge(self.lib.dll.smhip_della_merge, desc, rep, out, delta, layer_name,
+                              thresholds.data_ptr() if thresholds is not None else None)
         report = DellaMergeReport(threshold_lo=int(rep.T_lo), threshold_hi=int(rep.T_hi), kept=[int(rep.kept[i]) for i in range(k)])
         res = (out, report) + ((delta,) if want_delta else ())
         if want_thresholds:     # (uint16 values in an int16 tensor: widened here, 65536 of density 1 does not fit and is never written)
@@ -998,22 +996,9 @@ class Engine:
         for rho in dens:
             if not (0.0 < rho <= 1.0):
                 raise ValueError(f"delta_stats: density {rho} is not in (0, 1]")
-        dtypes = {t.dtype for t in list(finetunes) + list(bases)}        # (mixed dtypes are promoted, as _stage_delta_merge does)
-        in_dtype = next(iter(dtypes)) if len(dtypes) == 1 else torch.float32
-        if in_dtype not in _DTYPE_CODE:
-            in_dtype = torch.float32
         desc, rep, m = _lib.StatsDesc(), _lib.StatsReport(), len(dens)
-        keep, seen = [], {}
-        for i in range(k):
-            ft = self._dev(finetunes[i], in_dtype)
-            if id(bases[i]) not in seen:
-                seen[id(bases[i])] = self._dev(bases[i], in_dtype)
-            bs = seen[id(bases[i])]
-            if ft.shape != bs.shape or ft.shape != finetunes[0].shape:
-                raise ValueError(f"shape mismatch in {layer_name}: {tuple(ft.shape)} / {tuple(bs.shape)} / {tuple(finetunes[0].shape)}")
-            keep += [ft, bs]
-            desc.finetune[i], desc.base[i], desc.alpha[i] = ft.data_ptr(), bs.data_ptr(), float(alphas[i])
-        desc.k, desc.in_dtype, desc.n, desc.m = k, _DTYPE_CODE[in_dtype], keep[0].numel(), m
+        keep = self._stage_delta_merge(desc, finetunes, bases, alphas, None, layer_name, False)[0]
+        desc.n, desc.m = keep[0].numel(), m
         for q in range(m):
             desc.density[q] = dens[q]
         try:
