@@ -731,6 +731,86 @@ int smhip_fusion_merge(smhip_ctx* ctx, const smhip_fusion_desc* desc, void* out,
 enum { SMHIP_FUSION_EXP = 0, SMHIP_FUSION_LOG = 1 };
 int smhip_fusion_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream);
 
+/* ---- PCB merge (Du et al., "Parameter Competition Balancing for Model Merging", NeurIPS 2024): every entry of every
+ *      task vector gets a continuous weight of its own - how large it is within its own task (intra-balancing) times how
+ *      well it agrees with what all tasks together do to that weight (inter-balancing); the low scores are dropped, the
+ *      rest are averaged with their scores as weights.  The reference has no such operator; this section IS its
+ *      definition.  For one tensor of n elements (any shape, flat), finetunes i = 0..k-1 in order (1 <= k <= 16), and
+ *      the parameters ratio in (0, 1], clip in [0, 0.5) and lambda:
+ *        1. d_i = fp32(finetune_i) - fp32(base_i), tv_i = fl32(d_i * fp32(alpha_i)): one fp32 subtraction, one fp32
+ *           multiplication, as smhip_consensus_merge forms them; alpha_i of any sign, or zero.  A NaN or Inf in any d_i
+ *           fails the call with SMHIP_ERR_NONFINITE (the message lists the finetunes); out is then unspecified.
+ *        2. Clip.  r = (uint64) floor(clip * n) in fp64.  Per finetune, with the n values |tv_i| in ascending order
+ *           (0-based): lo_i is the one at index r, hi_i the one at index n - 1 - r - exact order statistics, whatever the
+ *           traversal order; r < n / 2, so lo_i <= hi_i.  fl32(|d| * |alpha|) is monotone in |d|, so they are computed as
+ *           lo_i = |fl32(q * fp32(alpha_i))| for the same order statistics q of |d_i|.  c_i = min(max(|tv_i|, lo_i), hi_i);
+ *           tvc_i = copysign(c_i, tv_i), and +0 where tv_i == 0.
+ *        3. Intra-balancing, in fp64, every operation ONE rounded IEEE operation, never an fma:
+ *           s_i = (fp64(c_i) - fp64(lo_i)) / (fp64(hi_i) - fp64(lo_i)), and 0 where hi_i == lo_i; 0 <= s_i <= 1.
+ *           intra_i = sm_exp(fp64(k) * (s_i * s_i - 1)): the argument lies in [-16, 0].  The paper's exp(k s^2) is this
+ *           times the constant e^k, which cancels in step 7.
+ *        4. Inter-balancing.  U = ((0 + tv_0) + tv_1) + ... in fp32, in order, over the UNCLIPPED entries.
+ *           x_i = fp64(tv_i) * fp64(U) (exact), inter_i = sm_tanh(x_i).
+ *        5. Score.  p_i = intra_i * inter_i in fp64; S_i = fp32(p_i) (one rounding to nearest even) where
+ *           p_i >= 2^-126, compared in fp64, and +0 elsewhere - so a score is +0 or a NORMAL positive fp32 number and
+ *           the result depends on no denormal mode.  An entry that opposes the sum of its element, or is zero, scores 0
+ *           and is never selected.  DEVIATION: the paper's code applies tanh unclamped, so a negative score can receive a
+ *           positive weight there once ratio exceeds the share of agreeing entries; here it cannot.
+ *        6. Select and weigh.  q = max(1, (uint64) floor(ratio * n)) (n when ratio == 1).  Per finetune t_i is the q-th
+ *           largest of its n scores (+0 when fewer than q are positive) and M_i the largest, both exact.
+ *           scale_i = 0 where S_i < t_i or S_i == 0; else 1 where M_i == t_i; else fl32(fl32(S_i - t_i) / fl32(M_i - t_i)).
+ *           The weight is continuous at the threshold - an entry equal to t_i < M_i weighs 0 - so the tie rule changes
+ *           the counts only.
+ *        7. merged = fl32(num / max(den, fp32(1e-12))), num = ((0 + fl32(scale_0 * tvc_0)) + ...), den = ((0 + scale_0) +
+ *           ...), fp32, in order; out = round_to(base_out_dtype, fl32(fp32(base_out) + fl32(fp32(lambda) * merged)));
+ *           delta_out = merged (NOT times lambda).
+ *      sm_tanh (csrc/sm_pcb.hpp) is DEFINED there, next to sm_exp and in its manner.  |x| < 2^-4: x * P(x * x), P the
+ *      series 1, -1/3, 2/15, -17/315, 62/2835, -1382/155925, 21844/6081075, -929569/638512875, 6404582/10854718875 (each
+ *      rounded to fp64) in Horner form.  2^-4 <= |x| <= 22.5: (1 - e) / (1 + e) with e = sm_exp(-2 |x|), the sign of x.
+ *      Beyond: +-1.  sm_tanh(+-0) = +-0.  One rounded operation at a time: the host, the device, the emulator and a numpy
+ *      restatement give the same bits; smhip_pcb_fn exposes it.
+ *      Report: lo, hi, t, M per finetune; positive[i] = #{S_i > 0}; selected[i] = #{S_i >= t_i and S_i > 0};
+ *      covered = #{den > 0}; contested = #{at least two finetunes with scale > 0}.
+ *      Every value is one correctly rounded operation, an exact order statistic or an integer count in a stated order:
+ *      the result is defined bit for bit.  Passes: "stats_hist" / "stats_select" three times (the two ranks of step 2 in
+ *      the same 11 + 10 + 10 bit levels over the magnitude bits), "pcb_hist" / "stats_select" three times (the two ranks of
+ *      step 6 over the score stream, recomputed from the inputs, lo, hi and U in every pass: no score is cached),
+ *      "pcb_merge" once: 3 (k + 1) + 3 (k + 1) + (k + 2) = 7 k + 8 tensor passes with a shared base and k <= 4 (beyond,
+ *      pcb_hist runs once per group of four finetunes and reads all k each time).  Counters are integers (LDS, then one
+ *      global atomic per counter and work-group), no floating-point atomics; the stream is synchronised once, at the
+ *      end.  Aliasing, alignment, n == 0 (a no-op, the report all zeros), dtypes and the size limit: the rules of
+ *      smhip_ties_merge.  SMHIP_ERR_ARG: k outside 1..16, ratio outside (0, 1], clip outside [0, 0.5), lambda or an
+ *      alpha not finite, out overlapping an input, a bad dtype, a null pointer. ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double ratio;                           /* 0 < ratio <= 1: the share of each finetune's scores that is kept */
+    double clip;                            /* 0 <= clip < 0.5: the share of magnitudes clamped at either end */
+    double lambda;
+} smhip_pcb_desc;
+typedef struct {
+    uint64_t clip_rank;                     /* r */
+    uint64_t q;                             /* scores asked for per finetune */
+    float lo[SMHIP_MAX_MODELS], hi[SMHIP_MAX_MODELS];     /* the clip bounds of |tv_i| */
+    float t[SMHIP_MAX_MODELS], M[SMHIP_MAX_MODELS];       /* the q-th largest and the largest score */
+    uint64_t positive[SMHIP_MAX_MODELS];    /* entries with S_i > 0 */
+    uint64_t selected[SMHIP_MAX_MODELS];    /* entries with S_i >= t_i and S_i > 0 */
+    uint64_t covered;                       /* elements with den > 0 */
+    uint64_t contested;                     /* elements where at least two finetunes have scale > 0 */
+} smhip_pcb_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], merged.  report (optional): HOST. */
+int smhip_pcb_merge(smhip_ctx* ctx, const smhip_pcb_desc* desc, void* out, float* delta_out,
+                    smhip_pcb_report* report, void* stream);
+/* y[i] = sm_tanh(x[i]) (op SMHIP_PCB_TANH) for n doubles.  on_device = 0: x and y are HOST arrays, evaluated on the
+ * host; 1: DEVICE arrays, evaluated by a kernel ("pcb_fn") on the stream. */
+enum { SMHIP_PCB_TANH = 0 };
+int smhip_pcb_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream);
+
 /* ---- Task-vector statistics: what the knobs of the delta merges (density above all) would do to THESE finetunes,
  *      before a merge has run.  No output tensor: for one tensor of n elements (any shape, flat), finetunes i = 0..k-1
  *      (1 <= k <= 16) and candidate densities rho_q, q = 0..m-1 (1 <= m <= SMHIP_STATS_MAX_DENSITIES, each in (0, 1],

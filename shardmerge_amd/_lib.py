@@ -197,6 +197,23 @@ class FusionReport(C.Structure):
                 ("selected", C.c_uint64), ("clipped", C.c_uint64), ("kl_min", C.c_float), ("kl_max", C.c_float)]
 
 
+PCB_TANH = 0
+
+
+class PcbDesc(C.Structure):
+    """smhip_pcb_desc: the leading fields of the delta merges, then ratio, clip and lambda"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("ratio", C.c_double), ("clip", C.c_double), ("lam", C.c_double)]
+
+
+class PcbReport(C.Structure):
+    """smhip_pcb_report"""
+    _fields_ = [("clip_rank", C.c_uint64), ("q", C.c_uint64),
+                ("lo", C.c_float * MAX_MODELS), ("hi", C.c_float * MAX_MODELS),
+                ("t", C.c_float * MAX_MODELS), ("M", C.c_float * MAX_MODELS),
+                ("positive", C.c_uint64 * MAX_MODELS), ("selected", C.c_uint64 * MAX_MODELS),
+                ("covered", C.c_uint64), ("contested", C.c_uint64)]
+
+
 STATS_MAX_DENSITIES = 4         # SMHIP_STATS_MAX_DENSITIES
 
 
@@ -307,7 +324,9 @@ class SmhipLibrary:
         d.smhip_consensus_merge.argtypes = [P, C.POINTER(ConsensusDesc), P, P, C.POINTER(ConsensusReport), P]
         d.smhip_fusion_merge.argtypes = [P, C.POINTER(FusionDesc), P, P, C.POINTER(FusionReport), P]
         d.smhip_fusion_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
-        d.smhip_delta_stats.argtypes = [P, C.POINTER(StatsDesc), C.POINTER(StatsReport), P]
+        d.smhip_pcb_merge.argtypes = [P, C.POINTER(PcbDesc), P, P, C.POINTER(PcbReport), P]
+        d.smhip_pcb_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
+        d.smhip_delta_stats.argtypes =[P, C.POINTER(StatsDesc), C.POINTER(StatsReport), P]
         d.smhip_correlate_pairs.argtypes = [P, I, C.POINTER(C.c_void_p), I, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_reference_cpu_norm.argtypes = [P, P, P, I, C.c_size_t, C.POINTER(C.c_float), P]
         d.smhip_slerp.argtypes = [P, P, P, C.c_size_t, C.c_size_t, C.c_float, P, P]

@@ -111,6 +111,16 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
                                 #   family's keys are rejected; keys:
       # fusion_iqr: 1.5         #   operator arcee_fusion only: -1e6 <= fusion_iqr <= 1e6 (mergekit's 1.5)
       # nearswap_t: 0.001       #   operator nearswap only, REQUIRED: 0 < nearswap_t <= 1e6
+                                # | pcb (PCB-Merging, Du et al. 2024; no counterpart in the reference): every entry of every
+                                #   weighted delta gets a continuous score - its magnitude within its own finetune (clamped
+                                #   at both ends, min-max normalised, through exp) times its agreement with the sum of all
+                                #   deltas at that weight (through tanh; an entry that opposes the sum scores 0) - each
+                                #   finetune keeps its pcb_ratio highest scores per tensor, and the clamped entries are
+                                #   averaged with their rescaled scores as weights.  alphas of any sign.  The spectral keys,
+                                #   norm_mode, task_add_models and every other family's keys are rejected; keys:
+      # pcb_ratio: 0.1          #   0 < pcb_ratio <= 1: the share of each finetune's scores that is kept
+      # pcb_clip: 0.0001        #   0 <= pcb_clip < 0.5: the share of magnitudes clamped at either end
+      # pcb_lambda: 1.0         #   scales the merged delta
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -138,7 +148,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -160,6 +170,7 @@ SPHERE_OPERATORS = ("karcher", "multislerp")             # Karcher means: slerp 
 SPHERE_OPTION_DEFAULTS = {"karcher_max_iter": 10, "karcher_tol": 1e-5, "sphere_row_wise": 0.0}
 FUSION_OPERATORS = ("arcee_fusion", "nearswap")          # the pairwise family: one model onto its base, no weights
 FUSION_OPTION_DEFAULTS = {"fusion_iqr": 1.5, "nearswap_t": None}      # nearswap_t has no default: it is required
+PCB_OPTION_DEFAULTS = {"pcb_ratio": 0.1, "pcb_clip": 0.0001, "pcb_lambda": 1.0}
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -264,6 +275,15 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "della": "(it drops nothing at random)",
                            "consensus_ta": "(it fuses one model: no masks to agree)"},
                   only={"fusion_iqr": ("arcee_fusion",), "nearswap_t": ("nearswap",)}, required=("nearswap_t",)),
+    _OptionFamily(("pcb",), PCB_OPTION_DEFAULTS,
+                  {"pcb_ratio": (0, 1, "(]"), "pcb_clip": (0, 0.5, "[)"), "pcb_lambda": _LAMBDA},
+                  earlier={"ties": "(its keys: pcb_ratio, pcb_lambda)", "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it clamps the largest magnitudes and drops by score: pcb_clip, pcb_ratio)",
+                           "model_stock": "(its weights are per element, from the scores)",
+                           "sce": "(it selects by score, per finetune: pcb_ratio)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it weighs by agreement with the sum, without masks)",
+                           "arcee_fusion": "(it merges several models by their scores)"}),
 )
 
 

@@ -372,6 +372,29 @@ int smhip_fusion_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n
     SM_FINISH(ctx, ctx->pipe.delta.fusion_fn_array(op, x, y, n, on_device != 0));
 }
 
+int smhip_pcb_merge(smhip_ctx* ctx, const smhip_pcb_desc* d, void* out, float* delta_out, smhip_pcb_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "pcb_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!(d->ratio > 0.0 && d->ratio <= 1.0)) return "ratio must be in (0, 1]";
+            if (!(d->clip >= 0.0 && d->clip < 0.5)) return "clip must be in [0, 0.5)";
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            return nullptr;
+        }))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.pcb_merge(*d, out, delta_out, report));
+}
+
+int smhip_pcb_fn(smhip_ctx* ctx, int op, const double* x, double* y, size_t n, int on_device, void* stream) {
+    SM_GUARD(ctx);
+    if (op != SMHIP_PCB_TANH) return ctx->pipe.fail(SMHIP_ERR_ARG, "pcb_fn: bad op");
+    if (n > 0 && (!x || !y)) return ctx->pipe.fail(SMHIP_ERR_ARG, "pcb_fn: null array");
+    if ((uintptr_t)x % 8 || (uintptr_t)y % 8) return ctx->pipe.fail(SMHIP_ERR_ARG, "pcb_fn: a pointer is not aligned to 8 bytes");
+    if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "pcb_fn: array too large");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.pcb_fn_array(op, x, y, n, on_device != 0));
+}
+
 int smhip_delta_stats(smhip_ctx* ctx, const smhip_stats_desc* d, smhip_stats_report* report, void* stream) {
     SM_GUARD(ctx);
     auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("delta_stats: ") + what); };

@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, the task-vector statistics and the low-rank extraction (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, the task-vector statistics and the low-rank extraction (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -23,6 +23,7 @@
 #include "sm_stats.hpp"
 #include "sm_extract.hpp"
 #include "sm_fusion.hpp"
+#include "sm_pcb.hpp"
 
 namespace smhip {
 
@@ -100,6 +101,14 @@ SM_KERNEL_TAG_LB(KFusionSelect, FusionSelectParams, "fusion_select", k_fusion_se
 SM_KERNEL_TAG_LB(KFusionMergeArcee, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_ARCEE>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KFusionMergeNear, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_NEARSWAP>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KFusionFn, FusionFnParams, "fusion_fn", k_fusion_fn(ex, p), 256, 4)
+// PCB merge (sm_pcb.hpp): the two-rank radix level over the score stream (its scan is stats_select, as the clip's two
+// order statistics are stats_hist / stats_select), the fused weighted pass - k <= 4 entries per element in registers, or
+// up to 16 - and the probe of sm_tanh
+SM_KERNEL_TAG_LB(KPcbHist, PcbHistParams, "pcb_hist", k_pcb_hist<PCB_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KPcbHistAny, PcbHistParams, "pcb_hist", k_pcb_hist<TIES_MAX_MODELS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KPcbMerge, PcbMergeParams, "pcb_merge", k_pcb_merge<PCB_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KPcbMergeAny, PcbMergeParams, "pcb_merge", k_pcb_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KPcbFn, PcbFnParams, "pcb_fn", k_pcb_fn(ex, p), 256, 4)
 // the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
@@ -108,6 +117,7 @@ SM_KERNEL_TAG_LB(KFusionFn, FusionFnParams, "fusion_fn", k_fusion_fn(ex, p), 256
 #define SM_SIDE_KERNELS_8(X) X(KStatsHist) X(KStatsSelect) X(KStatsPass) X(KStatsPassAny) X(KStatsFold)
 #define SM_SIDE_KERNELS_9(X) X(KXlFill) X(KXlDeltaMm) X(KXlFold) X(KXlGram) X(KXlGramFold) X(KXlPanelMm)
 #define SM_SIDE_KERNELS_10(X) X(KFusionRowKl) X(KFusionHist) X(KFusionSelect) X(KFusionMergeArcee) X(KFusionMergeNear) X(KFusionFn)
+#define SM_SIDE_KERNELS_11(X) X(KPcbHist) X(KPcbHistAny) X(KPcbMerge) X(KPcbMergeAny) X(KPcbFn)
 
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
@@ -887,6 +897,91 @@ class DeltaHost {
     }
     int fusion_fn_array(int op, const double* x, double* y, size_t n, bool on_device) {      // sm_exp / sm_log
         return fn_array<KFusionFn, FusionFnParams>([](int o, double v) { return fusion_fn(o, v); }, op, x, y, n, on_device);
+    }
+
+    // ---- PCB merge (sm_pcb.hpp; smhip_pcb_merge): the clip's two order statistics per finetune (stats_hist / stats_select
+    // with m = 2, unchanged), the histograms zeroed again, the three levels of the two-rank select over the score stream
+    // (pcb_hist, stats_select), the fused pass, ONE readback.  Workspace: select_workspace of stats' 32 streams with
+    // PcbWork as its tail ----
+    struct PcbReadback {
+        float q[STATS_MAX_RANKS * TIES_MAX_MODELS];                    // stats_select's layout: rank r of |d_i| at [r * TIES_MAX_MODELS + i]
+        unsigned long long q_kept[STATS_MAX_RANKS * TIES_MAX_MODELS];  // (its kept counts: not reported)
+        float tm[STATS_MAX_RANKS * TIES_MAX_MODELS];                   // M_i at [PCB_MAX], t_i at [PCB_CUT]
+        unsigned long long tm_kept[STATS_MAX_RANKS * TIES_MAX_MODELS]; // at [PCB_CUT]: selected[i]
+        float bounds[2 * TIES_MAX_MODELS];                             // lo_i, then hi_i
+        unsigned long long positive[TIES_MAX_MODELS], counts[PCB_COUNTS];
+        uint32_t flags[2];
+    };
+    struct PcbWork { RadixState clip[STATS_MAX_RANKS * TIES_MAX_MODELS], score[STATS_MAX_RANKS * TIES_MAX_MODELS]; PcbReadback rb; };
+    int pcb_merge(const smhip_pcb_desc& d, void* out, float* delta_out, smhip_pcb_report* rep) {
+        const int k = d.k;
+        const unsigned long long n = d.n;
+        const unsigned long long r = (unsigned long long)std::floor(d.clip * (double)n);
+        const unsigned long long q = d.ratio == 1.0 ? n : std::max(1ull, (unsigned long long)std::floor(d.ratio * (double)n));
+        if (rep) {
+            *rep = smhip_pcb_report{};
+            rep->clip_rank = r; rep->q = n ? q : 0;
+        }
+        if (n == 0) return SMHIP_OK;
+        const int streams = 2 * TIES_MAX_MODELS;
+        PcbWork* w;
+        int rc;
+        if ((rc = select_workspace(streams, w))) return rc;
+
+        PcbMergeParams m;
+        delta_inputs(d, out, delta_out, false, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < k ? i : 0];
+        m.lambda = (float)d.lambda;
+        m.q = w->rb.q; m.tm = w->rb.tm; m.bounds = w->rb.bounds; m.positive = w->rb.positive; m.counts = w->rb.counts;
+
+        // step 2: the (r + 1)-th largest and the (n - r)-th largest |d_i|
+        StatsHistParams h;
+        h.in = m.in; h.m = PCB_RANKS; h.state = w->clip; h.flags = w->rb.flags;
+        StatsSelectParams s;
+        s.m = PCB_RANKS; s.state = w->clip; s.tau = w->rb.q; s.kept = w->rb.q_kept;
+        for (int j = 0; j < STATS_MAX_RANKS; ++j) s.rank[j] = j == PCB_LO ? n - r : r + 1;
+        select_levels_per_finetune<KStatsHist, KStatsSelect>(streams, h, s, STATS_SELECT_LDS,
+                                                             [](int level) { return stats_hist_words(level, PCB_RANKS); }, false);
+        be.memset(ws_.p, 0, 3 * select_hist_level(streams), stream);
+
+        // step 6: the largest and the q-th largest score
+        PcbHistParams ph;
+        ph.in = m.in; ph.q = w->rb.q; ph.state = w->score;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) ph.alpha[i] = m.alpha[i];
+        const int hgrid = hist_grid(ph);
+        const bool small = k <= PCB_REG_SMALL;
+        StatsSelectParams ss;
+        ss.m = PCB_RANKS; ss.state = w->score; ss.tau = w->rb.tm; ss.kept = w->rb.tm_kept;
+        for (int j = 0; j < STATS_MAX_RANKS; ++j) ss.rank[j] = j == PCB_CUT ? q : 1ull;
+        select_levels<KStatsSelect>(streams, k, ss, ss, STATS_SELECT_LDS, [&](int level, unsigned long long* hist) {
+            ph.level = level; ph.hist = hist;
+            for (int first = 0; first < k; first += TIES_GROUP) {
+                ph.first = first; ph.count = std::min(TIES_GROUP, k - first);
+                const size_t lds = (LDS_SCRATCH_FLOATS + pcb_hist_lds_words(level, ph.count)) * 4;
+                if (small) be.template launch<KPcbHist>(hgrid, 256, lds, ph, stream);
+                else be.template launch<KPcbHistAny>(hgrid, 256, lds, ph, stream);
+            }
+        });
+
+        const int grid = stream_grid((d.n + 7) / 8, 256, m.chunks);
+        const size_t lds = (LDS_SCRATCH_FLOATS + pcb_merge_lds_words(k, 256)) * 4;
+        if (small) be.template launch<KPcbMerge>(grid, 256, lds, m, stream);
+        else be.template launch<KPcbMergeAny>(grid, 256, lds, m, stream);
+
+        PcbReadback host;
+        if ((rc = delta_readback("pcb_merge", k, &w->rb, host))) return rc;      // the call's one synchronisation
+        if (rep) {
+            for (int i = 0; i < k; ++i) {
+                rep->lo[i] = host.bounds[i]; rep->hi[i] = host.bounds[TIES_MAX_MODELS + i];
+                rep->M[i] = host.tm[PCB_MAX * TIES_MAX_MODELS + i]; rep->t[i] = host.tm[PCB_CUT * TIES_MAX_MODELS + i];
+                rep->positive[i] = host.positive[i]; rep->selected[i] = host.tm_kept[PCB_CUT * TIES_MAX_MODELS + i];
+            }
+            rep->covered = host.counts[PCB_COVERED]; rep->contested = host.counts[PCB_CONTESTED];
+        }
+        return SMHIP_OK;
+    }
+    int pcb_fn_array(int op, const double* x, double* y, size_t n, bool on_device) {         // sm_tanh
+        return fn_array<KPcbFn, PcbFnParams>([](int o, double v) { return pcb_fn(o, v); }, op, x, y, n, on_device);
     }
 
     // ---- Task-vector statistics (sm_stats.hpp; smhip_delta_stats): the three selection levels for every density at once,

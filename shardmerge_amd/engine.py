@@ -168,6 +168,21 @@ class FusionMergeReport:
 
 
 @dataclass
+class PcbMergeReport:
+    n: int = 0                                                       # elements of the tensor
+    clip_rank: int = 0                                               # r = floor(clip * n): magnitudes clamped at either end
+    q: int = 0                                                       # max(1, floor(ratio * n)): scores asked for per finetune
+    lo: List[float] = field(default_factory=list)                    # the clip bounds of |tv_i|: exact order statistics
+    hi: List[float] = field(default_factory=list)
+    t: List[float] = field(default_factory=list)                     # the q-th largest score of finetune i (0: fewer are positive)
+    M: List[float] = field(default_factory=list)                     # its largest score
+    positive: List[int] = field(default_factory=list)                # entries with a score above 0
+    selected: List[int] = field(default_factory=list)                # entries with a score >= t_i and above 0
+    covered: int = 0                                                 # elements that some finetune gives a weight above 0
+    contested: int = 0                                               # elements that at least two do
+
+
+@dataclass
 class DeltaStatsReport:
     n: int = 0                                                       # elements of the tensor
     densities: List[float] = field(default_factory=list)             # rho_q, as given
@@ -556,7 +571,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion, PCB; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -972,6 +987,52 @@ class Engine:
         y = torch.empty_like(x)
         self.ctx.check(self.lib.dll.smhip_fusion_fn(self.ctx.h, self.FUSION_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
                                                     1 if on_device else 0, self._stream() if on_device else None))
+        if on_device and self.device.type != "cpu":
+            torch.cuda.synchronize(self.device)
+        return y.cpu()
+
+    # -- PCB (parameter competition balancing) ---------------------------------------------------
+    PCB_FNS = {"tanh": _lib.PCB_TANH}
+
+    def pcb_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                  base_out: torch.Tensor, *, ratio: float = 0.1, clip: float = 0.0001, lam: float = 1.0,
+                  want_delta: bool = False, layer_name: str = ""):
+        """PCB merge of one tensor of any shape (``smhip_pcb_merge``; the function is stated in
+        include/shardmerge_hip.h): every weighted entry ``tv_i = (finetune_i - base_i) * alpha_i`` is scored by how
+        large it is within its own finetune (its magnitude, clamped at the ``clip`` share of either end and min-max
+        normalised, through ``exp``) times how well it agrees with the sum of all entries of its element (through
+        ``tanh``, entries that oppose the sum score 0); per finetune the ``ratio`` share of the highest scores is kept,
+        rescaled to [0, 1], and the clamped entries are averaged with those weights, times ``lam``, added onto
+        ``base_out`` in its dtype.  Returns (out, PcbMergeReport[, the fp32 merged delta before ``lam``]).  A NaN or Inf
+        in a delta raises ValueError naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if not (0.0 < float(ratio) <= 1.0):
+            raise ValueError(f"pcb_merge: ratio {ratio} is not in (0, 1]")
+        if not (0.0 <= float(clip) < 0.5):
+            raise ValueError(f"pcb_merge: clip {clip} is not in [0, 0.5)")
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"pcb_merge: lam {lam} is not finite")
+        desc, rep, k = _lib.PcbDesc(), _lib.PcbReport(), len(finetunes)
+        desc.ratio, desc.clip, desc.lam = float(ratio), float(clip), float(lam)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "pcb_merge")
+        desc.n = bo.numel()
+        self._run_delta_merge(self.lib.dll.smhip_pcb_merge, desc, rep, out, delta, layer_name)
+        per = lambda a, cast: [cast(a[i]) for i in range(k)]
+        report = PcbMergeReport(n=int(desc.n), clip_rank=int(rep.clip_rank), q=int(rep.q), lo=per(rep.lo, float), hi=per(rep.hi, float),
+                                t=per(rep.t, float), M=per(rep.M, float), positive=per(rep.positive, int),
+                                selected=per(rep.selected, int), covered=int(rep.covered), contested=int(rep.contested))
+        return (out, report, delta) if want_delta else (out, report)
+
+    def pcb_fn(self, op: str, x: torch.Tensor, on_device: bool = True) -> torch.Tensor:
+        """``sm_tanh`` of csrc/sm_pcb.hpp over an fp64 array (``smhip_pcb_fn``): by a kernel on the engine's device, or
+        on the host.  Returns an fp64 CPU tensor."""
+        if op not in self.PCB_FNS:
+            raise ValueError(f"pcb_fn: op {op!r} is not one of {sorted(self.PCB_FNS)}")
+        x = x.detach().to(torch.float64).contiguous().reshape(-1)
+        x = x.to(self.device) if on_device else x.cpu()
+        y = torch.empty_like(x)
+        self.ctx.check(self.lib.dll.smhip_pcb_fn(self.ctx.h, self.PCB_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
+                                                 1 if on_device else 0, self._stream() if on_device else None))
         if on_device and self.device.type != "cpu":
             torch.cuda.synchronize(self.device)
         return y.cpu()

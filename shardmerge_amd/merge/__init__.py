@@ -24,6 +24,7 @@ _OPERATOR_CLASSES = {
     "multislerp": ("spherical", "MultiSlerpMerge"),
     "arcee_fusion": ("fusion", "ArceeFusionMerge"),
     "nearswap": ("fusion", "NearSwapMerge"),
+    "pcb": ("pcb", "PcbMerge"),
 }
 
 
