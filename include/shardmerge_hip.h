@@ -998,6 +998,79 @@ typedef struct {
 size_t smhip_xl_probe_workspace(int rows, int cols, int L);    /* DELTA_MM: (rows, cols, L); GRAM: (rows, 1, L) */
 int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* desc, void* stream);
 
+/* ---- TSV merge (Gargiulo et al. 2025, "Task Singular Vectors"): the one operator that treats a task vector as a matrix.
+ *      One 2-D tensor [rows x cols], finetunes i = 0..k-1 in order, each with its own base and a weight alpha_i >= 0.
+ *      An entry with alpha_i == 0 is inactive: it is not read and its report fields are zero; k_a counts the others.
+ *      rank 1..256, power iterations q 0..4, r = min(rank, rows, cols), L = xl_panel_width(rows, cols, r) =
+ *      min(ceil16(r + 8), ceil16(min(rows, cols))), and k_a * r <= 256.  Every primitive (the sketch, the delta products,
+ *      orth, gram, pmm, eig) is the one stated at smhip_lora_extract.
+ *        1. Per active finetune, steps 1 - 4 of smhip_lora_extract on D_i = fp32(finetune_i) - fp32(base_i) with ONE
+ *           sketch Omega [cols x L] under `key` for the whole call: Q_i [rows x L], C_i = D_i^T Q_i [cols x L], the orth
+ *           ranks, and delta_sq_i as its step 7.  A NaN or Inf fails the call with SMHIP_ERR_NONFINITE (the message
+ *           names the finetune); out is then unspecified.
+ *        2. Singular triplets.  gram(C_i) = V_i diag(lambda_i) V_i^T (eig), sigma_ij = sqrt(max(lambda_ij, 0)),
+ *           rho_i = #{j < r : lambda_ij > 1e-12 * lambda_i0} (these j are a prefix: lambda descends), share_i =
+ *           (((0 + sigma_i0^2) + ...) + sigma_i,r-1^2) / delta_sq_i with sigma^2 = max(lambda, 0), 0 when delta_sq_i == 0.
+ *           U_i = pmm(Q_i, fp32(V_i[:, :rho_i])) [rows x rho_i], W_i = pmm(C_i, T_i), T_i[:, j] = fp32(V_i[:, j] / sigma_ij)
+ *           [cols x rho_i].  R = sum rho_i, Rp = ceil16(R).  U [rows x Rp] and W [cols x Rp] hold the blocks side by side
+ *           in finetune order; columns R .. Rp are exact zeros.  s = concat_i(alpha_i * sigma_ij, j < rho_i), fp64, one
+ *           multiplication each.  R == 0: merged = +0 everywhere and steps 3 - 4 do not run.
+ *        3. Whitening (Loewdin).  G_U = the leading R x R block of gram(U) = E diag(mu) E^T (eig).  In fp64, ONE rounded
+ *           operation at a time, j in index order over the kept j = {mu_j > 1e-6 * mu_0}:
+ *           S_U[a][b] = S_U[a][b] + (E[a][j] * E[b][j]) / sqrt(mu_j), from 0.  kept_U = their number.  S_W, mu_W, kept_W
+ *           from W alike.  (1e-6 is a constant of the definition: the panels are fp32, a Gram eigenvalue far below
+ *           R * 2^-23 of the largest is rounding, and two identical finetunes produce exact duplicates that fall under it.)
+ *        4. Core.  M[a][b] = ((0 + t_0) + t_1) + ... over c = 0..R-1 with t_c = (S_U[a][c] * s_c) * S_W[c][b], fp64, one
+ *           rounded operation at a time; M32 [Rp x Rp] = fp32(M), zero beyond R.  B = pmm(U, M32) [rows x Rp].
+ *        5. Apply ("tsv_apply", v_mfma_f32_16x16x4_f32).  merged[m][n] is ONE fp32 fma chain from +0 over the products
+ *           B[m][k] * W[n][k]; inside every block of 16 consecutive k the chain visits k0 + 4 g + j in the order
+ *           j = 0..3 (outer), g = 0..3 (inner) - a lane's 16-byte load feeds one k of four instructions.
+ *           out = round_to(base_out_dtype, fma(fp32(lambda), merged, fp32(base_out))) (one rounding, then the dtype's);
+ *           delta_out = merged (NOT times lambda).
+ *      At k_a = 1 the result is the rank-r truncation of D_0 times alpha_0 (whitening an orthonormal block changes it
+ *      by rounding only).  Every value is defined bit for bit.  Passes: k_a (2 q + 2) delta products of two tensor
+ *      reads each, k_a reads of both for delta_sq, base_out read and out written once.  Profile names: those of
+ *      smhip_lora_extract ("xl_fill" once per call) and "tsv_apply" once.  The stream is synchronised at every orth and
+ *      eig.  The workspace is the caller's: DEVICE memory, 256-byte aligned, at least
+ *      smhip_tsv_workspace(rows, cols, k, rank) bytes.  SMHIP_ERR_ARG: k outside 1..16, a negative or non-finite alpha,
+ *      lambda not finite, rank outside 1..256, q outside 0..4, k_a * r > 256, n != rows * cols, rows or cols < 1 (n > 0),
+ *      a bad workspace, and the aliasing, alignment, dtype and null-pointer rules of smhip_ties_merge.  n == 0: a no-op,
+ *      the report all zeros. ---- */
+#define SMHIP_TSV_MAX_R 256
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [rows x cols] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];         /* >= 0; 0: the entry is skipped */
+    int in_dtype;
+    const void* base_out; int base_out_dtype;
+    size_t n;                               /* rows * cols */
+    int rows, cols;
+    int rank;                               /* 1..256 */
+    int power_iters;                        /* q, 0..4 */
+    double lambda;
+    uint64_t key;
+    void* workspace; size_t workspace_bytes;
+} smhip_tsv_desc;
+typedef struct {
+    int L, r, R, Rp;
+    int rho[SMHIP_MAX_MODELS];
+    int n_orth[SMHIP_MAX_MODELS];           /* 2 q + 1 per active finetune */
+    int orth_rank[SMHIP_MAX_MODELS][SMHIP_EXTRACT_MAX_ORTH];
+    double sigma[SMHIP_MAX_MODELS][SMHIP_TSV_MAX_R];      /* sigma_i[0 .. r) */
+    double delta_sq[SMHIP_MAX_MODELS], share[SMHIP_MAX_MODELS];
+    double mu_U[SMHIP_TSV_MAX_R], mu_W[SMHIP_TSV_MAX_R];  /* [0 .. R) */
+    int kept_U, kept_W;
+} smhip_tsv_report;
+size_t smhip_tsv_workspace(int rows, int cols, int k, int rank);   /* 0: a bad argument */
+/* out: device, base_out_dtype, [rows x cols].  delta_out (optional): device float, merged.  report (optional): HOST. */
+int smhip_tsv_merge(smhip_ctx* ctx, const smhip_tsv_desc* desc, void* out, float* delta_out,
+                    smhip_tsv_report* report, void* stream);
+/* TEST ABI, as smhip_xl_probe: "tsv_apply" alone.  b [rows x Rp], w [cols x Rp]: DEVICE fp32 panels, contiguous rows,
+ * element-aligned; Rp a multiple of 16, 0..256. */
+int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
+                    int base_out_dtype, double lambda, void* out, float* delta_out, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device
@@ -1042,7 +1115,9 @@ int smhip_debug_option(smhip_ctx* ctx, const char* key, long value);
  * "spec_checked" / "spec_hits": how many speculations this context has checked / confirmed since it was created;
  * "aten_fast" / "aten_group" / "aten_slow": chunks the last smhip_reference_cpu_norm composed from their summaries /
  * crossed with the group summaries / walked cooperatively
- * ("aten_serial" = 1 as an option selects the old serial single-work-group chain instead) */
+ * ("aten_serial" = 1 as an option selects the old serial single-work-group chain instead);
+ * "eig_host_us": microseconds this context has spent on the host in the Jacobi eigensolver of smhip_lora_extract and
+ * smhip_tsv_merge since it was created */
 int smhip_debug_query(smhip_ctx* ctx, const char* key, long* value);
 
 /* ---- profiling: per-kernel device time measured with HIP events on the

@@ -262,7 +262,28 @@ class XlProbeDesc(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-DELLA_MAX_COLS = 32768          # the longest row smhip_della_merge ranks (a row is sorted in LDS)
+TSV_MAX_R = 256
+
+
+class TsvDesc(C.Structure):
+    """smhip_tsv_desc: the leading fields of the delta merges, then the shape, rank, q, lambda, key and the workspace"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("rank", C.c_int), ("power_iters", C.c_int),
+                                         ("lam", C.c_double), ("key", C.c_uint64),
+                                         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class TsvReport(C.Structure):
+    """smhip_tsv_report"""
+    _fields_ = [("L", C.c_int), ("r", C.c_int), ("R", C.c_int), ("Rp", C.c_int),
+                ("rho", C.c_int * MAX_MODELS), ("n_orth", C.c_int * MAX_MODELS),
+                ("orth_rank", (C.c_int * EXTRACT_MAX_ORTH) * MAX_MODELS),
+                ("sigma", (C.c_double * TSV_MAX_R) * MAX_MODELS),
+                ("delta_sq", C.c_double * MAX_MODELS), ("share", C.c_double * MAX_MODELS),
+                ("mu_U", C.c_double * TSV_MAX_R), ("mu_W", C.c_double * TSV_MAX_R),
+                ("kept_U", C.c_int), ("kept_W", C.c_int)]
+
+
+DELLA_MAX_COLS = 32768         # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
 class LayerReport(C.Structure):
@@ -340,6 +361,10 @@ class SmhipLibrary:
         d.smhip_xl_probe_workspace.argtypes = [I, I, I]
         d.smhip_xl_probe_workspace.restype = C.c_size_t
         d.smhip_xl_probe.argtypes = [P, C.POINTER(XlProbeDesc), P]
+        d.smhip_tsv_workspace.argtypes = [I, I, I, I]
+        d.smhip_tsv_workspace.restype = C.c_size_t
+        d.smhip_tsv_merge.argtypes = [P, C.POINTER(TsvDesc), P, P, C.POINTER(TsvReport), P]
+        d.smhip_tsv_probe.argtypes = [P, P, P, I, I, I, P, I, D, P, P, P]
         d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

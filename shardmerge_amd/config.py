@@ -121,6 +121,19 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # pcb_ratio: 0.1          #   0 < pcb_ratio <= 1: the share of each finetune's scores that is kept
       # pcb_clip: 0.0001        #   0 <= pcb_clip < 0.5: the share of magnitudes clamped at either end
       # pcb_lambda: 1.0         #   scales the merged delta
+                                # | tsv (TSV-Merge, Gargiulo et al. 2025; no counterpart in the reference): a block tensor's
+                                #   delta is taken as a MATRIX ([shape[0] x the rest]): its tsv_rank leading singular
+                                #   triplets by a randomized subspace iteration, the singular vectors of all covering
+                                #   finetunes whitened together so that overlapping subspaces count once, the delta rebuilt
+                                #   with the singular values times alpha.  1-D tensors and tensors one entry covers take the
+                                #   normalised weighted mean of their deltas (dare_linear at density 1) times tsv_lambda.
+                                #   alphas >= 0 with a sum > 0.  A layer whose k covering entries give
+                                #   k * min(tsv_rank, rows, cols) > 256 is an error before anything is written.  The
+                                #   spectral keys, norm_mode, task_add_models and every other family's keys are rejected; keys:
+      # tsv_rank: 64            #   an integer in 1..256: singular triplets kept per finetune
+      # tsv_power_iters: 2      #   an integer in 0..4: power steps of the subspace iteration
+      # tsv_lambda: 1.0         #   scales the merged delta
+      # seed: 0                 #   an integer in [0, 2^63): keys the sketch with the tensor's name (no position enters)
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -148,7 +161,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -171,6 +184,8 @@ SPHERE_OPTION_DEFAULTS = {"karcher_max_iter": 10, "karcher_tol": 1e-5, "sphere_r
 FUSION_OPERATORS = ("arcee_fusion", "nearswap")          # the pairwise family: one model onto its base, no weights
 FUSION_OPTION_DEFAULTS = {"fusion_iqr": 1.5, "nearswap_t": None}      # nearswap_t has no default: it is required
 PCB_OPTION_DEFAULTS = {"pcb_ratio": 0.1, "pcb_clip": 0.0001, "pcb_lambda": 1.0}
+TSV_OPTION_DEFAULTS = {"tsv_rank": 64, "tsv_power_iters": 2, "tsv_lambda": 1.0, "seed": 0}
+TSV_MAX_VECTORS = 256                               # k * min(tsv_rank, rows, cols) at most: the width of the whitened panels
 
 
 def _breadcrumbs_band(opts: Dict[str, Any]) -> None:
@@ -284,6 +299,16 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "della": "(it drops nothing at random)",
                            "consensus_ta": "(it weighs by agreement with the sum, without masks)",
                            "arcee_fusion": "(it merges several models by their scores)"}),
+    _OptionFamily(("tsv",), TSV_OPTION_DEFAULTS,
+                  {"tsv_rank": ("int", 1, 256), "tsv_power_iters": ("int", 0, 4), "tsv_lambda": _LAMBDA, "seed": "seed"},
+                  earlier={"ties": "(it truncates by singular value, not by magnitude: tsv_rank, tsv_lambda)",
+                           "dare_ties": "(it drops nothing at random; its seed keys the sketch)",
+                           "breadcrumbs": "(it truncates by singular value, not by magnitude)",
+                           "model_stock": "(it whitens singular vectors and weights by alpha)",
+                           "sce": "(it selects singular triplets, not entries: tsv_rank)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it masks nothing)",
+                           "arcee_fusion": "(it merges several models by their singular vectors)"}),
 )
 
 
@@ -478,6 +503,11 @@ class MergeConfig:
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
                 raise click.BadParameter(f"operator sce needs finetune_merge alphas >= 0 with a sum > 0 (an alpha is a prior on the "
                                          f"finetune's weight), not {alphas}")
+        if operator == "tsv":
+            alphas = [m.alpha for m in raw["finetune_merge"]]
+            if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
+                raise click.BadParameter(f"operator tsv needs finetune_merge alphas >= 0 with a sum > 0 (an alpha scales the "
+                                         f"finetune's singular values; 0 leaves the finetune out), not {alphas}")
         if operator in FUSION_OPERATORS:
             for m in raw["finetune_merge"]:
                 if isinstance(m.alpha, bool) or not isinstance(m.alpha, (int, float)) or m.alpha != 1:

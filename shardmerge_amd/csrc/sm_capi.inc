@@ -527,6 +527,51 @@ int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* d, void* stream) {
     SM_FINISH(ctx, ctx->pipe.delta.xl_probe(*d));
 }
 
+size_t smhip_tsv_workspace(int rows, int cols, int k, int rank) {
+    if (rows < 1 || cols < 1 || k < 1 || k > SMHIP_MAX_MODELS || rank < 1 || rank > smhip::XL_MAX_RANK) return 0;
+    return smhip::DeltaHost<SM_BACKEND>::tsv_layout(rows, cols, k, rank).total;
+}
+
+int smhip_tsv_merge(smhip_ctx* ctx, const smhip_tsv_desc* d, void* out, float* delta_out, smhip_tsv_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "tsv_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            if (d->rank < 1 || d->rank > smhip::XL_MAX_RANK) return "rank out of range (1..256)";
+            if (d->power_iters < 0 || d->power_iters > smhip::XL_MAX_POWER) return "power_iters out of range (0..4)";
+            for (int i = 0; i < d->k; ++i)
+                if (d->alpha[i] < 0.0) return "an alpha is negative";
+            return nullptr;
+        }))
+        return rc;
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("tsv_merge: ") + what); };
+    if (d->n > 0) {
+        if (d->rows < 1 || d->cols < 1 || (size_t)d->rows * (size_t)d->cols != d->n) return bad("rows and cols must be >= 1 and rows * cols == n");
+        int active = 0;
+        for (int i = 0; i < d->k; ++i) active += d->alpha[i] != 0.0;
+        const int r = std::min(d->rank, std::min(d->rows, d->cols));
+        if (active * r > SMHIP_TSV_MAX_R) return bad("active finetunes * min(rank, rows, cols) exceeds 256");
+        if (d->n / smhip::GEO_SEG_ELEMS > (size_t)1 << 30) return bad("tensor too large");
+        if (!d->workspace || (uintptr_t)d->workspace % 256 || d->workspace_bytes < smhip_tsv_workspace(d->rows, d->cols, d->k, d->rank))
+            return bad("the workspace is null, not 256-byte aligned or too small (smhip_tsv_workspace)");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.tsv_merge(*d, out, delta_out, report));
+}
+
+int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
+                    int base_out_dtype, double lambda, void* out, float* delta_out, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("tsv_probe: ") + what); };
+    if (rows < 1 || cols < 1 || Rp < 0 || Rp > SMHIP_TSV_MAX_R || Rp % 16) return bad("bad shape");
+    if (!base_out || !out || (Rp > 0 && (!b || !w))) return bad("null pointer");
+    if (base_out_dtype < SMHIP_BF16 || base_out_dtype > SMHIP_F32) return bad("bad dtype");
+    const size_t oes = base_out_dtype == SMHIP_F32 ? 4 : 2;
+    if ((uintptr_t)b % 4 || (uintptr_t)w % 4 || (uintptr_t)delta_out % 4 || (uintptr_t)base_out % oes || (uintptr_t)out % oes)
+        return bad("a pointer is not aligned to its element size");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.tsv_probe(b, w, rows, cols, Rp, base_out, base_out_dtype, lambda, out, delta_out));
+}
+
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
     SM_GUARD(ctx);
     if (!norm_out || (n > 0 && !x)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");
@@ -606,6 +651,7 @@ int smhip_debug_query(smhip_ctx* ctx, const char* key, long* value) {
         *value = (long)v3[std::string(key) == "aten_fast" ? 0 : std::string(key) == "aten_group" ? 1 : 2];
         SM_FINISH(ctx, SMHIP_OK);
     }
+    if (std::string(key) == "eig_host_us") { *value = (long)ctx->pipe.delta.eig_host_us; SM_FINISH(ctx, SMHIP_OK); }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug query");
 }
 

@@ -1,11 +1,12 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, the task-vector statistics and the low-rank extraction (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, the task-vector statistics and the low-rank extraction (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
 // The passes that several operators launch are written once, ahead of the operators.
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -24,6 +25,7 @@
 #include "sm_extract.hpp"
 #include "sm_fusion.hpp"
 #include "sm_pcb.hpp"
+#include "sm_tsv.hpp"
 
 namespace smhip {
 
@@ -109,6 +111,9 @@ SM_KERNEL_TAG_LB(KPcbHistAny, PcbHistParams, "pcb_hist", k_pcb_hist<TIES_MAX_MOD
 SM_KERNEL_TAG_LB(KPcbMerge, PcbMergeParams, "pcb_merge", k_pcb_merge<PCB_REG_SMALL>(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KPcbMergeAny, PcbMergeParams, "pcb_merge", k_pcb_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
 SM_KERNEL_TAG_LB(KPcbFn, PcbFnParams, "pcb_fn", k_pcb_fn(ex, p), 256, 4)
+// TSV merge (sm_tsv.hpp): base_out + lambda * B W^T on fp32 MFMA, four waves of 4 x 4 accumulator tiles (64 registers);
+// everything before it runs on the kernels of the low-rank extraction
+SM_KERNEL_TAG_LB(KTsvApply, TsvApplyParams, "tsv_apply", k_tsv_apply(ex, p), 256, 2)
 // the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
@@ -118,6 +123,7 @@ SM_KERNEL_TAG_LB(KPcbFn, PcbFnParams, "pcb_fn", k_pcb_fn(ex, p), 256, 4)
 #define SM_SIDE_KERNELS_9(X) X(KXlFill) X(KXlDeltaMm) X(KXlFold) X(KXlGram) X(KXlGramFold) X(KXlPanelMm)
 #define SM_SIDE_KERNELS_10(X) X(KFusionRowKl) X(KFusionHist) X(KFusionSelect) X(KFusionMergeArcee) X(KFusionMergeNear) X(KFusionFn)
 #define SM_SIDE_KERNELS_11(X) X(KPcbHist) X(KPcbHistAny) X(KPcbMerge) X(KPcbMergeAny) X(KPcbFn)
+#define SM_SIDE_KERNELS_12(X) X(KTsvApply)
 
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
@@ -159,6 +165,7 @@ class DeltaHost {
     std::string& err;
     void*& stream;
     size_t della_slab_rows = 0;               // test hook "della_slab_rows": rows per slab (0: at most 2^26 elements per finetune)
+    unsigned long long eig_host_us = 0;       // debug query "eig_host_us": host time in xl_sym_eig since the context was created
 
     DeltaHost(B& be_, std::string& err_, void*& stream_) : be(be_), err(err_), stream(stream_) {}
     ~DeltaHost() { if (ws_.p) be.free(ws_.p); }
@@ -1095,19 +1102,32 @@ class DeltaHost {
         f.part = m.part; f.out = out; f.n = (size_t)M * L; f.nseg = m.nseg; f.flags = (uint32_t*)((char*)ws + y.tail) + 2;
         be.template launch<KXlFold>((int)((f.n + 255) / 256), 256, 0, f, stream);
     }
-    void xl_gram(const float* pan, int m, int L, void* ws, const XlLayout& y) {
+    // gram of the leading L columns of a panel of `pitch` floats per row: partials to `part`, the matrix to `G`
+    void xl_gram_at(const float* pan, int m, int L, int pitch, double* part, double* G) {
         XlGramParams g;
-        g.pan = pan; g.m = m; g.L = L; g.part = (double*)((char*)ws + y.gpart);
+        g.pan = pan; g.m = m; g.L = L; g.pitch = pitch; g.part = part;
         const int nseg = (m + XL_GSEG - 1) / XL_GSEG;
         be.template launch<KXlGram>(nseg * xl_gram_tiles(L), 256, 256 * sizeof(double), g, stream);
         XlGramFoldParams f;
-        f.part = g.part; f.G = (double*)((char*)ws + y.G); f.L = L; f.nseg = nseg;
+        f.part = g.part; f.G = G; f.L = L; f.nseg = nseg;
         be.template launch<KXlGramFold>((L * L + 255) / 256, 256, 0, f, stream);
     }
-    void xl_panel_mm(const float* pan, int m, int L, const float* t, int L2, void* out, int out_dtype, int store_trans) {
+    void xl_gram(const float* pan, int m, int L, void* ws, const XlLayout& y) {
+        xl_gram_at(pan, m, L, L, (double*)((char*)ws + y.gpart), (double*)((char*)ws + y.G));
+    }
+    // pan_pitch / out_pitch 0: the panel's rows are L floats, the result's L2 elements apart
+    void xl_panel_mm(const float* pan, int m, int L, const float* t, int L2, void* out, int out_dtype, int store_trans,
+                     int pan_pitch = 0, int out_pitch = 0, int col0 = 0) {
         XlPanelMmParams q;
         q.pan = pan; q.t = t; q.out = out; q.m = m; q.L = L; q.L2 = L2; q.out_dtype = out_dtype; q.store_trans = store_trans;
+        q.pan_pitch = pan_pitch ? pan_pitch : L; q.out_pitch = out_pitch ? out_pitch : L2; q.col0 = col0;
         be.template launch<KXlPanelMm>((int)(((size_t)m * L2 + 255) / 256), 256, 0, q, stream);
+    }
+    // xl_sym_eig with its host time added to eig_host_us (what tools/tsv_bench.py reads)
+    void xl_sym_eig_timed(int n, double* a, double* lam, double* v) {
+        const auto t0 = std::chrono::steady_clock::now();
+        xl_sym_eig(n, a, lam, v);
+        eig_host_us += (unsigned long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     }
     // reads the flags and the Gram back (one synchronisation) and decomposes it; false: the panel or its Gram held a NaN
     // or an Inf (lam and V are then zeros)
@@ -1121,7 +1141,7 @@ class DeltaHost {
         be.d2h(G.data(), (char*)ws + y.G, G.size() * 8, stream);
         if (!be.ok()) return true;
         for (double v : G) if (!geo_finite(v)) return false;
-        xl_sym_eig(L, G.data(), lam.data(), V.data());
+        xl_sym_eig_timed(L, G.data(), lam.data(), V.data());
         return true;
     }
     // Q = orth(Y) (step 6): y_pan -> q_pan, both [m x L]; returns the kept rank, -1: not finite
@@ -1143,6 +1163,34 @@ class DeltaHost {
         xl_panel_mm(y_pan, m, L, dT, L, q_pan, DT_F32, 0);
         return kept;
     }
+    void xl_fill(float* out, int nrows, int L, uint64_t key) {
+        XlFillParams f;
+        f.out = out; f.n = (size_t)nrows * L; f.key = key;
+        be.template launch<KXlFill>((int)(((f.n + 31) / 32 + 255) / 256), 256, 0, f, stream);
+    }
+    // steps 2 - 4 of smhip_lora_extract, shared with smhip_tsv_merge: from the sketch `omega` [cols x L] (which may be
+    // p0) to Q [rows x L] in p0 and C = D^T Q [cols x L] in p1.  The kept rank of each orth goes to orth_rank[n_orth++];
+    // false: a panel held a NaN or an Inf
+    bool xl_range(const void* ft, const void* base, int dtype, int rows, int cols, int L, int power_iters, const float* omega,
+                  float* p0, float* p1, void* ws, const XlLayout& y, int* orth_rank, int& n_orth) {
+        auto mm = [&](int trans, const float* x, float* out) { xl_delta_mm(ft, base, dtype, rows, cols, trans, L, x, out, ws, y); };
+        mm(0, omega, p1);                                           // Y
+        n_orth = 0;
+        auto orth = [&](int m) {                                    // p1 -> p0
+            const int kept = xl_orth(p1, p0, m, L, ws, y);
+            if (kept >= 0) orth_rank[n_orth++] = kept;
+            return kept >= 0;
+        };
+        for (int it = 0; it < power_iters; ++it) {
+            if (!orth(rows)) return false;
+            mm(1, p0, p1);                                          // Z
+            if (!orth(cols)) return false;
+            mm(0, p0, p1);                                          // Y
+        }
+        if (!orth(rows)) return false;                              // Q in p0
+        mm(1, p0, p1);                                              // C in p1
+        return true;
+    }
     int lora_extract(const smhip_extract_desc& d, void* a_out, void* b_out, smhip_extract_report* rep) {
         const XlLayout y = xl_layout(d.rows, d.cols, d.rank);
         const int L = y.L, rows = d.rows, cols = d.cols, r = d.rank;
@@ -1161,27 +1209,10 @@ class DeltaHost {
         ties_inputs(in, 1, d.in_dtype, (size_t)rows * cols, &d.finetune, &d.base, true);
         gram_pass(in, false, GEO_SEG_ELEMS, y.eseg, (double*)((char*)ws + y.epart), flags, E);
 
-        XlFillParams f;
-        f.out = p0; f.n = (size_t)cols * L; f.key = d.key;
-        be.template launch<KXlFill>((int)(((f.n + 31) / 32 + 255) / 256), 256, 0, f, stream);
-        auto mm = [&](int trans, const float* x, float* out) {
-            xl_delta_mm(d.finetune, d.base, d.in_dtype, rows, cols, trans, L, x, out, ws, y);
-        };
-        mm(0, p0, p1);                                              // Y
+        xl_fill(p0, cols, L, d.key);
         int n_orth = 0;
-        auto orth = [&](int m) {                                    // p1 -> p0
-            const int kept = xl_orth(p1, p0, m, L, ws, y);
-            if (kept >= 0) rep->orth_rank[n_orth++] = kept;
-            return kept >= 0;
-        };
-        for (int it = 0; it < d.power_iters; ++it) {
-            if (!orth(rows)) return nonfinite();
-            mm(1, p0, p1);                                          // Z
-            if (!orth(cols)) return nonfinite();
-            mm(0, p0, p1);                                          // Y
-        }
-        if (!orth(rows)) return nonfinite();                        // Q in p0
-        mm(1, p0, p1);                                              // C in p1
+        if (!xl_range(d.finetune, d.base, d.in_dtype, rows, cols, L, d.power_iters, p0, p0, p1, ws, y, rep->orth_rank, n_orth))
+            return nonfinite();
         rep->n_orth = n_orth;
         xl_gram(p1, cols, L, ws, y);
         std::vector<double> lam, V;
@@ -1221,6 +1252,179 @@ class DeltaHost {
         rep->share = e_host[0] > 0.0 ? geo_ddiv(sum, e_host[0]) : 0.0;
         return SMHIP_OK;
     }
+    // ---- TSV merge (sm_tsv.hpp; smhip_tsv_merge).  The caller's workspace: the extraction's (for L) | Omega [cols x L] |
+    // U [rows x Rpm] | W [cols x Rpm] | B [rows x Rpm] | the partials of a Gram of width Rpm | that Gram | M32 [Rpm x Rpm],
+    // Rpm = min(256, ceil16(k r)) the widest the panels can get.  U and W have Rpm floats per row whatever Rp is. ----
+    struct TsvLayout {
+        XlLayout y;
+        int r, Rpm;
+        size_t omega, U, W, Bp, gpart, G, M, total;
+    };
+    static TsvLayout tsv_layout(int rows, int cols, int k, int rank) {
+        TsvLayout t;
+        t.r = std::min(rank, std::min(rows, cols));
+        t.y = xl_layout_L(rows, cols, xl_panel_width(rows, cols, t.r), t.r);
+        t.Rpm = std::min(TSV_MAX_R, xl_ceil16(k * t.r));
+        const size_t mx = (size_t)std::max(rows, cols), Rpm = (size_t)t.Rpm;
+        t.omega = t.y.total;
+        t.U = t.omega + round_up((size_t)cols * t.y.L * 4, 256);
+        t.W = t.U + round_up((size_t)rows * Rpm * 4, 256);
+        t.Bp = t.W + round_up((size_t)cols * Rpm * 4, 256);
+        t.gpart = t.Bp + round_up((size_t)rows * Rpm * 4, 256);
+        t.G = t.gpart + round_up((mx + XL_GSEG - 1) / XL_GSEG * Rpm * Rpm * 8, 256);
+        t.M = t.G + round_up(Rpm * Rpm * 8, 256);
+        t.total = t.M + round_up(Rpm * Rpm * 4, 256);
+        return t;
+    }
+    void tsv_apply(const float* b, int bp, const float* w, int wp, int rows, int cols, int Rp, const void* base_out, int dtype,
+                   double lambda, void* out, float* delta_out) {
+        TsvApplyParams a;
+        a.b = b; a.w = w; a.rows = rows; a.cols = cols; a.Rp = Rp; a.bp = bp; a.wp = wp;
+        a.pvec = (aligned16(b) && aligned16(w) && bp % 4 == 0 && wp % 4 == 0) ? 1 : 0;
+        a.base_out = base_out; a.dtype = dtype; a.lambda = (float)lambda; a.out = out; a.delta_out = delta_out;
+        a.gn = (cols + TSV_WG - 1) / TSV_WG;
+        be.template launch<KTsvApply>((rows + TSV_WG - 1) / TSV_WG * a.gn, 256, 0, a, stream);
+    }
+    int tsv_merge(const smhip_tsv_desc& d, void* out, float* delta_out, smhip_tsv_report* rep) {
+        if (rep) *rep = smhip_tsv_report{};
+        if (d.n == 0) return SMHIP_OK;
+        const TsvLayout t = tsv_layout(d.rows, d.cols, d.k, d.rank);
+        const XlLayout& y = t.y;
+        const int L = y.L, rows = d.rows, cols = d.cols, r = t.r, Rpm = t.Rpm;
+        char* ws = (char*)d.workspace;
+        float* p0 = (float*)ws;
+        float* p1 = (float*)(ws + y.pan);
+        float* omega = (float*)(ws + t.omega);
+        float* U = (float*)(ws + t.U);
+        float* W = (float*)(ws + t.W);
+        float* Bp = (float*)(ws + t.Bp);
+        float* dT = (float*)(ws + y.T);
+        uint32_t* flags = (uint32_t*)(ws + y.tail);                 // [0..1]: the Gram pass's, [2]: xl_fold's
+        double* E = (double*)(ws + y.tail + 16);                    // delta_sq per finetune
+        be.memset(flags, 0, 256, stream);
+        be.memset(U, 0, (size_t)rows * Rpm * 4, stream);
+        be.memset(W, 0, (size_t)cols * Rpm * 4, stream);
+        auto nonfinite = [&](int i) {
+            return fail(SMHIP_ERR_NONFINITE, "tsv_merge: NaN or Inf in finetune - base of finetune " + std::to_string(i));
+        };
+        smhip_tsv_report local;
+        smhip_tsv_report& R_ = rep ? *rep : local;
+        if (!rep) local = smhip_tsv_report{};
+        R_.L = L; R_.r = r;
+
+        xl_fill(omega, cols, L, d.key);
+        std::vector<double> s, sums(d.k, 0.0), lam, V;
+        int R = 0;
+        for (int i = 0; i < d.k; ++i) {
+            if (d.alpha[i] == 0.0) continue;
+            TiesInputs in;
+            ties_inputs(in, 1, d.in_dtype, (size_t)rows * cols, &d.finetune[i], &d.base[i], true);
+            gram_pass(in, false, GEO_SEG_ELEMS, y.eseg, (double*)(ws + y.epart), flags, E + i);
+            if (!xl_range(d.finetune[i], d.base[i], d.in_dtype, rows, cols, L, d.power_iters, omega, p0, p1, ws, y,
+                          R_.orth_rank[i], R_.n_orth[i])) {
+                R_.n_orth[i] = 0;
+                return nonfinite(i);
+            }
+            xl_gram(p1, cols, L, ws, y);
+            const bool finite = xl_eig_readback(L, ws, y, lam, V);
+            if (!be.ok()) return SMHIP_OK;
+            if (!finite) return nonfinite(i);
+            const double cut = geo_dmul(1e-12, lam[0]);
+            int rho = 0;
+            for (int j = 0; j < r; ++j) {
+                const double l2 = lam[j] > 0.0 ? lam[j] : 0.0;
+                R_.sigma[i][j] = geo_dsqrt(l2);
+                sums[i] = geo_dadd(sums[i], l2);
+                if (lam[j] > cut && rho == j) ++rho;
+            }
+            R_.rho[i] = rho;
+            if (rho) {
+                std::vector<float> T((size_t)2 * L * rho);          // V[:, :rho], then V[:, j] / sigma_j, [L x rho] each
+                for (int k = 0; k < L; ++k)
+                    for (int j = 0; j < rho; ++j) {
+                        T[(size_t)k * rho + j] = (float)V[(size_t)k * L + j];
+                        T[(size_t)L * rho + (size_t)k * rho + j] = (float)geo_ddiv(V[(size_t)k * L + j], R_.sigma[i][j]);
+                    }
+                be.h2d(dT, T.data(), T.size() * 4, stream);
+                xl_panel_mm(p0, rows, L, dT, rho, U, DT_F32, 0, 0, Rpm, R);
+                xl_panel_mm(p1, cols, L, dT + (size_t)L * rho, rho, W, DT_F32, 0, 0, Rpm, R);
+            }
+            for (int j = 0; j < rho; ++j) s.push_back(geo_dmul(d.alpha[i], R_.sigma[i][j]));
+            R += rho;
+        }
+        const int Rp = xl_ceil16(R);
+        R_.R = R; R_.Rp = Rp;
+
+        if (R > 0) {
+            // S = sum over the kept j of E_j E_j^T / sqrt(mu_j); 0: fine, else the call's return code
+            bool bad = false;
+            auto whiten = [&](const float* pan, int m, double* mu_out, int& kept, std::vector<double>& S) {
+                xl_gram_at(pan, m, Rp, Rpm, (double*)(ws + t.gpart), (double*)(ws + t.G));
+                std::vector<double> G((size_t)Rp * Rp), A((size_t)R * R), mu(R), Ev((size_t)R * R);
+                be.d2h(G.data(), ws + t.G, G.size() * 8, stream);
+                S.assign((size_t)R * R, 0.0);
+                if (!be.ok()) return;
+                for (int a = 0; a < R; ++a)
+                    for (int b = 0; b < R; ++b) {
+                        A[(size_t)a * R + b] = G[(size_t)a * Rp + b];
+                        if (!geo_finite(A[(size_t)a * R + b])) bad = true;
+                    }
+                if (bad) return;
+                xl_sym_eig_timed(R, A.data(), mu.data(), Ev.data());
+                const double cut = geo_dmul(1e-6, mu[0]);
+                for (int j = 0; j < R; ++j) {
+                    mu_out[j] = mu[j];
+                    if (!(mu[j] > cut)) continue;
+                    ++kept;
+                    const double sq = geo_dsqrt(mu[j]);
+                    for (int a = 0; a < R; ++a) {
+                        const double ea = Ev[(size_t)a * R + j];
+                        for (int b = 0; b < R; ++b)
+                            S[(size_t)a * R + b] = geo_dadd(S[(size_t)a * R + b], geo_ddiv(geo_dmul(ea, Ev[(size_t)b * R + j]), sq));
+                    }
+                }
+            };
+            std::vector<double> SU, SW;
+            whiten(U, rows, R_.mu_U, R_.kept_U, SU);
+            if (!bad) whiten(W, cols, R_.mu_W, R_.kept_W, SW);
+            if (!be.ok()) return SMHIP_OK;
+            if (bad) return fail(SMHIP_ERR_NONFINITE, "tsv_merge: the singular vectors are not finite");
+            std::vector<float> M32((size_t)Rp * Rp, 0.f);
+            std::vector<double> row(R);
+            for (int a = 0; a < R; ++a) {
+                for (int b = 0; b < R; ++b) row[b] = 0.0;
+                for (int c = 0; c < R; ++c) {
+                    const double us = geo_dmul(SU[(size_t)a * R + c], s[c]);
+                    for (int b = 0; b < R; ++b) row[b] = geo_dadd(row[b], geo_dmul(us, SW[(size_t)c * R + b]));
+                }
+                for (int b = 0; b < R; ++b) M32[(size_t)a * Rp + b] = (float)row[b];
+            }
+            float* dM = (float*)(ws + t.M);
+            be.h2d(dM, M32.data(), M32.size() * 4, stream);
+            xl_panel_mm(U, rows, Rp, dM, Rp, Bp, DT_F32, 0, Rpm, Rp, 0);
+        }
+        tsv_apply(Bp, Rp, W, Rpm, rows, cols, Rp, d.base_out, d.base_out_dtype, d.lambda, out, delta_out);
+
+        double e_host[TIES_MAX_MODELS];
+        uint32_t fl[4];
+        be.d2h(e_host, E, sizeof e_host, stream);
+        be.d2h(fl, flags, sizeof fl, stream);                       // the call's last synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (fl[0] || fl[2]) return fail(SMHIP_ERR_NONFINITE, "tsv_merge: NaN or Inf in finetune - base");
+        for (int i = 0; i < d.k; ++i) {
+            if (d.alpha[i] == 0.0) continue;
+            R_.delta_sq[i] = e_host[i];
+            R_.share[i] = e_host[i] > 0.0 ? geo_ddiv(sums[i], e_host[i]) : 0.0;
+        }
+        return SMHIP_OK;
+    }
+    int tsv_probe(const float* b, const float* w, int rows, int cols, int Rp, const void* base_out, int dtype, double lambda,
+                  void* out, float* delta_out) {
+        tsv_apply(b, Rp, w, Rp, rows, cols, Rp, base_out, dtype, lambda, out, delta_out);
+        be.sync(stream);
+        return SMHIP_OK;
+    }
+
     int xl_probe(const smhip_xl_probe_desc& d) {
         const int L = d.L;
         if (d.op == SMHIP_XL_SYM_EIG) {

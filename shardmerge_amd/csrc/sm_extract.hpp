@@ -25,7 +25,8 @@
 //                  q, q + 4, ... in order, a two-step binary tree through LDS ((s0 + s2) + (s1 + s3)).
 //   xl_gram_fold   the segments added in index order, both triangles written.
 //   xl_panel_mm    panel [m x L] . T [L x L2], per element one fp32 fmaf chain over k = 0..L-1 from +0 (VALU), stored as
-//                  an fp32 panel or rounded once into a factor dtype, optionally transposed.
+//                  an fp32 panel or rounded once into a factor dtype, optionally transposed; the panel may be the leading
+//                  columns of a wider one and the result a block of columns of a wider one (row pitches, a column offset).
 //   xl_sym_eig     host: cyclic Jacobi on a symmetric L x L fp64 matrix over geo_dmul / geo_dadd / geo_ddiv / geo_dsqrt,
 //                  each ONE rounded operation, so the hipcc build, the g++ emulator and a numpy restatement agree.
 #pragma once
@@ -243,8 +244,8 @@ SM_HD void k_xl_fold(Ex& ex, const XlFoldParams& p) {
 
 // ---- the Gram of a panel ----
 struct XlGramParams {
-    const float* pan;           // [m x L]
-    int m, L;
+    const float* pan;           // [m x L], `pitch` floats from row to row (L, or more: the leading columns of a wider panel)
+    int m, L, pitch;
     double* part;               // [nseg][L][L]: the tiles with block row <= block column
 };
 SM_HD int xl_gram_tiles(int L) { const int nb = L / 8; return nb * (nb + 1) / 2; }
@@ -263,7 +264,7 @@ SM_HD void k_xl_gram(Ex& ex, const XlGramParams& p) {
         const float* ca = p.pan + a0 + (pi >> 3);
         const float* cb = p.pan + b0 + (pi & 7);
         double acc = 0.0;
-        for (int r = r0 + q; r < r1; r += 4) acc = acc + (double)ca[(size_t)r * p.L] * (double)cb[(size_t)r * p.L];
+        for (int r = r0 + q; r < r1; r += 4) acc = acc + (double)ca[(size_t)r * p.pitch] * (double)cb[(size_t)r * p.pitch];
         red[tid] = acc;
     });
     ex.sync();
@@ -300,12 +301,13 @@ SM_HD void k_xl_gram_fold(Ex& ex, const XlGramFoldParams& p) {
 
 // ---- panel . T ----
 struct XlPanelMmParams {
-    const float* pan;           // [m x L]
+    const float* pan;           // [m x L], pan_pitch floats from row to row
     const float* t;             // [L x L2]
-    void* out;                  // [m x L2], or [L2 x m] when store_trans
+    void* out;                  // [m x L2] as columns col0 .. col0 + L2 of rows of out_pitch elements, or [L2 x m] when store_trans
     int m, L, L2;
     int out_dtype;
     int store_trans;
+    int pan_pitch, out_pitch, col0;
 };
 template <class Ex>
 SM_HD void k_xl_panel_mm(Ex& ex, const XlPanelMmParams& p) {
@@ -316,10 +318,10 @@ SM_HD void k_xl_panel_mm(Ex& ex, const XlPanelMmParams& p) {
         if (e >= (size_t)p.m * p.L2) return;
         const size_t row = e / p.L2;
         const int j = (int)(e % p.L2);
-        const float* pr = p.pan + row * p.L;
+        const float* pr = p.pan + row * p.pan_pitch;
         float acc = 0.f;
         for (int k = 0; k < p.L; ++k) acc = fmaf(pr[k], p.t[(size_t)k * p.L2 + j], acc);
-        lora_put(p.out, p.out_dtype, p.store_trans ? (size_t)j * p.m + row : e, acc);
+        lora_put(p.out, p.out_dtype, p.store_trans ? (size_t)j * p.m + row : row * p.out_pitch + p.col0 + j, acc);
     });
 }
 

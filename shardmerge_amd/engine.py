@@ -218,6 +218,27 @@ class LoraExtractReport:
 
 
 @dataclass
+class TsvReport:
+    rows: int = 0
+    cols: int = 0
+    rank: int = 0                                                    # as asked for
+    power_iters: int = 0
+    width: int = 0                                                   # L, the panel width of the subspace iterations
+    r: int = 0                                                       # min(rank, rows, cols)
+    R: int = 0                                                       # singular triplets kept over all finetunes
+    Rp: int = 0                                                      # ceil16(R), the width of the panels U, W and B
+    rho: List[int] = field(default_factory=list)                     # [i]: triplets finetune i contributes (0: inactive or no delta)
+    sigma: List[List[float]] = field(default_factory=list)           # [i][0 .. r): its singular values
+    delta_sq: List[float] = field(default_factory=list)              # [i]: ||finetune_i - base_i||_F^2
+    share: List[float] = field(default_factory=list)                 # [i]: sum_{j < r} sigma_ij^2 / delta_sq_i
+    orth_ranks: List[List[int]] = field(default_factory=list)        # [i]: the rank every orthonormalisation kept
+    mu_U: List[float] = field(default_factory=list)                  # [0 .. R): eigenvalues of the Gram of the left vectors
+    mu_W: List[float] = field(default_factory=list)                  # ... of the right vectors
+    kept_U: int = 0                                                  # eigenvalues above 1e-6 of the largest: directions whitened
+    kept_W: int = 0
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -1036,6 +1057,64 @@ class Engine:
         if on_device and self.device.type != "cpu":
             torch.cuda.synchronize(self.device)
         return y.cpu()
+
+    # -- TSV (task singular vectors) ------------------------------------------------------------
+    def tsv_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                  base_out: torch.Tensor, *, rank: int = 64, power_iters: int = 2, lam: float = 1.0, key: int = 0,
+                  want_delta: bool = False, layer_name: str = ""):
+        """TSV merge of one tensor with at least two dimensions, viewed as ``[shape[0], rest]`` (``smhip_tsv_merge``; the
+        function is stated in include/shardmerge_hip.h): the ``rank`` leading singular triplets of every delta
+        ``finetune_i - base_i`` by a randomized subspace iteration with ``power_iters`` power steps under ``key``, the
+        singular vectors of all finetunes whitened together (Loewdin) so that overlapping subspaces are counted once, the
+        merged delta rebuilt with the singular values times ``alpha_i`` and added, times ``lam``, onto ``base_out`` in its
+        dtype.  An entry with ``alpha_i == 0`` is skipped; the others must satisfy ``k * min(rank, rows, cols) <= 256``.
+        Returns (out, TsvReport[, the fp32 merged delta before ``lam``]).  A NaN or Inf in a delta raises ValueError
+        naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if isinstance(rank, bool) or not isinstance(rank, int) or not (1 <= rank <= _lib.EXTRACT_MAX_RANK):
+            raise ValueError(f"tsv_merge: rank must be an integer in 1..{_lib.EXTRACT_MAX_RANK}, not {rank!r}")
+        if isinstance(power_iters, bool) or not isinstance(power_iters, int) or not (0 <= power_iters <= _lib.EXTRACT_MAX_POWER):
+            raise ValueError(f"tsv_merge: power_iters must be an integer in 0..{_lib.EXTRACT_MAX_POWER}, not {power_iters!r}")
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"tsv_merge: lam {lam} is not finite")
+        if any(not (float(a) >= 0.0) for a in alphas):
+            raise ValueError(f"tsv_merge: the alphas {list(alphas)} must be >= 0")
+        if base_out.ndim < 2:
+            raise ValueError(f"tsv_merge: {layer_name} has shape {list(base_out.shape)}; at least two dimensions expected")
+        desc, rep, k = _lib.TsvDesc(), _lib.TsvReport(), len(finetunes)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "tsv_merge")
+        desc.n = bo.numel()
+        rows = int(bo.shape[0])
+        cols = int(desc.n // rows) if rows else 0
+        desc.rows, desc.cols, desc.rank, desc.power_iters, desc.lam, desc.key = rows, cols, rank, power_iters, float(lam), int(key)
+        r = min(rank, rows, cols)
+        active = sum(1 for a in alphas if float(a) != 0.0)
+        if active * r > _lib.TSV_MAX_R:
+            raise ValueError(f"tsv_merge: {layer_name}: {active} finetunes x rank {r} = {active * r} singular vectors; at most {_lib.TSV_MAX_R}")
+        if desc.n:
+            ws = self._xl_workspace(int(self.lib.dll.smhip_tsv_workspace(rows, cols, k, rank)))
+            desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
+        self._run_delta_merge(self.lib.dll.smhip_tsv_merge, desc, rep, out, delta, layer_name)
+        report = TsvReport(rows=rows, cols=cols, rank=rank, power_iters=power_iters, width=int(rep.L), r=int(rep.r), R=int(rep.R),
+                           Rp=int(rep.Rp), rho=[int(rep.rho[i]) for i in range(k)],
+                           sigma=[[float(rep.sigma[i][j]) for j in range(rep.r)] for i in range(k)],
+                           delta_sq=[float(rep.delta_sq[i]) for i in range(k)], share=[float(rep.share[i]) for i in range(k)],
+                           orth_ranks=[[int(rep.orth_rank[i][j]) for j in range(rep.n_orth[i])] for i in range(k)],
+                           mu_U=[float(rep.mu_U[j]) for j in range(rep.R)], mu_W=[float(rep.mu_W[j]) for j in range(rep.R)],
+                           kept_U=int(rep.kept_U), kept_W=int(rep.kept_W))
+        return (out, report, delta) if want_delta else (out, report)
+
+    def tsv_probe(self, b: torch.Tensor, w: torch.Tensor, base_out: torch.Tensor, lam: float = 1.0):
+        """``tsv_apply`` alone (``smhip_tsv_probe``; tests): (out, merged) for fp32 panels ``b [rows, Rp]``, ``w [cols, Rp]``
+        and ``base_out [rows, cols]``, which are used where they lie when they are contiguous on the engine's device"""
+        place = lambda t: t if (t.device == self.device and t.is_contiguous()) else self._dev(t)
+        bv, wv, bo = place(b), place(w), place(base_out)
+        rows, cols = bo.shape
+        out = torch.empty_like(bo)
+        merged = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        self._call(self.lib.dll.smhip_tsv_probe(self.ctx.h, bv.data_ptr(), wv.data_ptr(), rows, cols, int(bv.shape[1]), bo.data_ptr(),
+                                                _DTYPE_CODE[bo.dtype], float(lam), out.data_ptr(), merged.data_ptr(), self._stream()))
+        return out, merged
 
     # -- task-vector statistics ----------------------------------------------------------------
     def delta_stats(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],

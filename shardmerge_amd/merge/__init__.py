@@ -25,6 +25,7 @@ _OPERATOR_CLASSES = {
     "arcee_fusion": ("fusion", "ArceeFusionMerge"),
     "nearswap": ("fusion", "NearSwapMerge"),
     "pcb": ("pcb", "PcbMerge"),
+    "tsv": ("tsv", "TsvMerge"),
 }
 
 
