@@ -1071,6 +1071,77 @@ int smhip_tsv_merge(smhip_ctx* ctx, const smhip_tsv_desc* desc, void* out, float
 int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
                     int base_out_dtype, double lambda, void* out, float* delta_out, void* stream);
 
+/* ---- WIDEN merge (Yu, Yu, Yu, Huang, Li, "Extend Model Merging from Fine-Tuned to Pre-Trained Large Language Models via
+ *      Weight Disentanglement", 2024): every weight matrix is disentangled into a magnitude and a direction per column,
+ *      the divergences of each finetune from its base in both are RANKED within the finetune - which makes the measure
+ *      scale-free: a delta a hundred times larger ranks the same - and the ranks become per-column, per-finetune weights
+ *      through a softmax across the finetunes, with the above-average columns calibrated.  The reference has no such
+ *      operator; this section IS its definition (what the paper's code does was recalled, not checked: PAPERS.md).
+ *      One tensor of n elements is viewed as R x C, R = rows (the first dimension; a tensor of rank > 2 is
+ *      [shape[0] x the rest]), C = n / R.  Finetunes i = 0..k-1 in order, 1 <= k <= 16; f_i = fp32(finetune_i),
+ *      b_i = fp32(base_i), x_i = fl32(f_i - b_i).
+ *        1. Column sums (matrix mode, R >= 2).  Per finetune i and column j, in fp64: P = sum_r f[r,j]^2,
+ *           B = sum_r b[r,j]^2, X = sum_r f[r,j] b[r,j].  A product of two fp32 values is exact in fp64, so every addition
+ *           is ONE correctly rounded fp64 addition of an exact product, in this order: the rows are cut into segments
+ *           of 512, segment g = rows [512 g, min(R, 512 (g + 1))); inside a segment the row with local index rho belongs
+ *           to sub-lane u = rho % 8; a sub-lane starts from +0 and adds its rows in ascending rho; the 8 sub-lanes are
+ *           reduced by a binary tree, p_u = p_u + p_(u+s) for u < s, s = 4, 2, 1, the segment's value is p_0; the
+ *           segments' values are added from +0 in ascending g.  The order is a function of R alone - not of the grid,
+ *           the device or the number of processes - and no floating-point atomic takes part.  A NaN or Inf in
+ *           finetune_i or base_i shows as a non-finite P or B and fails the call with SMHIP_ERR_NONFINITE (the message
+ *           lists the finetunes); out is then unspecified.
+ *        2. Divergences (matrix mode), every operation ONE rounded fp64 operation, never an fma:
+ *           m_i[j] = |sqrt(P) - sqrt(B)|;  d_i[j] = 1 - c, den = sqrt(P * B), c = min(1, max(-1, X / den)); where den is
+ *           0 or not finite, d = 0 if P == B, else 1.  A column the finetune did not touch has P == B == X and
+ *           sqrt(P * P) == P, so c = 1 and d = +0 exactly (hence not X / (sqrt(P) * sqrt(B))).  Both are finite and >= +0:
+ *           their bit patterns order as unsigned integers.
+ *           Vector mode (R == 1: norm weights, any tensor whose first dimension is 1): ONE statistic, a_i[j] =
+ *           (double) |x_i[j]| (the paper's rule for 1-D parameters); a non-finite a_i fails the call as above.
+ *        3. Ranks.  rank_i^s[j] = #{j' : statistic s of finetune i at j' is strictly smaller than at j}: equal values
+ *           share a rank, so the result depends on no sort order (DEVIATION: the paper's stable argsort breaks ties by
+ *           index).  sigma = (double) rank / (double) C, one division; with S the sum of the ranks as a 64-bit integer,
+ *           mu_i^s = ((double) S / (double) C) / (double) C.
+ *        4. Scores, per column and statistic: sigma_max = max_i sigma_i, e_i = sm_exp(sigma_i - sigma_max) (sm_exp of
+ *           csrc/sm_fusion.hpp; the argument is <= 0), Z = ((0 + e_0) + e_1) + ..., p_i = e_i / Z;
+ *           score_i = calibration where sigma_i > ratio * mu_i^s (one multiplication, a strict comparison), else p_i.
+ *        5. Weights.  Matrix mode: h = 0.5 * (score^m + score^d), w_i[j] = fp32(alpha_i * h); vector mode:
+ *           w_i[j] = fp32(alpha_i * score).  alpha_i in fp64, of any sign; their sum may be 0: nothing divides by it.
+ *        6. Combine, for element [r, j]: M = ((0 + fl32(w_0[j] * x_0)) + fl32(w_1[j] * x_1)) + ... in fp32, product and
+ *           sum rounded separately; out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M));
+ *           delta_out (optional) = fl32(fp32(lambda) * M): steps 6 and 7 of smhip_dare_merge, so a call whose weights
+ *           all equal fp32(alpha_i) is dare_linear at density 1 without normalize, bit for bit.
+ *      Limits: C <= 65536 (SMHIP_ERR_ARG beyond); n > 0 needs rows >= 1 that divides n; ratio finite, calibration
+ *      finite and >= 0, lambda finite.  Aliasing, alignment, n == 0 (a no-op, the report all zeros), dtypes and the size
+ *      limit: the rules of smhip_ties_merge.
+ *      Passes: "widen_colstats" (matrix mode only: the finetune and its base once each, 2 k tensor passes - a shared
+ *      base is re-read per finetune), "widen_colfold", "widen_rank" (all pairs, O(C^2) integer comparisons per finetune
+ *      and statistic), "widen_coef", "widen_combine" (k + 2 tensor passes with a shared base): 3 k + 2.  Counters are
+ *      integers; the stream is synchronised once, at the end. ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    size_t rows;                            /* R; C = n / rows */
+    double ratio;                           /* the cut: a column is calibrated where sigma > ratio * mu */
+    double calibration;                     /* >= 0: the score of a calibrated column */
+    double lambda;
+} smhip_widen_desc;
+typedef struct {
+    uint64_t rows, cols;                    /* R, C */
+    int vector_mode;                        /* 1: R == 1, the one statistic a at index 0 */
+    double mu[SMHIP_MAX_MODELS][2];         /* [i][s]: s = 0 magnitude (or a), 1 direction */
+    uint64_t calibrated[SMHIP_MAX_MODELS][2];   /* columns with sigma > ratio * mu */
+} smhip_widen_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], lambda * M.  For the tests (optional,
+ * device, element-aligned): stat_out double [k][2][C] (m, d; vector mode a, then zeros), rank_out uint32 [k][2][C],
+ * weight_out float [k][C].  report (optional): HOST. */
+int smhip_widen_merge(smhip_ctx* ctx, const smhip_widen_desc* desc, void* out, float* delta_out, double* stat_out,
+                      uint32_t* rank_out, float* weight_out, smhip_widen_report* report, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device

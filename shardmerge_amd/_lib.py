@@ -265,6 +265,20 @@ class XlProbeDesc(C.Structure):
 TSV_MAX_R = 256
 
 
+class WidenDesc(C.Structure):
+    """smhip_widen_desc: the leading fields of the delta merges, then rows, ratio, calibration and lambda"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_size_t), ("ratio", C.c_double), ("calibration", C.c_double), ("lam", C.c_double)]
+
+
+class WidenReport(C.Structure):
+    """smhip_widen_report"""
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("vector_mode", C.c_int),
+                ("mu", (C.c_double * 2) * MAX_MODELS), ("calibrated", (C.c_uint64 * 2) * MAX_MODELS)]
+
+
+WIDEN_MAX_COLS = 65536          # C of smhip_widen_merge at most
+
+
 class TsvDesc(C.Structure):
     """smhip_tsv_desc: the leading fields of the delta merges, then the shape, rank, q, lambda, key and the workspace"""
     _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("rank", C.c_int), ("power_iters", C.c_int),
@@ -365,6 +379,7 @@ class SmhipLibrary:
         d.smhip_tsv_workspace.restype = C.c_size_t
         d.smhip_tsv_merge.argtypes = [P, C.POINTER(TsvDesc), P, P, C.POINTER(TsvReport), P]
         d.smhip_tsv_probe.argtypes = [P, P, P, I, I, I, P, I, D, P, P, P]
+        d.smhip_widen_merge.argtypes = [P, C.POINTER(WidenDesc), P, P, P, P, P, C.POINTER(WidenReport), P]
         d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

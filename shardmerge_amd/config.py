@@ -134,6 +134,19 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # tsv_power_iters: 2      #   an integer in 0..4: power steps of the subspace iteration
       # tsv_lambda: 1.0         #   scales the merged delta
       # seed: 0                 #   an integer in [0, 2^63): keys the sketch with the tensor's name (no position enters)
+                                # | widen (WIDEN, Yu et al. 2024; no counterpart in the reference): a block tensor is taken as
+                                #   a MATRIX ([shape[0] x the rest]) and weighed per COLUMN (per input feature of a Linear
+                                #   weight): how far each finetune moved the column's magnitude and its direction, both
+                                #   RANKED within the finetune (so a delta a hundred times larger ranks the same), the ranks
+                                #   turned into weights by a softmax across the covering finetunes; a column ranked above
+                                #   widen_ratio times its finetune's mean rank takes widen_calibration instead.  A tensor
+                                #   whose first dimension is 1 (norm weights) ranks the magnitudes of its delta's entries.
+                                #   alphas of any sign.  A block tensor with more than 65536 columns is an error before
+                                #   anything is written.  The spectral keys, norm_mode, task_add_models and every other
+                                #   family's keys are rejected; keys:
+      # widen_ratio: 1.0        #   -1e6 <= widen_ratio <= 1e6: the cut, in units of the mean rank (below 0: every column)
+      # widen_calibration: 1.0  #   0 <= widen_calibration <= 1e6: the score of a column above the cut
+      # widen_lambda: 1.0       #   scales the merged delta
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -161,7 +174,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -185,6 +198,9 @@ FUSION_OPERATORS = ("arcee_fusion", "nearswap")          # the pairwise family: 
 FUSION_OPTION_DEFAULTS = {"fusion_iqr": 1.5, "nearswap_t": None}      # nearswap_t has no default: it is required
 PCB_OPTION_DEFAULTS = {"pcb_ratio": 0.1, "pcb_clip": 0.0001, "pcb_lambda": 1.0}
 TSV_OPTION_DEFAULTS = {"tsv_rank": 64, "tsv_power_iters": 2, "tsv_lambda": 1.0, "seed": 0}
+WIDEN_OPERATORS = ("widen",)
+WIDEN_OPTION_DEFAULTS = {"widen_ratio": 1.0, "widen_calibration": 1.0, "widen_lambda": 1.0}
+WIDEN_MAX_COLS = 65536                              # columns of a block tensor at most: the ranks are counted over all pairs
 TSV_MAX_VECTORS = 256                               # k * min(tsv_rank, rows, cols) at most: the width of the whitened panels
 
 
@@ -309,6 +325,16 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "della": "(it drops nothing at random)",
                            "consensus_ta": "(it masks nothing)",
                            "arcee_fusion": "(it merges several models by their singular vectors)"}),
+    _OptionFamily(WIDEN_OPERATORS, WIDEN_OPTION_DEFAULTS,
+                  {"widen_ratio": (-1e6, 1e6, "[]"), "widen_calibration": (0, 1e6, "[]"), "widen_lambda": _LAMBDA},
+                  earlier={"ties": "(it trims nothing and weighs by column: widen_ratio, widen_lambda)",
+                           "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it trims nothing)",
+                           "model_stock": "(its weights are per column, from the ranks)",
+                           "sce": "(it selects nothing: every column gets a weight)",
+                           "della": "(it drops nothing at random; its ranks are per column, not per entry)",
+                           "consensus_ta": "(it masks nothing)",
+                           "arcee_fusion": "(it merges several models by their columns' ranks)"}),
 )
 
 

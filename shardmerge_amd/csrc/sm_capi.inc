@@ -558,6 +558,28 @@ int smhip_tsv_merge(smhip_ctx* ctx, const smhip_tsv_desc* d, void* out, float* d
     SM_FINISH(ctx, ctx->pipe.delta.tsv_merge(*d, out, delta_out, report));
 }
 
+int smhip_widen_merge(smhip_ctx* ctx, const smhip_widen_desc* d, void* out, float* delta_out, double* stat_out,
+                      uint32_t* rank_out, float* weight_out, smhip_widen_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "widen_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!std::isfinite(d->ratio)) return "ratio is not finite";
+            if (!(d->calibration >= 0.0) || !std::isfinite(d->calibration)) return "calibration must be finite and >= 0";
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            return nullptr;
+        }))
+        return rc;
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("widen_merge: ") + what); };
+    if (d->n > 0) {
+        if (d->rows < 1 || d->n % d->rows) return bad("rows must divide n");
+        const size_t C = d->n / d->rows;
+        if (C > smhip::WIDEN_MAX_COLS) return bad("more than 65536 columns");
+        if ((uintptr_t)stat_out % 8 || (uintptr_t)rank_out % 4 || (uintptr_t)weight_out % 4)
+            return bad("a pointer is not aligned to its element size");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.widen_merge(*d, out, delta_out, stat_out, rank_out, weight_out, report));
+}
+
 int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
                     int base_out_dtype, double lambda, void* out, float* delta_out, void* stream) {
     SM_GUARD(ctx);

@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, the task-vector statistics and the low-rank extraction (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, the task-vector statistics and the low-rank extraction (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -26,6 +26,7 @@
 #include "sm_fusion.hpp"
 #include "sm_pcb.hpp"
 #include "sm_tsv.hpp"
+#include "sm_widen.hpp"
 
 namespace smhip {
 
@@ -114,6 +115,15 @@ SM_KERNEL_TAG_LB(KPcbFn, PcbFnParams, "pcb_fn", k_pcb_fn(ex, p), 256, 4)
 // TSV merge (sm_tsv.hpp): base_out + lambda * B W^T on fp32 MFMA, four waves of 4 x 4 accumulator tiles (64 registers);
 // everything before it runs on the kernels of the low-rank extraction
 SM_KERNEL_TAG_LB(KTsvApply, TsvApplyParams, "tsv_apply", k_tsv_apply(ex, p), 256, 2)
+// WIDEN merge (sm_widen.hpp): the ordered fp64 column sums (24 accumulators per lane), their fold into the two divergences,
+// the ranks by counting, the per-column weights through sm_exp, the combine pass with k <= 4 x 8 weights per lane in
+// registers, or up to 16 x 8
+SM_KERNEL_TAG_LB(KWidenColstats, WidenColstatsParams, "widen_colstats", k_widen_colstats(ex, p), WIDEN_THREADS, 4)
+SM_KERNEL_TAG_LB(KWidenColfold, WidenColfoldParams, "widen_colfold", k_widen_colfold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KWidenRank, WidenRankParams, "widen_rank", k_widen_rank(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KWidenCoef, WidenCoefParams, "widen_coef", k_widen_coef(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KWidenCombine, WidenCombineParams, "widen_combine", k_widen_combine<WIDEN_REG_SMALL>(ex, p), WIDEN_THREADS, 4)
+SM_KERNEL_TAG_LB(KWidenCombineAny, WidenCombineParams, "widen_combine", k_widen_combine<TIES_MAX_MODELS>(ex, p), WIDEN_THREADS, 2)
 // the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
@@ -124,6 +134,7 @@ SM_KERNEL_TAG_LB(KTsvApply, TsvApplyParams, "tsv_apply", k_tsv_apply(ex, p), 256
 #define SM_SIDE_KERNELS_10(X) X(KFusionRowKl) X(KFusionHist) X(KFusionSelect) X(KFusionMergeArcee) X(KFusionMergeNear) X(KFusionFn)
 #define SM_SIDE_KERNELS_11(X) X(KPcbHist) X(KPcbHistAny) X(KPcbMerge) X(KPcbMergeAny) X(KPcbFn)
 #define SM_SIDE_KERNELS_12(X) X(KTsvApply)
+#define SM_SIDE_KERNELS_13(X) X(KWidenColstats) X(KWidenColfold) X(KWidenRank) X(KWidenCoef) X(KWidenCombine) X(KWidenCombineAny)
 
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
@@ -989,6 +1000,87 @@ class DeltaHost {
     }
     int pcb_fn_array(int op, const double* x, double* y, size_t n, bool on_device) {         // sm_tanh
         return fn_array<KPcbFn, PcbFnParams>([](int o, double v) { return pcb_fn(o, v); }, op, x, y, n, on_device);
+    }
+
+    // ---- WIDEN merge (sm_widen.hpp; smhip_widen_merge): the column sums and their fold (vector mode: the fold alone, from
+    // the inputs), the ranks, the weights, the combine pass, ONE readback.  Workspace: WidenHead (zeroed) | the partials
+    // [nseg][k][3][C] | the statistics [k][2][C] | the ranks [k][2][C] | the weights [k][C]; an optional output of the
+    // call takes the place of its workspace array ----
+    struct WidenHead {
+        uint32_t flags[2];
+        unsigned long long ranksum[TIES_MAX_MODELS * WIDEN_STATS], calibrated[TIES_MAX_MODELS * WIDEN_STATS];
+        double mu[TIES_MAX_MODELS * WIDEN_STATS];
+    };
+    int widen_merge(const smhip_widen_desc& d, void* out, float* delta_out, double* stat_out, uint32_t* rank_out,
+                    float* weight_out, smhip_widen_report* rep) {
+        const int k = d.k;
+        if (rep) *rep = smhip_widen_report{};
+        if (d.n == 0) return SMHIP_OK;
+        const size_t R = d.rows, C = d.n / d.rows;
+        const bool vector_mode = R == 1;
+        const int ns = vector_mode ? 1 : WIDEN_STATS;
+        if (rep) { rep->rows = R; rep->cols = C; rep->vector_mode = vector_mode ? 1 : 0; }
+        const size_t nseg = (R + WIDEN_SEG_ROWS - 1) / WIDEN_SEG_ROWS, ncb = (C + WIDEN_COLS - 1) / WIDEN_COLS;
+        if (nseg * ncb * (size_t)k > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "widen_merge: tensor too large");
+
+        const size_t off_part = round_up(sizeof(WidenHead), 256);
+        const size_t part_bytes = vector_mode ? 0 : round_up(nseg * k * WIDEN_SUMS * C * sizeof(double), 256);
+        const size_t off_stat = off_part + part_bytes, stat_bytes = round_up((size_t)k * WIDEN_STATS * C * sizeof(double), 256);
+        const size_t off_rank = off_stat + stat_bytes, rank_bytes = round_up((size_t)k * WIDEN_STATS * C * sizeof(uint32_t), 256);
+        const size_t off_weight = off_rank + rank_bytes, weight_bytes = round_up((size_t)k * C * sizeof(float), 256);
+        WidenHead* head;
+        int rc;
+        if ((rc = plain_workspace(head, off_weight + weight_bytes))) return rc;
+        double* stat = stat_out ? stat_out : (double*)ws_at(off_stat);
+        uint32_t* rank = rank_out ? rank_out : (uint32_t*)ws_at(off_rank);
+        float* weight = weight_out ? weight_out : (float*)ws_at(off_weight);
+
+        WidenCombineParams m;
+        delta_inputs(d, out, delta_out, false, m);
+        m.R = R; m.C = C; m.ncb = (int)ncb; m.vec = (m.in.aligned && C % 8 == 0) ? 1 : 0;
+        m.weight = weight; m.lambda = (float)d.lambda;
+        // about eight work-groups per CU, each thread at least one row
+        const size_t row_blocks = std::max<size_t>(1, std::min<size_t>((R + WIDEN_SUB - 1) / WIDEN_SUB, (2048 + ncb - 1) / ncb));
+        m.rows_per_wg = (int)round_up((R + row_blocks - 1) / row_blocks, WIDEN_SUB);
+        const size_t cgrid = ncb * ((R + m.rows_per_wg - 1) / m.rows_per_wg);
+
+        WidenColfoldParams f;
+        f.in = m.in; f.C = C; f.nseg = (int)nseg; f.vector_mode = vector_mode ? 1 : 0;
+        f.part = (const double*)ws_at(off_part); f.stat = stat; f.flags = head->flags;
+        if (!vector_mode) {
+            WidenColstatsParams c;
+            c.in = m.in; c.R = R; c.C = C; c.nseg = (int)nseg; c.ncb = (int)ncb; c.vec = m.vec;
+            c.part = (double*)ws_at(off_part);
+            be.template launch<KWidenColstats>((int)(nseg * ncb * k), WIDEN_THREADS, widen_colstats_lds_floats() * 4, c, stream);
+        }
+        const int col_blocks = (int)((C + 255) / 256);
+        be.template launch<KWidenColfold>(col_blocks * k, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+
+        WidenRankParams r;
+        r.C = C; r.ns = ns; r.stat = stat; r.rank = rank; r.ranksum = head->ranksum;
+        be.memset(rank, 0, (size_t)k * WIDEN_STATS * C * sizeof(uint32_t), stream);
+        be.template launch<KWidenRank>(col_blocks * k * WIDEN_STATS * widen_rank_tiles(C), 256, widen_rank_lds_floats() * 4, r, stream);
+
+        WidenCoefParams w;
+        w.k = k; w.C = C; w.ns = ns; w.ratio = d.ratio; w.calibration = d.calibration;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) w.alpha[i] = d.alpha[i < k ? i : 0];
+        w.rank = rank; w.ranksum = head->ranksum; w.weight = weight; w.mu = head->mu; w.calibrated = head->calibrated;
+        be.template launch<KWidenCoef>(col_blocks, 256, widen_coef_lds_floats() * 4, w, stream);
+
+        if (k <= WIDEN_REG_SMALL) be.template launch<KWidenCombine>((int)cgrid, WIDEN_THREADS, LDS_SCRATCH_FLOATS * 4, m, stream);
+        else be.template launch<KWidenCombineAny>((int)cgrid, WIDEN_THREADS, LDS_SCRATCH_FLOATS * 4, m, stream);
+
+        WidenHead host;
+        be.d2h(&host, head, sizeof host, stream);                  // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                             // (reported by the caller as SMHIP_ERR_HIP)
+        if (host.flags[0]) return delta_nonfinite("widen_merge", vector_mode ? "finetune - base" : "the finetune or the base", k, host.flags[0]);
+        if (rep)
+            for (int i = 0; i < k; ++i)
+                for (int s = 0; s < WIDEN_STATS; ++s) {
+                    rep->mu[i][s] = host.mu[i * WIDEN_STATS + s];
+                    rep->calibrated[i][s] = host.calibrated[i * WIDEN_STATS + s];
+                }
+        return SMHIP_OK;
     }
 
     // ---- Task-vector statistics (sm_stats.hpp; smhip_delta_stats): the three selection levels for every density at once,

@@ -183,6 +183,18 @@ class PcbMergeReport:
 
 
 @dataclass
+class WidenMergeReport:
+    rows: int = 0                                                    # R: the first dimension (1 for a 1-D tensor)
+    cols: int = 0                                                    # C = n / R
+    vector_mode: bool = False                                        # R == 1: one statistic, |delta|, at index 0
+    mu: List[List[float]] = field(default_factory=list)              # [finetune][statistic]: the mean significance
+    calibrated: List[List[int]] = field(default_factory=list)        # [finetune][statistic]: columns above ratio * mu
+    stat: Optional[torch.Tensor] = None                              # want_stats: fp64 [k, 2, C] (m, d; vector mode: a, zeros)
+    rank: Optional[torch.Tensor] = None                              # want_stats: int64 [k, 2, C]
+    weight: Optional[torch.Tensor] = None                            # want_stats: fp32 [k, C]
+
+
+@dataclass
 class DeltaStatsReport:
     n: int = 0                                                       # elements of the tensor
     densities: List[float] = field(default_factory=list)             # rho_q, as given
@@ -592,7 +604,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion, PCB; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -1115,6 +1127,49 @@ class Engine:
         self._call(self.lib.dll.smhip_tsv_probe(self.ctx.h, bv.data_ptr(), wv.data_ptr(), rows, cols, int(bv.shape[1]), bo.data_ptr(),
                                                 _DTYPE_CODE[bo.dtype], float(lam), out.data_ptr(), merged.data_ptr(), self._stream()))
         return out, merged
+
+    # -- WIDEN (weight disentanglement) ----------------------------------------------------------
+    def widen_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                    base_out: torch.Tensor, *, ratio: float = 1.0, calibration: float = 1.0, lam: float = 1.0,
+                    layer_name: str = "", want_stats: bool = False, want_delta: bool = False):
+        """WIDEN merge of one tensor viewed as ``[shape[0], rest]`` (``smhip_widen_merge``; the function is stated in
+        include/shardmerge_hip.h): per column and finetune the divergence of the column's magnitude and of its direction
+        from the base's, both ranked within the finetune, the ranks turned into weights by a softmax across the finetunes
+        - a column ranked above ``ratio`` times the finetune's mean rank takes ``calibration`` instead - and the deltas
+        added with those per-column weights times ``alpha_i``, times ``lam``, onto ``base_out`` in its dtype.  A tensor
+        whose first dimension is 1 (and a 1-D tensor) ranks the magnitudes of its delta's entries.  At most 65536
+        columns.  Returns (out, WidenMergeReport[, the fp32 merged delta times ``lam``]); ``want_stats`` adds every
+        column's statistics, ranks and weights to the report (CPU tensors).  A NaN or Inf in a finetune or a base raises
+        ValueError naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        if not math.isfinite(float(ratio)):
+            raise ValueError(f"widen_merge: ratio {ratio} is not finite")
+        if not (0.0 <= float(calibration) < math.inf):
+            raise ValueError(f"widen_merge: calibration {calibration} is not a finite number >= 0")
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"widen_merge: lam {lam} is not finite")
+        desc, rep, k = _lib.WidenDesc(), _lib.WidenReport(), len(finetunes)
+        desc.ratio, desc.calibration, desc.lam = float(ratio), float(calibration), float(lam)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "widen_merge")
+        desc.n = bo.numel()
+        rows = int(bo.shape[0]) if bo.ndim >= 2 else 1
+        desc.rows = rows
+        cols = int(desc.n // rows) if rows else 0
+        if cols > _lib.WIDEN_MAX_COLS:
+            raise ValueError(f"widen_merge: {layer_name} has shape {list(bo.shape)}: {cols} columns, at most {_lib.WIDEN_MAX_COLS}")
+        stat = rank = weight = None
+        if want_stats:
+            stat = torch.zeros((k, 2, cols), dtype=torch.float64, device=self.device)
+            rank = torch.zeros((k, 2, cols), dtype=torch.int32, device=self.device)
+            weight = torch.zeros((k, cols), dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        self._run_delta_merge(self.lib.dll.smhip_widen_merge, desc, rep, out, delta, layer_name, ptr(stat), ptr(rank), ptr(weight))
+        report = WidenMergeReport(rows=int(rep.rows), cols=int(rep.cols), vector_mode=bool(rep.vector_mode),
+                                  mu=[[float(rep.mu[i][s]) for s in range(2)] for i in range(k)],
+                                  calibrated=[[int(rep.calibrated[i][s]) for s in range(2)] for i in range(k)])
+        if want_stats:
+            report.stat, report.rank, report.weight = stat.cpu(), rank.cpu().to(torch.int64), weight.cpu()
+        return (out, report, delta) if want_delta else (out, report)
 
     # -- task-vector statistics ----------------------------------------------------------------
     def delta_stats(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],

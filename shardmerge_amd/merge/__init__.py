@@ -26,6 +26,7 @@ _OPERATOR_CLASSES = {
     "nearswap": ("fusion", "NearSwapMerge"),
     "pcb": ("pcb", "PcbMerge"),
     "tsv": ("tsv", "TsvMerge"),
+    "widen": ("widen", "WidenMerge"),
 }
 
 
