@@ -4,15 +4,13 @@ merged delta, both thresholds, kept and dropped_top counts, k_keep, n_top.  The 
 not measured: every step of the function is one correctly rounded fp32 operation or an exact order statistic
 (include/shardmerge_hip.h, smhip_breadcrumbs_merge)."""
 import math
-import re
 
 import pytest
 import torch
-import yaml
 
 from tests import breadcrumbs_oracle
-from tests import lora_fixtures as lf
-from tests.ties_checks import ALPHAS, DTYPES, KS, SMALL, assert_outputs, f32_bits, make_inputs, raw, run_cli  # noqa: F401
+from tests import harness
+from tests.harness import ALPHAS, DTYPES, SMALL, expected_by_tensor, f32_bits, make_inputs, raw, ties_models
 
 # (density, gamma); the last one has k_keep == 0: thresholds +inf, nothing kept
 DENSITY_GAMMA = ((0.9, 0.01), (0.2, 0.01), (0.5, 0.5), (0.9, 0.1), (1.0, 0.0), (0.2, 0.0), (1e-9, 0.3))
@@ -343,37 +341,16 @@ def options(operator):
     return {"operator": operator, "density": 0.3, "gamma": 0.05, "breadcrumbs_lambda": 0.7}
 
 
-def crumbs_models(third):
-    """layer 0: all three finetunes, layer 1: ft1 and `third`; ft2 is a finetune of ft1 (its own base)"""
-    return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-            {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-            {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
-
-
 def write_config(root, third, out_dir, opts, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": crumbs_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(opts)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, ties_models(third), out_dir, opts, device)
 
 
 def expected_outputs(base, full, opts):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        entries = [(ft1[name], base[name], 0.5)] + ([(ft2[name], ft1[name], 0.3)] if int(m.group(1)) == 0 else []) + \
-                  [(full[name], base[name], 0.4)]
-        out[name] = breadcrumbs_oracle.breadcrumbs_merge(
-            [e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-            density=opts.get("density", 0.9), gamma=opts.get("gamma", 0.01), lam=opts.get("breadcrumbs_lambda", 1.0),
-            normalize=bool(opts.get("breadcrumbs_normalize", 1)), sign_election=opts["operator"] == "breadcrumbs_ties")[0]
-    return out
+    def merge(fts, bases, alphas, base_out, name):
+        return breadcrumbs_oracle.breadcrumbs_merge(
+            fts, bases, alphas, base_out, density=opts.get("density", 0.9), gamma=opts.get("gamma", 0.01),
+            lam=opts.get("breadcrumbs_lambda", 1.0), normalize=bool(opts.get("breadcrumbs_normalize", 1)),
+            sign_election=opts["operator"] == "breadcrumbs_ties")[0]
+
+    return expected_by_tensor(base, full, ties_models("org/lora_full"), merge)

@@ -4,14 +4,13 @@ delta, masked / agree / selected counts and, for the TIES flavour, k_keep, thres
 zero and it is derived, not measured: every step of the function is one correctly rounded fp32 operation, a comparison,
 an integer count or an exact order statistic (include/shardmerge_hip.h, smhip_consensus_merge)."""
 import ctypes as C
-import re
 
 import pytest
 import torch
 
 from tests import consensus_oracle
-from tests import lora_fixtures as lf
-from tests.ties_checks import ALPHAS, DTYPES, assert_outputs, f32_bits, make_inputs, raw, run_cli, write_config  # noqa: F401
+from tests import harness
+from tests.harness import ALPHAS, expected_by_tensor, f32_bits, make_inputs, profile_of, raw, ties_models
 
 FLAVOURS = (False, True)                        # ties: consensus_ta, consensus_ties
 FLAVOUR_IDS = ["consensus_ta", "consensus_ties"]
@@ -275,17 +274,6 @@ PROFILES = [(False, 2, {"consensus_merge": 1}), (False, 5, {"consensus_merge": 1
 PROFILE_IDS = ["ta-k2", "ta-k5", "ties-k2", "ties-k5"]
 
 
-def profile_of(engine, call):
-    engine.ctx.profile(True)
-    engine.ctx.profile_reset()
-    try:
-        call()
-        table = engine.ctx.profile_table()
-    finally:
-        engine.ctx.profile(False)
-    return {n: table[n][0] for n in table}
-
-
 def check_profile(engine, ties, k, expected, shape=(40, 50), device="cpu"):
     """one fused launch; the TIES flavour adds exactly the selection launches that ties_merge makes at the same k"""
     fts, bases, bo = make_inputs(shape, k, seed=6, device=device)
@@ -343,21 +331,17 @@ def options(operator):
     return opts
 
 
+def write_config(root, third, out_dir, opts, device=None):
+    return harness.write_config(root, ties_models(third), out_dir, opts, device)
+
+
 def expected_outputs(base, full, opts):
-    """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough); the models of ties_checks.ties_models:
+    """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough); the models of ties_models:
     layer 0 has three entries, layer 1 two"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        entries = [(ft1[name], base[name], 0.5)] + ([(ft2[name], ft1[name], 0.3)] if int(m.group(1)) == 0 else []) + \
-                  [(full[name], base[name], 0.4)]
-        out[name] = consensus_oracle.consensus_merge(
-            [e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-            ties=opts["operator"] == "consensus_ties", density=opts.get("density", 0.2), mask_lambda=opts.get("mask_lambda", 0.4),
-            consensus_k=opts.get("consensus_k", 2), lam=opts.get("consensus_lambda", 1.0),
+    def merge(fts, bases, alphas, base_out, name):
+        return consensus_oracle.consensus_merge(
+            fts, bases, alphas, base_out, ties=opts["operator"] == "consensus_ties", density=opts.get("density", 0.2),
+            mask_lambda=opts.get("mask_lambda", 0.4), consensus_k=opts.get("consensus_k", 2), lam=opts.get("consensus_lambda", 1.0),
             normalize=bool(opts.get("consensus_normalize", 1)))["out"]
-    return out
+
+    return expected_by_tensor(base, full, ties_models("org/lora_full"), merge)

@@ -3,15 +3,13 @@
 kept counts.  The tolerance is zero and it is derived, not measured: every step of the function is an integer function
 or one correctly rounded fp32 operation (include/shardmerge_hip.h, smhip_dare_merge)."""
 import math
-import re
 
 import pytest
 import torch
-import yaml
 
 from tests import dare_oracle
-from tests import lora_fixtures as lf
-from tests.ties_checks import ALPHAS, DTYPES, KS, SMALL, assert_outputs, make_inputs, raw, run_cli  # noqa: F401
+from tests import harness
+from tests.harness import ALPHAS, DTYPES, SMALL, covering, expected_by_tensor, layer_of, make_inputs, raw, ties_models
 
 DENSITIES = (1.0, 0.5, 0.2, 0.01, 2.0 ** -16)   # the last one: T = 1, the smallest density there is
 MODES = (True, False)                           # sign_election: dare_ties, dare_linear
@@ -270,39 +268,28 @@ def options(operator):
 
 
 def dare_models(third):
-    """layer 0: all three entries; layer 1: entries 0 and 2 (entry 1's window ends at layer 0), so on layer 1 the third
-    entry is the SECOND covering finetune while its stream id stays 2; ft2 is a finetune of ft1 (its own base)"""
-    return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-            {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-            {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
+    """ties_models: layer 0: all three entries; layer 1: entries 0 and 2 (entry 1's window ends at layer 0), so on layer 1
+    the third entry is the SECOND covering finetune while its stream id stays 2"""
+    return ties_models(third)
+
+
+def stream_ids(models, name):
+    """a finetune's stream id is its position among ALL the entries, whichever of them cover the tensor's layer"""
+    return [i for i, _ in covering(models, layer_of(name))]
 
 
 def write_config(root, third, out_dir, opts, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": dare_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(opts)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, dare_models(third), out_dir, opts, device)
 
 
 def expected_outputs(base, full, opts):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        entries = [(ft1[name], base[name], 0.5, 0)] + ([(ft2[name], ft1[name], 0.3, 1)] if int(m.group(1)) == 0 else []) + \
-                  [(full[name], base[name], 0.4, 2)]
-        out[name] = dare_oracle.dare_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                           density=opts.get("density", 0.2), lam=opts.get("dare_lambda", 1.0),
-                                           normalize=bool(opts.get("dare_normalize", 1)), rescale=bool(opts.get("dare_rescale", 1)),
-                                           sign_election=opts["operator"] == "dare_ties",
-                                           key=dare_oracle.tensor_key(opts.get("seed", 0), name),
-                                           stream_ids=[e[3] for e in entries])[0]
-    return out
+    models = dare_models("org/lora_full")
+    def merge(fts, bases, alphas, base_out, name):
+        return dare_oracle.dare_merge(
+            fts, bases, alphas, base_out, density=opts.get("density", 0.2), lam=opts.get("dare_lambda", 1.0),
+            normalize=bool(opts.get("dare_normalize", 1)), rescale=bool(opts.get("dare_rescale", 1)),
+            sign_election=opts["operator"] == "dare_ties", key=dare_oracle.tensor_key(opts.get("seed", 0), name),
+            stream_ids=stream_ids(models, name))[0]
+
+    return expected_by_tensor(base, full, models, merge)

@@ -4,17 +4,15 @@ per-element thresholds, T_lo, T_hi and the kept counts.  The tolerance is zero a
 of the function is an integer function, an exact count or one correctly rounded operation (include/shardmerge_hip.h,
 smhip_della_merge)."""
 import math
-import re
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
 from tests import dare_oracle, della_oracle
-from tests import lora_fixtures as lf
-from tests.dare_checks import KEY, STAT_KEY, STAT_STREAMS, dare_models
-from tests.ties_checks import ALPHAS, DTYPES, KS, SMALL, assert_outputs, make_inputs, raw, run_cli  # noqa: F401
+from tests import harness
+from tests.dare_checks import KEY, STAT_KEY, STAT_STREAMS, dare_models, stream_ids
+from tests.harness import ALPHAS, DTYPES, SMALL, expected_by_tensor, make_inputs, raw
 
 WINDOWS = ((0.5, 0.15), (0.2, 0.1), (0.7, 0.29), (0.5, 0.0), (1.0, 0.0), (2.0 ** -15 + 0.01, 0.01))   # the last one: T_lo == 2
 MODES = (True, False)                           # sign_election: della, della_linear
@@ -348,31 +346,17 @@ def options(operator):
 
 
 def write_config(root, third, out_dir, opts, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": dare_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(opts)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, dare_models(third), out_dir, opts, device)
 
 
 def expected_outputs(base, full, opts):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        entries = [(ft1[name], base[name], 0.5, 0)] + ([(ft2[name], ft1[name], 0.3, 1)] if int(m.group(1)) == 0 else []) + \
-                  [(full[name], base[name], 0.4, 2)]
-        out[name] = della_oracle.della_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                             density=opts.get("density", 0.5), epsilon=opts.get("epsilon", 0.15),
-                                             lam=opts.get("della_lambda", 1.0), normalize=bool(opts.get("della_normalize", 1)),
-                                             rescale=bool(opts.get("della_rescale", 1)), sign_election=opts["operator"] == "della",
-                                             key=dare_oracle.tensor_key(opts.get("seed", 0), name),
-                                             stream_ids=[e[3] for e in entries])[0]
-    return out
+    models = dare_models("org/lora_full")
+    def merge(fts, bases, alphas, base_out, name):
+        return della_oracle.della_merge(
+            fts, bases, alphas, base_out, density=opts.get("density", 0.5), epsilon=opts.get("epsilon", 0.15),
+            lam=opts.get("della_lambda", 1.0), normalize=bool(opts.get("della_normalize", 1)),
+            rescale=bool(opts.get("della_rescale", 1)), sign_election=opts["operator"] == "della",
+            key=dare_oracle.tensor_key(opts.get("seed", 0), name), stream_ids=stream_ids(models, name))[0]
+
+    return expected_by_tensor(base, full, models, merge)

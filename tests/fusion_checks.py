@@ -11,11 +11,9 @@ import re
 import numpy as np
 import pytest
 import torch
-import yaml
 
 from tests import fusion_oracle as fo
-from tests import lora_fixtures as lf
-from tests.ties_checks import DTYPES, assert_outputs, f32_bits, raw, run_cli  # noqa: F401
+from tests.harness import DTYPES, expected_by_tensor, f32_bits, raw
 
 COLS = (1, 7, 8, 9, 2047, 2048, 2049, 4096, 28672)       # 2047..2049: around one full round of 256 lanes x 8
 ROWS = (1, 3, 257)
@@ -23,7 +21,7 @@ SHAPE = (37, 129)                                         # unaligned rows and a
 FN_TOL = 2.0 ** -50                                       # the issue's cap on the relative error of sm_exp / sm_log
 
 
-def make_inputs(shape, in_dtype=torch.bfloat16, bo_dtype=None, seed=0, sigma=1e-3, own_out=False, device="cpu"):
+def fusion_inputs(shape, in_dtype=torch.bfloat16, bo_dtype=None, seed=0, sigma=1e-3, own_out=False, device="cpu"):
     """(finetune, base, base_out): a base N(0, 0.02^2), a delta N(0, (sigma * u_r)^2) with a scale u_r per row of the last
     dimension, log-uniform in [0.5, 2] (so that the row KLs differ), all rounded to their dtype"""
     g = torch.Generator(device=device).manual_seed(2000 + seed)
@@ -115,7 +113,7 @@ def check_shape(engine, C, R, device="cpu"):
     """ARCEE and NEARSWAP on R x C: kl_out, quartiles, threshold, counts, delta and output, bit for bit.  C = 1 gives
     kappa = 0 everywhere (a softmax over one element): no sanity condition there"""
     small = R * C < 512
-    ft, base, bo = make_inputs((R, C), seed=C % 97 + R, sigma=1e-3 if small or (C + R) % 2 else 1e-4, device=device)
+    ft, base, bo = fusion_inputs((R, C), seed=C % 97 + R, sigma=1e-3 if small or (C + R) % 2 else 1e-4, device=device)
     if small and C > 1:
         ft[R - 1, C // 2] += 0.05                      # a handful of scores has no outlier of its own: plant one
     sane = C > 1
@@ -126,22 +124,22 @@ def check_shape(engine, C, R, device="cpu"):
 
 
 def check_dtypes(engine, in_dtype, bo_dtype, device="cpu"):
-    ft, base, bo = make_inputs(SHAPE, in_dtype, bo_dtype, seed=11, own_out=True, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, in_dtype, bo_dtype, seed=11, own_out=True, device=device)
     check(engine, ft, base, bo, "arcee", label=f"arcee {in_dtype}->{bo_dtype}")
     check(engine, ft, base, bo, "nearswap", t=1e-3, label=f"nearswap {in_dtype}->{bo_dtype}")
-    ft, base, bo = make_inputs(SHAPE, in_dtype, bo_dtype, seed=12, device=device)        # base_out is the base where the dtypes agree
+    ft, base, bo = fusion_inputs(SHAPE, in_dtype, bo_dtype, seed=12, device=device)        # base_out is the base where the dtypes agree
     check(engine, ft, base, bo, "arcee", iqr_mult=0.5, label=f"arcee {in_dtype}->{bo_dtype} shared")
 
 
 def check_tiny(engine, device="cpu"):
     for n in (1, 2, 4):
-        ft, base, bo = make_inputs((n,), seed=30 + n, device=device)
+        ft, base, bo = fusion_inputs((n,), seed=30 + n, device=device)
         check(engine, ft, base, bo, "arcee", sane=False, label=f"arcee n={n}")
         check(engine, ft, base, bo, "nearswap", t=1e-3, label=f"nearswap n={n}")
-    ft, base, bo = make_inputs((0,), seed=35, device=device)
+    ft, base, bo = fusion_inputs((0,), seed=35, device=device)
     out, rep = engine.fusion_merge(ft, base, bo, mode="arcee")
     assert out.numel() == 0 and rep.selected == 0
-    ft, base, bo = make_inputs((4, 33, 65), seed=36, own_out=True, device=device)          # rank 3: rows of the last dimension
+    ft, base, bo = fusion_inputs((4, 33, 65), seed=36, own_out=True, device=device)          # rank 3: rows of the last dimension
     check(engine, ft, base, bo, "arcee", label="arcee rank 3")
     check(engine, ft, base, bo, "nearswap", t=1e-3, label="nearswap rank 3")
 
@@ -151,9 +149,9 @@ def check_unaligned(engine, device="cpu"):
     for dtype in DTYPES:
         for R, C in ((1, 1003), (8, 256), (5, 129)):
             n = R * C
-            ft, base, bo = make_inputs((n + 5,), dtype, seed=71, own_out=True, device=device)
+            ft, base, bo = fusion_inputs((n + 5,), dtype, seed=71, own_out=True, device=device)
             cut = lambda t, o: t[o:o + n].view(R, C)
-            # (the row scale of make_inputs is per flat tensor here: scale the rows by hand)
+            # (the row scale of fusion_inputs is per flat tensor here: scale the rows by hand)
             f = cut(ft, 1).float()
             b = cut(base, 3).float()
             f = (b + (f - b) * 0.03 * torch.linspace(0.5, 2.0, R, device=f.device).view(R, 1)).to(dtype)
@@ -165,7 +163,7 @@ def check_unaligned(engine, device="cpu"):
 
 def check_tied_deltas(engine, device="cpu"):
     """heavily tied bf16 deltas: differences of bf16 weights collide, whole runs of scores are equal"""
-    ft, base, bo = make_inputs((64, 512), seed=65, sigma=1e-4, device=device)
+    ft, base, bo = fusion_inputs((64, 512), seed=65, sigma=1e-4, device=device)
     rep, _, _, ref = check(engine, ft, base, bo, "arcee", label="tied deltas")
     d = (ft.float() - base.float()).cpu()
     assert d.unique().numel() < d.numel() // 20
@@ -174,7 +172,7 @@ def check_tied_deltas(engine, device="cpu"):
 
 def check_mostly_zero(engine, device="cpu"):
     """more than three quarters of the deltas zero: Q1 = Q2 = Q3 = thr = 0 and exactly the nonzero scores are selected"""
-    ft, base, bo = make_inputs((64, 300), seed=66, device=device)
+    ft, base, bo = fusion_inputs((64, 300), seed=66, device=device)
     keep = torch.rand(ft.shape, generator=torch.Generator().manual_seed(5)).to(ft.device) < 0.2
     ft = torch.where(keep, ft, base)
     rep, _, delta, ref = check(engine, ft, base, bo, "arcee", sane=False, label="mostly zero")
@@ -186,12 +184,12 @@ def check_mostly_zero(engine, device="cpu"):
 def check_identical(engine, device="cpu"):
     """finetune == base: every kappa is 0 EXACTLY, nothing is selected, out is base_out's bytes"""
     for in_dtype, bo_dtype in ((torch.bfloat16, torch.bfloat16), (torch.float32, torch.bfloat16)):
-        ft, base, bo = make_inputs(SHAPE, in_dtype, bo_dtype, seed=67, own_out=True, device=device)
+        ft, base, bo = fusion_inputs(SHAPE, in_dtype, bo_dtype, seed=67, own_out=True, device=device)
         rep, out, delta, _ = check(engine, base.clone(), base, bo, "arcee", sane=False, label="identical")
         assert rep.selected == 0 and rep.kl_max == 0.0 and rep.kl_min == 0.0 and not bool(rep.kl.any())
         assert torch.equal(raw(out), raw(bo)) and not bool(delta.any())
     # one row identical among others
-    ft, base, bo = make_inputs(SHAPE, seed=68, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, seed=68, device=device)
     ft[5] = base[5]
     rep, _, _, _ = check(engine, ft, base, bo, "arcee", label="one identical row")
     assert float(rep.kl[5]) == 0.0 and rep.kl_min == 0.0 < rep.kl_max
@@ -199,11 +197,11 @@ def check_identical(engine, device="cpu"):
 
 def check_outliers(engine, device="cpu"):
     """one outlier delta; a row with one weight 80 above the rest (the other terms fall below the exp cutoff)"""
-    ft, base, bo = make_inputs(SHAPE, torch.float32, seed=69, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, torch.float32, seed=69, device=device)
     ft[3, 7] += 0.5
     rep, _, delta, _ = check(engine, ft, base, bo, "arcee", label="one outlier")
     assert float(delta[3, 7]) != 0.0
-    ft, base, bo = make_inputs((6, 300), torch.float32, seed=70, device=device)
+    ft, base, bo = fusion_inputs((6, 300), torch.float32, seed=70, device=device)
     base[2, 11] += 80.0
     ft[2, 11] += 80.0
     ft[4, 0] += 80.0                                   # ... and in the finetune alone: a large KL
@@ -215,7 +213,7 @@ def check_outliers(engine, device="cpu"):
 
 def check_iqr(engine, device="cpu"):
     """fusion_iqr 0; the selected sets are nested in fusion_iqr; -1e6 takes everything: dare_linear at density 1"""
-    ft, base, bo = make_inputs(SHAPE, seed=72, own_out=True, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, seed=72, own_out=True, device=device)
     rep0, _, _, ref = check(engine, ft, base, bo, "arcee", iqr_mult=0.0, label="iqr 0")
     assert f32_bits(rep0.threshold) == f32_bits(rep0.q2) and rep0.q3 > rep0.q1
     prev, prev_sel = None, None
@@ -235,7 +233,7 @@ def check_iqr(engine, device="cpu"):
 
 def check_nearswap_identity(engine, device="cpu"):
     """t >= max |d|: nothing is clipped - dare_linear at density 1 with alpha 1; a small t clips most"""
-    ft, base, bo = make_inputs(SHAPE, seed=73, own_out=True, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, seed=73, own_out=True, device=device)
     tmax = float((ft.float() - base.float()).abs().max())
     out, rep, delta = engine.fusion_merge(ft, base, bo, mode="nearswap", t=tmax, want_delta=True)
     d_out, _, d_delta = engine.dare_merge([ft], [base], [1.0], bo, density=1.0, lam=1.0, normalize=True, sign_election=False, want_delta=True)
@@ -251,7 +249,7 @@ def check_kl_against_log_softmax(engine, device="cpu"):
     bit for bit through kappa, checked here too) is held to it; the engine's fp32 kappa to the bound plus half an ulp of
     its fp32 rounding (2^-24 relative)."""
     for (R, C), sigma in (((33, 129), 1e-3), ((9, 4096), 1e-4), ((3, 28672), 1e-3)):
-        ft, base, bo = make_inputs((R, C), seed=90 + R, sigma=sigma, device=device)
+        ft, base, bo = fusion_inputs((R, C), seed=90 + R, sigma=sigma, device=device)
         _, rep = engine.fusion_merge(ft, base, bo, mode="arcee", want_kl=True)
         kappa, kl, span = fo.row_kl(ft.float().cpu().numpy(), base.float().cpu().numpy())
         assert np.array_equal(rep.kl.cpu().numpy().view(np.uint32), kappa.view(np.uint32))
@@ -270,9 +268,9 @@ def check_kl_against_log_softmax(engine, device="cpu"):
 def check_selected_share(engine, device="cpu"):
     """Gaussian bases (sigma 0.02), bf16 deltas (sigma 1e-3 and 1e-4, row-dependent scale): the selected share at
     fusion_iqr 1.5 is 0.13 to 0.17.  (The share is a property of the scale law: with one scale for all rows the scores are
-    half-normal and 5.5 % lie above median + 1.5 IQR; make_inputs' log-uniform [0.5, 2] is the law used throughout.)"""
+    half-normal and 5.5 % lie above median + 1.5 IQR; fusion_inputs' log-uniform [0.5, 2] is the law used throughout.)"""
     for sigma in (1e-3, 1e-4):
-        ft, base, bo = make_inputs((96, 1024), seed=95, sigma=sigma, device=device)
+        ft, base, bo = fusion_inputs((96, 1024), seed=95, sigma=sigma, device=device)
         _, rep = engine.fusion_merge(ft, base, bo, mode="arcee")
         share = rep.selected / rep.n
         print(f"sigma {sigma}: selected share {share:.4f}")
@@ -285,23 +283,23 @@ def check_nonfinite(engine, device="cpu"):
     name = "model.layers.7.mlp.up_proj.weight"
     for poison in (float("nan"), float("inf"), float("-inf")):
         for which, word in ((0, "the finetune"), (1, "the base")):
-            ft, base, bo = make_inputs(SHAPE, torch.float32, seed=80, own_out=True, device=device)
+            ft, base, bo = fusion_inputs(SHAPE, torch.float32, seed=80, own_out=True, device=device)
             (ft, base)[which].view(-1)[4321] = poison
             with pytest.raises(ValueError, match=re.escape(name) + ".*NaN or Inf in .*" + word):
                 engine.fusion_merge(ft, base, bo, mode="arcee", layer_name=name)
             with pytest.raises(ValueError, match=re.escape(name) + ".*NaN or Inf in finetune - base"):
                 engine.fusion_merge(ft, base, bo, mode="nearswap", t=1e-3, layer_name=name)
     # d only: finite fp32 weights whose difference overflows
-    ft, base, bo = make_inputs(SHAPE, torch.float32, seed=81, own_out=True, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, torch.float32, seed=81, own_out=True, device=device)
     ft.view(-1)[17], base.view(-1)[17] = 3e38, -3e38
     with pytest.raises(ValueError, match=re.escape(name) + ".*NaN or Inf in finetune - base"):
         engine.fusion_merge(ft, base, bo, mode="nearswap", t=1e-3, layer_name=name)
-    ft, base, bo = make_inputs(SHAPE, seed=82, device=device)
+    ft, base, bo = fusion_inputs(SHAPE, seed=82, device=device)
     check(engine, ft, base, bo, "arcee", label="after an error")
 
 
 def check_arguments(engine, device="cpu"):
-    ft, base, bo = make_inputs((8, 8), seed=91, device=device)
+    ft, base, bo = fusion_inputs((8, 8), seed=91, device=device)
     for bad in (0.0, -1e-3, float("nan"), float("inf"), None):
         with pytest.raises(ValueError, match="nearswap needs t > 0"):
             engine.fusion_merge(ft, base, bo, mode="nearswap", t=bad)
@@ -314,7 +312,7 @@ def check_arguments(engine, device="cpu"):
 
 
 def check_determinism(engine, device="cpu"):
-    ft, base, bo = make_inputs((300, 500), seed=92, own_out=True, device=device)
+    ft, base, bo = fusion_inputs((300, 500), seed=92, own_out=True, device=device)
     a, ra = engine.fusion_merge(ft, base, bo, mode="arcee")
     b, rb = engine.fusion_merge(ft, base, bo, mode="arcee")
     assert torch.equal(raw(a), raw(b)) and ra == rb
@@ -330,7 +328,7 @@ PROFILES = [("arcee", {"fusion_rowkl": 1, "fusion_hist": 3, "fusion_select": 3, 
 
 
 def check_profile(engine, mode, expected, shape=(40, 50), device="cpu"):
-    ft, base, bo = make_inputs(shape, seed=6, device=device)
+    ft, base, bo = fusion_inputs(shape, seed=6, device=device)
     engine.ctx.profile(True)
     engine.ctx.profile_reset()
     try:
@@ -389,27 +387,11 @@ def models(second):
             {"model": second, "base": "org/base", "is_output": True, "start_layer": 1}]
 
 
-def write_config(root, entries, out_dir, opts, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": entries, "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(opts)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
-
-
 def expected_outputs(base, full, opts):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough) for models()"""
-    ft1 = lf.model_tensors(1)
     mode = "arcee" if opts["operator"] == "arcee_fusion" else "nearswap"
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        ft = ft1[name] if int(m.group(1)) == 0 else full[name]
-        out[name] = fo.fusion_merge(ft, base[name], base[name], mode, iqr_mult=opts.get("fusion_iqr", 1.5), t=opts.get("nearswap_t"))["out"]
-    return out
+    def merge(fts, bases, alphas, base_out, name):
+        return fo.fusion_merge(
+            fts[0], bases[0], base_out, mode, iqr_mult=opts.get("fusion_iqr", 1.5), t=opts.get("nearswap_t"))["out"]
+
+    return expected_by_tensor(base, full, models("org/lora_full"), merge)

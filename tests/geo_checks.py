@@ -6,25 +6,18 @@ other step is one correctly rounded IEEE operation or the C library's acos / sin
 smhip_geo_merge).  The Gram is ALSO held against math.fsum of the exact products, within the a-priori bound of any
 summation order, so that an oracle and a kernel with the same mistake do not pass together."""
 import math
-import re
-import struct
 
 import pytest
 import torch
-import yaml
 
 from tests import geo_oracle
-from tests import lora_fixtures as lf
-from tests.ties_checks import ALPHAS, DTYPES, KS, SMALL, assert_outputs, f32_bits, make_inputs, raw, run_cli  # noqa: F401
+from tests import harness
+from tests.harness import ALPHAS, DTYPES, SMALL, expected_by_tensor, f32_bits, f64_bits, make_inputs, raw, ties_models
 
 MODES = geo_oracle.MODES
 # (mode, rowwise): the four operator variants
 VARIANTS = (("model_stock", False), ("model_stock", True), ("nuslerp", False), ("slerp", False))
 VARIANT_IDS = ["model_stock", "model_stock_rowwise", "nuslerp", "slerp"]
-
-
-def f64_bits(x: float) -> bytes:
-    return struct.pack("<d", float(x))
 
 
 def variant_k(mode, k):
@@ -352,39 +345,20 @@ def geo_models(operator, third):
     """model_stock: layer 0 all three finetunes, layer 1 ft1 and `third`; ft2 is a finetune of ft1 (its own base).
     nuslerp / slerp take two entries: ft1 on every layer, `third` from layer 1 on - layer 0 is left with ONE entry."""
     if operator == "model_stock":
-        return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-                {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-                {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
+        return ties_models(third)
     return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
             {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True, "start_layer": 1}]
 
 
 def write_config(root, third, out_dir, opts, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": geo_models(opts["operator"], third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(opts)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, geo_models(opts["operator"], third), out_dir, opts, device)
 
 
 def expected_outputs(base, full, opts):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
     operator = opts["operator"]
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        layer = int(m.group(1))
-        if operator == "model_stock":
-            entries = [(ft1[name], base[name], 0.5)] + ([(ft2[name], ft1[name], 0.3)] if layer == 0 else []) + [(full[name], base[name], 0.4)]
-        else:
-            entries = [(ft1[name], base[name], 0.5)] + ([(full[name], base[name], 0.4)] if layer >= 1 else [])
-        out[name] = geo_oracle.geo_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                         mode=operator, rowwise=bool(opts.get("stock_filter_wise", 0)))["out"]
-    return out
+    def merge(fts, bases, alphas, base_out, name):
+        return geo_oracle.geo_merge(
+            fts, bases, alphas, base_out, mode=operator, rowwise=bool(opts.get("stock_filter_wise", 0)))["out"]
+
+    return expected_by_tensor(base, full, geo_models(operator, "org/lora_full"), merge)

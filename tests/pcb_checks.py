@@ -7,15 +7,14 @@ smhip_pcb_merge).  sm_tanh is held to 2^-48 of mpmath's tanh: sm_exp's 2^-52 tim
 paper's form (exp(k s^2) with the factor e^k, torch.tanh clamped at 0, min-max normalisation) in quotient form."""
 import ctypes as C
 import math
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from tests import lora_fixtures as lf
+from tests import harness
 from tests import pcb_oracle
-from tests.ties_checks import ALPHAS, DTYPES, assert_outputs, f32_bits, make_inputs, raw, run_cli, ties_models, write_config  # noqa: F401
+from tests.harness import ALPHAS, expected_by_tensor, f32_bits, make_inputs, profile_of, raw, ties_models
 
 KS = (1, 2, 3, 4, 5, 16)                        # 4 | 5 straddles the two register variants of the kernels
 RATIOS = (0.1, 0.5, 1.0, 1e-9)                  # the last one: q = 1
@@ -266,17 +265,6 @@ PROFILES = [(2, {"stats_hist": 3, "stats_select": 6, "pcb_hist": 3, "pcb_merge":
 PROFILE_IDS = ["k2", "k5"]
 
 
-def profile_of(engine, call):
-    engine.ctx.profile(True)
-    engine.ctx.profile_reset()
-    try:
-        call()
-        table = engine.ctx.profile_table()
-    finally:
-        engine.ctx.profile(False)
-    return {n: table[n][0] for n in table}
-
-
 def check_profile(engine, k, expected, shape=(40, 50), device="cpu"):
     """three levels of the clip's select (the statistics' kernels, unchanged), three of the scores', one fused pass"""
     fts, bases, bo = make_inputs(shape, k, seed=6, device=device)
@@ -422,22 +410,16 @@ def check_c_abi(engine, device="cpu"):
 OPTIONS = {"operator": "pcb", "pcb_ratio": 0.3, "pcb_clip": 0.01, "pcb_lambda": 0.7}
 
 
+def write_config(root, third, out_dir, opts, device=None):
+    return harness.write_config(root, ties_models(third), out_dir, opts, device)
+
+
 def expected_outputs(base, full, opts, models=None):
-    """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough); the models of
-    ties_checks.ties_models: layer 0 has three entries, layer 1 two.  models: the finetune_merge entries, if others."""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        layer = int(m.group(1))
-        entries = [(ft1[name], base[name], 0.5, 0, -1), (ft2[name], ft1[name], 0.3, 0, 0), (full[name], base[name], 0.4, 0, -1)]
-        if models is not None:
-            entries = [(e[0], e[1], e[2], mm.get("start_layer", 0), mm.get("end_layer", -1)) for e, mm in zip(entries, models)]
-        entries = [e for e in entries if e[3] <= layer and (e[4] == -1 or layer <= e[4])]
-        out[name] = pcb_oracle.pcb_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                         ratio=opts.get("pcb_ratio", 0.1), clip=opts.get("pcb_clip", 0.0001),
-                                         lam=opts.get("pcb_lambda", 1.0))["out"]
-    return out
+    """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough); the models of ties_models:
+    layer 0 has three entries, layer 1 two.  models: the finetune_merge entries, if others."""
+    def merge(fts, bases, alphas, base_out, name):
+        return pcb_oracle.pcb_merge(
+            fts, bases, alphas, base_out, ratio=opts.get("pcb_ratio", 0.1), clip=opts.get("pcb_clip", 0.0001),
+            lam=opts.get("pcb_lambda", 1.0))["out"]
+
+    return expected_by_tensor(base, full, models or ties_models("org/lora_full"), merge)

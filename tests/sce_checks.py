@@ -3,26 +3,18 @@
 the selected count, the threshold's bits, the energies as doubles and the weights' bits.  The tolerance is zero and it is
 derived, not measured: every step of the function is one correctly rounded operation or an exact order statistic, in an
 order that the header writes out (include/shardmerge_hip.h, smhip_sce_merge)."""
-import re
-import struct
-
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from tests import lora_fixtures as lf
+from tests import harness
 from tests import sce_oracle
-from tests.ties_checks import ALPHAS, DTYPES, KS, SMALL, assert_outputs, f32_bits, make_inputs, raw, run_cli  # noqa: F401
+from tests.harness import ALPHAS, DTYPES, SMALL, expected_by_tensor, f32_bits, f64_bits, make_inputs, raw, ties_models
 
 TOPKS = (1.0, 0.5, 0.1, 0.01, 1e-9)              # the last one: k_keep == 0, the output is base_out
 # unequal alphas with one alpha of 0 (SCE takes alphas >= 0)
 SCE_ALPHAS = (0.5, 0.0, 0.4, 0.25, 0.6, 0.1, 0.35, 0.45, 0.2, 0.15, 0.55, 0.05, 0.7, 0.3, 0.5, 0.4)
 SIZES = (1, 7, 8, 9, 32767, 32768, 32769, 3 * 32768 + 5)     # the octet and segment boundaries of the energy order
-
-
-def f64_bits(x: float) -> bytes:
-    return struct.pack("<d", float(x))
 
 
 def check(engine, fts, bases, alphas, base_out, select_topk=1.0, lam=1.0, label=""):
@@ -301,35 +293,14 @@ OPTIONS = {"operator": "sce", "select_topk": 0.3, "sce_lambda": 0.7}
 README_WORDS = ("# SCE Merged Model", "SCE (sce:", "select_topk 0.3", "sce_lambda 0.7")
 
 
-def sce_models(third):
-    """layer 0: all three finetunes, layer 1: ft1 and `third`; ft2 is a finetune of ft1 (its own base)"""
-    return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-            {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-            {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
-
-
 def write_config(root, third, out_dir, options=OPTIONS, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": sce_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(options)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, ties_models(third), out_dir, options, device)
 
 
 def expected_outputs(base, full, options=OPTIONS):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        entries = [(ft1[name], base[name], 0.5)] + ([(ft2[name], ft1[name], 0.3)] if int(m.group(1)) == 0 else []) + \
-                  [(full[name], base[name], 0.4)]
-        out[name] = sce_oracle.sce_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                         options.get("select_topk", 1.0), options.get("sce_lambda", 1.0))["out"]
-    return out
+    def merge(fts, bases, alphas, base_out, name):
+        return sce_oracle.sce_merge(
+            fts, bases, alphas, base_out, options.get("select_topk", 1.0), options.get("sce_lambda", 1.0))["out"]
+
+    return expected_by_tensor(base, full, ties_models("org/lora_full"), merge)

@@ -11,27 +11,21 @@ the GPU tier (tests/test_sphere_gpu.py).
    k = 2, closed forms, invariances - so that an oracle and a kernel with the same mistake do not pass together."""
 import ctypes as C
 import math
-import re
 import struct
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from tests import lora_fixtures as lf
+from tests import harness
 from tests import sphere_oracle as so
-from tests.ties_checks import ALPHAS, DTYPES, KS, SMALL, assert_outputs, f32_bits, make_inputs, raw, run_cli  # noqa: F401
+from tests.harness import ALPHAS, DTYPES, SMALL, expected_by_tensor, f32_bits, f64_bits, make_inputs, raw, ties_models
 
 MODES = so.MODES
 # (mode, rowwise): the four operator variants
 VARIANTS = (("karcher", False), ("karcher", True), ("multislerp", False), ("multislerp", True))
 VARIANT_IDS = ["karcher", "karcher_rowwise", "multislerp", "multislerp_rowwise"]
 FN_BOUND = 2.0 ** -40
-
-
-def f64_bits(x: float) -> bytes:
-    return struct.pack("<d", float(x))
 
 
 def bits64(xs):
@@ -551,36 +545,15 @@ def options(operator, row_wise=None, **more):
     return opts
 
 
-def sphere_models(third):
-    """layer 0: all three finetunes, layer 1: ft1 and `third`; ft2 is a finetune of ft1 (its own base)"""
-    return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-            {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-            {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
-
-
 def write_config(root, third, out_dir, opts, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": sphere_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(opts)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, ties_models(third), out_dir, opts, device)
 
 
 def expected_outputs(base, full, opts):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        layer = int(m.group(1))
-        entries = [(ft1[name], base[name], 0.5)] + ([(ft2[name], ft1[name], 0.3)] if layer == 0 else []) + [(full[name], base[name], 0.4)]
-        out[name] = so.sphere_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                    mode=opts["operator"], rowwise=bool(opts.get("sphere_row_wise", 0)),
-                                    max_iter=int(opts.get("karcher_max_iter", 10)), tol=float(opts.get("karcher_tol", 1e-5)))["out"]
-    return out
+    def merge(fts, bases, alphas, base_out, name):
+        return so.sphere_merge(
+            fts, bases, alphas, base_out, mode=opts["operator"], rowwise=bool(opts.get("sphere_row_wise", 0)),
+            max_iter=int(opts.get("karcher_max_iter", 10)), tol=float(opts.get("karcher_tol", 1e-5)))["out"]
+
+    return expected_by_tensor(base, full, ties_models("org/lora_full"), merge)

@@ -10,12 +10,12 @@ import struct
 
 import pytest
 import torch
-import yaml
 from click.testing import CliRunner
 
+from tests import harness
 from tests import lora_fixtures as lf
 from tests import stats_oracle
-from tests.ties_checks import ALPHAS, DTYPES, f32_bits, make_inputs, ties_models  # noqa: F401
+from tests.harness import ALPHAS, f32_bits, make_inputs, profile_of, ties_models
 
 FIELDS = ("nonzero", "gram", "k_keep", "thresholds", "kept", "energy", "opposed", "alone", "cover", "conflict")
 SEG = 32768
@@ -27,7 +27,8 @@ DENS_MIXED = (0.5, 1.0, 0.5, 1e-9)              # a duplicate, density 1, and a 
 SHAPE = (37, 129)                               # 4773 elements: unaligned rows and a tail octet
 
 
-def f64_bits(x: float) -> bytes:
+def report_f64_bits(x: float) -> bytes:
+    """the value packed as it stands, without the float() of harness.f64_bits: what float() would parse, a string say, is an error here"""
     return struct.pack("<d", x)
 
 
@@ -36,7 +37,7 @@ def bits(field, value):
     if field == "thresholds":
         return [[f32_bits(v) for v in row] for row in value]
     if field in ("gram", "energy"):
-        return [[f64_bits(v) for v in row] for row in value]
+        return [[report_f64_bits(v) for v in row] for row in value]
     return value
 
 
@@ -49,7 +50,7 @@ def assert_identities(rep, label=""):
         for i in range(k):
             assert rep.opposed[q][i] <= rep.kept[q][i] <= rep.nonzero[i], (label, q, i)
             if rep.densities[q] == 1.0:
-                assert f64_bits(rep.energy[q][i]) == f64_bits(rep.gram[i][i]), (label, q, i, rep.energy[q][i], rep.gram[i][i])
+                assert report_f64_bits(rep.energy[q][i]) == report_f64_bits(rep.gram[i][i]), (label, q, i, rep.energy[q][i], rep.gram[i][i])
                 assert rep.kept[q][i] == rep.nonzero[i]
     assert all(rep.gram[i][j] == rep.gram[j][i] for i in range(k) for j in range(k))
 
@@ -223,17 +224,6 @@ CORNERS = [check_unaligned, check_duplicate_zero_and_one, check_signed_alphas, c
 
 
 # ---- profile names and launches ----------------------------------------------------------------------------
-def profile_of(engine, call):
-    engine.ctx.profile(True)
-    engine.ctx.profile_reset()
-    try:
-        call()
-        table = engine.ctx.profile_table()
-    finally:
-        engine.ctx.profile(False)
-    return {n: table[n][0] for n in table}
-
-
 def check_profile(engine, k, m, shape=(40, 50), device="cpu"):
     """three stats_hist launches per group of four finetunes and three stats_select launches, whatever m; the Gram through
     geo_gram's own launches; one fused pass and its fold"""
@@ -289,15 +279,7 @@ def check_model_shape(engine, shape, k, own, densities, device="cpu"):
 
 # ---- the CLI on the synthetic on-disk model of tests/lora_fixtures.py ----------------------------------------
 def write_config(root, third, out_dir, options=None, device=None, models=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": models or ties_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage")}
-    if options:
-        cfg["merge_options"] = dict(options)
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, models or ties_models(third), out_dir, options or None, device)
 
 
 def run_cli(args):
@@ -306,7 +288,7 @@ def run_cli(args):
 
 
 def expected_records(base, full, densities, windows=True):
-    """the oracle tensor by tensor, in the order merge takes the tensors: the models of ties_checks.ties_models - layer 0
+    """the oracle tensor by tensor, in the order merge takes the tensors: the models of harness.ties_models - layer 0
     has three entries, layer 1 two (windows) - or all three everywhere"""
     ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
     out = []

@@ -7,6 +7,7 @@ import torch
 
 from tests import breadcrumbs_checks as bc
 from tests import lora_fixtures as lf
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -16,22 +17,16 @@ MODEL_SHAPES = [((4096, 4096), 3), ((8192, 8192), 3), ((28672, 8192), 2), ((8192
                 ((4544, 4544), 3), ((128256, 4096), 2), ((1, 4096), 3)]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
-
-
 @pytest.mark.parametrize("sign_election", bc.MODES, ids=MODE_IDS)
-@pytest.mark.parametrize("bo_dtype", bc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", bc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype, sign_election):
     bc.check_dtypes(eng, in_dtype, bo_dtype, sign_election, device=eng.device)
 
 
 @pytest.mark.parametrize("sign_election", bc.MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("density,gamma", bc.DENSITY_GAMMA)
-@pytest.mark.parametrize("k", bc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_density_gamma(eng, k, density, gamma, sign_election):
     bc.check_k_density_gamma(eng, k, density, gamma, sign_election, device=eng.device)
 
@@ -51,23 +46,23 @@ def test_corner(eng, check):
 @pytest.mark.parametrize("case", list(enumerate(MODEL_SHAPES)), ids=lambda c: "x".join(map(str, c[1][0])) + f"-k{c[1][1]}-" + MODE_IDS[c[0] % 2])
 def test_model_shape(eng, case):
     i, (shape, k) = case
-    fts, bases, bo = bc.make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
-    rep = bc.check(eng, fts, bases, bc.ALPHAS[:k], bo, density=0.9, gamma=0.01, lam=0.7, sign_election=i % 2 == 0, label=f"{shape} k={k}")
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
+    rep = bc.check(eng, fts, bases, ALPHAS[:k], bo, density=0.9, gamma=0.01, lam=0.7, sign_election=i % 2 == 0, label=f"{shape} k={k}")
     assert all(kept >= rep.k_keep for kept in rep.kept) and all(d <= rep.n_top for d in rep.dropped_top)
     del fts, bases, bo
     torch.cuda.empty_cache()
 
 
 def test_model_shape_at_low_density(eng):
-    fts, bases, bo = bc.make_inputs((8192, 8192), 3, seed=7, device=eng.device)
-    rep = bc.check(eng, fts, bases, bc.ALPHAS[:3], bo, density=0.2, gamma=0.01, lam=0.7, sign_election=True, label="8192^2 k=3, 0.2 / 0.01")
+    fts, bases, bo = make_inputs((8192, 8192), 3, seed=7, device=eng.device)
+    rep = bc.check(eng, fts, bases, ALPHAS[:3], bo, density=0.2, gamma=0.01, lam=0.7, sign_election=True, label="8192^2 k=3, 0.2 / 0.01")
     assert all(kept >= rep.k_keep for kept in rep.kept) and all(1 <= d <= rep.n_top for d in rep.dropped_top)
     del fts, bases, bo
     torch.cuda.empty_cache()
 
 
 def test_model_shape_with_own_bases(eng):
-    fts, bases, bo = bc.make_inputs((4096, 4096), 3, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
+    fts, bases, bo = make_inputs((4096, 4096), 3, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
     bc.check(eng, fts, bases, [0.5, -0.3, 0.4], bo, density=0.05, gamma=0.002, normalize=False, sign_election=False,
              label="4096^2, own bases, fp32 output")
     del fts, bases, bo
@@ -87,7 +82,7 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, inplace, operator):
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
     opts = bc.options(operator)
-    res = bc.run_cli(bc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
+    res = run_cli(bc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
     assert res.exit_code == 0, res.output
-    bc.assert_outputs(tmp_path / "merged", bc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", bc.expected_outputs(base, full, opts))
     assert "Breadcrumbs" in (tmp_path / "merged" / "README.md").read_text()

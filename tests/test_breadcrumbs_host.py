@@ -2,47 +2,32 @@
 emulator against tests/breadcrumbs_oracle.py (bit for bit, tests/breadcrumbs_checks.py), the YAML options, the stamp, and
 `python -m shard merge` end to end - single process, in place, and two gloo ranks - with the emulator as the device."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
 
 import click
 import pytest
 import torch
-import yaml
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import MergeConfig
 from tests import breadcrumbs_checks as bc
 from tests import lora_fixtures as lf
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, emul, make_inputs, run_cli, run_ranks, yaml_config  # noqa: F401
 
-REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("breadcrumbs", "breadcrumbs_ties")
 MODE_IDS = ["breadcrumbs_ties", "breadcrumbs"]
 
 
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
-
-
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
 @pytest.mark.parametrize("sign_election", bc.MODES, ids=MODE_IDS)
-@pytest.mark.parametrize("bo_dtype", bc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", bc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype, sign_election):
     bc.check_dtypes(emul, in_dtype, bo_dtype, sign_election)
 
 
 @pytest.mark.parametrize("sign_election", bc.MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("density,gamma", bc.DENSITY_GAMMA)
-@pytest.mark.parametrize("k", bc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_density_gamma(emul, k, density, gamma, sign_election):
     bc.check_k_density_gamma(emul, k, density, gamma, sign_election)
 
@@ -60,8 +45,8 @@ def test_corner(emul, check):
 
 
 def test_largest_emulator_shape(emul):
-    fts, bases, bo = bc.make_inputs((512, 1024), 3, seed=5, own_bases=True)
-    bc.check(emul, fts, bases, bc.ALPHAS[:3], bo, density=0.2, gamma=0.01, lam=0.7, sign_election=True, label="512 x 1024")
+    fts, bases, bo = make_inputs((512, 1024), 3, seed=5, own_bases=True)
+    bc.check(emul, fts, bases, ALPHAS[:3], bo, density=0.2, gamma=0.01, lam=0.7, sign_election=True, label="512 x 1024")
 
 
 @pytest.mark.parametrize("k,expected", [(2, {"crumbs_hist": 3, "crumbs_select": 3, "crumbs_merge": 1}),
@@ -105,16 +90,6 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 @pytest.mark.parametrize("operator", OPERATORS)
 def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     from shardmerge_amd.merge import operator_class
@@ -124,21 +99,21 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     cls = operator_class(operator)
     assert cls is (BreadcrumbsTiesMerge if operator == "breadcrumbs_ties" else BreadcrumbsMerge) and issubclass(cls, TiesMerge)
     assert cls.sign_election is (operator == "breadcrumbs_ties")
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}))
     assert cfg.operator == operator and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.density, m.gamma, m.breadcrumbs_lambda, bool(m.breadcrumbs_normalize)) == (0.9, 0.01, 1.0, True)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 1, "gamma": 0, "breadcrumbs_lambda": 0.7,
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 1, "gamma": 0, "breadcrumbs_lambda": 0.7,
                                                  "breadcrumbs_normalize": 0}))
     assert cfg.merge_options == {"density": 1.0, "gamma": 0.0, "breadcrumbs_lambda": 0.7, "breadcrumbs_normalize": 0.0}
     m = cls(config=cfg, index_manager=object())
     assert (m.density, m.gamma, m.breadcrumbs_lambda, bool(m.breadcrumbs_normalize)) == (1.0, 0.0, 0.7, False)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 0.2, "gamma": 0.05, "breadcrumbs_lambda": 0.7}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 0.2, "gamma": 0.05, "breadcrumbs_lambda": 0.7}))
     readme = cls(config=cfg, index_manager=object()).get_readme()
     for word in ("# Breadcrumbs Merged Model", operator + ":", "density 0.2", "gamma 0.05", "lambda 0.7", "org/ft1",
                  "agreeing weights" if operator == "breadcrumbs_ties" else "sum of the weights"):
         assert word in readme, (word, readme)
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 0.5, "gamma": 0.5})).merge_options == \
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 0.5, "gamma": 0.5})).merge_options == \
         {"density": 0.5, "gamma": 0.5}
     # the one method both paths call is what differs; the cost model is TIES's
     assert cls.merge_block is not TiesMerge.merge_block and cls._merge_layer is FourierMerge._merge_layer
@@ -155,7 +130,7 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
 def test_yaml_rejects_out_of_range_values(tmp_path, operator, options):
     (key, _), = options.items()
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **options}))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -164,7 +139,7 @@ def test_yaml_rejects_out_of_range_values(tmp_path, operator, options):
 def test_yaml_rejects_density_plus_gamma_above_one(tmp_path, operator, options):
     """(the defaults take part: density 1 with the default gamma 0.01 is out of range)"""
     with pytest.raises(click.BadParameter) as e:
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **options}))
     assert "density" in str(e.value) and "gamma" in str(e.value)
 
 
@@ -175,7 +150,7 @@ def test_yaml_rejects_a_breadcrumbs_key_with_another_operator(tmp_path, operator
     if operator:
         opts["operator"] = operator
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: breadcrumbs"):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -185,11 +160,11 @@ def test_yaml_rejects_a_breadcrumbs_key_with_another_operator(tmp_path, operator
                                        ("seed", 0), ("bogus", 1)])
 def test_yaml_rejects_an_option_breadcrumbs_would_ignore(tmp_path, operator, key, value):
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}))
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "breadcrumbs", "density": 0.9, "gamma": 0.01, "breadcrumbs_lambda": 1.0, "breadcrumbs_normalize": 1}
     base = stamp(full)
     assert base == stamp(dict(full))
@@ -206,26 +181,26 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator):
     opts = bc.options(operator)
     expected = bc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = bc.run_cli(bc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(bc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    bc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in ("# Breadcrumbs Merged Model", operator + ":", "density 0.3", "gamma 0.05", "lambda 0.7"):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = bc.run_cli(bc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(bc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = bc.run_cli(bc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
+    res = run_cli(bc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
     assert res.exit_code == 0, res.output
-    bc.assert_outputs(tmp_path / "merged_default", bc.expected_outputs(base, full, {"operator": operator}))
+    assert_outputs(tmp_path / "merged_default", bc.expected_outputs(base, full, {"operator": operator}))
     # the upper cut shows in the output: gamma 0 is another model
-    res = bc.run_cli(bc.write_config(tmp_path, "org/lora_full", "merged_gamma0", {**opts, "gamma": 0}))
+    res = run_cli(bc.write_config(tmp_path, "org/lora_full", "merged_gamma0", {**opts, "gamma": 0}))
     assert res.exit_code == 0, res.output
     other = lf.read_outputs(tmp_path / "merged_gamma0")
     assert any(not torch.equal(other[n], expected[n]) for n in expected if "layers" in n)
-    bc.assert_outputs(tmp_path / "merged_gamma0", bc.expected_outputs(base, full, {**opts, "gamma": 0}))
+    assert_outputs(tmp_path / "merged_gamma0", bc.expected_outputs(base, full, {**opts, "gamma": 0}))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -235,9 +210,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator):
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = bc.options(operator)
-    res = bc.run_cli(bc.write_config(tmp_path, "org/lora", "merged", opts))
+    res = run_cli(bc.write_config(tmp_path, "org/lora", "merged", opts))
     assert res.exit_code == 0, res.output
-    bc.assert_outputs(tmp_path / "merged", bc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", bc.expected_outputs(base, full, opts))
     assert "Breadcrumbs" in (tmp_path / "merged" / "README.md").read_text()
 
 
@@ -246,16 +221,6 @@ def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul, operator):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = bc.options(operator)
     cfg = bc.write_config(tmp_path, "org/lora", "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    bc.assert_outputs(tmp_path / "merged", bc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", bc.expected_outputs(base, full, opts))

@@ -8,6 +8,7 @@ import torch
 
 from tests import consensus_checks as cc
 from tests import lora_fixtures as lf
+from tests.harness import ALPHAS, DTYPES, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -16,15 +17,9 @@ MODEL_SHAPES = [((1024, 4096), 3, cc.FLAVOURS), ((300, 4544), 3, cc.FLAVOURS), (
                 ((4096, 4096), 3, (True,))]     # (the selection's histograms need a tensor that spans many work-groups)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
-
-
 @pytest.mark.parametrize("ties", cc.FLAVOURS, ids=cc.FLAVOUR_IDS)
-@pytest.mark.parametrize("bo_dtype", cc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", cc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype, ties):
     cc.check_dtypes(eng, in_dtype, bo_dtype, ties, device=eng.device)
 
@@ -57,9 +52,9 @@ def test_corner(eng, check):
 
 @pytest.mark.parametrize("shape,k,flavours", MODEL_SHAPES, ids=["x".join(map(str, s)) + f"-k{k}" for s, k, _ in MODEL_SHAPES])
 def test_model_shape(eng, shape, k, flavours):
-    fts, bases, bo = cc.make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
     for ties in flavours:
-        rep, _, _ = cc.check(eng, fts, bases, cc.ALPHAS[:k], bo, ties=ties, lam=0.7, label=f"{shape} k={k} {cc.name_of(ties)}")
+        rep, _, _ = cc.check(eng, fts, bases, ALPHAS[:k], bo, ties=ties, lam=0.7, label=f"{shape} k={k} {cc.name_of(ties)}")
         assert 0 < rep.selected < rep.n
     del fts, bases, bo
     torch.cuda.empty_cache()
@@ -68,8 +63,8 @@ def test_model_shape(eng, shape, k, flavours):
 @pytest.mark.parametrize("ties", cc.FLAVOURS, ids=cc.FLAVOUR_IDS)
 def test_model_shape_k16_with_own_bases(eng, ties):
     """the 128-register variant over many work-groups, with the plain sum and with the TIES election"""
-    fts, bases, bo = cc.make_inputs((2048, 4096), 16, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
-    alphas = [a if i % 3 else -a for i, a in enumerate(cc.ALPHAS)]
+    fts, bases, bo = make_inputs((2048, 4096), 16, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
+    alphas = [a if i % 3 else -a for i, a in enumerate(ALPHAS)]
     cc.check(eng, fts, bases, alphas, bo, ties=ties, consensus_k=4, normalize=not ties,
              label=f"2048 x 4096 k=16, own bases, fp32 output, {cc.name_of(ties)}")
     del fts, bases, bo
@@ -92,7 +87,7 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, inplace, operator):
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
     opts = cc.options(operator)
-    res = cc.run_cli(cc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
+    res = run_cli(cc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
     assert res.exit_code == 0, res.output
-    cc.assert_outputs(tmp_path / "merged", cc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", cc.expected_outputs(base, full, opts))
     assert "Consensus" in (tmp_path / "merged" / "README.md").read_text()

@@ -2,39 +2,24 @@
 selection kernels of TIES) on the CPU work-group emulator against tests/consensus_oracle.py (bit for bit,
 tests/consensus_checks.py), the YAML options, the stamp, and `python -m shard merge` end to end - single process, in
 place, and two gloo ranks - with the emulator as the device."""
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
-
 import click
 import pytest
 import torch
-import yaml
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import MergeConfig
 from tests import consensus_checks as cc
 from tests import lora_fixtures as lf
+from tests.harness import (ALPHAS, DTYPES, assert_outputs, emul, make_inputs, run_cli, run_ranks,  # noqa: F401
+                           yaml_config)
 
-REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("consensus_ta", "consensus_ties")
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
 
 
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
 @pytest.mark.parametrize("ties", cc.FLAVOURS, ids=cc.FLAVOUR_IDS)
-@pytest.mark.parametrize("bo_dtype", cc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", cc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype, ties):
     cc.check_dtypes(emul, in_dtype, bo_dtype, ties)
 
@@ -66,9 +51,9 @@ def test_corner(emul, check):
 
 
 def test_largest_emulator_shape(emul):
-    fts, bases, bo = cc.make_inputs((512, 1024), 3, seed=5, own_bases=True)
+    fts, bases, bo = make_inputs((512, 1024), 3, seed=5, own_bases=True)
     for ties in cc.FLAVOURS:
-        cc.check(emul, fts, bases, cc.ALPHAS[:3], bo, ties=ties, lam=0.7, label="512 x 1024")
+        cc.check(emul, fts, bases, ALPHAS[:3], bo, ties=ties, lam=0.7, label="512 x 1024")
 
 
 @pytest.mark.parametrize("ties,k,expected", cc.PROFILES, ids=cc.PROFILE_IDS)
@@ -81,16 +66,6 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 @pytest.mark.parametrize("operator", OPERATORS)
 def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     from shardmerge_amd.merge import operator_class
@@ -101,7 +76,7 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     cls = operator_class(operator)
     assert cls is (ConsensusTiesMerge if ties else ConsensusTaMerge) and issubclass(cls, TiesMerge)
     assert cls.ties is ties
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}))
     assert cfg.operator == operator and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.mask_lambda, m.consensus_k, m.consensus_lambda, bool(m.consensus_normalize), m.density) == (0.4, 2, 1.0, True, 0.2)
@@ -109,7 +84,7 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     want = {"mask_lambda": 1.0, "consensus_k": 3, "consensus_lambda": 0.7, "consensus_normalize": 0.0}
     if ties:
         opts["density"], want["density"] = 1, 1.0
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, opts))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, opts))
     assert cfg.merge_options == want and type(cfg.merge_options["consensus_k"]) is int
     m = cls(config=cfg, index_manager=object())
     assert (m.mask_lambda, int(m.consensus_k), m.consensus_lambda, bool(m.consensus_normalize)) == (1.0, 3, 0.7, False)
@@ -117,10 +92,10 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     for word in ("# Consensus Merged Model", operator + ":", "mask_lambda 1", "consensus_k 3", "lambda 0.7", "plain sum", "org/ft1",
                  "density 1" if ties else "task arithmetic"):
         assert word in readme, (word, readme)
-    readme = cls(config=MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator})), index_manager=object()).get_readme()
+    readme = cls(config=MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator})), index_manager=object()).get_readme()
     assert ("agreeing weights" if ties else "sum of the weights") in readme and ("density" in readme) is ties, readme
     for edge in ({"mask_lambda": 0}, {"mask_lambda": 1e6}, {"consensus_k": 1}, {"consensus_k": 16}):
-        assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **edge})).merge_options == \
+        assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **edge})).merge_options == \
             {k: (v if k == "consensus_k" else float(v)) for k, v in edge.items()}
     # the one method both paths call is what differs; the routing is FourierMerge's
     assert cls.merge_block is not TiesMerge.merge_block and cls._merge_layer is FourierMerge._merge_layer
@@ -138,18 +113,18 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
 def test_yaml_rejects_out_of_range_values(tmp_path, operator, options):
     (key, _), = options.items()
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **options}))
 
 
 @pytest.mark.parametrize("value", [0, -0.1, 1.0001, "0.2", True])
 def test_yaml_rejects_an_out_of_range_density(tmp_path, value):
     with pytest.raises(click.BadParameter, match="density"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "consensus_ties", "density": value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "consensus_ties", "density": value}))
 
 
 def test_yaml_rejects_density_with_consensus_ta(tmp_path):
     with pytest.raises(click.BadParameter, match=r"merge_options\.density is accepted only with operator: consensus_ties"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "consensus_ta", "density": 0.2}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "consensus_ta", "density": 0.2}))
 
 
 @pytest.mark.parametrize("operator", [None, "fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear",
@@ -160,7 +135,7 @@ def test_yaml_rejects_a_consensus_key_with_another_operator(tmp_path, operator, 
     if operator:
         opts["operator"] = operator
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: consensus_ta or consensus_ties"):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -174,11 +149,11 @@ def test_yaml_rejects_an_option_consensus_would_ignore(tmp_path, operator, key, 
     """the message names the rejected key itself and the operator that would ignore it"""
     named = r"unknown keys \['bogus'\]" if key == "bogus" else rf"merge_options\.{key}\b.*operator '{operator}'"
     with pytest.raises(click.BadParameter, match=named):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}))
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "consensus_ties", "density": 0.2, "mask_lambda": 0.4, "consensus_k": 2, "consensus_lambda": 1.0,
             "consensus_normalize": 1}
     base = stamp(full)
@@ -197,26 +172,26 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator):
     opts = cc.options(operator)
     expected = cc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = cc.run_cli(cc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(cc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    cc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in ("# Consensus Merged Model", operator + ":", "mask_lambda 0.6", "consensus_k 2", "lambda 0.7"):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = cc.run_cli(cc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(cc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = cc.run_cli(cc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
+    res = run_cli(cc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
     assert res.exit_code == 0, res.output
-    cc.assert_outputs(tmp_path / "merged_default", cc.expected_outputs(base, full, {"operator": operator}))
+    assert_outputs(tmp_path / "merged_default", cc.expected_outputs(base, full, {"operator": operator}))
     # the consensus shows in the output: consensus_k 1 is another model
-    res = cc.run_cli(cc.write_config(tmp_path, "org/lora_full", "merged_k1", {**opts, "consensus_k": 1}))
+    res = run_cli(cc.write_config(tmp_path, "org/lora_full", "merged_k1", {**opts, "consensus_k": 1}))
     assert res.exit_code == 0, res.output
     other = lf.read_outputs(tmp_path / "merged_k1")
     assert any(not torch.equal(other[n], expected[n]) for n in expected if "layers" in n)
-    cc.assert_outputs(tmp_path / "merged_k1", cc.expected_outputs(base, full, {**opts, "consensus_k": 1}))
+    assert_outputs(tmp_path / "merged_k1", cc.expected_outputs(base, full, {**opts, "consensus_k": 1}))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -226,9 +201,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator):
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = cc.options(operator)
-    res = cc.run_cli(cc.write_config(tmp_path, "org/lora", "merged", opts))
+    res = run_cli(cc.write_config(tmp_path, "org/lora", "merged", opts))
     assert res.exit_code == 0, res.output
-    cc.assert_outputs(tmp_path / "merged", cc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", cc.expected_outputs(base, full, opts))
     assert "Consensus" in (tmp_path / "merged" / "README.md").read_text()
 
 
@@ -237,16 +212,6 @@ def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul, operator):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = cc.options(operator)
     cfg = cc.write_config(tmp_path, "org/lora", "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    cc.assert_outputs(tmp_path / "merged", cc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", cc.expected_outputs(base, full, opts))

@@ -5,9 +5,7 @@ ranks - with the emulator as the device."""
 import ctypes as C
 import fcntl
 import os
-import socket
 import subprocess
-import sys
 from pathlib import Path
 
 import click
@@ -21,19 +19,11 @@ from shardmerge_amd.config import MergeConfig
 from tests import dare_checks as dc
 from tests import dare_oracle
 from tests import lora_fixtures as lf
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, emul, make_inputs, run_cli, run_ranks, yaml_config  # noqa: F401
 
 REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("dare_ties", "dare_linear")
 MODE_IDS = ["dare_ties", "dare_linear"]
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
 
 
 # ---- the generator ------------------------------------------------------------------------------------------------
@@ -99,15 +89,15 @@ def test_mask_helper_at_64_bit_indices():
 
 # ---- the kernel on the emulator against the oracle ----------------------------------------------------------
 @pytest.mark.parametrize("sign_election", dc.MODES, ids=MODE_IDS)
-@pytest.mark.parametrize("bo_dtype", dc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", dc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype, sign_election):
     dc.check_dtypes(emul, in_dtype, bo_dtype, sign_election)
 
 
 @pytest.mark.parametrize("sign_election", dc.MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("density", dc.DENSITIES)
-@pytest.mark.parametrize("k", dc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_and_density(emul, k, density, sign_election):
     dc.check_k_density(emul, k, density, sign_election)
 
@@ -136,16 +126,16 @@ def test_statistics(emul, density):
 
 
 def test_largest_emulator_shape(emul):
-    fts, bases, bo = dc.make_inputs((512, 1024), 3, seed=5, own_bases=True)
-    dc.check(emul, fts, bases, dc.ALPHAS[:3], bo, density=0.2, lam=0.7, label="512 x 1024")
+    fts, bases, bo = make_inputs((512, 1024), 3, seed=5, own_bases=True)
+    dc.check(emul, fts, bases, ALPHAS[:3], bo, density=0.2, lam=0.7, label="512 x 1024")
 
 
 def test_profile_names_and_launches(emul):
-    fts, bases, bo = dc.make_inputs((40, 50), 5, seed=6)
+    fts, bases, bo = make_inputs((40, 50), 5, seed=6)
     emul.ctx.profile(True)
     emul.ctx.profile_reset()
     try:
-        emul.dare_merge(fts, bases, dc.ALPHAS[:5], bo)
+        emul.dare_merge(fts, bases, ALPHAS[:5], bo)
         table = emul.ctx.profile_table()
     finally:
         emul.ctx.profile(False)
@@ -182,16 +172,6 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 @pytest.mark.parametrize("operator", OPERATORS)
 def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     from shardmerge_amd.merge import operator_class
@@ -201,30 +181,30 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     cls = operator_class(operator)
     assert cls is (DareTiesMerge if operator == "dare_ties" else DareLinearMerge) and issubclass(cls, TiesMerge)
     assert cls.sign_election is (operator == "dare_ties")
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}))
     assert cfg.operator == operator and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.density, m.dare_lambda, bool(m.dare_normalize), bool(m.dare_rescale), m.seed) == (0.2, 1.0, True, True, 0)
     seed = 2 ** 63 - 1                                           # not representable in a double: it must survive exactly
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 1, "dare_lambda": 0.7, "dare_normalize": 0,
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 1, "dare_lambda": 0.7, "dare_normalize": 0,
                                                  "dare_rescale": 0, "seed": seed}))
     assert cfg.merge_options == {"density": 1.0, "dare_lambda": 0.7, "dare_normalize": 0.0, "dare_rescale": 0.0, "seed": seed}
     assert isinstance(cfg.merge_options["seed"], int)
     m = cls(config=cfg, index_manager=object())
     assert (m.density, m.dare_lambda, bool(m.dare_normalize), bool(m.dare_rescale)) == (1.0, 0.7, False, False)
     assert m.seed == seed and isinstance(m.seed, int)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 0.2, "dare_lambda": 0.7, "seed": 42}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 0.2, "dare_lambda": 0.7, "seed": 42}))
     readme = cls(config=cfg, index_manager=object()).get_readme()
     for word in ("DARE", operator, "density 0.2", "13107/65536", "0.199997", "lambda 0.7", "seed 42", "org/ft1"):
         assert word in readme, (word, readme)
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 2.0 ** -16})).merge_options == {"density": 2.0 ** -16}
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 2.0 ** -16})).merge_options == {"density": 2.0 ** -16}
     # the one method both paths call is what differs
     assert cls.merge_block is not TiesMerge.merge_block and cls._merge_layer is FourierMerge._merge_layer
 
 
 def test_stream_ids_are_positions_in_the_config(tmp_path):
     from shardmerge_amd.merge.dare import DareTiesMerge, tensor_key
-    doc = yaml.safe_load(_yaml(tmp_path, {"operator": "dare_ties"}).read_text())
+    doc = yaml.safe_load(yaml_config(tmp_path, {"operator": "dare_ties"}).read_text())
     doc["finetune_merge"] = dc.dare_models("org/ft3")
     p = tmp_path / "three.yaml"
     p.write_text(yaml.safe_dump(doc))
@@ -246,7 +226,7 @@ def test_stream_ids_are_positions_in_the_config(tmp_path):
                                        ("seed", 1.5), ("seed", 1.0), ("seed", True), ("seed", -1), ("seed", 2 ** 63), ("seed", "7")])
 def test_yaml_rejects_out_of_range_values(tmp_path, operator, key, value):
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}))
 
 
 @pytest.mark.parametrize("operator", [None, "fourier", "addition", "task_addition", "fourier_legacy", "ties"])
@@ -256,7 +236,7 @@ def test_yaml_rejects_a_dare_key_with_another_operator(tmp_path, operator, key):
     if operator:
         opts["operator"] = operator
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -265,11 +245,11 @@ def test_yaml_rejects_a_dare_key_with_another_operator(tmp_path, operator, key):
                                        ("ties_normalize", 1), ("bogus", 1)])
 def test_yaml_rejects_an_option_dare_would_ignore(tmp_path, operator, key, value):
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}))
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "dare_ties", "density": 0.2, "dare_lambda": 1.0, "dare_normalize": 1, "dare_rescale": 1, "seed": 2 ** 62}
     base = stamp(full)
     assert base == stamp(dict(full))
@@ -284,7 +264,7 @@ def test_config_stamp(tmp_path):
     from dataclasses import asdict
     from shardmerge_amd.constants import DEFAULT_NORM_MODE
     for opts, operator in (({"cutoff_pct": 0.05}, "fourier"), ({"operator": "ties", "density": 0.25, "ties_lambda": 0.5}, "ties")):
-        cfg = MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        cfg = MergeConfig.from_yaml(yaml_config(tmp_path, opts))
         doc = {"output_base_model": cfg.output_base_model, "output_dtype": cfg.output_dtype,
                "finetune_merge": [asdict(m) for m in cfg.finetune_merge],
                "merge_options": {k: float(v) for k, v in opts.items() if k != "operator"},
@@ -299,26 +279,26 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator):
     opts = dc.options(operator)
     expected = dc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(dc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in ("DARE", operator, "density 0.3", "19660/65536", "lambda 0.7", f"seed {opts['seed']}"):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(dc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
+    res = run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged_default", dc.expected_outputs(base, full, {"operator": operator}))
+    assert_outputs(tmp_path / "merged_default", dc.expected_outputs(base, full, {"operator": operator}))
     # another seed: another model
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_seed", {**opts, "seed": 1}))
+    res = run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_seed", {**opts, "seed": 1}))
     assert res.exit_code == 0, res.output
     other = lf.read_outputs(tmp_path / "merged_seed")
     assert any(not torch.equal(other[n], expected[n]) for n in expected if "layers" in n)
-    dc.assert_outputs(tmp_path / "merged_seed", dc.expected_outputs(base, full, {**opts, "seed": 1}))
+    assert_outputs(tmp_path / "merged_seed", dc.expected_outputs(base, full, {**opts, "seed": 1}))
 
 
 def test_expected_outputs_depend_on_the_stream_of_the_windowed_layer(tmp_path, emul):
@@ -340,9 +320,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator):
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = dc.options(operator)
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora", "merged", opts))
+    res = run_cli(dc.write_config(tmp_path, "org/lora", "merged", opts))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))
     assert "DARE" in (tmp_path / "merged" / "README.md").read_text()
 
 
@@ -351,16 +331,6 @@ def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul, operator):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = dc.options(operator)
     cfg = dc.write_config(tmp_path, "org/lora", "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    dc.assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))

@@ -3,11 +3,6 @@ tests/della_oracle.py (bit for bit, tests/della_checks.py), the YAML options and
 and `python -m shard merge` end to end - single process, an adapter entry, in place, and two gloo ranks - with the
 emulator as the device."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
 
 import click
 import pytest
@@ -18,32 +13,23 @@ from shardmerge_amd import distributed
 from shardmerge_amd.config import MergeConfig
 from tests import della_checks as dc
 from tests import lora_fixtures as lf
+from tests.harness import DTYPES, KS, assert_outputs, emul, run_cli, run_ranks, yaml_config  # noqa: F401
 
-REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("della", "della_linear")
 MODE_IDS = ["della", "della_linear"]
 
 
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
-
-
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
 @pytest.mark.parametrize("sign_election", dc.MODES, ids=MODE_IDS)
-@pytest.mark.parametrize("bo_dtype", dc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", dc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype, sign_election):
     dc.check_dtypes(emul, in_dtype, bo_dtype, sign_election)
 
 
 @pytest.mark.parametrize("sign_election", dc.MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("window", dc.WINDOWS, ids=lambda w: f"{w[0]:.4g}-{w[1]:g}")
-@pytest.mark.parametrize("k", dc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_and_window(emul, k, window, sign_election):
     dc.check_k_window(emul, k, window, sign_election)
 
@@ -121,16 +107,6 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 @pytest.mark.parametrize("operator", OPERATORS)
 def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     from shardmerge_amd.merge import operator_class
@@ -140,18 +116,18 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
     cls = operator_class(operator)
     assert cls is (DellaMerge if operator == "della" else DellaLinearMerge) and issubclass(cls, DareTiesMerge)
     assert cls.sign_election is (operator == "della")
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}))
     assert cfg.operator == operator and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.density, m.epsilon, m.della_lambda, bool(m.della_normalize), bool(m.della_rescale), m.seed) == (0.5, 0.15, 1.0, True, True, 0)
     seed = 2 ** 63 - 1
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 1, "epsilon": 0, "della_lambda": 0.7, "della_normalize": 0,
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 1, "epsilon": 0, "della_lambda": 0.7, "della_normalize": 0,
                                                  "della_rescale": 0, "seed": seed}))
     assert cfg.merge_options == {"density": 1.0, "epsilon": 0.0, "della_lambda": 0.7, "della_normalize": 0.0, "della_rescale": 0.0, "seed": seed}
     m = cls(config=cfg, index_manager=object())
     assert (m.density, m.epsilon, m.della_lambda, bool(m.della_normalize), bool(m.della_rescale)) == (1.0, 0.0, 0.7, False, False)
     assert m.seed == seed and isinstance(m.seed, int)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "density": 0.5, "epsilon": 0.15, "della_lambda": 0.7, "seed": 42}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "density": 0.5, "epsilon": 0.15, "della_lambda": 0.7, "seed": 42}))
     readme = cls(config=cfg, index_manager=object()).get_readme()
     for word in ("DELLA", f"({operator}:", "density 0.5", "epsilon 0.15", "22937/65536", "42598/65536", "0.349991", "0.649994", "lambda 0.7",
                  "seed 42", "org/ft1"):
@@ -169,13 +145,13 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path, operator):
                                        ({"della_rescale": 0.5}, "della_rescale"), ({"seed": 1.5}, "seed"), ({"seed": -1}, "seed"), ({"seed": 2 ** 63}, "seed")])
 def test_yaml_rejects_out_of_range_values(tmp_path, operator, opts, word):
     with pytest.raises(click.BadParameter, match=word):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **opts}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **opts}))
 
 
 def test_yaml_accepts_the_corners_of_the_window(tmp_path):
     for opts in ({"density": 1, "epsilon": 0}, {"density": 0.1 + 2.0 ** -16, "epsilon": 0.1}, {"density": 2.0 ** -16, "epsilon": 0},
                  {"density": 0.7, "epsilon": 0.29}):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "della", **opts}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "della", **opts}))
 
 
 @pytest.mark.parametrize("operator", [None, "fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear",
@@ -185,7 +161,7 @@ def test_yaml_rejects_a_della_key_with_another_operator(tmp_path, operator, key)
     opts = {key: 0}
     if operator:
         opts["operator"] = operator
-    doc = yaml.safe_load(_yaml(tmp_path, opts).read_text())
+    doc = yaml.safe_load(yaml_config(tmp_path, opts).read_text())
     if operator in ("nuslerp", "slerp"):
         doc["finetune_merge"] = doc["finetune_merge"] * 2
     p = tmp_path / "other.yaml"
@@ -202,11 +178,11 @@ def test_yaml_rejects_a_della_key_with_another_operator(tmp_path, operator, key)
                                        ("bogus", 1)])
 def test_yaml_rejects_an_option_della_would_ignore(tmp_path, operator, key, value):
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}))
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "della", "density": 0.5, "epsilon": 0.15, "della_lambda": 1.0, "della_normalize": 1, "della_rescale": 1, "seed": 2 ** 62}
     base = stamp(full)
     assert base == stamp(dict(full))
@@ -223,26 +199,26 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator):
     opts = dc.options(operator)
     expected = dc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(dc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in ("DELLA", operator, "density 0.4", "epsilon 0.2", "13107/65536", "39321/65536", "lambda 0.7", f"seed {opts['seed']}"):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(dc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
+    res = run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": operator}))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged_default", dc.expected_outputs(base, full, {"operator": operator}))
+    assert_outputs(tmp_path / "merged_default", dc.expected_outputs(base, full, {"operator": operator}))
     # no window: the DARE operator of the same mode, byte for byte
     from tests import dare_checks
     dare = {"operator": "dare_ties" if operator == "della" else "dare_linear", "density": 0.4, "dare_lambda": 0.7, "seed": opts["seed"]}
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_flat", {**opts, "epsilon": 0}))
+    res = run_cli(dc.write_config(tmp_path, "org/lora_full", "merged_flat", {**opts, "epsilon": 0}))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged_flat", dare_checks.expected_outputs(base, full, dare))
+    assert_outputs(tmp_path / "merged_flat", dare_checks.expected_outputs(base, full, dare))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -252,9 +228,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator):
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = dc.options(operator)
-    res = dc.run_cli(dc.write_config(tmp_path, "org/lora", "merged", opts))
+    res = run_cli(dc.write_config(tmp_path, "org/lora", "merged", opts))
     assert res.exit_code == 0, res.output
-    dc.assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))
     assert "DELLA" in (tmp_path / "merged" / "README.md").read_text()
 
 
@@ -263,16 +239,6 @@ def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul, operator):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = dc.options(operator)
     cfg = dc.write_config(tmp_path, "org/lora", "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    dc.assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", dc.expected_outputs(base, full, opts))

@@ -3,9 +3,6 @@ least-loaded rank, ONE asynchronous broadcast per base shard issued a few shards
 its results into the pre-sized output shards in place) and must produce the tensors the single-process
 writer path produces, shard for shard."""
 import os
-import socket
-import subprocess
-import sys
 from pathlib import Path
 
 import pytest
@@ -15,14 +12,7 @@ from safetensors import safe_open
 
 from shardmerge_amd import distributed
 from tests.golden import inputs as gi
-
-REPO = Path(__file__).resolve().parents[1]
-
-
-def free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+from tests.harness import run_ranks, start_ranks
 
 
 def test_partition_in_shard_order_is_balanced_on_every_prefix():
@@ -96,15 +86,7 @@ def test_two_rank_merge_equals_single_process(tmp_path, monkeypatch):
     stale_name = sorted(gi.CLI_SHARDS)[0]
     victim = gi.CLI_SHARDS[stale_name][0][0]
     save_file({victim: torch.full((2, 2), 7.0)}, str(two / "merged" / f".part-1-{stale_name}"))
-    port = free_port()
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg2)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg2)
 
     a, b = one / "merged", two / "merged"
     assert not list(b.glob(".part-*")) and not list(b.glob(".tmp-*"))      # every shard was completed and renamed into place
@@ -124,26 +106,14 @@ def test_two_rank_merge_resumes_at_shard_granularity(tmp_path):
     build()
     cfg = gi.write_cli_model(tmp_path)
 
-    def run():
-        port = free_port()
-        procs = []
-        for r in range(2):
-            env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                       MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-            procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-        outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-        assert all(p.returncode == 0 for p in procs), "\n".join(outs)
-        return "\n".join(outs)
-
-    run()
+    run_ranks(cfg)
     out = tmp_path / "merged"
     shards = sorted(gi.CLI_SHARDS)
     keep, redo = shards[0], shards[-1]
     before = {s: (out / s).read_bytes() for s in shards}
     stamp = (out / keep).stat().st_mtime_ns
     (out / redo).unlink()
-    log = run()
+    log = "\n".join(run_ranks(cfg))
     assert "already complete" in log
     assert (out / keep).stat().st_mtime_ns == stamp
     assert {s: (out / s).read_bytes() for s in shards} == before
@@ -207,19 +177,6 @@ def write_uneven_model(root: Path, n_ft: int = 3) -> Path:
     return p
 
 
-def _run_ranks(cfg, world, extra_env=None):
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1", **(extra_env or {}))
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=600)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
-    return outs
-
-
 def test_a_failing_rank_stops_the_others(tmp_path):
     """One rank raises in the middle of its tensors: it says so in the process group's store, releases its writer
     thread and files, and the other ranks stop with an error of their own instead of waiting in the barrier for ever
@@ -227,13 +184,7 @@ def test_a_failing_rank_stops_the_others(tmp_path):
     from tests.emul.loader import build
     build()
     cfg = write_uneven_model(tmp_path)
-    port = free_port()
-    procs = []
-    for r in range(4):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="4", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   OMP_NUM_THREADS="1", SHARDMERGE_TEST_FAULT_RANK="2")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+    procs = start_ranks(cfg, 4, {"SHARDMERGE_TEST_FAULT_RANK": "2"})
     outs = [p.communicate(timeout=180)[0].decode() for p in procs]           # (a hang fails here)
     assert all(p.returncode != 0 for p in procs), [p.returncode for p in procs]
     assert "injected fault" in outs[2]
@@ -262,7 +213,7 @@ def test_four_ranks_on_uneven_shards_equal_single_process(tmp_path, monkeypatch)
     four = tmp_path / "four"
     four.mkdir()
     cfg4 = write_uneven_model(four)
-    outs = _run_ranks(cfg4, 4)
+    outs = run_ranks(cfg4, 4, timeout=600)
     a, b = one / "merged", four / "merged"
     assert not list(b.glob(".tmp-*"))
     assert sorted(p.name for p in a.iterdir()) == sorted(p.name for p in b.iterdir())
@@ -286,14 +237,14 @@ def test_four_ranks_on_uneven_shards_equal_single_process(tmp_path, monkeypatch)
     before = {s: (b / s).read_bytes() for s in shards}
     stamp = (b / shards[0]).stat().st_mtime_ns
     (b / shards[2]).unlink()
-    outs = _run_ranks(cfg4, 4)
+    outs = run_ranks(cfg4, 4, timeout=600)
     assert any("4 shard(s) already complete" in o for o in outs)
     assert (b / shards[0]).stat().st_mtime_ns == stamp
     assert {s: (b / s).read_bytes() for s in shards} == before
     # a run with other options does not trust those shards
     cfgdoc = (four / "merge.yaml").read_text()
     (four / "merge.yaml").write_text(cfgdoc + "merge_options:\n  cutoff_pct: 0.05\n")
-    outs = _run_ranks(four / "merge.yaml", 4)
+    outs = run_ranks(four / "merge.yaml", 4, timeout=600)
     assert not any("already complete" in o for o in outs)
     assert (b / shards[2]).read_bytes() != before[shards[2]]
 
@@ -317,15 +268,10 @@ def test_four_ranks_with_real_engines_share_the_gpu(tmp_path):
     four.mkdir()
     cfg4 = write_uneven_model(four)
     cfg4.write_text(cfg4.read_text().replace("device: cpu", "device: cuda"))
-    env = {"SHARDMERGE_TEST_REAL_ENGINE": "1", "SHARDMERGE_DIST_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
-    port = free_port()
-    procs = []
-    for r in range(4):
-        e = dict(os.environ, RANK=str(r), WORLD_SIZE="4", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), **env)
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg4)], env=e,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=600)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    # every rank on the one device, and with the threads the environment gives it, not the single thread of the CPU ranks
+    env = {"SHARDMERGE_TEST_REAL_ENGINE": "1", "SHARDMERGE_DIST_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0",
+           "LOCAL_RANK": "0", "OMP_NUM_THREADS": os.environ.get("OMP_NUM_THREADS")}
+    outs = run_ranks(cfg4, 4, env, timeout=600)
     a, b = one / "merged", four / "merged"
     assert not list(b.glob(".tmp-*"))
     for shard in UNEVEN_SHARDS:
@@ -341,12 +287,5 @@ def test_four_ranks_with_real_engines_share_the_gpu(tmp_path):
     shards = sorted(UNEVEN_SHARDS)
     before = {s: (b / s).read_bytes() for s in shards}
     (b / shards[1]).unlink()
-    procs = []
-    port = free_port()
-    for r in range(4):
-        e = dict(os.environ, RANK=str(r), WORLD_SIZE="4", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), **env)
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg4)], env=e,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=600)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg4, 4, env, timeout=600)
     assert {s: (b / s).read_bytes() for s in shards} == before

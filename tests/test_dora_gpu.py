@@ -8,6 +8,7 @@ from click.testing import CliRunner
 
 from tests import dora_fixtures as df
 from tests import lora_fixtures as lf
+from tests.harness import eng  # noqa: F401
 from tests.test_dora_host import check_against_fp64, dora_slack
 
 pytestmark = pytest.mark.gpu
@@ -17,12 +18,6 @@ SHAPES = [(4096, 4096), (14336, 4096), (4096, 14336), (28672, 8192), (1024, 8192
 RANKS = {s: [16, 256] for s in SHAPES}
 RANKS[(4544, 4544)] = RANKS[(3, 5)] = [7, 16, 256]
 DTYPES = (torch.bfloat16, torch.float16, torch.float32)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 def _bits(t):

@@ -14,19 +14,11 @@ from shardmerge_amd.config import MergeConfig
 from shardmerge_amd.index import LocalModelIndex
 from tests import dora_fixtures as df
 from tests import lora_fixtures as lf
+from tests.harness import emul  # noqa: F401
 
 DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 Q0 = "base_model.model.model.layers.0.self_attn.q_proj"
 EMB = "base_model.model.model.embed_tokens"
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
 
 
 def _run_cli(cfg_path):

@@ -7,14 +7,9 @@ import pytest
 import torch
 
 from tests import extract_checks as xc
+from tests.harness import eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 @pytest.mark.parametrize("L", xc.WIDTHS)

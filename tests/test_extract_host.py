@@ -8,15 +8,7 @@ import torch
 
 from tests import extract_checks as xc
 from tests import extract_oracle as xo
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
+from tests.harness import emul  # noqa: F401
 
 
 # ---- the oracle's own tools ------------------------------------------------------------------------------------

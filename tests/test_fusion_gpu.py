@@ -8,16 +8,11 @@ import torch
 
 from tests import fusion_checks as fc
 from tests import lora_fixtures as lf
+from tests.harness import DTYPES, assert_outputs, eng, run_cli, write_config  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 MODEL_SHAPES = [(2048, 4096), (16, 28672)]
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 def test_sm_exp_and_sm_log(eng):
@@ -30,8 +25,8 @@ def test_shapes(eng, C, R):
     fc.check_shape(eng, C, R, device=eng.device)
 
 
-@pytest.mark.parametrize("bo_dtype", fc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", fc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype):
     fc.check_dtypes(eng, in_dtype, bo_dtype, device=eng.device)
 
@@ -43,7 +38,7 @@ def test_corner(eng, check):
 
 @pytest.mark.parametrize("shape", MODEL_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_model_shape(eng, shape):
-    ft, base, bo = fc.make_inputs(shape, torch.bfloat16, torch.float32, seed=sum(shape) % 97, device=eng.device)
+    ft, base, bo = fc.fusion_inputs(shape, torch.bfloat16, torch.float32, seed=sum(shape) % 97, device=eng.device)
     fc.check(eng, ft, base, bo, "arcee", label=f"arcee {shape}")
     fc.check(eng, ft, base, bo, "nearswap", t=1e-3, label=f"nearswap {shape}")
     del ft, base, bo
@@ -66,7 +61,7 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, inplace, operator):
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
     opts = fc.options(operator)
-    res = fc.run_cli(fc.write_config(tmp_path, fc.models("org/lora"), "merged", opts, device="cuda"))
+    res = run_cli(write_config(tmp_path, fc.models("org/lora"), "merged", opts, device="cuda"))
     assert res.exit_code == 0, res.output
-    fc.assert_outputs(tmp_path / "merged", fc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", fc.expected_outputs(base, full, opts))
     assert ("Arcee Fusion" if operator == "arcee_fusion" else "NearSwap") in (tmp_path / "merged" / "README.md").read_text()

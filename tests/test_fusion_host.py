@@ -2,35 +2,19 @@
 tests/fusion_oracle.py (bit for bit, tests/fusion_checks.py), the YAML options, the coverage rule, the stamp, and
 `python -m shard merge` / `analyze` end to end - single process, in place, and two gloo ranks - with the emulator as the
 device."""
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
-
 import click
 import pytest
 import torch
-import yaml
 from click.testing import CliRunner
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import MergeConfig
 from tests import fusion_checks as fc
 from tests import lora_fixtures as lf
+from tests.harness import DTYPES, assert_outputs, emul, run_cli, run_ranks, write_config, yaml_config  # noqa: F401
 
-REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("arcee_fusion", "nearswap")
 OWN = {"arcee_fusion": {"fusion_iqr": 1.5}, "nearswap": {"nearswap_t": 1e-3}}
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
 
 
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
@@ -44,8 +28,8 @@ def test_shapes(emul, C, R):
     fc.check_shape(emul, C, R)
 
 
-@pytest.mark.parametrize("bo_dtype", fc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", fc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype):
     fc.check_dtypes(emul, in_dtype, bo_dtype)
 
@@ -56,7 +40,7 @@ def test_corner(emul, check):
 
 
 def test_largest_emulator_shape(emul):
-    ft, base, bo = fc.make_inputs((16, 28672), torch.bfloat16, torch.float32, seed=5)
+    ft, base, bo = fc.fusion_inputs((16, 28672), torch.bfloat16, torch.float32, seed=5)
     fc.check(emul, ft, base, bo, "arcee", label="16 x 28672")
     fc.check(emul, ft, base, bo, "nearswap", t=1e-3, label="16 x 28672")
 
@@ -71,16 +55,6 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options, entries=None):
-    doc = {"output_base_model": "org/base", "finetune_merge": entries or [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 def test_yaml_accepts_the_operators_and_their_keys(tmp_path):
     from shardmerge_amd.merge import operator_class
     from shardmerge_amd.merge.fast_fourier import FourierMerge
@@ -88,19 +62,19 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path):
     from shardmerge_amd.merge.ties import TiesMerge
     assert operator_class("arcee_fusion") is ArceeFusionMerge and operator_class("nearswap") is NearSwapMerge
     assert issubclass(NearSwapMerge, TiesMerge) and ArceeFusionMerge._merge_layer is FourierMerge._merge_layer
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "arcee_fusion"}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "arcee_fusion"}))
     assert cfg.operator == "arcee_fusion" and cfg.merge_options == {}
     m = ArceeFusionMerge(config=cfg, index_manager=object())
     assert m.fusion_iqr == 1.5 and m.tensor_passes(1) == 12
     assert "fusion_iqr 1.5" in m.get_readme() and "arcee_fusion" in m.get_readme() and "org/ft1" in m.get_readme()
     for value in (-1e6, 0, 1e6):
-        assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "arcee_fusion", "fusion_iqr": value})).merge_options == {"fusion_iqr": float(value)}
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "nearswap", "nearswap_t": 0.002}))
+        assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "arcee_fusion", "fusion_iqr": value})).merge_options == {"fusion_iqr": float(value)}
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "nearswap", "nearswap_t": 0.002}))
     assert cfg.merge_options == {"nearswap_t": 0.002}
     m = NearSwapMerge(config=cfg, index_manager=object())
     assert m.nearswap_t == 0.002 and m.tensor_passes(1) == 4
     assert "nearswap_t 0.002" in m.get_readme() and "# NearSwap Merged Model" in m.get_readme() and "org/ft1" in m.get_readme()
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "nearswap", "nearswap_t": 1e6})).merge_options == {"nearswap_t": 1e6}
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "nearswap", "nearswap_t": 1e6})).merge_options == {"nearswap_t": 1e6}
 
 
 @pytest.mark.parametrize("operator,options", [("arcee_fusion", {"fusion_iqr": 1.1e6}), ("arcee_fusion", {"fusion_iqr": -1.1e6}),
@@ -112,19 +86,19 @@ def test_yaml_accepts_the_operators_and_their_keys(tmp_path):
 def test_yaml_rejects_out_of_range_values(tmp_path, operator, options):
     (key, _), = options.items()
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **options}))
 
 
 def test_yaml_requires_nearswap_t(tmp_path):
     with pytest.raises(click.BadParameter, match=r"merge_options\.nearswap_t is required with operator nearswap"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "nearswap"}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "nearswap"}))
 
 
 def test_yaml_rejects_the_other_operators_key(tmp_path):
     with pytest.raises(click.BadParameter, match=r"merge_options\.nearswap_t is accepted only with operator: nearswap \(operator 'arcee_fusion'"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "arcee_fusion", "nearswap_t": 1e-3}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "arcee_fusion", "nearswap_t": 1e-3}))
     with pytest.raises(click.BadParameter, match=r"merge_options\.fusion_iqr is accepted only with operator: arcee_fusion \(operator 'nearswap'"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "nearswap", "nearswap_t": 1e-3, "fusion_iqr": 1.5}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "nearswap", "nearswap_t": 1e-3, "fusion_iqr": 1.5}))
 
 
 @pytest.mark.parametrize("operator", [None, "fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear",
@@ -137,7 +111,7 @@ def test_yaml_rejects_a_fusion_key_with_another_operator(tmp_path, operator, key
         opts["operator"] = operator
     entries = [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"}]
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: {only} \(operator '{operator or 'fourier'}'"):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts, entries))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts, entries))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -153,7 +127,7 @@ def test_yaml_rejects_an_option_fusion_would_ignore(tmp_path, operator, key, val
     """the message names the rejected key itself and the operator that would ignore it"""
     named = r"unknown keys \['bogus'\]" if key == "bogus" else rf"merge_options\.{key}\b.*operator '{operator}'"
     with pytest.raises(click.BadParameter, match=named):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **OWN[operator], key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **OWN[operator], key: value}))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -161,13 +135,13 @@ def test_yaml_rejects_an_option_fusion_would_ignore(tmp_path, operator, key, val
 def test_yaml_rejects_an_alpha(tmp_path, operator, alpha):
     entries = [{"model": "org/ft1", "base": "org/base", "alpha": alpha}]
     with pytest.raises(click.BadParameter, match=rf"operator {operator} takes no weight.*org/ft1"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **OWN[operator]}, entries))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **OWN[operator]}, entries))
     entries[0]["alpha"] = 1.0
-    MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, **OWN[operator]}, entries))
+    MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, **OWN[operator]}, entries))
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     base = stamp({"operator": "arcee_fusion", "fusion_iqr": 1.5})
     others = [stamp({"operator": "arcee_fusion", "fusion_iqr": 1.0}), stamp({"operator": "nearswap", "nearswap_t": 1e-3}),
               stamp({"operator": "nearswap", "nearswap_t": 2e-3}), stamp({"operator": "dare_linear", "density": 1.0}), stamp(None)]
@@ -180,7 +154,7 @@ def test_two_entries_on_one_layer_are_an_error_before_anything_is_written(tmp_pa
     lf.setup_k3(tmp_path, emul)
     entries = [{"model": "org/ft1", "base": "org/base", "is_input": True},
                {"model": "org/ft2", "base": "org/base", "is_output": True, "start_layer": 1}]
-    res = fc.run_cli(fc.write_config(tmp_path, entries, "merged", fc.options(operator)))
+    res = run_cli(write_config(tmp_path, entries, "merged", fc.options(operator)))
     assert res.exit_code != 0
     text = res.output + str(res.exception)
     assert "layer 1 is covered by 2 finetune_merge entries (org/ft1, org/ft2)" in text and operator in text, text
@@ -188,7 +162,7 @@ def test_two_entries_on_one_layer_are_an_error_before_anything_is_written(tmp_pa
     assert not out.exists() or not list(out.glob("*.safetensors"))
     # ... and a layer that no entry covers
     entries[0]["end_layer"], entries[1]["start_layer"] = 0, 2
-    res = fc.run_cli(fc.write_config(tmp_path, entries, "merged2", fc.options(operator)))
+    res = run_cli(write_config(tmp_path, entries, "merged2", fc.options(operator)))
     assert res.exit_code != 0 and "layer 1 is covered by 0 finetune_merge entries" in res.output + str(res.exception)
     assert not (tmp_path / "merged2").exists() or not list((tmp_path / "merged2").glob("*.safetensors"))
 
@@ -199,19 +173,19 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator):
     opts = fc.options(operator)
     expected = fc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = fc.run_cli(fc.write_config(tmp_path, fc.models("org/lora_full"), "merged", opts))
+    res = run_cli(write_config(tmp_path, fc.models("org/lora_full"), "merged", opts))
     assert res.exit_code == 0, res.output
-    fc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in (operator, "fusion_iqr 1" if operator == "arcee_fusion" else "nearswap_t 0.002", "org/ft1", "org/lora_full", "layers 1..end"):
         assert word in readme, (word, readme)
     # the second entry given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = fc.run_cli(fc.write_config(tmp_path, fc.models("org/lora"), "merged_adapter", opts))
+    res = run_cli(write_config(tmp_path, fc.models("org/lora"), "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # analyze keeps accepting the config: the operator's options are validated and not used
     from shardmerge_amd.__main__ import cli
-    res = CliRunner().invoke(cli, ["analyze", str(fc.write_config(tmp_path, fc.models("org/lora_full"), "analysed", opts))])
+    res = CliRunner().invoke(cli, ["analyze", str(write_config(tmp_path, fc.models("org/lora_full"), "analysed", opts))])
     assert res.exit_code == 0, res.output
 
 
@@ -222,29 +196,19 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator):
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = fc.options(operator)
-    res = fc.run_cli(fc.write_config(tmp_path, fc.models("org/lora"), "merged", opts))
+    res = run_cli(write_config(tmp_path, fc.models("org/lora"), "merged", opts))
     assert res.exit_code == 0, res.output
-    fc.assert_outputs(tmp_path / "merged", fc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", fc.expected_outputs(base, full, opts))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
 def test_two_gloo_ranks_equal_a_single_process(tmp_path, emul, operator):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = fc.options(operator)
-    res = fc.run_cli(fc.write_config(tmp_path, fc.models("org/lora"), "single", opts))
+    res = run_cli(write_config(tmp_path, fc.models("org/lora"), "single", opts))
     assert res.exit_code == 0, res.output
-    cfg = fc.write_config(tmp_path, fc.models("org/lora"), "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    cfg = write_config(tmp_path, fc.models("org/lora"), "merged", opts, device="cpu")
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
     lf.assert_same_outputs(tmp_path / "merged", tmp_path / "single", file_bytes=False)
-    fc.assert_outputs(tmp_path / "merged", fc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", fc.expected_outputs(base, full, opts))

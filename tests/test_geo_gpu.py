@@ -7,6 +7,7 @@ import torch
 
 from tests import geo_checks as gc
 from tests import lora_fixtures as lf
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 from tests.test_ties_gpu import MODEL_SHAPES
 
 pytestmark = pytest.mark.gpu
@@ -15,21 +16,15 @@ pytestmark = pytest.mark.gpu
 SHAPE_CASES = [(shape, k, *gc.VARIANTS[i % len(gc.VARIANTS)]) for i, (shape, k) in enumerate(MODEL_SHAPES)]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
-
-
 @pytest.mark.parametrize("mode,rowwise", gc.VARIANTS, ids=gc.VARIANT_IDS)
-@pytest.mark.parametrize("bo_dtype", gc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", gc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype, mode, rowwise):
     gc.check_dtypes(eng, in_dtype, bo_dtype, mode, rowwise, device=eng.device)
 
 
 @pytest.mark.parametrize("rowwise", [False, True], ids=["whole", "rowwise"])
-@pytest.mark.parametrize("k", gc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_model_stock_k(eng, k, rowwise):
     gc.check_k(eng, k, rowwise, device=eng.device)
 
@@ -43,14 +38,14 @@ def test_property_or_corner(eng, check):
                          ids=["x".join(map(str, c[0])) + f"-k{c[1]}-{c[2]}{'-rowwise' if c[3] else ''}" for c in SHAPE_CASES])
 def test_model_shape(eng, shape, k, mode, rowwise):
     k = gc.variant_k(mode, k)
-    fts, bases, bo = gc.make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
-    gc.check(eng, fts, bases, gc.ALPHAS[:k], bo, mode, rowwise, label=f"{shape} k={k} {mode}")
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
+    gc.check(eng, fts, bases, ALPHAS[:k], bo, mode, rowwise, label=f"{shape} k={k} {mode}")
     del fts, bases, bo
     torch.cuda.empty_cache()
 
 
 def test_model_shape_with_own_bases(eng):
-    fts, bases, bo = gc.make_inputs((4096, 4096), 3, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
+    fts, bases, bo = make_inputs((4096, 4096), 3, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
     gc.check(eng, fts, bases, [0.5, -0.3, 0.4], bo, "model_stock", label="4096^2, own bases, fp32 output")
     gc.check(eng, fts, bases, [0.5, -0.3, 0.4], bo, "model_stock", True, label="4096^2, own bases, fp32 output, row-wise")
 
@@ -69,9 +64,9 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, operator, filter_wise, in
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
     opts = gc.options(operator, filter_wise)
-    res = gc.run_cli(gc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
+    res = run_cli(gc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
     assert res.exit_code == 0, res.output
-    gc.assert_outputs(tmp_path / "merged", gc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", gc.expected_outputs(base, full, opts))
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in gc.README_WORDS[operator]:
         assert word in readme, (word, readme)

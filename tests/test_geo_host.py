@@ -3,48 +3,33 @@ against tests/geo_oracle.py (bit for bit, tests/geo_checks.py), the Gram against
 stamp, and `python -m shard merge` end to end - single process, in place, and two gloo ranks - with the emulator as the
 device."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
 
 import click
 import pytest
 import torch
-import yaml
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import MergeConfig
 from tests import geo_checks as gc
 from tests import lora_fixtures as lf
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, emul, make_inputs, run_cli, run_ranks, yaml_config  # noqa: F401
 
-REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("model_stock", "nuslerp", "slerp")
 # what the CLI tests run: (operator, stock_filter_wise)
 CLI_CASES = [("model_stock", None), ("model_stock", 1), ("nuslerp", None), ("slerp", None)]
 CLI_IDS = ["model_stock", "model_stock_filter_wise", "nuslerp", "slerp"]
 
 
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
-
-
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
 @pytest.mark.parametrize("mode,rowwise", gc.VARIANTS, ids=gc.VARIANT_IDS)
-@pytest.mark.parametrize("bo_dtype", gc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", gc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype, mode, rowwise):
     gc.check_dtypes(emul, in_dtype, bo_dtype, mode, rowwise)
 
 
 @pytest.mark.parametrize("rowwise", [False, True], ids=["whole", "rowwise"])
-@pytest.mark.parametrize("k", gc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_model_stock_k(emul, k, rowwise):
     gc.check_k(emul, k, rowwise)
 
@@ -60,10 +45,10 @@ def test_corner(emul, check):
 
 
 def test_largest_emulator_shape(emul):
-    fts, bases, bo = gc.make_inputs((512, 1024), 3, seed=5, own_bases=True)
-    gc.check(emul, fts, bases, gc.ALPHAS[:3], bo, "model_stock", label="512 x 1024")
-    gc.check(emul, fts, bases, gc.ALPHAS[:3], bo, "model_stock", True, label="512 x 1024 row-wise")
-    gc.check(emul, fts[:2], bases[:2], gc.ALPHAS[:2], bo, "nuslerp", label="512 x 1024 nuslerp")
+    fts, bases, bo = make_inputs((512, 1024), 3, seed=5, own_bases=True)
+    gc.check(emul, fts, bases, ALPHAS[:3], bo, "model_stock", label="512 x 1024")
+    gc.check(emul, fts, bases, ALPHAS[:3], bo, "model_stock", True, label="512 x 1024 row-wise")
+    gc.check(emul, fts[:2], bases[:2], ALPHAS[:2], bo, "nuslerp", label="512 x 1024 nuslerp")
 
 
 @pytest.mark.parametrize("k", [2, 5, 16])
@@ -114,14 +99,7 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options, models=None):
-    entries = models or [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"}]
-    doc = {"output_base_model": "org/base", "finetune_merge": entries, "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
+PAIR = [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"}]
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -132,7 +110,7 @@ def test_yaml_accepts_the_operators_and_their_defaults(tmp_path, operator):
     from shardmerge_amd.merge.ties import TiesMerge
     cls = operator_class(operator)
     assert cls is {"model_stock": ModelStockMerge, "nuslerp": NuSlerpMerge, "slerp": SlerpMerge}[operator] and issubclass(cls, TiesMerge)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, PAIR))
     assert cfg.operator == operator and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert m.mode == operator and not m.stock_filter_wise
@@ -147,18 +125,18 @@ def test_yaml_accepts_the_operators_and_their_defaults(tmp_path, operator):
 def test_yaml_stock_filter_wise(tmp_path):
     from shardmerge_amd.merge.geometric import ModelStockMerge
     for value, want in ((1, 1.0), (0, 0.0), (1.0, 1.0)):
-        cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "model_stock", "stock_filter_wise": value}))
+        cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "model_stock", "stock_filter_wise": value}, PAIR))
         assert cfg.merge_options == {"stock_filter_wise": want}
         m = ModelStockMerge(config=cfg, index_manager=object())
         assert bool(m.stock_filter_wise) is bool(want)
         assert ("per row" in m.get_readme()) is bool(want)
     for bad in (2, 0.5, -1, "yes", True):
         with pytest.raises(click.BadParameter, match="stock_filter_wise must be 0 or 1"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "model_stock", "stock_filter_wise": bad}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "model_stock", "stock_filter_wise": bad}, PAIR))
     # model_stock takes any number of entries
     three = [{"model": f"org/ft{i}", "base": "org/base"} for i in range(3)]
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "model_stock"}, three)).operator == "model_stock"
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "model_stock"}, three[:1])).operator == "model_stock"
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "model_stock"}, three)).operator == "model_stock"
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "model_stock"}, three[:1])).operator == "model_stock"
 
 
 @pytest.mark.parametrize("operator", [None, "fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear",
@@ -168,7 +146,7 @@ def test_yaml_rejects_stock_filter_wise_with_another_operator(tmp_path, operator
     if operator:
         opts["operator"] = operator
     with pytest.raises(click.BadParameter, match=r"merge_options\.stock_filter_wise is accepted only with operator: model_stock \("):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts, PAIR))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -179,7 +157,7 @@ def test_yaml_rejects_stock_filter_wise_with_another_operator(tmp_path, operator
                                        ("breadcrumbs_normalize", 1), ("bogus", 1)])
 def test_yaml_rejects_an_option_the_operators_would_ignore(tmp_path, operator, key, value):
     with pytest.raises(click.BadParameter, match=key) as e:
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}, PAIR))
     assert f"merge_options.{key}" in str(e.value) or key == "bogus"
 
 
@@ -188,15 +166,15 @@ def test_yaml_rejects_pair_operators_without_a_pair(tmp_path, operator):
     entry = lambda i, a=1.0: {"model": f"org/ft{i}", "base": "org/base", "alpha": a}
     for models in ([entry(1)], [entry(1), entry(2), entry(3)]):
         with pytest.raises(click.BadParameter, match=f"operator {operator} interpolates between exactly two finetune_merge entries, not {len(models)}"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}, models))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, models))
     for a0, a1 in ((-0.5, 1.0), (0.5, -0.1), (0.0, 0.0), (float("nan"), 1.0)):
         with pytest.raises(click.BadParameter, match=f"operator {operator} needs finetune_merge alphas >= 0 with a sum > 0"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}, [entry(1, a0), entry(2, a1)]))
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}, [entry(1, 1.0), entry(2, 0.0)])).operator == operator
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, [entry(1, a0), entry(2, a1)]))
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, [entry(1, 1.0), entry(2, 0.0)])).operator == operator
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts, PAIR)))
     base = stamp({"operator": "model_stock", "stock_filter_wise": 0})
     assert base == stamp({"operator": "model_stock", "stock_filter_wise": 0})
     others = [stamp({"operator": "model_stock", "stock_filter_wise": 1}), stamp({"operator": "nuslerp"}), stamp({"operator": "slerp"}),
@@ -211,14 +189,14 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator, filter
     opts = gc.options(operator, filter_wise)
     expected = gc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = gc.run_cli(gc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(gc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    gc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in gc.README_WORDS[operator] + (("per row",) if filter_wise else ()):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = gc.run_cli(gc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(gc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     if operator == "model_stock":
@@ -235,9 +213,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator, f
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = gc.options(operator, filter_wise)
-    res = gc.run_cli(gc.write_config(tmp_path, "org/lora", "merged", opts))
+    res = run_cli(gc.write_config(tmp_path, "org/lora", "merged", opts))
     assert res.exit_code == 0, res.output
-    gc.assert_outputs(tmp_path / "merged", gc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", gc.expected_outputs(base, full, opts))
     assert gc.README_WORDS[operator][0] in (tmp_path / "merged" / "README.md").read_text()
 
 
@@ -246,16 +224,6 @@ def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul, operator, filter_wise):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = gc.options(operator, filter_wise)
     cfg = gc.write_config(tmp_path, "org/lora", "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    gc.assert_outputs(tmp_path / "merged", gc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", gc.expected_outputs(base, full, opts))

@@ -22,6 +22,7 @@ from shardmerge_amd.index import LocalModelIndex, order_weights
 from shardmerge_amd.merge.fast_fourier import FourierMerge, name_hash
 from shardmerge_amd.writer import ModelWriter, ShardLayer
 from tests.golden import inputs as gi
+from tests.harness import emul  # noqa: F401
 
 REPO = Path(__file__).resolve().parents[1]
 
@@ -189,15 +190,6 @@ def test_product_has_no_cpu_fallback(monkeypatch, tmp_path):
 
 
 # ---- operator + CLI with the emulator as the device --------------------------------------------
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
-
-
 def test_passthrough_and_block_layers(tmp_path, emul, golden):
     cfg_path = gi.write_cli_model(tmp_path)
     cfg = MergeConfig.from_yaml(cfg_path)

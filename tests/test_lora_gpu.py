@@ -7,6 +7,7 @@ import torch
 from click.testing import CliRunner
 
 from tests import lora_fixtures as lf
+from tests.harness import eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,12 +15,6 @@ SHAPES = [(4096, 4096), (14336, 4096), (4096, 14336), (28672, 8192), (1024, 8192
           (1, 4096), (3, 5)]
 RANKS = [1, 7, 16, 64, 256]
 DTYPES = (torch.bfloat16, torch.float16, torch.float32)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 def _inputs(rows, cols, rank, fd, rel, g, dev):

@@ -14,17 +14,9 @@ from shardmerge_amd.adapter import AdapterError, LoraAdapter, pattern_key
 from shardmerge_amd.config import MergeConfig
 from shardmerge_amd.index import LocalModelIndex
 from tests import lora_fixtures as lf
+from tests.harness import emul  # noqa: F401
 
 DTYPES = (torch.bfloat16, torch.float16, torch.float32)
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
 
 
 def _run_cli(cfg_path):

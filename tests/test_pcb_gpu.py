@@ -8,20 +8,15 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import pcb_checks as pc
+from tests.harness import ALPHAS, DTYPES, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 MODEL_SHAPES = [((1024, 4096), 3), ((300, 4544), 3), ((128, 11008), 5), ((1, 4096), 3)]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
-
-
-@pytest.mark.parametrize("bo_dtype", pc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", pc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype):
     pc.check_dtypes(eng, in_dtype, bo_dtype, device=eng.device)
 
@@ -51,8 +46,8 @@ def test_corner(eng, check):
 
 @pytest.mark.parametrize("shape,k", MODEL_SHAPES, ids=["x".join(map(str, s)) + f"-k{k}" for s, k in MODEL_SHAPES])
 def test_model_shape(eng, shape, k):
-    fts, bases, bo = pc.make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
-    rep, _, _, _ = pc.check(eng, fts, bases, pc.ALPHAS[:k], bo, lam=0.7, label=f"{shape} k={k}")
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
+    rep, _, _, _ = pc.check(eng, fts, bases, ALPHAS[:k], bo, lam=0.7, label=f"{shape} k={k}")
     assert 0 < rep.covered < rep.n
     del fts, bases, bo
     torch.cuda.empty_cache()
@@ -60,8 +55,8 @@ def test_model_shape(eng, shape, k):
 
 def test_model_shape_k16_with_own_bases(eng):
     """the 128-register variants over many work-groups: four pcb_hist launches per level, several octets per thread"""
-    fts, bases, bo = pc.make_inputs((2048, 4096), 16, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
-    alphas = [a if i % 3 else -a for i, a in enumerate(pc.ALPHAS)]
+    fts, bases, bo = make_inputs((2048, 4096), 16, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
+    alphas = [a if i % 3 else -a for i, a in enumerate(ALPHAS)]
     rep, _, _, _ = pc.check(eng, fts, bases, alphas, bo, label="2048 x 4096 k=16, own bases, fp32 output")
     assert 0 < rep.covered < rep.n
     del fts, bases, bo
@@ -93,7 +88,7 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, inplace):
     if inplace:
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
-    res = pc.run_cli(pc.write_config(tmp_path, "org/lora", "merged", pc.OPTIONS, device="cuda"))
+    res = run_cli(pc.write_config(tmp_path, "org/lora", "merged", pc.OPTIONS, device="cuda"))
     assert res.exit_code == 0, res.output
-    pc.assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS))
+    assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS))
     assert "PCB" in (tmp_path / "merged" / "README.md").read_text()

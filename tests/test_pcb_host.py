@@ -3,12 +3,6 @@ on the CPU work-group emulator against tests/pcb_oracle.py (bit for bit, tests/p
 the function against a torch fp64 restatement of the paper's form, the YAML options, the stamp, and
 `python -m shard merge` / `analyze` end to end - single process, in place, and two gloo ranks - with the emulator as the
 device."""
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
-
 import click
 import pytest
 import torch
@@ -19,22 +13,12 @@ from shardmerge_amd import distributed
 from shardmerge_amd.config import OPERATORS, MergeConfig
 from tests import lora_fixtures as lf
 from tests import pcb_checks as pc
-
-REPO = Path(__file__).resolve().parents[1]
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
+from tests.harness import DTYPES, assert_outputs, emul, run_cli, run_ranks, ties_models, yaml_config  # noqa: F401
 
 
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
-@pytest.mark.parametrize("bo_dtype", pc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", pc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype):
     pc.check_dtypes(emul, in_dtype, bo_dtype)
 
@@ -85,16 +69,6 @@ def test_paper_form_in_fp64(emul, n, k):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge import operator_class
     from shardmerge_amd.merge.fast_fourier import FourierMerge
@@ -102,18 +76,18 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge.ties import TiesMerge
     cls = operator_class("pcb")
     assert cls is PcbMerge and issubclass(cls, TiesMerge) and "pcb" in OPERATORS
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "pcb"}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "pcb"}))
     assert cfg.operator == "pcb" and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.pcb_ratio, m.pcb_clip, m.pcb_lambda) == (0.1, 0.0001, 1.0)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "pcb", "pcb_ratio": 1, "pcb_clip": 0, "pcb_lambda": 0.7}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "pcb", "pcb_ratio": 1, "pcb_clip": 0, "pcb_lambda": 0.7}))
     assert cfg.merge_options == {"pcb_ratio": 1.0, "pcb_clip": 0.0, "pcb_lambda": 0.7}
     m = cls(config=cfg, index_manager=object())
     readme = m.get_readme()
     for word in ("# PCB Merged Model", "PCB (", "ratio 1", "clip 0", "lambda 0.7", "org/ft1"):
         assert word in readme, (word, readme)
     for edge in ({"pcb_ratio": 1e-9}, {"pcb_ratio": 1.0}, {"pcb_clip": 0}, {"pcb_clip": 0.4999}, {"pcb_lambda": -1e6}, {"pcb_lambda": 1e6}):
-        assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "pcb", **edge})).merge_options == {k: float(v) for k, v in edge.items()}
+        assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "pcb", **edge})).merge_options == {k: float(v) for k, v in edge.items()}
     # the one method both paths call is what differs; the routing is FourierMerge's
     assert cls.merge_block is not TiesMerge.merge_block and cls._merge_layer is FourierMerge._merge_layer
     assert [m.tensor_passes(k) for k in (1, 2, 3)] == [15, 22, 29]
@@ -128,7 +102,7 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
 def test_yaml_rejects_out_of_range_values(tmp_path, options, text):
     (key, _), = options.items()
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} must be a number in {text}"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "pcb", **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "pcb", **options}))
 
 
 @pytest.mark.parametrize("operator", [None] + [op for op in OPERATORS if op != "pcb"])
@@ -139,7 +113,7 @@ def test_yaml_rejects_a_pcb_key_with_another_operator(tmp_path, operator, key):
         opts["operator"] = operator
     shown = operator or "fourier"
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: pcb \(operator '{shown}' would ignore it\)"):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("key,value", [("cutoff_pct", 0.08), ("cull_start_pct", 0.2), ("t_sum", 1.0), ("target_norm_offset", 1e-10),
@@ -153,7 +127,7 @@ def test_yaml_rejects_an_option_pcb_would_ignore(tmp_path, key, value):
     """the message names the rejected key itself and the operator that would ignore it"""
     named = r"unknown keys \['bogus'\]" if key == "bogus" else rf"merge_options\.{key}\b.*operator 'pcb'"
     with pytest.raises(click.BadParameter, match=named):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "pcb", key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "pcb", key: value}))
 
 
 def test_yaml_words_the_rejections_as_the_families_do(tmp_path):
@@ -163,18 +137,18 @@ def test_yaml_words_the_rejections_as_the_families_do(tmp_path):
                        ({"cutoff_pct": 0.1}, r"merge_options\.cutoff_pct is an option of the spectral operators; operator 'pcb' would ignore it"),
                        ({"norm_mode": "exact"}, r"merge_options\.norm_mode is an option of the spectral operators; operator 'pcb' takes no norm")):
         with pytest.raises(click.BadParameter, match=text):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "pcb", **opts}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "pcb", **opts}))
 
 
 def test_a_zero_alpha_sum_is_no_error(tmp_path):
-    doc = yaml.safe_load(_yaml(tmp_path, {"operator": "pcb"}).read_text())
+    doc = yaml.safe_load(yaml_config(tmp_path, {"operator": "pcb"}).read_text())
     doc["finetune_merge"] = [{"model": "org/ft1", "base": "org/base", "alpha": 0.5}, {"model": "org/ft2", "base": "org/base", "alpha": -0.5}]
     (tmp_path / "cfg.yaml").write_text(yaml.safe_dump(doc))
     assert [m.alpha for m in MergeConfig.from_yaml(tmp_path / "cfg.yaml").finetune_merge] == [0.5, -0.5]
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "pcb", "pcb_ratio": 0.1, "pcb_clip": 0.0001, "pcb_lambda": 1.0}
     base = stamp(full)
     assert base == stamp(dict(full))
@@ -189,22 +163,22 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
     opts = pc.OPTIONS
     expected = pc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = pc.run_cli(pc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(pc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    pc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in ("# PCB Merged Model", "PCB (", "ratio 0.3", "clip 0.01", "lambda 0.7"):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = pc.run_cli(pc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(pc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = pc.run_cli(pc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": "pcb"}))
+    res = run_cli(pc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": "pcb"}))
     assert res.exit_code == 0, res.output
-    pc.assert_outputs(tmp_path / "merged_default", pc.expected_outputs(base, full, {"operator": "pcb"}))
+    assert_outputs(tmp_path / "merged_default", pc.expected_outputs(base, full, {"operator": "pcb"}))
     # the ratio shows in the output
-    res = pc.run_cli(pc.write_config(tmp_path, "org/lora_full", "merged_r1", {**opts, "pcb_ratio": 1.0}))
+    res = run_cli(pc.write_config(tmp_path, "org/lora_full", "merged_r1", {**opts, "pcb_ratio": 1.0}))
     assert res.exit_code == 0, res.output
     other = lf.read_outputs(tmp_path / "merged_r1")
     assert any(not torch.equal(other[n], expected[n]) for n in expected if "layers" in n)
@@ -217,15 +191,15 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
 def test_cli_a_window_that_leaves_one_entry(tmp_path, emul):
     """layer 1 is covered by the third entry alone: the function at k = 1"""
     base, factors, full = lf.setup_k3(tmp_path, emul)
-    models = pc.ties_models("org/lora_full")
+    models = ties_models("org/lora_full")
     models[0]["end_layer"] = 0
     cfg = yaml.safe_load(pc.write_config(tmp_path, "org/lora_full", "merged", pc.OPTIONS).read_text())
     cfg["finetune_merge"] = models
     path = tmp_path / "one_entry.yaml"
     path.write_text(yaml.safe_dump(cfg))
-    res = pc.run_cli(path)
+    res = run_cli(path)
     assert res.exit_code == 0, res.output
-    pc.assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS, models=models))
+    assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS, models=models))
 
 
 def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
@@ -233,25 +207,15 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
     monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
-    res = pc.run_cli(pc.write_config(tmp_path, "org/lora", "merged", pc.OPTIONS))
+    res = run_cli(pc.write_config(tmp_path, "org/lora", "merged", pc.OPTIONS))
     assert res.exit_code == 0, res.output
-    pc.assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS))
+    assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS))
     assert "PCB" in (tmp_path / "merged" / "README.md").read_text()
 
 
 def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     cfg = pc.write_config(tmp_path, "org/lora", "merged", pc.OPTIONS, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    pc.assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS))
+    assert_outputs(tmp_path / "merged", pc.expected_outputs(base, full, pc.OPTIONS))

@@ -2,43 +2,30 @@
 (bit for bit, tests/sce_checks.py), the YAML options, the stamp, and `python -m shard merge` end to end - single process,
 in place, and two gloo ranks - with the emulator as the device."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
 from pathlib import Path
 
 import click
 import pytest
 import torch
-import yaml
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import MergeConfig
 from tests import lora_fixtures as lf
 from tests import sce_checks as sc
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, emul, make_inputs, run_cli, run_ranks, yaml_config  # noqa: F401
 
 REPO = Path(__file__).resolve().parents[1]
 
 
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
-
-
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
-@pytest.mark.parametrize("bo_dtype", sc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", sc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype):
     sc.check_dtypes(emul, in_dtype, bo_dtype)
 
 
 @pytest.mark.parametrize("topk", sc.TOPKS)
-@pytest.mark.parametrize("k", sc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_and_select_topk(emul, k, topk):
     sc.check_k_topk(emul, k, topk)
 
@@ -59,8 +46,8 @@ def test_corner(emul, check):
 
 
 def test_largest_emulator_shape(emul):
-    fts, bases, bo = sc.make_inputs((512, 1024), 3, seed=5, own_bases=True)
-    sc.check(emul, fts, bases, sc.ALPHAS[:3], bo, select_topk=0.1, lam=0.7, label="512 x 1024")
+    fts, bases, bo = make_inputs((512, 1024), 3, seed=5, own_bases=True)
+    sc.check(emul, fts, bases, ALPHAS[:3], bo, select_topk=0.1, lam=0.7, label="512 x 1024")
 
 
 @pytest.mark.parametrize("topk", [0.1, 1.0])
@@ -112,14 +99,7 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options, models=None):
-    entries = models or [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"}]
-    doc = {"output_base_model": "org/base", "finetune_merge": entries, "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
+PAIR = [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"}]
 
 
 def test_yaml_accepts_sce_and_its_defaults(tmp_path):
@@ -129,7 +109,7 @@ def test_yaml_accepts_sce_and_its_defaults(tmp_path):
     from shardmerge_amd.merge.ties import TiesMerge
     cls = operator_class("sce")
     assert cls is SceMerge and issubclass(cls, TiesMerge)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce"}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce"}, PAIR))
     assert cfg.operator == "sce" and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert m.select_topk == 1.0 and m.sce_lambda == 1.0                      # mergekit's name and default
@@ -139,7 +119,7 @@ def test_yaml_accepts_sce_and_its_defaults(tmp_path):
     assert cls.merge_block is not TiesMerge.merge_block and cls._merge_layer is FourierMerge._merge_layer
     assert [m.tensor_passes(k) for k in (1, 2, 3)] == [5, 7, 9]                # no selection: 2k + 3
     assert m.block_cost_ms((128, 64), 2) == TiesMerge.block_cost_ms(m, (128, 64), 2)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce", "select_topk": 0.25, "sce_lambda": -2}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce", "select_topk": 0.25, "sce_lambda": -2}, PAIR))
     assert cfg.merge_options == {"select_topk": 0.25, "sce_lambda": -2.0}
     m = cls(config=cfg, index_manager=object())
     assert (m.select_topk, m.sce_lambda) == (0.25, -2.0)
@@ -147,8 +127,8 @@ def test_yaml_accepts_sce_and_its_defaults(tmp_path):
     assert "select_topk 0.25" in m.get_readme() and "sce_lambda -2" in m.get_readme()
     # any number of entries; an alpha of 0 next to a positive one
     three = [{"model": f"org/ft{i}", "base": "org/base", "alpha": a} for i, a in enumerate((0.5, 0.0, 2))]
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce"}, three)).operator == "sce"
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce"}, three[:1])).operator == "sce"
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce"}, three)).operator == "sce"
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce"}, three[:1])).operator == "sce"
 
 
 @pytest.mark.parametrize("key,value", [("cutoff_pct", 0.08), ("cull_start_pct", 0.2), ("t_sum", 1.0), ("target_norm_offset", 1e-10),
@@ -158,7 +138,7 @@ def test_yaml_accepts_sce_and_its_defaults(tmp_path):
                                        ("breadcrumbs_normalize", 1), ("stock_filter_wise", 1), ("bogus", 1)])
 def test_yaml_rejects_an_option_sce_would_ignore(tmp_path, key, value):
     with pytest.raises(click.BadParameter, match=key) as e:
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce", key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce", key: value}, PAIR))
     assert f"merge_options.{key}" in str(e.value) or key == "bogus"
     assert "sce" in str(e.value)
 
@@ -171,26 +151,26 @@ def test_yaml_rejects_the_sce_keys_with_another_operator(tmp_path, operator, key
     if operator:
         opts["operator"] = operator
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: sce \("):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts, PAIR))
 
 
 def test_yaml_rejects_bad_values_and_alphas(tmp_path):
     for bad in (0, 0.0, -0.1, 1.5, "half", True, float("nan")):
         with pytest.raises(click.BadParameter, match=r"merge_options\.select_topk must be a number in \(0, 1\]"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce", "select_topk": bad}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce", "select_topk": bad}, PAIR))
     for bad in (1e7, -1e7, "two", float("inf")):
         with pytest.raises(click.BadParameter, match=r"merge_options\.sce_lambda must be a number in"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce", "sce_lambda": bad}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce", "sce_lambda": bad}, PAIR))
     entry = lambda i, a=1.0: {"model": f"org/ft{i}", "base": "org/base", "alpha": a}
     for alphas in ((-0.5, 1.0), (0.5, -0.1), (0.0, 0.0), (float("nan"), 1.0), (float("inf"), 1.0), (1.0, 1.0, -1e-9)):
         with pytest.raises(click.BadParameter, match="operator sce needs finetune_merge alphas >= 0 with a sum > 0"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "sce"}, [entry(i, a) for i, a in enumerate(alphas)]))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "sce"}, [entry(i, a) for i, a in enumerate(alphas)]))
     # the other delta-merge operators keep taking signed alphas
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "ties"}, [entry(1, -0.5), entry(2, 1.0)])).operator == "ties"
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "ties"}, [entry(1, -0.5), entry(2, 1.0)])).operator == "ties"
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts, PAIR)))
     base = stamp({"operator": "sce", "select_topk": 0.5})
     assert base == stamp({"operator": "sce", "select_topk": 0.5})
     others = [stamp({"operator": "sce", "select_topk": 0.25}), stamp({"operator": "sce"}), stamp({"operator": "sce", "select_topk": 0.5, "sce_lambda": 0.5}),
@@ -210,14 +190,14 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     expected = sc.expected_outputs(base, full)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora_full", "merged"))
+    res = run_cli(sc.write_config(tmp_path, "org/lora_full", "merged"))
     assert res.exit_code == 0, res.output
-    sc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in sc.README_WORDS:
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora", "merged_adapter"))
+    res = run_cli(sc.write_config(tmp_path, "org/lora", "merged_adapter"))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # another select_topk is another model
@@ -230,25 +210,15 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
     monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora", "merged"))
+    res = run_cli(sc.write_config(tmp_path, "org/lora", "merged"))
     assert res.exit_code == 0, res.output
-    sc.assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full))
+    assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full))
     assert sc.README_WORDS[0] in (tmp_path / "merged" / "README.md").read_text()
 
 
 def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     cfg = sc.write_config(tmp_path, "org/lora", "merged", device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    sc.assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full))
+    assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full))

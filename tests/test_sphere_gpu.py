@@ -6,6 +6,7 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import sphere_checks as sc
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,21 +16,15 @@ SHAPE_CASES = [((4096, 4096), 3, "karcher", False), ((4096, 4096), 3, "multisler
                ((4096, 4096), 16, "karcher", True)]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
-
-
 @pytest.mark.parametrize("mode,rowwise", sc.VARIANTS, ids=sc.VARIANT_IDS)
-@pytest.mark.parametrize("bo_dtype", sc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", sc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype, mode, rowwise):
     sc.check_dtypes(eng, in_dtype, bo_dtype, mode, rowwise, device=eng.device)
 
 
 @pytest.mark.parametrize("mode,rowwise", sc.VARIANTS, ids=sc.VARIANT_IDS)
-@pytest.mark.parametrize("k", sc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k(eng, k, mode, rowwise):
     sc.check_k(eng, k, mode, rowwise, device=eng.device)
 
@@ -46,8 +41,8 @@ def test_property_or_corner(eng, check):
 @pytest.mark.parametrize("shape,k,mode,rowwise", SHAPE_CASES,
                          ids=["x".join(map(str, c[0])) + f"-k{c[1]}-{c[2]}{'-rowwise' if c[3] else ''}" for c in SHAPE_CASES])
 def test_model_shape(eng, shape, k, mode, rowwise):
-    fts, bases, bo = sc.make_inputs(shape, k, seed=sum(shape) % 97 + k, device=eng.device)
-    sc.check(eng, fts, bases, sc.ALPHAS[:k], bo, mode, rowwise, label=f"{shape} k={k} {mode}")
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97 + k, device=eng.device)
+    sc.check(eng, fts, bases, ALPHAS[:k], bo, mode, rowwise, label=f"{shape} k={k} {mode}")
     del fts, bases, bo
     torch.cuda.empty_cache()
 
@@ -63,9 +58,9 @@ def test_profile_names_and_launches(eng, mode, rowwise, k):
 def test_cli_on_the_device(tmp_path, eng, operator, row_wise):
     base, factors, full = lf.setup_k3(tmp_path, eng)
     opts = sc.options(operator, row_wise)
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
+    res = run_cli(sc.write_config(tmp_path, "org/lora", "merged", opts, device="cuda"))
     assert res.exit_code == 0, res.output
-    sc.assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full, opts))
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in sc.README_WORDS[operator]:
         assert word in readme, (word, readme)

@@ -2,24 +2,17 @@
 emulator against tests/sphere_oracle.py (bit for bit, tests/sphere_checks.py), the three defined functions, the checks
 that need no oracle, the YAML options, the stamp, and `python -m shard merge` end to end - single process, in place, and
 two gloo ranks - with the emulator as the device."""
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
-
 import click
 import pytest
 import torch
-import yaml
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import OPERATORS as ALL_OPERATORS
 from shardmerge_amd.config import MergeConfig
 from tests import lora_fixtures as lf
 from tests import sphere_checks as sc
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, emul, make_inputs, run_cli, run_ranks, yaml_config  # noqa: F401
 
-REPO = Path(__file__).resolve().parents[1]
 OPERATORS = ("karcher", "multislerp")
 # what the CLI tests run: (operator, sphere_row_wise)
 CLI_CASES = [("karcher", None), ("karcher", 1), ("multislerp", None), ("multislerp", 1)]
@@ -27,25 +20,16 @@ CLI_IDS = ["karcher", "karcher_row_wise", "multislerp", "multislerp_row_wise"]
 NEW_KEYS = [("karcher_max_iter", 5), ("karcher_tol", 1e-6), ("sphere_row_wise", 1)]
 
 
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
-
-
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
 @pytest.mark.parametrize("mode,rowwise", sc.VARIANTS, ids=sc.VARIANT_IDS)
-@pytest.mark.parametrize("bo_dtype", sc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", sc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype, mode, rowwise):
     sc.check_dtypes(emul, in_dtype, bo_dtype, mode, rowwise)
 
 
 @pytest.mark.parametrize("mode,rowwise", sc.VARIANTS, ids=sc.VARIANT_IDS)
-@pytest.mark.parametrize("k", sc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k(emul, k, mode, rowwise):
     sc.check_k(emul, k, mode, rowwise)
 
@@ -77,24 +61,17 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 def test_existing_entry_points_keep_their_limits(emul):
     """the new operators have their own entry point: geo_merge still knows three modes and pairs only"""
-    fts, bases, bo = sc.make_inputs((8, 8), 3, seed=1)
+    fts, bases, bo = make_inputs((8, 8), 3, seed=1)
     for mode in ("karcher", "multislerp"):
         with pytest.raises(ValueError, match="mode"):
-            emul.geo_merge(fts, bases, sc.ALPHAS[:3], bo, mode=mode)
+            emul.geo_merge(fts, bases, ALPHAS[:3], bo, mode=mode)
     with pytest.raises(ValueError, match="at most 2"):
-        emul.geo_merge(fts, bases, sc.ALPHAS[:3], bo, mode="slerp")
+        emul.geo_merge(fts, bases, ALPHAS[:3], bo, mode="slerp")
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options, models=None):
-    entries = models or [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"},
-                         {"model": "org/ft3", "base": "org/base"}]
-    doc = {"output_base_model": "org/base", "finetune_merge": entries, "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
+TRIPLE = [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"},
+          {"model": "org/ft3", "base": "org/base"}]
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -105,7 +82,7 @@ def test_yaml_accepts_the_operators_and_their_defaults(tmp_path, operator):
     from shardmerge_amd.merge.ties import TiesMerge
     cls = operator_class(operator)
     assert cls is {"karcher": KarcherMerge, "multislerp": MultiSlerpMerge}[operator] and issubclass(cls, TiesMerge)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, TRIPLE))
     assert cfg.operator == operator and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert m.mode == operator and not m.sphere_row_wise and int(m.karcher_max_iter) == 10 and m.karcher_tol == 1e-5
@@ -118,13 +95,13 @@ def test_yaml_accepts_the_operators_and_their_defaults(tmp_path, operator):
     # any number of entries >= 1
     for n in (1, 2, 16):
         models = [{"model": f"org/ft{i}", "base": "org/base"} for i in range(n)]
-        assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}, models)).operator == operator
+        assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, models)).operator == operator
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
 def test_yaml_keys(tmp_path, operator):
     from shardmerge_amd.merge import operator_class
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "karcher_max_iter": 25, "karcher_tol": 0, "sphere_row_wise": 1}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "karcher_max_iter": 25, "karcher_tol": 0, "sphere_row_wise": 1}, TRIPLE))
     assert cfg.merge_options == {"karcher_max_iter": 25, "karcher_tol": 0.0, "sphere_row_wise": 1.0}
     assert isinstance(cfg.merge_options["karcher_max_iter"], int)
     m = operator_class(operator)(config=cfg, index_manager=object())
@@ -133,13 +110,13 @@ def test_yaml_keys(tmp_path, operator):
         assert word in m.get_readme()
     for bad in (0, 101, 2.5, "ten", True):
         with pytest.raises(click.BadParameter, match=r"karcher_max_iter must be an integer in 1\.\.100"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "karcher_max_iter": bad}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "karcher_max_iter": bad}, TRIPLE))
     for bad in (-1e-9, 1, 1.5, "small", True):
         with pytest.raises(click.BadParameter, match=r"karcher_tol must be a number in \[0, 1\)"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "karcher_tol": bad}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "karcher_tol": bad}, TRIPLE))
     for bad in (2, 0.5, -1, "yes", True):
         with pytest.raises(click.BadParameter, match="sphere_row_wise must be 0 or 1"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, "sphere_row_wise": bad}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, "sphere_row_wise": bad}, TRIPLE))
 
 
 @pytest.mark.parametrize("key,value", NEW_KEYS)
@@ -150,7 +127,7 @@ def test_yaml_rejects_the_new_keys_with_every_other_operator(tmp_path, operator,
         opts["operator"] = operator
     models = [{"model": "org/ft1", "base": "org/base"}, {"model": "org/ft2", "base": "org/base"}]
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: karcher or multislerp \("):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts, models))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts, models))
 
 
 @pytest.mark.parametrize("operator", OPERATORS)
@@ -164,7 +141,7 @@ def test_yaml_rejects_the_new_keys_with_every_other_operator(tmp_path, operator,
                                        ("bogus", 1)])
 def test_yaml_rejects_an_option_the_operators_would_ignore(tmp_path, operator, key, value):
     with pytest.raises(click.BadParameter, match=key) as e:
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator, key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator, key: value}, TRIPLE))
     assert f"merge_options.{key}" in str(e.value) or key == "bogus"
     assert f"operator {operator!r} would ignore it" in str(e.value) or f"operator {operator!r} takes no norm" in str(e.value) or key == "bogus"
 
@@ -174,12 +151,12 @@ def test_yaml_alpha_rule(tmp_path, operator):
     entry = lambda i, a=1.0: {"model": f"org/ft{i}", "base": "org/base", "alpha": a}
     for alphas in ((-0.5, 1.0), (0.5, -0.1, 1.0), (0.0, 0.0), (0.0,), (float("nan"), 1.0), (float("inf"), 1.0), (True, 1.0)):
         with pytest.raises(click.BadParameter, match=f"operator {operator} needs finetune_merge alphas >= 0 with a sum > 0"):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}, [entry(i, a) for i, a in enumerate(alphas)]))
-    assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": operator}, [entry(1, 1.0), entry(2, 0.0), entry(3, 2)])).operator == operator
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, [entry(i, a) for i, a in enumerate(alphas)]))
+    assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": operator}, [entry(1, 1.0), entry(2, 0.0), entry(3, 2)])).operator == operator
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts, [{"model": "org/ft1", "base": "org/base"},
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts, [{"model": "org/ft1", "base": "org/base"},
                                                                                               {"model": "org/ft2", "base": "org/base"}])))
     base = stamp({"operator": "karcher"})
     assert base == stamp({"operator": "karcher"})
@@ -197,14 +174,14 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul, operator, row_wi
     opts = sc.options(operator, row_wise)
     expected = sc.expected_outputs(base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(sc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    sc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in sc.README_WORDS[operator] + (("per row",) if row_wise else ("per tensor",)):
         assert word in readme, (word, readme)
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(sc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the other granularity and the other operator are other models
@@ -220,9 +197,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch, operator, r
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = sc.options(operator, row_wise, karcher_max_iter=20)
-    res = sc.run_cli(sc.write_config(tmp_path, "org/lora", "merged", opts))
+    res = run_cli(sc.write_config(tmp_path, "org/lora", "merged", opts))
     assert res.exit_code == 0, res.output
-    sc.assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full, opts))
     readme = (tmp_path / "merged" / "README.md").read_text()
     assert sc.README_WORDS[operator][0] in readme and "max_iter 20" in readme
 
@@ -232,16 +209,6 @@ def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul, operator, row_wise):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = sc.options(operator, row_wise)
     cfg = sc.write_config(tmp_path, "org/lora", "merged", opts, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    sc.assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full, opts))
+    assert_outputs(tmp_path / "merged", sc.expected_outputs(base, full, opts))

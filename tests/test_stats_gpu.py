@@ -7,18 +7,13 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import stats_checks as sc
+from tests.harness import DTYPES, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 # (shape, k, own bases, densities); the last: histograms that span many work-groups
 MODEL_SHAPES = [((1024, 4096), 3, False, sc.DENS4), ((300, 4544), 3, False, (0.5, 1.0, 0.5, 0.01)), ((128, 11008), 5, False, sc.DENS4),
                 ((1, 4096), 3, False, sc.DENS4), ((2048, 4096), 16, True, (0.2,)), ((4096, 4096), 3, False, (0.2, 0.05))]
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 @pytest.mark.parametrize("n", sc.SIZES)
@@ -32,7 +27,7 @@ def test_k_and_m(eng, k, m):
     sc.check_k_m(eng, k, m, device=eng.device)
 
 
-@pytest.mark.parametrize("in_dtype", sc.DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype):
     sc.check_dtypes(eng, in_dtype, device=eng.device)
 

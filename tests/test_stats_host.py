@@ -9,15 +9,7 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import stats_checks as sc
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
+from tests.harness import DTYPES, emul, make_inputs, ties_models  # noqa: F401
 
 
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
@@ -32,7 +24,7 @@ def test_k_and_m(emul, k, m):
     sc.check_k_m(emul, k, m)
 
 
-@pytest.mark.parametrize("in_dtype", sc.DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype):
     sc.check_dtypes(emul, in_dtype)
 
@@ -53,7 +45,7 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 def test_report_dataclass_holds_python_values(emul):
-    fts, bases, _ = sc.make_inputs((16, 16), 2, seed=1)
+    fts, bases, _ = make_inputs((16, 16), 2, seed=1)
     rep = emul.delta_stats(fts, bases, [0.5, 0.5], (0.5,))
     assert type(rep.n) is int and type(rep.kept[0][0]) is int and type(rep.thresholds[0][0]) is float
     assert type(rep.gram[0][1]) is float and type(rep.energy[0][0]) is float and type(rep.cover[0][2]) is int
@@ -87,7 +79,7 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
     assert not (tmp_path / "merged_adapter").exists()                          # --report elsewhere: output_dir is not even created
     assert json.loads(other.read_text())["tensors"] == doc["tensors"]
     # other densities; no windows: every entry covers every block tensor
-    models = [{**m, "end_layer": -1} for m in sc.ties_models("org/lora_full")]
+    models = [{**m, "end_layer": -1} for m in ties_models("org/lora_full")]
     res = sc.run_cli(["analyze", sc.write_config(tmp_path, "org/lora_full", "merged_all", models=models), "--densities", "1,0.5"])
     assert res.exit_code == 0, res.output
     expected = sc.expected_records(base, full, (1.0, 0.5), windows=False)
@@ -96,7 +88,7 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
 
 
 def test_a_merge_after_an_analysis_writes_the_same_bytes(tmp_path, emul):
-    from tests.ties_checks import run_cli as run_merge
+    from tests.harness import run_cli as run_merge
     base, factors, full = lf.setup_k3(tmp_path, emul)
     opts = {"operator": "ties", "density": 0.3}
     assert sc.run_cli(["analyze", sc.write_config(tmp_path, "org/lora_full", "merged", opts)]).exit_code == 0

@@ -6,6 +6,7 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import ties_checks as tc
+from tests.harness import ALPHAS, DTYPES, KS, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,20 +16,14 @@ MODEL_SHAPES = [((4096, 4096), 3), ((8192, 8192), 3), ((28672, 8192), 2), ((8192
                 ((4544, 4544), 3), ((128256, 4096), 2), ((1, 4096), 3)]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
-
-
-@pytest.mark.parametrize("bo_dtype", tc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", tc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype):
     tc.check_dtypes(eng, in_dtype, bo_dtype, device=eng.device)
 
 
 @pytest.mark.parametrize("density", tc.DENSITIES)
-@pytest.mark.parametrize("k", tc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_and_density(eng, k, density):
     tc.check_k_density(eng, k, density, device=eng.device)
 
@@ -49,24 +44,24 @@ def test_corner(eng, check):
 
 @pytest.mark.parametrize("shape,k", MODEL_SHAPES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else f"k{v}")
 def test_model_shape(eng, shape, k):
-    fts, bases, bo = tc.make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
-    rep = tc.check(eng, fts, bases, tc.ALPHAS[:k], bo, density=0.2, lam=0.7, label=f"{shape} k={k}")
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
+    rep = tc.check(eng, fts, bases, ALPHAS[:k], bo, density=0.2, lam=0.7, label=f"{shape} k={k}")
     assert all(kept >= rep.k_keep for kept in rep.kept)
     del fts, bases, bo
     torch.cuda.empty_cache()
 
 
 def test_model_shape_with_own_bases(eng):
-    fts, bases, bo = tc.make_inputs((4096, 4096), 3, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
+    fts, bases, bo = make_inputs((4096, 4096), 3, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
     tc.check(eng, fts, bases, [0.5, -0.3, 0.4], bo, density=0.05, normalize=False, label="4096^2, own bases, fp32 output")
 
 
 def test_profile_names(eng):
-    fts, bases, bo = tc.make_inputs((1024, 1024), 2, seed=4, device=eng.device)
+    fts, bases, bo = make_inputs((1024, 1024), 2, seed=4, device=eng.device)
     eng.ctx.profile(True)
     eng.ctx.profile_reset()
     try:
-        eng.ties_merge(fts, bases, tc.ALPHAS[:2], bo)
+        eng.ties_merge(fts, bases, ALPHAS[:2], bo)
         table = eng.ctx.profile_table()
     finally:
         eng.ctx.profile(False)
@@ -78,7 +73,7 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, inplace):
     if inplace:
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora", "merged", device="cuda"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora", "merged", device="cuda"))
     assert res.exit_code == 0, res.output
-    tc.assert_outputs(tmp_path / "merged", tc.expected_outputs(base, full))
+    assert_outputs(tmp_path / "merged", tc.expected_outputs(base, full))
     assert "TIES" in (tmp_path / "merged" / "README.md").read_text()

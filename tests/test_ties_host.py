@@ -2,12 +2,7 @@
 tests/ties_oracle.py (bit for bit, tests/ties_checks.py), the YAML options, the stamp, and `python -m shard merge`
 end to end - single process, in place, and two gloo ranks - with the emulator as the device."""
 import json
-import os
 import re
-import socket
-import subprocess
-import sys
-from pathlib import Path
 
 import click
 import pytest
@@ -20,28 +15,19 @@ from shardmerge_amd.config import MergeConfig
 from tests import lora_fixtures as lf
 from tests import ties_checks as tc
 from tests import ties_oracle
-
-REPO = Path(__file__).resolve().parents[1]
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
+from tests.harness import (ALPHAS, DTYPES, KS, assert_outputs, emul, make_inputs, run_cli, run_ranks, ties_models,  # noqa: F401
+                           yaml_config)
 
 
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
-@pytest.mark.parametrize("bo_dtype", tc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", tc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype):
     tc.check_dtypes(emul, in_dtype, bo_dtype)
 
 
 @pytest.mark.parametrize("density", tc.DENSITIES)
-@pytest.mark.parametrize("k", tc.KS)
+@pytest.mark.parametrize("k", KS)
 def test_k_and_density(emul, k, density):
     tc.check_k_density(emul, k, density)
 
@@ -61,17 +47,17 @@ def test_corner(emul, check):
 
 
 def test_largest_emulator_shape(emul):
-    fts, bases, bo = tc.make_inputs((512, 1024), 3, seed=5, own_bases=True)
-    tc.check(emul, fts, bases, tc.ALPHAS[:3], bo, density=0.2, lam=0.7, label="512 x 1024")
+    fts, bases, bo = make_inputs((512, 1024), 3, seed=5, own_bases=True)
+    tc.check(emul, fts, bases, ALPHAS[:3], bo, density=0.2, lam=0.7, label="512 x 1024")
 
 
 def test_profile_names_and_launches(emul):
     """K = 5: two groups of finetunes per selection level"""
-    fts, bases, bo = tc.make_inputs((40, 50), 5, seed=6)
+    fts, bases, bo = make_inputs((40, 50), 5, seed=6)
     emul.ctx.profile(True)
     emul.ctx.profile_reset()
     try:
-        emul.ties_merge(fts, bases, tc.ALPHAS[:5], bo)
+        emul.ties_merge(fts, bases, ALPHAS[:5], bo)
         table = emul.ctx.profile_table()
     finally:
         emul.ctx.profile(False)
@@ -105,26 +91,16 @@ def test_c_abi_rejects_bad_arguments(emul):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge import operator_class
     from shardmerge_amd.merge.fast_fourier import FourierMerge
     from shardmerge_amd.merge.ties import TiesMerge
     assert operator_class("ties") is TiesMerge
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "ties"}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "ties"}))
     assert cfg.operator == "ties" and cfg.merge_options == {}
     m = TiesMerge(config=cfg, index_manager=object())
     assert (m.density, m.ties_lambda, bool(m.ties_normalize)) == (0.2, 1.0, True)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "ties", "density": 1, "ties_lambda": 0.7, "ties_normalize": 0}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "ties", "density": 1, "ties_lambda": 0.7, "ties_normalize": 0}))
     assert cfg.merge_options == {"density": 1.0, "ties_lambda": 0.7, "ties_normalize": 0.0}
     m = TiesMerge(config=cfg, index_manager=object())
     assert (m.density, m.ties_lambda, bool(m.ties_normalize)) == (1.0, 0.7, False)
@@ -139,7 +115,7 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
                                        ("ties_normalize", 2), ("ties_normalize", 0.5), ("ties_normalize", -1), ("ties_normalize", "yes")])
 def test_yaml_rejects_out_of_range_values(tmp_path, key, value):
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "ties", key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "ties", key: value}))
 
 
 @pytest.mark.parametrize("operator", [None, "fourier", "addition", "task_addition", "fourier_legacy"])
@@ -149,18 +125,18 @@ def test_yaml_rejects_a_ties_key_with_another_operator(tmp_path, operator, key):
     if operator:
         opts["operator"] = operator
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("key,value", [("cutoff_pct", 0.08), ("cull_start_pct", 0.2), ("t_sum", 1.0), ("target_norm_offset", 1e-10),
                                        ("b", 0.1), ("norm_mode", "exact"), ("task_add_models", ["org/ft1"]), ("bogus", 1)])
 def test_yaml_rejects_an_option_ties_would_ignore(tmp_path, key, value):
     with pytest.raises(click.BadParameter, match=key):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "ties", key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "ties", key: value}))
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     base = stamp({"operator": "ties", "density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1})
     assert base == stamp({"operator": "ties", "density": 0.2, "ties_lambda": 1.0, "ties_normalize": 1})
     others = [stamp({"operator": "ties", "density": 0.3, "ties_lambda": 1.0, "ties_normalize": 1}),
@@ -172,7 +148,7 @@ def test_config_stamp(tmp_path):
     import hashlib
     from dataclasses import asdict
     from shardmerge_amd.constants import DEFAULT_NORM_MODE
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"cutoff_pct": 0.05}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"cutoff_pct": 0.05}))
     doc = {"output_base_model": cfg.output_base_model, "output_dtype": cfg.output_dtype,
            "finetune_merge": [asdict(m) for m in cfg.finetune_merge], "merge_options": {"cutoff_pct": 0.05},
            "operator": "fourier", "norm_mode": DEFAULT_NORM_MODE}
@@ -184,19 +160,19 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     expected = tc.expected_outputs(base, full)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "merged"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "merged"))
     assert res.exit_code == 0, res.output
-    tc.assert_outputs(tmp_path / "merged", expected)
+    assert_outputs(tmp_path / "merged", expected)
     readme = (tmp_path / "merged" / "README.md").read_text()
     assert "TIES" in readme and "density 0.3" in readme and "lambda 0.7" in readme
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora", "merged_adapter"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora", "merged_adapter"))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": "ties"}))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": "ties"}))
     assert res.exit_code == 0, res.output
-    tc.assert_outputs(tmp_path / "merged_default", tc.expected_outputs(base, full, {}))
+    assert_outputs(tmp_path / "merged_default", tc.expected_outputs(base, full, {}))
 
 
 def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
@@ -204,39 +180,29 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
     monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora", "merged"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora", "merged"))
     assert res.exit_code == 0, res.output
-    tc.assert_outputs(tmp_path / "merged", tc.expected_outputs(base, full))
+    assert_outputs(tmp_path / "merged", tc.expected_outputs(base, full))
     assert "TIES" in (tmp_path / "merged" / "README.md").read_text()
 
 
 def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     cfg = tc.write_config(tmp_path, "org/lora", "merged", device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    tc.assert_outputs(tmp_path / "merged", tc.expected_outputs(base, full))
+    assert_outputs(tmp_path / "merged", tc.expected_outputs(base, full))
 
 
 def test_uncovered_layer_is_the_same_error(tmp_path, emul, caplog):
     lf.setup_k3(tmp_path, emul)
-    models = tc.ties_models("org/lora_full")
+    models = ties_models("org/lora_full")
     for m in models:
         m["end_layer"] = 0                              # nobody covers layer 1
     cfg = yaml.safe_load(tc.write_config(tmp_path, "org/lora_full", "merged").read_text())
     cfg["finetune_merge"] = models
     p = tmp_path / "uncovered.yaml"
     p.write_text(yaml.safe_dump(cfg))
-    res = tc.run_cli(p)
+    res = run_cli(p)
     assert res.exit_code != 0
     assert any("No finetune covers layer 1" in r.getMessage() for r in caplog.records) or "No finetune covers layer 1" in str(res.exception)

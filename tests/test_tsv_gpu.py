@@ -8,14 +8,9 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import tsv_checks as tc
+from tests.harness import eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 @pytest.mark.parametrize("Rp", tc.APPLY_WIDTHS)

@@ -5,22 +5,13 @@ with the emulator as the device."""
 import click
 import pytest
 import torch
-import yaml
 from click.testing import CliRunner
 
 from shardmerge_amd import distributed
 from shardmerge_amd.config import OPERATORS, MergeConfig
 from tests import lora_fixtures as lf
 from tests import tsv_checks as tc
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
+from tests.harness import emul, run_cli, ties_models, yaml_config  # noqa: F401
 
 
 # ---- 1. tsv_apply through the probe --------------------------------------------------------------------------------
@@ -123,16 +114,6 @@ def test_k1_is_the_truncation(emul, which, rank):
 
 
 # ---- 4. YAML ---------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options, models=None):
-    doc = {"output_base_model": "org/base", "finetune_merge": models or [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge import operator_class
     from shardmerge_amd.merge.fast_fourier import FourierMerge
@@ -140,11 +121,11 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge.tsv import TsvMerge
     cls = operator_class("tsv")
     assert cls is TsvMerge and issubclass(cls, TiesMerge) and "tsv" in OPERATORS
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "tsv"}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "tsv"}))
     assert cfg.operator == "tsv" and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.tsv_rank, m.tsv_power_iters, m.tsv_lambda, m.seed) == (64, 2, 1.0, 0) and isinstance(m.tsv_rank, int)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "tsv", "tsv_rank": 256, "tsv_power_iters": 0, "tsv_lambda": 0.7, "seed": 2 ** 62}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "tsv", "tsv_rank": 256, "tsv_power_iters": 0, "tsv_lambda": 0.7, "seed": 2 ** 62}))
     assert cfg.merge_options == {"tsv_rank": 256, "tsv_power_iters": 0, "tsv_lambda": 0.7, "seed": 2 ** 62}
     m = cls(config=cfg, index_manager=object())
     assert (m.tsv_rank, m.tsv_power_iters, m.seed) == (256, 0, 2 ** 62)
@@ -164,7 +145,7 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
 def test_yaml_rejects_out_of_range_values(tmp_path, options, text):
     (key, _), = options.items()
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} must be {text}"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "tsv", **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "tsv", **options}))
 
 
 @pytest.mark.parametrize("operator", [None] + [op for op in OPERATORS if op != "tsv"])
@@ -175,7 +156,7 @@ def test_yaml_rejects_a_tsv_key_with_another_operator(tmp_path, operator, key):
         opts["operator"] = operator
     shown = operator or "fourier"
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: tsv \(operator '{shown}' would ignore it\)"):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("key,value", [("cutoff_pct", 0.08), ("cull_start_pct", 0.2), ("t_sum", 1.0), ("target_norm_offset", 1e-10),
@@ -190,20 +171,20 @@ def test_yaml_rejects_an_option_tsv_would_ignore(tmp_path, key, value):
     """the message names the rejected key itself and the operator that would ignore it"""
     named = r"unknown keys \['bogus'\]" if key == "bogus" else rf"merge_options\.{key}\b.*operator 'tsv'"
     with pytest.raises(click.BadParameter, match=named):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "tsv", key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "tsv", key: value}))
 
 
 @pytest.mark.parametrize("alphas", [(0.5, -0.5), (0.0, 0.0), (-1.0, 2.0), (float("inf"), 1.0)], ids=str)
 def test_yaml_rejects_a_negative_alpha_or_a_zero_sum(tmp_path, alphas):
     models = [{"model": f"org/ft{i + 1}", "base": "org/base", "alpha": a} for i, a in enumerate(alphas)]
     with pytest.raises(click.BadParameter, match=r"operator tsv needs finetune_merge alphas >= 0 with a sum > 0"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "tsv"}, models))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "tsv"}, models))
     models[0]["alpha"], models[1]["alpha"] = 0.0, 1.0
-    assert [m.alpha for m in MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "tsv"}, models)).finetune_merge] == [0.0, 1.0]
+    assert [m.alpha for m in MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "tsv"}, models)).finetune_merge] == [0.0, 1.0]
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "tsv", "tsv_rank": 64, "tsv_power_iters": 2, "tsv_lambda": 1.0, "seed": 0}
     base = stamp(full)
     assert base == stamp(dict(full))
@@ -216,16 +197,16 @@ def test_config_stamp(tmp_path):
 def test_cli_equals_the_oracle_and_dare_linear(tmp_path, emul):
     got = tc.check_cli(tmp_path, emul)
     # two runs give the same bytes; an adapter entry is the run on its materialised checkpoint
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "again"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "again"))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "again", tmp_path / "merged")
     assert (tmp_path / "again" / "README.md").read_bytes() == (tmp_path / "merged" / "README.md").read_bytes()
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora", "merged_adapter"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora", "merged_adapter"))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the seed and the rank show in the output
     for change in ({"seed": 6}, {"tsv_rank": 8}):
-        res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "changed", {**tc.OPTIONS, **change}))
+        res = run_cli(tc.write_config(tmp_path, "org/lora_full", "changed", {**tc.OPTIONS, **change}))
         assert res.exit_code == 0, res.output
         other = lf.read_outputs(tmp_path / "changed")
         assert any(not torch.equal(other[n], got[n]) for n in got if "proj" in n and "layers" in n), change
@@ -238,12 +219,12 @@ def test_cli_equals_the_oracle_and_dare_linear(tmp_path, emul):
 def test_cli_a_window_that_leaves_one_entry(tmp_path, emul):
     """layer 1 is covered by the third entry alone: every tensor of it is dare_linear's at density 1, bit for bit"""
     lf.setup_k3(tmp_path, emul)
-    models = tc.tsv_models("org/lora_full")
+    models = ties_models("org/lora_full")
     models[0]["end_layer"] = 0
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "merged", models=models))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "merged", models=models))
     assert res.exit_code == 0, res.output
     linear = {"operator": "dare_linear", "density": 1.0, "dare_lambda": tc.OPTIONS["tsv_lambda"]}
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "linear", linear, models=models))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "linear", linear, models=models))
     assert res.exit_code == 0, res.output
     got, other = lf.read_outputs(tmp_path / "merged"), lf.read_outputs(tmp_path / "linear")
     layer1 = [n for n in got if ".layers.1." in n]
@@ -254,11 +235,11 @@ def test_cli_a_window_that_leaves_one_entry(tmp_path, emul):
 def test_cli_in_place_equals_one_process(tmp_path, emul, monkeypatch):
     """the partitioned path merges block tensors itself (distributed._merge_block_tensor): it must run TSV too"""
     lf.setup_k3(tmp_path, emul)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora", "merged"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora", "merged"))
     assert res.exit_code == 0, res.output
     monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora", "inplace"))
+    res = run_cli(tc.write_config(tmp_path, "org/lora", "inplace"))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "inplace", tmp_path / "merged", file_bytes=False)
     assert "TSV" in (tmp_path / "inplace" / "README.md").read_text()
@@ -271,11 +252,11 @@ def test_too_many_singular_vectors_fail_in_initialize(tmp_path, emul, monkeypatc
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
         monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     lf.setup_k3(tmp_path, emul)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "merged", {"operator": "tsv", "tsv_rank": 128}))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "merged", {"operator": "tsv", "tsv_rank": 128}))
     assert res.exit_code != 0
     text = res.output + repr(res.exception)
     assert "model.layers.0.self_attn.q_proj.weight" in text and "3 x 128 = 384" in text, text
     assert not list((tmp_path / "merged").glob("*.safetensors"))
     # 86 vectors per entry still fit (3 x 64 at the 64-row tensors, 3 x 85 = 255 at q_proj)
-    res = tc.run_cli(tc.write_config(tmp_path, "org/lora_full", "merged", {"operator": "tsv", "tsv_rank": 85, "tsv_power_iters": 0}))
+    res = run_cli(tc.write_config(tmp_path, "org/lora_full", "merged", {"operator": "tsv", "tsv_rank": 85, "tsv_power_iters": 0}))
     assert res.exit_code == 0, res.output

@@ -8,17 +8,12 @@ import torch
 
 from tests import lora_fixtures as lf
 from tests import widen_checks as wc
+from tests.harness import ALPHAS, DTYPES, assert_outputs, eng, make_inputs, run_cli  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 MODEL_SHAPES = [((1024, 4096), 3), ((300, 4544), 3), ((1030, 257), 5), ((1, 4096), 3)]
 IDS = ["x".join(map(str, s)) + f"-k{k}" for s, k in MODEL_SHAPES]
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shardmerge_amd.engine import get_engine
-    return get_engine("cuda:0")
 
 
 @pytest.mark.parametrize("R", wc.ROWS)
@@ -37,8 +32,8 @@ def test_k(eng, k, own):
     wc.check_k(eng, k, own, device=eng.device)
 
 
-@pytest.mark.parametrize("bo_dtype", wc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", wc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(eng, in_dtype, bo_dtype):
     wc.check_dtypes(eng, in_dtype, bo_dtype, device=eng.device)
 
@@ -57,8 +52,8 @@ def test_corner(eng, check):
 
 @pytest.mark.parametrize("shape,k", MODEL_SHAPES, ids=IDS)
 def test_model_shape(eng, shape, k):
-    fts, bases, bo = wc.make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
-    rep, _, _, _ = wc.check(eng, fts, bases, wc.ALPHAS[:k], bo, calibration=0.5, lam=0.7, label=f"{shape} k={k}")
+    fts, bases, bo = make_inputs(shape, k, seed=sum(shape) % 97, device=eng.device)
+    rep, _, _, _ = wc.check(eng, fts, bases, ALPHAS[:k], bo, calibration=0.5, lam=0.7, label=f"{shape} k={k}")
     assert all(0 < c < rep.cols for row in rep.calibrated for c in row[:1 if rep.vector_mode else 2])
     del fts, bases, bo
     torch.cuda.empty_cache()
@@ -66,8 +61,8 @@ def test_model_shape(eng, shape, k):
 
 def test_model_shape_k16_with_own_bases(eng):
     """the 128-register variant of widen_combine over many work-groups and four segments"""
-    fts, bases, bo = wc.make_inputs((2048, 4096), 16, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
-    alphas = [a if i % 3 else -a for i, a in enumerate(wc.ALPHAS)]
+    fts, bases, bo = make_inputs((2048, 4096), 16, torch.bfloat16, torch.float32, seed=3, own_bases=True, device=eng.device)
+    alphas = [a if i % 3 else -a for i, a in enumerate(ALPHAS)]
     wc.check(eng, fts, bases, alphas, bo, calibration=0.5, label="2048 x 4096 k=16, own bases, fp32 output")
     del fts, bases, bo
     torch.cuda.empty_cache()
@@ -102,7 +97,7 @@ def test_cli_on_the_device(tmp_path, eng, monkeypatch, inplace):
     if inplace:
         monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     base, factors, full = lf.setup_k3(tmp_path, eng)
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora", "merged", wc.OPTIONS, device="cuda"))
+    res = run_cli(wc.write_config(tmp_path, "org/lora", "merged", wc.OPTIONS, device="cuda"))
     assert res.exit_code == 0, res.output
-    wc.assert_outputs(tmp_path / "merged", wc.expected_outputs(eng, base, full, wc.OPTIONS))
+    assert_outputs(tmp_path / "merged", wc.expected_outputs(eng, base, full, wc.OPTIONS))
     assert "WIDEN" in (tmp_path / "merged" / "README.md").read_text()

@@ -3,12 +3,6 @@ tests/widen_oracle.py (bit for bit, tests/widen_checks.py), the column sums agai
 torch fp64 restatement of the paper's form, the properties, the YAML options, the stamp, the column limit in
 initialize(), and `python -m shard merge` / `analyze` end to end - single process, in place, and two gloo ranks - with
 the emulator as the device."""
-import os
-import socket
-import subprocess
-import sys
-from pathlib import Path
-
 import click
 import pytest
 import torch
@@ -19,18 +13,9 @@ from shardmerge_amd import distributed
 from shardmerge_amd.config import OPERATORS, WIDEN_OPERATORS, MergeConfig
 from tests import lora_fixtures as lf
 from tests import widen_checks as wc
+from tests.harness import DTYPES, assert_outputs, emul, run_cli, run_ranks, ties_models, yaml_config  # noqa: F401
 
-REPO = Path(__file__).resolve().parents[1]
 KEYS = ["widen_ratio", "widen_calibration", "widen_lambda"]
-
-
-@pytest.fixture()
-def emul(monkeypatch):
-    from tests.emul.loader import emul_engine
-    from shardmerge_amd import engine as engine_mod
-    eng = emul_engine()
-    monkeypatch.setattr(engine_mod, "get_engine", lambda device=None: eng)
-    return eng
 
 
 # ---- the kernels on the emulator against the oracle ---------------------------------------------------------
@@ -50,8 +35,8 @@ def test_k(emul, k, own):
     wc.check_k(emul, k, own)
 
 
-@pytest.mark.parametrize("bo_dtype", wc.DTYPES, ids=str)
-@pytest.mark.parametrize("in_dtype", wc.DTYPES, ids=str)
+@pytest.mark.parametrize("bo_dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("in_dtype", DTYPES, ids=str)
 def test_dtypes(emul, in_dtype, bo_dtype):
     wc.check_dtypes(emul, in_dtype, bo_dtype)
 
@@ -89,16 +74,6 @@ def test_paper_form_in_fp64(emul, shape, k):
 
 
 # ---- YAML ------------------------------------------------------------------------------------------------------
-def _yaml(tmp_path, options):
-    doc = {"output_base_model": "org/base", "finetune_merge": [{"model": "org/ft1", "base": "org/base"}],
-           "output_dir": str(tmp_path / "merged")}
-    if options is not None:
-        doc["merge_options"] = options
-    p = tmp_path / "cfg.yaml"
-    p.write_text(yaml.safe_dump(doc))
-    return p
-
-
 def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge import operator_class
     from shardmerge_amd.merge.fast_fourier import FourierMerge
@@ -106,11 +81,11 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
     from shardmerge_amd.merge.widen import WidenMerge
     cls = operator_class("widen")
     assert cls is WidenMerge and issubclass(cls, TiesMerge) and "widen" in OPERATORS and WIDEN_OPERATORS == ("widen",)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "widen"}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "widen"}))
     assert cfg.operator == "widen" and cfg.merge_options == {}
     m = cls(config=cfg, index_manager=object())
     assert (m.widen_ratio, m.widen_calibration, m.widen_lambda) == (1.0, 1.0, 1.0)
-    cfg = MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "widen", "widen_ratio": -1, "widen_calibration": 0, "widen_lambda": 0.7}))
+    cfg = MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "widen", "widen_ratio": -1, "widen_calibration": 0, "widen_lambda": 0.7}))
     assert cfg.merge_options == {"widen_ratio": -1.0, "widen_calibration": 0.0, "widen_lambda": 0.7}
     m = cls(config=cfg, index_manager=object())
     readme = m.get_readme()
@@ -118,7 +93,7 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
         assert word in readme, (word, readme)
     for edge in ({"widen_ratio": -1e6}, {"widen_ratio": 1e6}, {"widen_calibration": 0}, {"widen_calibration": 1e6},
                  {"widen_lambda": -1e6}, {"widen_lambda": 1e6}):
-        assert MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "widen", **edge})).merge_options == {k: float(v) for k, v in edge.items()}
+        assert MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "widen", **edge})).merge_options == {k: float(v) for k, v in edge.items()}
     assert cls.merge_block is not TiesMerge.merge_block and cls._merge_layer is FourierMerge._merge_layer
     assert [m.tensor_passes(k) for k in (1, 2, 3)] == [5, 8, 11]
 
@@ -134,7 +109,7 @@ def test_yaml_accepts_the_operator_and_its_keys(tmp_path):
 def test_yaml_rejects_out_of_range_values(tmp_path, options, text):
     (key, _), = options.items()
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} must be a number in {text}"):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "widen", **options}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "widen", **options}))
 
 
 @pytest.mark.parametrize("operator", [None] + [op for op in OPERATORS if op != "widen"])
@@ -145,7 +120,7 @@ def test_yaml_rejects_a_widen_key_with_another_operator(tmp_path, operator, key)
         opts["operator"] = operator
     shown = operator or "fourier"
     with pytest.raises(click.BadParameter, match=rf"merge_options\.{key} is accepted only with operator: widen \(operator '{shown}' would ignore it\)"):
-        MergeConfig.from_yaml(_yaml(tmp_path, opts))
+        MergeConfig.from_yaml(yaml_config(tmp_path, opts))
 
 
 @pytest.mark.parametrize("key,value", [("cutoff_pct", 0.08), ("cull_start_pct", 0.2), ("t_sum", 1.0), ("target_norm_offset", 1e-10),
@@ -161,7 +136,7 @@ def test_yaml_rejects_an_option_widen_would_ignore(tmp_path, key, value):
     """the message names the rejected key itself and the operator that would ignore it"""
     named = r"unknown keys \['bogus'\]" if key == "bogus" else rf"merge_options\.{key}\b.*operator 'widen'"
     with pytest.raises(click.BadParameter, match=named):
-        MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "widen", key: value}))
+        MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "widen", key: value}))
 
 
 def test_yaml_words_the_rejections_as_the_families_do(tmp_path):
@@ -173,18 +148,18 @@ def test_yaml_words_the_rejections_as_the_families_do(tmp_path):
                        ({"cutoff_pct": 0.1}, r"merge_options\.cutoff_pct is an option of the spectral operators; operator 'widen' would ignore it"),
                        ({"norm_mode": "exact"}, r"merge_options\.norm_mode is an option of the spectral operators; operator 'widen' takes no norm")):
         with pytest.raises(click.BadParameter, match=text):
-            MergeConfig.from_yaml(_yaml(tmp_path, {"operator": "widen", **opts}))
+            MergeConfig.from_yaml(yaml_config(tmp_path, {"operator": "widen", **opts}))
 
 
 def test_a_zero_alpha_sum_is_no_error(tmp_path):
-    doc = yaml.safe_load(_yaml(tmp_path, {"operator": "widen"}).read_text())
+    doc = yaml.safe_load(yaml_config(tmp_path, {"operator": "widen"}).read_text())
     doc["finetune_merge"] = [{"model": "org/ft1", "base": "org/base", "alpha": 0.5}, {"model": "org/ft2", "base": "org/base", "alpha": -0.5}]
     (tmp_path / "cfg.yaml").write_text(yaml.safe_dump(doc))
     assert [m.alpha for m in MergeConfig.from_yaml(tmp_path / "cfg.yaml").finetune_merge] == [0.5, -0.5]
 
 
 def test_config_stamp(tmp_path):
-    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(_yaml(tmp_path, opts)))
+    stamp = lambda opts: distributed.config_stamp(MergeConfig.from_yaml(yaml_config(tmp_path, opts)))
     full = {"operator": "widen", "widen_ratio": 1.0, "widen_calibration": 1.0, "widen_lambda": 1.0}
     base = stamp(full)
     assert base == stamp(dict(full))
@@ -199,24 +174,24 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
     opts = wc.OPTIONS
     expected = wc.expected_outputs(emul, base, full, opts)
     assert any(not torch.equal(expected[n], base[n]) for n in expected if "layers" in n)
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora_full", "merged", opts))
+    res = run_cli(wc.write_config(tmp_path, "org/lora_full", "merged", opts))
     assert res.exit_code == 0, res.output
-    wc.assert_outputs(tmp_path / "merged", expected)           # (passthrough tensors included: torch.equal)
+    assert_outputs(tmp_path / "merged", expected)           # (passthrough tensors included: torch.equal)
     readme = (tmp_path / "merged" / "README.md").read_text()
     for word in ("# WIDEN Merged Model", "WIDEN (", "ratio 0.5", "calibration 0.8", "lambda 0.7"):
         assert word in readme, (word, readme)
     # two runs give the same bytes
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora_full", "merged_again", opts))
+    res = run_cli(wc.write_config(tmp_path, "org/lora_full", "merged_again", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_again", tmp_path / "merged")
     # one finetune given as a LoRA adapter directory: the run on its materialised checkpoint
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
+    res = run_cli(wc.write_config(tmp_path, "org/lora", "merged_adapter", opts))
     assert res.exit_code == 0, res.output
     lf.assert_same_outputs(tmp_path / "merged_adapter", tmp_path / "merged")
     # the default options
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": "widen"}))
+    res = run_cli(wc.write_config(tmp_path, "org/lora_full", "merged_default", {"operator": "widen"}))
     assert res.exit_code == 0, res.output
-    wc.assert_outputs(tmp_path / "merged_default", wc.expected_outputs(emul, base, full, {"operator": "widen"}))
+    assert_outputs(tmp_path / "merged_default", wc.expected_outputs(emul, base, full, {"operator": "widen"}))
     # analyze keeps accepting the config: the operator's options are validated and not used
     from shardmerge_amd.__main__ import cli
     res = CliRunner().invoke(cli, ["analyze", str(wc.write_config(tmp_path, "org/lora_full", "analysed", opts))])
@@ -226,15 +201,15 @@ def test_cli_equals_the_oracle_tensor_by_tensor(tmp_path, emul):
 def test_cli_a_window_that_leaves_one_entry(tmp_path, emul):
     """layer 1 is covered by the third entry alone: the function at k = 1; ft2 has a base of its own (ft1)"""
     base, factors, full = lf.setup_k3(tmp_path, emul)
-    models = wc.ties_models("org/lora_full")
+    models = ties_models("org/lora_full")
     models[0]["end_layer"] = 0
     cfg = yaml.safe_load(wc.write_config(tmp_path, "org/lora_full", "merged", wc.OPTIONS).read_text())
     cfg["finetune_merge"] = models
     path = tmp_path / "one_entry.yaml"
     path.write_text(yaml.safe_dump(cfg))
-    res = wc.run_cli(path)
+    res = run_cli(path)
     assert res.exit_code == 0, res.output
-    wc.assert_outputs(tmp_path / "merged", wc.expected_outputs(emul, base, full, wc.OPTIONS, models=models))
+    assert_outputs(tmp_path / "merged", wc.expected_outputs(emul, base, full, wc.OPTIONS, models=models))
 
 
 def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
@@ -242,9 +217,9 @@ def test_cli_in_place_equals_the_oracle(tmp_path, emul, monkeypatch):
     monkeypatch.setenv("SHARDMERGE_INPLACE", "1")
     monkeypatch.setattr(distributed, "ENGINE_FACTORY", lambda: emul)
     base, factors, full = lf.setup_k3(tmp_path, emul)
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora", "merged", wc.OPTIONS))
+    res = run_cli(wc.write_config(tmp_path, "org/lora", "merged", wc.OPTIONS))
     assert res.exit_code == 0, res.output
-    wc.assert_outputs(tmp_path / "merged", wc.expected_outputs(emul, base, full, wc.OPTIONS))
+    assert_outputs(tmp_path / "merged", wc.expected_outputs(emul, base, full, wc.OPTIONS))
     assert "WIDEN" in (tmp_path / "merged" / "README.md").read_text()
 
 
@@ -260,7 +235,7 @@ def test_too_many_columns_fail_in_initialize(tmp_path, emul, monkeypatch, inplac
     tensors = load_file(str(shard))
     tensors["model.layers.0.mlp.wide.weight"] = torch.zeros((2, 65537), dtype=torch.bfloat16)
     save_file(tensors, str(shard), metadata={"format": "pt"})
-    res = wc.run_cli(wc.write_config(tmp_path, "org/lora_full", "merged", wc.OPTIONS))
+    res = run_cli(wc.write_config(tmp_path, "org/lora_full", "merged", wc.OPTIONS))
     assert res.exit_code != 0
     text = res.output + repr(res.exception)
     assert "model.layers.0.mlp.wide.weight" in text and "65537 columns" in text and "at most 65536" in text, text
@@ -270,16 +245,6 @@ def test_too_many_columns_fail_in_initialize(tmp_path, emul, monkeypatch, inplac
 def test_two_gloo_ranks_equal_the_oracle(tmp_path, emul):
     base, factors, full = lf.setup_k3(tmp_path, emul)
     cfg = wc.write_config(tmp_path, "org/lora", "merged", wc.OPTIONS, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(REPO / "tests" / "dist_worker.py"), str(cfg)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    run_ranks(cfg)
     assert not list((tmp_path / "merged").glob(".tmp-*"))
-    wc.assert_outputs(tmp_path / "merged", wc.expected_outputs(emul, base, full, wc.OPTIONS))
+    assert_outputs(tmp_path / "merged", wc.expected_outputs(emul, base, full, wc.OPTIONS))

@@ -2,46 +2,13 @@
 (tests/test_ties_gpu.py): Engine.ties_merge against tests/ties_oracle.py, BIT FOR BIT - output, merged delta,
 thresholds and kept counts.  The tolerance is zero and it is derived, not measured: every step of the function is one
 correctly rounded fp32 operation or an exact order statistic (include/shardmerge_hip.h, smhip_ties_merge)."""
-import re
-import struct
-
 import pytest
 import torch
-import yaml
-from click.testing import CliRunner
 
-from tests import lora_fixtures as lf
-from tests import ties_oracle
+from tests import harness, ties_oracle
+from tests.harness import ALPHAS, DTYPES, SMALL, expected_by_tensor, f32_bits, make_inputs, raw, ties_models
 
-DTYPES = (torch.bfloat16, torch.float16, torch.float32)
-KS = (1, 2, 3, 5, 16)
 DENSITIES = (1.0, 0.5, 0.2, 0.01, 1e-9)          # the last one: k_keep == 0, the output is base_out
-ALPHAS = (0.5, 0.3, 0.4, 0.25, 0.6, 0.1, 0.35, 0.45, 0.2, 0.15, 0.55, 0.05, 0.7, 0.3, 0.5, 0.4)
-SMALL = (97, 131)                                # 12707 elements: not a multiple of 8
-
-
-def raw(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32 if t.element_size() == 4 else torch.int16)
-
-
-def f32_bits(x: float) -> bytes:
-    return struct.pack("<f", x)
-
-
-def make_inputs(shape, k, in_dtype=torch.bfloat16, bo_dtype=None, seed=0, own_bases=False, sigma=3e-3, device="cpu"):
-    """(finetunes, bases, base_out): a base N(0, 0.02^2), finetunes base + N(0, sigma^2), all rounded to their dtype;
-    own_bases: every finetune has a base of its own and base_out is yet another tensor"""
-    g = torch.Generator(device=device).manual_seed(1000 + seed)
-    rn = lambda s: torch.randn(shape, generator=g, device=device, dtype=torch.float32) * s
-    bo_dtype = bo_dtype or in_dtype
-    shared = rn(0.02)
-    bases = [(rn(0.02) if own_bases else shared).to(in_dtype) for _ in range(k)]
-    if not own_bases:
-        bases = [bases[0]] * k
-    fts = [(bases[i].float() + rn(sigma)).to(in_dtype) for i in range(k)]
-    base_out = rn(0.02).to(bo_dtype) if own_bases or bo_dtype != in_dtype else bases[0]
-    return fts, bases, base_out
 
 
 def check(engine, fts, bases, alphas, base_out, density=0.2, lam=1.0, normalize=True, label=""):
@@ -207,49 +174,15 @@ def check_arguments(engine, device="cpu"):
 OPTIONS = {"operator": "ties", "density": 0.3, "ties_lambda": 0.7}
 
 
-def ties_models(third):
-    """layer 0: all three finetunes, layer 1: ft1 and `third`; ft2 is a finetune of ft1 (its own base)"""
-    return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-            {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-            {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
-
-
 def write_config(root, third, out_dir, options=OPTIONS, device=None):
-    cfg = {"output_base_model": "org/base", "finetune_merge": ties_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(options)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
+    return harness.write_config(root, ties_models(third), out_dir, options, device)
 
 
 def expected_outputs(base, full, options=OPTIONS):
     """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough)"""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        entries = [(ft1[name], base[name], 0.5)] + ([(ft2[name], ft1[name], 0.3)] if int(m.group(1)) == 0 else []) + \
-                  [(full[name], base[name], 0.4)]
-        out[name] = ties_oracle.ties_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                           options.get("density", 0.2), options.get("ties_lambda", 1.0),
-                                           bool(options.get("ties_normalize", 1)))[0]
-    return out
+    def merge(fts, bases, alphas, base_out, name):
+        return ties_oracle.ties_merge(
+            fts, bases, alphas, base_out, options.get("density", 0.2), options.get("ties_lambda", 1.0),
+            bool(options.get("ties_normalize", 1)))[0]
 
-
-def assert_outputs(out_dir, expected):
-    got = lf.read_outputs(out_dir)
-    assert sorted(got) == sorted(expected)
-    for name in expected:
-        assert got[name].dtype == expected[name].dtype and got[name].shape == expected[name].shape, name
-        assert torch.equal(raw(got[name]), raw(expected[name])), name
-
-
-def run_cli(cfg_path):
-    from shardmerge_amd.__main__ import cli
-    return CliRunner().invoke(cli, ["merge", str(cfg_path)])
+    return expected_by_tensor(base, full, ties_models("org/lora_full"), merge)

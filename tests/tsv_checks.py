@@ -13,9 +13,11 @@ import torch
 from shardmerge_amd import _lib
 from shardmerge_amd.merge.dare import tensor_key
 from tests import extract_checks as xc
+from tests import harness
 from tests import lora_fixtures as lf
 from tests import tsv_oracle as to
 from tests.extract_checks import bits32, bits64, host, on, pair
+from tests.harness import run_cli, ties_models
 
 APPLY_SHAPES = ((1, 1), (3, 5), (17, 33), (130, 257), (257, 130))
 APPLY_WIDTHS = (16, 32, 80, 256)
@@ -350,29 +352,8 @@ def check_profile(engine, k, q, shape=(320, 192), r=8):
 OPTIONS = {"operator": "tsv", "tsv_rank": 16, "tsv_power_iters": 1, "tsv_lambda": 0.7, "seed": 5}
 
 
-def tsv_models(third):
-    """layer 0: all three finetunes, layer 1: ft1 and `third`; ft2 is a finetune of ft1 (its own base)"""
-    return [{"model": "org/ft1", "base": "org/base", "alpha": 0.5, "is_input": True},
-            {"model": "org/ft2", "base": "org/ft1", "alpha": 0.3, "end_layer": 0},
-            {"model": third, "base": "org/base", "alpha": 0.4, "is_output": True}]
-
-
 def write_config(root, third, out_dir, options=OPTIONS, device=None, models=None):
-    import yaml
-    cfg = {"output_base_model": "org/base", "finetune_merge": models or tsv_models(third), "output_dir": str(root / out_dir),
-           "output_dtype": "bfloat16", "cache_dir": str(root / "cache"), "storage_dir": str(root / "storage"),
-           "merge_options": dict(options)}
-    if device:
-        cfg["device"] = device
-    p = root / f"{out_dir}.yaml"
-    p.write_text(yaml.safe_dump(cfg))
-    return p
-
-
-def run_cli(cfg_path, command="merge"):
-    from click.testing import CliRunner
-    from shardmerge_amd.__main__ import cli
-    return CliRunner().invoke(cli, [command, str(cfg_path)])
+    return harness.write_config(root, models or ties_models(third), out_dir, options, device)
 
 
 def expected_matrices(base, full, opts):

@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests import lora_fixtures as lf
+from tests import harness
 from tests import widen_oracle as wo
-from tests.ties_checks import ALPHAS, DTYPES, assert_outputs, make_inputs, raw, run_cli, ties_models, write_config  # noqa: F401
+from tests.harness import ALPHAS, DTYPES, expected_by_tensor, make_inputs, profile_of, raw, ties_models
 
 KS = (1, 2, 4, 5, 16)                           # 4 | 5 straddles the two register variants of widen_combine
 ROWS = (1, 2, 7, 8, 9, 511, 512, 513, 1025)     # around the sub-lanes (8) and the segments (512)
@@ -363,17 +363,6 @@ PROFILES = [((40, 50), 2, {"widen_colstats": 1, "widen_colfold": 1, "widen_rank"
 PROFILE_IDS = ["matrix_k2", "matrix_k5", "vector_k3"]
 
 
-def profile_of(engine, call):
-    engine.ctx.profile(True)
-    engine.ctx.profile_reset()
-    try:
-        call()
-        table = engine.ctx.profile_table()
-    finally:
-        engine.ctx.profile(False)
-    return {n: table[n][0] for n in table}
-
-
 def check_profile(engine, shape, k, expected, device="cpu"):
     """five kernels in matrix mode, four in vector mode, one launch each whatever k"""
     fts, bases, bo = make_inputs(shape, k, seed=6, device=device)
@@ -559,22 +548,16 @@ def check_c_abi(engine, device="cpu"):
 OPTIONS = {"operator": "widen", "widen_ratio": 0.5, "widen_calibration": 0.8, "widen_lambda": 0.7}
 
 
+def write_config(root, third, out_dir, opts, device=None):
+    return harness.write_config(root, ties_models(third), out_dir, opts, device)
+
+
 def expected_outputs(engine, base, full, opts, models=None):
-    """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough); the models of
-    ties_checks.ties_models: layer 0 has three entries, layer 1 two.  models: the finetune_merge entries, if others."""
-    ft1, ft2 = lf.model_tensors(1), lf.model_tensors(2)
-    out = {}
-    for name, _ in lf.TENSORS:
-        m = re.match(r"model\.layers\.(\d+)\.", name)
-        if m is None:
-            out[name] = ft1[name] if name == "model.embed_tokens.weight" else full[name]
-            continue
-        layer = int(m.group(1))
-        entries = [(ft1[name], base[name], 0.5, 0, -1), (ft2[name], ft1[name], 0.3, 0, 0), (full[name], base[name], 0.4, 0, -1)]
-        if models is not None:
-            entries = [(e[0], e[1], e[2], mm.get("start_layer", 0), mm.get("end_layer", -1)) for e, mm in zip(entries, models)]
-        entries = [e for e in entries if e[3] <= layer and (e[4] == -1 or layer <= e[4])]
-        out[name] = wo.widen_merge([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries], base[name],
-                                   ratio=opts.get("widen_ratio", 1.0), calibration=opts.get("widen_calibration", 1.0),
-                                   lam=opts.get("widen_lambda", 1.0), exp=wo.exp_of(engine))["out"]
-    return out
+    """the oracle tensor by tensor (block tensors) / the provider's tensor (passthrough); the models of ties_models:
+    layer 0 has three entries, layer 1 two.  models: the finetune_merge entries, if others."""
+    def merge(fts, bases, alphas, base_out, name):
+        return wo.widen_merge(
+            fts, bases, alphas, base_out, ratio=opts.get("widen_ratio", 1.0), calibration=opts.get("widen_calibration", 1.0),
+            lam=opts.get("widen_lambda", 1.0), exp=wo.exp_of(engine))["out"]
+
+    return expected_by_tensor(base, full, models or ties_models("org/lora_full"), merge)
