@@ -1142,6 +1142,72 @@ typedef struct {
 int smhip_widen_merge(smhip_ctx* ctx, const smhip_widen_desc* desc, void* out, float* delta_out, double* stat_out,
                       uint32_t* rank_out, float* weight_out, smhip_widen_report* report, void* stream);
 
+/* ---- CABS merge (Yang et al., "CABS: Conflict-Aware and Balanced Sparsification for Enhancing Model Merging", ICML 2025,
+ *      as recalled: PAPERS.md): n:m sparsification of every task vector - each group of M consecutive weights of a row
+ *      keeps its N largest magnitudes, so the budget is spent evenly over the tensor (BS) - applied to the finetunes one
+ *      after another, each allowed only the positions that no earlier one kept (CA), so the kept sets are disjoint; the
+ *      sparse task vectors are then added with their weights.  The reference has no such operator; this section IS its
+ *      definition.  The tensor of n elements is seen as R = rows rows of C = n / rows elements (the caller passes the
+ *      length of the last dimension; a 0-D or 1-D tensor is one row: DELLA's view), finetunes i = 0..k-1 IN THE ORDER
+ *      GIVEN (1 <= k <= 16); n_keep = N, group = M, conflict_aware are integers:
+ *        1. d_i = fp32(finetune_i) - fp32(base_i).  A NaN or Inf in any d_i fails the call with SMHIP_ERR_NONFINITE
+ *           (the message lists the finetunes), detected as smhip_dare_merge detects it; out is then unspecified.
+ *        2. Groups.  Row r is cut into G = ceil(C / M) groups; group g covers the columns [g M, min(C, (g + 1) M)) and has
+ *           m' of them.  Its quota is q = ceil(N m' / M) in integers, (N * m' + M - 1) / M: N for a full group, at least
+ *           1 for a tail.
+ *        3. Selection, for i = 0, 1, ..., k - 1 in this order.  The CANDIDATES of finetune i in a group are its elements
+ *           with d_i != 0 and, when conflict_aware == 1, kept by no j < i.  With c candidates: c <= q keeps them all (the
+ *           group is SHORT for i if c < q); otherwise tau is the q-th largest |d_i| among the candidates, exact on the
+ *           31 magnitude bits as unsigned integers, and a candidate is KEPT iff |d_i| >= tau.  TIE RULE: a candidate that
+ *           ties with tau is kept (the rule of smhip_ties_merge), so the result depends on no traversal order and a
+ *           group may keep more than q; the excess is its SURPLUS.
+ *        4. tv_i = fl32(d_i * fp32(alpha_i)) where kept, +0 elsewhere; M = ((0 + tv_0) + tv_1) + ... in fp32, in order.
+ *           There is NO normalisation: under CA at most one term of an element is non-zero, and a division by the sum
+ *           of the weights would shrink it.  The alphas may have any sign and any sum.
+ *        5. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * M)), delta_out = fl32(lambda * M):
+ *           step 7 of smhip_ties_merge.
+ *        6. mask_out (optional): device uint16 [n], bit i set iff finetune i kept the element.
+ *        7. The report, all integers: groups = R G; kept[i]; short_groups[i]; surplus[i], the elements kept beyond the
+ *           quota summed over the groups; covered, the elements kept by at least one finetune; overlap, those kept by at
+ *           least two (0 whenever conflict_aware == 1).
+ *      Every step is an integer function, an exact order statistic or one correctly rounded fp32 operation: the result is
+ *      defined bit for bit.  conflict_aware == 0 with N == M keeps every non-zero entry: smhip_dare_merge (sign_election 0,
+ *      normalize 0) at density 1.  SMHIP_ERR_ARG: group not a power of two in 4..512, n_keep outside 1..group,
+ *      conflict_aware not 0 or 1, k outside 1..16, rows that do not divide n, lambda or an alpha not finite, a mask_out
+ *      that is misaligned or overlaps another tensor.  Aliasing, alignment, n == 0 (a no-op, the report all zeros),
+ *      dtypes and the size limit: the rules of smhip_ties_merge.
+ *      ONE kernel, one pass over the inputs (k + 2 tensor passes with a shared base): a lane holds the k deltas of 8
+ *      columns of a row in registers, the max(M, 8) / 8 lanes of a group select together - in the lane for M <= 8, else by a
+ *      digit descent over the 31 key bits through a 16-bin histogram in LDS, one barrier per digit, 8 per finetune.  No
+ *      histogram launch, no second read.  C % 8 == 0 with 16-byte aligned pointers takes 16-byte accesses, anything else
+ *      goes element by element and is as exact.  Counters are integers (LDS, then one global atomic per counter and
+ *      work-group), no floating-point atomics; the call synchronises the stream once, at its end.  Profile name:
+ *      "cabs_merge" (k <= 4) or "cabs_merge_any". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    size_t rows;                            /* R; C = n / rows */
+    int n_keep, group;                      /* N : M */
+    int conflict_aware;                     /* 1: a finetune may keep only what no earlier one kept */
+    double lambda;
+} smhip_cabs_desc;
+typedef struct {
+    uint64_t groups;                        /* R * ceil(C / M) */
+    uint64_t kept[SMHIP_MAX_MODELS];
+    uint64_t short_groups[SMHIP_MAX_MODELS];/* groups with fewer candidates than their quota */
+    uint64_t surplus[SMHIP_MAX_MODELS];     /* elements kept beyond the quota (ties with tau) */
+    uint64_t covered, overlap;              /* elements kept by >= 1 and by >= 2 finetunes */
+} smhip_cabs_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], lambda * M.  mask_out (optional): device
+ * uint16 [n].  report (optional): HOST. */
+int smhip_cabs_merge(smhip_ctx* ctx, const smhip_cabs_desc* desc, void* out, float* delta_out, uint16_t* mask_out,
+                     smhip_cabs_report* report, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device

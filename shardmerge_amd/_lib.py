@@ -279,6 +279,21 @@ class WidenReport(C.Structure):
 WIDEN_MAX_COLS = 65536          # C of smhip_widen_merge at most
 
 
+class CabsDesc(C.Structure):
+    """smhip_cabs_desc: the leading fields of the delta merges, then rows, n_keep, group, conflict_aware and lambda"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_size_t), ("n_keep", C.c_int), ("group", C.c_int),
+                                         ("conflict_aware", C.c_int), ("lam", C.c_double)]
+
+
+class CabsReport(C.Structure):
+    """smhip_cabs_report"""
+    _fields_ = [("groups", C.c_uint64), ("kept", C.c_uint64 * MAX_MODELS), ("short_groups", C.c_uint64 * MAX_MODELS),
+                ("surplus", C.c_uint64 * MAX_MODELS), ("covered", C.c_uint64), ("overlap", C.c_uint64)]
+
+
+CABS_GROUPS = (4, 8, 16, 32, 64, 128, 256, 512)     # group of smhip_cabs_merge: a power of two in 4..512
+
+
 class TsvDesc(C.Structure):
     """smhip_tsv_desc: the leading fields of the delta merges, then the shape, rank, q, lambda, key and the workspace"""
     _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("rank", C.c_int), ("power_iters", C.c_int),
@@ -380,6 +395,7 @@ class SmhipLibrary:
         d.smhip_tsv_merge.argtypes = [P, C.POINTER(TsvDesc), P, P, C.POINTER(TsvReport), P]
         d.smhip_tsv_probe.argtypes = [P, P, P, I, I, I, P, I, D, P, P, P]
         d.smhip_widen_merge.argtypes = [P, C.POINTER(WidenDesc), P, P, P, P, P, C.POINTER(WidenReport), P]
+        d.smhip_cabs_merge.argtypes = [P, C.POINTER(CabsDesc), P, P, P, C.POINTER(CabsReport), P]
         d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

@@ -147,6 +147,18 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # widen_ratio: 1.0        #   -1e6 <= widen_ratio <= 1e6: the cut, in units of the mean rank (below 0: every column)
       # widen_calibration: 1.0  #   0 <= widen_calibration <= 1e6: the score of a column above the cut
       # widen_lambda: 1.0       #   scales the merged delta
+                                # | cabs (CABS, Yang et al. 2025; no counterpart in the reference): n:m sparsification of the
+                                #   deltas - every group of cabs_m consecutive weights of a ROW (the last dimension) keeps
+                                #   the cabs_n largest magnitudes of a finetune's delta (ties at the cut all kept), so the
+                                #   budget is spent evenly over the tensor - applied to the covering finetunes ONE AFTER
+                                #   ANOTHER IN THE ORDER OF finetune_merge, each allowed only the positions that no earlier
+                                #   one kept (cabs_conflict_aware: 1), so the kept sets are disjoint; the sparse deltas are
+                                #   added with their alphas, without normalisation.  alphas of any sign.  The spectral keys,
+                                #   norm_mode, task_add_models and every other family's keys are rejected; keys:
+      # cabs_n: 64              #   an integer in 1..cabs_m: magnitudes kept per group and finetune
+      # cabs_m: 256             #   a power of two in 4..512: the group (64:256 keeps a quarter)
+      # cabs_conflict_aware: 1  #   1: later finetunes take only what is left; 0: every finetune is pruned on its own
+      # cabs_lambda: 1.0        #   scales the merged delta
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -174,7 +186,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -200,6 +212,9 @@ PCB_OPTION_DEFAULTS = {"pcb_ratio": 0.1, "pcb_clip": 0.0001, "pcb_lambda": 1.0}
 TSV_OPTION_DEFAULTS = {"tsv_rank": 64, "tsv_power_iters": 2, "tsv_lambda": 1.0, "seed": 0}
 WIDEN_OPERATORS = ("widen",)
 WIDEN_OPTION_DEFAULTS = {"widen_ratio": 1.0, "widen_calibration": 1.0, "widen_lambda": 1.0}
+CABS_OPERATORS = ("cabs",)
+CABS_OPTION_DEFAULTS = {"cabs_n": 64, "cabs_m": 256, "cabs_conflict_aware": 1.0, "cabs_lambda": 1.0}
+CABS_GROUPS = (4, 8, 16, 32, 64, 128, 256, 512)     # cabs_m: a group is selected inside one work-group
 WIDEN_MAX_COLS = 65536                              # columns of a block tensor at most: the ranks are counted over all pairs
 TSV_MAX_VECTORS = 256                               # k * min(tsv_rank, rows, cols) at most: the width of the whitened panels
 
@@ -237,6 +252,15 @@ def _della_window(opts: Dict[str, Any]) -> None:
     if not (int((density - epsilon) * 65536.0) >= 1):
         raise click.BadParameter(f"floor((merge_options.density - merge_options.epsilon) * 65536) must be at least 1 (density {density:g}, "
                                  f"epsilon {epsilon:g}): the mask draws 16 bits per element")
+
+
+def _cabs_n_of_m(opts: Dict[str, Any]) -> None:
+    """the argument rules of smhip_cabs_merge (include/shardmerge_hip.h): the group a power of two, 1 <= n <= m"""
+    n, m = opts.get("cabs_n", CABS_OPTION_DEFAULTS["cabs_n"]), opts.get("cabs_m", CABS_OPTION_DEFAULTS["cabs_m"])
+    if m not in CABS_GROUPS:
+        raise click.BadParameter(f"merge_options.cabs_m must be a power of two in 4..512, not {m}")
+    if not (1 <= n <= m):
+        raise click.BadParameter(f"merge_options.cabs_n must be an integer in 1..cabs_m = {m}, not {n}")
 
 
 @dataclass(frozen=True)
@@ -335,6 +359,17 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "della": "(it drops nothing at random; its ranks are per column, not per entry)",
                            "consensus_ta": "(it masks nothing)",
                            "arcee_fusion": "(it merges several models by their columns' ranks)"}),
+    _OptionFamily(CABS_OPERATORS, CABS_OPTION_DEFAULTS,
+                  {"cabs_n": ("int", 1, 512), "cabs_m": ("int", 4, 512), "cabs_conflict_aware": "flag", "cabs_lambda": _LAMBDA},
+                  earlier={"ties": "(its trim is n:m within groups of a row: cabs_n, cabs_m, cabs_lambda)",
+                           "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it trims n:m within groups of a row and never the largest)",
+                           "model_stock": "(it weights by alpha and sparsifies n:m)",
+                           "sce": "(it selects by magnitude within groups, per finetune)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it masks by order: earlier finetunes keep their positions)",
+                           "arcee_fusion": "(it merges several models by n:m sparsification)"},
+                  check=_cabs_n_of_m),
 )
 
 

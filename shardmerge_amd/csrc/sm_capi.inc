@@ -580,6 +580,33 @@ int smhip_widen_merge(smhip_ctx* ctx, const smhip_widen_desc* d, void* out, floa
     SM_FINISH(ctx, ctx->pipe.delta.widen_merge(*d, out, delta_out, stat_out, rank_out, weight_out, report));
 }
 
+int smhip_cabs_merge(smhip_ctx* ctx, const smhip_cabs_desc* d, void* out, float* delta_out, uint16_t* mask_out,
+                     smhip_cabs_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "cabs_merge", d, out, delta_out, true, [&]() -> const char* {
+            const int M = d->group;
+            if (M < smhip::CABS_MIN_GROUP || M > smhip::CABS_MAX_GROUP || (M & (M - 1))) return "group must be a power of two in 4..512";
+            if (d->n_keep < 1 || d->n_keep > M) return "n_keep must be in 1..group";
+            if (d->conflict_aware != 0 && d->conflict_aware != 1) return "conflict_aware must be 0 or 1";
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            return nullptr;
+        }))
+        return rc;
+    if (d->n > 0) {
+        if (d->rows < 1 || d->n % d->rows) return ctx->pipe.fail(SMHIP_ERR_ARG, "cabs_merge: rows must divide n");
+        if (mask_out) {
+            const uintptr_t t0 = (uintptr_t)mask_out, t1 = t0 + d->n * 2;
+            const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2;
+            auto hits = [&](const void* p, size_t bytes) { return p && (uintptr_t)p < t1 && t0 < (uintptr_t)p + bytes; };
+            bool hit = t0 % 2 != 0 || hits(out, d->n * oes) || hits(delta_out, d->n * 4) || hits(d->base_out, d->n * oes);
+            for (int i = 0; i < d->k; ++i) hit = hit || hits(d->finetune[i], d->n * ies) || hits(d->base[i], d->n * ies);
+            if (hit) return ctx->pipe.fail(SMHIP_ERR_ARG, "cabs_merge: mask_out is misaligned or overlaps another tensor");
+        }
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.cabs_merge(*d, out, delta_out, mask_out, report));
+}
+
 int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
                     int base_out_dtype, double lambda, void* out, float* delta_out, void* stream) {
     SM_GUARD(ctx);

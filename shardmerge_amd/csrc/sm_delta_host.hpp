@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, the task-vector statistics and the low-rank extraction (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, the task-vector statistics and the low-rank extraction (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -27,6 +27,7 @@
 #include "sm_pcb.hpp"
 #include "sm_tsv.hpp"
 #include "sm_widen.hpp"
+#include "sm_cabs.hpp"
 
 namespace smhip {
 
@@ -124,6 +125,10 @@ SM_KERNEL_TAG_LB(KWidenRank, WidenRankParams, "widen_rank", k_widen_rank(ex, p),
 SM_KERNEL_TAG_LB(KWidenCoef, WidenCoefParams, "widen_coef", k_widen_coef(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KWidenCombine, WidenCombineParams, "widen_combine", k_widen_combine<WIDEN_REG_SMALL>(ex, p), WIDEN_THREADS, 4)
 SM_KERNEL_TAG_LB(KWidenCombineAny, WidenCombineParams, "widen_combine", k_widen_combine<TIES_MAX_MODELS>(ex, p), WIDEN_THREADS, 2)
+// CABS merge (sm_cabs.hpp): the one fused pass with the k deltas of a row octet in registers across the sequential n:m
+// selections of the finetunes; k <= 4 at dare_merge's residency, or up to 16
+SM_KERNEL_TAG_LB(KCabsMerge, CabsMergeParams, "cabs_merge", k_cabs_merge<CABS_REG_SMALL>(ex, p), CABS_THREADS, 4)
+SM_KERNEL_TAG_LB(KCabsMergeAny, CabsMergeParams, "cabs_merge_any", k_cabs_merge<TIES_MAX_MODELS>(ex, p), CABS_THREADS, 2)
 // the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
@@ -135,6 +140,7 @@ SM_KERNEL_TAG_LB(KWidenCombineAny, WidenCombineParams, "widen_combine", k_widen_
 #define SM_SIDE_KERNELS_11(X) X(KPcbHist) X(KPcbHistAny) X(KPcbMerge) X(KPcbMergeAny) X(KPcbFn)
 #define SM_SIDE_KERNELS_12(X) X(KTsvApply)
 #define SM_SIDE_KERNELS_13(X) X(KWidenColstats) X(KWidenColfold) X(KWidenRank) X(KWidenCoef) X(KWidenCombine) X(KWidenCombineAny)
+#define SM_SIDE_KERNELS_14(X) X(KCabsMerge) X(KCabsMergeAny)
 
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
@@ -1080,6 +1086,55 @@ class DeltaHost {
                     rep->mu[i][s] = host.mu[i * WIDEN_STATS + s];
                     rep->calibrated[i][s] = host.calibrated[i * WIDEN_STATS + s];
                 }
+        return SMHIP_OK;
+    }
+
+    // ---- CABS merge (sm_cabs.hpp; smhip_cabs_merge): no select launch, one kernel; the workspace is CabsReadback ----
+    struct CabsReadback { unsigned long long kept[TIES_MAX_MODELS], counts[CABS_COUNTS]; uint32_t flags[2]; };
+    int cabs_merge(const smhip_cabs_desc& d, void* out, float* delta_out, uint16_t* mask_out, smhip_cabs_report* rep) {
+        const int k = d.k, M = d.group;
+        if (rep) *rep = smhip_cabs_report{};
+        if (d.n == 0) return SMHIP_OK;
+        const size_t R = d.rows, C = d.n / R;
+        const size_t Mu = (size_t)std::max(M, 8);
+        CabsMergeParams m;
+        delta_inputs(d, out, delta_out, false, m);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.alpha[i] = (float)d.alpha[i < k ? i : 0];
+        m.lambda = (float)d.lambda;
+        m.mask_out = mask_out;
+        m.R = R; m.C = C; m.G = (C + Mu - 1) / Mu;
+        m.M = M; m.N = d.n_keep; m.L = (int)(Mu / 8);
+        m.log2L = 0;
+        while ((1 << m.log2L) < m.L) ++m.log2L;
+        m.conflict_aware = d.conflict_aware ? 1 : 0;
+        m.row_vec = (m.in.aligned && C % 8 == 0 && aligned16(mask_out)) ? 1 : 0;
+        // every row octet of every team, the idle ones of the tail groups included: at most n / 8 + R * M / 8
+        if (R > ((size_t)1 << 56) / (m.G * (size_t)m.L)) return fail(SMHIP_ERR_ARG, "cabs_merge: tensor too large");
+        m.units = R * m.G * (size_t)m.L;
+        m.chunks = pick_chunks(m.units, CABS_THREADS, 2, 8);
+        if ((m.units + CABS_THREADS - 1) / CABS_THREADS / (size_t)m.chunks > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "cabs_merge: tensor too large");
+        CabsReadback* rb;
+        int rc;
+        if ((rc = plain_workspace(rb))) return rc;
+        m.kept = rb->kept; m.counts = rb->counts; m.flags = rb->flags;
+
+        const int grid = stream_grid(m.units, CABS_THREADS, m.chunks);
+        const size_t lds = (LDS_SCRATCH_FLOATS + cabs_lds_words(k, m.L, CABS_THREADS)) * 4;
+        if (k <= CABS_REG_SMALL) be.template launch<KCabsMerge>(grid, CABS_THREADS, lds, m, stream);
+        else be.template launch<KCabsMergeAny>(grid, CABS_THREADS, lds, m, stream);
+
+        CabsReadback host;
+        if ((rc = delta_readback("cabs_merge", k, rb, host))) return rc;     // the call's one synchronisation
+        if (rep) {
+            rep->groups = (uint64_t)R * (uint64_t)((C + (size_t)M - 1) / (size_t)M);
+            for (int i = 0; i < k; ++i) {
+                rep->kept[i] = host.kept[i];
+                rep->short_groups[i] = host.counts[i];
+                rep->surplus[i] = host.counts[TIES_MAX_MODELS + i];
+            }
+            rep->covered = host.counts[2 * TIES_MAX_MODELS];
+            rep->overlap = host.counts[2 * TIES_MAX_MODELS + 1];
+        }
         return SMHIP_OK;
     }
 

@@ -195,6 +195,23 @@ class WidenMergeReport:
 
 
 @dataclass
+class CabsReport:
+    n: int = 0                                                       # elements of the tensor
+    rows: int = 0                                                    # R: n over the last dimension (1 for a 0-D or 1-D tensor)
+    cols: int = 0                                                    # C: the last dimension
+    n_keep: int = 0                                                  # N of N:M
+    group: int = 0                                                   # M
+    conflict_aware: bool = True
+    groups: int = 0                                                  # R * ceil(C / M)
+    kept: List[int] = field(default_factory=list)                    # [i]: elements finetune i kept
+    short_groups: List[int] = field(default_factory=list)            # [i]: groups with fewer candidates than their quota
+    surplus: List[int] = field(default_factory=list)                 # [i]: elements kept beyond the quota (ties at the cut)
+    covered: int = 0                                                 # elements kept by at least one finetune
+    overlap: int = 0                                                 # elements kept by at least two (0 when conflict-aware)
+    mask: Optional[torch.Tensor] = None                              # want_mask: int32 [*shape], bit i = finetune i kept it
+
+
+@dataclass
 class DeltaStatsReport:
     n: int = 0                                                       # elements of the tensor
     densities: List[float] = field(default_factory=list)             # rho_q, as given
@@ -604,7 +621,7 @@ class Engine:
                                                      1 if sign_agreement else 0, out.data_ptr(), self._stream()))
         return out
 
-    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN; merge_layer stages its inputs the same way) ---------
+    # -- the delta merges (TIES, DARE, Breadcrumbs, the geometric ones, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS; merge_layer stages its inputs the same way) ---------
     def _stage_delta_merge(self, desc, finetunes, bases, alphas, base_out, layer_name: str, want_delta: bool,
                            op: Optional[str] = None, out_dtype: Optional[torch.dtype] = None):
         """Device copies of the inputs of one delta-merge call, ``desc``'s common fields (k, finetune, base, alpha,
@@ -1169,6 +1186,46 @@ class Engine:
                                   calibrated=[[int(rep.calibrated[i][s]) for s in range(2)] for i in range(k)])
         if want_stats:
             report.stat, report.rank, report.weight = stat.cpu(), rank.cpu().to(torch.int64), weight.cpu()
+        return (out, report, delta) if want_delta else (out, report)
+
+    # -- CABS (conflict-aware, balanced n:m sparsification) -----------------------------------------
+    def cabs_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                   base_out: torch.Tensor, *, n_keep: int, group: int, conflict_aware: bool = True, lam: float = 1.0,
+                   layer_name: str = "", want_delta: bool = False, want_mask: bool = False):
+        """CABS merge of one tensor viewed as rows of its last dimension (``smhip_cabs_merge``; the function is stated in
+        include/shardmerge_hip.h): every group of ``group`` consecutive weights of a row keeps the ``n_keep`` largest
+        magnitudes of each delta ``finetune_i - base_i`` (ties at the cut all kept), the finetunes IN THE ORDER GIVEN and,
+        when ``conflict_aware``, each only where no earlier one kept an entry; the kept entries are weighted by
+        ``alpha_i``, summed without normalisation, times ``lam``, added onto ``base_out`` in its dtype.  ``group`` is a
+        power of two in 4..512, ``1 <= n_keep <= group``.  Returns (out, CabsReport[, the fp32 merged delta times
+        ``lam``]); ``want_mask`` adds the kept bits of every element to the report.  A NaN or Inf in a delta raises
+        ValueError naming ``layer_name`` and the finetune."""
+        layer_name = layer_name or "layer"
+        for name, v in (("n_keep", n_keep), ("group", group)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"cabs_merge: {name} must be an integer, not {v!r}")
+        if group not in _lib.CABS_GROUPS:
+            raise ValueError(f"cabs_merge: group {group} is not a power of two in 4..512")
+        if not (1 <= n_keep <= group):
+            raise ValueError(f"cabs_merge: n_keep {n_keep} is not in 1..{group}")
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"cabs_merge: lam {lam} is not finite")
+        desc, rep, k = _lib.CabsDesc(), _lib.CabsReport(), len(finetunes)
+        desc.n_keep, desc.group, desc.conflict_aware, desc.lam = n_keep, group, 1 if conflict_aware else 0, float(lam)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "cabs_merge")
+        desc.n = bo.numel()
+        cols = int(bo.shape[-1]) if bo.ndim >= 1 else 1
+        rows = (desc.n // cols if cols else 1) or 1
+        desc.rows = rows
+        mask = torch.zeros(bo.shape, dtype=torch.int16, device=self.device) if want_mask else None
+        self._run_delta_merge(self.lib.dll.smhip_cabs_merge, desc, rep, out, delta, layer_name,
+                              mask.data_ptr() if mask is not None and mask.numel() else None)
+        report = CabsReport(n=int(desc.n), rows=int(rows), cols=cols, n_keep=n_keep, group=group, conflict_aware=bool(conflict_aware),
+                            groups=int(rep.groups), kept=[int(rep.kept[i]) for i in range(k)],
+                            short_groups=[int(rep.short_groups[i]) for i in range(k)],
+                            surplus=[int(rep.surplus[i]) for i in range(k)], covered=int(rep.covered), overlap=int(rep.overlap))
+        if want_mask:           # (uint16 values in an int16 tensor: widened here)
+            report.mask = mask.to(torch.int32) & 0xFFFF
         return (out, report, delta) if want_delta else (out, report)
 
     # -- task-vector statistics ----------------------------------------------------------------

@@ -27,6 +27,7 @@ _OPERATOR_CLASSES = {
     "pcb": ("pcb", "PcbMerge"),
     "tsv": ("tsv", "TsvMerge"),
     "widen": ("widen", "WidenMerge"),
+    "cabs": ("cabs", "CabsMerge"),
 }
 
 
