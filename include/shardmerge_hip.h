@@ -1071,6 +1071,97 @@ int smhip_tsv_merge(smhip_ctx* ctx, const smhip_tsv_desc* desc, void* out, float
 int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
                     int base_out_dtype, double lambda, void* out, float* delta_out, void* stream);
 
+/* ---- Iso-C merge (Marczak et al. 2025, "No Task Left Behind: Isotropic Model Merging with Common and Task-Specific
+ *      Subspaces"): the task-arithmetic sum T = sum_i alpha_i (finetune_i - base_i) of one 2-D tensor [rows x cols], with
+ *      SVD T = U S V^T, has its spectrum replaced by its mean: merged = mean(S) U V^T.  U V^T is the orthogonal polar
+ *      factor of T and mean(S) = <U V^T, T> / min(rows, cols), so no SVD is taken: a Newton-Schulz iteration finds the
+ *      polar factor with matrix products alone.  s = min(rows, cols) <= 16384, L = max(rows, cols).
+ *      gemm(A, B) below is "iso_gemm": every element is ONE fp32 fmaf chain from +0 over the products in ASCENDING k,
+ *      followed, when the number of products is odd, by one step fmaf(+0, +0, acc) (which changes -0 to +0 and nothing
+ *      else); a symmetric product is computed for m >= n (by whole 128 x 128 tiles; inside a diagonal tile both halves,
+ *      which are equal bit for bit because fp32 products commute) and mirrored.  An ordered sum is fp64 in the order of
+ *      smhip_geo_merge's Gram: segments of 32768 elements of the row-major matrix, inside a segment lane t of 256 adds the
+ *      elements of the octets t, t + 256, ... one after another from 0, the 256 lane sums go through the binary tree
+ *      p[t] += p[t + h], h = 128 .. 1, and the segments are added in index order from 0.
+ *        1. The sum.  T[e] = ((0 + d_0 * a_0) + d_1 * a_1) + ..., d_i = fp32(finetune_i) - fp32(base_i), a_i = fp32(alpha_i):
+ *           one rounded fp32 operation at a time - dare_linear at density 1 without normalisation.  Alphas of any sign.
+ *           A NaN or Inf in a d_i fails the call with SMHIP_ERR_NONFINITE (the message names the finetunes).
+ *        2. Orientation.  X = T when rows <= cols, else T^T (a copy): [s x L], row-major.  Everything below runs on the
+ *           oriented matrix, so transposed inputs give the transposed output bit for bit.
+ *        3. Scale.  nu = sqrt(ordered sum of X_ij^2) (a product of two fp32 values is exact in fp64).  nu not finite:
+ *           SMHIP_ERR_NONFINITE.  nu == 0: zero = 1, merged = +0 and step 6 runs with it; no iteration.
+ *           X_0 = X * fp32(1 / nu), 1 / nu one fp64 division.
+ *        4. Iteration, t = 0, 1, ...:  G = gemm(X_t, X_t^T) [s x s], symmetric.
+ *           e_t = sqrt((ordered sum of ((fp64(G_ij) - [i == j]) squared)) / s): the subtraction, the square, each addition,
+ *           the division and the root are one rounded fp64 operation each.  e_t not finite: SMHIP_ERR_NONFINITE.
+ *           e_t <= tol: converged, Q = X_t.  Else t == max_iter: not converged, Q = X_t, and no error.
+ *           The quintic phase lasts while e_t > 0.35 AND (t == 0 or e_t < e_{t-1}); it ends for good at the first t where
+ *           either fails.  (The quintic does not converge: it throws the spectrum into a band around 1, about
+ *           [0.68, 1.13], where e settles between 0.35 and 0.40 - above the threshold on many inputs, a 128 x 128 Gaussian
+ *           among them.  A residual that stops falling is that band; from it, and from any spectrum below sqrt(3), the
+ *           cubic converges monotonically.)
+ *           The quintic step: P = fmaf(c5, gemm(G, G), b5 * G) (symmetric), X_{t+1} = fmaf(a5, X_t, gemm(P, X_t)),
+ *           (a5, b5, c5) = (0x1.b8e56p+1, -0x1.31999ap+2, 0x1.040832p+1) = fp32(3.4445, -4.7750, 2.0315).
+ *           The cubic step: X_{t+1} = fmaf(1.5, X_t, -0.5 * gemm(G, X_t)).
+ *           steps[t] is 'q' or 'c'; iterations = the number of steps taken.
+ *        5. N = ordered sum of Q_ij * X_ij over the UNSCALED oriented X of step 2; sigma_bar = N / s (fp64).  Not finite:
+ *           SMHIP_ERR_NONFINITE.
+ *        6. merged = fp32(sigma_bar) * Q, oriented back; out = round_to(base_out_dtype, fma(fp32(lambda), merged,
+ *           fp32(base_out))); delta_out = merged (NOT times lambda).
+ *      A T without full rank (merged LoRA adapters) has directions in its null space that are whatever rounding puts
+ *      there, amplified to singular value 1 - as arbitrary as the SVD's basis of the null space in the paper's form, and
+ *      the same bits everywhere.  It is not guarded against.  Passes: the k finetunes and their bases read once;
+ *      3 gemm per quintic step, 2 per cubic step and one more for the last G.  Profile names: "iso_sum",
+ *      "iso_transpose" (rows > cols only: 2, or 1 when T is zero), "iso_norm", "iso_scale", "iso_gemm_nt", "iso_gemm_nn", "iso_resid", "iso_dot",
+ *      "iso_apply", "geo_gram_fold".  The stream is synchronised once per e_t, once for nu and once for N.  The
+ *      workspace is the caller's: DEVICE memory, 256-byte aligned, at least smhip_iso_workspace(rows, cols) bytes -
+ *      three [rows x cols] and two [s x s] fp32 buffers and the sums' partials.  SMHIP_ERR_ARG: k outside 1..16, a
+ *      non-finite alpha or lambda, tol outside (0, 1], max_iter outside 0..200, n != rows * cols, rows or cols < 1
+ *      (n > 0), s > 16384, a bad workspace, and the aliasing, alignment, dtype and null-pointer rules of
+ *      smhip_ties_merge.  n == 0: a no-op, the report all zeros. ---- */
+#define SMHIP_ISO_MAX_S 16384
+#define SMHIP_ISO_MAX_ITER 200
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [rows x cols] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];
+    int in_dtype;
+    const void* base_out; int base_out_dtype;
+    size_t n;                               /* rows * cols */
+    int rows, cols;
+    double lambda;
+    double tol;                             /* (0, 1] */
+    int max_iter;                           /* 0..200 */
+    void* workspace; size_t workspace_bytes;
+} smhip_iso_desc;
+typedef struct {
+    int s, L, transposed;
+    int iterations, converged, zero;
+    double nu, N, sigma_bar;
+    double e[SMHIP_ISO_MAX_ITER + 1];       /* e_0 .. e_iterations */
+    char steps[SMHIP_ISO_MAX_ITER + 4];     /* 'q' / 'c' per step, NUL-terminated */
+} smhip_iso_report;
+size_t smhip_iso_workspace(int rows, int cols);   /* 0: a bad argument */
+/* out: device, base_out_dtype, [rows x cols].  delta_out (optional): device float, merged.  report (optional): HOST. */
+int smhip_iso_merge(smhip_ctx* ctx, const smhip_iso_desc* desc, void* out, float* delta_out,
+                    smhip_iso_report* report, void* stream);
+/* TEST ABI, as smhip_tsv_probe: "iso_gemm" alone on DEVICE fp32 matrices with element-aligned pointers and pitches.
+ * form 0 (NT): c = ep(a b^T), a [M x K] pitch lda, b [N x K] pitch ldb; form 1 (NN): c = ep(a b), b [K x N].  sym (NT,
+ * M == N, b^T the transpose of a's partner bit for bit - a == b, or a == b symmetric): m >= n computed and mirrored.
+ * epilogue 0: acc; 1: fmaf(ca, acc, cb * e[m][n]); 2: fmaf(ca, e[m][n], acc); 3: fmaf(ca, e[m][n], cb * acc); e [M x N]
+ * pitch lde.  c [M x N] pitch ldc may not overlap an input.  M, N, K >= 1. */
+typedef struct {
+    int form, sym, epilogue;
+    int M, N, K;
+    const float* a; int lda;
+    const float* b; int ldb;
+    const float* e; int lde;
+    float ca, cb;
+    float* c; int ldc;
+} smhip_iso_gemm_desc;
+int smhip_iso_gemm(smhip_ctx* ctx, const smhip_iso_gemm_desc* desc, void* stream);
+
 /* ---- WIDEN merge (Yu, Yu, Yu, Huang, Li, "Extend Model Merging from Fine-Tuned to Pre-Trained Large Language Models via
  *      Weight Disentanglement", 2024): every weight matrix is disentangled into a magnitude and a direction per column,
  *      the divergences of each finetune from its base in both are RANKED within the finetune - which makes the measure

@@ -312,6 +312,32 @@ class TsvReport(C.Structure):
                 ("kept_U", C.c_int), ("kept_W", C.c_int)]
 
 
+ISO_MAX_S, ISO_MAX_ITER = 16384, 200               # SMHIP_ISO_MAX_S, SMHIP_ISO_MAX_ITER
+ISO_NT, ISO_NN = 0, 1                               # form of smhip_iso_gemm
+ISO_EP_PLAIN, ISO_EP_POLY, ISO_EP_AXPY, ISO_EP_CUBIC = range(4)
+
+
+class IsoDesc(C.Structure):
+    """smhip_iso_desc: the leading fields of the delta merges, then the shape, lambda, tol, max_iter and the workspace"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("lam", C.c_double), ("tol", C.c_double),
+                                         ("max_iter", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class IsoReport(C.Structure):
+    """smhip_iso_report"""
+    _fields_ = [("s", C.c_int), ("L", C.c_int), ("transposed", C.c_int),
+                ("iterations", C.c_int), ("converged", C.c_int), ("zero", C.c_int),
+                ("nu", C.c_double), ("N", C.c_double), ("sigma_bar", C.c_double),
+                ("e", C.c_double * (ISO_MAX_ITER + 1)), ("steps", C.c_char * (ISO_MAX_ITER + 4))]
+
+
+class IsoGemmDesc(C.Structure):
+    """smhip_iso_gemm_desc"""
+    _fields_ = [("form", C.c_int), ("sym", C.c_int), ("epilogue", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("e", C.c_void_p), ("lde", C.c_int),
+                ("ca", C.c_float), ("cb", C.c_float), ("c", C.c_void_p), ("ldc", C.c_int)]
+
+
 DELLA_MAX_COLS = 32768         # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -396,7 +422,11 @@ class SmhipLibrary:
         d.smhip_tsv_probe.argtypes = [P, P, P, I, I, I, P, I, D, P, P, P]
         d.smhip_widen_merge.argtypes = [P, C.POINTER(WidenDesc), P, P, P, P, P, C.POINTER(WidenReport), P]
         d.smhip_cabs_merge.argtypes = [P, C.POINTER(CabsDesc), P, P, P, C.POINTER(CabsReport), P]
-        d.smhip_debug_option.argtypes = [P, C.c_char_p, C.c_long]
+        d.smhip_iso_workspace.argtypes = [I, I]
+        d.smhip_iso_workspace.restype = C.c_size_t
+        d.smhip_iso_merge.argtypes = [P, C.POINTER(IsoDesc), P, P, C.POINTER(IsoReport), P]
+        d.smhip_iso_gemm.argtypes = [P, C.POINTER(IsoGemmDesc), P]
+        d.smhip_debug_option.argtypes =[P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]
         d.smhip_profile_reset.argtypes = [P]

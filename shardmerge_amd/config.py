@@ -159,6 +159,18 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # cabs_m: 256             #   a power of two in 4..512: the group (64:256 keeps a quarter)
       # cabs_conflict_aware: 1  #   1: later finetunes take only what is left; 0: every finetune is pruned on its own
       # cabs_lambda: 1.0        #   scales the merged delta
+                                # | iso_c (Iso-C, Marczak et al. 2025; no counterpart in the reference): a block tensor's
+                                #   deltas are summed with their alphas into ONE task matrix ([shape[0] x the rest]) whose
+                                #   singular values are all replaced by their mean, the singular vectors kept: every
+                                #   direction any finetune moved gets the same weight.  No SVD is taken: the polar factor
+                                #   comes from a Newton-Schulz iteration on an fp32 MFMA GEMM.  1-D tensors take the
+                                #   normalised weighted mean of their deltas (dare_linear at density 1) times iso_lambda.
+                                #   alphas of any sign.  A block tensor with min(rows, cols) > 16384 is an error before
+                                #   anything is written.  The spectral keys, norm_mode, task_add_models and every other
+                                #   family's keys are rejected; keys:
+      # iso_lambda: 1.0         #   scales the merged delta
+      # iso_tol: 0.0001         #   0 < iso_tol <= 1: the iteration stops at ||X X^T - I||_F / sqrt(min(rows, cols)) <= iso_tol
+      # iso_max_iter: 40        #   an integer in 0..200: steps at most (reaching it is reported, not an error)
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -186,7 +198,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs", "iso_c")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -216,6 +228,9 @@ CABS_OPERATORS = ("cabs",)
 CABS_OPTION_DEFAULTS = {"cabs_n": 64, "cabs_m": 256, "cabs_conflict_aware": 1.0, "cabs_lambda": 1.0}
 CABS_GROUPS = (4, 8, 16, 32, 64, 128, 256, 512)     # cabs_m: a group is selected inside one work-group
 WIDEN_MAX_COLS = 65536                              # columns of a block tensor at most: the ranks are counted over all pairs
+ISO_OPERATORS = ("iso_c",)
+ISO_OPTION_DEFAULTS = {"iso_lambda": 1.0, "iso_tol": 1e-4, "iso_max_iter": 40}
+ISO_MAX_S = 16384                                   # min(rows, cols) of a block tensor at most
 TSV_MAX_VECTORS = 256                               # k * min(tsv_rank, rows, cols) at most: the width of the whitened panels
 
 
@@ -370,6 +385,16 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "consensus_ta": "(it masks by order: earlier finetunes keep their positions)",
                            "arcee_fusion": "(it merges several models by n:m sparsification)"},
                   check=_cabs_n_of_m),
+    _OptionFamily(ISO_OPERATORS, ISO_OPTION_DEFAULTS,
+                  {"iso_lambda": _LAMBDA, "iso_tol": (0, 1, "(]"), "iso_max_iter": ("int", 0, 200)},
+                  earlier={"ties": "(it trims nothing and flattens the spectrum of the summed delta: iso_lambda)",
+                           "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it trims nothing)",
+                           "model_stock": "(it weights by alpha and flattens the spectrum of the sum)",
+                           "sce": "(it selects nothing: every singular direction gets the mean singular value)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it masks nothing)",
+                           "arcee_fusion": "(it merges several models by the spectrum of their summed delta)"}),
 )
 
 

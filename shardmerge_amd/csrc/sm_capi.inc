@@ -621,6 +621,58 @@ int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, in
     SM_FINISH(ctx, ctx->pipe.delta.tsv_probe(b, w, rows, cols, Rp, base_out, base_out_dtype, lambda, out, delta_out));
 }
 
+size_t smhip_iso_workspace(int rows, int cols) {
+    if (rows < 1 || cols < 1 || std::min(rows, cols) > SMHIP_ISO_MAX_S) return 0;
+    return smhip::DeltaHost<SM_BACKEND>::iso_layout(rows, cols).total;
+}
+
+int smhip_iso_merge(smhip_ctx* ctx, const smhip_iso_desc* d, void* out, float* delta_out, smhip_iso_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "iso_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            if (!(d->tol > 0.0 && d->tol <= 1.0)) return "tol must be in (0, 1]";
+            if (d->max_iter < 0 || d->max_iter > SMHIP_ISO_MAX_ITER) return "max_iter out of range (0..200)";
+            return nullptr;
+        }))
+        return rc;
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("iso_merge: ") + what); };
+    if (d->n > 0) {
+        if (d->rows < 1 || d->cols < 1 || (size_t)d->rows * (size_t)d->cols != d->n) return bad("rows and cols must be >= 1 and rows * cols == n");
+        if (std::min(d->rows, d->cols) > SMHIP_ISO_MAX_S) return bad("min(rows, cols) exceeds 16384");
+        if (d->n / smhip::GEO_SEG_ELEMS > (size_t)1 << 30) return bad("tensor too large");
+        if (!d->workspace || (uintptr_t)d->workspace % 256 || d->workspace_bytes < smhip_iso_workspace(d->rows, d->cols))
+            return bad("the workspace is null, not 256-byte aligned or too small (smhip_iso_workspace)");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.iso_merge(*d, out, delta_out, report));
+}
+
+int smhip_iso_gemm(smhip_ctx* ctx, const smhip_iso_gemm_desc* d, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("iso_gemm: ") + what); };
+    if (!d) return bad("null descriptor");
+    if (d->form != 0 && d->form != 1) return bad("bad form");
+    if (d->epilogue < 0 || d->epilogue > 3) return bad("bad epilogue");
+    if (d->M < 1 || d->N < 1 || d->K < 1 || d->M > (1 << 24) || d->N > (1 << 24)) return bad("bad shape");
+    if (d->sym != 0 && d->sym != 1) return bad("sym must be 0 or 1");
+    if (d->sym && (d->form != 0 || d->M != d->N)) return bad("sym needs the NT form and M == N");
+    if (!d->a || !d->b || !d->c || (d->epilogue && !d->e)) return bad("null pointer");
+    if ((uintptr_t)d->a % 4 || (uintptr_t)d->b % 4 || (uintptr_t)d->c % 4 || (uintptr_t)d->e % 4)
+        return bad("a pointer is not aligned to its element size");
+    if (d->lda < d->K || d->ldb < (d->form == 0 ? d->K : d->N) || d->ldc < d->N || (d->epilogue && d->lde < d->N))
+        return bad("a pitch is shorter than its row");
+    const int gm = (d->M + 127) / 128, gn = (d->N + 127) / 128;
+    if ((long long)gm * gn > 0x7fffffffLL) return bad("bad shape");
+    auto span = [](const float* p, int rows, int ld, int cols) { return std::make_pair((uintptr_t)p, (uintptr_t)(p + (size_t)(rows - 1) * ld + cols)); };
+    const auto sc = span(d->c, d->M, d->ldc, d->N);
+    auto hits = [&](std::pair<uintptr_t, uintptr_t> x) { return x.first < sc.second && sc.first < x.second; };
+    if (hits(span(d->a, d->M, d->lda, d->K)) || hits(d->form == 0 ? span(d->b, d->N, d->ldb, d->K) : span(d->b, d->K, d->ldb, d->N)) ||
+        (d->epilogue && hits(span(d->e, d->M, d->lde, d->N))))
+        return bad("c overlaps an input");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.iso_gemm_probe(*d));
+}
+
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
     SM_GUARD(ctx);
     if (!norm_out || (n > 0 && !x)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

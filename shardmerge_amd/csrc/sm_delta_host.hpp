@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, the task-vector statistics and the low-rank extraction (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics and the low-rank extraction (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -28,6 +28,7 @@
 #include "sm_tsv.hpp"
 #include "sm_widen.hpp"
 #include "sm_cabs.hpp"
+#include "sm_iso.hpp"
 
 namespace smhip {
 
@@ -129,6 +130,17 @@ SM_KERNEL_TAG_LB(KWidenCombineAny, WidenCombineParams, "widen_combine", k_widen_
 // selections of the finetunes; k <= 4 at dare_merge's residency, or up to 16
 SM_KERNEL_TAG_LB(KCabsMerge, CabsMergeParams, "cabs_merge", k_cabs_merge<CABS_REG_SMALL>(ex, p), CABS_THREADS, 4)
 SM_KERNEL_TAG_LB(KCabsMergeAny, CabsMergeParams, "cabs_merge_any", k_cabs_merge<TIES_MAX_MODELS>(ex, p), CABS_THREADS, 2)
+// Iso-C merge (sm_iso.hpp): the LDS-staged fp32 MFMA GEMM in its two forms (four waves of 2 x 2 accumulator tiles of
+// 32 x 32, 64 registers), the sum of the weighted deltas, the transposing copy, the three ordered fp64 sums, scale, apply
+SM_KERNEL_TAG_LB(KIsoGemmNT, IsoGemmParams, "iso_gemm_nt", k_iso_gemm<ISO_NT>(ex, p), ISO_THREADS, 2)
+SM_KERNEL_TAG_LB(KIsoGemmNN, IsoGemmParams, "iso_gemm_nn", k_iso_gemm<ISO_NN>(ex, p), ISO_THREADS, 2)
+SM_KERNEL_TAG_LB(KIsoSum, IsoSumParams, "iso_sum", k_iso_sum(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KIsoTranspose, IsoTransposeParams, "iso_transpose", k_iso_transpose(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KIsoNorm, IsoReduceParams, "iso_norm", k_iso_reduce<ISO_RED_NORM>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KIsoResid, IsoReduceParams, "iso_resid", k_iso_reduce<ISO_RED_RESID>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KIsoDot, IsoReduceParams, "iso_dot", k_iso_reduce<ISO_RED_DOT>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KIsoScale, IsoScaleParams, "iso_scale", k_iso_scale(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KIsoApply, IsoApplyParams, "iso_apply", k_iso_apply(ex, p), 256, 4)
 // the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
@@ -141,6 +153,7 @@ SM_KERNEL_TAG_LB(KCabsMergeAny, CabsMergeParams, "cabs_merge_any", k_cabs_merge<
 #define SM_SIDE_KERNELS_12(X) X(KTsvApply)
 #define SM_SIDE_KERNELS_13(X) X(KWidenColstats) X(KWidenColfold) X(KWidenRank) X(KWidenCoef) X(KWidenCombine) X(KWidenCombineAny)
 #define SM_SIDE_KERNELS_14(X) X(KCabsMerge) X(KCabsMergeAny)
+#define SM_SIDE_KERNELS_15(X) X(KIsoGemmNT) X(KIsoGemmNN) X(KIsoSum) X(KIsoTranspose) X(KIsoNorm) X(KIsoResid) X(KIsoDot) X(KIsoScale) X(KIsoApply)
 
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
@@ -1568,6 +1581,159 @@ class DeltaHost {
     int tsv_probe(const float* b, const float* w, int rows, int cols, int Rp, const void* base_out, int dtype, double lambda,
                   void* out, float* delta_out) {
         tsv_apply(b, Rp, w, Rp, rows, cols, Rp, base_out, dtype, lambda, out, delta_out);
+        be.sync(stream);
+        return SMHIP_OK;
+    }
+
+    // ---- Iso-C merge (sm_iso.hpp; smhip_iso_merge).  The caller's workspace: three [rows x cols] fp32 buffers (T oriented,
+    // and the two X of the iteration; the second also takes the sum before a transposing copy and Q oriented back) | two
+    // [s x s] buffers (G; P) | the partials of the ordered sums | 256 bytes: flags, then the three sums. ----
+    struct IsoLayout {
+        int s, L;
+        size_t n, B1, B2, S1, S2, part, tail, total;
+    };
+    static IsoLayout iso_layout(int rows, int cols) {
+        IsoLayout t;
+        t.s = std::min(rows, cols); t.L = std::max(rows, cols);
+        t.n = (size_t)rows * cols;
+        const size_t nb = round_up(t.n * 4, 256), sb = round_up((size_t)t.s * t.s * 4, 256);
+        const size_t nseg = (std::max(t.n, (size_t)t.s * t.s) + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
+        t.B1 = nb; t.B2 = 2 * nb; t.S1 = 3 * nb; t.S2 = t.S1 + sb;
+        t.part = t.S2 + sb;
+        t.tail = t.part + round_up(nseg * 8, 256);
+        t.total = t.tail + 256;
+        return t;
+    }
+    void iso_gemm(int form, int sym, const float* a, int lda, const float* b, int ldb, int M, int N, int K, int ep, float ca,
+                  float cb, const float* e, int lde, float* c, int ldc) {
+        IsoGemmParams g;
+        g.a = a; g.b = b; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
+        g.avec = (aligned16(a) && lda % 4 == 0) ? 1 : 0; g.bvec = (aligned16(b) && ldb % 4 == 0) ? 1 : 0;
+        g.sym = sym; g.ep = ep; g.ca = ca; g.cb = cb; g.e = e; g.lde = lde; g.c = c; g.ldc = ldc;
+        const int gm = (M + ISO_WG - 1) / ISO_WG;
+        g.gn = (N + ISO_WG - 1) / ISO_WG;
+        const int grid = sym ? gm * (gm + 1) / 2 : gm * g.gn;
+        if (form == ISO_NT) be.template launch<KIsoGemmNT>(grid, ISO_THREADS, ISO_GEMM_LDS_FLOATS * 4, g, stream);
+        else be.template launch<KIsoGemmNN>(grid, ISO_THREADS, ISO_GEMM_LDS_FLOATS * 4, g, stream);
+    }
+    void iso_transpose(const float* src, float* dst, int rows, int cols) {
+        IsoTransposeParams t;
+        t.src = src; t.dst = dst; t.rows = rows; t.cols = cols; t.gc = (cols + 31) / 32;
+        be.template launch<KIsoTranspose>((rows + 31) / 32 * t.gc, 256, 32 * 33 * 4, t, stream);
+    }
+    // one ordered fp64 sum: the segments' partials, then their fold into *result (device)
+    template <class K>
+    void iso_reduce(const float* x, const float* y, size_t n, int s, double* part, double* result) {
+        IsoReduceParams r;
+        r.x = x; r.y = y; r.n = n; r.s = s; r.part = part;
+        const size_t nseg = (n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
+        be.template launch<K>((int)nseg, GEO_THREADS, iso_reduce_lds_floats() * 4, r, stream);
+        GeoFoldParams f;
+        f.np = 1; f.nseg = nseg; f.part = part; f.G = result;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+    }
+    int iso_merge(const smhip_iso_desc& d, void* out, float* delta_out, smhip_iso_report* rep) {
+        smhip_iso_report local;
+        smhip_iso_report& R_ = rep ? *rep : local;
+        R_ = smhip_iso_report{};
+        if (d.n == 0) return SMHIP_OK;
+        const IsoLayout t = iso_layout(d.rows, d.cols);
+        const int rows = d.rows, cols = d.cols, s = t.s, L = t.L;
+        const bool tr = rows > cols;
+        char* ws = (char*)d.workspace;
+        float* T = (float*)ws;
+        float* X = (float*)(ws + t.B1);
+        float* Xn = (float*)(ws + t.B2);
+        float* G = (float*)(ws + t.S1);
+        float* P = (float*)(ws + t.S2);
+        double* part = (double*)(ws + t.part);
+        uint32_t* flags = (uint32_t*)(ws + t.tail);
+        double* res = (double*)(ws + t.tail + 16);                  // [0]: sum X^2, [1]: the residual's sum, [2]: N
+        be.memset(flags, 0, 256, stream);
+        R_.s = s; R_.L = L; R_.transposed = tr ? 1 : 0;
+
+        // 1, 2: the sum, oriented
+        IsoSumParams sp;
+        sp.t = tr ? Xn : T;
+        ties_inputs(sp.in, d.k, d.in_dtype, d.n, d.finetune, d.base, true);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) sp.alpha[i] = (float)d.alpha[i < d.k ? i : 0];
+        sp.flags = flags;
+        sp.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+        be.template launch<KIsoSum>(stream_grid((d.n + 7) / 8, 256, sp.chunks), 256, 0, sp, stream);
+        if (tr) iso_transpose(Xn, T, rows, cols);
+        // 3: the scale
+        iso_reduce<KIsoNorm>(T, nullptr, d.n, s, part, res);
+        double sum = 0.0;
+        uint32_t fl[2];
+        be.d2h(fl, flags, sizeof fl, stream);
+        be.d2h(&sum, res, 8, stream);
+        if (!be.ok()) return SMHIP_OK;
+        if (fl[0]) return delta_nonfinite("iso_merge", "finetune - base", d.k, fl[0]);
+        const double nu = geo_dsqrt(sum);
+        R_.nu = nu;
+        if (!geo_finite(nu)) return fail(SMHIP_ERR_NONFINITE, "iso_merge: the sum of the weighted deltas is not finite");
+        auto apply = [&](const float* q, float sigma) {
+            IsoApplyParams a;
+            a.q = q; a.sigma = sigma; a.lambda = (float)d.lambda; a.base_out = d.base_out; a.dtype = d.base_out_dtype;
+            a.out = out; a.delta_out = delta_out; a.n = d.n;
+            a.aligned = (aligned16(d.base_out) && aligned16(out) && aligned16(delta_out)) ? 1 : 0;
+            a.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+            be.template launch<KIsoApply>(stream_grid((d.n + 7) / 8, 256, a.chunks), 256, 0, a, stream);
+        };
+        if (nu == 0.0) {
+            R_.zero = 1;
+            be.memset(X, 0, d.n * 4, stream);
+            apply(X, 0.f);
+            be.sync(stream);
+            return SMHIP_OK;
+        }
+        IsoScaleParams sc;
+        sc.x = T; sc.y = X; sc.n = d.n; sc.c = (float)geo_ddiv(1.0, nu);
+        be.template launch<KIsoScale>((int)(((d.n + 3) / 4 + 255) / 256), 256, 0, sc, stream);
+        // 4: the iteration
+        int it = 0;
+        bool cubic = false;                                         // the quintic phase is over
+        double prev = 0.0;
+        for (;; ++it) {
+            iso_gemm(ISO_NT, 1, X, L, X, L, s, s, L, ISO_EP_PLAIN, 0.f, 0.f, nullptr, 0, G, s);
+            iso_reduce<KIsoResid>(G, nullptr, (size_t)s * s, s, part, res + 1);
+            double rs = 0.0;
+            be.d2h(&rs, res + 1, 8, stream);                        // the iteration's one synchronisation
+            if (!be.ok()) return SMHIP_OK;
+            const double e = geo_dsqrt(geo_ddiv(rs, (double)s));
+            R_.e[it] = e;
+            if (!geo_finite(e)) { R_.iterations = it; return fail(SMHIP_ERR_NONFINITE, "iso_merge: the iteration left the finite numbers"); }
+            if (e <= d.tol) { R_.converged = 1; break; }
+            if (it == d.max_iter) break;
+            if (!(e > ISO_QUINTIC_ABOVE) || (it > 0 && !(e < prev))) cubic = true;
+            prev = e;
+            if (!cubic) {
+                iso_gemm(ISO_NT, 1, G, s, G, s, s, s, s, ISO_EP_POLY, ISO_C5, ISO_B5, G, s, P, s);
+                iso_gemm(ISO_NN, 0, P, s, X, L, s, L, s, ISO_EP_AXPY, ISO_A5, 0.f, X, L, Xn, L);
+                R_.steps[it] = 'q';
+            } else {
+                iso_gemm(ISO_NN, 0, G, s, X, L, s, L, s, ISO_EP_CUBIC, ISO_A3, ISO_B3, X, L, Xn, L);
+                R_.steps[it] = 'c';
+            }
+            std::swap(X, Xn);
+        }
+        R_.iterations = it;
+        // 5: the mean singular value
+        iso_reduce<KIsoDot>(X, T, d.n, s, part, res + 2);
+        double N = 0.0;
+        be.d2h(&N, res + 2, 8, stream);
+        if (!be.ok()) return SMHIP_OK;
+        R_.N = N;
+        R_.sigma_bar = geo_ddiv(N, (double)s);
+        if (!geo_finite(N)) return fail(SMHIP_ERR_NONFINITE, "iso_merge: the mean singular value is not finite");
+        // 6: the output
+        if (tr) iso_transpose(X, Xn, cols, rows);
+        apply(tr ? Xn : X, (float)R_.sigma_bar);
+        be.sync(stream);
+        return SMHIP_OK;
+    }
+    int iso_gemm_probe(const smhip_iso_gemm_desc& d) {
+        iso_gemm(d.form, d.sym, d.a, d.lda, d.b, d.ldb, d.M, d.N, d.K, d.epilogue, d.ca, d.cb, d.e, d.lde, d.c, d.ldc);
         be.sync(stream);
         return SMHIP_OK;
     }

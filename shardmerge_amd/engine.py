@@ -268,6 +268,23 @@ class TsvReport:
 
 
 @dataclass
+class IsoReport:
+    rows: int = 0
+    cols: int = 0
+    s: int = 0                                                       # min(rows, cols)
+    L: int = 0                                                       # max(rows, cols)
+    transposed: bool = False                                         # rows > cols: the iteration ran on the transpose
+    nu: float = 0.0                                                  # ||T||_F of the summed delta (fp64, ordered)
+    iterations: int = 0                                              # steps taken
+    steps: str = ""                                                  # 'q' (quintic) or 'c' (cubic) per step
+    e: List[float] = field(default_factory=list)                     # e_0 .. e_iterations: ||X X^T - I||_F / sqrt(s)
+    converged: bool = False                                          # the last e is <= tol
+    N: float = 0.0                                                   # <Q, T>
+    sigma_bar: float = 0.0                                           # N / s: the mean singular value
+    zero: bool = False                                               # T == 0: nothing to merge, out = base_out
+
+
+@dataclass
 class LayerMergeReport:
     target_norm: float = 0.0
     delta_norms: List[float] = field(default_factory=list)
@@ -1144,6 +1161,70 @@ class Engine:
         self._call(self.lib.dll.smhip_tsv_probe(self.ctx.h, bv.data_ptr(), wv.data_ptr(), rows, cols, int(bv.shape[1]), bo.data_ptr(),
                                                 _DTYPE_CODE[bo.dtype], float(lam), out.data_ptr(), merged.data_ptr(), self._stream()))
         return out, merged
+
+    # -- Iso-C (isotropic merging) ----------------------------------------------------------------
+    def iso_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                  base_out: torch.Tensor, *, lam: float = 1.0, tol: float = 1e-4, max_iter: int = 40,
+                  want_delta: bool = False, layer_name: str = ""):
+        """Iso-C merge of one tensor with at least two dimensions, viewed as ``[shape[0], rest]`` (``smhip_iso_merge``; the
+        function is stated in include/shardmerge_hip.h): the sum ``T`` of the deltas ``finetune_i - base_i`` times
+        ``alpha_i`` with its singular values replaced by their mean - ``mean(S) U V^T``, the polar factor of ``T`` by a
+        Newton-Schulz iteration on fp32 MFMA that stops at ``||X X^T - I||_F / sqrt(s) <= tol`` or after ``max_iter``
+        steps (which is reported, not raised) - added, times ``lam``, onto ``base_out`` in its dtype.
+        ``min(rows, cols) <= 16384``.  Returns (out, IsoReport[, the fp32 merged delta before ``lam``]).  A NaN or Inf in
+        a delta or in the sum raises ValueError naming ``layer_name``."""
+        layer_name = layer_name or "layer"
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"iso_merge: lam {lam} is not finite")
+        if not (0.0 < float(tol) <= 1.0):
+            raise ValueError(f"iso_merge: tol {tol} is not in (0, 1]")
+        if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not (0 <= max_iter <= _lib.ISO_MAX_ITER):
+            raise ValueError(f"iso_merge: max_iter must be an integer in 0..{_lib.ISO_MAX_ITER}, not {max_iter!r}")
+        if base_out.ndim < 2:
+            raise ValueError(f"iso_merge: {layer_name} has shape {list(base_out.shape)}; at least two dimensions expected")
+        rows = int(base_out.shape[0])
+        cols = int(base_out.numel() // rows) if rows else 0
+        if min(rows, cols) > _lib.ISO_MAX_S:        # (before anything is staged)
+            raise ValueError(f"iso_merge: {layer_name} has shape {list(base_out.shape)}: min(rows, cols) = {min(rows, cols)}, at most {_lib.ISO_MAX_S}")
+        desc, rep = _lib.IsoDesc(), _lib.IsoReport()
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "iso_merge")
+        desc.n = bo.numel()
+        desc.rows, desc.cols, desc.lam, desc.tol, desc.max_iter = rows, cols, float(lam), float(tol), max_iter
+        if desc.n:
+            ws = self._xl_workspace(int(self.lib.dll.smhip_iso_workspace(rows, cols)))
+            desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
+        self._run_delta_merge(self.lib.dll.smhip_iso_merge, desc, rep, out, delta, layer_name)
+        it = int(rep.iterations)
+        report = IsoReport(rows=rows, cols=cols, s=int(rep.s), L=int(rep.L), transposed=bool(rep.transposed), nu=float(rep.nu),
+                           iterations=it, steps=rep.steps.decode(), e=[float(rep.e[t]) for t in range(it + 1)] if rep.nu > 0.0 else [],
+                           converged=bool(rep.converged), N=float(rep.N), sigma_bar=float(rep.sigma_bar), zero=bool(rep.zero))
+        return (out, report, delta) if want_delta else (out, report)
+
+    def iso_gemm(self, a: torch.Tensor, b: torch.Tensor, *, form: int = 0, sym: bool = False, epilogue: int = 0,
+                 ca: float = 0.0, cb: float = 0.0, e: Optional[torch.Tensor] = None, ldc: Optional[int] = None) -> torch.Tensor:
+        """``iso_gemm`` alone (``smhip_iso_gemm``; tests and tools): ``ep(a b^T)`` (form 0, ``b [N, K]``) or ``ep(a b)``
+        (form 1, ``b [K, N]``) for 2-D fp32 tensors whose rows are contiguous - views with an offset or a pitch are used
+        where they lie when they are on the engine's device.  Returns ``c [M, N]`` (a view of pitch ``ldc`` when given)."""
+        def place(t):
+            if t is None:
+                return None
+            if t.dtype != torch.float32 or t.device != self.device or t.ndim != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+                return self._dev(t, torch.float32)
+            return t
+        av, bv, ev = place(a), place(b), place(e)
+        M, K = av.shape
+        N = bv.shape[0] if form == _lib.ISO_NT else bv.shape[1]
+        pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+        ldc = int(ldc or N)
+        store = torch.zeros((M, ldc), dtype=torch.float32, device=self.device)
+        d = _lib.IsoGemmDesc()
+        d.form, d.sym, d.epilogue, d.M, d.N, d.K = int(form), 1 if sym else 0, int(epilogue), M, N, K
+        d.a, d.lda, d.b, d.ldb = av.data_ptr(), pitch(av), bv.data_ptr(), pitch(bv)
+        if ev is not None:
+            d.e, d.lde = ev.data_ptr(), pitch(ev)
+        d.ca, d.cb, d.c, d.ldc = float(ca), float(cb), store.data_ptr(), ldc
+        self._call(self.lib.dll.smhip_iso_gemm(self.ctx.h, C.byref(d), self._stream()))
+        return store[:, :N]
 
     # -- WIDEN (weight disentanglement) ----------------------------------------------------------
     def widen_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],

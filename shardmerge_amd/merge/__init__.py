@@ -28,6 +28,7 @@ _OPERATOR_CLASSES = {
     "tsv": ("tsv", "TsvMerge"),
     "widen": ("widen", "WidenMerge"),
     "cabs": ("cabs", "CabsMerge"),
+    "iso_c": ("iso", "IsoMerge"),
 }
 
 
