@@ -1299,6 +1299,76 @@ typedef struct {
 int smhip_cabs_merge(smhip_ctx* ctx, const smhip_cabs_desc* desc, void* out, float* delta_out, uint16_t* mask_out,
                      smhip_cabs_report* report, void* stream);
 
+/* ---- Delta pack: a finetune stored as one or two bits per weight and a scale, on top of its base.  bits == 1 keeps the
+ *      sign of every delta and one scale (BitDelta, Liu et al. 2024); bits == 2 keeps a mask of the `density` largest
+ *      magnitudes and their signs, a sparse ternary delta (ComPEFT, Yadav et al. 2023; both as recalled: PAPERS.md).  It
+ *      is no merge operator: smhip_dpack_apply rebuilds a finetune tensor that every operator then takes.  The reference
+ *      has no such format; this section IS its definition.  The tensor is seen as R = rows rows of C = cols elements
+ *      (the caller passes shape[0] and the product of the rest; a 0-D or 1-D tensor is one row), n = R C.
+ *      PACK, smhip_dpack_pack:
+ *        1. d_e = fl32(fp32(finetune_e) - fp32(base_e)).  A NaN or Inf in d fails the call with SMHIP_ERR_NONFINITE; the
+ *           outputs are then unspecified.
+ *        2. bits == 2, density in (0, 1]: k_keep and tau are those of smhip_ties_merge (step 2) with this one finetune at
+ *           this density, found by its selection kernels; an element is KEPT iff |d| >= tau and d != 0, every tie is kept.
+ *           bits == 1 (density must be 1): nothing is selected, EVERY element is kept, a zero delta included.
+ *        3. Planes, uint8 [R][ceil(C / 8)]: bit c % 8 of byte c / 8 of row r is element (r, c).  mask (bits == 2 only): set
+ *           iff kept.  sign: set iff kept and d < 0.  The padding bits of a row's last byte are 0.
+ *        4. Sums per row, fp64, in the row-wise order of step 2 of smhip_geo_merge: octet o of the row (columns 8 o ..
+ *           8 o + 7) goes to lane o % 256, a lane adds its elements in ascending order from +0, the 256 lanes are added by
+ *           the binary tree v[t] += v[t + s], s = 128, 64, ..., 1.  (double) of an fp32 value and the product of two are
+ *           exact.  A_r = sum over kept of |d|, Q_r = sum over kept of d^2, Z_r = sum over the others of d^2; c_r the
+ *           kept count and nz_r the count of d != 0, integers.  The totals A, Q, Z, c, nz are the rows' values added in
+ *           ascending row order from +0.
+ *        5. Scale.  scale_mode ROW: s_r = fp32(A_r / (double) c_r), +0 when c_r == 0; scale is float [R].  TENSOR:
+ *           s = fp32(A / (double) c) of the totals, +0 when c == 0; scale is float [1].  The mean of the kept magnitudes is
+ *           the scale that minimises sum over kept of (d - s sgn d)^2.
+ *        6. Residual, fp64, one IEEE operation at a time, no fused multiply-add:
+ *             e(A, Q, c, s) = max((Q - 2 (s A)) + c (s s), 0)
+ *           ROW: resid_sq = sum_r (Z_r + e(A_r, Q_r, c_r, s_r)) and delta_sq = sum_r (Q_r + Z_r), rows added in ascending
+ *           order from +0.  TENSOR: the same with the totals as the one row: resid_sq = Z + e(A, Q, c, s), delta_sq = Q + Z.
+ *        7. The report: rows, cols, bits, k_keep (n for bits == 1), threshold (tau; +inf when k_keep == 0, 0 for
+ *           bits == 1), kept = c, nonzero = nz, delta_sq, resid_sq.
+ *      APPLY, smhip_dpack_apply: a kept element gives round_to(dtype, fp32(base_e) + (sign ? -s_r : s_r)), one fp32 addition
+ *      and one round-to-nearest-even cast; an element that is not kept gives base_e bit for bit, a -0 included.  mask ==
+ *      NULL (a 1-bit pack): every element is kept.  Padding bits are not read as elements.
+ *      Every step is an exact order statistic, an integer function or one correctly rounded operation, there is no
+ *      floating-point atomic, and nothing depends on the grid or the device: both results are defined bit for bit.
+ *      n == 0: no plane has a byte, the scales are +0, the report is zero but for the threshold, apply is a no-op.
+ *      SMHIP_ERR_ARG: bits not 1 or 2, a density outside (0, 1], bits == 1 with density != 1, a bad scale_mode or dtype, a
+ *      null or misaligned pointer (mask is needed iff bits == 2), an output that overlaps an input, a tensor too large.
+ *      C % 8 == 0 with 16-byte aligned tensors moves them in 16-byte accesses; anything else goes element by element and is
+ *      as exact.  Pack synchronises the stream once, at its end; apply does not.  Profile names: "ties_hist",
+ *      "ties_select" (bits == 2), "dpack_pack", "geo_gram_fold", "dpack_scale"; "dpack_apply". ---- */
+enum { SMHIP_DPACK_ROW = 0, SMHIP_DPACK_TENSOR = 1 };
+typedef struct {
+    const void* finetune; const void* base; /* device, dtype, [rows][cols] */
+    int dtype;                              /* SMHIP_BF16 / F16 / F32 */
+    size_t rows, cols;
+    int bits;                               /* 1 or 2 */
+    double density;                         /* bits == 2: in (0, 1]; bits == 1: 1 */
+    int scale_mode;                         /* SMHIP_DPACK_ROW / SMHIP_DPACK_TENSOR */
+} smhip_dpack_desc;
+typedef struct {
+    uint64_t rows, cols;
+    int bits;
+    uint64_t k_keep;
+    float threshold;
+    uint64_t kept, nonzero;
+    double delta_sq, resid_sq;
+} smhip_dpack_report;
+/* sign, mask (bits == 2, else NULL): device uint8 [rows][ceil(cols / 8)].  scale: device float [rows] or [1].
+ * report (optional): HOST. */
+int smhip_dpack_pack(smhip_ctx* ctx, const smhip_dpack_desc* desc, uint8_t* sign, uint8_t* mask, float* scale,
+                     smhip_dpack_report* report, void* stream);
+typedef struct {
+    const void* base; int dtype;            /* device, [rows][cols] */
+    size_t rows, cols;
+    const uint8_t* sign; const uint8_t* mask; /* device; mask NULL: a 1-bit pack */
+    const float* scale; int scale_mode;
+} smhip_dpack_apply_desc;
+/* out: device, dtype, [rows][cols]; it must not overlap an input */
+int smhip_dpack_apply(smhip_ctx* ctx, const smhip_dpack_apply_desc* desc, void* out, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device

@@ -3,7 +3,8 @@ through the alias package): the merge entry point of the reference CLI
 (shard/__main__.py:78-158) with the same arguments and options; and `analyze CONFIG`,
 the per-tensor task-vector statistics of the same config (merge/analyze.py), which
 writes no tensor; and `extract-lora MODEL --base BASE --rank R --out DIR`, a PEFT LoRA adapter
-from a full finetune (merge/extract.py)."""
+from a full finetune (merge/extract.py); and `compress-delta MODEL --base BASE --out DIR`, a 1- or 2-bit delta
+pack from a full finetune (merge/compress.py)."""
 from __future__ import annotations
 
 import asyncio
@@ -153,6 +154,39 @@ def extract_lora_command(model: str, base: str, rank: int, out_dir: Path, storag
         raise click.Abort()
     click.echo(format_table(result))
     click.echo(f"adapter: {out_dir}")
+
+
+@cli.command("compress-delta")
+@click.argument("model", type=str)
+@click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the delta pack is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL and BASE live")
+@click.option("--bits", type=int, default=1, help="1: the sign of every delta; 2: a mask of the largest deltas and their signs")
+@click.option("--density", type=float, default=None, help="--bits 2: the share of the largest deltas to keep, in (0, 1]")
+@click.option("--scale", type=click.Choice(["row", "tensor"]), default="row", help="One scale per row of shape[0], or per tensor")
+@click.option("--modules", type=str, default=None, help="Pack only the modules whose name ends in one of these, comma-separated; the others are stored whole")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def compress_delta_command(model: str, base: str, out_dir: Path, storage_dir: Path, bits: int, density: Optional[float], scale: str,
+                           modules: Optional[str], device: str, verbose: bool):
+    """A delta pack of the full finetune MODEL on its base: one or two bits per weight and a scale per row.
+
+    DIR receives delta_model.safetensors, delta_config.json and compression.json (per tensor what was kept, the threshold
+    and the relative residual); it can be named as a finetune_merge entry of `merge` in place of MODEL.
+    """
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.compress import format_table, run_compression
+        from .merge.extract import parse_modules
+        result = asyncio.run(run_compression(model, base, out_dir, storage_dir, bits, density, scale, parse_modules(modules), device))
+    except Exception as exc:
+        logging.error(f"Error during compress-delta: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"delta pack: {out_dir}")
 
 
 if __name__ == "__main__":

@@ -338,6 +338,28 @@ class IsoGemmDesc(C.Structure):
                 ("ca", C.c_float), ("cb", C.c_float), ("c", C.c_void_p), ("ldc", C.c_int)]
 
 
+DPACK_ROW, DPACK_TENSOR = 0, 1                      # scale_mode of smhip_dpack_pack / smhip_dpack_apply
+DPACK_SCALE_MODES = {"row": DPACK_ROW, "tensor": DPACK_TENSOR}
+
+
+class DpackDesc(C.Structure):
+    """smhip_dpack_desc"""
+    _fields_ = [("finetune", C.c_void_p), ("base", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t),
+                ("bits", C.c_int), ("density", C.c_double), ("scale_mode", C.c_int)]
+
+
+class DpackReport(C.Structure):
+    """smhip_dpack_report"""
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("bits", C.c_int), ("k_keep", C.c_uint64), ("threshold", C.c_float),
+                ("kept", C.c_uint64), ("nonzero", C.c_uint64), ("delta_sq", C.c_double), ("resid_sq", C.c_double)]
+
+
+class DpackApplyDesc(C.Structure):
+    """smhip_dpack_apply_desc"""
+    _fields_ = [("base", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t),
+                ("sign", C.c_void_p), ("mask", C.c_void_p), ("scale", C.c_void_p), ("scale_mode", C.c_int)]
+
+
 DELLA_MAX_COLS = 32768         # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -426,6 +448,8 @@ class SmhipLibrary:
         d.smhip_iso_workspace.restype = C.c_size_t
         d.smhip_iso_merge.argtypes = [P, C.POINTER(IsoDesc), P, P, C.POINTER(IsoReport), P]
         d.smhip_iso_gemm.argtypes = [P, C.POINTER(IsoGemmDesc), P]
+        d.smhip_dpack_pack.argtypes = [P, C.POINTER(DpackDesc), P, P, P, C.POINTER(DpackReport), P]
+        d.smhip_dpack_apply.argtypes = [P, C.POINTER(DpackApplyDesc), P, P]
         d.smhip_debug_option.argtypes =[P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

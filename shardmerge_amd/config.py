@@ -176,7 +176,9 @@ A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
 base + s * lora_B @ lora_A applied to its own `base` (shardmerge_amd/adapter.py): embedding LoRA
 factors transposed, DoRA (use_dora) rows rescaled to their magnitude vector.  Same keys; no new
-option.
+option.  Or a delta pack directory (delta_config.json + delta_model.safetensors, written by
+`python -m shard compress-delta`): the entry then stands for its `base` plus or minus a scale per
+row where the pack's planes keep an element (shardmerge_amd/deltapack.py).  Same keys; no new option.
 """
 from __future__ import annotations
 

@@ -607,6 +607,70 @@ int smhip_cabs_merge(smhip_ctx* ctx, const smhip_cabs_desc* d, void* out, float*
     SM_FINISH(ctx, ctx->pipe.delta.cabs_merge(*d, out, delta_out, mask_out, report));
 }
 
+}  // extern "C"
+
+// what smhip_dpack_pack and smhip_dpack_apply share: the shape, the dtype and the tensors' spans ({pointer, bytes,
+// alignment}; ins are read, outs written).  n == 0: only the shape and the dtype are checked
+struct dpack_span { const void* p; size_t bytes, align; };
+static int dpack_check(smhip_ctx* ctx, const char* op, int dtype, size_t rows, size_t cols, int scale_mode,
+                       std::initializer_list<dpack_span> ins, std::initializer_list<dpack_span> outs) {
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + what); };
+    if (dtype < SMHIP_BF16 || dtype > SMHIP_F32) return bad("bad dtype");
+    if (scale_mode != SMHIP_DPACK_ROW && scale_mode != SMHIP_DPACK_TENSOR) return bad("bad scale_mode");
+    if (rows && cols > ((size_t)1 << 40) / rows) return bad("tensor too large");
+    for (const dpack_span& o : outs) {
+        if (!o.bytes) continue;
+        if (!o.p) return bad("null pointer");
+        if ((uintptr_t)o.p % o.align) return bad("a pointer is not aligned to its element size");
+        for (const dpack_span& i : ins)
+            if (i.p && i.bytes && (uintptr_t)i.p < (uintptr_t)o.p + o.bytes && (uintptr_t)o.p < (uintptr_t)i.p + i.bytes)
+                return bad("an output overlaps an input");
+        for (const dpack_span& q : outs)
+            if (q.p != o.p && q.bytes && (uintptr_t)q.p < (uintptr_t)o.p + o.bytes && (uintptr_t)o.p < (uintptr_t)q.p + q.bytes)
+                return bad("two outputs overlap");
+    }
+    for (const dpack_span& i : ins) {
+        if (!i.bytes) continue;
+        if (!i.p) return bad("null pointer");
+        if ((uintptr_t)i.p % i.align) return bad("a pointer is not aligned to its element size");
+    }
+    return SMHIP_OK;
+}
+
+extern "C" {
+
+int smhip_dpack_pack(smhip_ctx* ctx, const smhip_dpack_desc* d, uint8_t* sign, uint8_t* mask, float* scale,
+                     smhip_dpack_report* report, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("dpack_pack: ") + what); };
+    if (!d) return bad("null descriptor");
+    if (d->bits != 1 && d->bits != 2) return bad("bits must be 1 or 2");
+    if (!(d->density > 0.0 && d->density <= 1.0)) return bad("density must be in (0, 1]");
+    if (d->bits == 1 && d->density != 1.0) return bad("bits == 1 needs density == 1");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols, plane = d->rows * ((d->cols + 7) / 8);
+    const size_t ns = d->scale_mode == SMHIP_DPACK_TENSOR ? 1 : d->rows;
+    if (d->bits == 1 && mask) return bad("a mask with bits == 1");
+    if (int rc = dpack_check(ctx, "dpack_pack", d->dtype, d->rows, d->cols, d->scale_mode,
+                             {{d->finetune, n * es, es}, {d->base, n * es, es}},
+                             {{sign, plane, 1}, {mask, d->bits == 2 ? plane : 0, 1}, {scale, ns * 4, 4}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.dpack_pack(*d, sign, mask, scale, report));
+}
+
+int smhip_dpack_apply(smhip_ctx* ctx, const smhip_dpack_apply_desc* d, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "dpack_apply: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols, plane = n ? d->rows * ((d->cols + 7) / 8) : 0;
+    const size_t ns = !n ? 0 : (d->scale_mode == SMHIP_DPACK_TENSOR ? 1 : d->rows);
+    if (int rc = dpack_check(ctx, "dpack_apply", d->dtype, d->rows, d->cols, d->scale_mode,
+                             {{d->base, n * es, es}, {d->sign, plane, 1}, {d->mask, d->mask ? plane : 0, 1}, {d->scale, ns * 4, 4}},
+                             {{out, n * es, es}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.dpack_apply(*d, out));
+}
+
 int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
                     int base_out_dtype, double lambda, void* out, float* delta_out, void* stream) {
     SM_GUARD(ctx);

@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics and the low-rank extraction (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction and the delta pack (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -29,6 +29,7 @@
 #include "sm_widen.hpp"
 #include "sm_cabs.hpp"
 #include "sm_iso.hpp"
+#include "sm_dpack.hpp"
 
 namespace smhip {
 
@@ -141,6 +142,11 @@ SM_KERNEL_TAG_LB(KIsoResid, IsoReduceParams, "iso_resid", k_iso_reduce<ISO_RED_R
 SM_KERNEL_TAG_LB(KIsoDot, IsoReduceParams, "iso_dot", k_iso_reduce<ISO_RED_DOT>(ex, p), GEO_THREADS, 4)
 SM_KERNEL_TAG_LB(KIsoScale, IsoScaleParams, "iso_scale", k_iso_scale(ex, p), 256, 4)
 SM_KERNEL_TAG_LB(KIsoApply, IsoApplyParams, "iso_apply", k_iso_apply(ex, p), 256, 4)
+// Delta pack (sm_dpack.hpp): the fused pass over whole rows (planes, ordered fp64 sums), the scales, the streaming apply;
+// its selection is ties_hist / ties_select and its folds are geo_gram_fold
+SM_KERNEL_TAG_LB(KDpackPack, DpackPackParams, "dpack_pack", k_dpack_pack(ex, p), DPACK_THREADS, 4)
+SM_KERNEL_TAG_LB(KDpackScale, DpackScaleParams, "dpack_scale", k_dpack_scale(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KDpackApply, DpackApplyParams, "dpack_apply", k_dpack_apply(ex, p), 256, 4)
 // the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
 #define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
     X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
@@ -154,6 +160,7 @@ SM_KERNEL_TAG_LB(KIsoApply, IsoApplyParams, "iso_apply", k_iso_apply(ex, p), 256
 #define SM_SIDE_KERNELS_13(X) X(KWidenColstats) X(KWidenColfold) X(KWidenRank) X(KWidenCoef) X(KWidenCombine) X(KWidenCombineAny)
 #define SM_SIDE_KERNELS_14(X) X(KCabsMerge) X(KCabsMergeAny)
 #define SM_SIDE_KERNELS_15(X) X(KIsoGemmNT) X(KIsoGemmNN) X(KIsoSum) X(KIsoTranspose) X(KIsoNorm) X(KIsoResid) X(KIsoDot) X(KIsoScale) X(KIsoApply)
+#define SM_SIDE_KERNELS_16(X) X(KDpackPack) X(KDpackScale) X(KDpackApply)
 
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
@@ -1735,6 +1742,82 @@ class DeltaHost {
     int iso_gemm_probe(const smhip_iso_gemm_desc& d) {
         iso_gemm(d.form, d.sym, d.a, d.lda, d.b, d.ldb, d.M, d.N, d.K, d.epilogue, d.ca, d.cb, d.e, d.lde, d.c, d.ldc);
         be.sync(stream);
+        return SMHIP_OK;
+    }
+
+    // ---- Delta pack (sm_dpack.hpp; smhip_dpack_pack, smhip_dpack_apply).  bits == 2: the threshold through the shared
+    // select path with one finetune (TIES's kernels, unchanged), then in both cases the fused pass, the fold of the rows'
+    // partials, the scales (of the rows, or of the one row of the totals), the fold of their terms, ONE readback.
+    // Workspace: [the histograms |] DpackHead | the rows' partials [R][5] | the rows' terms [max(R, 1)][2] ----
+    struct DpackHead { RadixState state[TIES_MAX_MODELS]; TiesReadback rb; double tot[DPACK_NP]; double T[DPACK_NT]; };
+    static int dpack_row_vec(size_t C, const void* a, const void* b) { return (C % 8 == 0 && aligned16(a) && aligned16(b)) ? 1 : 0; }
+    int dpack_pack(const smhip_dpack_desc& d, uint8_t* sign, uint8_t* mask, float* scale, smhip_dpack_report* rep) {
+        const size_t R = d.rows, C = d.cols, n = R * C, PB = (C + 7) / 8;
+        const bool tensor = d.scale_mode == SMHIP_DPACK_TENSOR;
+        const unsigned long long k_keep = d.bits == 1 ? (unsigned long long)n : delta_k_keep(d.density, n);
+        if (rep) {
+            *rep = smhip_dpack_report{};
+            rep->rows = R; rep->cols = C; rep->bits = d.bits; rep->k_keep = k_keep;
+            rep->threshold = (d.bits == 2 && k_keep == 0) ? INFINITY : 0.f;
+        }
+        if (n == 0) {                                    // no plane has a byte; the scales are +0
+            const size_t ns = tensor ? 1 : R;
+            if (ns) be.memset(scale, 0, ns * sizeof(float), stream);
+            return SMHIP_OK;
+        }
+        const size_t part_bytes = round_up(R * DPACK_NP * sizeof(double), 256), terms_bytes = R * DPACK_NT * sizeof(double);
+        DpackHead* w;
+        size_t off = round_up(sizeof(DpackHead), 256);
+        int rc;
+        if (d.bits == 2) rc = select_workspace(TIES_MAX_MODELS, w, part_bytes + terms_bytes, &off);
+        else rc = plain_workspace(w, off + part_bytes + terms_bytes);
+        if (rc) return rc;
+        double* part = (double*)ws_at(off);
+        double* terms = (double*)ws_at(off + part_bytes);
+
+        if (d.bits == 2) {
+            TiesInputs in;
+            const void* ft[1] = {d.finetune};
+            const void* bs[1] = {d.base};
+            ties_inputs(in, 1, d.dtype, n, ft, bs, true);
+            ties_thresholds(in, k_keep, w);
+        }
+        DpackPackParams p;
+        p.ft = d.finetune; p.base = d.base; p.dtype = d.dtype;
+        p.R = R; p.C = C; p.PB = PB; p.bits = d.bits; p.threshold = w->rb.threshold;
+        p.sign = sign; p.mask = mask; p.row_vec = dpack_row_vec(C, d.finetune, d.base);
+        p.part = part; p.flags = w->rb.flags;
+        be.template launch<KDpackPack>((int)std::min<size_t>(R, (size_t)1 << 20), DPACK_THREADS, dpack_pack_lds_floats() * 4, p, stream);
+
+        GeoFoldParams f;
+        f.np = DPACK_NP; f.nseg = R; f.part = part; f.G = w->tot;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        DpackScaleParams s;
+        s.rows = tensor ? 1 : R; s.part = tensor ? w->tot : part; s.scale = scale; s.terms = terms;
+        be.template launch<KDpackScale>((int)((s.rows + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, s, stream);
+        f.np = DPACK_NT; f.nseg = s.rows; f.part = terms; f.G = w->T;
+        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+
+        DpackHead host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the report stays as it is)
+        if (host.rb.flags[0]) return fail(SMHIP_ERR_NONFINITE, "dpack_pack: NaN or Inf in finetune - base");
+        if (rep) {
+            if (d.bits == 2) rep->threshold = host.rb.threshold[0];
+            rep->kept = (uint64_t)host.tot[3]; rep->nonzero = (uint64_t)host.tot[4];
+            rep->resid_sq = host.T[0]; rep->delta_sq = host.T[1];
+        }
+        return SMHIP_OK;
+    }
+    int dpack_apply(const smhip_dpack_apply_desc& d, void* out) {
+        const size_t R = d.rows, C = d.cols, PB = (C + 7) / 8;
+        if (R * C == 0) return SMHIP_OK;
+        DpackApplyParams p;
+        p.base = d.base; p.dtype = d.dtype; p.R = R; p.C = C; p.PB = PB; p.units = R * PB;
+        p.sign = d.sign; p.mask = d.mask; p.scale = d.scale; p.scale_mode = d.scale_mode == SMHIP_DPACK_TENSOR ? DPACK_TENSOR : DPACK_ROW;
+        p.out = out; p.row_vec = dpack_row_vec(C, d.base, out);
+        p.chunks = pick_chunks(p.units, 256, 2, 8);
+        be.template launch<KDpackApply>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         return SMHIP_OK;
     }
 

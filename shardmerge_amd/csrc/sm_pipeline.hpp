@@ -228,7 +228,7 @@ SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finis
     X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
     X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
     X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
-#define SM_SIDE_GROUPS 16        // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics; 9: the low-rank extraction; 10: the pairwise fusion; 11: the PCB merge; 12: the TSV merge; 13: the WIDEN merge; 14: the CABS merge; 15: the Iso-C merge
+#define SM_SIDE_GROUPS 17        // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics; 9: the low-rank extraction; 10: the pairwise fusion; 11: the PCB merge; 12: the TSV merge; 13: the WIDEN merge; 14: the CABS merge; 15: the Iso-C merge; 16: the delta pack
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {

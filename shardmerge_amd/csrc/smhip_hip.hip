@@ -31,6 +31,7 @@ SM_SIDE_KERNELS_12(SM_DECL_EXTERN)
 SM_SIDE_KERNELS_13(SM_DECL_EXTERN)
 SM_SIDE_KERNELS_14(SM_DECL_EXTERN)
 SM_SIDE_KERNELS_15(SM_DECL_EXTERN)
+SM_SIDE_KERNELS_16(SM_DECL_EXTERN)
 SM_FFT_KERNELS_OF(SM_DECL_EXTERN, DynPlan)
 #undef SM_DECL_EXTERN
 

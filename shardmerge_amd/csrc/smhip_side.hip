@@ -1,5 +1,5 @@
 // smhip_side.hip - explicit instantiation of one group of kernels, selected with -DSM_SIDE_GROUP=<g>
-// (SM_SIDE_KERNELS_<g>: groups 0..2 in sm_pipeline.hpp, 7..15 in sm_delta_host.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction, 10: the pairwise fusion, 11: the PCB merge, 12: the TSV merge, 13: the WIDEN merge, 14: the CABS merge, 15: the Iso-C merge).
+// (SM_SIDE_KERNELS_<g>: groups 0..2 in sm_pipeline.hpp, 7..16 in sm_delta_host.hpp; groups 3..6: the transform kernels for run-time planned lengths, 7: the delta and geometric merges, 8: the task-vector statistics, 9: the low-rank extraction, 10: the pairwise fusion, 11: the PCB merge, 12: the TSV merge, 13: the WIDEN merge, 14: the CABS merge, 15: the Iso-C merge, 16: the delta pack).
 #include "smhip_device.hpp"
 
 namespace smhip {
@@ -36,7 +36,9 @@ SM_SIDE_KERNELS_13(SM_INST)
 SM_SIDE_KERNELS_14(SM_INST)
 #elif SM_SIDE_GROUP == 15
 SM_SIDE_KERNELS_15(SM_INST)
+#elif SM_SIDE_GROUP == 16
+SM_SIDE_KERNELS_16(SM_INST)
 #else
-#error "SM_SIDE_GROUP must be 0..15"
+#error "SM_SIDE_GROUP must be 0..16"
 #endif
 }  // namespace smhip

@@ -39,6 +39,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .adapter import ADAPTER_CONFIG, ADAPTER_WEIGHTS, is_adapter_dir, read_header
+from .deltapack import is_pack_dir, pack_identity
 from .config import MergeConfig
 from .constants import DEFAULT_NORM_MODE, INPUT_LAYER, OUTPUT_LAYER
 from .index import LocalModelIndex
@@ -185,6 +186,10 @@ def config_stamp(config: MergeConfig) -> str:
                                  "adapter_header": hashlib.sha256(read_header(path / ADAPTER_WEIGHTS)[0]).hexdigest()}
     if adapters:
         doc["adapters"] = adapters
+    packs = {m.model: pack_identity(Path(config.storage_path) / m.model) for m in config.finetune_merge
+             if is_pack_dir(Path(config.storage_path) / m.model)}          # a delta pack's: its config and its tensors' header
+    if packs:
+        doc["delta_packs"] = packs
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 
@@ -372,12 +377,12 @@ async def run_partitioned_merge(config: MergeConfig, index: LocalModelIndex, dev
     def out_shape(s: str, name: str) -> List[int]:
         sl = ShardLayer(rank_of[name], s, name, False)
         if fourier and sl.layer_number in (INPUT_LAYER, OUTPUT_LAYER):
-            uri = merger._layer_requests(sl)[0][0]
+            uri, tname = merger._layer_requests(sl)[0]      # (a delta pack's whole tensor is stored under <name>.full)
             if uri != base_uri:
-                f = index.model_indexes[uri]["weight_map"][name]
+                f = index.model_indexes[uri]["weight_map"][tname]
                 if (uri, f) not in provider_meta:
                     provider_meta[(uri, f)] = _tensor_meta(index, uri, f)
-                return list(provider_meta[(uri, f)][name][0])
+                return list(provider_meta[(uri, f)][tname][0])
         return list(metas[s][name][0])
 
     names, costs, groups = [], [], []

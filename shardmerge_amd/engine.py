@@ -228,6 +228,33 @@ class DeltaStatsReport:
 
 
 @dataclass
+class DeltaPackReport:
+    rows: int = 0                                                    # R: shape[0] (1 for a 0-D or 1-D tensor)
+    cols: int = 0                                                    # C: the rest
+    bits: int = 1
+    density: float = 1.0
+    scale: str = "row"
+    k_keep: int = 0                                                  # elements the trim asks for (n for bits == 1)
+    threshold: float = 0.0                                           # tau (+inf: nothing kept; 0 for bits == 1)
+    kept: int = 0                                                    # elements with a sign bit (ties at tau included)
+    nonzero: int = 0                                                 # elements where the finetune differs from its base
+    delta_sq: float = 0.0                                            # ||finetune - base||^2 (fp64, ordered)
+    resid_sq: float = 0.0                                            # ||finetune - base - unpacked||^2 before the rounding of apply
+
+    @property
+    def rel_residual(self) -> float:
+        """||d - q|| / ||d||, 0 for a zero delta"""
+        return math.sqrt(self.resid_sq / self.delta_sq) if self.delta_sq > 0.0 else 0.0
+
+
+def _shape_rows(t: torch.Tensor) -> Tuple[int, int]:
+    """the delta pack's view of a tensor: R = shape[0] rows of the rest; a 0-D or 1-D tensor is one row"""
+    if t.ndim <= 1:
+        return 1, t.numel()
+    return t.shape[0], math.prod(t.shape[1:])
+
+
+@dataclass
 class LoraExtractReport:
     rows: int = 0
     cols: int = 0
@@ -535,6 +562,72 @@ class Engine:
         bs = self._dev(base).contiguous()
         av, bv = self._dev(a, fdtype).contiguous(), self._dev(b, fdtype).contiguous()
         return rows, cols, rank, bs, av, bv, fdtype
+
+    # -- the delta pack ----------------------------------------------------------------------
+    def delta_pack(self, finetune: torch.Tensor, base: torch.Tensor, *, bits: int = 1, density: float = 1.0,
+                   scale: str = "row", name: str = ""):
+        """One tensor's delta ``finetune - base`` as bit planes and scales (``smhip_dpack_pack``; the function is stated
+        in include/shardmerge_hip.h).  bits = 1: the sign of every delta; bits = 2: a mask of its ``density`` largest
+        magnitudes (the trim of ``ties_merge``, ties kept) and their signs.  scale: "row", the mean kept magnitude of
+        each row of ``shape[0]``, or "tensor", one for all.  Returns ``(sign, mask | None, scale, DeltaPackReport)``:
+        uint8 planes [R, ceil(C / 8)] and a float32 [R] or [1].  A NaN or Inf in the delta raises ValueError naming
+        ``name``."""
+        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (1, 2):
+            raise ValueError(f"delta_pack: bits must be 1 or 2, not {bits!r}")
+        if isinstance(density, bool) or not isinstance(density, (int, float)) or not (0.0 < float(density) <= 1.0):
+            raise ValueError(f"delta_pack: density {density!r} is not in (0, 1]")
+        if bits == 1 and float(density) != 1.0:
+            raise ValueError(f"delta_pack: bits = 1 keeps every sign, density must be 1, not {density!r}")
+        if scale not in _lib.DPACK_SCALE_MODES:
+            raise ValueError(f"delta_pack: scale must be 'row' or 'tensor', not {scale!r}")
+        if finetune.shape != base.shape:
+            raise ValueError(f"delta_pack: shape mismatch in {name or 'tensor'}: {list(finetune.shape)} / {list(base.shape)}")
+        in_dtype = finetune.dtype if finetune.dtype == base.dtype and finetune.dtype in _DTYPE_CODE else torch.float32
+        ft, bs = self._dev(finetune, in_dtype), self._dev(base, in_dtype)
+        rows, cols = _shape_rows(ft)
+        pb = (cols + 7) // 8
+        sign = torch.empty((rows, pb), dtype=torch.uint8, device=self.device)
+        mask = torch.empty((rows, pb), dtype=torch.uint8, device=self.device) if bits == 2 else None
+        sc = torch.empty((rows if scale == "row" else 1,), dtype=torch.float32, device=self.device)
+        desc = _lib.DpackDesc(ft.data_ptr(), bs.data_ptr(), _DTYPE_CODE[in_dtype], rows, cols, bits, float(density),
+                              _lib.DPACK_SCALE_MODES[scale])
+        rep = _lib.DpackReport()
+        try:
+            self.ctx.check(self.lib.dll.smhip_dpack_pack(self.ctx.h, C.byref(desc), sign.data_ptr(),
+                                                         mask.data_ptr() if mask is not None else None, sc.data_ptr(),
+                                                         C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {name or 'tensor'}: {e.message}") from e
+            raise
+        return sign, mask, sc, DeltaPackReport(rows=rows, cols=cols, bits=bits, density=float(density), scale=scale,
+                                               k_keep=int(rep.k_keep), threshold=float(rep.threshold), kept=int(rep.kept),
+                                               nonzero=int(rep.nonzero), delta_sq=float(rep.delta_sq),
+                                               resid_sq=float(rep.resid_sq))
+
+    def delta_apply(self, base: torch.Tensor, sign: torch.Tensor, mask: Optional[torch.Tensor], scale: torch.Tensor) -> torch.Tensor:
+        """the finetune tensor a delta pack defines: ``base + s`` or ``base - s`` where an element is kept, one fp32
+        addition rounded once into base's dtype, and ``base`` bit for bit elsewhere (``smhip_dpack_apply``).  mask None:
+        a 1-bit pack, every element is kept.  scale: float32 [R] (per row) or [1] (per tensor)."""
+        if base.dtype not in _DTYPE_CODE:
+            raise ValueError(f"delta_apply: base is {base.dtype}; bf16, f16 or f32 expected")
+        rows, cols = _shape_rows(base)
+        pb = (cols + 7) // 8
+        for what, t in (("sign", sign), ("mask", mask)):
+            if t is None:
+                continue
+            if t.dtype != torch.uint8 or tuple(t.shape) != (rows, pb):
+                raise ValueError(f"delta_apply: {what} is {t.dtype} {list(t.shape)}; uint8 [{rows}, {pb}] expected for base {list(base.shape)}")
+        if scale.dtype != torch.float32 or scale.ndim != 1 or scale.shape[0] not in (1, rows):
+            raise ValueError(f"delta_apply: scale is {scale.dtype} {list(scale.shape)}; float32 [{rows}] or [1] expected")
+        mode = _lib.DPACK_ROW if scale.shape[0] == rows else _lib.DPACK_TENSOR
+        bs, sg, sc = self._dev(base), self._dev(sign), self._dev(scale)
+        mk = self._dev(mask) if mask is not None else None
+        out = torch.empty_like(bs)
+        desc = _lib.DpackApplyDesc(bs.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols, sg.data_ptr(),
+                                   mk.data_ptr() if mk is not None else None, sc.data_ptr(), mode)
+        self._call(self.lib.dll.smhip_dpack_apply(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()))
+        return out
 
     # -- extract-lora ------------------------------------------------------------------------
     def lora_extract(self, finetune: torch.Tensor, base: torch.Tensor, rank: int, *, power_iters: int = 2,

@@ -22,6 +22,7 @@ import torch
 from safetensors import safe_open
 
 from .adapter import ADAPTER_BIN, AdapterError, LoraAdapter, is_adapter_dir, is_bin_only_adapter_dir
+from .deltapack import DeltaPack, is_pack_dir
 
 logger = logging.getLogger(__name__)
 
@@ -66,6 +67,7 @@ class LocalModelIndex:
         self.model_indexes: Dict[str, Dict] = {}
         self._ordered_weights: Dict[str, List[str]] = {}
         self.adapters: Dict[str, LoraAdapter] = {}     # LoRA adapter directories (adapter.py), by model uri
+        self.packs: Dict[str, DeltaPack] = {}          # delta pack directories (deltapack.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -78,6 +80,15 @@ class LocalModelIndex:
             self.model_indexes[model_uri] = {"metadata": {}, "weight_map": adapter.weight_map()}
             self._ordered_weights[model_uri] = sorted(adapter.weight_map())
             logger.info(f"Model {model_uri}: LoRA adapter, {len(adapter.pairs)} targeted tensors")
+            return
+        if is_pack_dir(self.storage_path / model_uri):
+            # a delta pack: its planes, scales and whole tensors load through the same weight map as a model's tensors
+            pack = DeltaPack(model_uri, self.storage_path / model_uri)
+            self.packs[model_uri] = pack
+            self.model_indexes[model_uri] = {"metadata": {}, "weight_map": pack.weight_map()}
+            self._ordered_weights[model_uri] = sorted(pack.weight_map())
+            n_packed = sum(t.kind == "packed" for t in pack.tensors.values())
+            logger.info(f"Model {model_uri}: {pack.bits}-bit delta pack, {n_packed} packed and {len(pack.tensors) - n_packed} whole tensors")
             return
         if is_bin_only_adapter_dir(self.storage_path / model_uri):
             raise AdapterError(f"LoRA adapter {model_uri}: only {ADAPTER_BIN} found; adapters are read from "
@@ -94,6 +105,10 @@ class LocalModelIndex:
     def adapter(self, model_uri: str) -> Optional[LoraAdapter]:
         """the LoRA adapter registered under this uri, None for a full model"""
         return self.adapters.get(model_uri)
+
+    def pack(self, model_uri: str) -> Optional[DeltaPack]:
+        """the delta pack registered under this uri, None for a full model or an adapter"""
+        return self.packs.get(model_uri)
 
     def _require(self, model_uri: str, tensor_name: Optional[str] = None) -> Dict:
         if model_uri not in self.model_indexes:

@@ -45,8 +45,18 @@ class MergeTensorsBase(ABC):
         return self._engine
 
     def _finetune_requests(self, m: MergeModel, layer_name: str) -> List[Tuple[str, str]]:
-        """the (uri, tensor) reads `finetune_tensor` makes for entry m: the model's tensor, or for a LoRA adapter entry
-        its base's tensor and, when the adapter targets it, the two factors"""
+        """the (uri, tensor) reads `finetune_tensor` makes for entry m: the model's tensor; for a LoRA adapter entry its
+        base's tensor and, when the adapter targets it, the two factors; for a delta pack entry its base's tensor and
+        the planes and scale, the tensor the pack stores whole, or the base's tensor alone"""
+        pack = self.index_manager.pack(m.model)
+        if pack is not None:
+            t = pack.tensors.get(layer_name)
+            if t is None:
+                return [(m.base, layer_name)]
+            if t.kind == "full":
+                return [(m.model, t.full_key)]
+            return [(m.base, layer_name), (m.model, t.sign_key), (m.model, t.scale_key)] + \
+                ([(m.model, t.mask_key)] if t.mask_key is not None else [])
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return [(m.model, layer_name)]
@@ -60,11 +70,25 @@ class MergeTensorsBase(ABC):
         """THE finetune tensor of entry m - every operator and the partitioned path resolve finetunes here.  A full
         model's own tensor; for a LoRA adapter entry (adapter.py) base + s * B @ A rounded once into the base's dtype
         on the engine (embedding factors transposed; DoRA rows scaled to their magnitudes, where a zero or non-finite
-        row norm raises AdapterError), or the base tensor itself where the adapter does not target it.
+        row norm raises AdapterError), or the base tensor itself where the adapter does not target it.  For a delta
+        pack entry (deltapack.py) `Engine.delta_apply` on the base tensor and the planes, the tensor the pack stores
+        whole, or the base tensor itself where the pack holds nothing for it.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
                 return await self._fetch(uri, tname, device)
+        pack = self.index_manager.pack(m.model)
+        if pack is not None:
+            t = pack.tensors.get(layer_name)
+            if t is not None and t.kind == "full":
+                return await fetch(m.model, t.full_key)
+            base = await fetch(m.base, layer_name)
+            if t is None:
+                return base
+            sign = await fetch(m.model, t.sign_key)
+            scale = await fetch(m.model, t.scale_key)
+            mask = await fetch(m.model, t.mask_key) if t.mask_key is not None else None
+            return self.engine(device).delta_apply(base, sign, mask, scale)
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return await fetch(m.model, layer_name)
@@ -124,7 +148,15 @@ class MergeTensorsBase(ABC):
                     raise ValueError(f"{m.model}: the base of a LoRA adapter entry must be a full model, {m.base} is an adapter")
                 from ..adapter import base_tensor_meta
                 adapter.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
-            keys = self.index_manager.get_model_keys(m.base if adapter is not None else m.model)
+            pack = self.index_manager.pack(m.model)
+            if pack is not None:
+                # a pack's finetune has its base's tensors too: check what it stores against the base's shard headers
+                if self.index_manager.pack(m.base) is not None or self.index_manager.adapter(m.base) is not None:
+                    kind = "a delta pack" if self.index_manager.pack(m.base) is not None else "an adapter"
+                    raise ValueError(f"{m.model}: the base of a delta pack entry must be a full model, {m.base} is {kind}")
+                from ..adapter import base_tensor_meta
+                pack.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
+            keys = self.index_manager.get_model_keys(m.base if adapter is not None or pack is not None else m.model)
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)

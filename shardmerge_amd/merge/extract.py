@@ -72,6 +72,9 @@ class LoraExtraction:
             path = self.storage_dir / uri
             if is_adapter_dir(path) or is_bin_only_adapter_dir(path):
                 raise ValueError(f"extract-lora: {uri} is itself an adapter directory; a full model is expected")
+            from ..deltapack import is_pack_dir
+            if is_pack_dir(path):
+                raise ValueError(f"extract-lora: {uri} is a delta pack directory; a full model is expected")
         if (self.out_dir / ADAPTER_WEIGHTS).exists() or (self.out_dir / ADAPTER_CONFIG).exists():
             raise ValueError(f"extract-lora: {self.out_dir} already holds an adapter; it is not overwritten")
         if self.index_manager is None:

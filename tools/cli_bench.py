@@ -4,10 +4,13 @@ writes base + K finetunes with Llama-3-8B block shapes under a RAM-backed direct
 runs the CLI's merge with the prefetching loader on and off and prints one JSON line per run
 (wall time includes reading the safetensors shards, H2D, the merge, D2H and writing the output).
 
-    python tools/cli_bench.py [--blocks 4] [--k 2] [--root /dev/shm/smcli] [--device cuda] [--lora-rank R]
+    python tools/cli_bench.py [--blocks 4] [--k 2] [--root /dev/shm/smcli] [--device cuda] [--lora-rank R] [--delta-bits B]
 
 --lora-rank R writes every finetune as a LoRA adapter of rank R instead (adapter_config.json +
 adapter_model.safetensors, every 2-D block projection targeted); input_GB is then what the run reads.
+--delta-bits B (1 or 2; 2 at --delta-density) compresses every full finetune into a delta pack with `compress-delta`'s
+driver and runs every merge twice: with the full finetunes, then with the packs in their place ("finetunes": "full" /
+"delta"), input_GB being what each run reads.
 """
 import argparse
 import asyncio
@@ -108,7 +111,11 @@ def main():
                     help="block shapes; llama3-70b with --k 3 is the metric's configuration (1.7 GB of bf16 per block and model)")
     ap.add_argument("--runs", default="0,1,0,1", help="SHARDMERGE_PREFETCH value of each run")
     ap.add_argument("--lora-rank", type=int, default=0, help="write the finetunes as LoRA adapters of this rank")
+    ap.add_argument("--delta-bits", type=int, default=0, choices=[0, 1, 2], help="also run with the finetunes as delta packs of this many bits")
+    ap.add_argument("--delta-density", type=float, default=0.25, help="--delta-bits 2: the density of the packs")
     args = ap.parse_args()
+    if args.delta_bits and args.lora_rank:
+        sys.exit("cli_bench: --delta-bits compresses full finetunes; it does not combine with --lora-rank")
     from shardmerge_amd.constants import tune_hip_queues
     tune_hip_queues()
     root = Path(args.root)
@@ -118,41 +125,57 @@ def main():
     t0 = time.time()
     cfg_path, n_params = write_models(root, args.blocks, args.k, args.device if torch.cuda.is_available() else "cpu", args.model,
                                      args.lora_rank)
-    read_bytes = sum(f.stat().st_size for f in (root / "storage").rglob("*.safetensors"))
+    size_of = lambda uri: sum(f.stat().st_size for f in (root / "storage" / uri).rglob("*.safetensors"))
+    uris = [f"org/ft{i}" for i in range(1, args.k + 1)]
+    configs = [("full", cfg_path, size_of("org/base") + sum(size_of(u) for u in uris))]
+    if args.delta_bits:
+        from shardmerge_amd.merge.compress import run_compression
+        t1 = time.time()
+        for u in uris:
+            asyncio.run(run_compression(u, "org/base", root / "storage" / (u + "_delta"), root / "storage", args.delta_bits,
+                                        args.delta_density if args.delta_bits == 2 else None, device=args.device))
+        doc = yaml.safe_load(open(cfg_path))
+        for m in doc["finetune_merge"]:
+            m["model"] += "_delta"
+        delta_cfg = root / "merge_delta.yaml"
+        yaml.safe_dump(doc, open(delta_cfg, "w"))
+        configs.append(("delta", delta_cfg, size_of("org/base") + sum(size_of(u + "_delta") for u in uris)))
+        print(f"# compressed {args.k} finetunes to {args.delta_bits} bit(s) in {time.time() - t1:.1f} s", file=sys.stderr)
     print(f"# wrote {args.k + 1} models, {n_params / 1e6:.0f} M params each, in {time.time() - t0:.1f} s under {root}", file=sys.stderr)
 
     from shardmerge_amd.__main__ import run_merge
     from shardmerge_amd.config import MergeConfig
     from shardmerge_amd import iostats
-    for prefetch in args.runs.split(","):
-        inplace = prefetch.endswith("i")              # "1i": prefetch on + in-place output shards (SHARDMERGE_INPLACE)
-        prefetch = prefetch.rstrip("i")
-        os.environ["SHARDMERGE_INPLACE"] = "1" if inplace else "0"
-        os.environ["SHARDMERGE_PREFETCH"] = prefetch
-        out_dir = root / "merged"
-        if out_dir.exists():
-            shutil.rmtree(out_dir)
-        config = MergeConfig.from_yaml(cfg_path)
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-        iostats.snapshot(reset=True)
-        t0 = time.time()
-        asyncio.run(run_merge(config, args.device, clean_cache=False))
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-        dt = time.time() - t0
-        st = iostats.snapshot(reset=True)
-        in_gb, out_gb = read_bytes / 1e9, 2.0 * n_params / 1e9
-        rec = {"cli_merge": "end to end", "model": args.model, "lora_rank": args.lora_rank, "prefetch": prefetch == "1", "inplace_shards": inplace, "blocks": args.blocks, "k": args.k,
-               "params": n_params, "seconds": round(dt, 3), "merged_GBps": round(out_gb / dt, 3), "input_GB": round(in_gb, 2),
-               "stages": st}
-        # what the PCIe link allows: every input byte crosses it once, every output byte once, at the H2D rate
-        # measured on the copy stream in this run (the two directions are separate lanes: max, not sum)
-        h2d = st.get("h2d", {}).get("GBps")
-        if h2d:
-            rec["pcie_bound_merged_GBps"] = round(out_gb / (max(in_gb, out_gb) / h2d), 3)
-            rec["fraction_of_pcie_bound"] = round(rec["merged_GBps"] / rec["pcie_bound_merged_GBps"], 3)
-        print(json.dumps(rec))
+    for kind, path, read_bytes in configs:
+        for prefetch in args.runs.split(","):
+            inplace = prefetch.endswith("i")              # "1i": prefetch on + in-place output shards (SHARDMERGE_INPLACE)
+            prefetch = prefetch.rstrip("i")
+            os.environ["SHARDMERGE_INPLACE"] = "1" if inplace else "0"
+            os.environ["SHARDMERGE_PREFETCH"] = prefetch
+            out_dir = root / "merged"
+            if out_dir.exists():
+                shutil.rmtree(out_dir)
+            config = MergeConfig.from_yaml(path)
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+            iostats.snapshot(reset=True)
+            t0 = time.time()
+            asyncio.run(run_merge(config, args.device, clean_cache=False))
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+            dt = time.time() - t0
+            st = iostats.snapshot(reset=True)
+            in_gb, out_gb = read_bytes / 1e9, 2.0 * n_params / 1e9
+            rec = {"cli_merge": "end to end", "model": args.model, "lora_rank": args.lora_rank, "finetunes": kind, "delta_bits": args.delta_bits if kind == "delta" else 0, "prefetch": prefetch == "1", "inplace_shards": inplace, "blocks": args.blocks, "k": args.k,
+                   "params": n_params, "seconds": round(dt, 3), "merged_GBps": round(out_gb / dt, 3), "input_GB": round(in_gb, 2),
+                   "stages": st}
+            # what the PCIe link allows: every input byte crosses it once, every output byte once, at the H2D rate
+            # measured on the copy stream in this run (the two directions are separate lanes: max, not sum)
+            h2d = st.get("h2d", {}).get("GBps")
+            if h2d:
+                rec["pcie_bound_merged_GBps"] = round(out_gb / (max(in_gb, out_gb) / h2d), 3)
+                rec["fraction_of_pcie_bound"] = round(rec["merged_GBps"] / rec["pcie_bound_merged_GBps"], 3)
+            print(json.dumps(rec))
     if not args.keep:
         shutil.rmtree(root)
 

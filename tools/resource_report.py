@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPRs / spills / scratch / occupancy of the transform kernels of one static plan, or of one group of the other kernels.
 usage: tools/resource_report.py <plan index in SM_STATIC_PLANS> [extra hipcc flags]
-       tools/resource_report.py side<group> [extra hipcc flags]      (SM_SIDE_KERNELS_<group>; side7: the delta and geometric merges, side8: the task-vector statistics, side9: the low-rank extraction, side10: the pairwise fusion, side11: the PCB merge, side12: the TSV merge, side13: the WIDEN merge, side14: the CABS merge, side15: the Iso-C merge)"""
+       tools/resource_report.py side<group> [extra hipcc flags]      (SM_SIDE_KERNELS_<group>; side7: the delta and geometric merges, side8: the task-vector statistics, side9: the low-rank extraction, side10: the pairwise fusion, side11: the PCB merge, side12: the TSV merge, side13: the WIDEN merge, side14: the CABS merge, side15: the Iso-C merge, side16: the delta pack)"""
 import re
 import subprocess
 import sys
