@@ -989,4 +989,22 @@ inline double aten_gauss_norm_ratio(double n, double sigma) {
     return exact > 0 ? std::sqrt(S / exact) : 1.0;
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 0 of smhip_side.hip (smhip_device.hpp) ----
+// (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
+SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KAtenScan, AtenScanParams, "aten_norm_scan", k_aten_scan(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KAtenRec, AtenRecParams, "aten_norm_rec", k_aten_rec(ex, p), 256, 4)
+#ifndef SM_ATEN_PART_WAVES
+#define SM_ATEN_PART_WAVES 3
+#endif
+SM_KERNEL_TAG_LB(KAtenPart16, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_RAW16>(ex, p), 256, SM_ATEN_PART_WAVES)   // 16 running summaries per thread
+SM_KERNEL_TAG_LB(KAtenPart32, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_RAW32>(ex, p), 256, SM_ATEN_PART_WAVES)
+SM_KERNEL_TAG_LB(KAtenPart, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_SIGNAL>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KAtenPartC, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_CLASS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KAtenWalk, AtenWalkParams, "aten_norm_walk", k_aten_walk<0>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KAtenWalkC, AtenWalkParams, "aten_norm_walk", k_aten_walk<1>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finish(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_0(X) X(KAtenPre) X(KAtenPreC) X(KAtenScan) X(KAtenRec) X(KAtenPart16) X(KAtenPart32) X(KAtenPart) X(KAtenPartC) X(KAtenWalk) X(KAtenWalkC) X(KAtenFinish)
+
 }  // namespace smhip

@@ -256,4 +256,9 @@ SM_HD void k_i2b(Ex& ex, const I2BParams& pp) {
     }
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 6 of smhip_side.hip (smhip_device.hpp): the run-time planned (DynPlan) row passes ----
+SM_BLUE_KERNEL_TAG(KF1B, F1BParams, "f1_rows_fwd", k_f1b<P>(ex, p))
+SM_BLUE_KERNEL_TAG(KI2B, I2BParams, "i2_rows_inv", k_i2b<P>(ex, p))
+#define SM_SIDE_KERNELS_6(X) X(KF1B<DynPlan>) X(KI2B<DynPlan>)
+
 }  // namespace smhip

@@ -183,4 +183,11 @@ SM_HD void k_crumbs_merge(Ex& ex, const CrumbsMergeParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// the two-rank radix level, its scan, and the fused two-sided merge pass
+SM_KERNEL_TAG_LB(KCrumbsHist, CrumbsHistParams, "crumbs_hist", k_crumbs_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KCrumbsSelect, CrumbsSelectParams, "crumbs_select", k_crumbs_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KCrumbsMerge, CrumbsMergeParams, "crumbs_merge", k_crumbs_merge(ex, p), 256, 4)
+#define SM_KERNELS_CRUMBS(X) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge)
+
 }  // namespace smhip

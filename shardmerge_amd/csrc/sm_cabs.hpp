@@ -300,4 +300,11 @@ SM_HD void k_cabs_merge(Ex& ex, const CabsMergeParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 14 of smhip_side.hip (smhip_device.hpp) ----
+// the one fused pass with the k deltas of a row octet in registers across the sequential n:m selections of the finetunes;
+// k <= 4 at dare_merge's residency, or up to 16
+SM_KERNEL_TAG_LB(KCabsMerge, CabsMergeParams, "cabs_merge", k_cabs_merge<CABS_REG_SMALL>(ex, p), CABS_THREADS, 4)
+SM_KERNEL_TAG_LB(KCabsMergeAny, CabsMergeParams, "cabs_merge_any", k_cabs_merge<TIES_MAX_MODELS>(ex, p), CABS_THREADS, 2)
+#define SM_SIDE_KERNELS_14(X) X(KCabsMerge) X(KCabsMergeAny)
+
 }  // namespace smhip

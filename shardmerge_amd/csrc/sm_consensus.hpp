@@ -149,4 +149,11 @@ SM_HD void k_consensus_merge(Ex& ex, const ConsensusMergeParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// the one fused pass with the k weighted entries of an octet in registers across the sum / election; k <= 4 at
+// dare_merge's residency, or up to 16
+SM_KERNEL_TAG_LB(KConsensusMerge, ConsensusMergeParams, "consensus_merge", k_consensus_merge<CONSENSUS_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KConsensusMergeAny, ConsensusMergeParams, "consensus_merge", k_consensus_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
+#define SM_KERNELS_CONSENSUS(X) X(KConsensusMerge) X(KConsensusMergeAny)
+
 }  // namespace smhip

@@ -132,4 +132,9 @@ SM_HD void k_dare_merge(Ex& ex, const DareMergeParams& p) {
     kept_fold(ex, st, lc, k, p.kept);
 }
 
+// ---- kernel tag (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// the one fused pass, the drop mask from a Philox block per octet in registers
+SM_KERNEL_TAG_LB(KDareMerge, DareMergeParams, "dare_merge", k_dare_merge(ex, p), 256, 4)
+#define SM_KERNELS_DARE(X) X(KDareMerge)
+
 }  // namespace smhip

@@ -303,4 +303,12 @@ SM_HD void k_della_merge(Ex& ex, const DellaMergeParams& p) {
     kept_fold(ex, st, lc, k, p.kept);
 }
 
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// T as a function of the rank, the whole-row sort in LDS (one work-group per finetune and row, up to 1024 threads), the
+// fused pass with a threshold per element
+SM_KERNEL_TAG_LB(KDellaTable, DellaTableParams, "della_table", k_della_table(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KDellaRank, DellaRankParams, "della_rank", k_della_rank(ex, p), 1024, 4)
+SM_KERNEL_TAG_LB(KDellaMerge, DellaMergeParams, "della_merge", k_della_merge(ex, p), 256, 4)
+#define SM_KERNELS_DELLA(X) X(KDellaTable) X(KDellaRank) X(KDellaMerge)
+
 }  // namespace smhip

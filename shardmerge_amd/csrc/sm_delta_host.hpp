@@ -33,135 +33,6 @@
 
 namespace smhip {
 
-// ---- kernel tags -------------------------------------------------------------
-// a kernel with explicit launch bounds (work-group size limit, waves per SIMD the registers are budgeted for)
-#define SM_KERNEL_TAG_LB(Tag, ParamsT, NAME, CALL, MAXT, WAVES)                      \
-    struct Tag {                                                                     \
-        using Params = ParamsT;                                                      \
-        static constexpr int waves = WAVES;                                          \
-        static constexpr int max_threads = MAXT;                                     \
-        static const char* name() { return NAME; }                                   \
-        template <class Ex> static SM_HD void run(Ex& ex, const Params& p) { CALL; } \
-    };
-// TIES merge (sm_ties.hpp): one radix level of the magnitude selection, its scan, and the fused merge pass
-SM_KERNEL_TAG_LB(KTiesHist, TiesHistParams, "ties_hist", k_ties_hist(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KTiesSelect, TiesSelectParams, "ties_select", k_ties_select(ex, p), TIES_SELECT_THREADS, 4)
-SM_KERNEL_TAG_LB(KTiesMerge, TiesMergeParams, "ties_merge", k_ties_merge(ex, p), 256, 4)
-// DARE merge (sm_dare.hpp): the one fused pass, the drop mask from a Philox block per octet in registers
-SM_KERNEL_TAG_LB(KDareMerge, DareMergeParams, "dare_merge", k_dare_merge(ex, p), 256, 4)
-// Breadcrumbs merge (sm_breadcrumbs.hpp): the two-rank radix level, its scan, and the fused two-sided merge pass
-SM_KERNEL_TAG_LB(KCrumbsHist, CrumbsHistParams, "crumbs_hist", k_crumbs_hist(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KCrumbsSelect, CrumbsSelectParams, "crumbs_select", k_crumbs_select(ex, p), TIES_SELECT_THREADS, 4)
-SM_KERNEL_TAG_LB(KCrumbsMerge, CrumbsMergeParams, "crumbs_merge", k_crumbs_merge(ex, p), 256, 4)
-// Geometric merges (sm_geo.hpp): the ordered fp64 Gram pass, its fold over the segments, the row-wise coefficients, the combine pass
-SM_KERNEL_TAG_LB(KGeoGram, GeoGramParams, "geo_gram", k_geo_gram<false>(ex, p), GEO_THREADS, 4)       // k <= 4: one tile of pairs
-SM_KERNEL_TAG_LB(KGeoGramTiled, GeoGramParams, "geo_gram", k_geo_gram<true>(ex, p), GEO_THREADS, 2)
-SM_KERNEL_TAG_LB(KGeoFold, GeoFoldParams, "geo_gram_fold", k_geo_fold(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KGeoCoef, GeoCoefParams, "geo_coef", k_geo_coef(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KGeoCombine, GeoCombineParams, "geo_combine", k_geo_combine(ex, p), 256, 4)
-// Karcher-mean merges (sm_sphere.hpp): the row-wise coefficient iteration, k <= 4 in registers or up to 16 in LDS, and the
-// probe of the three defined functions
-SM_KERNEL_TAG_LB(KSphereCoef, SphereCoefParams, "sphere_coef", k_sphere_coef<false>(ex, p), SPH_REG_THREADS, 2)
-SM_KERNEL_TAG_LB(KSphereCoefLds, SphereCoefParams, "sphere_coef", k_sphere_coef<true>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KSphereFn, SphereFnParams, "sphere_fn", k_sphere_fn(ex, p), 256, 4)
-// SCE merge (sm_sce.hpp): the one-stream radix level over the variance scores, its scan, the masked ordered fp64 energies
-// and their fold, the fused merge pass; k <= 4 deltas per octet in registers, or up to 16
-SM_KERNEL_TAG_LB(KSceHist, SceHistParams, "sce_hist", k_sce_hist<SCE_REG_SMALL>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KSceHistAny, SceHistParams, "sce_hist", k_sce_hist<TIES_MAX_MODELS>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KSceSelect, SceSelectParams, "sce_select", k_sce_select(ex, p), TIES_SELECT_THREADS, 4)
-SM_KERNEL_TAG_LB(KSceEnergy, SceEnergyParams, "sce_energy", k_sce_energy<SCE_REG_SMALL>(ex, p), GEO_THREADS, 4)
-SM_KERNEL_TAG_LB(KSceEnergyAny, SceEnergyParams, "sce_energy", k_sce_energy<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 2)
-SM_KERNEL_TAG_LB(KSceFold, SceFoldParams, "sce_energy_fold", k_sce_fold(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KSceMerge, SceMergeParams, "sce_merge", k_sce_merge<SCE_REG_SMALL>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KSceMergeAny, SceMergeParams, "sce_merge", k_sce_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
-// DELLA merge (sm_della.hpp): T as a function of the rank, the whole-row sort in LDS (one work-group per finetune and row,
-// up to 1024 threads), the fused pass with a threshold per element
-SM_KERNEL_TAG_LB(KDellaTable, DellaTableParams, "della_table", k_della_table(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KDellaRank, DellaRankParams, "della_rank", k_della_rank(ex, p), 1024, 4)
-SM_KERNEL_TAG_LB(KDellaMerge, DellaMergeParams, "della_merge", k_della_merge(ex, p), 256, 4)
-// Consensus merge (sm_consensus.hpp): the one fused pass with the k weighted entries of an octet in registers across the
-// sum / election; k <= 4 at dare_merge's residency, or up to 16
-SM_KERNEL_TAG_LB(KConsensusMerge, ConsensusMergeParams, "consensus_merge", k_consensus_merge<CONSENSUS_REG_SMALL>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KConsensusMergeAny, ConsensusMergeParams, "consensus_merge", k_consensus_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
-// Task-vector statistics (sm_stats.hpp): the m-rank radix level and its scan, the one fused pass over the k deltas of an
-// octet (k <= 4 with every density in registers, or up to 16 with the densities tiled), the fold of its energies
-SM_KERNEL_TAG_LB(KStatsHist, StatsHistParams, "stats_hist", k_stats_hist(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KStatsSelect, StatsSelectParams, "stats_select", k_stats_select(ex, p), TIES_SELECT_THREADS, 4)
-SM_KERNEL_TAG_LB(KStatsPass, StatsPassParams, "stats_pass", k_stats_pass<STATS_REG_SMALL>(ex, p), GEO_THREADS, 2)
-SM_KERNEL_TAG_LB(KStatsPassAny, StatsPassParams, "stats_pass", k_stats_pass<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 1)
-SM_KERNEL_TAG_LB(KStatsFold, StatsFoldParams, "stats_fold", k_stats_fold(ex, p), 256, 4)
-// Low-rank extraction (sm_extract.hpp): the Rademacher panel, the delta product on fp32 MFMA (one wave per work-group: 40
-// or 160 accumulator registers) and its fold, the ordered fp64 Gram of a panel and its fold, panel x small matrix
-SM_KERNEL_TAG_LB(KXlFill, XlFillParams, "xl_fill", k_xl_fill(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KXlDeltaMm, XlMmParams, "xl_delta_mm", k_xl_delta_mm(ex, p), 64, 2)
-SM_KERNEL_TAG_LB(KXlFold, XlFoldParams, "xl_fold", k_xl_fold(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KXlGram, XlGramParams, "xl_gram", k_xl_gram(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KXlGramFold, XlGramFoldParams, "xl_gram_fold", k_xl_gram_fold(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KXlPanelMm, XlPanelMmParams, "xl_panel_mm", k_xl_panel_mm(ex, p), 256, 4)
-// Pairwise fusion (sm_fusion.hpp): the row KL through sm_exp / sm_log (54 VGPRs: the fp64
-// Horner chains run one element after another), the three-rank radix level over the score stream and its scan, the
-// fused gate pass - which with FUS_NEARSWAP is the whole of nearswap - and the probe of the two defined functions
-SM_KERNEL_TAG_LB(KFusionRowKl, FusionRowKlParams, "fusion_rowkl", k_fusion_rowkl(ex, p), GEO_THREADS, 4)
-SM_KERNEL_TAG_LB(KFusionHist, FusionHistParams, "fusion_hist", k_fusion_hist(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KFusionSelect, FusionSelectParams, "fusion_select", k_fusion_select(ex, p), TIES_SELECT_THREADS, 4)
-SM_KERNEL_TAG_LB(KFusionMergeArcee, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_ARCEE>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KFusionMergeNear, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_NEARSWAP>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KFusionFn, FusionFnParams, "fusion_fn", k_fusion_fn(ex, p), 256, 4)
-// PCB merge (sm_pcb.hpp): the two-rank radix level over the score stream (its scan is stats_select, as the clip's two
-// order statistics are stats_hist / stats_select), the fused weighted pass - k <= 4 entries per element in registers, or
-// up to 16 - and the probe of sm_tanh
-SM_KERNEL_TAG_LB(KPcbHist, PcbHistParams, "pcb_hist", k_pcb_hist<PCB_REG_SMALL>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KPcbHistAny, PcbHistParams, "pcb_hist", k_pcb_hist<TIES_MAX_MODELS>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KPcbMerge, PcbMergeParams, "pcb_merge", k_pcb_merge<PCB_REG_SMALL>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KPcbMergeAny, PcbMergeParams, "pcb_merge", k_pcb_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KPcbFn, PcbFnParams, "pcb_fn", k_pcb_fn(ex, p), 256, 4)
-// TSV merge (sm_tsv.hpp): base_out + lambda * B W^T on fp32 MFMA, four waves of 4 x 4 accumulator tiles (64 registers);
-// everything before it runs on the kernels of the low-rank extraction
-SM_KERNEL_TAG_LB(KTsvApply, TsvApplyParams, "tsv_apply", k_tsv_apply(ex, p), 256, 2)
-// WIDEN merge (sm_widen.hpp): the ordered fp64 column sums (24 accumulators per lane), their fold into the two divergences,
-// the ranks by counting, the per-column weights through sm_exp, the combine pass with k <= 4 x 8 weights per lane in
-// registers, or up to 16 x 8
-SM_KERNEL_TAG_LB(KWidenColstats, WidenColstatsParams, "widen_colstats", k_widen_colstats(ex, p), WIDEN_THREADS, 4)
-SM_KERNEL_TAG_LB(KWidenColfold, WidenColfoldParams, "widen_colfold", k_widen_colfold(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KWidenRank, WidenRankParams, "widen_rank", k_widen_rank(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KWidenCoef, WidenCoefParams, "widen_coef", k_widen_coef(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KWidenCombine, WidenCombineParams, "widen_combine", k_widen_combine<WIDEN_REG_SMALL>(ex, p), WIDEN_THREADS, 4)
-SM_KERNEL_TAG_LB(KWidenCombineAny, WidenCombineParams, "widen_combine", k_widen_combine<TIES_MAX_MODELS>(ex, p), WIDEN_THREADS, 2)
-// CABS merge (sm_cabs.hpp): the one fused pass with the k deltas of a row octet in registers across the sequential n:m
-// selections of the finetunes; k <= 4 at dare_merge's residency, or up to 16
-SM_KERNEL_TAG_LB(KCabsMerge, CabsMergeParams, "cabs_merge", k_cabs_merge<CABS_REG_SMALL>(ex, p), CABS_THREADS, 4)
-SM_KERNEL_TAG_LB(KCabsMergeAny, CabsMergeParams, "cabs_merge_any", k_cabs_merge<TIES_MAX_MODELS>(ex, p), CABS_THREADS, 2)
-// Iso-C merge (sm_iso.hpp): the LDS-staged fp32 MFMA GEMM in its two forms (four waves of 2 x 2 accumulator tiles of
-// 32 x 32, 64 registers), the sum of the weighted deltas, the transposing copy, the three ordered fp64 sums, scale, apply
-SM_KERNEL_TAG_LB(KIsoGemmNT, IsoGemmParams, "iso_gemm_nt", k_iso_gemm<ISO_NT>(ex, p), ISO_THREADS, 2)
-SM_KERNEL_TAG_LB(KIsoGemmNN, IsoGemmParams, "iso_gemm_nn", k_iso_gemm<ISO_NN>(ex, p), ISO_THREADS, 2)
-SM_KERNEL_TAG_LB(KIsoSum, IsoSumParams, "iso_sum", k_iso_sum(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KIsoTranspose, IsoTransposeParams, "iso_transpose", k_iso_transpose(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KIsoNorm, IsoReduceParams, "iso_norm", k_iso_reduce<ISO_RED_NORM>(ex, p), GEO_THREADS, 4)
-SM_KERNEL_TAG_LB(KIsoResid, IsoReduceParams, "iso_resid", k_iso_reduce<ISO_RED_RESID>(ex, p), GEO_THREADS, 4)
-SM_KERNEL_TAG_LB(KIsoDot, IsoReduceParams, "iso_dot", k_iso_reduce<ISO_RED_DOT>(ex, p), GEO_THREADS, 4)
-SM_KERNEL_TAG_LB(KIsoScale, IsoScaleParams, "iso_scale", k_iso_scale(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KIsoApply, IsoApplyParams, "iso_apply", k_iso_apply(ex, p), 256, 4)
-// Delta pack (sm_dpack.hpp): the fused pass over whole rows (planes, ordered fp64 sums), the scales, the streaming apply;
-// its selection is ties_hist / ties_select and its folds are geo_gram_fold
-SM_KERNEL_TAG_LB(KDpackPack, DpackPackParams, "dpack_pack", k_dpack_pack(ex, p), DPACK_THREADS, 4)
-SM_KERNEL_TAG_LB(KDpackScale, DpackScaleParams, "dpack_scale", k_dpack_scale(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KDpackApply, DpackApplyParams, "dpack_apply", k_dpack_apply(ex, p), 256, 4)
-// the operators' groups of smhip_side.hip (one group per translation unit; SM_SIDE_GROUPS and groups 0 - 6: sm_pipeline.hpp)
-#define SM_SIDE_KERNELS_7(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge) X(KDareMerge) X(KCrumbsHist) X(KCrumbsSelect) X(KCrumbsMerge) \
-    X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn) \
-    X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny) \
-    X(KDellaTable) X(KDellaRank) X(KDellaMerge) X(KConsensusMerge) X(KConsensusMergeAny)
-#define SM_SIDE_KERNELS_8(X) X(KStatsHist) X(KStatsSelect) X(KStatsPass) X(KStatsPassAny) X(KStatsFold)
-#define SM_SIDE_KERNELS_9(X) X(KXlFill) X(KXlDeltaMm) X(KXlFold) X(KXlGram) X(KXlGramFold) X(KXlPanelMm)
-#define SM_SIDE_KERNELS_10(X) X(KFusionRowKl) X(KFusionHist) X(KFusionSelect) X(KFusionMergeArcee) X(KFusionMergeNear) X(KFusionFn)
-#define SM_SIDE_KERNELS_11(X) X(KPcbHist) X(KPcbHistAny) X(KPcbMerge) X(KPcbMergeAny) X(KPcbFn)
-#define SM_SIDE_KERNELS_12(X) X(KTsvApply)
-#define SM_SIDE_KERNELS_13(X) X(KWidenColstats) X(KWidenColfold) X(KWidenRank) X(KWidenCoef) X(KWidenCombine) X(KWidenCombineAny)
-#define SM_SIDE_KERNELS_14(X) X(KCabsMerge) X(KCabsMergeAny)
-#define SM_SIDE_KERNELS_15(X) X(KIsoGemmNT) X(KIsoGemmNN) X(KIsoSum) X(KIsoTranspose) X(KIsoNorm) X(KIsoResid) X(KIsoDot) X(KIsoScale) X(KIsoApply)
-#define SM_SIDE_KERNELS_16(X) X(KDpackPack) X(KDpackScale) X(KDpackApply)
-
 // ---- what every host path uses, the spectral pipeline's included -------------------------------
 struct Buffer {
     void* p = nullptr;
@@ -326,6 +197,14 @@ class DeltaHost {
         select_levels_per_finetune<KTiesHist, KTiesSelect>(TIES_MAX_MODELS, h, s, TIES_SELECT_LDS,
                                                            [](int level) { return radix_bins(level); }, k_keep == 0);
     }
+    // The ordered fp64 fold (k_geo_fold, sm_geo.hpp) of part[nseg][np] under the tag K: into out[np], or with row > 0 as
+    // rows of `row` values `pitch` apart
+    template <class K>
+    void fold_pass(int np, size_t nseg, const double* part, double* out, int row = 0, int pitch = 0) {
+        GeoFoldParams f;
+        f.np = np; f.row = row ? row : np; f.pitch = row ? pitch : np; f.nseg = nseg; f.part = part; f.out = out;
+        be.template launch<K>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+    }
     // The ordered fp64 Gram pass (sm_geo.hpp) over nseg segments of seg_len elements: a work-group per segment and tile of
     // pairs, the segments' partials into part, a bit per non-finite vector into flags[0]; G: folded over the segments into
     // it, or nullptr.  gram_grid is the bound on that grid, for the caller to check before its workspace grows.
@@ -341,10 +220,7 @@ class DeltaHost {
         const int grid = (int)(nseg * (size_t)geo_tiles(in.k));
         if (in.k <= GEO_TILE) be.template launch<KGeoGram>(grid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
         else be.template launch<KGeoGramTiled>(grid, GEO_THREADS, geo_gram_lds_floats() * 4, g, stream);
-        if (!G) return;
-        GeoFoldParams f;
-        f.np = geo_pairs(in.k); f.nseg = nseg; f.part = part; f.G = G;
-        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        if (G) fold_pass<KGeoFold>(geo_pairs(in.k), nseg, part, G);
     }
 
     // ---- TIES merge ----
@@ -725,9 +601,7 @@ class DeltaHost {
         e.part = (double*)ws_at(off_part); e.flags = head->flags;
         if (small) be.template launch<KSceEnergy>((int)nseg, GEO_THREADS, sce_energy_lds_floats<SCE_REG_SMALL>() * 4, e, stream);
         else be.template launch<KSceEnergyAny>((int)nseg, GEO_THREADS, sce_energy_lds_floats<TIES_MAX_MODELS>() * 4, e, stream);
-        SceFoldParams f;
-        f.k = k; f.nseg = nseg; f.part = e.part; f.E = head->E;
-        be.template launch<KSceFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        fold_pass<KSceFold>(k, nseg, e.part, head->E);
 
         SceHead host;
         if ((rc = delta_readback("sce_merge", k, head, host))) return rc;     // the call's one synchronisation
@@ -1204,9 +1078,7 @@ class DeltaHost {
         sp.part = (double*)ws_at(off_part + gram_bytes); sp.counts = w->rb.counts;
         if (k <= STATS_REG_SMALL) be.template launch<KStatsPass>((int)nseg, GEO_THREADS, stats_pass_lds_floats(m, k) * 4, sp, stream);
         else be.template launch<KStatsPassAny>((int)nseg, GEO_THREADS, stats_pass_lds_floats(m, k) * 4, sp, stream);
-        StatsFoldParams sf;
-        sf.m = m; sf.k = k; sf.nseg = nseg; sf.part = sp.part; sf.energy = w->rb.energy;
-        be.template launch<KStatsFold>(1, 256, LDS_SCRATCH_FLOATS * 4, sf, stream);
+        fold_pass<KStatsFold>(m * k, nseg, sp.part, w->rb.energy, k, TIES_MAX_MODELS);
 
         StatsReadback host;
         if ((rc = delta_readback("delta_stats", k, &w->rb, host))) return rc;       // the call's one synchronisation
@@ -1635,9 +1507,7 @@ class DeltaHost {
         r.x = x; r.y = y; r.n = n; r.s = s; r.part = part;
         const size_t nseg = (n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
         be.template launch<K>((int)nseg, GEO_THREADS, iso_reduce_lds_floats() * 4, r, stream);
-        GeoFoldParams f;
-        f.np = 1; f.nseg = nseg; f.part = part; f.G = result;
-        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        fold_pass<KGeoFold>(1, nseg, part, result);
     }
     int iso_merge(const smhip_iso_desc& d, void* out, float* delta_out, smhip_iso_report* rep) {
         smhip_iso_report local;
@@ -1789,14 +1659,11 @@ class DeltaHost {
         p.part = part; p.flags = w->rb.flags;
         be.template launch<KDpackPack>((int)std::min<size_t>(R, (size_t)1 << 20), DPACK_THREADS, dpack_pack_lds_floats() * 4, p, stream);
 
-        GeoFoldParams f;
-        f.np = DPACK_NP; f.nseg = R; f.part = part; f.G = w->tot;
-        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        fold_pass<KGeoFold>(DPACK_NP, R, part, w->tot);
         DpackScaleParams s;
         s.rows = tensor ? 1 : R; s.part = tensor ? w->tot : part; s.scale = scale; s.terms = terms;
         be.template launch<KDpackScale>((int)((s.rows + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, s, stream);
-        f.np = DPACK_NT; f.nseg = s.rows; f.part = terms; f.G = w->T;
-        be.template launch<KGeoFold>(1, 256, LDS_SCRATCH_FLOATS * 4, f, stream);
+        fold_pass<KGeoFold>(DPACK_NT, s.rows, terms, w->T);
 
         DpackHead host;
         be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation

@@ -192,4 +192,12 @@ SM_HD void k_dpack_apply(Ex& ex, const DpackApplyParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 16 of smhip_side.hip (smhip_device.hpp) ----
+// the fused pass over whole rows (planes, ordered fp64 sums), the scales, the streaming apply; its selection is
+// ties_hist / ties_select and its folds are geo_gram_fold
+SM_KERNEL_TAG_LB(KDpackPack, DpackPackParams, "dpack_pack", k_dpack_pack(ex, p), DPACK_THREADS, 4)
+SM_KERNEL_TAG_LB(KDpackScale, DpackScaleParams, "dpack_scale", k_dpack_scale(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KDpackApply, DpackApplyParams, "dpack_apply", k_dpack_apply(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_16(X) X(KDpackPack) X(KDpackScale) X(KDpackApply)
+
 }  // namespace smhip

@@ -400,4 +400,15 @@ inline int xl_sym_eig(int n, double* a, double* lam, double* v) {
     return sweeps;
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 9 of smhip_side.hip (smhip_device.hpp) ----
+// the Rademacher panel, the delta product on fp32 MFMA (one wave per work-group: 40 or 160 accumulator registers) and its
+// fold, the ordered fp64 Gram of a panel and its fold, panel x small matrix
+SM_KERNEL_TAG_LB(KXlFill, XlFillParams, "xl_fill", k_xl_fill(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlDeltaMm, XlMmParams, "xl_delta_mm", k_xl_delta_mm(ex, p), 64, 2)
+SM_KERNEL_TAG_LB(KXlFold, XlFoldParams, "xl_fold", k_xl_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlGram, XlGramParams, "xl_gram", k_xl_gram(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlGramFold, XlGramFoldParams, "xl_gram_fold", k_xl_gram_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KXlPanelMm, XlPanelMmParams, "xl_panel_mm", k_xl_panel_mm(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_9(X) X(KXlFill) X(KXlDeltaMm) X(KXlFold) X(KXlGram) X(KXlGramFold) X(KXlPanelMm)
+
 }  // namespace smhip

@@ -377,4 +377,16 @@ SM_HD void k_fusion_merge(Ex& ex, const FusionMergeParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 10 of smhip_side.hip (smhip_device.hpp) ----
+// the row KL through sm_exp / sm_log (54 VGPRs: the fp64 Horner chains run one element after another), the three-rank
+// radix level over the score stream and its scan, the fused gate pass - which with FUS_NEARSWAP is the whole of
+// nearswap - and the probe of the two defined functions
+SM_KERNEL_TAG_LB(KFusionRowKl, FusionRowKlParams, "fusion_rowkl", k_fusion_rowkl(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KFusionHist, FusionHistParams, "fusion_hist", k_fusion_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KFusionSelect, FusionSelectParams, "fusion_select", k_fusion_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KFusionMergeArcee, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_ARCEE>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KFusionMergeNear, FusionMergeParams, "fusion_merge", k_fusion_merge<FUS_NEARSWAP>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KFusionFn, FusionFnParams, "fusion_fn", k_fusion_fn(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_10(X) X(KFusionRowKl) X(KFusionHist) X(KFusionSelect) X(KFusionMergeArcee) X(KFusionMergeNear) X(KFusionFn)
+
 }  // namespace smhip

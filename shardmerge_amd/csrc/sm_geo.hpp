@@ -189,11 +189,14 @@ SM_HD void k_geo_gram(Ex& ex, const GeoGramParams& p) {
     });
 }
 
+// The ordered fp64 fold over the segments, one work-group of at least np threads: the Gram's (geo_gram_fold), and under
+// their own tags SCE's energies (sce_energy_fold, sm_sce.hpp) and the statistics' (stats_fold, sm_stats.hpp).
 struct GeoFoldParams {
-    int np;                     // geo_pairs(k)
+    int np;                     // values per segment: geo_pairs(k)
+    int row, pitch;             // value t lands at out[(t / row) * pitch + t % row]; row = pitch = np: at out[t]
     size_t nseg;
     const double* part;         // [nseg][np]
-    double* G;                  // [np]: G = (((0 + part[0]) + part[1]) + ...)
+    double* out;                // out = (((0 + part[0]) + part[1]) + ...)
 };
 template <class Ex>
 SM_HD void k_geo_fold(Ex& ex, const GeoFoldParams& p) {
@@ -202,8 +205,8 @@ SM_HD void k_geo_fold(Ex& ex, const GeoFoldParams& p) {
     ex.each(st, [&](int tid, EmptyState&) {
         if (tid >= p.np) return;
         double s = 0.0;
-        for (size_t q = 0; q < p.nseg; ++q) s = s + p.part[q * p.np + tid];
-        p.G[tid] = s;
+        for (size_t q = 0; q < p.nseg; ++q) s = geo_dadd(s, p.part[q * p.np + tid]);
+        p.out[(tid / p.row) * p.pitch + tid % p.row] = s;
     });
 }
 
@@ -284,5 +287,14 @@ SM_HD void k_geo_combine(Ex& ex, const GeoCombineParams& p) {
         }
     });
 }
+
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// the ordered fp64 Gram pass, its fold over the segments, the row-wise coefficients, the combine pass
+SM_KERNEL_TAG_LB(KGeoGram, GeoGramParams, "geo_gram", k_geo_gram<false>(ex, p), GEO_THREADS, 4)       // k <= 4: one tile of pairs
+SM_KERNEL_TAG_LB(KGeoGramTiled, GeoGramParams, "geo_gram", k_geo_gram<true>(ex, p), GEO_THREADS, 2)
+SM_KERNEL_TAG_LB(KGeoFold, GeoFoldParams, "geo_gram_fold", k_geo_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KGeoCoef, GeoCoefParams, "geo_coef", k_geo_coef(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KGeoCombine, GeoCombineParams, "geo_combine", k_geo_combine(ex, p), 256, 4)
+#define SM_KERNELS_GEO(X) X(KGeoGram) X(KGeoGramTiled) X(KGeoFold) X(KGeoCoef) X(KGeoCombine)
 
 }  // namespace smhip

@@ -408,4 +408,18 @@ SM_HD void k_iso_apply(Ex& ex, const IsoApplyParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 15 of smhip_side.hip (smhip_device.hpp) ----
+// the LDS-staged fp32 MFMA GEMM in its two forms (four waves of 2 x 2 accumulator tiles of 32 x 32, 64 registers), the sum
+// of the weighted deltas, the transposing copy, the three ordered fp64 sums, scale, apply
+SM_KERNEL_TAG_LB(KIsoGemmNT, IsoGemmParams, "iso_gemm_nt", k_iso_gemm<ISO_NT>(ex, p), ISO_THREADS, 2)
+SM_KERNEL_TAG_LB(KIsoGemmNN, IsoGemmParams, "iso_gemm_nn", k_iso_gemm<ISO_NN>(ex, p), ISO_THREADS, 2)
+SM_KERNEL_TAG_LB(KIsoSum, IsoSumParams, "iso_sum", k_iso_sum(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KIsoTranspose, IsoTransposeParams, "iso_transpose", k_iso_transpose(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KIsoNorm, IsoReduceParams, "iso_norm", k_iso_reduce<ISO_RED_NORM>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KIsoResid, IsoReduceParams, "iso_resid", k_iso_reduce<ISO_RED_RESID>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KIsoDot, IsoReduceParams, "iso_dot", k_iso_reduce<ISO_RED_DOT>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KIsoScale, IsoScaleParams, "iso_scale", k_iso_scale(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KIsoApply, IsoApplyParams, "iso_apply", k_iso_apply(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_15(X) X(KIsoGemmNT) X(KIsoGemmNN) X(KIsoSum) X(KIsoTranspose) X(KIsoNorm) X(KIsoResid) X(KIsoDot) X(KIsoScale) X(KIsoApply)
+
 }  // namespace smhip

@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "fft_engine.hpp"
+#include "sm_tag.hpp"
 #include "sm_aten_core.hpp"
 
 namespace smhip {
@@ -4314,5 +4315,72 @@ SM_HD void k_transpose(Ex& ex, const TransposeParams& p) {
         }
     });
 }
+
+// ---- kernel tags (sm_tag.hpp) ----
+SM_FFT_KERNEL_TAG(KF1, F1Params, "f1_rows_fwd", k_f1<P>(ex, p), 1, 3)
+SM_FFT_KERNEL_TAG(KF2, F2Params, "f2_cols_fwd", (k_f2<P, f2_bins<P>()>(ex, p)), 2 * f2_bins<P>(), 4)
+SM_FFT_KERNEL_TAG(KI1x1, I1Params, "i1_cols_inv", (k_i1<P, 1>(ex, p)), 1, 4)
+SM_FFT_KERNEL_TAG(KI1x2, I1Params, "i1_cols_inv", (k_i1<P, i1_bins<P>()>(ex, p)), i1_bins<P>(), 4)
+SM_FFT_KERNEL_TAG(KI2, I2Params, "i2_rows_inv", k_i2<P>(ex, p), 1, 4)
+SM_FFT_KERNEL_TAG(KF2S, F2SParams, "f2s_cols_fwd1", (k_f2s<P, f2s_groups<P>()>(ex, p)), f2s_groups<P>(), 4)
+// radix-4 column step folded into the row pass (k_f1q) and its column-side companions
+SM_FFT_KERNEL_TAG(KF1Q, F1Params, "f1_rows_fwd", k_f1q<P>(ex, p), 4, 4)
+SM_FFT_KERNEL_TAG(KF2Q, F2Params, "f2_cols_fwd", (k_f2<P, f2_bins<P>(), true>(ex, p)), 2 * f2_bins<P>(), 4)
+SM_FFT_KERNEL_TAG(KF2SQ, F2SParams, "f2s_cols_fwd1", (k_f2s<P, f2s_groups<P>(), true>(ex, p)), f2s_groups<P>(), 4)
+SM_FFT_KERNEL_TAG(KI1x1Q, I1Params, "i1_cols_inv", (k_i1<P, 1, true>(ex, p)), 1, 4)
+SM_FFT_KERNEL_TAG(KI1x2Q, I1Params, "i1_cols_inv", (k_i1<P, i1_bins<P>(), true>(ex, p)), i1_bins<P>(), 4)
+SM_FFT_KERNEL_TAG(KPair1d, Pair1dParams, "pair_1d", k_pair1d<P>(ex, p), 1, 1)      // one work-group per launch: all the registers it wants
+SM_KERNEL_TAG(KF2R1, F2Params, "f2_cols_fwd", k_f2_r1(ex, p))
+SM_KERNEL_TAG(KI1R1, I1Params, "i1_cols_inv", k_i1_r1(ex, p))
+SM_KERNEL_TAG(KPublish, PublishParams, "publish", k_publish(ex, p))
+SM_KERNEL_TAG(KHist, HistParams, "select_hist", k_hist(ex, p))
+SM_KERNEL_TAG(KScan, ScanParams, "select_scan", k_scan(ex, p))
+SM_KERNEL_TAG(KSelect2, Select2Params, "select_lvl2", k_select2<false>(ex, p))
+SM_KERNEL_TAG(KSelect2Cull, Select2Params, "select_lvl2_cull", k_select2<false>(ex, p))     // the cull's pass: returns at once after a confirmed speculation
+SM_KERNEL_TAG(KBlendSel, Select2Params, "blend", k_select2<true>(ex, p))
+SM_KERNEL_TAG(KSpecCheck, SpecCheckParams, "select_spec_check", k_spec_check(ex, p))
+SM_KERNEL_TAG(KSelect3, Select3Params, "select_lvl3_cand", k_select3(ex, p))
+SM_KERNEL_TAG(KReduceCand, ReduceCandParams, "slerp_reduce_cand", k_reduce_cand(ex, p))
+SM_KERNEL_TAG(KReduce, ReduceParams, "slerp_reduce", k_reduce(ex, p))
+SM_KERNEL_TAG(KSlerpConsts, SlerpConstParams, "slerp_consts", k_slerp_consts(ex, p))
+SM_KERNEL_TAG_LB(KClassEmf, ClassEmfParams, "class_norm_stats", k_class_emf(ex, p), 256, 2)
+SM_KERNEL_TAG(KSumPartials, SumPartialsParams, "sum_partials", k_sum_partials(ex, p))
+SM_KERNEL_TAG(KDeltaNorms, DeltaNormsParams, "delta_norms", k_delta_norms(ex, p))
+SM_KERNEL_TAG(KSumPartialsN, SumNParams, "sum_partials", k_sum_partials_n(ex, p))
+SM_KERNEL_TAG(KBlend, BlendParams, "blend", k_blend(ex, p))
+SM_KERNEL_TAG(KCombine, CombineParams, "combine", k_combine(ex, p))
+SM_KERNEL_TAG(KExpand, ExpandParams, "expand_full", k_expand(ex, p))
+SM_KERNEL_TAG(KPack, PackParams, "pack_planes", k_pack(ex, p))
+SM_KERNEL_TAG(KSplit, SplitParams, "split_complex", k_split(ex, p))
+SM_KERNEL_TAG(KJoin, JoinParams, "join_complex", k_join(ex, p))
+SM_KERNEL_TAG(KCull, CullParams, "cull_inplace", k_cull(ex, p))
+SM_KERNEL_TAG(KAddition, AdditionParams, "addition_merge", k_addition(ex, p))
+SM_KERNEL_TAG(KFnSums, FnSumsParams, "fn_slerp_sums", k_fn_sums(ex, p))
+SM_KERNEL_TAG(KFnSlerpFin, FnSlerpFinParams, "fn_slerp_consts", k_fn_slerp_fin(ex, p))
+SM_KERNEL_TAG(KFnSlerpRows0, FnSlerpRowsParams, "fn_slerp_relnorm", k_fn_slerp_rows<0>(ex, p))
+SM_KERNEL_TAG(KFnSlerpRows1, FnSlerpRowsParams, "fn_slerp_out", k_fn_slerp_rows<1>(ex, p))
+SM_KERNEL_TAG(KFnSlerpDen, FnSlerpDenParams, "fn_slerp_den", k_fn_slerp_den(ex, p))
+SM_KERNEL_TAG(KSumsqAny, SumsqAnyParams, "fn_sumsq", k_sumsq_any(ex, p))
+SM_KERNEL_TAG(KDivScalar, DivScalarParams, "fn_div_scalar", k_div_scalar(ex, p))
+SM_KERNEL_TAG(KCorrPartial, CorrPartialParams, "correlate_pairs", k_corr_partial(ex, p))
+SM_KERNEL_TAG(KCorrFinish, CorrFinishParams, "correlate_finish", k_corr_finish(ex, p))
+SM_KERNEL_TAG(KSerialNorm, SerialNormParams, "serial_norm", k_serial_norm(ex, p))
+SM_KERNEL_TAG(KSpecNorm, SpecNormParams, "spec_norm", k_spec_norm(ex, p))
+SM_KERNEL_TAG(KSumsqCand, SumsqCandParams, "spec_norm_cand", k_sumsq_cand(ex, p))
+SM_KERNEL_TAG(KSumSpec, SumSpecParams, "spec_norm_sum", k_sum_spec(ex, p))
+SM_KERNEL_TAG(KSpecRescale, SpecRescaleParams, "spec_rescale", k_spec_rescale(ex, p))
+SM_KERNEL_TAG(KDftp, DftpParams, "dft_across_slices", k_dftp(ex, p))
+SM_KERNEL_TAG(KDftpPairs, DftpParams, "dft_across_slices", k_dftp_pairs(ex, p))
+SM_KERNEL_TAG(KTranspose, TransposeParams, "transpose", k_transpose(ex, p))
+// groups of smhip_side.hip (smhip_device.hpp): the selection and reduction kernels, the run-time planned (DynPlan)
+// transforms in three groups, and this header's share of group 2
+#define SM_SIDE_KERNELS_1(X) X(KF2R1) X(KI1R1) X(KPublish) X(KHist) X(KScan) X(KSelect2) X(KSelect2Cull) X(KBlendSel) \
+    X(KSpecCheck) X(KSelect3) X(KReduceCand) X(KReduce) X(KSlerpConsts) X(KSumPartials) X(KClassEmf)
+#define SM_SIDE_KERNELS_3(X) X(KF1<DynPlan>) X(KF1Q<DynPlan>) X(KI2<DynPlan>) X(KPair1d<DynPlan>)
+#define SM_SIDE_KERNELS_4(X) X(KF2<DynPlan>) X(KF2Q<DynPlan>) X(KF2S<DynPlan>) X(KF2SQ<DynPlan>)
+#define SM_SIDE_KERNELS_5(X) X(KI1x1<DynPlan>) X(KI1x2<DynPlan>) X(KI1x1Q<DynPlan>) X(KI1x2Q<DynPlan>)
+#define SM_KERNELS_MERGE(X) X(KDeltaNorms) X(KSumPartialsN) X(KBlend) X(KCombine) X(KExpand) X(KPack) X(KSplit) X(KJoin) \
+    X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) \
+    X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec) X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose)
 
 }  // namespace smhip

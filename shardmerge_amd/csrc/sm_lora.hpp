@@ -485,4 +485,21 @@ SM_HD void k_dora_scale(Ex& ex, const DoraScaleParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 2 of smhip_side.hip (smhip_device.hpp) ----
+// LoRA low-rank update: the factor packing and the MFMA product, one per factor dtype
+SM_KERNEL_TAG_LB(KLoraPack, LoraPackParams, "lora_pack", k_lora_pack(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KLoraBf16, LoraApplyParams, "lora_apply", k_lora_apply<DT_BF16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KLoraF16, LoraApplyParams, "lora_apply", k_lora_apply<DT_F16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KLoraF32, LoraApplyParams, "lora_apply", k_lora_apply<DT_F32>(ex, p), 256, 2)
+// DoRA: the row-norm pass, the row factors and the scaled apply pass
+SM_KERNEL_TAG_LB(KDoraNormBf16, LoraApplyParams, "dora_norm", k_dora_norm<DT_BF16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraNormF16, LoraApplyParams, "dora_norm", k_dora_norm<DT_F16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraNormF32, LoraApplyParams, "dora_norm", k_dora_norm<DT_F32>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraScale, DoraScaleParams, "dora_scale", k_dora_scale(ex, p), DORA_SCALE_THREADS, 4)
+SM_KERNEL_TAG_LB(KDoraApplyBf16, LoraApplyParams, "dora_apply", k_dora_apply<DT_BF16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraApplyF16, LoraApplyParams, "dora_apply", k_dora_apply<DT_F16>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KDoraApplyF32, LoraApplyParams, "dora_apply", k_dora_apply<DT_F32>(ex, p), 256, 2)
+#define SM_KERNELS_LORA(X) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
+    X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
+
 }  // namespace smhip

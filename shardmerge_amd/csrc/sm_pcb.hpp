@@ -308,4 +308,15 @@ SM_HD void k_pcb_merge(Ex& ex, const PcbMergeParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 11 of smhip_side.hip (smhip_device.hpp) ----
+// the two-rank radix level over the score stream (its scan is stats_select, as the clip's two order statistics are
+// stats_hist / stats_select), the fused weighted pass - k <= 4 entries per element in registers, or up to 16 - and the
+// probe of sm_tanh
+SM_KERNEL_TAG_LB(KPcbHist, PcbHistParams, "pcb_hist", k_pcb_hist<PCB_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KPcbHistAny, PcbHistParams, "pcb_hist", k_pcb_hist<TIES_MAX_MODELS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KPcbMerge, PcbMergeParams, "pcb_merge", k_pcb_merge<PCB_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KPcbMergeAny, PcbMergeParams, "pcb_merge", k_pcb_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KPcbFn, PcbFnParams, "pcb_fn", k_pcb_fn(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_11(X) X(KPcbHist) X(KPcbHistAny) X(KPcbMerge) X(KPcbMergeAny) X(KPcbFn)
+
 }  // namespace smhip

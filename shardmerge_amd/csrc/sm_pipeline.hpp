@@ -21,58 +21,6 @@
 
 namespace smhip {
 
-// ---- kernel tags (SM_KERNEL_TAG_LB, the same with explicit launch bounds: sm_delta_host.hpp) ----
-#define SM_KERNEL_TAG(Tag, ParamsT, NAME, CALL)                                      \
-    struct Tag {                                                                     \
-        using Params = ParamsT;                                                      \
-        static constexpr int waves = 4;                                              \
-        static constexpr int max_threads = 1024;                                     \
-        static const char* name() { return NAME; }                                   \
-        template <class Ex> static SM_HD void run(Ex& ex, const Params& p) { CALL; } \
-    };
-// the four transform kernels exist once per static plan plus once for DynPlan
-template <class P, int GROUPS> constexpr int fft_max_threads() {
-    if constexpr (P::is_static) return (GROUPS * P::T < 256) ? 256 : (GROUPS * P::T > 1024 ? 1024 : GROUPS * P::T);
-    else return 1024;
-}
-#ifndef SM_W3_MAX_THREADS
-#define SM_W3_MAX_THREADS 256
-#endif
-#define SM_FFT_KERNEL_TAG(Tag, ParamsT, NAME, CALL, GROUPS, WAVES)                   \
-    template <class P> struct Tag {                                                  \
-        using Params = ParamsT;                                                      \
-        static constexpr int waves = (WAVES < 4 && P::is_static && fft_max_threads<P, GROUPS>() <= SM_W3_MAX_THREADS) ? WAVES : 4; \
-        static constexpr int max_threads = waves < 4 ? fft_max_threads<P, GROUPS>() : 1024; \
-        static const char* name() { return NAME; }                                   \
-        template <class Ex> static SM_HD void run(Ex& ex, const Params& p) { CALL; } \
-    };
-SM_FFT_KERNEL_TAG(KF1, F1Params, "f1_rows_fwd", k_f1<P>(ex, p), 1, 3)
-SM_FFT_KERNEL_TAG(KF2, F2Params, "f2_cols_fwd", (k_f2<P, f2_bins<P>()>(ex, p)), 2 * f2_bins<P>(), 4)
-SM_FFT_KERNEL_TAG(KI1x1, I1Params, "i1_cols_inv", (k_i1<P, 1>(ex, p)), 1, 4)
-SM_FFT_KERNEL_TAG(KI1x2, I1Params, "i1_cols_inv", (k_i1<P, i1_bins<P>()>(ex, p)), i1_bins<P>(), 4)
-SM_FFT_KERNEL_TAG(KI2, I2Params, "i2_rows_inv", k_i2<P>(ex, p), 1, 4)
-SM_FFT_KERNEL_TAG(KF2S, F2SParams, "f2s_cols_fwd1", (k_f2s<P, f2s_groups<P>()>(ex, p)), f2s_groups<P>(), 4)
-// radix-4 column step folded into the row pass (k_f1q) and its column-side companions
-SM_FFT_KERNEL_TAG(KF1Q, F1Params, "f1_rows_fwd", k_f1q<P>(ex, p), 4, 4)
-SM_FFT_KERNEL_TAG(KF2Q, F2Params, "f2_cols_fwd", (k_f2<P, f2_bins<P>(), true>(ex, p)), 2 * f2_bins<P>(), 4)
-SM_FFT_KERNEL_TAG(KF2SQ, F2SParams, "f2s_cols_fwd1", (k_f2s<P, f2s_groups<P>(), true>(ex, p)), f2s_groups<P>(), 4)
-SM_FFT_KERNEL_TAG(KI1x1Q, I1Params, "i1_cols_inv", (k_i1<P, 1, true>(ex, p)), 1, 4)
-SM_FFT_KERNEL_TAG(KI1x2Q, I1Params, "i1_cols_inv", (k_i1<P, i1_bins<P>(), true>(ex, p)), i1_bins<P>(), 4)
-// row passes of a row length without a plan (sm_bluestein.hpp); P is the plan of the convolution length
-// (one transform per work-group and two of them back to back: compiled for two waves per SIMD - 256 VGPRs - where
-//  the work-group allows it; at 128 the 16384-point convolution kept 700 bytes per lane in scratch)
-#define SM_BLUE_KERNEL_TAG(Tag, ParamsT, NAME, CALL)                                 \
-    template <class P> struct Tag {                                                  \
-        using Params = ParamsT;                                                      \
-        static constexpr int max_threads = fft_max_threads<P, 1>();                  \
-        static constexpr int waves = max_threads > 512 ? 4 : 2;                      \
-        static const char* name() { return NAME; }                                   \
-        template <class Ex> static SM_HD void run(Ex& ex, const Params& p) { CALL; } \
-    };
-SM_BLUE_KERNEL_TAG(KF1B, F1BParams, "f1_rows_fwd", k_f1b<P>(ex, p))
-SM_BLUE_KERNEL_TAG(KI2B, I2BParams, "i2_rows_inv", k_i2b<P>(ex, p))
-SM_FFT_KERNEL_TAG(KPair1d, Pair1dParams, "pair_1d", k_pair1d<P>(ex, p), 1, 1)      // one work-group per launch: all the registers it wants
-
 // lengths that get straight-line kernels (powers of two, the 7 * 2^k of Llama-3 / Mixtral MLPs,
 // the 3/5/7 * 2^k hidden and MLP sizes of other common models, and 256 / 512: the row blocks of the
 // split column lengths 11008 = 43 * 256 (Llama-2-7B), 18944 = 37 * 512 (Qwen2-7B), 4544 = 71 * 64 and 4672 = 73 * 64
@@ -148,87 +96,6 @@ inline bool plan_matches(const FftPlanDev& pl) {
         if (pl.radix[i] != PL::radix(i)) return false;
     return true;
 }
-SM_KERNEL_TAG(KF2R1, F2Params, "f2_cols_fwd", k_f2_r1(ex, p))
-SM_KERNEL_TAG(KI1R1, I1Params, "i1_cols_inv", k_i1_r1(ex, p))
-SM_KERNEL_TAG(KPublish, PublishParams, "publish", k_publish(ex, p))
-SM_KERNEL_TAG(KHist, HistParams, "select_hist", k_hist(ex, p))
-SM_KERNEL_TAG(KScan, ScanParams, "select_scan", k_scan(ex, p))
-SM_KERNEL_TAG(KSelect2, Select2Params, "select_lvl2", k_select2<false>(ex, p))
-SM_KERNEL_TAG(KSelect2Cull, Select2Params, "select_lvl2_cull", k_select2<false>(ex, p))     // the cull's pass: returns at once after a confirmed speculation
-SM_KERNEL_TAG(KBlendSel, Select2Params, "blend", k_select2<true>(ex, p))
-SM_KERNEL_TAG(KSpecCheck, SpecCheckParams, "select_spec_check", k_spec_check(ex, p))
-SM_KERNEL_TAG(KSelect3, Select3Params, "select_lvl3_cand", k_select3(ex, p))
-SM_KERNEL_TAG(KReduceCand, ReduceCandParams, "slerp_reduce_cand", k_reduce_cand(ex, p))
-SM_KERNEL_TAG(KReduce, ReduceParams, "slerp_reduce", k_reduce(ex, p))
-SM_KERNEL_TAG(KSlerpConsts, SlerpConstParams, "slerp_consts", k_slerp_consts(ex, p))
-SM_KERNEL_TAG_LB(KClassEmf, ClassEmfParams, "class_norm_stats", k_class_emf(ex, p), 256, 2)
-SM_KERNEL_TAG(KSumPartials, SumPartialsParams, "sum_partials", k_sum_partials(ex, p))
-SM_KERNEL_TAG(KDeltaNorms, DeltaNormsParams, "delta_norms", k_delta_norms(ex, p))
-SM_KERNEL_TAG(KSumPartialsN, SumNParams, "sum_partials", k_sum_partials_n(ex, p))
-SM_KERNEL_TAG(KBlend, BlendParams, "blend", k_blend(ex, p))
-SM_KERNEL_TAG(KCombine, CombineParams, "combine", k_combine(ex, p))
-SM_KERNEL_TAG(KExpand, ExpandParams, "expand_full", k_expand(ex, p))
-SM_KERNEL_TAG(KPack, PackParams, "pack_planes", k_pack(ex, p))
-SM_KERNEL_TAG(KSplit, SplitParams, "split_complex", k_split(ex, p))
-SM_KERNEL_TAG(KJoin, JoinParams, "join_complex", k_join(ex, p))
-SM_KERNEL_TAG(KCull, CullParams, "cull_inplace", k_cull(ex, p))
-SM_KERNEL_TAG(KAddition, AdditionParams, "addition_merge", k_addition(ex, p))
-SM_KERNEL_TAG(KFnSums, FnSumsParams, "fn_slerp_sums", k_fn_sums(ex, p))
-SM_KERNEL_TAG(KFnSlerpFin, FnSlerpFinParams, "fn_slerp_consts", k_fn_slerp_fin(ex, p))
-SM_KERNEL_TAG(KFnSlerpRows0, FnSlerpRowsParams, "fn_slerp_relnorm", k_fn_slerp_rows<0>(ex, p))
-SM_KERNEL_TAG(KFnSlerpRows1, FnSlerpRowsParams, "fn_slerp_out", k_fn_slerp_rows<1>(ex, p))
-SM_KERNEL_TAG(KFnSlerpDen, FnSlerpDenParams, "fn_slerp_den", k_fn_slerp_den(ex, p))
-SM_KERNEL_TAG(KSumsqAny, SumsqAnyParams, "fn_sumsq", k_sumsq_any(ex, p))
-SM_KERNEL_TAG(KDivScalar, DivScalarParams, "fn_div_scalar", k_div_scalar(ex, p))
-SM_KERNEL_TAG(KCorrPartial, CorrPartialParams, "correlate_pairs", k_corr_partial(ex, p))
-SM_KERNEL_TAG(KCorrFinish, CorrFinishParams, "correlate_finish", k_corr_finish(ex, p))
-SM_KERNEL_TAG(KSerialNorm, SerialNormParams, "serial_norm", k_serial_norm(ex, p))
-SM_KERNEL_TAG(KSpecNorm, SpecNormParams, "spec_norm", k_spec_norm(ex, p))
-SM_KERNEL_TAG(KSumsqCand, SumsqCandParams, "spec_norm_cand", k_sumsq_cand(ex, p))
-SM_KERNEL_TAG(KSumSpec, SumSpecParams, "spec_norm_sum", k_sum_spec(ex, p))
-SM_KERNEL_TAG(KSpecRescale, SpecRescaleParams, "spec_rescale", k_spec_rescale(ex, p))
-SM_KERNEL_TAG(KDftp, DftpParams, "dft_across_slices", k_dftp(ex, p))
-SM_KERNEL_TAG(KDftpPairs, DftpParams, "dft_across_slices", k_dftp_pairs(ex, p))
-SM_KERNEL_TAG(KTranspose, TransposeParams, "transpose", k_transpose(ex, p))
-// LoRA low-rank update (sm_lora.hpp): the factor packing and the MFMA product, one per factor dtype
-SM_KERNEL_TAG_LB(KLoraPack, LoraPackParams, "lora_pack", k_lora_pack(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KLoraBf16, LoraApplyParams, "lora_apply", k_lora_apply<DT_BF16>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KLoraF16, LoraApplyParams, "lora_apply", k_lora_apply<DT_F16>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KLoraF32, LoraApplyParams, "lora_apply", k_lora_apply<DT_F32>(ex, p), 256, 2)
-// DoRA (sm_lora.hpp): the row-norm pass, the row factors and the scaled apply pass
-SM_KERNEL_TAG_LB(KDoraNormBf16, LoraApplyParams, "dora_norm", k_dora_norm<DT_BF16>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KDoraNormF16, LoraApplyParams, "dora_norm", k_dora_norm<DT_F16>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KDoraNormF32, LoraApplyParams, "dora_norm", k_dora_norm<DT_F32>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KDoraScale, DoraScaleParams, "dora_scale", k_dora_scale(ex, p), DORA_SCALE_THREADS, 4)
-SM_KERNEL_TAG_LB(KDoraApplyBf16, LoraApplyParams, "dora_apply", k_dora_apply<DT_BF16>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KDoraApplyF16, LoraApplyParams, "dora_apply", k_dora_apply<DT_F16>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KDoraApplyF32, LoraApplyParams, "dora_apply", k_dora_apply<DT_F32>(ex, p), 256, 2)
-// (two instantiations each: signals x - base, and the slerp class of two spectrum planes)
-SM_KERNEL_TAG_LB(KAtenPre, AtenPreParams, "aten_norm_pre", k_aten_pre<0>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KAtenPreC, AtenPreParams, "aten_norm_pre", k_aten_pre<1>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KAtenScan, AtenScanParams, "aten_norm_scan", k_aten_scan(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KAtenRec, AtenRecParams, "aten_norm_rec", k_aten_rec(ex, p), 256, 4)
-#ifndef SM_ATEN_PART_WAVES
-#define SM_ATEN_PART_WAVES 3
-#endif
-SM_KERNEL_TAG_LB(KAtenPart16, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_RAW16>(ex, p), 256, SM_ATEN_PART_WAVES)   // 16 running summaries per thread
-SM_KERNEL_TAG_LB(KAtenPart32, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_RAW32>(ex, p), 256, SM_ATEN_PART_WAVES)
-SM_KERNEL_TAG_LB(KAtenPart, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_SIGNAL>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KAtenPartC, AtenPartParams, "aten_norm_part", k_aten_part<ATEN_PART_CLASS>(ex, p), 256, 2)
-SM_KERNEL_TAG_LB(KAtenWalk, AtenWalkParams, "aten_norm_walk", k_aten_walk<0>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KAtenWalkC, AtenWalkParams, "aten_norm_walk", k_aten_walk<1>(ex, p), 256, 4)
-SM_KERNEL_TAG_LB(KAtenFinish, AtenFinishParams, "aten_norm_finish", k_aten_finish(ex, p), 256, 4)
-// Every kernel is instantiated in smhip_side.hip (one group per translation unit, -DSM_SIDE_GROUP=<g>) or, the
-// static-plan transforms, in smhip_inst.hip; smhip_hip.hip holds host code only.  The build parallelises and a
-// change to the host orchestration does not recompile a single kernel.  (Groups 7 - 10: sm_delta_host.hpp.)
-#define SM_SIDE_KERNELS_0(X) X(KAtenPre) X(KAtenPreC) X(KAtenScan) X(KAtenRec) X(KAtenPart16) X(KAtenPart32) X(KAtenPart) X(KAtenPartC) X(KAtenWalk) X(KAtenWalkC) X(KAtenFinish)
-#define SM_SIDE_KERNELS_1(X) X(KF2R1) X(KI1R1) X(KPublish) X(KHist) X(KScan) X(KSelect2) X(KSelect2Cull) X(KBlendSel) \
-    X(KSpecCheck) X(KSelect3) X(KReduceCand) X(KReduce) X(KSlerpConsts) X(KSumPartials) X(KClassEmf)
-#define SM_SIDE_KERNELS_2(X) X(KDeltaNorms) X(KSumPartialsN) X(KBlend) X(KCombine) X(KExpand) X(KPack) X(KSplit) X(KJoin) \
-    X(KCull) X(KAddition) X(KFnSums) X(KFnSlerpFin) X(KFnSlerpRows0) X(KFnSlerpRows1) X(KFnSlerpDen) X(KSumsqAny) X(KDivScalar) X(KCorrPartial) X(KCorrFinish) X(KSerialNorm) X(KSpecNorm) X(KSumsqCand) X(KSumSpec)       \
-    X(KSpecRescale) X(KDftp) X(KDftpPairs) X(KTranspose) X(KLoraPack) X(KLoraBf16) X(KLoraF16) X(KLoraF32) \
-    X(KDoraNormBf16) X(KDoraNormF16) X(KDoraNormF32) X(KDoraScale) X(KDoraApplyBf16) X(KDoraApplyF16) X(KDoraApplyF32)
-#define SM_SIDE_GROUPS 17        // groups 3 - 6: the run-time planned (DynPlan) transform kernels; 7: TIES, DARE, Breadcrumbs, the geometric merges, SCE, DELLA and Consensus; 8: the task-vector statistics; 9: the low-rank extraction; 10: the pairwise fusion; 11: the PCB merge; 12: the TSV merge; 13: the WIDEN merge; 14: the CABS merge; 15: the Iso-C merge; 16: the delta pack
 
 // ---- FFT planner ---------------------------------------------------------------
 struct HostPlan {

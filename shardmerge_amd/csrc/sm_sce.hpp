@@ -14,7 +14,7 @@
 //                    level 3 the threshold and the selected count are final and stay on the device.
 //   sce_energy       E_i = sum of x_i^2 in fp64 over the selected elements, in the order of geo_gram: a work-group of
 //                    256 per 32768-element segment, octet o to lane o % 256, the binary tree through LDS.
-//   sce_energy_fold  the segments added in index order, a thread per finetune.
+//   sce_energy_fold  the segments added in index order, a thread per finetune (k_geo_fold, sm_geo.hpp).
 //   sce_merge        the fused streaming pass: the k finetunes, their bases and base_out are loaded once, q and the mask
 //                    recomputed, sign election / weighted masked sums / division / add-back in registers; the weights
 //                    arrive as kernel arguments.
@@ -227,24 +227,6 @@ SM_HD void k_sce_energy(Ex& ex, const SceEnergyParams& p) {
     });
 }
 
-struct SceFoldParams {
-    int k;
-    size_t nseg;
-    const double* part;         // [nseg][k]
-    double* E;                  // [k]: E_i = (((0 + part[0][i]) + part[1][i]) + ...)
-};
-template <class Ex>
-SM_HD void k_sce_fold(Ex& ex, const SceFoldParams& p) {
-    typename Ex::template State<EmptyState> st;
-    ex.init(st);
-    ex.each(st, [&](int tid, EmptyState&) {
-        if (tid >= p.k) return;
-        double s = 0.0;
-        for (size_t q = 0; q < p.nseg; ++q) s = geo_dadd(s, p.part[q * p.k + tid]);
-        p.E[tid] = s;
-    });
-}
-
 struct SceMergeParams {
     TiesInputs in;
     float w[TIES_MAX_MODELS];   // the weights of step 3 (alpha acts through them only)
@@ -302,5 +284,18 @@ SM_HD void k_sce_merge(Ex& ex, const SceMergeParams& p) {
         }
     });
 }
+
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// the one-stream radix level over the variance scores, its scan, the masked ordered fp64 energies and their fold (the
+// fold of sm_geo.hpp under its own profile name), the fused merge pass; k <= 4 deltas per octet in registers, or up to 16
+SM_KERNEL_TAG_LB(KSceHist, SceHistParams, "sce_hist", k_sce_hist<SCE_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KSceHistAny, SceHistParams, "sce_hist", k_sce_hist<TIES_MAX_MODELS>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KSceSelect, SceSelectParams, "sce_select", k_sce_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KSceEnergy, SceEnergyParams, "sce_energy", k_sce_energy<SCE_REG_SMALL>(ex, p), GEO_THREADS, 4)
+SM_KERNEL_TAG_LB(KSceEnergyAny, SceEnergyParams, "sce_energy", k_sce_energy<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 2)
+SM_KERNEL_TAG_LB(KSceFold, GeoFoldParams, "sce_energy_fold", k_geo_fold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KSceMerge, SceMergeParams, "sce_merge", k_sce_merge<SCE_REG_SMALL>(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KSceMergeAny, SceMergeParams, "sce_merge", k_sce_merge<TIES_MAX_MODELS>(ex, p), 256, 2)
+#define SM_KERNELS_SCE(X) X(KSceHist) X(KSceHistAny) X(KSceSelect) X(KSceEnergy) X(KSceEnergyAny) X(KSceFold) X(KSceMerge) X(KSceMergeAny)
 
 }  // namespace smhip

@@ -277,4 +277,11 @@ SM_HD void k_sphere_fn(Ex& ex, const SphereFnParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// the row-wise coefficient iteration, k <= 4 in registers or up to 16 in LDS, and the probe of the three defined functions
+SM_KERNEL_TAG_LB(KSphereCoef, SphereCoefParams, "sphere_coef", k_sphere_coef<false>(ex, p), SPH_REG_THREADS, 2)
+SM_KERNEL_TAG_LB(KSphereCoefLds, SphereCoefParams, "sphere_coef", k_sphere_coef<true>(ex, p), 256, 2)
+SM_KERNEL_TAG_LB(KSphereFn, SphereFnParams, "sphere_fn", k_sphere_fn(ex, p), 256, 4)
+#define SM_KERNELS_SPHERE(X) X(KSphereCoef) X(KSphereCoefLds) X(KSphereFn)
+
 }  // namespace smhip

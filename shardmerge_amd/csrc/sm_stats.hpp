@@ -20,7 +20,7 @@
 //                 work-group, as consensus_merge does.  KR = 4 serves k <= 4: the segment is read once, every density's
 //                 accumulators and counters in registers.  KR = 16 serves any k (the same source): 16 deltas per octet
 //                 leave registers for one density's, so the densities are tiled inside the launch, a sweep each.
-//   stats_fold    the segments' energies added in index order, a thread per (density, finetune).
+//   stats_fold    the segments' energies added in index order, a thread per (density, finetune) (k_geo_fold, sm_geo.hpp).
 // The Gram is geo_gram / geo_gram_fold themselves, launched unchanged.
 // Tensor passes with a shared base, k <= 4: 3 (K + 1) selection + (K + 1) Gram + (K + 1) stats_pass = 5 (K + 1), whatever m
 // (k > 4: geo_gram re-reads per tile of pairs and stats_pass per density).
@@ -335,23 +335,15 @@ SM_HD void k_stats_pass(Ex& ex, const StatsPassParams& p) {
     });
 }
 
-struct StatsFoldParams {
-    int m, k;
-    size_t nseg;
-    const double* part;         // [nseg][m * k]
-    double* energy;             // [STATS_MAX_RANKS][TIES_MAX_MODELS]: (((0 + part[0]) + part[1]) + ...)
-};
-template <class Ex>
-SM_HD void k_stats_fold(Ex& ex, const StatsFoldParams& p) {
-    typename Ex::template State<EmptyState> st;
-    ex.init(st);
-    ex.each(st, [&](int tid, EmptyState&) {
-        const int np = p.m * p.k;
-        if (tid >= np) return;
-        double s = 0.0;
-        for (size_t q = 0; q < p.nseg; ++q) s = geo_dadd(s, p.part[q * np + tid]);
-        p.energy[(tid / p.k) * TIES_MAX_MODELS + tid % p.k] = s;
-    });
-}
+// ---- kernel tags (sm_tag.hpp) and group 8 of smhip_side.hip (smhip_device.hpp) ----
+// the m-rank radix level and its scan, the one fused pass over the k deltas of an octet (k <= 4 with every density in
+// registers, or up to 16 with the densities tiled), the fold of its energies (the fold of sm_geo.hpp under its own
+// profile name, a row of k per rank at the report's pitch)
+SM_KERNEL_TAG_LB(KStatsHist, StatsHistParams, "stats_hist", k_stats_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KStatsSelect, StatsSelectParams, "stats_select", k_stats_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KStatsPass, StatsPassParams, "stats_pass", k_stats_pass<STATS_REG_SMALL>(ex, p), GEO_THREADS, 2)
+SM_KERNEL_TAG_LB(KStatsPassAny, StatsPassParams, "stats_pass", k_stats_pass<TIES_MAX_MODELS>(ex, p), GEO_THREADS, 1)
+SM_KERNEL_TAG_LB(KStatsFold, GeoFoldParams, "stats_fold", k_geo_fold(ex, p), 256, 4)
+#define SM_SIDE_KERNELS_8(X) X(KStatsHist) X(KStatsSelect) X(KStatsPass) X(KStatsPassAny) X(KStatsFold)
 
 }  // namespace smhip

@@ -147,4 +147,11 @@ SM_HD void k_ties_merge(Ex& ex, const TiesMergeParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and this header's share of group 7 of smhip_side.hip (smhip_device.hpp) ----
+// one radix level of the magnitude selection, its scan, and the fused merge pass
+SM_KERNEL_TAG_LB(KTiesHist, TiesHistParams, "ties_hist", k_ties_hist(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KTiesSelect, TiesSelectParams, "ties_select", k_ties_select(ex, p), TIES_SELECT_THREADS, 4)
+SM_KERNEL_TAG_LB(KTiesMerge, TiesMergeParams, "ties_merge", k_ties_merge(ex, p), 256, 4)
+#define SM_KERNELS_TIES(X) X(KTiesHist) X(KTiesSelect) X(KTiesMerge)
+
 }  // namespace smhip

@@ -121,4 +121,10 @@ SM_HD void k_tsv_apply(Ex& ex, const TsvApplyParams& p) {
 #endif
 }
 
+// ---- kernel tag (sm_tag.hpp) and group 12 of smhip_side.hip (smhip_device.hpp) ----
+// base_out + lambda * B W^T on fp32 MFMA, four waves of 4 x 4 accumulator tiles (64 registers); everything before it runs
+// on the kernels of the low-rank extraction
+SM_KERNEL_TAG_LB(KTsvApply, TsvApplyParams, "tsv_apply", k_tsv_apply(ex, p), 256, 2)
+#define SM_SIDE_KERNELS_12(X) X(KTsvApply)
+
 }  // namespace smhip

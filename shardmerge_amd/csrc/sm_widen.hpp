@@ -380,4 +380,15 @@ SM_HD void k_widen_combine(Ex& ex, const WidenCombineParams& p) {
     });
 }
 
+// ---- kernel tags (sm_tag.hpp) and group 13 of smhip_side.hip (smhip_device.hpp) ----
+// the ordered fp64 column sums (24 accumulators per lane), their fold into the two divergences, the ranks by counting, the
+// per-column weights through sm_exp, the combine pass with k <= 4 x 8 weights per lane in registers, or up to 16 x 8
+SM_KERNEL_TAG_LB(KWidenColstats, WidenColstatsParams, "widen_colstats", k_widen_colstats(ex, p), WIDEN_THREADS, 4)
+SM_KERNEL_TAG_LB(KWidenColfold, WidenColfoldParams, "widen_colfold", k_widen_colfold(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KWidenRank, WidenRankParams, "widen_rank", k_widen_rank(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KWidenCoef, WidenCoefParams, "widen_coef", k_widen_coef(ex, p), 256, 4)
+SM_KERNEL_TAG_LB(KWidenCombine, WidenCombineParams, "widen_combine", k_widen_combine<WIDEN_REG_SMALL>(ex, p), WIDEN_THREADS, 4)
+SM_KERNEL_TAG_LB(KWidenCombineAny, WidenCombineParams, "widen_combine", k_widen_combine<TIES_MAX_MODELS>(ex, p), WIDEN_THREADS, 2)
+#define SM_SIDE_KERNELS_13(X) X(KWidenColstats) X(KWidenColfold) X(KWidenRank) X(KWidenCoef) X(KWidenCombine) X(KWidenCombineAny)
+
 }  // namespace smhip

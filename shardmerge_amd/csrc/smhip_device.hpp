@@ -1,7 +1,7 @@
 // smhip_device.hpp - DeviceExec (one real gfx950 work-group per block) and the
 // generic __global__ entry point; shared by smhip_hip.hip, smhip_side.hip and smhip_inst.hip.
-// The kernel tags and the lists of what each translation unit instantiates: sm_pipeline.hpp
-// (the spectral pipeline, SM_STATIC_PLANS) and sm_delta_host.hpp (the delta operators).
+// Each kernel's tag stands at the end of the header that defines the kernel; what each
+// translation unit instantiates is listed at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,11 +94,36 @@ __global__ void __launch_bounds__(K::max_threads, K::waves) sm_kernel(const type
     K::run(ex, p);
 }
 
-// static-plan transform kernels are compiled in separate translation units
-// (smhip_inst.hip, one per plan) so that the build parallelises
+// Every kernel is instantiated in exactly one translation unit and smhip_hip.hip holds host code only (it declares
+// them all extern, and the Makefile fails the build if main.o defines one): the build parallelises and a change to the
+// host orchestration does not recompile a single kernel.
+// The static-plan transform kernels: smhip_inst.hip, one translation unit per plan of SM_STATIC_PLANS (sm_pipeline.hpp).
 #define SM_FFT_KERNELS_OF(X, ...)                      \
     X(KF1<__VA_ARGS__>) X(KF2<__VA_ARGS__>) X(KI1x1<__VA_ARGS__>) X(KI1x2<__VA_ARGS__>) X(KI2<__VA_ARGS__>) X(KF2S<__VA_ARGS__>) \
     X(KF1Q<__VA_ARGS__>) X(KF2Q<__VA_ARGS__>) X(KF2SQ<__VA_ARGS__>) X(KI1x1Q<__VA_ARGS__>) X(KI1x2Q<__VA_ARGS__>) \
     X(KPair1d<__VA_ARGS__>) X(KF1B<__VA_ARGS__>) X(KI2B<__VA_ARGS__>)
+// Every other kernel: smhip_side.hip, one translation unit per group g (-DSM_SIDE_GROUP=<g>) of SM_SIDE_KERNELS_<g>,
+// which the header that defines the group's kernels states after their tags.  The groups:
+//    0  the torch.norm emulation (sm_aten_norm.hpp)
+//    1  the selection and reduction kernels of the spectral pipeline (sm_kernels.hpp)
+//    2  its blend, norm, layout and element-wise kernels (sm_kernels.hpp) and the LoRA / DoRA update (sm_lora.hpp)
+//    3 - 6  the transform kernels for run-time planned lengths, SM_FFT_KERNELS_OF(X, DynPlan) in four parts
+//       (sm_kernels.hpp; 6, the row passes of a length without a plan: sm_bluestein.hpp)
+//    7  the delta and geometric merges: TIES, DARE, Breadcrumbs, Model Stock / SLERP / NuSLERP, the Karcher-mean merges,
+//       SCE, DELLA and Consensus (sm_ties.hpp .. sm_consensus.hpp, a sub-list each)
+//    8  the task-vector statistics (sm_stats.hpp)       9  the low-rank extraction (sm_extract.hpp)
+//   10  the pairwise fusion (sm_fusion.hpp)            11  the PCB merge (sm_pcb.hpp)
+//   12  the TSV merge (sm_tsv.hpp)                     13  the WIDEN merge (sm_widen.hpp)
+//   14  the CABS merge (sm_cabs.hpp)                   15  the Iso-C merge (sm_iso.hpp)
+//   16  the delta pack (sm_dpack.hpp)
+// A new group: its SM_SIDE_KERNELS_<g>, one more entry in SM_SIDE_KERNELS_ALL, and SM_SIDE_GROUPS (the Makefile reads it).
+#define SM_SIDE_KERNELS_2(X) SM_KERNELS_MERGE(X) SM_KERNELS_LORA(X)
+#define SM_SIDE_KERNELS_7(X) SM_KERNELS_TIES(X) SM_KERNELS_DARE(X) SM_KERNELS_CRUMBS(X) SM_KERNELS_GEO(X) SM_KERNELS_SPHERE(X) \
+    SM_KERNELS_SCE(X) SM_KERNELS_DELLA(X) SM_KERNELS_CONSENSUS(X)
+#define SM_SIDE_GROUPS 17
+#define SM_SIDE_KERNELS_ALL(X)                                                                                       \
+    SM_SIDE_KERNELS_0(X) SM_SIDE_KERNELS_1(X) SM_SIDE_KERNELS_2(X) SM_SIDE_KERNELS_3(X) SM_SIDE_KERNELS_4(X) SM_SIDE_KERNELS_5(X)     \
+    SM_SIDE_KERNELS_6(X) SM_SIDE_KERNELS_7(X) SM_SIDE_KERNELS_8(X) SM_SIDE_KERNELS_9(X) SM_SIDE_KERNELS_10(X) SM_SIDE_KERNELS_11(X)   \
+    SM_SIDE_KERNELS_12(X) SM_SIDE_KERNELS_13(X) SM_SIDE_KERNELS_14(X) SM_SIDE_KERNELS_15(X) SM_SIDE_KERNELS_16(X)
 
 }  // namespace smhip

@@ -20,19 +20,7 @@ namespace smhip {
 #define SM_DECL_PLAN(...) SM_FFT_KERNELS_OF(SM_DECL_EXTERN, __VA_ARGS__)
 SM_STATIC_PLANS(SM_DECL_PLAN)
 #undef SM_DECL_PLAN
-SM_SIDE_KERNELS_0(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_1(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_2(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_7(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_8(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_10(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_11(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_12(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_13(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_14(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_15(SM_DECL_EXTERN)
-SM_SIDE_KERNELS_16(SM_DECL_EXTERN)
-SM_FFT_KERNELS_OF(SM_DECL_EXTERN, DynPlan)
+SM_SIDE_KERNELS_ALL(SM_DECL_EXTERN)
 #undef SM_DECL_EXTERN
 
 struct HipBackend {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""VGPRs / spills / scratch / occupancy of the transform kernels of one static plan, or of one group of the other kernels.
+"""Registers / spills / scratch / occupancy / LDS of the transform kernels of one static plan, or of one group of the other kernels.
 usage: tools/resource_report.py <plan index in SM_STATIC_PLANS> [extra hipcc flags]
-       tools/resource_report.py side<group> [extra hipcc flags]      (SM_SIDE_KERNELS_<group>; side7: the delta and geometric merges, side8: the task-vector statistics, side9: the low-rank extraction, side10: the pairwise fusion, side11: the PCB merge, side12: the TSV merge, side13: the WIDEN merge, side14: the CABS merge, side15: the Iso-C merge, side16: the delta pack)"""
+       tools/resource_report.py side<group> [extra hipcc flags]      (SM_SIDE_KERNELS_<group>; the groups: the end of csrc/smhip_device.hpp)"""
 import re
 import subprocess
 import sys
@@ -27,5 +27,5 @@ for blk in txt.split("Function Name:")[1:]:
     m = re.search(r"sm_kernelINS_(\w+?)INS_5SPlanILi(\d+)ELi(\d+)", blk)
     side = re.search(r"sm_kernelINS_\d+(\w+?)EEvN", blk)
     name = f"{m.group(1)}<{m.group(2)},{m.group(3)}>" if m else (side.group(1) if side else blk[:40])
-    print(f"{name:22s} VGPRs {field(blk, 'VGPRs'):>4s}  spill {field(blk, 'VGPRs Spill'):>3s}  scratch {field(blk, 'ScratchSize [bytes/lane]'):>4s}"
+    print(f"{name:22s} VGPRs {field(blk, 'VGPRs'):>4s}  AGPRs {field(blk, 'AGPRs'):>3s}  SGPRs {field(blk, 'SGPRs'):>3s}  spill {field(blk, 'VGPRs Spill'):>3s}  scratch {field(blk, 'ScratchSize [bytes/lane]'):>4s}"
           f"  waves/SIMD {field(blk, 'Occupancy [waves/SIMD]'):>2s}  LDS {field(blk, 'LDS Size [bytes/block]')}")
