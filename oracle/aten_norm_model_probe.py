@@ -2,7 +2,7 @@
 """What torch.norm does on a contiguous fp32 CPU tensor, and how well the product's models of it hold.
 
 TEST INFRASTRUCTURE (like everything under oracle/): run by hand, its output is quoted in DESIGN.md 6.3 and in
-shardmerge_amd/csrc/sm_aten_norm.hpp / sm_kernels.hpp.  Three parts:
+shardmerge_amd/csrc/sm_aten_norm.hpp / sm_select.hpp.  Three parts:
 
 (a) the STRUCTURE of ATen's kernel, established on random vectors: acc = fma(x, x, acc) in 8 serial fp32 lanes, lanes
     added in order, then the T = n % 8 tail elements - the first 4 * (T // 4) as a rounded product and an add, the

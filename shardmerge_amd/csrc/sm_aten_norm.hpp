@@ -52,7 +52,9 @@
 // zero) reproduces the reference's norms to 2e-6 where exact norms are off by 2e-4 (4096^2;
 // oracle/aten_norm_model_probe.py).
 #pragma once
-#include "sm_kernels.hpp"        // (brings sm_aten_core.hpp: AtenSum, the chain evaluation, the fused row summaries)
+#include "sm_common.hpp"
+#include "sm_tag.hpp"
+#include "sm_aten_core.hpp"      // (AtenSum, the chain evaluation, the fused row summaries)
 
 namespace smhip {
 

@@ -22,7 +22,7 @@
 // Rough lengths are rare and these kernels are written for correctness first: element-wise global
 // accesses, one row (pair) per work-group, 3-4x the arithmetic of a planned length.
 #pragma once
-#include "sm_kernels.hpp"
+#include "sm_kernels.hpp"        // (F1Params, I2Params and the contracts of k_f1 / k_i2)
 
 namespace smhip {
 
@@ -256,9 +256,11 @@ SM_HD void k_i2b(Ex& ex, const I2BParams& pp) {
     }
 }
 
-// ---- kernel tags (sm_tag.hpp) and group 6 of smhip_side.hip (smhip_device.hpp): the run-time planned (DynPlan) row passes ----
+// ---- kernel tags (sm_tag.hpp) and groups 6 and 20 of smhip_side.hip (smhip_device.hpp): the run-time planned (DynPlan) row
+// passes, one kernel per group ----
 SM_BLUE_KERNEL_TAG(KF1B, F1BParams, "f1_rows_fwd", k_f1b<P>(ex, p))
 SM_BLUE_KERNEL_TAG(KI2B, I2BParams, "i2_rows_inv", k_i2b<P>(ex, p))
-#define SM_SIDE_KERNELS_6(X) X(KF1B<DynPlan>) X(KI2B<DynPlan>)
+#define SM_SIDE_KERNELS_6(X) X(KF1B<DynPlan>)
+#define SM_SIDE_KERNELS_20(X) X(KI2B<DynPlan>)
 
 }  // namespace smhip

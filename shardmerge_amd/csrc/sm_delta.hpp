@@ -11,7 +11,8 @@
 //   radix_bin, hist_zero, hist_flush  one level of its histograms in LDS
 // A kernel of an operator is these plus the lines that ARE the operator: its keep test, its scale, its extra loads.
 #pragma once
-#include "sm_kernels.hpp"
+#include "sm_common.hpp"
+#include "sm_tag.hpp"
 
 namespace smhip {
 

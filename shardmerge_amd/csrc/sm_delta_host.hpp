@@ -12,7 +12,6 @@
 #include <vector>
 
 #include "../../include/shardmerge_hip.h"
-#include "sm_kernels.hpp"
 #include "sm_ties.hpp"
 #include "sm_dare.hpp"
 #include "sm_breadcrumbs.hpp"

@@ -40,7 +40,8 @@
 #pragma once
 #include <cmath>
 
-#include "sm_kernels.hpp"
+#include "sm_common.hpp"
+#include "sm_tag.hpp"
 
 namespace smhip {
 

@@ -21,6 +21,7 @@
 // The kernels hold the k deltas of an octet in registers, KR of them: KR = 4 serves k <= 4, KR = 16 any k (same source).
 #pragma once
 #include "sm_geo.hpp"
+#include "sm_ties.hpp"        // (TiesSelectState)
 
 namespace smhip {
 

@@ -1,11 +1,12 @@
 // smhip_device.hpp - DeviceExec (one real gfx950 work-group per block) and the
 // generic __global__ entry point; shared by smhip_hip.hip, smhip_side.hip and smhip_inst.hip.
-// Each kernel's tag stands at the end of the header that defines the kernel; what each
-// translation unit instantiates is listed at the end of this file.
+// Each kernel's tag stands at the end of the header that defines the kernel; which header each
+// translation unit compiles from is listed at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 
-#include "sm_pipeline.hpp"
+#include "fft_engine.hpp"        // (static_for)
 
 namespace smhip {
 
@@ -95,35 +96,47 @@ __global__ void __launch_bounds__(K::max_threads, K::waves) sm_kernel(const type
 }
 
 // Every kernel is instantiated in exactly one translation unit and smhip_hip.hip holds host code only (it declares
-// them all extern, and the Makefile fails the build if main.o defines one): the build parallelises and a change to the
-// host orchestration does not recompile a single kernel.
-// The static-plan transform kernels: smhip_inst.hip, one translation unit per plan of SM_STATIC_PLANS (sm_pipeline.hpp).
+// them all extern, and the Makefile fails the build if main.o defines one).  A kernel unit includes this header and the
+// header its kernels come from, never the host orchestration (sm_pipeline.hpp, sm_delta_host.hpp, sm_capi.inc), and
+// the Makefile rebuilds a unit when a file it includes changes: the build parallelises, a change to the host
+// orchestration recompiles main.o alone, and a change to one operator's header that operator's group and main.o.
+// The static-plan transform kernels: smhip_inst.hip, one translation unit per plan of SM_STATIC_PLANS (sm_plans.hpp).
 #define SM_FFT_KERNELS_OF(X, ...)                      \
     X(KF1<__VA_ARGS__>) X(KF2<__VA_ARGS__>) X(KI1x1<__VA_ARGS__>) X(KI1x2<__VA_ARGS__>) X(KI2<__VA_ARGS__>) X(KF2S<__VA_ARGS__>) \
     X(KF1Q<__VA_ARGS__>) X(KF2Q<__VA_ARGS__>) X(KF2SQ<__VA_ARGS__>) X(KI1x1Q<__VA_ARGS__>) X(KI1x2Q<__VA_ARGS__>) \
     X(KPair1d<__VA_ARGS__>) X(KF1B<__VA_ARGS__>) X(KI2B<__VA_ARGS__>)
-// Every other kernel: smhip_side.hip, one translation unit per group g (-DSM_SIDE_GROUP=<g>) of SM_SIDE_KERNELS_<g>,
-// which the header that defines the group's kernels states after their tags.  The groups:
-//    0  the torch.norm emulation (sm_aten_norm.hpp)
-//    1  the selection and reduction kernels of the spectral pipeline (sm_kernels.hpp)
-//    2  its blend, norm, layout and element-wise kernels (sm_kernels.hpp) and the LoRA / DoRA update (sm_lora.hpp)
-//    3 - 6  the transform kernels for run-time planned lengths, SM_FFT_KERNELS_OF(X, DynPlan) in four parts
-//       (sm_kernels.hpp; 6, the row passes of a length without a plan: sm_bluestein.hpp)
-//    7  the delta and geometric merges: TIES, DARE, Breadcrumbs, Model Stock / SLERP / NuSLERP, the Karcher-mean merges,
-//       SCE, DELLA and Consensus (sm_ties.hpp .. sm_consensus.hpp, a sub-list each)
-//    8  the task-vector statistics (sm_stats.hpp)       9  the low-rank extraction (sm_extract.hpp)
-//   10  the pairwise fusion (sm_fusion.hpp)            11  the PCB merge (sm_pcb.hpp)
-//   12  the TSV merge (sm_tsv.hpp)                     13  the WIDEN merge (sm_widen.hpp)
-//   14  the CABS merge (sm_cabs.hpp)                   15  the Iso-C merge (sm_iso.hpp)
-//   16  the delta pack (sm_dpack.hpp)
-// A new group: its SM_SIDE_KERNELS_<g>, one more entry in SM_SIDE_KERNELS_ALL, and SM_SIDE_GROUPS (the Makefile reads it).
-#define SM_SIDE_KERNELS_2(X) SM_KERNELS_MERGE(X) SM_KERNELS_LORA(X)
-#define SM_SIDE_KERNELS_7(X) SM_KERNELS_TIES(X) SM_KERNELS_DARE(X) SM_KERNELS_CRUMBS(X) SM_KERNELS_GEO(X) SM_KERNELS_SPHERE(X) \
-    SM_KERNELS_SCE(X) SM_KERNELS_DELLA(X) SM_KERNELS_CONSENSUS(X)
-#define SM_SIDE_GROUPS 17
+// Every other kernel: smhip_side.hip, one translation unit per group g (-DSM_SIDE_GROUP=<g>).  It includes
+// SM_SIDE_HEADER_<g> and instantiates SM_SIDE_KERNELS_<g>, which that header states after its kernels' tags.
+// (3 - 6 and 17 - 20 are SM_FFT_KERNELS_OF(X, DynPlan), the transforms of run-time planned lengths; the row passes
+//  among them take a minute or more each to compile and stand one to a group.)
+#define SM_SIDE_HEADER_0 "sm_aten_norm.hpp"      // the torch.norm emulation
+#define SM_SIDE_HEADER_1 "sm_side_1.hpp"         // the selection and reduction kernels, the _r1 column passes
+#define SM_SIDE_HEADER_2 "sm_side_2.hpp"         // the blend, norm, layout and element-wise kernels, the LoRA / DoRA update
+#define SM_SIDE_HEADER_3 "sm_kernels.hpp"        // DynPlan: the forward row pass
+#define SM_SIDE_HEADER_4 "sm_kernels.hpp"        // DynPlan: the forward column passes
+#define SM_SIDE_HEADER_5 "sm_kernels.hpp"        // DynPlan: the inverse column passes
+#define SM_SIDE_HEADER_6 "sm_bluestein.hpp"      // DynPlan: the forward row pass of a length without a plan
+#define SM_SIDE_HEADER_7 "sm_side_7.hpp"         // the delta and geometric merges: TIES ... Consensus, a sub-list each
+#define SM_SIDE_HEADER_8 "sm_stats.hpp"          // the task-vector statistics
+#define SM_SIDE_HEADER_9 "sm_extract.hpp"        // the low-rank extraction
+#define SM_SIDE_HEADER_10 "sm_fusion.hpp"        // the pairwise fusion
+#define SM_SIDE_HEADER_11 "sm_pcb.hpp"           // the PCB merge
+#define SM_SIDE_HEADER_12 "sm_tsv.hpp"           // the TSV merge
+#define SM_SIDE_HEADER_13 "sm_widen.hpp"         // the WIDEN merge
+#define SM_SIDE_HEADER_14 "sm_cabs.hpp"          // the CABS merge
+#define SM_SIDE_HEADER_15 "sm_iso.hpp"           // the Iso-C merge
+#define SM_SIDE_HEADER_16 "sm_dpack.hpp"         // the delta pack
+#define SM_SIDE_HEADER_17 "sm_kernels.hpp"       // DynPlan: the folded forward row pass
+#define SM_SIDE_HEADER_18 "sm_kernels.hpp"       // DynPlan: the inverse row pass
+#define SM_SIDE_HEADER_19 "sm_kernels.hpp"       // DynPlan: the 1-D pair merge
+#define SM_SIDE_HEADER_20 "sm_bluestein.hpp"     // DynPlan: the inverse row pass of a length without a plan
+// A new group: its SM_SIDE_HEADER_<g> and SM_SIDE_KERNELS_<g>, one more entry in SM_SIDE_KERNELS_ALL, and SM_SIDE_GROUPS
+// (the Makefile reads it).
+#define SM_SIDE_GROUPS 21
 #define SM_SIDE_KERNELS_ALL(X)                                                                                       \
     SM_SIDE_KERNELS_0(X) SM_SIDE_KERNELS_1(X) SM_SIDE_KERNELS_2(X) SM_SIDE_KERNELS_3(X) SM_SIDE_KERNELS_4(X) SM_SIDE_KERNELS_5(X)     \
     SM_SIDE_KERNELS_6(X) SM_SIDE_KERNELS_7(X) SM_SIDE_KERNELS_8(X) SM_SIDE_KERNELS_9(X) SM_SIDE_KERNELS_10(X) SM_SIDE_KERNELS_11(X)   \
-    SM_SIDE_KERNELS_12(X) SM_SIDE_KERNELS_13(X) SM_SIDE_KERNELS_14(X) SM_SIDE_KERNELS_15(X) SM_SIDE_KERNELS_16(X)
+    SM_SIDE_KERNELS_12(X) SM_SIDE_KERNELS_13(X) SM_SIDE_KERNELS_14(X) SM_SIDE_KERNELS_15(X) SM_SIDE_KERNELS_16(X) SM_SIDE_KERNELS_17(X) \
+    SM_SIDE_KERNELS_18(X) SM_SIDE_KERNELS_19(X) SM_SIDE_KERNELS_20(X)
 
 }  // namespace smhip

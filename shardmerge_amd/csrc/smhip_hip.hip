@@ -11,6 +11,10 @@
 #include <vector>
 
 #include "smhip_device.hpp"
+#include "sm_pipeline.hpp"
+#include "sm_side_1.hpp"
+#include "sm_side_2.hpp"
+#include "sm_side_7.hpp"
 
 #define SM_VERSION_STRING "shardmerge-hip 0.1 (gfx950)"
 

@@ -1,6 +1,9 @@
 // smhip_inst.hip - explicit instantiation of the five transform kernels for ONE
 // static plan, selected with -DSM_PLAN_INDEX=<i> (order of SM_STATIC_PLANS).
 #include "smhip_device.hpp"
+#include "sm_plans.hpp"
+#include "sm_kernels.hpp"
+#include "sm_bluestein.hpp"
 
 namespace smhip {
 #define SM_INST(...) template __global__ void sm_kernel<__VA_ARGS__>(const typename __VA_ARGS__::Params);

@@ -1,6 +1,6 @@
 // smhip_emul.cpp - CPU work-group emulator of the HIP kernels (TEST INFRASTRUCTURE).
 //
-// Compiles the very same kernel bodies (shardmerge_amd/csrc/sm_kernels.hpp) and
+// Compiles the very same kernel bodies (the kernel headers of shardmerge_amd/csrc) and
 // the same host orchestration (sm_pipeline.hpp) with g++, running each
 // work-group's threads one after another between barriers.  It exists so that
 // the "not gpu" test tier can check indexing, planning and the tournament logic

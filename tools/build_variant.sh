@@ -11,20 +11,17 @@ UNITS=${@:-3 6 11}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$ROOT/shardmerge_amd/csrc
 OUT=$ROOT/exp_libs; mkdir -p $OUT/obj_$NAME
-BASE="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-variable -Wno-unused-but-set-variable"
-noslp="0 1 4 5 6 7 8 9 10 11 12 13 14 15 18 19"
-objs=""
-pids=""
+# the Makefile's own rules and per-unit flags, objects into a folder of this variant
+targets=""
 for u in $UNITS; do
     case $u in
-        main) cmd="/opt/rocm/bin/hipcc $BASE $FLAGS -c $SRC/smhip_hip.hip -o $OUT/obj_$NAME/main.o" ;;
-        side_*) g=${u#side_}; cmd="/opt/rocm/bin/hipcc $BASE $FLAGS -DSM_SIDE_GROUP=$g -c $SRC/smhip_side.hip -o $OUT/obj_$NAME/side_$g.o" ;;
-        *) pf=""; for n in $noslp; do [ "$n" = "$u" ] && pf="-fno-slp-vectorize"; done
-           cmd="/opt/rocm/bin/hipcc $BASE $pf $FLAGS -DSM_PLAN_INDEX=$u -c $SRC/smhip_inst.hip -o $OUT/obj_$NAME/inst_$u.o" ;;
+        main|side_*) targets="$targets $OUT/obj_$NAME/$u.o" ;;
+        *) targets="$targets $OUT/obj_$NAME/inst_$u.o" ;;
     esac
-    $cmd & pids="$pids $!"
 done
-for p in $pids; do wait $p; done
+rm -f $targets      # (the flags may differ from this variant's last build)
+make -C $SRC -j8 BUILD=$OUT/obj_$NAME EXTRA="$FLAGS" $targets
+objs=""
 for f in $SRC/build/main.o $SRC/build/side_[0-9]*.o $SRC/build/inst_*.o; do
     b=$(basename $f)
     if [ -f $OUT/obj_$NAME/$b ]; then objs="$objs $OUT/obj_$NAME/$b"; else objs="$objs $f"; fi

@@ -5,17 +5,20 @@ usage: tools/resource_report.py <plan index in SM_STATIC_PLANS> [extra hipcc fla
 import re
 import subprocess
 import sys
+import tempfile
 from pathlib import Path
 
 csrc = Path(__file__).resolve().parents[1] / "shardmerge_amd" / "csrc"
 idx = sys.argv[1] if len(sys.argv) > 1 else "6"
-if idx.startswith("side"):       # (the Makefile's flags for these translation units: no -fno-slp-vectorize)
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", *sys.argv[2:],
-           "-Rpass-analysis=kernel-resource-usage", f"-DSM_SIDE_GROUP={idx[4:]}", "-c", "smhip_side.hip", "-o", f"/tmp/resource_report_{idx}.o"]
-else:
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-slp-vectorize", *sys.argv[2:],
-           "-Rpass-analysis=kernel-resource-usage", f"-DSM_PLAN_INDEX={idx}", "-c", "smhip_inst.hip", "-o", f"/tmp/resource_report_{idx}.o"]
-txt = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True).stderr
+# the Makefile's own rule and flags for the unit (so -fno-slp-vectorize for the plans that are built with it, and only
+# for those), into a temporary folder
+with tempfile.TemporaryDirectory(prefix="resource_report_") as build:
+    obj = f"{build}/side_{idx[4:]}.o" if idx.startswith("side") else f"{build}/inst_{idx}.o"
+    extra = " ".join(["-Rpass-analysis=kernel-resource-usage", *sys.argv[2:]])
+    r = subprocess.run(["make", f"BUILD={build}", f"EXTRA={extra}", obj], cwd=csrc, capture_output=True, text=True)
+if r.returncode != 0:
+    sys.exit(r.stdout + r.stderr)
+txt = r.stderr
 
 
 def field(blk, key):
