@@ -1369,6 +1369,96 @@ typedef struct {
 /* out: device, dtype, [rows][cols]; it must not overlap an input */
 int smhip_dpack_apply(smhip_ctx* ctx, const smhip_dpack_apply_desc* desc, void* out, void* stream);
 
+/* ---- EMR-Merging (Huang et al., "EMR-Merging: Tuning-Free High-Performance Model Merging", NeurIPS 2024; as recalled:
+ *      PAPERS.md): ONE unified task vector is ELECTED from the finetunes' deltas - per element the sign of their sum and
+ *      the largest magnitude among the entries of that sign - and every task gets a 1-bit MASK (where its own delta
+ *      agrees in sign with the unified one) and ONE RESCALER on top of it, which recover a model for that task.  The
+ *      reference has no such operator; this section IS its definition.  Three functions: the unified model
+ *      (smhip_emr_merge), a task's modulator from (finetune, base, unified model) (smhip_emr_mask), and the task's
+ *      tensor from (base, unified model, mask, rescaler) (smhip_emr_apply).
+ *      MERGE, smhip_emr_merge.  One tensor of n elements (any shape, flat), finetunes i = 0..k-1 in order (1 <= k <= 16):
+ *        1. d_i = fl32(fp32(finetune_i) - fp32(base_i)), each entry against its own base.  A NaN or Inf in any d_i fails
+ *           the call with SMHIP_ERR_NONFINITE (the message lists the finetunes); out is then unspecified.
+ *        2. S = ((+0 + d_0) + d_1) + ... in fp32, in order.  A NaN or Inf in S fails the call the same way.
+ *           pos = S >= 0: the rule of smhip_ties_merge, an exact zero sum elects plus (the authors' code, as recalled,
+ *           takes sum > 0; the deviation is stated in PAPERS.md).
+ *        3. eps = the largest |d_i| over the entries with d_i > 0 (pos) or d_i < 0 (not pos), +0 when there is none;
+ *           w = the smallest such i that attains it.
+ *        4. tau = pos ? eps : -eps, and +0 when eps == 0: tau is +0 or exactly one of the d_i.
+ *        5. out = round_to(base_out_dtype, fp32(base_out) + fl32(fp32(lambda) * tau)), delta_out = fl32(lambda * tau):
+ *           step 7 of smhip_ties_merge.  The method has no weights: alpha is not read.
+ *      Nothing rounds between 1 and 4 but the subtraction and the sum: the result is defined bit for bit.  k == 1 is
+ *      smhip_dare_merge (sign_election 0) at density 1 with alpha 1 and the same lambda.  The report: n; elected_pos,
+ *      elected_neg (eps > 0 and pos / not pos) and zero (eps == 0), which sum to n; contested (elements with non-zero
+ *      entries of both signs); winner[i] (elements with w == i; with zero they sum to n); agree[i] (elements where
+ *      d_i != 0 has the sign of tau).  ONE kernel, one pass over the inputs (k + 2 tensor passes): the k deltas of an
+ *      element stay in registers between the sum and the maximum, no finetune is read twice.  Counters are integers
+ *      (LDS, then one global atomic per counter and work-group), no floating-point atomics; the call synchronises the
+ *      stream once, at its end.  Aliasing, alignment, n == 0, dtypes and the size limit: the rules of smhip_ties_merge.
+ *      SMHIP_ERR_ARG: k outside 1..16, lambda not finite, out overlapping an input, a bad dtype, a null descriptor.
+ *      MASK, smhip_emr_mask.  The tensor is seen as R = rows rows of C = cols elements as smhip_dpack_pack sees it:
+ *        1. d = fl32(fp32(finetune) - fp32(base)), u = fl32(fp32(unified) - fp32(base)).  A NaN or Inf in d or u fails
+ *           the call with SMHIP_ERR_NONFINITE (the message says which); the outputs are then unspecified.
+ *        2. m = (d > 0 and u > 0) or (d < 0 and u < 0): the signs are compared, no product is formed (it underflows).
+ *           mask, uint8 [R][ceil(C / 8)]: bit c % 8 of byte c / 8 of row r is m of element (r, c); padding bits are 0.
+ *        3. Seven sums per row, fp64, in exactly the order of step 4 of smhip_dpack_pack (lane o % 256, ascending, the
+ *           binary tree, rows added in ascending order from +0); the product of two fp32 values is exact in fp64:
+ *           A = sum |d|, B = sum over m of |u|, D2 = sum d d, X = sum over m of d u, U2 = sum over m of u u, and the
+ *           integer counts c = sum m, nz = sum [d != 0].
+ *        4. lambda = fp32(A / B), +0 when B == 0: the paper's rescaler sum |tau_t| / sum |M_t . tau_uni| of this tensor
+ *           (a caller that wants one rescaler for a whole model adds A and B over its tensors).  scale: float [1].
+ *        5. resid_sq = max((D2 - 2 (lambda X)) + (lambda lambda) U2, 0), one IEEE fp64 operation at a time, no fused
+ *           multiply-add: sum (d - lambda m u)^2.  delta_sq = D2.
+ *      n == 0: the plane has no byte, lambda is +0, the report is zero.  SMHIP_ERR_ARG: a bad dtype, a null or
+ *      misaligned pointer, an output that overlaps an input, a tensor too large.  One synchronisation, at the end.
+ *      APPLY, smhip_emr_apply.  Per element: mask bit clear: base bit for bit, a -0 included.  Set: u = fl32(fp32(unified)
+ *      - fp32(base)), t = fl32(lambda * u), out = round_to(dtype, fp32(base) + t), one rounding each; lambda = scale[0].
+ *      Padding bits are not read as elements.  It does not synchronise.  C % 8 == 0 with 16-byte aligned tensors moves
+ *      them in 16-byte accesses; anything else goes element by element and is as exact.
+ *      Profile names: "emr_merge"; "emr_mask", "geo_gram_fold"; "emr_apply". ---- */
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [n] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];         /* not read (the layout of the other merge descriptors) */
+    int in_dtype;                           /* SMHIP_BF16 / F16 / F32, finetunes and their bases */
+    const void* base_out; int base_out_dtype;
+    size_t n;
+    double lambda;
+} smhip_emr_desc;
+typedef struct {
+    uint64_t n;
+    uint64_t elected_pos, elected_neg, zero, contested;
+    uint64_t winner[SMHIP_MAX_MODELS];
+    uint64_t agree[SMHIP_MAX_MODELS];
+} smhip_emr_report;
+/* out: device, base_out_dtype, [n].  delta_out (optional): device float [n], fl32(lambda * tau).  report (optional): HOST. */
+int smhip_emr_merge(smhip_ctx* ctx, const smhip_emr_desc* desc, void* out, float* delta_out, smhip_emr_report* report,
+                    void* stream);
+typedef struct {
+    const void* finetune; const void* base; const void* unified; /* device, dtype, [rows][cols] */
+    int dtype;                              /* SMHIP_BF16 / F16 / F32 */
+    size_t rows, cols;
+} smhip_emr_mask_desc;
+typedef struct {
+    uint64_t rows, cols;
+    double A, B, D2, X, U2;
+    uint64_t c, nonzero;
+    float lambda;
+    double delta_sq, resid_sq;
+} smhip_emr_mask_report;
+/* mask: device uint8 [rows][ceil(cols / 8)].  scale: device float [1].  report (optional): HOST. */
+int smhip_emr_mask(smhip_ctx* ctx, const smhip_emr_mask_desc* desc, uint8_t* mask, float* scale,
+                   smhip_emr_mask_report* report, void* stream);
+typedef struct {
+    const void* base; const void* unified; int dtype; /* device, [rows][cols] */
+    size_t rows, cols;
+    const uint8_t* mask;                    /* device uint8 [rows][ceil(cols / 8)] */
+    const float* scale;                     /* device float [1] */
+} smhip_emr_apply_desc;
+/* out: device, dtype, [rows][cols]; it must not overlap an input */
+int smhip_emr_apply(smhip_ctx* ctx, const smhip_emr_apply_desc* desc, void* out, void* stream);
+
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
  *      cosine_similarity(t_i, t_j, dim=0).nan_to_num(0); zero diagonal.  tensors: k (2..8) device

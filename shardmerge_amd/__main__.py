@@ -189,5 +189,36 @@ def compress_delta_command(model: str, base: str, out_dir: Path, storage_dir: Pa
     click.echo(f"delta pack: {out_dir}")
 
 
+@cli.command("emr-task")
+@click.argument("model", type=str)
+@click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")
+@click.option("--unified", required=True, type=str, help="The unified model of an `operator: emr` merge (under the storage directory)")
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the EMR pack is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL, BASE and the unified model live")
+@click.option("--scale", type=click.Choice(["model", "tensor"]), default="model", help="One rescaler for the whole model, or one per tensor")
+@click.option("--full", "full", type=str, default=None, help="Store whole the tensors whose name ends in one of these, comma-separated")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def emr_task_command(model: str, base: str, unified: str, out_dir: Path, storage_dir: Path, scale: str, full: Optional[str],
+                     device: str, verbose: bool):
+    """The modulator of task MODEL on an EMR-Merging merge: per tensor a 1-bit mask and one rescaler.
+
+    DIR receives emr_model.safetensors, emr_config.json and emr_task.json (per tensor the mask's count, the rescaler and
+    the relative residual); it can be named as a finetune_merge entry of `merge` in place of MODEL.
+    """
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.emr_task import format_table, parse_suffixes, run_emr_task
+        result = asyncio.run(run_emr_task(model, base, unified, out_dir, storage_dir, scale, parse_suffixes(full), device))
+    except Exception as exc:
+        logging.error(f"Error during emr-task: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"EMR pack: {out_dir}")
+
+
 if __name__ == "__main__":
     cli()

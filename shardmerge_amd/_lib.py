@@ -354,6 +354,36 @@ class DpackReport(C.Structure):
                 ("kept", C.c_uint64), ("nonzero", C.c_uint64), ("delta_sq", C.c_double), ("resid_sq", C.c_double)]
 
 
+class EmrDesc(C.Structure):
+    """smhip_emr_desc: the leading fields of smhip_ties_desc up to n, then lambda"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("lam", C.c_double)]
+
+
+class EmrReport(C.Structure):
+    """smhip_emr_report"""
+    _fields_ = [("n", C.c_uint64), ("elected_pos", C.c_uint64), ("elected_neg", C.c_uint64), ("zero", C.c_uint64),
+                ("contested", C.c_uint64), ("winner", C.c_uint64 * MAX_MODELS), ("agree", C.c_uint64 * MAX_MODELS)]
+
+
+class EmrMaskDesc(C.Structure):
+    """smhip_emr_mask_desc"""
+    _fields_ = [("finetune", C.c_void_p), ("base", C.c_void_p), ("unified", C.c_void_p), ("dtype", C.c_int),
+                ("rows", C.c_size_t), ("cols", C.c_size_t)]
+
+
+class EmrMaskReport(C.Structure):
+    """smhip_emr_mask_report"""
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("A", C.c_double), ("B", C.c_double), ("D2", C.c_double),
+                ("X", C.c_double), ("U2", C.c_double), ("c", C.c_uint64), ("nonzero", C.c_uint64), ("lam", C.c_float),
+                ("delta_sq", C.c_double), ("resid_sq", C.c_double)]
+
+
+class EmrApplyDesc(C.Structure):
+    """smhip_emr_apply_desc"""
+    _fields_ = [("base", C.c_void_p), ("unified", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t),
+                ("mask", C.c_void_p), ("scale", C.c_void_p)]
+
+
 class DpackApplyDesc(C.Structure):
     """smhip_dpack_apply_desc"""
     _fields_ = [("base", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t),
@@ -450,6 +480,9 @@ class SmhipLibrary:
         d.smhip_iso_gemm.argtypes = [P, C.POINTER(IsoGemmDesc), P]
         d.smhip_dpack_pack.argtypes = [P, C.POINTER(DpackDesc), P, P, P, C.POINTER(DpackReport), P]
         d.smhip_dpack_apply.argtypes = [P, C.POINTER(DpackApplyDesc), P, P]
+        d.smhip_emr_merge.argtypes = [P, C.POINTER(EmrDesc), P, P, C.POINTER(EmrReport), P]
+        d.smhip_emr_mask.argtypes = [P, C.POINTER(EmrMaskDesc), P, P, C.POINTER(EmrMaskReport), P]
+        d.smhip_emr_apply.argtypes = [P, C.POINTER(EmrApplyDesc), P, P]
         d.smhip_debug_option.argtypes =[P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

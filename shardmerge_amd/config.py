@@ -171,6 +171,14 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # iso_lambda: 1.0         #   scales the merged delta
       # iso_tol: 0.0001         #   0 < iso_tol <= 1: the iteration stops at ||X X^T - I||_F / sqrt(min(rows, cols)) <= iso_tol
       # iso_max_iter: 40        #   an integer in 0..200: steps at most (reaching it is reported, not an error)
+                                # | emr (EMR-Merging, Huang et al. 2024; no counterpart in the reference): the UNIFIED model -
+                                #   per element the deltas are summed, the sign of the sum is elected (a zero sum elects
+                                #   plus), and the entry of that sign with the largest magnitude is taken as it is.  It takes
+                                #   no weight: an entry alpha other than 1 is rejected.  A task's 1-bit mask and its rescaler
+                                #   are computed afterwards by `python -m shard emr-task` from the finetune, its base and the
+                                #   merged model.  The spectral keys, norm_mode, task_add_models and every other family's keys
+                                #   are rejected; the one key:
+      # emr_lambda: 1.0         #   scales the elected delta
 
 A finetune_merge `model` may also name a LoRA adapter directory (adapter_config.json +
 adapter_model.safetensors, no model.safetensors.index.json): the entry then stands for
@@ -178,7 +186,10 @@ base + s * lora_B @ lora_A applied to its own `base` (shardmerge_amd/adapter.py)
 factors transposed, DoRA (use_dora) rows rescaled to their magnitude vector.  Same keys; no new
 option.  Or a delta pack directory (delta_config.json + delta_model.safetensors, written by
 `python -m shard compress-delta`): the entry then stands for its `base` plus or minus a scale per
-row where the pack's planes keep an element (shardmerge_amd/deltapack.py).  Same keys; no new option.
+row where the pack's planes keep an element (shardmerge_amd/deltapack.py).  Same keys; no new option.  Or an EMR pack
+directory (emr_config.json + emr_model.safetensors, written by `python -m shard emr-task`): the entry then stands for
+its `base` moved towards the pack's unified model by the pack's rescaler where the pack's mask is set
+(shardmerge_amd/emrpack.py).  Same keys; no new option.
 """
 from __future__ import annotations
 
@@ -200,7 +211,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs", "iso_c")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs", "iso_c", "emr")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -233,6 +244,8 @@ WIDEN_MAX_COLS = 65536                              # columns of a block tensor 
 ISO_OPERATORS = ("iso_c",)
 ISO_OPTION_DEFAULTS = {"iso_lambda": 1.0, "iso_tol": 1e-4, "iso_max_iter": 40}
 ISO_MAX_S = 16384                                   # min(rows, cols) of a block tensor at most
+EMR_OPERATORS = ("emr",)                            # the elected unified model; it takes no weights
+EMR_OPTION_DEFAULTS = {"emr_lambda": 1.0}
 TSV_MAX_VECTORS = 256                               # k * min(tsv_rank, rows, cols) at most: the width of the whitened panels
 
 
@@ -397,6 +410,15 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "della": "(it drops nothing at random)",
                            "consensus_ta": "(it masks nothing)",
                            "arcee_fusion": "(it merges several models by the spectrum of their summed delta)"}),
+    _OptionFamily(EMR_OPERATORS, EMR_OPTION_DEFAULTS, {"emr_lambda": _LAMBDA},
+                  earlier={"ties": "(it trims nothing and takes the largest agreeing entry: emr_lambda)",
+                           "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it trims nothing)",
+                           "model_stock": "(it takes no weights and elects one entry per element)",
+                           "sce": "(it selects nothing by variance)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(its masks are per task, computed by emr-task afterwards)",
+                           "arcee_fusion": "(it merges several models by election)"}),
 )
 
 
@@ -596,7 +618,7 @@ class MergeConfig:
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
                 raise click.BadParameter(f"operator tsv needs finetune_merge alphas >= 0 with a sum > 0 (an alpha scales the "
                                          f"finetune's singular values; 0 leaves the finetune out), not {alphas}")
-        if operator in FUSION_OPERATORS:
+        if operator in FUSION_OPERATORS + EMR_OPERATORS:
             for m in raw["finetune_merge"]:
                 if isinstance(m.alpha, bool) or not isinstance(m.alpha, (int, float)) or m.alpha != 1:
                     raise click.BadParameter(f"operator {operator} takes no weight: finetune_merge alpha of {m.model} must be 1 "

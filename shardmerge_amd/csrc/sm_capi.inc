@@ -671,6 +671,43 @@ int smhip_dpack_apply(smhip_ctx* ctx, const smhip_dpack_apply_desc* d, void* out
     SM_FINISH(ctx, ctx->pipe.delta.dpack_apply(*d, out));
 }
 
+int smhip_emr_merge(smhip_ctx* ctx, const smhip_emr_desc* d, void* out, float* delta_out, smhip_emr_report* report,
+                    void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "emr_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            return nullptr;
+        }))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.emr_merge(*d, out, delta_out, report));
+}
+
+int smhip_emr_mask(smhip_ctx* ctx, const smhip_emr_mask_desc* d, uint8_t* mask, float* scale, smhip_emr_mask_report* report,
+                   void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "emr_mask: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols, plane = d->rows * ((d->cols + 7) / 8);
+    if (int rc = dpack_check(ctx, "emr_mask", d->dtype, d->rows, d->cols, SMHIP_DPACK_TENSOR,
+                             {{d->finetune, n * es, es}, {d->base, n * es, es}, {d->unified, n * es, es}},
+                             {{mask, plane, 1}, {scale, 4, 4}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.emr_mask(*d, mask, scale, report));
+}
+
+int smhip_emr_apply(smhip_ctx* ctx, const smhip_emr_apply_desc* d, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "emr_apply: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols, plane = n ? d->rows * ((d->cols + 7) / 8) : 0;
+    if (int rc = dpack_check(ctx, "emr_apply", d->dtype, d->rows, d->cols, SMHIP_DPACK_TENSOR,
+                             {{d->base, n * es, es}, {d->unified, n * es, es}, {d->mask, plane, 1}, {d->scale, n ? (size_t)4 : (size_t)0, 4}},
+                             {{out, n * es, es}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.emr_apply(*d, out));
+}
+
 int smhip_tsv_probe(smhip_ctx* ctx, const float* b, const float* w, int rows, int cols, int Rp, const void* base_out,
                     int base_out_dtype, double lambda, void* out, float* delta_out, void* stream) {
     SM_GUARD(ctx);

@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction and the delta pack (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack and EMR-Merging (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -29,6 +29,7 @@
 #include "sm_cabs.hpp"
 #include "sm_iso.hpp"
 #include "sm_dpack.hpp"
+#include "sm_emr.hpp"
 
 namespace smhip {
 
@@ -1684,6 +1685,97 @@ class DeltaHost {
         p.out = out; p.row_vec = dpack_row_vec(C, d.base, out);
         p.chunks = pick_chunks(p.units, 256, 2, 8);
         be.template launch<KDpackApply>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
+        return SMHIP_OK;
+    }
+
+    // ---- EMR-Merging (sm_emr.hpp; smhip_emr_merge, smhip_emr_mask, smhip_emr_apply).  The unified model: no select, one
+    // kernel, the workspace is EmrReadback alone.  A task's mask: the fused pass over whole rows, the fold of the rows'
+    // partials, ONE readback; the rescaler and the residual are formed here from the seven totals.
+    // Workspace of the mask: EmrMaskHead | the rows' partials [R][7] ----
+    struct EmrReadback {
+        unsigned long long agree[TIES_MAX_MODELS], winner[TIES_MAX_MODELS], counts[EMR_COUNTS];
+        uint32_t flags[2];
+    };
+    int emr_merge(const smhip_emr_desc& d, void* out, float* delta_out, smhip_emr_report* rep) {
+        const int k = d.k;
+        if (rep) {
+            *rep = smhip_emr_report{};
+            rep->n = d.n;
+        }
+        if (d.n == 0) return SMHIP_OK;
+        EmrReadback* w;
+        int rc;
+        if ((rc = plain_workspace(w))) return rc;
+
+        EmrMergeParams m;
+        delta_inputs(d, out, delta_out, false, m);
+        m.lambda = (float)d.lambda;
+        m.agree = w->agree; m.winner = w->winner; m.counts = w->counts; m.flags = w->flags;
+        const int grid = stream_grid((d.n + 7) / 8, 256, m.chunks);
+        const size_t lds = (LDS_SCRATCH_FLOATS + emr_lds_words(k, 256)) * 4;
+        if (k <= EMR_REG_SMALL) be.template launch<KEmrMerge>(grid, 256, lds, m, stream);
+        else be.template launch<KEmrMergeAny>(grid, 256, lds, m, stream);
+
+        EmrReadback host;
+        if ((rc = delta_readback("emr_merge", k, w, host))) return rc;     // the call's one synchronisation
+        if (host.flags[1]) return fail(SMHIP_ERR_NONFINITE, "emr_merge: NaN or Inf in the sum of the deltas");
+        if (rep) {
+            for (int i = 0; i < k; ++i) { rep->agree[i] = host.agree[i]; rep->winner[i] = host.winner[i]; }
+            rep->elected_pos = host.counts[EMR_POS]; rep->elected_neg = host.counts[EMR_NEG];
+            rep->zero = host.counts[EMR_ZERO]; rep->contested = host.counts[EMR_CONTESTED];
+        }
+        return SMHIP_OK;
+    }
+    struct EmrMaskHead { double tot[EMR_NP]; uint32_t flags[2]; };
+    static int emr_row_vec(size_t C, const void* a, const void* b, const void* c) {
+        return (C % 8 == 0 && aligned16(a) && aligned16(b) && aligned16(c)) ? 1 : 0;
+    }
+    int emr_mask(const smhip_emr_mask_desc& d, uint8_t* mask, float* scale, smhip_emr_mask_report* rep) {
+        const size_t R = d.rows, C = d.cols, n = R * C, PB = (C + 7) / 8;
+        if (rep) {
+            *rep = smhip_emr_mask_report{};
+            rep->rows = R; rep->cols = C;
+        }
+        if (n == 0) {                                    // the plane has no byte; the rescaler is +0
+            be.memset(scale, 0, sizeof(float), stream);
+            return SMHIP_OK;
+        }
+        EmrMaskHead* w;
+        const size_t off = round_up(sizeof(EmrMaskHead), 256);
+        int rc;
+        if ((rc = plain_workspace(w, off + R * EMR_NP * sizeof(double)))) return rc;
+        double* part = (double*)ws_at(off);
+
+        EmrMaskParams p;
+        p.ft = d.finetune; p.base = d.base; p.uni = d.unified; p.dtype = d.dtype;
+        p.R = R; p.C = C; p.PB = PB; p.mask = mask; p.row_vec = emr_row_vec(C, d.finetune, d.base, d.unified);
+        p.part = part; p.flags = w->flags;
+        be.template launch<KEmrMask>((int)std::min<size_t>(R, (size_t)1 << 20), EMR_THREADS, emr_mask_lds_floats() * 4, p, stream);
+        fold_pass<KGeoFold>(EMR_NP, R, part, w->tot);
+
+        EmrMaskHead host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the report stays as it is)
+        if (host.flags[0] & 1u) return fail(SMHIP_ERR_NONFINITE, "emr_mask: NaN or Inf in finetune - base");
+        if (host.flags[0] & 2u) return fail(SMHIP_ERR_NONFINITE, "emr_mask: NaN or Inf in unified - base");
+        const float l = emr_scale_of(host.tot[0], host.tot[1]);
+        be.h2d(scale, &l, sizeof l, stream);
+        if (rep) {
+            rep->A = host.tot[0]; rep->B = host.tot[1]; rep->D2 = host.tot[2]; rep->X = host.tot[3]; rep->U2 = host.tot[4];
+            rep->c = (uint64_t)host.tot[5]; rep->nonzero = (uint64_t)host.tot[6];
+            rep->lambda = l; rep->delta_sq = host.tot[2]; rep->resid_sq = emr_resid_of(host.tot[2], host.tot[3], host.tot[4], l);
+        }
+        return SMHIP_OK;
+    }
+    int emr_apply(const smhip_emr_apply_desc& d, void* out) {
+        const size_t R = d.rows, C = d.cols, PB = (C + 7) / 8;
+        if (R * C == 0) return SMHIP_OK;
+        EmrApplyParams p;
+        p.base = d.base; p.uni = d.unified; p.dtype = d.dtype; p.R = R; p.C = C; p.PB = PB; p.units = R * PB;
+        p.mask = d.mask; p.scale = d.scale;
+        p.out = out; p.row_vec = emr_row_vec(C, d.base, d.unified, out);
+        p.chunks = pick_chunks(p.units, 256, 2, 8);
+        be.template launch<KEmrApply>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         return SMHIP_OK;
     }
 

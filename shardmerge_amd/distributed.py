@@ -40,6 +40,7 @@ import torch
 
 from .adapter import ADAPTER_CONFIG, ADAPTER_WEIGHTS, is_adapter_dir, read_header
 from .deltapack import is_pack_dir, pack_identity
+from .emrpack import emr_identity, is_emr_dir
 from .config import MergeConfig
 from .constants import DEFAULT_NORM_MODE, INPUT_LAYER, OUTPUT_LAYER
 from .index import LocalModelIndex
@@ -190,6 +191,10 @@ def config_stamp(config: MergeConfig) -> str:
              if is_pack_dir(Path(config.storage_path) / m.model)}          # a delta pack's: its config and its tensors' header
     if packs:
         doc["delta_packs"] = packs
+    emrs = {m.model: emr_identity(Path(config.storage_path) / m.model) for m in config.finetune_merge
+            if is_emr_dir(Path(config.storage_path) / m.model)}            # an EMR pack's: its config and its tensors' header
+    if emrs:
+        doc["emr_packs"] = emrs
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 

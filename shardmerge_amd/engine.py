@@ -153,6 +153,33 @@ class ConsensusMergeReport:
 
 
 @dataclass
+class EmrReport:
+    n: int = 0                                                       # elements of the tensor
+    elected_pos: int = 0                                             # elements whose elected entry is positive
+    elected_neg: int = 0                                             # ... negative
+    zero: int = 0                                                    # elements with no entry of the elected sign (all deltas zero)
+    contested: int = 0                                               # elements with non-zero entries of both signs
+    winner: List[int] = field(default_factory=list)                  # elements whose elected entry is finetune i's (the first that attains it)
+    agree: List[int] = field(default_factory=list)                   # elements where finetune i's non-zero delta has the elected sign
+
+
+@dataclass
+class EmrMaskReport:
+    rows: int = 0                                                    # R: shape[0] (1 for a 0-D or 1-D tensor)
+    cols: int = 0                                                    # C: the rest
+    A: float = 0.0                                                   # sum |finetune - base| (fp64, ordered, as the rest)
+    B: float = 0.0                                                   # sum over the mask of |unified - base|
+    D2: float = 0.0                                                  # sum (finetune - base)^2
+    X: float = 0.0                                                   # sum over the mask of (finetune - base) (unified - base)
+    U2: float = 0.0                                                  # sum over the mask of (unified - base)^2
+    c: int = 0                                                       # mask bits set
+    nonzero: int = 0                                                 # elements where the finetune differs from its base
+    lam: float = 0.0                                                 # fp32(A / B), +0 when B == 0: this tensor's rescaler
+    delta_sq: float = 0.0                                            # D2
+    resid_sq: float = 0.0                                            # ||finetune - base - lam * mask * (unified - base)||^2
+
+
+@dataclass
 class FusionMergeReport:
     mode: str = "arcee"                                              # "arcee" (arcee_fusion) or "nearswap"
     n: int = 0                                                       # elements of the tensor
@@ -627,6 +654,76 @@ class Engine:
         desc = _lib.DpackApplyDesc(bs.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols, sg.data_ptr(),
                                    mk.data_ptr() if mk is not None else None, sc.data_ptr(), mode)
         self._call(self.lib.dll.smhip_dpack_apply(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()))
+        return out
+
+    # -- EMR-Merging: the unified model, a task's mask and rescaler, the task's tensor --------------
+    def emr_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], base_out: torch.Tensor, *,
+                  lam: float = 1.0, want_delta: bool = False, layer_name: str = ""):
+        """The unified model of EMR-Merging for one tensor of any shape (``smhip_emr_merge``; the function is stated in
+        include/shardmerge_hip.h): per element the deltas ``finetune_i - base_i`` are summed in order, the sign of the
+        sum is elected (zero elects plus), and the entry of that sign with the largest magnitude is taken as it is,
+        times ``lam``, added onto ``base_out`` in its dtype.  The method has no weights.  Returns (out, EmrReport[, the
+        fp32 merged delta]).  A NaN or Inf in a delta or in the sum raises ValueError naming ``layer_name``."""
+        layer_name = layer_name or "layer"
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(float(lam)):
+            raise ValueError(f"emr_merge: lam {lam!r} is not a finite number")
+        desc, rep, k = _lib.EmrDesc(), _lib.EmrReport(), len(finetunes)
+        desc.lam = float(lam)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, [1.0] * len(bases), base_out, layer_name,
+                                                       want_delta, "emr_merge")
+        desc.n = bo.numel()
+        self._run_delta_merge(self.lib.dll.smhip_emr_merge, desc, rep, out, delta, layer_name)
+        report = EmrReport(n=int(rep.n), elected_pos=int(rep.elected_pos), elected_neg=int(rep.elected_neg), zero=int(rep.zero),
+                           contested=int(rep.contested), winner=[int(rep.winner[i]) for i in range(k)],
+                           agree=[int(rep.agree[i]) for i in range(k)])
+        return (out, report, delta) if want_delta else (out, report)
+
+    def emr_mask(self, finetune: torch.Tensor, base: torch.Tensor, unified: torch.Tensor, *, name: str = ""):
+        """One task's modulator for one tensor (``smhip_emr_mask``): the mask of the elements where ``finetune - base``
+        and ``unified - base`` have the same sign, bit-packed as the delta pack's planes (uint8 [R, ceil(C / 8)]), and
+        the rescaler ``sum |finetune - base| / sum over the mask of |unified - base|`` as a float32 [1].  Returns
+        ``(mask, scale, EmrMaskReport)``; the report holds the ordered fp64 sums, from which a caller forms one rescaler
+        for a whole model.  A NaN or Inf in either delta raises ValueError naming ``name``."""
+        if not (finetune.shape == base.shape == unified.shape):
+            raise ValueError(f"emr_mask: shape mismatch in {name or 'tensor'}: {list(finetune.shape)} / {list(base.shape)} / "
+                             f"{list(unified.shape)}")
+        dtypes = {finetune.dtype, base.dtype, unified.dtype}
+        in_dtype = finetune.dtype if len(dtypes) == 1 and finetune.dtype in _DTYPE_CODE else torch.float32
+        ft, bs, un = self._dev(finetune, in_dtype), self._dev(base, in_dtype), self._dev(unified, in_dtype)
+        rows, cols = _shape_rows(ft)
+        mask = torch.empty((rows, (cols + 7) // 8), dtype=torch.uint8, device=self.device)
+        sc = torch.empty((1,), dtype=torch.float32, device=self.device)
+        desc = _lib.EmrMaskDesc(ft.data_ptr(), bs.data_ptr(), un.data_ptr(), _DTYPE_CODE[in_dtype], rows, cols)
+        rep = _lib.EmrMaskReport()
+        try:
+            self.ctx.check(self.lib.dll.smhip_emr_mask(self.ctx.h, C.byref(desc), mask.data_ptr(), sc.data_ptr(),
+                                                       C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {name or 'tensor'}: {e.message}") from e
+            raise
+        return mask, sc, EmrMaskReport(rows=rows, cols=cols, A=float(rep.A), B=float(rep.B), D2=float(rep.D2), X=float(rep.X),
+                                       U2=float(rep.U2), c=int(rep.c), nonzero=int(rep.nonzero), lam=float(rep.lam),
+                                       delta_sq=float(rep.delta_sq), resid_sq=float(rep.resid_sq))
+
+    def emr_apply(self, base: torch.Tensor, unified: torch.Tensor, mask: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+        """the task tensor an EMR modulator defines: ``base + scale * (unified - base)`` where the mask bit is set, one
+        rounding per operation and once into base's dtype, and ``base`` bit for bit elsewhere (``smhip_emr_apply``).
+        mask: uint8 [R, ceil(C / 8)]; scale: float32 [1]."""
+        if base.dtype not in _DTYPE_CODE:
+            raise ValueError(f"emr_apply: base is {base.dtype}; bf16, f16 or f32 expected")
+        if unified.dtype != base.dtype or unified.shape != base.shape:
+            raise ValueError(f"emr_apply: unified is {unified.dtype} {list(unified.shape)}; {base.dtype} {list(base.shape)} expected")
+        rows, cols = _shape_rows(base)
+        pb = (cols + 7) // 8
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (rows, pb):
+            raise ValueError(f"emr_apply: mask is {mask.dtype} {list(mask.shape)}; uint8 [{rows}, {pb}] expected for base {list(base.shape)}")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (1,):
+            raise ValueError(f"emr_apply: scale is {scale.dtype} {list(scale.shape)}; float32 [1] expected")
+        bs, un, mk, sc = self._dev(base), self._dev(unified), self._dev(mask), self._dev(scale)
+        out = torch.empty_like(bs)
+        desc = _lib.EmrApplyDesc(bs.data_ptr(), un.data_ptr(), _DTYPE_CODE[bs.dtype], rows, cols, mk.data_ptr(), sc.data_ptr())
+        self._call(self.lib.dll.smhip_emr_apply(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()))
         return out
 
     # -- extract-lora ------------------------------------------------------------------------

@@ -23,6 +23,7 @@ from safetensors import safe_open
 
 from .adapter import ADAPTER_BIN, AdapterError, LoraAdapter, is_adapter_dir, is_bin_only_adapter_dir
 from .deltapack import DeltaPack, is_pack_dir
+from .emrpack import EmrPack, is_emr_dir
 
 logger = logging.getLogger(__name__)
 
@@ -68,6 +69,7 @@ class LocalModelIndex:
         self._ordered_weights: Dict[str, List[str]] = {}
         self.adapters: Dict[str, LoraAdapter] = {}     # LoRA adapter directories (adapter.py), by model uri
         self.packs: Dict[str, DeltaPack] = {}          # delta pack directories (deltapack.py), by model uri
+        self.emrs: Dict[str, EmrPack] = {}             # EMR pack directories (emrpack.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -90,6 +92,15 @@ class LocalModelIndex:
             n_packed = sum(t.kind == "packed" for t in pack.tensors.values())
             logger.info(f"Model {model_uri}: {pack.bits}-bit delta pack, {n_packed} packed and {len(pack.tensors) - n_packed} whole tensors")
             return
+        if is_emr_dir(self.storage_path / model_uri):
+            # an EMR pack: its masks, rescalers and whole tensors load through the same weight map as a model's tensors
+            emr = EmrPack(model_uri, self.storage_path / model_uri)
+            self.emrs[model_uri] = emr
+            self.model_indexes[model_uri] = {"metadata": {}, "weight_map": emr.weight_map()}
+            self._ordered_weights[model_uri] = sorted(emr.weight_map())
+            n_masked = sum(t.kind == "masked" for t in emr.tensors.values())
+            logger.info(f"Model {model_uri}: EMR pack on {emr.unified}, {n_masked} masked and {len(emr.tensors) - n_masked} whole tensors")
+            return
         if is_bin_only_adapter_dir(self.storage_path / model_uri):
             raise AdapterError(f"LoRA adapter {model_uri}: only {ADAPTER_BIN} found; adapters are read from "
                                "adapter_model.safetensors")
@@ -109,6 +120,10 @@ class LocalModelIndex:
     def pack(self, model_uri: str) -> Optional[DeltaPack]:
         """the delta pack registered under this uri, None for a full model or an adapter"""
         return self.packs.get(model_uri)
+
+    def emr(self, model_uri: str) -> Optional[EmrPack]:
+        """the EMR pack registered under this uri, None for anything else"""
+        return self.emrs.get(model_uri)
 
     def _require(self, model_uri: str, tensor_name: Optional[str] = None) -> Dict:
         if model_uri not in self.model_indexes:

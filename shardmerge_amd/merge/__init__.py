@@ -29,6 +29,7 @@ _OPERATOR_CLASSES = {
     "widen": ("widen", "WidenMerge"),
     "cabs": ("cabs", "CabsMerge"),
     "iso_c": ("iso", "IsoMerge"),
+    "emr": ("emr", "EmrMerge"),
 }
 
 

@@ -47,7 +47,8 @@ class MergeTensorsBase(ABC):
     def _finetune_requests(self, m: MergeModel, layer_name: str) -> List[Tuple[str, str]]:
         """the (uri, tensor) reads `finetune_tensor` makes for entry m: the model's tensor; for a LoRA adapter entry its
         base's tensor and, when the adapter targets it, the two factors; for a delta pack entry its base's tensor and
-        the planes and scale, the tensor the pack stores whole, or the base's tensor alone"""
+        the planes and scale, the tensor the pack stores whole, or the base's tensor alone; for an EMR pack entry its
+        base's and the unified model's tensor, the mask and the rescaler, the whole tensor, or the base's tensor alone"""
         pack = self.index_manager.pack(m.model)
         if pack is not None:
             t = pack.tensors.get(layer_name)
@@ -57,6 +58,14 @@ class MergeTensorsBase(ABC):
                 return [(m.model, t.full_key)]
             return [(m.base, layer_name), (m.model, t.sign_key), (m.model, t.scale_key)] + \
                 ([(m.model, t.mask_key)] if t.mask_key is not None else [])
+        emr = self.index_manager.emr(m.model)
+        if emr is not None:
+            t = emr.tensors.get(layer_name)
+            if t is None:
+                return [(m.base, layer_name)]
+            if t.kind == "full":
+                return [(m.model, t.full_key)]
+            return [(m.base, layer_name), (emr.unified, layer_name), (m.model, t.mask_key), (m.model, t.scale_key)]
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return [(m.model, layer_name)]
@@ -72,7 +81,8 @@ class MergeTensorsBase(ABC):
         on the engine (embedding factors transposed; DoRA rows scaled to their magnitudes, where a zero or non-finite
         row norm raises AdapterError), or the base tensor itself where the adapter does not target it.  For a delta
         pack entry (deltapack.py) `Engine.delta_apply` on the base tensor and the planes, the tensor the pack stores
-        whole, or the base tensor itself where the pack holds nothing for it.
+        whole, or the base tensor itself where the pack holds nothing for it.  For an EMR pack entry (emrpack.py)
+        `Engine.emr_apply` on the base tensor, the unified model's tensor, the mask and the rescaler, likewise.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
@@ -89,6 +99,18 @@ class MergeTensorsBase(ABC):
             scale = await fetch(m.model, t.scale_key)
             mask = await fetch(m.model, t.mask_key) if t.mask_key is not None else None
             return self.engine(device).delta_apply(base, sign, mask, scale)
+        emr = self.index_manager.emr(m.model)
+        if emr is not None:
+            t = emr.tensors.get(layer_name)
+            if t is not None and t.kind == "full":
+                return await fetch(m.model, t.full_key)
+            base = await fetch(m.base, layer_name)
+            if t is None:
+                return base
+            unified = await fetch(emr.unified, layer_name)
+            mask = await fetch(m.model, t.mask_key)
+            scale = await fetch(m.model, t.scale_key)
+            return self.engine(device).emr_apply(base, unified, mask, scale)
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return await fetch(m.model, layer_name)
@@ -156,7 +178,19 @@ class MergeTensorsBase(ABC):
                     raise ValueError(f"{m.model}: the base of a delta pack entry must be a full model, {m.base} is {kind}")
                 from ..adapter import base_tensor_meta
                 pack.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
-            keys = self.index_manager.get_model_keys(m.base if adapter is not None or pack is not None else m.model)
+            emr = self.index_manager.emr(m.model)
+            if emr is not None:
+                # an EMR pack's finetune has its base's tensors as well: check it against the base's and the unified model's headers
+                await self.index_manager.add_model(emr.unified)
+                for role, uri in (("base", m.base), ("unified model", emr.unified)):
+                    kinds = (("an EMR pack", self.index_manager.emr), ("a delta pack", self.index_manager.pack), ("an adapter", self.index_manager.adapter))
+                    kind = next((k for k, get in kinds if get(uri) is not None), None)
+                    if kind is not None:
+                        raise ValueError(f"{m.model}: the {role} of an EMR pack entry must be a full model, {uri} is {kind}")
+                from ..adapter import base_tensor_meta
+                emr.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
+                emr.check_against(emr.unified, base_tensor_meta(self.index_manager, emr.unified), what="unified model")
+            keys = self.index_manager.get_model_keys(m.base if adapter is not None or pack is not None or emr is not None else m.model)
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)

@@ -19,6 +19,7 @@ import torch
 
 from ..adapter import base_tensor_meta, is_adapter_dir, is_bin_only_adapter_dir
 from ..deltapack import FORMAT, PACK_CONFIG, PACK_WEIGHTS, SCALES, VERSION, is_pack_dir
+from ..emrpack import is_emr_dir
 
 logger = logging.getLogger(__name__)
 
@@ -67,6 +68,8 @@ class DeltaCompression:
                 raise ValueError(f"compress-delta: {uri} is an adapter directory; a full model is expected")
             if is_pack_dir(path):
                 raise ValueError(f"compress-delta: {uri} is itself a delta pack directory; a full model is expected")
+            if is_emr_dir(path):
+                raise ValueError(f"compress-delta: {uri} is an EMR pack directory; a full model is expected")
         if (self.out_dir / PACK_WEIGHTS).exists() or (self.out_dir / PACK_CONFIG).exists():
             raise ValueError(f"compress-delta: {self.out_dir} already holds a delta pack; it is not overwritten")
         if self.index_manager is None:

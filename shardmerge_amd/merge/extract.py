@@ -75,6 +75,9 @@ class LoraExtraction:
             from ..deltapack import is_pack_dir
             if is_pack_dir(path):
                 raise ValueError(f"extract-lora: {uri} is a delta pack directory; a full model is expected")
+            from ..emrpack import is_emr_dir
+            if is_emr_dir(path):
+                raise ValueError(f"extract-lora: {uri} is an EMR pack directory; a full model is expected")
         if (self.out_dir / ADAPTER_WEIGHTS).exists() or (self.out_dir / ADAPTER_CONFIG).exists():
             raise ValueError(f"extract-lora: {self.out_dir} already holds an adapter; it is not overwritten")
         if self.index_manager is None:
