@@ -1458,6 +1458,38 @@ typedef struct {
 } smhip_emr_apply_desc;
 /* out: device, dtype, [rows][cols]; it must not overlap an input */
 int smhip_emr_apply(smhip_ctx* ctx, const smhip_emr_apply_desc* desc, void* out, void* stream);
+/* ---- MERGE AND MASKS, smhip_emr_merge_masks: the unified tensor and every entry's modulator from ONE pass.  It is the
+ *      composition of the two functions above, and that composition is its whole specification.  The tensor of
+ *      desc->n = rows * cols elements is seen as R = rows rows of C = cols elements (a 0-D or 1-D tensor: one row), k
+ *      entries, 1 <= k <= 16:
+ *        1. out, delta_out and report are those of smhip_emr_merge(desc), bit for bit.
+ *        2. g = the fp32 value of the element of out AS STORED, after its one rounding into base_out_dtype.  Per entry i
+ *           and element: d = fl32(fp32(finetune_i) - fp32(base_i)), u = fl32(g - fp32(base_i)), each entry against its
+ *           own base.
+ *        3. m = (d > 0 and u > 0) or (d < 0 and u < 0); masks[i], uint8 [R][ceil(C / 8)]: bit c % 8 of byte c / 8 of row
+ *           r is m of element (r, c) of entry i, padding bits 0.
+ *        4. Per entry and row the seven values A, B, D2, X, U2, c, nz of step 3 of smhip_emr_mask in exactly its order:
+ *           lane t of 256 takes octets t, t + 256, ... of the row in ascending order, each value one rounded fp64
+ *           addition; then the fixed binary tree v[t] = v[t] + v[t + s], s = 128 .. 1; then the rows added in index
+ *           order from 0.0.
+ *        5. scales[i][0] = fp32(A_i / B_i), +0 when B_i == 0; resid_sq_i as step 5 of smhip_emr_mask forms it.
+ *      So (masks[i], scales[i], mask_reports[i]) equals smhip_emr_mask(finetune_i, base_i, out) for every i, bit for
+ *      bit (with in_dtype != base_out_dtype: of the three tensors converted to fp32, which changes no value).
+ *      SMHIP_ERR_NONFINITE, in this order of precedence: a NaN or Inf in a d_i (the message names the lowest such
+ *      finetune), in the sum of the deltas, in a u (the message names the lowest such entry); the outputs are then
+ *      unspecified.  n == 0: the planes have no byte, every scale is +0, the reports are zero.  SMHIP_ERR_ARG, before
+ *      any launch: what smhip_emr_merge rejects; rows * cols != n; cols >= 2^31; null masks, scales or one of their
+ *      first k entries; a plane or a scale that is misaligned or overlaps another tensor of the call.
+ *      Two launches: "emr_merge_mask" (a work-group of 256 per row; k <= 4: one sweep, k + 2 tensor passes plus k / 8
+ *      of a byte per element of planes; k > 4: the row is swept again once per group of four entries, which reads the
+ *      finetunes twice, the bases once per group (own bases: twice) and out once per group) and "emr_fold" (the ordered
+ *      fold of the rows' 7k partials, staged through LDS).  No floating-point atomics; one synchronisation, at the
+ *      end, which fetches the counters, the flags and the 7k totals at once. ---- */
+/* out, delta_out, report: as smhip_emr_merge.  masks: HOST array of k device pointers, uint8 [rows][ceil(cols / 8)] each.
+ * scales: HOST array of k device pointers, float [1] each.  mask_reports (optional): HOST array of k reports. */
+int smhip_emr_merge_masks(smhip_ctx* ctx, const smhip_emr_desc* desc, size_t rows, size_t cols, void* out, float* delta_out,
+                          uint8_t* const* masks, float* const* scales, smhip_emr_report* report,
+                          smhip_emr_mask_report* mask_reports, void* stream);
 
 /* ---- correlate_pairs (reference shard/tensor/functions.py:304-314, the legacy fourier.py operator's
  *      pairing matrix): matrix[i][j] = mean over the trailing positions of
@@ -1497,7 +1529,9 @@ int smhip_reference_cpu_norm(smhip_ctx* ctx, const void* x, const void* base, in
  *      (inverse transform to fp32, forward again) as round 1 of this library did, instead of
  *      keeping it in the spectral domain (default 1);
  *      "della_slab_rows" = r makes smhip_della_merge rank and merge r rows at a time (0, the default: as many whole
- *      rows as hold at most 2^26 elements per finetune); the result does not depend on it. ------- */
+ *      rows as hold at most 2^26 elements per finetune); the result does not depend on it;
+ *      "emr_fused_geo_fold" = 1 makes smhip_emr_merge_masks fold its rows' partials with "geo_gram_fold" instead of
+ *      "emr_fold" (default 0; the same bits, for A/B timing). ------- */
 int smhip_debug_option(smhip_ctx* ctx, const char* key, long value);
 /* test hook, read side: "spec_hit" = 1 if the last speculative blend's guess was confirmed, 0 if it was voided;
  * "spec_checked" / "spec_hits": how many speculations this context has checked / confirmed since it was created;

@@ -27,12 +27,21 @@ def setup_logging(verbose: bool):
                         format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
 
 
-async def run_merge(config: MergeConfig, device: str, clean_cache: bool, **kwargs):
+async def run_merge(config: MergeConfig, device: str, clean_cache: bool, emr_pack_options=None, **kwargs):
     """Build the index and the operator, run the merge (reference __main__.py:47-76).
-    With more than one rank (torchrun) the tensor list is partitioned over the GPUs."""
-    index_manager = LocalModelIndex(storage_path=config.storage_path, cache_path=config.cache_path)
+    With more than one rank (torchrun) the tensor list is partitioned over the GPUs.
+    emr_pack_options (merge/emr_packs.py): the merge also writes every entry's EMR pack; what they rule out is rejected
+    here, before an index is built or a path is chosen."""
     from . import distributed
     import os
+    if emr_pack_options is not None:
+        emr_pack_options.check(config)
+        if emr_pack_options.asked:
+            from .merge.emr_packs import EmrPackMerge
+            index_manager = LocalModelIndex(storage_path=config.storage_path, cache_path=config.cache_path)
+            await EmrPackMerge(config=config, index_manager=index_manager, emr_pack_options=emr_pack_options, **kwargs).merge(device=device)
+            return
+    index_manager = LocalModelIndex(storage_path=config.storage_path, cache_path=config.cache_path)
     # SHARDMERGE_INPLACE=1: a single process takes the multi-GPU path's in-place output shards too (pre-sized files,
     # every tensor pwritten at its offset as soon as its copy to the host is done) instead of writing a shard when it
     # is complete - one file takes ~7 GB/s on tmpfs whatever the thread count, so the sooner its writes start the better
@@ -56,11 +65,21 @@ def cli():
 @click.option("--clean_cache", is_flag=True, help="Delete cached files after merging")
 @click.option("--device", type=str, default=None, help="Device to perform tensor operations on (cuda/cpu)")
 @click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def merge_command(config_file: Path, cache_dir: Optional[Path], verbose: bool, **kwargs):
+@click.option("--emr-packs", "emr_packs", type=click.Path(path_type=Path), default=None,
+              help="operator emr: also write every entry's EMR pack, to DIR/<its model URI>-emr")
+@click.option("--emr-unified", "emr_unified", type=str, default=None,
+              help="With --emr-packs: the name under storage_dir at which the merged model will be found (recorded in every pack)")
+@click.option("--emr-scale", "emr_scale", type=click.Choice(["model", "tensor"]), default=None,
+              help="With --emr-packs: one rescaler for the whole model (default), or one per tensor")
+@click.option("--emr-full", "emr_full", type=str, default=None,
+              help="With --emr-packs: store whole the tensors whose name ends in one of these, comma-separated")
+def merge_command(config_file: Path, cache_dir: Optional[Path], verbose: bool, emr_packs: Optional[Path], emr_unified: Optional[str],
+                  emr_scale: Optional[str], emr_full: Optional[str], **kwargs):
     """Merge multiple finetuned models by computing and combining their deltas.
 
     CONFIG_FILE is a YAML file with output_base_model, finetune_merge (list of
     {model, base, alpha, is_input, is_output, start_layer, end_layer}) and output_dir.
+    With operator emr, --emr-packs DIR --emr-unified NAME also writes what `emr-task` would write per entry afterwards.
     """
     setup_logging(verbose)
     from .constants import tune_hip_queues
@@ -71,7 +90,9 @@ def merge_command(config_file: Path, cache_dir: Optional[Path], verbose: bool, *
         if cache_dir:
             config.cache_dir = cache_dir
         config.update({k: v for k, v in kwargs.items() if v is not None})
-        asyncio.run(run_merge(config=config, **config.to_dict()))
+        from .merge.emr_packs import EmrPackOptions
+        options = EmrPackOptions(emr_packs, emr_unified, emr_scale, emr_full)
+        asyncio.run(run_merge(config=config, emr_pack_options=options, **config.to_dict()))
     except Exception as exc:
         logging.error(f"Error during merge: {exc}", exc_info=verbose)
         traceback.print_exc()

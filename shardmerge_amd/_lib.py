@@ -483,6 +483,8 @@ class SmhipLibrary:
         d.smhip_emr_merge.argtypes = [P, C.POINTER(EmrDesc), P, P, C.POINTER(EmrReport), P]
         d.smhip_emr_mask.argtypes = [P, C.POINTER(EmrMaskDesc), P, P, C.POINTER(EmrMaskReport), P]
         d.smhip_emr_apply.argtypes = [P, C.POINTER(EmrApplyDesc), P, P]
+        d.smhip_emr_merge_masks.argtypes = [P, C.POINTER(EmrDesc), C.c_size_t, C.c_size_t, P, P, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p), C.POINTER(EmrReport), C.POINTER(EmrMaskReport), P]
         d.smhip_debug_option.argtypes =[P, C.c_char_p, C.c_long]
         d.smhip_debug_query.argtypes = [P, C.c_char_p, C.POINTER(C.c_long)]
         d.smhip_profile_enable.argtypes = [P, I]

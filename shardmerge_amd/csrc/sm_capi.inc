@@ -696,6 +696,45 @@ int smhip_emr_mask(smhip_ctx* ctx, const smhip_emr_mask_desc* d, uint8_t* mask, 
     SM_FINISH(ctx, ctx->pipe.delta.emr_mask(*d, mask, scale, report));
 }
 
+int smhip_emr_merge_masks(smhip_ctx* ctx, const smhip_emr_desc* d, size_t rows, size_t cols, void* out, float* delta_out,
+                          uint8_t* const* masks, float* const* scales, smhip_emr_report* report,
+                          smhip_emr_mask_report* mask_reports, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "emr_merge_masks", d, out, delta_out, true, [&]() -> const char* {
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            return nullptr;
+        }))
+        return rc;
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("emr_merge_masks: ") + what); };
+    if (rows && cols > ((size_t)1 << 40) / rows) return bad("tensor too large");
+    if (rows * cols != d->n) return bad("rows * cols is not n");
+    if (cols >= (size_t)1 << 31) return bad("a row of 2^31 elements or more");
+    if (!masks || !scales) return bad("null masks or scales");
+    const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, oes = d->base_out_dtype == SMHIP_F32 ? 4 : 2, plane = rows * ((cols + 7) / 8);
+    auto overlaps = [&](const void* o, size_t obytes, const void* q, size_t bytes) {
+        return o && q && obytes && bytes && (uintptr_t)q < (uintptr_t)o + obytes && (uintptr_t)o < (uintptr_t)q + bytes;
+    };
+    for (int i = 0; i < d->k; ++i) {
+        if (!scales[i] || (plane && !masks[i])) return bad("null mask or scale");
+        if ((uintptr_t)scales[i] % 4) return bad("a pointer is not aligned to its element size");
+        // a plane or a rescaler is written while every input is still read, and after out
+        const void* outs[2] = {masks[i], scales[i]};
+        const size_t obytes[2] = {plane, 4};
+        for (int o = 0; o < 2; ++o) {
+            bool hit = overlaps(outs[o], obytes[o], out, d->n * oes) || overlaps(outs[o], obytes[o], delta_out, d->n * 4) ||
+                       overlaps(outs[o], obytes[o], d->base_out, d->n * oes);
+            for (int j = 0; j < d->k; ++j) {
+                hit = hit || overlaps(outs[o], obytes[o], d->finetune[j], d->n * ies) || overlaps(outs[o], obytes[o], d->base[j], d->n * ies);
+                if (j != i) hit = hit || overlaps(outs[o], obytes[o], masks[j], plane) || overlaps(outs[o], obytes[o], scales[j], 4);
+            }
+            hit = hit || (o == 0 && overlaps(masks[i], plane, scales[i], 4));
+            if (hit) return bad("a mask or a scale overlaps another tensor");
+        }
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.emr_merge_masks(*d, rows, cols, out, delta_out, masks, scales, report, mask_reports));
+}
+
 int smhip_emr_apply(smhip_ctx* ctx, const smhip_emr_apply_desc* d, void* out, void* stream) {
     SM_GUARD(ctx);
     if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "emr_apply: null descriptor");
@@ -833,6 +872,7 @@ int smhip_debug_option(smhip_ctx* ctx, const char* key, long value) {
     if (key && std::string(key) == "force_split") { ctx->pipe.debug_force_split = value > 1 && value <= smhip::DFTP_MAX_P ? (int)value : 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_columns") { ctx->pipe.fold_enabled = value != 0; return SMHIP_OK; }
     if (key && std::string(key) == "della_slab_rows") { ctx->pipe.delta.della_slab_rows = value > 0 ? (size_t)value : 0; return SMHIP_OK; }
+    if (key && std::string(key) == "emr_fused_geo_fold") { ctx->pipe.delta.emr_fused_geo_fold = value != 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_min_rows") { ctx->pipe.fold_min_rows = value > 0 ? (int)value : SM_FOLD_MIN_ROWS; return SMHIP_OK; }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug option");
 }

@@ -30,6 +30,7 @@
 #include "sm_iso.hpp"
 #include "sm_dpack.hpp"
 #include "sm_emr.hpp"
+#include "sm_emr_fused.hpp"
 
 namespace smhip {
 
@@ -1764,6 +1765,93 @@ class DeltaHost {
             rep->A = host.tot[0]; rep->B = host.tot[1]; rep->D2 = host.tot[2]; rep->X = host.tot[3]; rep->U2 = host.tot[4];
             rep->c = (uint64_t)host.tot[5]; rep->nonzero = (uint64_t)host.tot[6];
             rep->lambda = l; rep->delta_sq = host.tot[2]; rep->resid_sq = emr_resid_of(host.tot[2], host.tot[3], host.tot[4], l);
+        }
+        return SMHIP_OK;
+    }
+    // The unified model and every task's modulator from one call (sm_emr_fused.hpp; smhip_emr_merge_masks): the fused
+    // pass over whole rows, ONE fold of the rows' 7k partials, ONE readback of the counters, the flags and the 7k
+    // totals; the k rescalers are formed here and copied to the device.  Workspace: EmrFusedHead | part [R][k][7] ----
+    struct EmrFusedHead {
+        unsigned long long agree[TIES_MAX_MODELS], winner[TIES_MAX_MODELS], counts[EMR_COUNTS];
+        uint32_t flags[4];
+        double tot[TIES_MAX_MODELS * EMR_NP];
+    };
+    bool emr_fused_geo_fold = false;          // test and bench hook "emr_fused_geo_fold": fold with geo_gram_fold (the same bits)
+    int emr_merge_masks(const smhip_emr_desc& d, size_t R, size_t C, void* out, float* delta_out, uint8_t* const* masks,
+                        float* const* scales, smhip_emr_report* rep, smhip_emr_mask_report* mreps) {
+        const int k = d.k;
+        if (rep) {
+            *rep = smhip_emr_report{};
+            rep->n = d.n;
+        }
+        for (int i = 0; mreps && i < k; ++i) {
+            mreps[i] = smhip_emr_mask_report{};
+            mreps[i].rows = R; mreps[i].cols = C;
+        }
+        if (d.n == 0) {                                  // the planes have no byte; the rescalers are +0
+            for (int i = 0; i < k; ++i) be.memset(scales[i], 0, sizeof(float), stream);
+            return SMHIP_OK;
+        }
+        EmrFusedHead* w;
+        const size_t off = round_up(sizeof(EmrFusedHead), 256);
+        int rc;
+        if ((rc = plain_workspace(w, off + R * k * EMR_NP * sizeof(double)))) return rc;
+        double* part = (double*)ws_at(off);
+
+        EmrFusedParams m;
+        ties_inputs(m.in, k, d.in_dtype, d.n, d.finetune, d.base, aligned16(out) && aligned16(delta_out) && aligned16(d.base_out));
+        m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
+        m.out_is_base0 = (m.in.shared_base && d.base_out == m.in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
+        m.lambda = (float)d.lambda; m.out = out; m.delta_out = delta_out;
+        m.agree = w->agree; m.winner = w->winner; m.counts = w->counts; m.flags = w->flags;
+        m.R = R; m.C = C; m.PB = (C + 7) / 8; m.row_vec = (m.in.aligned && C % 8 == 0) ? 1 : 0;
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) m.mask[i] = masks[i < k ? i : 0];
+        m.part = part;
+        const int grid = (int)std::min<size_t>(R, (size_t)1 << 20);
+        if (k <= EMR_REG_SMALL) be.template launch<KEmrMergeMask>(grid, EMR_THREADS, emr_fused_lds_bytes(k, EMR_THREADS), m, stream);
+        else be.template launch<KEmrMergeMaskAny>(grid, EMR_THREADS, emr_fused_lds_bytes(k, EMR_THREADS), m, stream);
+        if (emr_fused_geo_fold) {
+            fold_pass<KGeoFold>(EMR_NP * k, R, part, w->tot);
+        } else {
+            EmrFoldParams f;
+            f.np = EMR_NP * k; f.nseg = R; f.part = part; f.out = w->tot;
+            be.template launch<KEmrFold>(1, EMR_FOLD_THREADS, emr_fold_lds_bytes(f.np), f, stream);
+        }
+
+        EmrFusedHead host;
+        if ((rc = delta_readback("emr_merge_masks", k, w, host))) {      // the call's one synchronisation
+            uint32_t lowest = host.flags[0] & (0u - host.flags[0]);      // (the message names the lowest such finetune)
+            return delta_nonfinite("emr_merge_masks", "finetune - base", k, lowest);
+        }
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the reports stay as they are)
+        if (host.flags[1]) return fail(SMHIP_ERR_NONFINITE, "emr_merge_masks: NaN or Inf in the sum of the deltas");
+        if (host.flags[2]) {
+            int i = 0;
+            while (!(host.flags[2] & (1u << i))) ++i;
+            return fail(SMHIP_ERR_NONFINITE, "emr_merge_masks: NaN or Inf in unified - base of entry " + std::to_string(i));
+        }
+        if (rep) {
+            for (int i = 0; i < k; ++i) { rep->agree[i] = host.agree[i]; rep->winner[i] = host.winner[i]; }
+            rep->elected_pos = host.counts[EMR_POS]; rep->elected_neg = host.counts[EMR_NEG];
+            rep->zero = host.counts[EMR_ZERO]; rep->contested = host.counts[EMR_CONTESTED];
+        }
+        float ls[TIES_MAX_MODELS];
+        bool run = true;                                 // the k rescalers stand one after the other: one copy
+        for (int i = 0; i < k; ++i) {
+            ls[i] = emr_scale_of(host.tot[(size_t)i * EMR_NP], host.tot[(size_t)i * EMR_NP + 1]);
+            run = run && scales[i] == scales[0] + i;
+        }
+        if (run) be.h2d(scales[0], ls, k * sizeof(float), stream);
+        for (int i = 0; i < k; ++i) {
+            const double* t = host.tot + (size_t)i * EMR_NP;
+            const float l = ls[i];
+            if (!run) be.h2d(scales[i], &l, sizeof l, stream);
+            if (mreps) {
+                smhip_emr_mask_report& q = mreps[i];
+                q.A = t[0]; q.B = t[1]; q.D2 = t[2]; q.X = t[3]; q.U2 = t[4];
+                q.c = (uint64_t)t[5]; q.nonzero = (uint64_t)t[6];
+                q.lambda = l; q.delta_sq = t[2]; q.resid_sq = emr_resid_of(t[2], t[3], t[4], l);
+            }
         }
         return SMHIP_OK;
     }

@@ -131,13 +131,14 @@ __global__ void __launch_bounds__(K::max_threads, K::waves) sm_kernel(const type
 #define SM_SIDE_HEADER_19 "sm_kernels.hpp"       // DynPlan: the 1-D pair merge
 #define SM_SIDE_HEADER_20 "sm_bluestein.hpp"     // DynPlan: the inverse row pass of a length without a plan
 #define SM_SIDE_HEADER_21 "sm_emr.hpp"           // EMR-Merging: the unified model, a task's mask, its apply
+#define SM_SIDE_HEADER_22 "sm_emr_fused.hpp"     // EMR-Merging: the unified model and every task's mask in one pass, their fold
 // A new group: its SM_SIDE_HEADER_<g> and SM_SIDE_KERNELS_<g>, one more entry in SM_SIDE_KERNELS_ALL, and SM_SIDE_GROUPS
 // (the Makefile reads it).
-#define SM_SIDE_GROUPS 22
+#define SM_SIDE_GROUPS 23
 #define SM_SIDE_KERNELS_ALL(X)                                                                                       \
     SM_SIDE_KERNELS_0(X) SM_SIDE_KERNELS_1(X) SM_SIDE_KERNELS_2(X) SM_SIDE_KERNELS_3(X) SM_SIDE_KERNELS_4(X) SM_SIDE_KERNELS_5(X)     \
     SM_SIDE_KERNELS_6(X) SM_SIDE_KERNELS_7(X) SM_SIDE_KERNELS_8(X) SM_SIDE_KERNELS_9(X) SM_SIDE_KERNELS_10(X) SM_SIDE_KERNELS_11(X)   \
     SM_SIDE_KERNELS_12(X) SM_SIDE_KERNELS_13(X) SM_SIDE_KERNELS_14(X) SM_SIDE_KERNELS_15(X) SM_SIDE_KERNELS_16(X) SM_SIDE_KERNELS_17(X) \
-    SM_SIDE_KERNELS_18(X) SM_SIDE_KERNELS_19(X) SM_SIDE_KERNELS_20(X) SM_SIDE_KERNELS_21(X)
+    SM_SIDE_KERNELS_18(X) SM_SIDE_KERNELS_19(X) SM_SIDE_KERNELS_20(X) SM_SIDE_KERNELS_21(X) SM_SIDE_KERNELS_22(X)
 
 }  // namespace smhip

@@ -706,6 +706,47 @@ class Engine:
                                        U2=float(rep.U2), c=int(rep.c), nonzero=int(rep.nonzero), lam=float(rep.lam),
                                        delta_sq=float(rep.delta_sq), resid_sq=float(rep.resid_sq))
 
+    def emr_merge_masks(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], base_out: torch.Tensor, *,
+                        lam: float = 1.0, want_delta: bool = False, layer_name: str = ""):
+        """The unified tensor AND every entry's modulator from one fused pass (``smhip_emr_merge_masks``): what
+        ``emr_merge`` followed by ``emr_mask(finetunes[i], bases[i], out)`` for every i returns, bit for bit, while the
+        finetunes and the bases are read once.  Returns ``(out, EmrReport, masks, scales, mask_reports[, delta])``:
+        ``masks`` k uint8 [R, ceil(C / 8)] tensors, ``scales`` k float32 [1] tensors, ``mask_reports`` k EmrMaskReport.
+        A NaN or Inf in a delta, in the sum or in ``out - base_i`` raises ValueError naming ``layer_name`` and, where
+        there is one, the entry."""
+        layer_name = layer_name or "layer"
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(float(lam)):
+            raise ValueError(f"emr_merge_masks: lam {lam!r} is not a finite number")
+        desc, rep, k = _lib.EmrDesc(), _lib.EmrReport(), len(finetunes)
+        desc.lam = float(lam)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, [1.0] * len(bases), base_out, layer_name,
+                                                       want_delta, "emr_merge_masks")
+        desc.n = bo.numel()
+        rows, cols = _shape_rows(bo)
+        pb = (cols + 7) // 8
+        planes = torch.empty((k, rows, pb), dtype=torch.uint8, device=self.device)
+        sc = torch.empty((k,), dtype=torch.float32, device=self.device)
+        masks, scales = [planes[i] for i in range(k)], [sc[i:i + 1] for i in range(k)]
+        mptr = (C.c_void_p * k)(*[m.data_ptr() for m in masks])
+        sptr = (C.c_void_p * k)(*[s.data_ptr() for s in scales])
+        mreps = (_lib.EmrMaskReport * k)()
+        try:
+            self.ctx.check(self.lib.dll.smhip_emr_merge_masks(
+                self.ctx.h, C.byref(desc), rows, cols, out.data_ptr(), delta.data_ptr() if delta is not None else None,
+                mptr, sptr, C.byref(rep), mreps, self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite delta in {layer_name}: {e.message}") from e
+            raise
+        report = EmrReport(n=int(rep.n), elected_pos=int(rep.elected_pos), elected_neg=int(rep.elected_neg), zero=int(rep.zero),
+                           contested=int(rep.contested), winner=[int(rep.winner[i]) for i in range(k)],
+                           agree=[int(rep.agree[i]) for i in range(k)])
+        mask_reports = [EmrMaskReport(rows=rows, cols=cols, A=float(q.A), B=float(q.B), D2=float(q.D2), X=float(q.X),
+                                      U2=float(q.U2), c=int(q.c), nonzero=int(q.nonzero), lam=float(q.lam),
+                                      delta_sq=float(q.delta_sq), resid_sq=float(q.resid_sq)) for q in mreps]
+        res = (out, report, masks, scales, mask_reports)
+        return res + (delta,) if want_delta else res
+
     def emr_apply(self, base: torch.Tensor, unified: torch.Tensor, mask: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
         """the task tensor an EMR modulator defines: ``base + scale * (unified - base)`` where the mask bit is set, one
         rounding per operation and once into base's dtype, and ``base`` bit for bit elsewhere (``smhip_emr_apply``).

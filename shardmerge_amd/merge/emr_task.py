@@ -124,11 +124,7 @@ class EmrTask:
             from ..loader import PrefetchLoader
             self._loader = PrefetchLoader(self.index_manager, dev)
             self._loader.start(schedule)
-        stored: Dict[str, torch.Tensor] = {}
-        declared: Dict[str, dict] = {}
-        tensors, unchanged = [], []
-        nbytes = lambda *ts: sum(t.numel() * t.element_size() for t in ts if t is not None)
-        same = lambda a, b: torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))       # bit for bit
+        self.begin()
         try:
             for pos, name in enumerate(order):
                 if self._loader is not None:
@@ -136,25 +132,69 @@ class EmrTask:
                 ft = await self._fetch(self.model, name, dev)
                 bs = await self._fetch(self.base, name, dev)
                 un = await self._fetch(self.unified, name, dev)
-                if same(ft, bs):
-                    unchanged.append(name)
-                    continue
                 shape, dtype = meta[name]
-                declared[name] = {"shape": [int(s) for s in shape], "dtype": dtype}
-                if self.whole(name, dtype) or same(un, bs):
-                    stored[f"{name}.full"] = ft.cpu()
-                    tensors.append({"name": name, "shape": list(ft.shape), "stored": "full", "bytes": nbytes(ft), "full_bytes": nbytes(ft)})
-                    continue
-                mask, scale, rep = eng.emr_mask(ft, bs, un, name=name)
-                stored[f"{name}.mask"], stored[f"{name}.scale"] = mask.cpu(), scale.cpu()
-                tensors.append({"name": name, "shape": list(ft.shape), "stored": "masked", "rows": rep.rows, "cols": rep.cols,
-                                "c": rep.c, "nonzero": rep.nonzero, "A": rep.A, "B": rep.B, "D2": rep.D2, "X": rep.X, "U2": rep.U2,
-                                "lambda": rep.lam, "delta_sq": rep.delta_sq, "resid_sq": rep.resid_sq,
-                                "bytes": nbytes(mask, scale), "full_bytes": nbytes(ft)})
+                kind = self.decide(name, dtype, ft, bs, un)
+                if kind == "unchanged":
+                    self.add_unchanged(name)
+                elif kind == "full":
+                    self.add_full(name, shape, dtype, ft)
+                else:
+                    mask, scale, rep = eng.emr_mask(ft, bs, un, name=name)
+                    self.add_masked(name, shape, dtype, ft, mask, scale, rep)
         finally:
             if self._loader is not None:
                 self._loader.close()
                 self._loader = None
+        return self.finish(order)
+
+    # ---- the per-tensor records and the pack they end in: `run` above and the merge that writes its packs itself
+    # (merge/emr_packs.py) decide, record and write through these ----------------------------------------------------
+    @staticmethod
+    def same(a: torch.Tensor, b: torch.Tensor) -> bool:
+        """bit for bit"""
+        return torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
+
+    def begin(self):
+        self._stored: Dict[str, torch.Tensor] = {}
+        self._declared: Dict[str, dict] = {}
+        self._records: Dict[str, dict] = {}
+        self._unchanged = set()
+
+    def decide(self, name: str, dtype: str, ft: torch.Tensor, bs: torch.Tensor, un: torch.Tensor) -> str:
+        """'unchanged': MODEL's tensor is its base's, nothing is stored; 'full': it is stored whole (the unified tensor is
+        the base's, a dtype without a mask, one of --full); 'masked' otherwise"""
+        if self.same(ft, bs):
+            return "unchanged"
+        return "full" if self.whole(name, dtype) or self.same(un, bs) else "masked"
+
+    def add_unchanged(self, name: str):
+        self._unchanged.add(name)
+
+    def _declare(self, name: str, shape, dtype: str):
+        self._declared[name] = {"shape": [int(s) for s in shape], "dtype": dtype}
+
+    def add_full(self, name: str, shape, dtype: str, ft: torch.Tensor):
+        nbytes = ft.numel() * ft.element_size()
+        self._declare(name, shape, dtype)
+        self._stored[f"{name}.full"] = ft.cpu()
+        self._records[name] = {"name": name, "shape": list(ft.shape), "stored": "full", "bytes": nbytes, "full_bytes": nbytes}
+
+    def add_masked(self, name: str, shape, dtype: str, ft: torch.Tensor, mask: torch.Tensor, scale: torch.Tensor, rep):
+        nbytes = lambda *ts: sum(t.numel() * t.element_size() for t in ts)
+        self._declare(name, shape, dtype)
+        self._stored[f"{name}.mask"], self._stored[f"{name}.scale"] = mask.cpu(), scale.cpu()
+        self._records[name] = {"name": name, "shape": list(ft.shape), "stored": "masked", "rows": rep.rows, "cols": rep.cols,
+                               "c": rep.c, "nonzero": rep.nonzero, "A": rep.A, "B": rep.B, "D2": rep.D2, "X": rep.X, "U2": rep.U2,
+                               "lambda": rep.lam, "delta_sq": rep.delta_sq, "resid_sq": rep.resid_sq,
+                               "bytes": nbytes(mask, scale), "full_bytes": nbytes(ft)}
+
+    def finish(self, order: Sequence[str]) -> dict:
+        """the records in `order` (MODEL's layer order: the fp64 sums of --scale model depend on it), the model's
+        rescaler, the config and the report; writes the pack and returns the report"""
+        stored = self._stored
+        declared = {n: self._declared[n] for n in order if n in self._declared}
+        tensors = [self._records[n] for n in order if n in self._records]
+        unchanged = [n for n in order if n in self._unchanged]
         if not stored:
             raise ValueError(f"emr-task: no tensor of {self.model} differs from {self.base}; nothing to write")
         masked = [t for t in tensors if t["stored"] == "masked"]
