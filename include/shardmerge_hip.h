@@ -967,6 +967,7 @@ typedef struct {
     uint64_t key;
     int factor_dtype;                       /* of A and B */
     void* workspace; size_t workspace_bytes;
+    int eig;                                /* SMHIP_EIG_HOST (0, "eig" above) or SMHIP_EIG_DEVICE (smhip_sym_eig_par) */
 } smhip_extract_desc;
 typedef struct {
     int L;                                  /* the panel width */
@@ -997,6 +998,45 @@ typedef struct {
 } smhip_xl_probe_desc;
 size_t smhip_xl_probe_workspace(int rows, int cols, int L);    /* DELTA_MM: (rows, cols, L); GRAM: (rows, 1, L) */
 int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* desc, void* stream);
+
+/* ---- The device-side symmetric eigensolver: a Jacobi iteration with a PARALLEL ordering (a round-robin tournament, Brent
+ *      and Luk), "eig_jacobi", one work-group per matrix and the whole iteration in one launch (csrc/sm_eig.hpp).  The
+ *      cyclic solver "eig" above (xl_sym_eig) is a serial chain: each rotation's angle depends on the one before it.  This
+ *      one is a different function with the same conventions; smhip_lora_extract and smhip_tsv_merge use it for every eig
+ *      when their descriptor says eig = SMHIP_EIG_DEVICE, and nothing changes a bit when it says SMHIP_EIG_HOST (0).
+ *      Input: `batch` symmetric fp64 matrices a[b][n][n], both triangles given, finite values (the caller's check; a
+ *      matrix that holds a NaN or an Inf is not iterated on: its sweeps are -1, its lam and v zeros, and the call returns
+ *      SMHIP_ERR_NONFINITE after the whole batch ran).  1 <= n <= 272.  Output per matrix: lam[n] descending (ties: the
+ *      lower original index first), v[n][n] with eigenvector i in COLUMN i, its largest-magnitude entry (the first on
+ *      ties) positive, and the sweeps run.  Every arithmetic step is ONE rounded fp64 operation; nothing is fused.
+ *        1. V = I.  thr = (((0 + |a_00|) + |a_11|) + ...) * 2^-70.  m = n rounded up to even.
+ *        2. A sweep is the rounds r = 0 .. m-2.  Round r pairs {m-1, r} and, for i = 1 .. m/2 - 1,
+ *           {(r + i) mod (m-1), (r - i + m - 1) mod (m-1)}; a pair is written (p, q) with p < q, and the pairs of a round
+ *           are ordered by i (i = 0 first).  A pair with an index >= n is the bye and does nothing.
+ *        3. The rotations of a round, all from the matrix as it stands at the start of the round: a pair with
+ *           !(|a_pq| > thr) is skipped; else theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| +
+ *           sqrt(theta^2 + 1)) with sgn(0) = +1, c = 1 / sqrt(t^2 + 1), s = t c.
+ *        4. The update of a round, A <- J^T A J with J the product of its rotations.  For two different pairs P = (p, q)
+ *           before Q = (p', q') the block X = A[{p,q}][{p',q'}] becomes Y = R_P^T X (the row side: y_p. = c x_p. - s x_q.,
+ *           y_q. = s x_p. + c x_q.), then Z = Y R_Q (the column side: z_.p' = c' y_.p' - s' y_.q', z_.q' = s' y_.p' + c' y_.q'),
+ *           each as fl(fl(c x) -/+ fl(s x')).  The side of a skipped pair or of the bye leaves its values untouched (it is
+ *           not a multiplication by 1 and 0: a -0 keeps its sign).  A[{p',q'}][{p,q}] is written from the same Z, so A
+ *           stays symmetric bit for bit.  A rotated pair's own block: a_pp <- a_pp - t a_pq, a_qq <- a_qq + t a_pq,
+ *           a_pq = a_qp = +0.  Its columns of V, for every row k: v_kp <- c v_kp - s v_kq, v_kq <- s v_kp + c v_kq.
+ *        5. The iteration stops after the first sweep in which no pair rotated, or after 60 sweeps.
+ *        6. Sort and signs as in the cyclic solver (one shared host routine): stable by descending diagonal, then each
+ *           column's sign.
+ *      a and the workspace are DEVICE memory (a is not written; the workspace 256-byte aligned and at least
+ *      smhip_sym_eig_par_workspace(n, batch) bytes), lam [batch][n], v [batch][n][n] and sweeps [batch] (optional) HOST
+ *      memory.  Matrices of n <= 96 are iterated on wholly in LDS, of n <= 128 with V in the workspace, larger ones in
+ *      the workspace.  The stream is synchronised once per matrix.  SMHIP_ERR_ARG (before any launch): a null pointer, n
+ *      outside 1..272, batch < 1, a misaligned pointer, a bad workspace.  Profile name: "eig_jacobi", one launch. ---- */
+enum { SMHIP_EIG_HOST = 0, SMHIP_EIG_DEVICE = 1 };
+size_t smhip_sym_eig_par_workspace(int n, int batch);             /* 0: a bad argument */
+int smhip_sym_eig_par(smhip_ctx* ctx, int n, int batch, const double* a, double* lam, double* v, int* sweeps,
+                      void* workspace, void* stream);
+/* TEST ABI: the cyclic host solver on HOST memory with the same outputs (what Engine.sym_eig(method="host") calls). */
+int smhip_sym_eig_host(smhip_ctx* ctx, int n, int batch, const double* a, double* lam, double* v, int* sweeps);
 
 /* ---- TSV merge (Gargiulo et al. 2025, "Task Singular Vectors"): the one operator that treats a task vector as a matrix.
  *      One 2-D tensor [rows x cols], finetunes i = 0..k-1 in order, each with its own base and a weight alpha_i >= 0.
@@ -1051,6 +1091,7 @@ typedef struct {
     double lambda;
     uint64_t key;
     void* workspace; size_t workspace_bytes;
+    int eig;                                /* SMHIP_EIG_HOST (0) or SMHIP_EIG_DEVICE: every eig of the call, the whitening's too */
 } smhip_tsv_desc;
 typedef struct {
     int L, r, R, Rp;

@@ -153,10 +153,11 @@ def analyze_command(config_file: Path, densities, report: Optional[Path], device
 @click.option("--power-iters", type=int, default=2, help="Power iterations of the subspace iteration, 0..4")
 @click.option("--dtype", "dtype_name", type=click.Choice(["bf16", "fp16", "fp32"]), default="bf16", help="The factors' dtype")
 @click.option("--seed", type=int, default=0, help="Seed of the sketch")
+@click.option("--eig", type=click.Choice(["host", "device"]), default="host", help="Where the small eigenproblems are solved")
 @click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
 @click.option("--verbose", is_flag=True, help="Enable verbose logging")
 def extract_lora_command(model: str, base: str, rank: int, out_dir: Path, storage_dir: Path, modules: Optional[str], power_iters: int,
-                         dtype_name: str, seed: int, device: str, verbose: bool):
+                         dtype_name: str, seed: int, eig: str, device: str, verbose: bool):
     """A PEFT LoRA adapter of rank RANK from the full finetune MODEL and its base: every Linear weight that differs.
 
     DIR receives adapter_model.safetensors, adapter_config.json and extraction.json (per tensor the singular values, the
@@ -168,7 +169,7 @@ def extract_lora_command(model: str, base: str, rank: int, out_dir: Path, storag
     try:
         from .merge.extract import DTYPES, format_table, parse_modules, run_extraction
         result = asyncio.run(run_extraction(model, base, rank, out_dir, storage_dir, parse_modules(modules), power_iters,
-                                            DTYPES[dtype_name], seed, device))
+                                            DTYPES[dtype_name], seed, device, eig=eig))
     except Exception as exc:
         logging.error(f"Error during extract-lora: {exc}", exc_info=verbose)
         traceback.print_exc()

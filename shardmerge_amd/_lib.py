@@ -239,13 +239,15 @@ class StatsReport(C.Structure):
 
 EXTRACT_MAX_RANK, EXTRACT_MAX_L, EXTRACT_MAX_ORTH, EXTRACT_MAX_POWER = 256, 272, 9, 4
 XL_FILL, XL_DELTA_MM, XL_GRAM, XL_PANEL_MM, XL_SYM_EIG = range(5)
+EIG_METHODS = {"host": 0, "device": 1}              # SMHIP_EIG_HOST, SMHIP_EIG_DEVICE
+EIG_SWEEPS = 60                                     # XL_EIG_SWEEPS
 
 
 class ExtractDesc(C.Structure):
     """smhip_extract_desc"""
     _fields_ = [("finetune", C.c_void_p), ("base", C.c_void_p), ("in_dtype", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
                 ("rank", C.c_int), ("power_iters", C.c_int), ("key", C.c_uint64), ("factor_dtype", C.c_int),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("eig", C.c_int)]
 
 
 class ExtractReport(C.Structure):
@@ -298,7 +300,7 @@ class TsvDesc(C.Structure):
     """smhip_tsv_desc: the leading fields of the delta merges, then the shape, rank, q, lambda, key and the workspace"""
     _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("rank", C.c_int), ("power_iters", C.c_int),
                                          ("lam", C.c_double), ("key", C.c_uint64),
-                                         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                                         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("eig", C.c_int)]
 
 
 class TsvReport(C.Structure):
@@ -468,6 +470,10 @@ class SmhipLibrary:
         d.smhip_xl_probe_workspace.argtypes = [I, I, I]
         d.smhip_xl_probe_workspace.restype = C.c_size_t
         d.smhip_xl_probe.argtypes = [P, C.POINTER(XlProbeDesc), P]
+        d.smhip_sym_eig_par_workspace.argtypes = [I, I]
+        d.smhip_sym_eig_par_workspace.restype = C.c_size_t
+        d.smhip_sym_eig_par.argtypes = [P, I, I, P, P, P, P, P, P]
+        d.smhip_sym_eig_host.argtypes = [P, I, I, P, P, P, P]
         d.smhip_tsv_workspace.argtypes = [I, I, I, I]
         d.smhip_tsv_workspace.restype = C.c_size_t
         d.smhip_tsv_merge.argtypes = [P, C.POINTER(TsvDesc), P, P, C.POINTER(TsvReport), P]

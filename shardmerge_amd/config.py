@@ -132,6 +132,8 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
                                 #   spectral keys, norm_mode, task_add_models and every other family's keys are rejected; keys:
       # tsv_rank: 64            #   an integer in 1..256: singular triplets kept per finetune
       # tsv_power_iters: 2      #   an integer in 0..4: power steps of the subspace iteration
+      # tsv_eig: host           #   host | device: where the small eigenproblems are solved (device: the parallel Jacobi kernel;
+                                #   the two solvers differ by rounding, and a resumed run does not mix them)
       # tsv_lambda: 1.0         #   scales the merged delta
       # seed: 0                 #   an integer in [0, 2^63): keys the sketch with the tensor's name (no position enters)
                                 # | widen (WIDEN, Yu et al. 2024; no counterpart in the reference): a block tensor is taken as
@@ -234,7 +236,8 @@ SPHERE_OPTION_DEFAULTS = {"karcher_max_iter": 10, "karcher_tol": 1e-5, "sphere_r
 FUSION_OPERATORS = ("arcee_fusion", "nearswap")          # the pairwise family: one model onto its base, no weights
 FUSION_OPTION_DEFAULTS = {"fusion_iqr": 1.5, "nearswap_t": None}      # nearswap_t has no default: it is required
 PCB_OPTION_DEFAULTS = {"pcb_ratio": 0.1, "pcb_clip": 0.0001, "pcb_lambda": 1.0}
-TSV_OPTION_DEFAULTS = {"tsv_rank": 64, "tsv_power_iters": 2, "tsv_lambda": 1.0, "seed": 0}
+TSV_OPTION_DEFAULTS = {"tsv_rank": 64, "tsv_power_iters": 2, "tsv_lambda": 1.0, "seed": 0, "tsv_eig": "host"}
+EIG_SOLVERS = ("host", "device")                     # tsv_eig, extract-lora --eig: the cyclic Jacobi solver on the host, the parallel one on the device
 WIDEN_OPERATORS = ("widen",)
 WIDEN_OPTION_DEFAULTS = {"widen_ratio": 1.0, "widen_calibration": 1.0, "widen_lambda": 1.0}
 CABS_OPERATORS = ("cabs",)
@@ -296,7 +299,7 @@ def _cabs_n_of_m(opts: Dict[str, Any]) -> None:
 @dataclass(frozen=True)
 class _OptionFamily:
     """One family's merge_options.  rules: key -> "flag" (0 or 1), "seed" (an exact integer in [0, 2^63)), ("int", lo, hi)
-    (an exact integer in lo..hi, kept an int) or a range (lo, hi, brackets[, the message's own wording of the range]).
+    (an exact integer in lo..hi, kept an int), ("choice", names...) (one of the names, kept a string) or a range (lo, hi, brackets[, the message's own wording of the range]).
     earlier: what the message says after a key of an earlier family, by that family's first operator.  only: a key that
     not every operator of the family takes.  required: keys that have no default.  check: a rule over several keys."""
     operators: tuple
@@ -370,7 +373,8 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "consensus_ta": "(it weighs by agreement with the sum, without masks)",
                            "arcee_fusion": "(it merges several models by their scores)"}),
     _OptionFamily(("tsv",), TSV_OPTION_DEFAULTS,
-                  {"tsv_rank": ("int", 1, 256), "tsv_power_iters": ("int", 0, 4), "tsv_lambda": _LAMBDA, "seed": "seed"},
+                  {"tsv_rank": ("int", 1, 256), "tsv_power_iters": ("int", 0, 4), "tsv_lambda": _LAMBDA, "seed": "seed",
+                   "tsv_eig": ("choice",) + EIG_SOLVERS},
                   earlier={"ties": "(it truncates by singular value, not by magnitude: tsv_rank, tsv_lambda)",
                            "dare_ties": "(it drops nothing at random; its seed keys the sketch)",
                            "breadcrumbs": "(it truncates by singular value, not by magnitude)",
@@ -466,6 +470,11 @@ def _family_options(opts: Dict[str, Any], norm_mode: str, task_add: List[str], o
             if not isinstance(value, int) or isinstance(value, bool) or not (0 <= value < 2 ** 63):
                 raise click.BadParameter(f"merge_options.{key} must be an integer in [0, 2^63)")
             out[key] = int(value)
+            continue
+        if rule[0] == "choice":
+            if value not in rule[1:]:
+                raise click.BadParameter(f"merge_options.{key} must be one of {' | '.join(rule[1:])}")
+            out[key] = str(value)
             continue
         if rule[0] == "int":
             if not isinstance(value, int) or isinstance(value, bool) or not (rule[1] <= value <= rule[2]):

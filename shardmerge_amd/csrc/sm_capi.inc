@@ -496,6 +496,7 @@ int smhip_lora_extract(smhip_ctx* ctx, const smhip_extract_desc* d, void* a_out,
         return bad("bad dtype");
     if (d->rank < 1 || d->rank > smhip::XL_MAX_RANK) return bad("rank out of range (1..256)");
     if (d->power_iters < 0 || d->power_iters > smhip::XL_MAX_POWER) return bad("power_iters out of range (0..4)");
+    if (d->eig != SMHIP_EIG_HOST && d->eig != SMHIP_EIG_DEVICE) return bad("eig must be SMHIP_EIG_HOST or SMHIP_EIG_DEVICE");
     const size_t ies = d->in_dtype == SMHIP_F32 ? 4 : 2, fes = d->factor_dtype == SMHIP_F32 ? 4 : 2;
     if ((uintptr_t)d->finetune % ies || (uintptr_t)d->base % ies || (uintptr_t)a_out % fes || (uintptr_t)b_out % fes)
         return bad("a pointer is not aligned to its element size");
@@ -527,6 +528,38 @@ int smhip_xl_probe(smhip_ctx* ctx, const smhip_xl_probe_desc* d, void* stream) {
     SM_FINISH(ctx, ctx->pipe.delta.xl_probe(*d));
 }
 
+size_t smhip_sym_eig_par_workspace(int n, int batch) {
+    if (n < 1 || n > smhip::XL_MAX_L || batch < 1) return 0;
+    return smhip::DeltaHost<SM_BACKEND>::eig_workspace(n, batch);
+}
+
+int smhip_sym_eig_par(smhip_ctx* ctx, int n, int batch, const double* a, double* lam, double* v, int* sweeps, void* workspace,
+                      void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("sym_eig_par: ") + what); };
+    if (n < 1 || n > smhip::XL_MAX_L) return bad("n out of range (1..272)");
+    if (batch < 1) return bad("batch must be >= 1");
+    if (!a || !lam || !v) return bad("null matrix or output");
+    if ((uintptr_t)a % 8 || (uintptr_t)lam % 8 || (uintptr_t)v % 8) return bad("a pointer is not aligned to its element size");
+    if (!workspace || (uintptr_t)workspace % 256) return bad("the workspace is null or not 256-byte aligned (smhip_sym_eig_par_workspace)");
+    ctx->pipe.stream = stream;
+    const bool finite = ctx->pipe.delta.sym_eig_par(n, n, batch, a, lam, v, sweeps, workspace);
+    if (ctx->pipe.be.ok() && !finite) SM_FINISH(ctx, ctx->pipe.fail(SMHIP_ERR_NONFINITE, "sym_eig_par: NaN or Inf in a matrix"));
+    SM_FINISH(ctx, SMHIP_OK);
+}
+
+int smhip_sym_eig_host(smhip_ctx* ctx, int n, int batch, const double* a, double* lam, double* v, int* sweeps) {
+    SM_GUARD(ctx);
+    if (n < 1 || n > smhip::XL_MAX_L || batch < 1 || !a || !lam || !v) return ctx->pipe.fail(SMHIP_ERR_ARG, "sym_eig_host: bad argument");
+    std::vector<double> w((size_t)n * n);
+    for (int b = 0; b < batch; ++b) {
+        w.assign(a + (size_t)b * n * n, a + (size_t)(b + 1) * n * n);
+        const int sw = smhip::xl_sym_eig(n, w.data(), lam + (size_t)b * n, v + (size_t)b * n * n);
+        if (sweeps) sweeps[b] = sw;
+    }
+    SM_FINISH(ctx, SMHIP_OK);
+}
+
 size_t smhip_tsv_workspace(int rows, int cols, int k, int rank) {
     if (rows < 1 || cols < 1 || k < 1 || k > SMHIP_MAX_MODELS || rank < 1 || rank > smhip::XL_MAX_RANK) return 0;
     return smhip::DeltaHost<SM_BACKEND>::tsv_layout(rows, cols, k, rank).total;
@@ -538,6 +571,7 @@ int smhip_tsv_merge(smhip_ctx* ctx, const smhip_tsv_desc* d, void* out, float* d
             if (!std::isfinite(d->lambda)) return "lambda is not finite";
             if (d->rank < 1 || d->rank > smhip::XL_MAX_RANK) return "rank out of range (1..256)";
             if (d->power_iters < 0 || d->power_iters > smhip::XL_MAX_POWER) return "power_iters out of range (0..4)";
+            if (d->eig != SMHIP_EIG_HOST && d->eig != SMHIP_EIG_DEVICE) return "eig must be SMHIP_EIG_HOST or SMHIP_EIG_DEVICE";
             for (int i = 0; i < d->k; ++i)
                 if (d->alpha[i] < 0.0) return "an alpha is negative";
             return nullptr;
@@ -894,6 +928,7 @@ int smhip_debug_query(smhip_ctx* ctx, const char* key, long* value) {
         SM_FINISH(ctx, SMHIP_OK);
     }
     if (std::string(key) == "eig_host_us") { *value = (long)ctx->pipe.delta.eig_host_us; SM_FINISH(ctx, SMHIP_OK); }
+    if (std::string(key) == "eig_dev_us") { *value = (long)ctx->pipe.delta.eig_dev_us; SM_FINISH(ctx, SMHIP_OK); }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug query");
 }
 

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,7 @@
 #include "sm_dpack.hpp"
 #include "sm_emr.hpp"
 #include "sm_emr_fused.hpp"
+#include "sm_eig.hpp"
 
 namespace smhip {
 
@@ -75,6 +77,8 @@ class DeltaHost {
     void*& stream;
     size_t della_slab_rows = 0;               // test hook "della_slab_rows": rows per slab (0: at most 2^26 elements per finetune)
     unsigned long long eig_host_us = 0;       // debug query "eig_host_us": host time in xl_sym_eig since the context was created
+    unsigned long long eig_dev_us = 0;        // debug query "eig_dev_us": wall time of the device solves (launch, read-back, sort)
+    int eig_device = 0;                       // the eigensolver of the running tsv_merge / lora_extract call (SMHIP_EIG_*)
 
     DeltaHost(B& be_, std::string& err_, void*& stream_) : be(be_), err(err_), stream(stream_) {}
     ~DeltaHost() { if (ws_.p) be.free(ws_.p); }
@@ -1106,7 +1110,7 @@ class DeltaHost {
     // and the flags ----
     struct XlLayout {
         int L;
-        size_t pan, part, gpart, G, T, epart, tail, total;      // byte offsets; pan: the size of one panel
+        size_t pan, part, gpart, G, T, epart, tail, eig, total; // byte offsets; pan: the size of one panel; eig: the device solver's
         size_t eseg;
     };
     static XlLayout xl_layout_L(int rows, int cols, int L_, int tcols) {
@@ -1124,7 +1128,8 @@ class DeltaHost {
         y.T = y.G + round_up(L * L * 8, 256);
         y.epart = y.T + round_up(2 * L * (size_t)std::max(y.L, tcols) * 4, 256);     // T [L x L], or Tb and Ta [L x r]
         y.tail = y.epart + round_up(y.eseg * 8, 256);
-        y.total = y.tail + 256;
+        y.eig = y.tail + 256;
+        y.total = y.eig + eig_workspace(y.L, 1);
         return y;
     }
     static XlLayout xl_layout(int rows, int cols, int rank) { return xl_layout_L(rows, cols, xl_panel_width(rows, cols, rank), rank); }
@@ -1163,6 +1168,36 @@ class DeltaHost {
         q.pan_pitch = pan_pitch ? pan_pitch : L; q.out_pitch = out_pitch ? out_pitch : L2; q.col0 = col0;
         be.template launch<KXlPanelMm>((int)(((size_t)m * L2 + 255) / 256), 256, 0, q, stream);
     }
+    // ---- the device-side eigensolver (sm_eig.hpp; smhip_sym_eig_par).  a: DEVICE [batch][n][lda]; ws: DEVICE,
+    // eig_workspace(n, batch) bytes; lam [batch][n], v [batch][n][n], sweeps [batch]: HOST.  One launch, then per matrix
+    // one read-back of V, the diagonal and the sweeps, and the host's sort and signs.  false: a matrix was not finite
+    // (its lam and v are zeros, its sweeps -1) ----
+    static size_t eig_workspace(int n, int batch) { return round_up((size_t)batch * eig_ws_doubles(n) * 8, 256); }
+    bool sym_eig_par(int n, int lda, int batch, const double* a, double* lam, double* v, int* sweeps, void* ws) {
+        const auto t0 = std::chrono::steady_clock::now();
+        EigJacobiParams q;
+        q.a = a; q.ws = (double*)ws; q.n = n; q.lda = lda;
+        be.template launch<KEigJacobi>(batch, eig_threads(n), eig_lds_bytes(n), q, stream);
+        const size_t mat = (size_t)n * eig_pitch(n), head = mat + n + 1;
+        std::vector<double> h(head);
+        bool finite = true;
+        for (int b = 0; b < batch && be.ok(); ++b) {
+            be.d2h(h.data(), (double*)ws + (size_t)b * eig_ws_doubles(n), head * 8, stream);
+            if (!be.ok()) break;
+            int sw;
+            memcpy(&sw, h.data() + mat + n, sizeof sw);
+            if (sweeps) sweeps[b] = sw;
+            if (sw < 0) {
+                finite = false;
+                std::fill(lam + (size_t)b * n, lam + (size_t)(b + 1) * n, 0.0);
+                std::fill(v + (size_t)b * n * n, v + (size_t)(b + 1) * n * n, 0.0);
+            } else {
+                xl_eig_sort_signs(n, h.data() + mat, 1, h.data(), eig_pitch(n), lam + (size_t)b * n, v + (size_t)b * n * n);
+            }
+        }
+        eig_dev_us += (unsigned long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        return finite;
+    }
     // xl_sym_eig with its host time added to eig_host_us (what tools/tsv_bench.py reads)
     void xl_sym_eig_timed(int n, double* a, double* lam, double* v) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -1177,6 +1212,8 @@ class DeltaHost {
         be.d2h(flags, (char*)ws + y.tail, sizeof flags, stream);
         if (!be.ok()) return true;                              // (reported by the caller as SMHIP_ERR_HIP)
         if (flags[2]) return false;
+        if (eig_device)                                         // the Gram stays where it is: lam and V come back instead
+            return sym_eig_par(L, L, 1, (const double*)((char*)ws + y.G), lam.data(), V.data(), nullptr, (char*)ws + y.eig);
         std::vector<double> G((size_t)L * L);
         be.d2h(G.data(), (char*)ws + y.G, G.size() * 8, stream);
         if (!be.ok()) return true;
@@ -1234,6 +1271,7 @@ class DeltaHost {
     int lora_extract(const smhip_extract_desc& d, void* a_out, void* b_out, smhip_extract_report* rep) {
         const XlLayout y = xl_layout(d.rows, d.cols, d.rank);
         const int L = y.L, rows = d.rows, cols = d.cols, r = d.rank;
+        eig_device = d.eig == SMHIP_EIG_DEVICE;
         *rep = smhip_extract_report{};
         rep->L = L;
         void* ws = d.workspace;
@@ -1298,7 +1336,7 @@ class DeltaHost {
     struct TsvLayout {
         XlLayout y;
         int r, Rpm;
-        size_t omega, U, W, Bp, gpart, G, M, total;
+        size_t omega, U, W, Bp, gpart, G, M, eig, total;
     };
     static TsvLayout tsv_layout(int rows, int cols, int k, int rank) {
         TsvLayout t;
@@ -1313,7 +1351,8 @@ class DeltaHost {
         t.gpart = t.Bp + round_up((size_t)rows * Rpm * 4, 256);
         t.G = t.gpart + round_up((mx + XL_GSEG - 1) / XL_GSEG * Rpm * Rpm * 8, 256);
         t.M = t.G + round_up(Rpm * Rpm * 8, 256);
-        t.total = t.M + round_up(Rpm * Rpm * 4, 256);
+        t.eig = t.M + round_up(Rpm * Rpm * 4, 256);
+        t.total = t.eig + eig_workspace(t.Rpm, 1);
         return t;
     }
     void tsv_apply(const float* b, int bp, const float* w, int wp, int rows, int cols, int Rp, const void* base_out, int dtype,
@@ -1331,6 +1370,7 @@ class DeltaHost {
         const TsvLayout t = tsv_layout(d.rows, d.cols, d.k, d.rank);
         const XlLayout& y = t.y;
         const int L = y.L, rows = d.rows, cols = d.cols, r = t.r, Rpm = t.Rpm;
+        eig_device = d.eig == SMHIP_EIG_DEVICE;
         char* ws = (char*)d.workspace;
         float* p0 = (float*)ws;
         float* p1 = (float*)(ws + y.pan);
@@ -1401,16 +1441,21 @@ class DeltaHost {
             auto whiten = [&](const float* pan, int m, double* mu_out, int& kept, std::vector<double>& S) {
                 xl_gram_at(pan, m, Rp, Rpm, (double*)(ws + t.gpart), (double*)(ws + t.G));
                 std::vector<double> G((size_t)Rp * Rp), A((size_t)R * R), mu(R), Ev((size_t)R * R);
-                be.d2h(G.data(), ws + t.G, G.size() * 8, stream);
                 S.assign((size_t)R * R, 0.0);
-                if (!be.ok()) return;
-                for (int a = 0; a < R; ++a)
-                    for (int b = 0; b < R; ++b) {
-                        A[(size_t)a * R + b] = G[(size_t)a * Rp + b];
-                        if (!geo_finite(A[(size_t)a * R + b])) bad = true;
-                    }
-                if (bad) return;
-                xl_sym_eig_timed(R, A.data(), mu.data(), Ev.data());
+                if (eig_device) {                               // the leading R x R block of the Gram, where it is
+                    if (!sym_eig_par(R, Rp, 1, (const double*)(ws + t.G), mu.data(), Ev.data(), nullptr, ws + t.eig)) bad = true;
+                    if (!be.ok() || bad) return;
+                } else {
+                    be.d2h(G.data(), ws + t.G, G.size() * 8, stream);
+                    if (!be.ok()) return;
+                    for (int a = 0; a < R; ++a)
+                        for (int b = 0; b < R; ++b) {
+                            A[(size_t)a * R + b] = G[(size_t)a * Rp + b];
+                            if (!geo_finite(A[(size_t)a * R + b])) bad = true;
+                        }
+                    if (bad) return;
+                    xl_sym_eig_timed(R, A.data(), mu.data(), Ev.data());
+                }
                 const double cut = geo_dmul(1e-6, mu[0]);
                 for (int j = 0; j < R; ++j) {
                     mu_out[j] = mu[j];

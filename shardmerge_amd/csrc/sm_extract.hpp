@@ -325,6 +325,32 @@ SM_HD void k_xl_panel_mm(Ex& ex, const XlPanelMmParams& p) {
     });
 }
 
+// ---- host: the tail of both eigensolvers (xl_sym_eig below, smhip_sym_eig_par of sm_eig.hpp).  From the iteration's
+// diagonal (element i at d[i * dstride]) and its vectors vin [n][vpitch]: sort (stable insertion by descending eigenvalue,
+// ties keep the lower original index first), then the signs (the largest-magnitude entry of a column, the first on ties,
+// positive).  lam [n], vout [n][n]; vout may be vin. ----
+inline void xl_eig_sort_signs(int n, const double* d, size_t dstride, const double* vin, size_t vpitch, double* lam, double* vout) {
+    std::vector<int> ord(n);
+    for (int i = 0; i < n; ++i) ord[i] = i;
+    for (int i = 1; i < n; ++i) {
+        const int o = ord[i];
+        int j = i;
+        while (j > 0 && d[ord[j - 1] * dstride] < d[o * dstride]) { ord[j] = ord[j - 1]; --j; }
+        ord[j] = o;
+    }
+    std::vector<double> vs((size_t)n * n);
+    for (int i = 0; i < n; ++i) {
+        const int o = ord[i];
+        lam[i] = d[o * dstride];
+        int big = 0;
+        for (int k = 1; k < n; ++k)
+            if (std::fabs(vin[k * vpitch + o]) > std::fabs(vin[big * vpitch + o])) big = k;
+        const bool neg = vin[big * vpitch + o] < 0.0;
+        for (int k = 0; k < n; ++k) vs[(size_t)k * n + i] = neg ? -vin[k * vpitch + o] : vin[k * vpitch + o];
+    }
+    for (size_t i = 0; i < (size_t)n * n; ++i) vout[i] = vs[i];
+}
+
 // ---- host: eigenvalues and eigenvectors of a symmetric n x n fp64 matrix, cyclic Jacobi ----
 // a [n][n] (both triangles; destroyed), lam [n] descending (ties: the lower original index first), v [n][n] with
 // eigenvector i in COLUMN i, its largest-magnitude entry (the first on ties) positive.  Every operation is one rounded
@@ -377,26 +403,7 @@ inline int xl_sym_eig(int n, double* a, double* lam, double* v) {
             }
         if (!rotated) break;
     }
-    // sort (stable insertion by descending eigenvalue), then the signs
-    std::vector<int> ord(n);
-    for (int i = 0; i < n; ++i) ord[i] = i;
-    for (int i = 1; i < n; ++i) {
-        const int o = ord[i];
-        int j = i;
-        while (j > 0 && a[(size_t)ord[j - 1] * n + ord[j - 1]] < a[(size_t)o * n + o]) { ord[j] = ord[j - 1]; --j; }
-        ord[j] = o;
-    }
-    std::vector<double> vs((size_t)n * n);
-    for (int i = 0; i < n; ++i) {
-        const int o = ord[i];
-        lam[i] = a[(size_t)o * n + o];
-        int big = 0;
-        for (int k = 1; k < n; ++k)
-            if (std::fabs(v[(size_t)k * n + o]) > std::fabs(v[(size_t)big * n + o])) big = k;
-        const bool neg = v[(size_t)big * n + o] < 0.0;
-        for (int k = 0; k < n; ++k) vs[(size_t)k * n + i] = neg ? -v[(size_t)k * n + o] : v[(size_t)k * n + o];
-    }
-    for (size_t i = 0; i < (size_t)n * n; ++i) v[i] = vs[i];
+    xl_eig_sort_signs(n, a, (size_t)n + 1, v, n, lam, v);
     return sweeps;
 }
 

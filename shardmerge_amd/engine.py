@@ -769,13 +769,15 @@ class Engine:
 
     # -- extract-lora ------------------------------------------------------------------------
     def lora_extract(self, finetune: torch.Tensor, base: torch.Tensor, rank: int, *, power_iters: int = 2,
-                     factor_dtype: Optional[torch.dtype] = None, seed: int = 0, name: str = ""):
+                     factor_dtype: Optional[torch.dtype] = None, seed: int = 0, name: str = "", eig: str = "host"):
         """A rank-``rank`` adapter of one 2-D tensor: ``(A [rank, cols], B [rows, rank], LoraExtractReport)`` with
         ``B @ A`` the randomized rank-``rank`` approximation of ``finetune - base`` (``smhip_lora_extract``; the function
         is stated in include/shardmerge_hip.h), ``lora_alpha = rank``.  The sketch is keyed as the DARE mask is: the
         first 8 bytes of ``sha256(f"{seed}\\n{name}")``.  factor_dtype: of A and B, default the inputs' dtype.  A NaN or
-        Inf in the delta raises ValueError naming ``name``."""
+        Inf in the delta raises ValueError naming ``name``.  eig: "host" (the cyclic solver) or "device" (``sym_eig``'s)."""
         import hashlib
+        if eig not in _lib.EIG_METHODS:
+            raise ValueError(f"lora_extract: eig must be 'host' or 'device', not {eig!r}")
         if finetune.ndim != 2 or finetune.shape != base.shape:
             raise ValueError(f"lora_extract: two 2-D tensors of one shape expected, got {list(finetune.shape)} / {list(base.shape)}")
         if isinstance(rank, bool) or not isinstance(rank, int) or not (1 <= rank <= _lib.EXTRACT_MAX_RANK):
@@ -793,7 +795,7 @@ class Engine:
         ws = self._xl_workspace(int(self.lib.dll.smhip_lora_extract_workspace(rows, cols, rank)))
         key = int.from_bytes(hashlib.sha256(f"{seed}\n{name}".encode()).digest()[:8], "little")
         desc = _lib.ExtractDesc(ft.data_ptr(), bs.data_ptr(), _DTYPE_CODE[in_dtype], rows, cols, rank, power_iters, key,
-                                _DTYPE_CODE[factor_dtype], ws.data_ptr(), ws.numel())
+                                _DTYPE_CODE[factor_dtype], ws.data_ptr(), ws.numel(), _lib.EIG_METHODS[eig])
         rep = _lib.ExtractReport()
         self._call(self.lib.dll.smhip_lora_extract(self.ctx.h, C.byref(desc), a.data_ptr(), b.data_ptr(), C.byref(rep),
                                                    self._stream()), name or "tensor")
@@ -801,6 +803,39 @@ class Engine:
                                        effective_rank=int(rep.rho), orth_ranks=[int(rep.orth_rank[i]) for i in range(rep.n_orth)],
                                        sigma=[float(rep.sigma[i]) for i in range(rep.L)], delta_sq=float(rep.delta_sq),
                                        share=float(rep.share))
+
+    # -- the symmetric eigensolver ---------------------------------------------------------------
+    def sym_eig(self, a: torch.Tensor, *, method: str = "device"):
+        """Eigenvalues and eigenvectors of a symmetric fp64 matrix ``[n, n]`` or of a batch ``[b, n, n]``, n <= 272:
+        ``(lam, v, sweeps)`` on the CPU with ``lam`` descending, eigenvector i in column i with its largest entry positive,
+        and the Jacobi sweeps run per matrix.  ``method="device"`` is the parallel-ordered Jacobi kernel
+        (``smhip_sym_eig_par``, one work-group per matrix), ``"host"`` the cyclic solver of ``lora_extract`` and
+        ``tsv_merge``; both are stated in include/shardmerge_hip.h and differ by rounding.  Both triangles are read; a NaN
+        or an Inf raises ValueError."""
+        if method not in _lib.EIG_METHODS:
+            raise ValueError(f"sym_eig: method must be 'host' or 'device', not {method!r}")
+        if a.dtype != torch.float64 or a.ndim not in (2, 3) or a.shape[-1] != a.shape[-2]:
+            raise ValueError(f"sym_eig: an fp64 tensor [n, n] or [b, n, n] expected, got {a.dtype} {list(a.shape)}")
+        n, batch = int(a.shape[-1]), int(a.shape[0]) if a.ndim == 3 else 1
+        if not (1 <= n <= _lib.EXTRACT_MAX_L) or batch < 1:
+            raise ValueError(f"sym_eig: n must be in 1..{_lib.EXTRACT_MAX_L} and the batch not empty, got {list(a.shape)}")
+        lam = torch.empty((batch, n), dtype=torch.float64)
+        v = torch.empty((batch, n, n), dtype=torch.float64)
+        sweeps = torch.empty(batch, dtype=torch.int32)
+        if method == "host":
+            src = a.detach().cpu().contiguous()
+            if not bool(torch.isfinite(src).all()):
+                raise ValueError("sym_eig: NaN or Inf in the matrix")
+            self._call(self.lib.dll.smhip_sym_eig_host(self.ctx.h, n, batch, src.data_ptr(), lam.data_ptr(), v.data_ptr(),
+                                                       sweeps.data_ptr()))
+        else:
+            src = self._dev(a, torch.float64)
+            ws = self._xl_workspace(int(self.lib.dll.smhip_sym_eig_par_workspace(n, batch)))
+            self._call(self.lib.dll.smhip_sym_eig_par(self.ctx.h, n, batch, src.data_ptr(), lam.data_ptr(), v.data_ptr(),
+                                                      sweeps.data_ptr(), ws.data_ptr(), self._stream()), "sym_eig")
+        if a.ndim == 2:
+            return lam[0], v[0], int(sweeps[0])
+        return lam, v, sweeps
 
     def _xl_workspace(self, nbytes: int) -> torch.Tensor:
         """a 256-byte aligned device buffer of at least nbytes (kept and regrown: the walk calls per tensor)"""
@@ -1338,7 +1373,7 @@ class Engine:
     # -- TSV (task singular vectors) ------------------------------------------------------------
     def tsv_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
                   base_out: torch.Tensor, *, rank: int = 64, power_iters: int = 2, lam: float = 1.0, key: int = 0,
-                  want_delta: bool = False, layer_name: str = ""):
+                  want_delta: bool = False, layer_name: str = "", eig: str = "host"):
         """TSV merge of one tensor with at least two dimensions, viewed as ``[shape[0], rest]`` (``smhip_tsv_merge``; the
         function is stated in include/shardmerge_hip.h): the ``rank`` leading singular triplets of every delta
         ``finetune_i - base_i`` by a randomized subspace iteration with ``power_iters`` power steps under ``key``, the
@@ -1346,8 +1381,11 @@ class Engine:
         merged delta rebuilt with the singular values times ``alpha_i`` and added, times ``lam``, onto ``base_out`` in its
         dtype.  An entry with ``alpha_i == 0`` is skipped; the others must satisfy ``k * min(rank, rows, cols) <= 256``.
         Returns (out, TsvReport[, the fp32 merged delta before ``lam``]).  A NaN or Inf in a delta raises ValueError
-        naming ``layer_name`` and the finetune."""
+        naming ``layer_name`` and the finetune.  eig: "host" (the cyclic solver) or "device" (``sym_eig``'s, for every
+        decomposition of the call)."""
         layer_name = layer_name or "layer"
+        if eig not in _lib.EIG_METHODS:
+            raise ValueError(f"tsv_merge: eig must be 'host' or 'device', not {eig!r}")
         if isinstance(rank, bool) or not isinstance(rank, int) or not (1 <= rank <= _lib.EXTRACT_MAX_RANK):
             raise ValueError(f"tsv_merge: rank must be an integer in 1..{_lib.EXTRACT_MAX_RANK}, not {rank!r}")
         if isinstance(power_iters, bool) or not isinstance(power_iters, int) or not (0 <= power_iters <= _lib.EXTRACT_MAX_POWER):
@@ -1364,6 +1402,7 @@ class Engine:
         rows = int(bo.shape[0])
         cols = int(desc.n // rows) if rows else 0
         desc.rows, desc.cols, desc.rank, desc.power_iters, desc.lam, desc.key = rows, cols, rank, power_iters, float(lam), int(key)
+        desc.eig = _lib.EIG_METHODS[eig]
         r = min(rank, rows, cols)
         active = sum(1 for a in alphas if float(a) != 0.0)
         if active * r > _lib.TSV_MAX_R:

@@ -43,7 +43,9 @@ def parse_modules(text: Optional[str]) -> Optional[List[str]]:
 
 class LoraExtraction:
     def __init__(self, model: str, base: str, rank: int, out_dir: Path, storage_dir: Path, modules: Optional[Sequence[str]] = None,
-                 power_iters: int = 2, factor_dtype: torch.dtype = torch.bfloat16, seed: int = 0, index_manager=None, engine=None):
+                 power_iters: int = 2, factor_dtype: torch.dtype = torch.bfloat16, seed: int = 0, index_manager=None, engine=None,
+                 eig: str = "host"):
+        self.eig = eig                      # "host" | "device": the solver of the small eigenproblems (Engine.lora_extract)
         self.model, self.base, self.rank, self.out_dir = model, base, rank, Path(out_dir)
         self.storage_dir, self.modules = Path(storage_dir), list(modules) if modules else None
         self.power_iters, self.factor_dtype, self.seed = power_iters, factor_dtype, seed
@@ -154,7 +156,7 @@ class LoraExtraction:
                 rows, cols = ft.shape
                 r = min(self.rank, rows, cols)
                 a, b, rep = eng.lora_extract(ft, bs, r, power_iters=self.power_iters, factor_dtype=self.factor_dtype,
-                                             seed=self.seed, name=name)
+                                             seed=self.seed, name=name, eig=self.eig)
                 if r != self.rank:
                     rank_pattern[module] = r
                 if module.split(".")[-1] in EMBEDDING_MODULES:
@@ -179,7 +181,7 @@ class LoraExtraction:
                   "use_rslora": False, "use_dora": False, "modules_to_save": None, "rank_pattern": rank_pattern,
                   "alpha_pattern": dict(rank_pattern), "base_model_name_or_path": self.base}
         report = {"model": self.model, "base": self.base, "rank": self.rank, "power_iters": self.power_iters, "seed": self.seed,
-                  "factor_dtype": next(k for k, v in DTYPES.items() if v == self.factor_dtype), "tensors": tensors,
+                  "eig": self.eig, "factor_dtype": next(k for k, v in DTYPES.items() if v == self.factor_dtype), "tensors": tensors,
                   "skipped": skipped, "unchanged": unchanged, "not_selected": not_selected}
         self.write(factors, config, report)
         return report
@@ -204,5 +206,5 @@ def format_table(report: dict) -> str:
 
 
 async def run_extraction(model: str, base: str, rank: int, out_dir: Path, storage_dir: Path, modules=None, power_iters: int = 2,
-                         factor_dtype: torch.dtype = torch.bfloat16, seed: int = 0, device: str = "cuda") -> dict:
-    return await LoraExtraction(model, base, rank, out_dir, storage_dir, modules, power_iters, factor_dtype, seed).extract(device)
+                         factor_dtype: torch.dtype = torch.bfloat16, seed: int = 0, device: str = "cuda", eig: str = "host") -> dict:
+    return await LoraExtraction(model, base, rank, out_dir, storage_dir, modules, power_iters, factor_dtype, seed, eig=eig).extract(device)

@@ -45,7 +45,7 @@ class FourierMerge(MergeTensorsBase):
         self.norm_mode = getattr(config, "norm_mode", None) or DEFAULT_NORM_MODE
         # optional YAML overrides (config.merge_options); absent keys keep the reference's values
         for key, value in (getattr(config, "merge_options", None) or {}).items():
-            setattr(self, key, float(value))
+            setattr(self, key, value if isinstance(value, str) else float(value))
         self._engine = engine
         self.last_report = None
 

@@ -34,6 +34,7 @@ class TsvMerge(TiesMerge):
         opts = getattr(config, "merge_options", None) or {}
         for key in ("tsv_rank", "tsv_power_iters", "seed"):         # exactly
             setattr(self, key, int(opts.get(key, TSV_OPTION_DEFAULTS[key])))
+        self.tsv_eig = str(opts.get("tsv_eig", TSV_OPTION_DEFAULTS["tsv_eig"]))
 
     async def initialize(self):
         await super().initialize()
@@ -70,7 +71,7 @@ class TsvMerge(TiesMerge):
     def get_readme(self) -> str:
         return self._readme("TSV", f"TSV (task singular vectors: the leading singular triplets of every delta, whitened across "
                                    f"the finetunes, rebuilt), rank {self.tsv_rank}, power iterations {self.tsv_power_iters}, "
-                                   f"lambda {self.tsv_lambda:g}, seed {self.seed}; 1-D tensors and tensors of one entry: the "
+                                   f"lambda {self.tsv_lambda:g}, seed {self.seed}, eigensolver {self.tsv_eig}; 1-D tensors and tensors of one entry: the "
                                    f"normalised weighted mean of the deltas")
 
     def merge_block(self, eng, fts, bases, alphas, base_out, name: str):
@@ -79,7 +80,7 @@ class TsvMerge(TiesMerge):
                                   sign_election=False, key=tensor_key(self.seed, name), stream_ids=list(range(len(fts))),
                                   layer_name=name)
         return eng.tsv_merge(fts, bases, alphas, base_out, rank=self.tsv_rank, power_iters=self.tsv_power_iters,
-                             lam=self.tsv_lambda, key=tensor_key(self.seed, name), layer_name=name)
+                             lam=self.tsv_lambda, key=tensor_key(self.seed, name), layer_name=name, eig=self.tsv_eig)
 
     def tensor_passes(self, k: int) -> int:
         # k (2 q + 2) delta products and k energies of two reads each, base_out read and out written
@@ -90,5 +91,5 @@ class TsvMerge(TiesMerge):
             logger.info(f"Merged {name}: {k} model(s), TSV took the weighted mean of the deltas (not a matrix, or one entry)")
             return
         logger.info(f"Merged {name}: {k} model(s), TSV rank {self.tsv_rank} q {self.tsv_power_iters} lambda {self.tsv_lambda:g} "
-                    f"seed {self.seed}: R {report.R}, kept_U {report.kept_U} / kept_W {report.kept_W}, energy shares "
+                    f"seed {self.seed} eig {self.tsv_eig}: R {report.R}, kept_U {report.kept_U} / kept_W {report.kept_W}, energy shares "
                     f"{[float(f'{s:.4g}') for s in report.share]}")

@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--power-iters", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="8192x8192,28672x8192")
+    ap.add_argument("--eig", default="host", choices=["host", "device"], help="the eigensolver of the extraction")
     args = ap.parse_args()
     from shardmerge_amd.engine import get_engine
     eng = get_engine("cuda:0")
@@ -42,14 +43,14 @@ def main():
         g = torch.Generator(device="cuda").manual_seed(1)
         base = (0.02 * torch.randn(rows, cols, device="cuda", generator=g)).bfloat16()
         ft = (base.float() + 0.003 * torch.randn(rows, cols, device="cuda", generator=g)).bfloat16()
-        t_x = timed(lambda: eng.lora_extract(ft, base, r, power_iters=q, name="bench"), args.reps)
+        t_x = timed(lambda: eng.lora_extract(ft, base, r, power_iters=q, name="bench", eig=args.eig), args.reps)
         t_c = timed(lambda: [(ft.clone(), base.clone()) for _ in range(2 * q + 2)], args.reps)
         delta = ft.float() - base.float()
         t_s = timed(lambda: torch.svd_lowrank(delta, q=r + 8, niter=q), max(1, args.reps // 2))
         eng.ctx.profile(True)
         eng.ctx.profile_reset()
         t0 = time.perf_counter()
-        eng.lora_extract(ft, base, r, power_iters=q, name="bench")
+        eng.lora_extract(ft, base, r, power_iters=q, name="bench", eig=args.eig)
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t0) * 1e3
         table = eng.ctx.profile_table()

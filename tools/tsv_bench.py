@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--seconds", type=float, default=1.0, help="timed work per streaming contender and case")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--eig", default="host", choices=["host", "device"],
+                    help="the eigensolver of the timed tsv; with device the host solver is timed beside it, alternating in every round")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if args.rounds < 5:
@@ -61,7 +63,8 @@ def main():
     for rows, cols, k, base, fts, bases in cases(args.shapes, args.ks, DT[args.dtype], dev):
         nbytes = (2 * k * (2 * q + 3) + 2) * base.numel() * base.element_size()
         blob = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-        tsv = lambda: eng.tsv_merge(fts, bases, alphas[:k], base, rank=args.rank, power_iters=q, key=1)
+        tsv = lambda: eng.tsv_merge(fts, bases, alphas[:k], base, rank=args.rank, power_iters=q, key=1, eig=args.eig)
+        tsv_host = lambda: eng.tsv_merge(fts, bases, alphas[:k], base, rank=args.rank, power_iters=q, key=1)
         streaming = {"ties": lambda: eng.ties_merge(fts, bases, alphas[:k], base, density=args.density), "clone": lambda: blob.clone()}
         tsv()                                                       # warm-up: the workspace, the code objects
         reps = {}
@@ -71,20 +74,25 @@ def main():
             torch.cuda.synchronize()
             reps[name] = max(5, int(args.seconds * 1e3 / args.rounds / max(window(fn, 3), 1e-3)))
         times = {"tsv": [], "ties": [], "clone": []}
+        if args.eig == "device":
+            times["tsv_eig_host"] = []
         for _ in range(args.rounds):
             times["tsv"].append(wall_ms(tsv))
+            if args.eig == "device":
+                times["tsv_eig_host"].append(wall_ms(tsv_host))
             for name, fn in streaming.items():
                 times[name].append(window(fn, reps[name]))
         eng.ctx.profile(True)
         eng.ctx.profile_reset()
         try:
-            eig0 = eng.ctx.debug_query("eig_host_us")
+            eig0, dev0 = eng.ctx.debug_query("eig_host_us"), eng.ctx.debug_query("eig_dev_us")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             _, rep = tsv()
             torch.cuda.synchronize()
             profiled_ms = (time.perf_counter() - t0) * 1e3
             eig_ms = (eng.ctx.debug_query("eig_host_us") - eig0) / 1e3
+            dev_ms = (eng.ctx.debug_query("eig_dev_us") - dev0) / 1e3      # launch, read-back and sort; it contains eig_jacobi's time
             table = eng.ctx.profile_table()
         finally:
             eng.ctx.profile(False)
@@ -92,7 +100,7 @@ def main():
         kernel_ms = sum(v[1] for v in kernels.values())
         rec = {"tsv_bench": f"{rows}x{cols}", "dtype": args.dtype, "k": k, "rank": args.rank, "power_iters": q, "R": rep.R, "Rp": rep.Rp,
                "L": rep.width, "kept": [rep.kept_U, rep.kept_W], "share": [round(s, 4) for s in rep.share], "ties_density": args.density,
-               "bytes": nbytes, "rounds": args.rounds}
+               "eig": args.eig, "bytes": nbytes, "rounds": args.rounds}
         med = {name: statistics.median(t) for name, t in times.items()}
         for name, t in times.items():
             rec[f"{name}_ms"] = round(med[name], 4)
@@ -104,7 +112,8 @@ def main():
         rec["kernels_ms"] = kernels
         rec["kernels_sum_ms"] = round(kernel_ms, 3)
         rec["host_sym_eig_ms"] = round(eig_ms, 3)
-        rec["host_other_ms"] = round(profiled_ms - kernel_ms - eig_ms, 3)
+        rec["device_sym_eig_ms"] = round(dev_ms, 3)
+        rec["host_other_ms"] = round(profiled_ms - kernel_ms - eig_ms - max(0.0, dev_ms - kernels.get("eig_jacobi", [0, 0.0])[1]), 3)
         apply_ms = kernels["tsv_apply"][1]
         rec["tsv_apply_TF"] = round(2.0 * rows * cols * rep.Rp / apply_ms / 1e9, 2)
         rec["tsv_apply_share_of_155TF"] = round(rec["tsv_apply_TF"] / FP32_MFMA_TF, 3)
