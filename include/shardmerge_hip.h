@@ -1410,6 +1410,65 @@ typedef struct {
 /* out: device, dtype, [rows][cols]; it must not overlap an input */
 int smhip_dpack_apply(smhip_ctx* ctx, const smhip_dpack_apply_desc* desc, void* out, void* stream);
 
+/* ---- Block-scaled FP8: a tensor as OCP E4M3 codes and one fp32 scale per 128 x 128 block, the layout of the
+ *      `quant_method: "fp8"` checkpoints (X.weight as F8_E4M3, X.weight_scale_inv as F32 [ceil(R / 128)][ceil(C / 128)];
+ *      as recalled: PAPERS.md).  It is a DATA TYPE, no merge operator: smhip_fp8_dequant rebuilds the tensor that every
+ *      operator then takes.  The reference has no such type; this section IS its definition.
+ *      THE ENCODING.  OCP E4M3 "fn": one sign bit, four exponent bits of bias 7, three mantissa bits; no infinities; NaN
+ *      is S.1111.111 (0x7F, 0xFF); the largest finite value is 448 (0x7E), the smallest subnormal 2^-9 (0x01).
+ *        e4m3_to_f32(code) is exact; a NaN code gives the fp32 NaN sign | 0x7ff00000.
+ *        f32_to_e4m3(v) rounds to nearest, ties to even, on the E4M3 grid, subnormals included.  It SATURATES: every
+ *        |v| >= 448, Inf included, gives +-448 (0x7E / 0xFE) - on [448, 464] that is the rounding, beyond it the clamp.
+ *        NaN gives 0x7F.
+ *      QUANT, smhip_fp8_quant.  The tensor is R = rows rows of C = cols elements of bf16, fp16 or fp32; block (bi, bj)
+ *      holds rows 128 bi .. and columns 128 bj .., edge blocks are partial.
+ *        1. Per block a = max |fp32(x)| over its elements: exact and order-free.  A NaN or an Inf in the input fails the
+ *           call with SMHIP_ERR_NONFINITE; the outputs are then unspecified.
+ *        2. s = max(a / 448.0f, 2^-126): ONE rounded fp32 division.  A block of zeros, or one whose a / 448 is
+ *           denormal, gets the smallest normal scale; nothing divides by zero.
+ *        3. code = f32_to_e4m3(fp32(x) / s): ONE rounded fp32 division per element, then the conversion.  The two
+ *           roundings are part of the definition.  |x / s| <= 448 (1 + 2^-23): the clamp never acts.
+ *        4. scale_inv[bi][bj] = s.
+ *        5. The report: blocks, zero_blocks (the blocks with a == 0: their codes are all 0x00 or 0x80), amax (the
+ *           largest a) and flags (bit 0: a NaN or an Inf was met).
+ *      DEQUANT, smhip_fp8_dequant: w = round_to(out_dtype, e4m3_to_f32(code) * s) with s the scale of the element's
+ *      block - ONE fp32 multiplication rounded once, then one round-to-nearest-even cast into bf16, fp16 or fp32.  A NaN
+ *      code fails the call with SMHIP_ERR_NONFINITE.
+ *      Both functions equal three lines of torch on the CPU bit for bit: a.float() / 448 (clamped below at 2^-126),
+ *      (x.float() / s).to(torch.float8_e4m3fn) and (q.float() * s).to(dtype), with s broadcast over its block.
+ *      PROBE, smhip_fp8_fn: the two conversions alone over a flat array - SMHIP_FP8_ENCODE: x float [n] -> y uint8 [n];
+ *      SMHIP_FP8_DECODE: x uint8 [n] -> y float [n]; by a kernel (on_device != 0, device arrays) or on the host.
+ *      rows cols == 0: nothing is written and the report is zero.  SMHIP_ERR_ARG: a block other than 128 x 128, a bad
+ *      dtype, a null or misaligned pointer, an output that overlaps an input or another output, a tensor too large.
+ *      C % 8 == 0 with a 16-byte aligned tensor and 8-byte aligned codes moves whole blocks in 16- and 8-byte accesses;
+ *      anything else goes element by element and is as exact.  Both synchronise the stream once, at their end (the
+ *      blocks' maxima / the flag word are read back).  Profile names: "fp8_quant"; "fp8_dequant"; "fp8_fn". ---- */
+#define SMHIP_FP8_BLOCK 128
+enum { SMHIP_FP8_ENCODE = 0, SMHIP_FP8_DECODE = 1 };
+typedef struct {
+    const void* x; int dtype;               /* device, [rows][cols], SMHIP_BF16 / F16 / F32 */
+    size_t rows, cols;
+    int block_rows, block_cols;             /* both SMHIP_FP8_BLOCK */
+} smhip_fp8_quant_desc;
+typedef struct {
+    uint64_t blocks, zero_blocks;
+    float amax;
+    uint32_t flags;
+} smhip_fp8_report;
+/* codes: device uint8 [rows][cols].  scale_inv: device float [ceil(rows / 128)][ceil(cols / 128)].
+ * report (optional): HOST. */
+int smhip_fp8_quant(smhip_ctx* ctx, const smhip_fp8_quant_desc* desc, uint8_t* codes, float* scale_inv,
+                    smhip_fp8_report* report, void* stream);
+typedef struct {
+    const uint8_t* codes; const float* scale_inv; /* device, as smhip_fp8_quant writes them */
+    size_t rows, cols;
+    int block_rows, block_cols;             /* both SMHIP_FP8_BLOCK */
+    int out_dtype;                          /* SMHIP_BF16 / F16 / F32 */
+} smhip_fp8_dequant_desc;
+/* out: device, out_dtype, [rows][cols]; it must not overlap an input */
+int smhip_fp8_dequant(smhip_ctx* ctx, const smhip_fp8_dequant_desc* desc, void* out, void* stream);
+int smhip_fp8_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int on_device, void* stream);
+
 /* ---- EMR-Merging (Huang et al., "EMR-Merging: Tuning-Free High-Performance Model Merging", NeurIPS 2024; as recalled:
  *      PAPERS.md): ONE unified task vector is ELECTED from the finetunes' deltas - per element the sign of their sum and
  *      the largest magnitude among the entries of that sign - and every task gets a 1-bit MASK (where its own delta

@@ -211,6 +211,55 @@ def compress_delta_command(model: str, base: str, out_dir: Path, storage_dir: Pa
     click.echo(f"delta pack: {out_dir}")
 
 
+def _fp8_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str, verbose: bool):
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.extract import parse_modules
+        from .merge.fp8 import format_table, run_fp8
+        result = asyncio.run(run_fp8(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device))
+    except Exception as exc:
+        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"model: {out_dir}")
+
+
+@cli.command("quantize-fp8")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the FP8 checkpoint is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--modules", type=str, default=None,
+              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
+                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def quantize_fp8_command(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool):
+    """MODEL as a block-scaled FP8 checkpoint: E4M3 weights with one fp32 scale per 128 x 128 block.
+
+    DIR receives the shards (X.weight as F8_E4M3, X.weight_scale_inv as F32), model.safetensors.index.json and a
+    config.json with the quantization_config block; it can be named as a finetune_merge entry of `merge` in place of MODEL.
+    """
+    _fp8_command("quantize-fp8", model, out_dir, storage_dir, modules, "bf16", device, verbose)
+
+
+@cli.command("dequantize-fp8")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the FP8 tensors are written in")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def dequantize_fp8_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
+    """The block-scaled FP8 checkpoint MODEL written out in 16 or 32 bits: code times its block's scale, rounded once.
+
+    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
+    """
+    _fp8_command("dequantize-fp8", model, out_dir, storage_dir, None, dtype, device, verbose)
+
+
 @cli.command("emr-task")
 @click.argument("model", type=str)
 @click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")

@@ -392,7 +392,28 @@ class DpackApplyDesc(C.Structure):
                 ("sign", C.c_void_p), ("mask", C.c_void_p), ("scale", C.c_void_p), ("scale_mode", C.c_int)]
 
 
-DELLA_MAX_COLS = 32768         # the longest row smhip_della_merge ranks (a row is sorted in LDS)
+FP8_BLOCK = 128                                     # rows and columns of a scale block of smhip_fp8_quant / smhip_fp8_dequant
+FP8_ENCODE, FP8_DECODE = 0, 1                       # op of smhip_fp8_fn
+
+
+class Fp8QuantDesc(C.Structure):
+    """smhip_fp8_quant_desc"""
+    _fields_ = [("x", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t),
+                ("block_rows", C.c_int), ("block_cols", C.c_int)]
+
+
+class Fp8Report(C.Structure):
+    """smhip_fp8_report"""
+    _fields_ = [("blocks", C.c_uint64), ("zero_blocks", C.c_uint64), ("amax", C.c_float), ("flags", C.c_uint32)]
+
+
+class Fp8DequantDesc(C.Structure):
+    """smhip_fp8_dequant_desc"""
+    _fields_ = [("codes", C.c_void_p), ("scale_inv", C.c_void_p), ("rows", C.c_size_t), ("cols", C.c_size_t),
+                ("block_rows", C.c_int), ("block_cols", C.c_int), ("out_dtype", C.c_int)]
+
+
+DELLA_MAX_COLS = 32768        # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
 class LayerReport(C.Structure):
@@ -486,6 +507,9 @@ class SmhipLibrary:
         d.smhip_iso_gemm.argtypes = [P, C.POINTER(IsoGemmDesc), P]
         d.smhip_dpack_pack.argtypes = [P, C.POINTER(DpackDesc), P, P, P, C.POINTER(DpackReport), P]
         d.smhip_dpack_apply.argtypes = [P, C.POINTER(DpackApplyDesc), P, P]
+        d.smhip_fp8_quant.argtypes = [P, C.POINTER(Fp8QuantDesc), P, P, C.POINTER(Fp8Report), P]
+        d.smhip_fp8_dequant.argtypes = [P, C.POINTER(Fp8DequantDesc), P, P]
+        d.smhip_fp8_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
         d.smhip_emr_merge.argtypes = [P, C.POINTER(EmrDesc), P, P, C.POINTER(EmrReport), P]
         d.smhip_emr_mask.argtypes = [P, C.POINTER(EmrMaskDesc), P, P, C.POINTER(EmrMaskReport), P]
         d.smhip_emr_apply.argtypes = [P, C.POINTER(EmrApplyDesc), P, P]

@@ -705,6 +705,51 @@ int smhip_dpack_apply(smhip_ctx* ctx, const smhip_dpack_apply_desc* d, void* out
     SM_FINISH(ctx, ctx->pipe.delta.dpack_apply(*d, out));
 }
 
+// what smhip_fp8_quant and smhip_fp8_dequant share on top of dpack_check: the block size
+static int fp8_check(smhip_ctx* ctx, const char* op, int dtype, size_t rows, size_t cols, int block_rows, int block_cols,
+                     std::initializer_list<dpack_span> ins, std::initializer_list<dpack_span> outs) {
+    if (block_rows != SMHIP_FP8_BLOCK || block_cols != SMHIP_FP8_BLOCK)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": block size " + std::to_string(block_rows) + " x " +
+                                                 std::to_string(block_cols) + " is not 128 x 128");
+    return dpack_check(ctx, op, dtype, rows, cols, SMHIP_DPACK_ROW, ins, outs);
+}
+static size_t fp8_blocks(size_t rows, size_t cols) {
+    return rows * cols ? ((rows + SMHIP_FP8_BLOCK - 1) / SMHIP_FP8_BLOCK) * ((cols + SMHIP_FP8_BLOCK - 1) / SMHIP_FP8_BLOCK) : 0;
+}
+
+int smhip_fp8_quant(smhip_ctx* ctx, const smhip_fp8_quant_desc* d, uint8_t* codes, float* scale_inv,
+                    smhip_fp8_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "fp8_quant: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols;
+    if (int rc = fp8_check(ctx, "fp8_quant", d->dtype, d->rows, d->cols, d->block_rows, d->block_cols, {{d->x, n * es, es}},
+                           {{codes, n, 1}, {scale_inv, fp8_blocks(d->rows, d->cols) * 4, 4}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.fp8_quant(*d, codes, scale_inv, report));
+}
+
+int smhip_fp8_dequant(smhip_ctx* ctx, const smhip_fp8_dequant_desc* d, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "fp8_dequant: null descriptor");
+    const size_t es = d->out_dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols;
+    if (int rc = fp8_check(ctx, "fp8_dequant", d->out_dtype, d->rows, d->cols, d->block_rows, d->block_cols,
+                           {{d->codes, n, 1}, {d->scale_inv, fp8_blocks(d->rows, d->cols) * 4, 4}}, {{out, n * es, es}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.fp8_dequant(*d, out));
+}
+
+int smhip_fp8_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int on_device, void* stream) {
+    SM_GUARD(ctx);
+    if (op != SMHIP_FP8_ENCODE && op != SMHIP_FP8_DECODE) return ctx->pipe.fail(SMHIP_ERR_ARG, "fp8_fn: bad op");
+    if (n > 0 && (!x || !y)) return ctx->pipe.fail(SMHIP_ERR_ARG, "fp8_fn: null array");
+    if ((uintptr_t)(op == SMHIP_FP8_ENCODE ? x : y) % 4) return ctx->pipe.fail(SMHIP_ERR_ARG, "fp8_fn: the float array is not aligned to 4 bytes");
+    if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "fp8_fn: array too large");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.fp8_fn(op, x, y, n, on_device != 0));
+}
+
 int smhip_emr_merge(smhip_ctx* ctx, const smhip_emr_desc* d, void* out, float* delta_out, smhip_emr_report* report,
                     void* stream) {
     SM_GUARD(ctx);

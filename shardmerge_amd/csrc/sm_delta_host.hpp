@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack and EMR-Merging (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack, block-scaled FP8 and EMR-Merging (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -33,6 +33,7 @@
 #include "sm_emr.hpp"
 #include "sm_emr_fused.hpp"
 #include "sm_eig.hpp"
+#include "sm_fp8.hpp"
 
 namespace smhip {
 
@@ -1731,6 +1732,69 @@ class DeltaHost {
         p.out = out; p.row_vec = dpack_row_vec(C, d.base, out);
         p.chunks = pick_chunks(p.units, 256, 2, 8);
         be.template launch<KDpackApply>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
+        return SMHIP_OK;
+    }
+
+    // ---- Block-scaled FP8 (sm_fp8.hpp; smhip_fp8_quant, smhip_fp8_dequant, smhip_fp8_fn).  Quant: one kernel, a
+    // work-group per block; the blocks' maxima are read back once and the report is formed from them here (a maximum of
+    // maxima, a count of zeros, the NaN / Inf test: all exact and order-free).  Dequant: one kernel, the flag word read back.
+    // Workspace: Fp8Head | the blocks' maxima [blocks] ----
+    struct Fp8Head { uint32_t flags[2]; };
+    int fp8_quant(const smhip_fp8_quant_desc& d, uint8_t* codes, float* scale_inv, smhip_fp8_report* rep) {
+        const size_t R = d.rows, C = d.cols;
+        if (rep) *rep = smhip_fp8_report{};
+        if (R * C == 0) return SMHIP_OK;
+        Fp8QuantParams p;
+        p.x = d.x; p.dtype = d.dtype; p.R = R; p.C = C;
+        p.BR = (R + FP8_BLOCK - 1) / FP8_BLOCK; p.BC = (C + FP8_BLOCK - 1) / FP8_BLOCK;
+        const size_t blocks = p.BR * p.BC, off = round_up(sizeof(Fp8Head), 256);
+        Fp8Head* w;
+        if (int rc = plain_workspace(w, off + blocks * sizeof(uint32_t))) return rc;
+        p.codes = codes; p.scale = scale_inv; p.amax = (uint32_t*)ws_at(off);
+        p.vec = (C % 8 == 0 && aligned16(d.x) && ((uintptr_t)codes & 7) == 0) ? 1 : 0;
+        be.template launch<KFp8Quant>((int)std::min<size_t>(blocks, (size_t)1 << 20), FP8_THREADS, (LDS_SCRATCH_FLOATS + 8) * 4, p, stream);
+        std::vector<uint32_t> amax(blocks);
+        be.d2h(amax.data(), p.amax, blocks * sizeof(uint32_t), stream);      // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
+        uint32_t top = 0;
+        uint64_t zeros = 0;
+        for (uint32_t a : amax) { top = std::max(top, a); zeros += a == 0u; }
+        const bool bad = top >= TIES_KEY_INF;
+        if (rep) {
+            rep->blocks = blocks; rep->zero_blocks = zeros; rep->amax = u2f(top); rep->flags = bad ? FP8_FLAG_NONFINITE : 0u;
+        }
+        if (bad) return fail(SMHIP_ERR_NONFINITE, "fp8_quant: NaN or Inf in the tensor");
+        return SMHIP_OK;
+    }
+    int fp8_dequant(const smhip_fp8_dequant_desc& d, void* out) {
+        const size_t R = d.rows, C = d.cols;
+        if (R * C == 0) return SMHIP_OK;
+        Fp8Head* w;
+        if (int rc = plain_workspace(w)) return rc;
+        Fp8DequantParams p;
+        p.codes = d.codes; p.scale = d.scale_inv; p.R = R; p.C = C; p.PB = (C + 7) / 8; p.BC = (C + FP8_BLOCK - 1) / FP8_BLOCK;
+        p.units = R * p.PB; p.out = out; p.out_dtype = d.out_dtype;
+        p.row_vec = (C % 8 == 0 && ((uintptr_t)d.codes & 7) == 0 && aligned16(out)) ? 1 : 0;
+        p.chunks = pick_chunks(p.units, 256, 2, 8);
+        p.flags = w->flags;
+        be.template launch<KFp8Dequant>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
+        Fp8Head host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0] & FP8_FLAG_NAN_CODE) return fail(SMHIP_ERR_NONFINITE, "fp8_dequant: a NaN code (0x7F or 0xFF) in the tensor");
+        return SMHIP_OK;
+    }
+    int fp8_fn(int op, const void* x, void* y, size_t n, bool on_device) {
+        Fp8FnParams p;
+        p.op = op; p.n = n; p.x = x; p.y = y;
+        if (!on_device) {
+            for (size_t i = 0; i < n; ++i) {
+                if (op == FP8_ENCODE) ((uint8_t*)y)[i] = (uint8_t)f32_to_e4m3(((const float*)x)[i]);
+                else ((float*)y)[i] = e4m3_to_f32(((const uint8_t*)x)[i]);
+            }
+        } else if (n) {
+            be.template launch<KFp8Fn>((int)((n + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
+        }
         return SMHIP_OK;
     }
 

@@ -195,6 +195,11 @@ def config_stamp(config: MergeConfig) -> str:
             if is_emr_dir(Path(config.storage_path) / m.model)}            # an EMR pack's: its config and its tensors' header
     if emrs:
         doc["emr_packs"] = emrs
+    from .fp8model import fp8_identity
+    fp8s = {m.model: ident for m in config.finetune_merge
+            if (ident := fp8_identity(Path(config.storage_path) / m.model)) is not None}   # an FP8 checkpoint's: its shard headers
+    if fp8s:
+        doc["fp8_models"] = fp8s
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 

@@ -274,6 +274,16 @@ class DeltaPackReport:
         return math.sqrt(self.resid_sq / self.delta_sq) if self.delta_sq > 0.0 else 0.0
 
 
+@dataclass
+class Fp8Report:
+    rows: int = 0
+    cols: int = 0
+    blocks: int = 0                                                  # 128 x 128 scale blocks, the partial ones included
+    zero_blocks: int = 0                                             # blocks of zeros: scale 2^-126, zero codes
+    amax: float = 0.0                                                # max |x| of the tensor
+    flags: int = 0                                                   # bit 0: a NaN or an Inf was met
+
+
 def _shape_rows(t: torch.Tensor) -> Tuple[int, int]:
     """the delta pack's view of a tensor: R = shape[0] rows of the rest; a 0-D or 1-D tensor is one row"""
     if t.ndim <= 1:
@@ -655,6 +665,89 @@ class Engine:
                                    mk.data_ptr() if mk is not None else None, sc.data_ptr(), mode)
         self._call(self.lib.dll.smhip_dpack_apply(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()))
         return out
+
+    # -- block-scaled FP8 (E4M3, one fp32 scale per 128 x 128 block) -----------------------------------
+    FP8_FNS = {"f32_to_e4m3": _lib.FP8_ENCODE, "e4m3_to_f32": _lib.FP8_DECODE}
+
+    @staticmethod
+    def _fp8_block(op: str, block) -> Tuple[int, int]:
+        if not isinstance(block, (tuple, list)) or len(block) != 2 or any(isinstance(b, bool) or not isinstance(b, int) for b in block):
+            raise ValueError(f"{op}: block {block!r} is not a pair of integers")
+        return int(block[0]), int(block[1])
+
+    def fp8_quant(self, x: torch.Tensor, *, block=(_lib.FP8_BLOCK, _lib.FP8_BLOCK), name: str = ""):
+        """A 2-D tensor as OCP E4M3 codes and one fp32 scale per 128 x 128 block (``smhip_fp8_quant``; the function is
+        stated in include/shardmerge_hip.h): per block ``s = max(amax / 448, 2^-126)`` and ``code = e4m3(x / s)``.
+        Returns ``(codes as torch.float8_e4m3fn [R, C], scale_inv float32 [ceil(R / 128), ceil(C / 128)], Fp8Report)``.
+        A NaN or Inf in ``x`` raises ValueError naming ``name``."""
+        br, bc = self._fp8_block("fp8_quant", block)
+        if x.ndim != 2:
+            raise ValueError(f"fp8_quant: {name or 'tensor'} is {list(x.shape)}; a 2-D tensor expected")
+        if x.dtype not in _DTYPE_CODE:
+            raise ValueError(f"fp8_quant: {name or 'tensor'} is {x.dtype}; bf16, f16 or f32 expected")
+        xs = self._dev(x)
+        rows, cols = xs.shape
+        codes = torch.empty((rows, cols), dtype=torch.uint8, device=self.device)
+        sc = torch.empty((-(-rows // _lib.FP8_BLOCK), -(-cols // _lib.FP8_BLOCK)), dtype=torch.float32, device=self.device)
+        desc = _lib.Fp8QuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, br, bc)
+        rep = _lib.Fp8Report()
+        try:
+            self.ctx.check(self.lib.dll.smhip_fp8_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(),
+                                                        C.byref(rep), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"Non-finite value in {name or 'tensor'}: {e.message}") from e
+            if e.code == _lib.ERR_ARG:
+                raise ValueError(e.message) from e
+            raise
+        return codes.view(torch.float8_e4m3fn), sc, Fp8Report(rows=rows, cols=cols, blocks=int(rep.blocks),
+                                                              zero_blocks=int(rep.zero_blocks), amax=float(rep.amax),
+                                                              flags=int(rep.flags))
+
+    def fp8_dequant(self, codes: torch.Tensor, scale_inv: torch.Tensor, dtype: torch.dtype = torch.bfloat16, *,
+                    block=(_lib.FP8_BLOCK, _lib.FP8_BLOCK), name: str = "") -> torch.Tensor:
+        """the tensor a block-scaled FP8 tensor stands for: ``e4m3_to_f32(code) * s`` of the element's block, one fp32
+        product rounded once, then once into ``dtype`` (``smhip_fp8_dequant``).  codes: torch.float8_e4m3fn (or its
+        bytes as uint8) [R, C]; scale_inv: float32 [ceil(R / 128), ceil(C / 128)].  A NaN code raises ValueError naming
+        ``name``."""
+        br, bc = self._fp8_block("fp8_dequant", block)
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"fp8_dequant: dtype is {dtype}; bf16, f16 or f32 expected")
+        if codes.dtype not in (torch.float8_e4m3fn, torch.uint8) or codes.ndim != 2:
+            raise ValueError(f"fp8_dequant: codes of {name or 'tensor'} are {codes.dtype} {list(codes.shape)}; a 2-D float8_e4m3fn tensor expected")
+        rows, cols = codes.shape
+        want = (-(-rows // _lib.FP8_BLOCK), -(-cols // _lib.FP8_BLOCK))
+        if scale_inv.dtype != torch.float32 or tuple(scale_inv.shape) != want:
+            raise ValueError(f"fp8_dequant: scale_inv of {name or 'tensor'} is {scale_inv.dtype} {list(scale_inv.shape)}; "
+                             f"float32 {list(want)} expected for codes {list(codes.shape)}")
+        cs, sc = self._dev(codes.view(torch.uint8)), self._dev(scale_inv)
+        out = torch.empty((rows, cols), dtype=dtype, device=self.device)
+        desc = _lib.Fp8DequantDesc(cs.data_ptr(), sc.data_ptr(), rows, cols, br, bc, _DTYPE_CODE[dtype])
+        try:
+            self.ctx.check(self.lib.dll.smhip_fp8_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()))
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"NaN code in {name or 'tensor'}: {e.message}") from e
+            if e.code == _lib.ERR_ARG:
+                raise ValueError(e.message) from e
+            raise
+        return out
+
+    def fp8_fn(self, op: str, x: torch.Tensor, on_device: bool = True) -> torch.Tensor:
+        """the conversions of csrc/sm_fp8.hpp alone over a flat array (``smhip_fp8_fn``): "f32_to_e4m3" takes float32
+        and returns the codes as uint8, "e4m3_to_f32" takes uint8 codes and returns float32; by a kernel on the engine's
+        device, or on the host.  Returns a CPU tensor."""
+        if op not in self.FP8_FNS:
+            raise ValueError(f"fp8_fn: op {op!r} is not one of {sorted(self.FP8_FNS)}")
+        enc = op == "f32_to_e4m3"
+        x = x.detach().to(torch.float32 if enc else torch.uint8).contiguous().reshape(-1)
+        x = x.to(self.device) if on_device else x.cpu()
+        y = torch.empty(x.shape, dtype=torch.uint8 if enc else torch.float32, device=x.device)
+        self.ctx.check(self.lib.dll.smhip_fp8_fn(self.ctx.h, self.FP8_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
+                                                 1 if on_device else 0, self._stream() if on_device else None))
+        if on_device and self.device.type != "cpu":
+            torch.cuda.synchronize(self.device)
+        return y.cpu()
 
     # -- EMR-Merging: the unified model, a task's mask and rescaler, the task's tensor --------------
     def emr_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], base_out: torch.Tensor, *,

@@ -24,6 +24,7 @@ from safetensors import safe_open
 from .adapter import ADAPTER_BIN, AdapterError, LoraAdapter, is_adapter_dir, is_bin_only_adapter_dir
 from .deltapack import DeltaPack, is_pack_dir
 from .emrpack import EmrPack, is_emr_dir
+from .fp8model import Fp8Model, fp8_model
 
 logger = logging.getLogger(__name__)
 
@@ -70,6 +71,7 @@ class LocalModelIndex:
         self.adapters: Dict[str, LoraAdapter] = {}     # LoRA adapter directories (adapter.py), by model uri
         self.packs: Dict[str, DeltaPack] = {}          # delta pack directories (deltapack.py), by model uri
         self.emrs: Dict[str, EmrPack] = {}             # EMR pack directories (emrpack.py), by model uri
+        self.fp8s: Dict[str, Fp8Model] = {}            # block-scaled FP8 checkpoints (fp8model.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -111,6 +113,11 @@ class LocalModelIndex:
             index = json.load(fh)
         self.model_indexes[model_uri] = index
         self._ordered_weights[model_uri] = order_weights(list(index["weight_map"].keys()))
+        fp8 = fp8_model(model_uri, self.storage_path / model_uri, index["weight_map"])
+        if fp8 is not None:
+            # a block-scaled FP8 checkpoint: a full model whose E4M3 tensors come with a scale tensor each
+            self.fp8s[model_uri] = fp8
+            logger.info(f"Model {model_uri}: FP8 checkpoint, {len(fp8.scale_keys)} block-scaled E4M3 tensors")
         logger.info(f"Model {model_uri}: {len(set(index['weight_map'].values()))} shards, {len(index['weight_map'])} tensors")
 
     def adapter(self, model_uri: str) -> Optional[LoraAdapter]:
@@ -124,6 +131,10 @@ class LocalModelIndex:
     def emr(self, model_uri: str) -> Optional[EmrPack]:
         """the EMR pack registered under this uri, None for anything else"""
         return self.emrs.get(model_uri)
+
+    def fp8(self, model_uri: str) -> Optional[Fp8Model]:
+        """the block-scaled FP8 checkpoint registered under this uri, None for anything else"""
+        return self.fp8s.get(model_uri)
 
     def _require(self, model_uri: str, tensor_name: Optional[str] = None) -> Dict:
         if model_uri not in self.model_indexes:

@@ -48,7 +48,8 @@ class MergeTensorsBase(ABC):
         """the (uri, tensor) reads `finetune_tensor` makes for entry m: the model's tensor; for a LoRA adapter entry its
         base's tensor and, when the adapter targets it, the two factors; for a delta pack entry its base's tensor and
         the planes and scale, the tensor the pack stores whole, or the base's tensor alone; for an EMR pack entry its
-        base's and the unified model's tensor, the mask and the rescaler, the whole tensor, or the base's tensor alone"""
+        base's and the unified model's tensor, the mask and the rescaler, the whole tensor, or the base's tensor alone;
+        for an FP8 checkpoint entry the codes and their scale tensor, or the tensor it keeps in 16 bits"""
         pack = self.index_manager.pack(m.model)
         if pack is not None:
             t = pack.tensors.get(layer_name)
@@ -66,6 +67,9 @@ class MergeTensorsBase(ABC):
             if t.kind == "full":
                 return [(m.model, t.full_key)]
             return [(m.base, layer_name), (emr.unified, layer_name), (m.model, t.mask_key), (m.model, t.scale_key)]
+        fp8 = self.index_manager.fp8(m.model)
+        if fp8 is not None and layer_name in fp8.scale_keys:
+            return [(m.model, layer_name), (m.model, fp8.scale_keys[layer_name])]
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return [(m.model, layer_name)]
@@ -82,7 +86,9 @@ class MergeTensorsBase(ABC):
         row norm raises AdapterError), or the base tensor itself where the adapter does not target it.  For a delta
         pack entry (deltapack.py) `Engine.delta_apply` on the base tensor and the planes, the tensor the pack stores
         whole, or the base tensor itself where the pack holds nothing for it.  For an EMR pack entry (emrpack.py)
-        `Engine.emr_apply` on the base tensor, the unified model's tensor, the mask and the rescaler, likewise.
+        `Engine.emr_apply` on the base tensor, the unified model's tensor, the mask and the rescaler, likewise.  For a
+        block-scaled FP8 checkpoint entry (fp8model.py) `Engine.fp8_dequant` of the codes and their scales into the
+        dtype its base holds the tensor in; the tensors it keeps in 16 bits pass as they are.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
@@ -111,6 +117,12 @@ class MergeTensorsBase(ABC):
             mask = await fetch(m.model, t.mask_key)
             scale = await fetch(m.model, t.scale_key)
             return self.engine(device).emr_apply(base, unified, mask, scale)
+        fp8 = self.index_manager.fp8(m.model)
+        if fp8 is not None and layer_name in fp8.scale_keys:
+            codes = await fetch(m.model, layer_name)
+            scale = await fetch(m.model, fp8.scale_keys[layer_name])
+            return self.engine(device).fp8_dequant(codes, scale, self._fp8_out_dtype(m, layer_name),
+                                                   name=f"{m.model}: {layer_name}")
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return await fetch(m.model, layer_name)
@@ -130,6 +142,19 @@ class MergeTensorsBase(ABC):
                 raise
             from ..adapter import AdapterError
             raise AdapterError(f"LoRA adapter {m.model}: tensor {layer_name} (DoRA): {e.message}") from e
+
+    def _fp8_out_dtype(self, m: MergeModel, layer_name: str) -> torch.dtype:
+        """the dtype an FP8 entry's tensor is dequantised into: the one its base holds the tensor in (shard headers)"""
+        from ..adapter import base_tensor_meta
+        from ..stformat import ST_DTYPES
+        cache = self.__dict__.setdefault("_fp8_base_meta", {})
+        if m.base not in cache:
+            cache[m.base] = base_tensor_meta(self.index_manager, m.base)
+        dtype = ST_DTYPES.get(cache[m.base][layer_name][1])
+        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"{m.model}: tensor {layer_name} is FP8, but its base {m.base} holds it as "
+                             f"{cache[m.base][layer_name][1]} (BF16, F16 or F32 expected)")
+        return dtype
 
     async def _fetch(self, model_uri: str, layer_name: str, device: str) -> torch.Tensor:
         if self._loader is not None:
@@ -161,6 +186,11 @@ class MergeTensorsBase(ABC):
         for m in cfg.finetune_merge:
             await self.index_manager.add_model(m.base)
             await self.index_manager.add_model(m.model)
+        # an FP8 checkpoint is read as a finetune only: the merge walks the output base's tensor list and writes its dtypes
+        for role, uri in [("output_base_model", cfg.output_base_model)] + [(f"the base of {m.model}", m.base) for m in cfg.finetune_merge]:
+            if self.index_manager.fp8(uri) is not None:
+                raise ValueError(f"{uri} is a block-scaled FP8 checkpoint and cannot be {role}: write it out in 16 bits with "
+                                 f"`dequantize-fp8 {uri} --out DIR` first and name that directory")
         base_keys = self.index_manager.get_model_keys(cfg.output_base_model)
         for m in cfg.finetune_merge:
             adapter = self.index_manager.adapter(m.model)
@@ -191,6 +221,9 @@ class MergeTensorsBase(ABC):
                 emr.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
                 emr.check_against(emr.unified, base_tensor_meta(self.index_manager, emr.unified), what="unified model")
             keys = self.index_manager.get_model_keys(m.base if adapter is not None or pack is not None or emr is not None else m.model)
+            fp8 = self.index_manager.fp8(m.model)
+            if fp8 is not None:
+                keys = keys - fp8.scale_names                  # (the scale tensors belong to their weights)
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)

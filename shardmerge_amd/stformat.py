@@ -9,18 +9,19 @@ from typing import Dict, Sequence, Tuple
 
 import torch
 
-ST_DTYPES = {"BF16": torch.bfloat16, "F16": torch.float16, "F32": torch.float32, "F64": torch.float64}
-ST_NAMES = {torch.bfloat16: "BF16", torch.float16: "F16", torch.float32: "F32", torch.float64: "F64"}
-ST_SIZE = {"BF16": 2, "F16": 2, "F32": 4, "F64": 8}
+ST_DTYPES = {"BF16": torch.bfloat16, "F16": torch.float16, "F32": torch.float32, "F64": torch.float64,
+             "F8_E4M3": torch.float8_e4m3fn}
+ST_NAMES = {v: k for k, v in ST_DTYPES.items()}
+ST_SIZE = {"BF16": 2, "F16": 2, "F32": 4, "F64": 8, "F8_E4M3": 1}
 _ST_SIZE = ST_SIZE
 
 
 def shard_header(entries: Sequence[Tuple[str, str, Sequence[int]]], metadata: Dict[str, str]) -> Tuple[bytes, Dict[str, Tuple[int, int]]]:
     """The bytes in front of a safetensors payload (8-byte length + JSON padded to 8 bytes) for tensors
-    (name, dtype string, shape), laid out as safetensors' own writer does it (by dtype, widest first, then by
+    (name, dtype string, shape), laid out as safetensors' own writer does it (by dtype, widest first - the 8-bit floats after the 16-bit types - then by
     name - tests/test_host_logic.py pins the bytes against safetensors.torch.save_file), and the payload
     offsets (begin, end) per name."""
-    rank_of_dtype = {"F64": 0, "F32": 1, "BF16": 2, "F16": 2}
+    rank_of_dtype = {"F64": 0, "F32": 1, "BF16": 2, "F16": 2, "F8_E4M3": 3}
     order = sorted(entries, key=lambda e: (rank_of_dtype.get(e[1], 9), e[0]))
     doc: Dict[str, object] = {"__metadata__": dict(metadata)}
     offsets, pos = {}, 0
