@@ -1469,6 +1469,66 @@ typedef struct {
 int smhip_fp8_dequant(smhip_ctx* ctx, const smhip_fp8_dequant_desc* desc, void* out, void* stream);
 int smhip_fp8_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int on_device, void* stream);
 
+/* ---- MXFP4: a tensor as E2M1 codes, two to a byte, and one E8M0 power-of-two scale per block of 32 consecutive
+ *      elements of a row - the OCP micro-scaling form (X.weight as U8 [R][C / 2], X.weight_scale as U8 [R][C / 32]; AS
+ *      RECALLED, NOT CHECKED: PAPERS.md).  A DATA TYPE like block-scaled FP8 above: smhip_mx4_dequant rebuilds the
+ *      tensor that every operator then takes.  The reference has no such type; this section IS its definition.
+ *      THE ENCODINGS.  E2M1: one sign bit, two exponent bits of bias 1, one mantissa bit; the magnitudes are
+ *      {0, 0.5, 1, 1.5, 2, 3, 4, 6} (codes 0..7; 0.5 is the one subnormal); there is no NaN and no infinity.
+ *        e2m1_to_f32(code) is exact: the fp32 bits are built from the three fields (bits above the low four are ignored).
+ *        f32_to_e2m1(v) rounds |v| to the nearest magnitude, ties to the even mantissa (0.25 -> 0, 0.75 -> 1, 1.25 -> 1,
+ *        1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), and SATURATES: every |v| > 5, Inf and NaN included, gives 6.  The sign
+ *        bit of v becomes bit 3; -0 keeps it.  It is an integer function of the fp32 bits.
+ *      E8M0: eight bits, e8m0_to_f32(s) = 2^(s - 127); s == 0 is 2^-127, an fp32 denormal; s == 0xFF is NaN (0x7fc00000).
+ *        amax_to_e8m0(a) = max(E - 2, 0) with E the biased exponent field of |a| (0 for a zero or a denormal): the
+ *        scale 2^(floor(log2 |a|) - 2) wherever that is at least 2^-127, so that |a| / scale lies in [4, 8).
+ *      THE LAYOUT.  Only tensors with cols % 32 == 0 are converted; block b of row r holds its columns 32 b ...  Element
+ *      2 j of a row goes to the LOW nibble of code byte j and element 2 j + 1 to the HIGH nibble.
+ *      QUANT, smhip_mx4_quant, all integer arithmetic on the fp32 bit patterns, per block:
+ *        1. a = max |fp32(x)| over its 32 elements, after the exact promotion: exact and order-free.
+ *        2. s = amax_to_e8m0(a).  No special case: a block of zeros gets code 0 and nothing divides.
+ *        3. v = |fp32(x)| 2^(127 - s): a subtraction in the exponent field, exact (a v below 2^-126 counts as 0: it
+ *           rounds to 0 anyway) and |v| < 8.  code = sign | f32_to_e2m1(v).
+ *        4. The report, integers only: blocks; zero_blocks (a == 0); saturated, the elements whose v rounds ABOVE 6, that
+ *           is v >= 7 (they are stored as 6); nonfinite, the blocks that hold a NaN or an Inf.
+ *      A NaN or an Inf in the input fails the call with SMHIP_ERR_NONFINITE; the outputs are then unspecified.
+ *      The error, derived: the scale is at most a / 4 and the widest gap of the grid is 2, so |x - dq| <= a / 4 where
+ *      the element did not saturate and < a / 2 where it did.
+ *      DEQUANT, smhip_mx4_dequant: w = round_to(out_dtype, e2m1_to_f32(code) * e8m0_to_f32(s)) - ONE fp32
+ *      multiplication (exact short of overflow: two significant bits times a power of two, denormal results included;
+ *      6 * 2^127 and its like give Inf), then one round-to-nearest-even cast into bf16, fp16 or fp32.  A scale code
+ *      0xFF fails the call with SMHIP_ERR_NONFINITE.
+ *      PROBE, smhip_mx4_fn, the conversions alone over a flat array - SMHIP_MX4_F32_TO_E2M1 and SMHIP_MX4_AMAX_TO_E8M0:
+ *      x float [n] -> y uint8 [n]; SMHIP_MX4_E2M1_TO_F32 and SMHIP_MX4_E8M0_TO_F32: x uint8 [n] -> y float [n]; by a
+ *      kernel (on_device != 0, device arrays) or on the host.
+ *      rows cols == 0: nothing is written and the report is zero.  SMHIP_ERR_ARG: a block other than 32, cols % 32 != 0,
+ *      a bad dtype, a null or misaligned pointer, an output that overlaps an input or another output, a tensor too
+ *      large.  With x / out, codes and scales 16-byte aligned everything moves in 16-byte accesses; anything else goes
+ *      element by element and gives the same bytes.  Both synchronise the stream once, at their end (the counters /
+ *      the flag word are read back).  Profile names: "mx4_quant"; "mx4_dequant"; "mx4_fn". ---- */
+#define SMHIP_MX4_BLOCK 32
+enum { SMHIP_MX4_F32_TO_E2M1 = 0, SMHIP_MX4_E2M1_TO_F32 = 1, SMHIP_MX4_AMAX_TO_E8M0 = 2, SMHIP_MX4_E8M0_TO_F32 = 3 };
+typedef struct {
+    const void* x; int dtype;               /* device, [rows][cols], SMHIP_BF16 / F16 / F32 */
+    size_t rows, cols;                      /* cols % 32 == 0 */
+    int block;                              /* SMHIP_MX4_BLOCK */
+} smhip_mx4_quant_desc;
+typedef struct {
+    uint64_t blocks, zero_blocks, saturated, nonfinite;
+} smhip_mx4_report;
+/* codes: device uint8 [rows][cols / 2].  scales: device uint8 [rows][cols / 32].  report (optional): HOST. */
+int smhip_mx4_quant(smhip_ctx* ctx, const smhip_mx4_quant_desc* desc, uint8_t* codes, uint8_t* scales,
+                    smhip_mx4_report* report, void* stream);
+typedef struct {
+    const uint8_t* codes; const uint8_t* scales; /* device, as smhip_mx4_quant writes them */
+    size_t rows, cols;
+    int block;                              /* SMHIP_MX4_BLOCK */
+    int out_dtype;                          /* SMHIP_BF16 / F16 / F32 */
+} smhip_mx4_dequant_desc;
+/* out: device, out_dtype, [rows][cols]; it must not overlap an input */
+int smhip_mx4_dequant(smhip_ctx* ctx, const smhip_mx4_dequant_desc* desc, void* out, void* stream);
+int smhip_mx4_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int on_device, void* stream);
+
 /* ---- EMR-Merging (Huang et al., "EMR-Merging: Tuning-Free High-Performance Model Merging", NeurIPS 2024; as recalled:
  *      PAPERS.md): ONE unified task vector is ELECTED from the finetunes' deltas - per element the sign of their sum and
  *      the largest magnitude among the entries of that sign - and every task gets a 1-bit MASK (where its own delta

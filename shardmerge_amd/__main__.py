@@ -260,6 +260,56 @@ def dequantize_fp8_command(model: str, out_dir: Path, storage_dir: Path, dtype: 
     _fp8_command("dequantize-fp8", model, out_dir, storage_dir, None, dtype, device, verbose)
 
 
+def _mx4_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str, verbose: bool):
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.extract import parse_modules
+        from .merge.mx4 import format_table, run_mx4
+        result = asyncio.run(run_mx4(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device))
+    except Exception as exc:
+        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"model: {out_dir}")
+
+
+@cli.command("quantize-mxfp4")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the MXFP4 checkpoint is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--modules", type=str, default=None,
+              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
+                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def quantize_mxfp4_command(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool):
+    """MODEL as an MXFP4 checkpoint: E2M1 weights, two to a byte, with one E8M0 scale per 32 elements of a row.
+
+    DIR receives the shards (X.weight as U8 [R, C / 2], X.weight_scale as U8 [R, C / 32]), model.safetensors.index.json
+    and a config.json with the quantization_config block; it can be named as a finetune_merge entry of `merge` in place
+    of MODEL.  A weight whose row length is no multiple of 32 is copied as it is.
+    """
+    _mx4_command("quantize-mxfp4", model, out_dir, storage_dir, modules, "bf16", device, verbose)
+
+
+@cli.command("dequantize-mxfp4")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the MXFP4 tensors are written in")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def dequantize_mxfp4_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
+    """The MXFP4 checkpoint MODEL written out in 16 or 32 bits: code times its block's power-of-two scale.
+
+    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
+    """
+    _mx4_command("dequantize-mxfp4", model, out_dir, storage_dir, None, dtype, device, verbose)
+
+
 @cli.command("emr-task")
 @click.argument("model", type=str)
 @click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")

@@ -413,6 +413,26 @@ class Fp8DequantDesc(C.Structure):
                 ("block_rows", C.c_int), ("block_cols", C.c_int), ("out_dtype", C.c_int)]
 
 
+MX4_BLOCK = 32                                      # elements of a scale block of smhip_mx4_quant / smhip_mx4_dequant
+MX4_F32_TO_E2M1, MX4_E2M1_TO_F32, MX4_AMAX_TO_E8M0, MX4_E8M0_TO_F32 = 0, 1, 2, 3   # op of smhip_mx4_fn
+
+
+class Mx4QuantDesc(C.Structure):
+    """smhip_mx4_quant_desc"""
+    _fields_ = [("x", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t), ("block", C.c_int)]
+
+
+class Mx4Report(C.Structure):
+    """smhip_mx4_report"""
+    _fields_ = [("blocks", C.c_uint64), ("zero_blocks", C.c_uint64), ("saturated", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
+class Mx4DequantDesc(C.Structure):
+    """smhip_mx4_dequant_desc"""
+    _fields_ = [("codes", C.c_void_p), ("scales", C.c_void_p), ("rows", C.c_size_t), ("cols", C.c_size_t),
+                ("block", C.c_int), ("out_dtype", C.c_int)]
+
+
 DELLA_MAX_COLS = 32768        # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -510,6 +530,9 @@ class SmhipLibrary:
         d.smhip_fp8_quant.argtypes = [P, C.POINTER(Fp8QuantDesc), P, P, C.POINTER(Fp8Report), P]
         d.smhip_fp8_dequant.argtypes = [P, C.POINTER(Fp8DequantDesc), P, P]
         d.smhip_fp8_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
+        d.smhip_mx4_quant.argtypes = [P, C.POINTER(Mx4QuantDesc), P, P, C.POINTER(Mx4Report), P]
+        d.smhip_mx4_dequant.argtypes = [P, C.POINTER(Mx4DequantDesc), P, P]
+        d.smhip_mx4_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
         d.smhip_emr_merge.argtypes = [P, C.POINTER(EmrDesc), P, P, C.POINTER(EmrReport), P]
         d.smhip_emr_mask.argtypes = [P, C.POINTER(EmrMaskDesc), P, P, C.POINTER(EmrMaskReport), P]
         d.smhip_emr_apply.argtypes = [P, C.POINTER(EmrApplyDesc), P, P]

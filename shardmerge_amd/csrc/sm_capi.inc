@@ -750,6 +750,50 @@ int smhip_fp8_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int o
     SM_FINISH(ctx, ctx->pipe.delta.fp8_fn(op, x, y, n, on_device != 0));
 }
 
+// what smhip_mx4_quant and smhip_mx4_dequant share on top of dpack_check: whole blocks of 32 along a row
+static int mx4_check(smhip_ctx* ctx, const char* op, int dtype, size_t rows, size_t cols, int block,
+                     std::initializer_list<dpack_span> ins, std::initializer_list<dpack_span> outs) {
+    if (block != SMHIP_MX4_BLOCK)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": block size " + std::to_string(block) + " is not 32");
+    if (cols % SMHIP_MX4_BLOCK)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + std::to_string(cols) + " columns are no multiple of 32");
+    return dpack_check(ctx, op, dtype, rows, cols, SMHIP_DPACK_ROW, ins, outs);
+}
+
+int smhip_mx4_quant(smhip_ctx* ctx, const smhip_mx4_quant_desc* d, uint8_t* codes, uint8_t* scales,
+                    smhip_mx4_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "mx4_quant: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols;
+    if (int rc = mx4_check(ctx, "mx4_quant", d->dtype, d->rows, d->cols, d->block, {{d->x, n * es, es}},
+                           {{codes, n / 2, 1}, {scales, n / SMHIP_MX4_BLOCK, 1}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.mx4_quant(*d, codes, scales, report));
+}
+
+int smhip_mx4_dequant(smhip_ctx* ctx, const smhip_mx4_dequant_desc* d, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "mx4_dequant: null descriptor");
+    const size_t es = d->out_dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols;
+    if (int rc = mx4_check(ctx, "mx4_dequant", d->out_dtype, d->rows, d->cols, d->block,
+                           {{d->codes, n / 2, 1}, {d->scales, n / SMHIP_MX4_BLOCK, 1}}, {{out, n * es, es}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.mx4_dequant(*d, out));
+}
+
+int smhip_mx4_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int on_device, void* stream) {
+    SM_GUARD(ctx);
+    if (op < SMHIP_MX4_F32_TO_E2M1 || op > SMHIP_MX4_E8M0_TO_F32) return ctx->pipe.fail(SMHIP_ERR_ARG, "mx4_fn: bad op");
+    if (n > 0 && (!x || !y)) return ctx->pipe.fail(SMHIP_ERR_ARG, "mx4_fn: null array");
+    const bool from_float = op == SMHIP_MX4_F32_TO_E2M1 || op == SMHIP_MX4_AMAX_TO_E8M0;
+    if ((uintptr_t)(from_float ? x : y) % 4) return ctx->pipe.fail(SMHIP_ERR_ARG, "mx4_fn: the float array is not aligned to 4 bytes");
+    if (n > ((size_t)1 << 30)) return ctx->pipe.fail(SMHIP_ERR_ARG, "mx4_fn: array too large");
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.mx4_fn(op, x, y, n, on_device != 0));
+}
+
 int smhip_emr_merge(smhip_ctx* ctx, const smhip_emr_desc* d, void* out, float* delta_out, smhip_emr_report* report,
                     void* stream) {
     SM_GUARD(ctx);

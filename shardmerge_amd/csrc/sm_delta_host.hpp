@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack, block-scaled FP8 and EMR-Merging (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack, block-scaled FP8, MXFP4 and EMR-Merging (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -34,6 +34,7 @@
 #include "sm_emr_fused.hpp"
 #include "sm_eig.hpp"
 #include "sm_fp8.hpp"
+#include "sm_mx4.hpp"
 
 namespace smhip {
 
@@ -1794,6 +1795,62 @@ class DeltaHost {
             }
         } else if (n) {
             be.template launch<KFp8Fn>((int)((n + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
+        }
+        return SMHIP_OK;
+    }
+
+    // ---- MXFP4 (sm_mx4.hpp; smhip_mx4_quant, smhip_mx4_dequant, smhip_mx4_fn).  Quant: one kernel, a block per lane; the
+    // three counters are read back once.  Dequant: one kernel, the flag word read back.  Workspace: Mx4Head alone ----
+    struct Mx4Head { unsigned long long counts[MX4_COUNTERS]; uint32_t flags[2]; };
+    // the rounds per work-group and the grid of a kernel that takes 256 blocks per round
+    static int mx4_grid(size_t nblk, int& chunks) {
+        chunks = pick_chunks(nblk, MX4_THREADS, 1, 8);
+        return stream_grid(nblk, MX4_THREADS, chunks);
+    }
+    int mx4_quant(const smhip_mx4_quant_desc& d, uint8_t* codes, uint8_t* scales, smhip_mx4_report* rep) {
+        const size_t nblk = d.rows * d.cols / MX4_BLOCK;
+        if (rep) *rep = smhip_mx4_report{};
+        if (nblk == 0) return SMHIP_OK;
+        Mx4Head* w;
+        if (int rc = plain_workspace(w)) return rc;
+        Mx4QuantParams p;
+        p.x = d.x; p.dtype = d.dtype; p.nblk = nblk; p.codes = codes; p.scale = scales; p.counts = w->counts;
+        p.vec = (aligned16(d.x) && aligned16(codes) && aligned16(scales)) ? 1 : 0;
+        const int grid = mx4_grid(nblk, p.chunks);
+        be.template launch<KMx4Quant>(grid, MX4_THREADS, (LDS_SCRATCH_FLOATS + MX4_LDS_FLOATS) * 4, p, stream);
+        Mx4Head host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
+        if (rep) {
+            rep->blocks = nblk; rep->zero_blocks = host.counts[MX4_ZERO_BLOCKS];
+            rep->saturated = host.counts[MX4_SATURATED]; rep->nonfinite = host.counts[MX4_NONFINITE];
+        }
+        if (host.counts[MX4_NONFINITE]) return fail(SMHIP_ERR_NONFINITE, "mx4_quant: NaN or Inf in the tensor");
+        return SMHIP_OK;
+    }
+    int mx4_dequant(const smhip_mx4_dequant_desc& d, void* out) {
+        const size_t nblk = d.rows * d.cols / MX4_BLOCK;
+        if (nblk == 0) return SMHIP_OK;
+        Mx4Head* w;
+        if (int rc = plain_workspace(w)) return rc;
+        Mx4DequantParams p;
+        p.codes = d.codes; p.scale = d.scales; p.nblk = nblk; p.out = out; p.out_dtype = d.out_dtype; p.flags = w->flags;
+        p.vec = (aligned16(d.codes) && aligned16(d.scales) && aligned16(out)) ? 1 : 0;
+        const int grid = mx4_grid(nblk, p.chunks);
+        be.template launch<KMx4Dequant>(grid, MX4_THREADS, (LDS_SCRATCH_FLOATS + MX4_LDS_FLOATS) * 4, p, stream);
+        Mx4Head host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0] & MX4_FLAG_NAN_SCALE) return fail(SMHIP_ERR_NONFINITE, "mx4_dequant: a NaN scale code (0xFF) in the tensor");
+        return SMHIP_OK;
+    }
+    int mx4_fn(int op, const void* x, void* y, size_t n, bool on_device) {
+        Mx4FnParams p;
+        p.op = op; p.n = n; p.x = x; p.y = y;
+        if (!on_device) {
+            for (size_t i = 0; i < n; ++i) mx4_fn_elem(p, i);
+        } else if (n) {
+            be.template launch<KMx4Fn>((int)((n + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         }
         return SMHIP_OK;
     }

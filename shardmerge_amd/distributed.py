@@ -200,6 +200,11 @@ def config_stamp(config: MergeConfig) -> str:
             if (ident := fp8_identity(Path(config.storage_path) / m.model)) is not None}   # an FP8 checkpoint's: its shard headers
     if fp8s:
         doc["fp8_models"] = fp8s
+    from .mx4model import mx4_identity
+    mx4s = {m.model: ident for m in config.finetune_merge
+            if (ident := mx4_identity(Path(config.storage_path) / m.model)) is not None}   # an MXFP4 checkpoint's: its shard headers
+    if mx4s:
+        doc["mx4_models"] = mx4s
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 

@@ -284,6 +284,16 @@ class Fp8Report:
     flags: int = 0                                                   # bit 0: a NaN or an Inf was met
 
 
+@dataclass
+class Mx4Report:
+    rows: int = 0
+    cols: int = 0
+    blocks: int = 0                                                  # scale blocks of 32 elements
+    zero_blocks: int = 0                                             # blocks of zeros: scale code 0, zero codes
+    saturated: int = 0                                               # elements whose scaled magnitude rounds above 6 (stored as 6)
+    nonfinite: int = 0                                               # blocks that hold a NaN or an Inf
+
+
 def _shape_rows(t: torch.Tensor) -> Tuple[int, int]:
     """the delta pack's view of a tensor: R = shape[0] rows of the rest; a 0-D or 1-D tensor is one row"""
     if t.ndim <= 1:
@@ -744,6 +754,88 @@ class Engine:
         x = x.to(self.device) if on_device else x.cpu()
         y = torch.empty(x.shape, dtype=torch.uint8 if enc else torch.float32, device=x.device)
         self.ctx.check(self.lib.dll.smhip_fp8_fn(self.ctx.h, self.FP8_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
+                                                 1 if on_device else 0, self._stream() if on_device else None))
+        if on_device and self.device.type != "cpu":
+            torch.cuda.synchronize(self.device)
+        return y.cpu()
+
+    # -- MXFP4 (E2M1 codes, two to a byte, one E8M0 scale per 32 elements of a row) ---------------------
+    MX4_FNS = {"f32_to_e2m1": _lib.MX4_F32_TO_E2M1, "e2m1_to_f32": _lib.MX4_E2M1_TO_F32,
+               "amax_to_e8m0": _lib.MX4_AMAX_TO_E8M0, "e8m0_to_f32": _lib.MX4_E8M0_TO_F32}
+
+    def _mx4_check(self, rc: int, what: str, layer_name: str):
+        try:
+            self.ctx.check(rc)
+        except SmhipError as e:
+            if e.code == _lib.ERR_NONFINITE:
+                raise ValueError(f"{what} in {layer_name or 'tensor'}: {e.message}") from e
+            if e.code == _lib.ERR_ARG:
+                raise ValueError(f"{layer_name or 'tensor'}: {e.message}") from e
+            raise
+
+    def mx4_quant(self, x: torch.Tensor, *, layer_name: str = ""):
+        """A 2-D tensor with ``C % 32 == 0`` as MXFP4 (``smhip_mx4_quant``; the function is stated in
+        include/shardmerge_hip.h): per block of 32 elements of a row the E8M0 scale ``2^(floor(log2 amax) - 2)`` and
+        the E2M1 codes of ``x / scale``, element ``2 j`` in the low nibble of byte ``j``.  Returns ``(codes uint8
+        [R, C / 2], scales uint8 [R, C / 32], Mx4Report)``.  A NaN or Inf in ``x`` raises ValueError naming
+        ``layer_name``."""
+        who = layer_name or "tensor"
+        if x.ndim != 2:
+            raise ValueError(f"mx4_quant: {who} is {list(x.shape)}; a 2-D tensor expected")
+        if x.dtype not in _DTYPE_CODE:
+            raise ValueError(f"mx4_quant: {who} is {x.dtype}; bf16, f16 or f32 expected")
+        rows, cols = x.shape
+        if cols % _lib.MX4_BLOCK:
+            raise ValueError(f"mx4_quant: {who} is {list(x.shape)}; its {cols} columns are no multiple of {_lib.MX4_BLOCK}")
+        xs = self._dev(x)
+        codes = torch.empty((rows, cols // 2), dtype=torch.uint8, device=self.device)
+        sc = torch.empty((rows, cols // _lib.MX4_BLOCK), dtype=torch.uint8, device=self.device)
+        desc = _lib.Mx4QuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, _lib.MX4_BLOCK)
+        rep = _lib.Mx4Report()
+        self._mx4_check(self.lib.dll.smhip_mx4_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(), C.byref(rep),
+                                                     self._stream()), "Non-finite value", layer_name)
+        return codes, sc, Mx4Report(rows=rows, cols=cols, blocks=int(rep.blocks), zero_blocks=int(rep.zero_blocks),
+                                    saturated=int(rep.saturated), nonfinite=int(rep.nonfinite))
+
+    def mx4_dequant(self, codes: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = torch.bfloat16, *,
+                    out: Optional[torch.Tensor] = None, layer_name: str = "") -> torch.Tensor:
+        """the tensor an MXFP4 tensor stands for: ``e2m1_to_f32(code) * 2^(scale - 127)``, one fp32 product, then one
+        rounding into ``dtype`` (``smhip_mx4_dequant``).  codes: uint8 [R, C / 2]; scales: uint8 [R, C / 32]; out
+        (optional): a contiguous ``dtype`` [R, C] tensor on the engine's device that overlaps neither.  A scale code
+        0xFF raises ValueError naming ``layer_name``."""
+        who = layer_name or "tensor"
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"mx4_dequant: dtype of {who} is {dtype}; bf16, f16 or f32 expected")
+        if codes.dtype != torch.uint8 or codes.ndim != 2 or (2 * codes.shape[1]) % _lib.MX4_BLOCK:
+            raise ValueError(f"mx4_dequant: codes of {who} are {codes.dtype} {list(codes.shape)}; uint8 [R, C / 2] with "
+                             f"C a multiple of {_lib.MX4_BLOCK} expected")
+        rows, cols = codes.shape[0], 2 * codes.shape[1]
+        want = (rows, cols // _lib.MX4_BLOCK)
+        if scales.dtype != torch.uint8 or tuple(scales.shape) != want:
+            raise ValueError(f"mx4_dequant: scales of {who} are {scales.dtype} {list(scales.shape)}; "
+                             f"uint8 {list(want)} expected for codes {list(codes.shape)}")
+        cs, sc = self._dev(codes), self._dev(scales)
+        if out is None:
+            out = torch.empty((rows, cols), dtype=dtype, device=self.device)
+        elif out.dtype != dtype or tuple(out.shape) != (rows, cols) or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"mx4_dequant: out of {who} is {out.dtype} {list(out.shape)} on {out.device}; a contiguous "
+                             f"{dtype} {[rows, cols]} tensor on {self.device} expected")
+        desc = _lib.Mx4DequantDesc(cs.data_ptr(), sc.data_ptr(), rows, cols, _lib.MX4_BLOCK, _DTYPE_CODE[dtype])
+        self._mx4_check(self.lib.dll.smhip_mx4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
+                        "NaN scale code", layer_name)
+        return out
+
+    def mx4_fn(self, op: str, x: torch.Tensor, on_device: bool = True) -> torch.Tensor:
+        """the conversions of csrc/sm_mx4.hpp alone over a flat array (``smhip_mx4_fn``): "f32_to_e2m1" and
+        "amax_to_e8m0" take float32 and return codes as uint8, "e2m1_to_f32" and "e8m0_to_f32" take uint8 codes and
+        return float32; by a kernel on the engine's device, or on the host.  Returns a CPU tensor."""
+        if op not in self.MX4_FNS:
+            raise ValueError(f"mx4_fn: op {op!r} is not one of {sorted(self.MX4_FNS)}")
+        enc = op in ("f32_to_e2m1", "amax_to_e8m0")
+        x = x.detach().to(torch.float32 if enc else torch.uint8).contiguous().reshape(-1)
+        x = x.to(self.device) if on_device else x.cpu()
+        y = torch.empty(x.shape, dtype=torch.uint8 if enc else torch.float32, device=x.device)
+        self.ctx.check(self.lib.dll.smhip_mx4_fn(self.ctx.h, self.MX4_FNS[op], x.data_ptr(), y.data_ptr(), x.numel(),
                                                  1 if on_device else 0, self._stream() if on_device else None))
         if on_device and self.device.type != "cpu":
             torch.cuda.synchronize(self.device)

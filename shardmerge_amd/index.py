@@ -25,6 +25,7 @@ from .adapter import ADAPTER_BIN, AdapterError, LoraAdapter, is_adapter_dir, is_
 from .deltapack import DeltaPack, is_pack_dir
 from .emrpack import EmrPack, is_emr_dir
 from .fp8model import Fp8Model, fp8_model
+from .mx4model import Mx4Model, mx4_model
 
 logger = logging.getLogger(__name__)
 
@@ -72,6 +73,7 @@ class LocalModelIndex:
         self.packs: Dict[str, DeltaPack] = {}          # delta pack directories (deltapack.py), by model uri
         self.emrs: Dict[str, EmrPack] = {}             # EMR pack directories (emrpack.py), by model uri
         self.fp8s: Dict[str, Fp8Model] = {}            # block-scaled FP8 checkpoints (fp8model.py), by model uri
+        self.mx4s: Dict[str, Mx4Model] = {}            # MXFP4 checkpoints (mx4model.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -118,6 +120,11 @@ class LocalModelIndex:
             # a block-scaled FP8 checkpoint: a full model whose E4M3 tensors come with a scale tensor each
             self.fp8s[model_uri] = fp8
             logger.info(f"Model {model_uri}: FP8 checkpoint, {len(fp8.scale_keys)} block-scaled E4M3 tensors")
+        mx4 = mx4_model(model_uri, self.storage_path / model_uri, index["weight_map"])
+        if mx4 is not None:
+            # an MXFP4 checkpoint: config.json says so and its coded weights come with a scale tensor each
+            self.mx4s[model_uri] = mx4
+            logger.info(f"Model {model_uri}: MXFP4 checkpoint, {len(mx4.scale_keys)} micro-scaled E2M1 tensors")
         logger.info(f"Model {model_uri}: {len(set(index['weight_map'].values()))} shards, {len(index['weight_map'])} tensors")
 
     def adapter(self, model_uri: str) -> Optional[LoraAdapter]:
@@ -135,6 +142,10 @@ class LocalModelIndex:
     def fp8(self, model_uri: str) -> Optional[Fp8Model]:
         """the block-scaled FP8 checkpoint registered under this uri, None for anything else"""
         return self.fp8s.get(model_uri)
+
+    def mx4(self, model_uri: str) -> Optional[Mx4Model]:
+        """the MXFP4 checkpoint registered under this uri, None for anything else"""
+        return self.mx4s.get(model_uri)
 
     def _require(self, model_uri: str, tensor_name: Optional[str] = None) -> Dict:
         if model_uri not in self.model_indexes:

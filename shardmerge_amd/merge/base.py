@@ -49,7 +49,7 @@ class MergeTensorsBase(ABC):
         base's tensor and, when the adapter targets it, the two factors; for a delta pack entry its base's tensor and
         the planes and scale, the tensor the pack stores whole, or the base's tensor alone; for an EMR pack entry its
         base's and the unified model's tensor, the mask and the rescaler, the whole tensor, or the base's tensor alone;
-        for an FP8 checkpoint entry the codes and their scale tensor, or the tensor it keeps in 16 bits"""
+        for an FP8 or an MXFP4 checkpoint entry the codes and their scale tensor, or the tensor it keeps in 16 bits"""
         pack = self.index_manager.pack(m.model)
         if pack is not None:
             t = pack.tensors.get(layer_name)
@@ -70,6 +70,9 @@ class MergeTensorsBase(ABC):
         fp8 = self.index_manager.fp8(m.model)
         if fp8 is not None and layer_name in fp8.scale_keys:
             return [(m.model, layer_name), (m.model, fp8.scale_keys[layer_name])]
+        mx4 = self.index_manager.mx4(m.model)
+        if mx4 is not None and layer_name in mx4.scale_keys:
+            return [(m.model, layer_name), (m.model, mx4.scale_keys[layer_name])]
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return [(m.model, layer_name)]
@@ -88,7 +91,8 @@ class MergeTensorsBase(ABC):
         whole, or the base tensor itself where the pack holds nothing for it.  For an EMR pack entry (emrpack.py)
         `Engine.emr_apply` on the base tensor, the unified model's tensor, the mask and the rescaler, likewise.  For a
         block-scaled FP8 checkpoint entry (fp8model.py) `Engine.fp8_dequant` of the codes and their scales into the
-        dtype its base holds the tensor in; the tensors it keeps in 16 bits pass as they are.
+        dtype its base holds the tensor in; the tensors it keeps in 16 bits pass as they are.  For an MXFP4
+        checkpoint entry (mx4model.py) `Engine.mx4_dequant` of the codes and their scales, likewise.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
@@ -123,6 +127,12 @@ class MergeTensorsBase(ABC):
             scale = await fetch(m.model, fp8.scale_keys[layer_name])
             return self.engine(device).fp8_dequant(codes, scale, self._fp8_out_dtype(m, layer_name),
                                                    name=f"{m.model}: {layer_name}")
+        mx4 = self.index_manager.mx4(m.model)
+        if mx4 is not None and layer_name in mx4.scale_keys:
+            codes = await fetch(m.model, layer_name)
+            scale = await fetch(m.model, mx4.scale_keys[layer_name])
+            return self.engine(device).mx4_dequant(codes, scale, self._fp8_out_dtype(m, layer_name, "MXFP4"),
+                                                   layer_name=f"{m.model}: {layer_name}")
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return await fetch(m.model, layer_name)
@@ -143,8 +153,8 @@ class MergeTensorsBase(ABC):
             from ..adapter import AdapterError
             raise AdapterError(f"LoRA adapter {m.model}: tensor {layer_name} (DoRA): {e.message}") from e
 
-    def _fp8_out_dtype(self, m: MergeModel, layer_name: str) -> torch.dtype:
-        """the dtype an FP8 entry's tensor is dequantised into: the one its base holds the tensor in (shard headers)"""
+    def _fp8_out_dtype(self, m: MergeModel, layer_name: str, what: str = "FP8") -> torch.dtype:
+        """the dtype an FP8 or MXFP4 entry's tensor is dequantised into: the one its base holds the tensor in (shard headers)"""
         from ..adapter import base_tensor_meta
         from ..stformat import ST_DTYPES
         cache = self.__dict__.setdefault("_fp8_base_meta", {})
@@ -152,7 +162,7 @@ class MergeTensorsBase(ABC):
             cache[m.base] = base_tensor_meta(self.index_manager, m.base)
         dtype = ST_DTYPES.get(cache[m.base][layer_name][1])
         if dtype not in (torch.bfloat16, torch.float16, torch.float32):
-            raise ValueError(f"{m.model}: tensor {layer_name} is FP8, but its base {m.base} holds it as "
+            raise ValueError(f"{m.model}: tensor {layer_name} is {what}, but its base {m.base} holds it as "
                              f"{cache[m.base][layer_name][1]} (BF16, F16 or F32 expected)")
         return dtype
 
@@ -191,6 +201,9 @@ class MergeTensorsBase(ABC):
             if self.index_manager.fp8(uri) is not None:
                 raise ValueError(f"{uri} is a block-scaled FP8 checkpoint and cannot be {role}: write it out in 16 bits with "
                                  f"`dequantize-fp8 {uri} --out DIR` first and name that directory")
+            if self.index_manager.mx4(uri) is not None:
+                raise ValueError(f"{uri} is an MXFP4 checkpoint and cannot be {role}: write it out in 16 bits with "
+                                 f"`dequantize-mxfp4 {uri} --out DIR` first and name that directory")
         base_keys = self.index_manager.get_model_keys(cfg.output_base_model)
         for m in cfg.finetune_merge:
             adapter = self.index_manager.adapter(m.model)
@@ -224,6 +237,9 @@ class MergeTensorsBase(ABC):
             fp8 = self.index_manager.fp8(m.model)
             if fp8 is not None:
                 keys = keys - fp8.scale_names                  # (the scale tensors belong to their weights)
+            mx4 = self.index_manager.mx4(m.model)
+            if mx4 is not None:
+                keys = keys - mx4.scale_names
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)

@@ -31,6 +31,8 @@ _QUANTISABLE = ("BF16", "F16", "F32")
 
 
 class Fp8Conversion:
+    QUANTISE = "quantize-fp8"                           # the command that writes quantization_config (merge/mx4.py: its own)
+    quantization_config = staticmethod(quantization_config)
     def __init__(self, command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[Sequence[str]] = None,
                  dtype: str = "bf16", index_manager=None, engine=None):
         self.command, self.model, self.out_dir, self.storage_dir = command, model, Path(out_dir), Path(storage_dir)
@@ -121,8 +123,8 @@ class Fp8Conversion:
             total += sum(t.numel() * t.element_size() for t in tensors.values())
         (self.out_dir / FULL_INDEX).write_text(json.dumps({"metadata": {"total_size": total}, "weight_map": dict(sorted(weight_map.items()))}, indent=2))
         config = json.loads((src / "config.json").read_bytes()) if (src / "config.json").exists() else {}
-        if self.command == "quantize-fp8":
-            config["quantization_config"] = quantization_config(untouched)
+        if self.command == self.QUANTISE:
+            config["quantization_config"] = self.quantization_config(untouched)
         else:
             config.pop("quantization_config", None)
             config["torch_dtype"] = str(DTYPES[self.dtype]).replace("torch.", "")
