@@ -1690,6 +1690,10 @@ int smhip_reference_cpu_norm(smhip_ctx* ctx, const void* x, const void* base, in
  *      keeping it in the spectral domain (default 1);
  *      "della_slab_rows" = r makes smhip_della_merge rank and merge r rows at a time (0, the default: as many whole
  *      rows as hold at most 2^26 elements per finetune); the result does not depend on it;
+ *      "stream_chunks" = c makes every streaming kernel of the delta operators, the delta pack, FP8, MXFP4 and EMR
+ *      (the kernels whose work-groups loop over rounds of 256 units) run c rounds per work-group, c at most 4096,
+ *      whatever the tensor's size and the kernel's usual minimum (0, the default: chosen from the size); no result
+ *      depends on it.  The spectral pipeline's kernels are not touched ("sel_chunks" is theirs);
  *      "emr_fused_geo_fold" = 1 makes smhip_emr_merge_masks fold its rows' partials with "geo_gram_fold" instead of
  *      "emr_fold" (default 0; the same bits, for A/B timing). ------- */
 int smhip_debug_option(smhip_ctx* ctx, const char* key, long value);
@@ -1699,7 +1703,9 @@ int smhip_debug_option(smhip_ctx* ctx, const char* key, long value);
  * crossed with the group summaries / walked cooperatively
  * ("aten_serial" = 1 as an option selects the old serial single-work-group chain instead);
  * "eig_host_us": microseconds this context has spent on the host in the Jacobi eigensolver of smhip_lora_extract and
- * smhip_tsv_merge since it was created */
+ * smhip_tsv_merge since it was created;
+ * "stream_chunks_applied": how many round counts the option "stream_chunks" has supplied since it was last set - one per
+ * streaming pass of a call (the launches of one pass, such as a select's histogram levels, share theirs) */
 int smhip_debug_query(smhip_ctx* ctx, const char* key, long* value);
 
 /* ---- profiling: per-kernel device time measured with HIP events on the

@@ -995,6 +995,11 @@ int smhip_debug_option(smhip_ctx* ctx, const char* key, long value) {
     if (key && std::string(key) == "force_split") { ctx->pipe.debug_force_split = value > 1 && value <= smhip::DFTP_MAX_P ? (int)value : 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_columns") { ctx->pipe.fold_enabled = value != 0; return SMHIP_OK; }
     if (key && std::string(key) == "della_slab_rows") { ctx->pipe.delta.della_slab_rows = value > 0 ? (size_t)value : 0; return SMHIP_OK; }
+    if (key && std::string(key) == "stream_chunks") {
+        ctx->pipe.delta.debug_stream_chunks = value > 0 ? (int)std::min(value, 4096l) : 0;
+        ctx->pipe.delta.stream_chunks_applied = 0;
+        return SMHIP_OK;
+    }
     if (key && std::string(key) == "emr_fused_geo_fold") { ctx->pipe.delta.emr_fused_geo_fold = value != 0; return SMHIP_OK; }
     if (key && std::string(key) == "fold_min_rows") { ctx->pipe.fold_min_rows = value > 0 ? (int)value : SM_FOLD_MIN_ROWS; return SMHIP_OK; }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug option");
@@ -1017,6 +1022,7 @@ int smhip_debug_query(smhip_ctx* ctx, const char* key, long* value) {
         SM_FINISH(ctx, SMHIP_OK);
     }
     if (std::string(key) == "eig_host_us") { *value = (long)ctx->pipe.delta.eig_host_us; SM_FINISH(ctx, SMHIP_OK); }
+    if (std::string(key) == "stream_chunks_applied") { *value = (long)ctx->pipe.delta.stream_chunks_applied; SM_FINISH(ctx, SMHIP_OK); }
     if (std::string(key) == "eig_dev_us") { *value = (long)ctx->pipe.delta.eig_dev_us; SM_FINISH(ctx, SMHIP_OK); }
     return ctx->pipe.fail(SMHIP_ERR_ARG, "unknown debug query");
 }

@@ -78,6 +78,8 @@ class DeltaHost {
     std::string& err;
     void*& stream;
     size_t della_slab_rows = 0;               // test hook "della_slab_rows": rows per slab (0: at most 2^26 elements per finetune)
+    int debug_stream_chunks = 0;              // test hook "stream_chunks": the rounds of every streaming kernel below (0: pick_chunks)
+    unsigned long long stream_chunks_applied = 0;   // debug query "stream_chunks_applied": round counts the hook has supplied since it was set
     unsigned long long eig_host_us = 0;       // debug query "eig_host_us": host time in xl_sym_eig since the context was created
     unsigned long long eig_dev_us = 0;        // debug query "eig_dev_us": wall time of the device solves (launch, read-back, sort)
     int eig_device = 0;                       // the eigensolver of the running tsv_merge / lora_extract call (SMHIP_EIG_*)
@@ -88,6 +90,14 @@ class DeltaHost {
 
     int fail(int code, const std::string& msg) { err = msg; return code; }
     size_t workspace_bytes() const { return ws_.cap; }
+
+    // the rounds per work-group of a streaming kernel launched here: pick_chunks, or the test hook's count as it is - at
+    // most pick_chunks' own cap, min_chunks not applied: every kernel's loop is correct from one round up
+    int stream_chunks(size_t units, int block, int min_chunks, int wgs_per_cu) {
+        if (debug_stream_chunks <= 0) return pick_chunks(units, block, min_chunks, wgs_per_cu);
+        ++stream_chunks_applied;
+        return std::min(debug_stream_chunks, 4096);
+    }
 
     // ---- the shared passes.  The descriptors share their leading fields and the *MergeParams their common ones, so what the
     // host paths share is written once, as templates. ----
@@ -114,7 +124,7 @@ class DeltaHost {
         m.base_out = d.base_out; m.base_out_dtype = d.base_out_dtype;
         m.out_is_base0 = (!weight_space && m.in.shared_base && d.base_out == m.in.base[0] && d.base_out_dtype == d.in_dtype) ? 1 : 0;
         m.out = out; m.delta_out = delta_out;
-        m.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+        m.chunks = stream_chunks((d.n + 7) / 8, 256, 2, 8);
     }
     // ... and what the descriptors of the election operators add: the weights, lambda, normalize
     template <class Desc, class MergeParams>
@@ -173,9 +183,9 @@ class DeltaHost {
     }
     // the grid of a *_hist launch over the octets of h.in, h.chunks per thread
     template <class HistParams>
-    static int hist_grid(HistParams& h) {
+    int hist_grid(HistParams& h) {
         const size_t noct = (h.in.n + 7) / 8;
-        h.chunks = pick_chunks(noct, 256, 4, 5);
+        h.chunks = stream_chunks(noct, 256, 4, 5);
         return stream_grid(noct, 256, h.chunks);
     }
     // ... with a select work-group per finetune: hist launches in groups of TIES_GROUP finetunes.  The caller has filled h
@@ -684,7 +694,7 @@ class DeltaHost {
             be.template launch<KDellaRank>((int)(rows * k), rank_threads, (LDS_SCRATCH_FLOATS + (size_t)r.P) * 4, r, stream);
             m.slab = s;
             const size_t noct = ((s.e0 + s.len + 7) >> 3) - (s.e0 >> 3);
-            m.chunks = pick_chunks(noct, 256, 2, 8);
+            m.chunks = stream_chunks(noct, 256, 2, 8);
             be.template launch<KDellaMerge>(stream_grid(noct, 256, m.chunks), 256, (LDS_SCRATCH_FLOATS + dare_lds_words(k, 256)) * 4, m, stream);
         }
         return dare_readback("della_merge", k, rb, kept);
@@ -1012,7 +1022,7 @@ class DeltaHost {
         // every row octet of every team, the idle ones of the tail groups included: at most n / 8 + R * M / 8
         if (R > ((size_t)1 << 56) / (m.G * (size_t)m.L)) return fail(SMHIP_ERR_ARG, "cabs_merge: tensor too large");
         m.units = R * m.G * (size_t)m.L;
-        m.chunks = pick_chunks(m.units, CABS_THREADS, 2, 8);
+        m.chunks = stream_chunks(m.units, CABS_THREADS, 2, 8);
         if ((m.units + CABS_THREADS - 1) / CABS_THREADS / (size_t)m.chunks > (size_t)0x7fffffff) return fail(SMHIP_ERR_ARG, "cabs_merge: tensor too large");
         CabsReadback* rb;
         int rc;
@@ -1583,7 +1593,7 @@ class DeltaHost {
         ties_inputs(sp.in, d.k, d.in_dtype, d.n, d.finetune, d.base, true);
         for (int i = 0; i < TIES_MAX_MODELS; ++i) sp.alpha[i] = (float)d.alpha[i < d.k ? i : 0];
         sp.flags = flags;
-        sp.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+        sp.chunks = stream_chunks((d.n + 7) / 8, 256, 2, 8);
         be.template launch<KIsoSum>(stream_grid((d.n + 7) / 8, 256, sp.chunks), 256, 0, sp, stream);
         if (tr) iso_transpose(Xn, T, rows, cols);
         // 3: the scale
@@ -1602,7 +1612,7 @@ class DeltaHost {
             a.q = q; a.sigma = sigma; a.lambda = (float)d.lambda; a.base_out = d.base_out; a.dtype = d.base_out_dtype;
             a.out = out; a.delta_out = delta_out; a.n = d.n;
             a.aligned = (aligned16(d.base_out) && aligned16(out) && aligned16(delta_out)) ? 1 : 0;
-            a.chunks = pick_chunks((d.n + 7) / 8, 256, 2, 8);
+            a.chunks = stream_chunks((d.n + 7) / 8, 256, 2, 8);
             be.template launch<KIsoApply>(stream_grid((d.n + 7) / 8, 256, a.chunks), 256, 0, a, stream);
         };
         if (nu == 0.0) {
@@ -1731,7 +1741,7 @@ class DeltaHost {
         p.base = d.base; p.dtype = d.dtype; p.R = R; p.C = C; p.PB = PB; p.units = R * PB;
         p.sign = d.sign; p.mask = d.mask; p.scale = d.scale; p.scale_mode = d.scale_mode == SMHIP_DPACK_TENSOR ? DPACK_TENSOR : DPACK_ROW;
         p.out = out; p.row_vec = dpack_row_vec(C, d.base, out);
-        p.chunks = pick_chunks(p.units, 256, 2, 8);
+        p.chunks = stream_chunks(p.units, 256, 2, 8);
         be.template launch<KDpackApply>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         return SMHIP_OK;
     }
@@ -1776,7 +1786,7 @@ class DeltaHost {
         p.codes = d.codes; p.scale = d.scale_inv; p.R = R; p.C = C; p.PB = (C + 7) / 8; p.BC = (C + FP8_BLOCK - 1) / FP8_BLOCK;
         p.units = R * p.PB; p.out = out; p.out_dtype = d.out_dtype;
         p.row_vec = (C % 8 == 0 && ((uintptr_t)d.codes & 7) == 0 && aligned16(out)) ? 1 : 0;
-        p.chunks = pick_chunks(p.units, 256, 2, 8);
+        p.chunks = stream_chunks(p.units, 256, 2, 8);
         p.flags = w->flags;
         be.template launch<KFp8Dequant>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         Fp8Head host;
@@ -1803,8 +1813,8 @@ class DeltaHost {
     // three counters are read back once.  Dequant: one kernel, the flag word read back.  Workspace: Mx4Head alone ----
     struct Mx4Head { unsigned long long counts[MX4_COUNTERS]; uint32_t flags[2]; };
     // the rounds per work-group and the grid of a kernel that takes 256 blocks per round
-    static int mx4_grid(size_t nblk, int& chunks) {
-        chunks = pick_chunks(nblk, MX4_THREADS, 1, 8);
+    int mx4_grid(size_t nblk, int& chunks) {
+        chunks = stream_chunks(nblk, MX4_THREADS, 1, 8);
         return stream_grid(nblk, MX4_THREADS, chunks);
     }
     int mx4_quant(const smhip_mx4_quant_desc& d, uint8_t* codes, uint8_t* scales, smhip_mx4_report* rep) {
@@ -2028,7 +2038,7 @@ class DeltaHost {
         p.base = d.base; p.uni = d.unified; p.dtype = d.dtype; p.R = R; p.C = C; p.PB = PB; p.units = R * PB;
         p.mask = d.mask; p.scale = d.scale;
         p.out = out; p.row_vec = emr_row_vec(C, d.base, d.unified, out);
-        p.chunks = pick_chunks(p.units, 256, 2, 8);
+        p.chunks = stream_chunks(p.units, 256, 2, 8);
         be.template launch<KEmrApply>(stream_grid(p.units, 256, p.chunks), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         return SMHIP_OK;
     }

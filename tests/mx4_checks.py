@@ -283,3 +283,76 @@ def check_commands_and_merge(tmp_path, engine, device):
         (q4 / "config.json").write_text(json.dumps(doc))
         with pytest.raises(ValueError, match=rf"org/ft1-mx4.*{field}"):
             asyncio.run(LocalModelIndex(storage_path=storage).add_model("org/ft1-mx4"))
+
+
+ODDS = ("model.layers.0.mlp.up_proj.weight", "model.layers.1.mlp.up_proj.weight")      # (every layer has the same tensors)
+ODD = ODDS[1]                                         # a named module's weight of 80 columns: two blocks and a half
+
+
+def add_odd_weight(storage, src, dst, which):
+    """a copy of the model `src` as `dst` with the tensors ODDS added to its last shard (which = 0: the base's; 1, 2: a
+    finetune's); the shared tensors of tests/lora_fixtures.py stay as they are.  Returns the tensor"""
+    import shutil
+    from safetensors.torch import load_file, save_file
+    from tests import lora_fixtures as lf
+    shutil.copytree(storage / src, storage / dst)
+    index = storage / dst / "model.safetensors.index.json"
+    doc = json.loads(index.read_text())
+    shard = sorted(set(doc["weight_map"].values()))[-1]
+    tensors = load_file(str(storage / dst / shard))
+    for j, name in enumerate(ODDS):
+        t = lf.randn((64, 80), 900 + j, 0.02)
+        tensors[name] = (t + lf.randn((64, 80), 900 + 10 * which + j, 0.003) if which else t).to(torch.bfloat16)
+        doc["weight_map"][name] = shard
+    save_file(tensors, str(storage / dst / shard), metadata={"format": "pt"})
+    index.write_text(json.dumps(doc))
+    return {name: tensors[name] for name in ODDS}
+
+
+def check_odd_columns(tmp_path, engine, device):
+    """a named module's weight whose column count is no multiple of 32: `quantize-mxfp4` copies it byte for byte, writes no
+    scale for it and lists its module under modules_to_not_convert; `dequantize-mxfp4` and a merge of the result succeed"""
+    import asyncio
+    from safetensors.torch import load_file
+    from shardmerge_amd.index import LocalModelIndex
+    from tests import harness, lora_fixtures as lf
+    lf.setup_k3(tmp_path, engine)
+    storage = tmp_path / "storage"
+    odd = [add_odd_weight(storage, f"org/{m}", f"org/{m}-odd", which) for which, m in enumerate(("base", "ft1", "ft2"))]
+    assert odd[1][ODD].shape[1] % 32 != 0 and not torch.equal(odd[1][ODD], odd[0][ODD])
+    q4, back = storage / "org/ft1-odd-mx4", storage / "org/ft1-odd-back"
+    for args in (["quantize-mxfp4", "org/ft1-odd", "--out", q4], ["dequantize-mxfp4", "org/ft1-odd-mx4", "--out", back, "--dtype", "bf16"]):
+        res = run_cli(args + ["--storage-dir", storage, "--device", device])
+        assert res.exit_code == 0, res.output
+    ft1 = dict(lf.model_tensors(1), **odd[1])
+    got = {}
+    for f in sorted(q4.glob("*.safetensors")):
+        got.update(load_file(str(f)))
+    quantised = [n for n, t in ft1.items() if t.ndim == 2 and n.split(".")[-2].endswith("_proj") and n not in ODDS]
+    assert len(quantised) == 6 and sorted(got) == sorted(list(ft1) + [f"{n}_scale" for n in quantised])     # no scale for ODD
+    for n in ODDS:
+        assert got[n].dtype == torch.bfloat16 and got[n].shape == odd[1][n].shape and torch.equal(raw(got[n]), raw(odd[1][n])), n
+    for n in quantised:
+        assert all(np.array_equal(got[k].numpy(), w) for k, w in zip((n, f"{n}_scale"), restate(ft1[n]))), n
+    qc = json.loads((q4 / "config.json").read_text())["quantization_config"]
+    assert all(n.rsplit(".", 1)[0] in qc["modules_to_not_convert"] for n in ODDS)
+    assert qc["modules_to_not_convert"] == sorted({n.rsplit(".", 1)[0] for n in set(ft1) - set(quantised)})
+    restored = {}
+    for f in sorted(back.glob("*.safetensors")):
+        restored.update(load_file(str(f)))
+    assert sorted(restored) == sorted(ft1) and all(torch.equal(raw(restored[n]), raw(odd[1][n])) for n in ODDS)
+    index = LocalModelIndex(storage_path=storage)
+    asyncio.run(index.add_model("org/ft1-odd-mx4"))
+    assert index.mx4("org/ft1-odd-mx4") is not None and ODD not in index.mx4("org/ft1-odd-mx4").scale_keys
+    outs = []
+    for entry in ("org/ft1-odd-mx4", "org/ft1-odd-back", "org/ft1-odd"):
+        models = [{"model": entry, "base": "org/base-odd", "alpha": 0.5, "is_input": True},
+                  {"model": "org/ft2-odd", "base": "org/base-odd", "alpha": 0.4, "is_output": True}]
+        p = harness.write_config(tmp_path, models, f"merged-{entry[-3:]}", {"operator": "ties", "density": 0.3, "ties_lambda": 0.7}, device)
+        p.write_text(p.read_text().replace("output_base_model: org/base", "output_base_model: org/base-odd"))
+        res = harness.run_cli(p)
+        assert res.exit_code == 0, res.output
+        outs.append(lf.read_outputs(tmp_path / f"merged-{entry[-3:]}"))
+    assert sorted(outs[0]) == sorted(outs[1]) == sorted(ft1) and all(torch.equal(raw(outs[0][n]), raw(outs[1][n])) for n in ft1)
+    # the copied tensor merges as the model that was never quantised does, and it does merge: the output is not the base's
+    assert torch.equal(raw(outs[0][ODD]), raw(outs[2][ODD])) and not torch.equal(raw(outs[0][ODD]), raw(odd[0][ODD]))

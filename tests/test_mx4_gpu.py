@@ -47,3 +47,7 @@ def test_device_against_emulator(eng, shape):
 
 def test_commands_and_merge_on_the_device(tmp_path, eng):
     mc.check_commands_and_merge(tmp_path, eng, "cuda")
+
+
+def test_odd_columns_are_copied_on_the_device(tmp_path, eng):
+    mc.check_odd_columns(tmp_path, eng, "cuda")

@@ -31,3 +31,7 @@ def test_error_bound_in_fp64(emul):
 
 def test_commands_and_merge(tmp_path, emul):
     mc.check_commands_and_merge(tmp_path, emul, "cpu")
+
+
+def test_odd_columns_are_copied(tmp_path, emul):
+    mc.check_odd_columns(tmp_path, emul, "cpu")
