@@ -1203,6 +1203,98 @@ typedef struct {
 } smhip_iso_gemm_desc;
 int smhip_iso_gemm(smhip_ctx* ctx, const smhip_iso_gemm_desc* desc, void* stream);
 
+/* ---- WUDI-Merging (Cheng et al. 2025, "Whoever Started the Interference Should End It: Guiding Data-Free Model Merging via
+ *      Task Vectors"; the method as recalled): per 2-D tensor [rows x cols] = R x C with task vectors
+ *      d_i, the merged task vector X minimises L(X) = sum_i ||(X - d_i) d_i^T||_F^2 / ||d_i||_F^2 - the rows of d_i stand
+ *      in for the layer's inputs on task i, no data is read.  grad L = 2 (X S - P) with S = sum_i d_i^T d_i / n_i [C x C]
+ *      and P = sum_i d_i (d_i^T d_i) / n_i [R x C], so S and P are built once and a step is ONE product X S plus Adam's
+ *      update.  Every fp32 step below is one correctly rounded operation or one fmaf; a chain is one fmaf per product in
+ *      ascending index from +0, followed, when the number of products is odd, by one step fmaf(+0, +0, acc).
+ *        1. Task vectors.  d_i = fp32(finetune_i) - fp32(base_i), one rounded subtraction, formed wherever it is read.
+ *        2. Norms.  n_i = the ordered fp64 sum of d_i^2 (smhip_iso_merge's ordered sum; "geo_gram" over the one entry, its
+ *           diagonal).  A NaN or Inf in ANY d_i fails the call with SMHIP_ERR_NONFINITE (the message names the finetunes).
+ *           An entry with alpha_i == 0 or n_i == 0 is inactive and left out of steps 3, 4.  All inactive: zero = 1,
+ *           merged = +0, step 8 runs with it.
+ *        3. Weights.  w_i = fp32(alpha_i / n_i), the division in fp64.  alpha_i >= 0.
+ *        4. Per active task, in entry order:
+ *             Sh_i[a][b] = fmul(w_i, chain_r fmaf(d_i[r][a], d_i[r][b], .)), computed for whole 128 x 128 tiles ta >= tb and
+ *             mirrored (inside a diagonal tile both halves: fp32 products commute), so Sh_i == Sh_i^T bit for bit;
+ *             S = fadd(S, Sh_i), the first active task stores Sh_i;
+ *             P[r][c] = fadd(P[r][c], chain_a fmaf(d_i[r][a], Sh_i[c][a], .)), the first active task stores the chain.
+ *        5. Start.  X_0[e] = ((0 + d_0 * a_0) + d_1 * a_1) + ... over ALL entries, a_i = fp32(alpha_i): step 1 of
+ *           smhip_iso_merge ("iso_sum").  m_0 = v_0 = +0.
+ *        6. Constants.  b1 = 0x1.ccccccp-1 = fp32(0.9), b2 = 0x1.ff7ceep-1 = fp32(0.999), eps = 0x1.5798eep-27 = fp32(1e-8),
+ *           c1 = fp32(1 - 0.9), c2 = fp32(1 - 0.999), the subtractions in fp64.  With B1_t = B1_{t-1} * 0.9 and
+ *           B2_t = B2_{t-1} * 0.999 from 1 (one fp64 product per step): s_t = fp32(lr / (1 - B1_t)),
+ *           q_t = fp32(1 / sqrt(1 - B2_t)), every operation one fp64 operation.
+ *        7. Step t = 1 .. iters, per element:
+ *             acc = chain_a fmaf(X[r][a], S[c][a], .)
+ *             g   = fmul(2, fsub(acc, P))
+ *             m'  = fmaf(b1, m, fmul(c1, g))
+ *             v'  = fmaf(b2, v, fmul(fmul(c2, g), g))
+ *             den = fadd(fmul(sqrt(v'), q_t), eps)
+ *             X'  = fsub(X, fmul(s_t, fdiv(m', den)))
+ *           grad_sq_first / grad_sq_last = the ordered fp64 sum of g^2 at t = 1 / t = iters (0 when iters == 0).
+ *        8. merged = X_iters; out = round_to(base_out_dtype, fma(fp32(lambda), merged, fp32(base_out))); delta_out = merged.
+ *      Passes: every finetune and base read once for n_i, ceil(C / 128) / 2 + 1 times (about) for Sh_i, ceil(C / 128) times
+ *      for P, once for X_0; 2 K R C^2 flops to build S and P, 2 R C^2 per step.  Profile names: "geo_gram",
+ *      "geo_gram_fold" (k + 0..2), "wudi_gram" and "wudi_rhs" (one per active task), "iso_sum", "wudi_step" (one per
+ *      step), "iso_norm" (0..2), "iso_apply".  The stream is synchronised twice: for the norms and for the report.  The
+ *      workspace is the caller's: DEVICE memory, 256-byte aligned, at least smhip_wudi_workspace(rows, cols) bytes - S
+ *      [C x C], Sh (max(C C, R C) floats: g of the two reported steps goes there), P, m, v, X, X' [R x C] and the sums'
+ *      partials.  SMHIP_ERR_ARG: k outside 1..16, an alpha that is not finite or < 0, a non-finite lambda, lr outside
+ *      (0, 1], iters outside 0..2000, n != rows * cols, rows or cols < 1 (n > 0), cols > 32768, a bad workspace, and the
+ *      aliasing, alignment, dtype and null-pointer rules of smhip_ties_merge.  n == 0: a no-op, the report all zeros. ---- */
+#define SMHIP_WUDI_MAX_C 32768
+#define SMHIP_WUDI_MAX_ITER 2000
+typedef struct {
+    int k;
+    const void* finetune[SMHIP_MAX_MODELS]; /* device, in_dtype, [rows x cols] */
+    const void* base[SMHIP_MAX_MODELS];     /* device, in_dtype: each finetune's own base */
+    double alpha[SMHIP_MAX_MODELS];         /* >= 0 */
+    int in_dtype;
+    const void* base_out; int base_out_dtype;
+    size_t n;                               /* rows * cols */
+    int rows, cols;
+    double lambda;
+    double lr;                              /* (0, 1] */
+    int iters;                              /* 0..2000 */
+    void* workspace; size_t workspace_bytes;
+} smhip_wudi_desc;
+typedef struct {
+    int rows, cols;
+    int k_active, iterations, zero;
+    int active[SMHIP_MAX_MODELS];           /* the active entries, ascending; k_active of them */
+    double n[SMHIP_MAX_MODELS];             /* n_i of every entry */
+    float w[SMHIP_MAX_MODELS];              /* w_i of every entry, 0 for an inactive one */
+    double grad_sq_first, grad_sq_last;
+} smhip_wudi_report;
+size_t smhip_wudi_workspace(int rows, int cols);  /* 0: a bad argument */
+/* out: device, base_out_dtype, [rows x cols].  delta_out (optional): device float, merged.  report (optional): HOST. */
+int smhip_wudi_merge(smhip_ctx* ctx, const smhip_wudi_desc* desc, void* out, float* delta_out,
+                     smhip_wudi_report* report, void* stream);
+/* TEST ABI, as smhip_iso_gemm: one of the three kernels alone on DEVICE operands with element-aligned pointers and pitches.
+ * kind 0 "wudi_gram": d = finetune - base [K x N] (dtype, pitch ld); sh = fmul(w, d^T d), s = sh (first) or fadd(s, sh),
+ *   both [N x N] contiguous.
+ * kind 1 "wudi_rhs": d [M x K]; p = chain_k d[m][k] b[n][k] (first) or fadd(p, chain); b [N x K] fp32 pitch ldb.
+ * kind 2 "wudi_step": acc = chain_k a[m][k] b[n][k], a [M x K] pitch lda; step 7 with the planes p, m, v (updated in
+ *   place), x (pitch ldx; the X of the update), xn and the optional g, all [M x N], contiguous but x; s_t and q_t of
+ *   step `t` at `lr`.  No output may overlap an operand. */
+typedef struct {
+    int kind;
+    int M, N, K;
+    const void* finetune; const void* base; int dtype; int ld;
+    const float* a; int lda;
+    const float* b; int ldb;
+    int first; float w;
+    float* sh; float* s;
+    float* p; float* m; float* v;
+    const float* x; int ldx;
+    float* xn; float* g;
+    int t; double lr;
+} smhip_wudi_gemm_desc;
+int smhip_wudi_gemm(smhip_ctx* ctx, const smhip_wudi_gemm_desc* desc, void* stream);
+
 /* ---- WIDEN merge (Yu, Yu, Yu, Huang, Li, "Extend Model Merging from Fine-Tuned to Pre-Trained Large Language Models via
  *      Weight Disentanglement", 2024): every weight matrix is disentangled into a magnitude and a direction per column,
  *      the divergences of each finetune from its base in both are RANKED within the finetune - which makes the measure

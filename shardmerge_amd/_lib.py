@@ -340,6 +340,32 @@ class IsoGemmDesc(C.Structure):
                 ("ca", C.c_float), ("cb", C.c_float), ("c", C.c_void_p), ("ldc", C.c_int)]
 
 
+WUDI_MAX_C, WUDI_MAX_ITER = 32768, 2000            # SMHIP_WUDI_MAX_C, SMHIP_WUDI_MAX_ITER
+WUDI_GRAM, WUDI_RHS, WUDI_STEP = range(3)           # kind of smhip_wudi_gemm
+
+
+class WudiDesc(C.Structure):
+    """smhip_wudi_desc: the leading fields of the delta merges, then the shape, lambda, lr, iters and the workspace"""
+    _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("lam", C.c_double), ("lr", C.c_double),
+                                         ("iters", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class WudiReport(C.Structure):
+    """smhip_wudi_report"""
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("k_active", C.c_int), ("iterations", C.c_int), ("zero", C.c_int),
+                ("active", C.c_int * MAX_MODELS), ("n", C.c_double * MAX_MODELS), ("w", C.c_float * MAX_MODELS),
+                ("grad_sq_first", C.c_double), ("grad_sq_last", C.c_double)]
+
+
+class WudiGemmDesc(C.Structure):
+    """smhip_wudi_gemm_desc"""
+    _fields_ = [("kind", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("finetune", C.c_void_p), ("base", C.c_void_p), ("dtype", C.c_int), ("ld", C.c_int),
+                ("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("first", C.c_int), ("w", C.c_float),
+                ("sh", C.c_void_p), ("s", C.c_void_p), ("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+                ("x", C.c_void_p), ("ldx", C.c_int), ("xn", C.c_void_p), ("g", C.c_void_p), ("t", C.c_int), ("lr", C.c_double)]
+
+
 DPACK_ROW, DPACK_TENSOR = 0, 1                      # scale_mode of smhip_dpack_pack / smhip_dpack_apply
 DPACK_SCALE_MODES = {"row": DPACK_ROW, "tensor": DPACK_TENSOR}
 
@@ -525,6 +551,10 @@ class SmhipLibrary:
         d.smhip_iso_workspace.restype = C.c_size_t
         d.smhip_iso_merge.argtypes = [P, C.POINTER(IsoDesc), P, P, C.POINTER(IsoReport), P]
         d.smhip_iso_gemm.argtypes = [P, C.POINTER(IsoGemmDesc), P]
+        d.smhip_wudi_workspace.argtypes = [I, I]
+        d.smhip_wudi_workspace.restype = C.c_size_t
+        d.smhip_wudi_merge.argtypes = [P, C.POINTER(WudiDesc), P, P, C.POINTER(WudiReport), P]
+        d.smhip_wudi_gemm.argtypes = [P, C.POINTER(WudiGemmDesc), P]
         d.smhip_dpack_pack.argtypes = [P, C.POINTER(DpackDesc), P, P, P, C.POINTER(DpackReport), P]
         d.smhip_dpack_apply.argtypes = [P, C.POINTER(DpackApplyDesc), P, P]
         d.smhip_fp8_quant.argtypes = [P, C.POINTER(Fp8QuantDesc), P, P, C.POINTER(Fp8Report), P]

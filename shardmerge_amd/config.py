@@ -173,6 +173,19 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # iso_lambda: 1.0         #   scales the merged delta
       # iso_tol: 0.0001         #   0 < iso_tol <= 1: the iteration stops at ||X X^T - I||_F / sqrt(min(rows, cols)) <= iso_tol
       # iso_max_iter: 40        #   an integer in 0..200: steps at most (reaching it is reported, not an error)
+                                # | wudi (WUDI-Merging, Cheng et al. 2025; no counterpart in the reference): per block
+                                #   matrix ([shape[0] x the rest]) the merged task vector X that minimises the interference
+                                #   sum_i ||(X - d_i) d_i^T||^2 / ||d_i||^2 between the tasks, the deltas d_i themselves
+                                #   standing in for the layer's inputs: wudi_iters Adam steps from the sum of the deltas
+                                #   times their alphas, one fp32 MFMA product per step.  alphas >= 0 with a positive sum.
+                                #   1-D tensors, and a matrix that the layer windows leave with ONE covering entry, take
+                                #   the normalised weighted mean of their deltas (dare_linear at density 1) times
+                                #   wudi_lambda.  A block tensor with more than 32768 columns is an error before anything
+                                #   is written.  The spectral keys, norm_mode, task_add_models and every other family's
+                                #   keys are rejected; keys:
+      # wudi_iters: 300         #   an integer in 0..2000: Adam steps
+      # wudi_lr: 0.00001        #   0 < wudi_lr <= 1: the step size
+      # wudi_lambda: 1.0        #   scales the merged task vector
                                 # | emr (EMR-Merging, Huang et al. 2024; no counterpart in the reference): the UNIFIED model -
                                 #   per element the deltas are summed, the sign of the sum is elected (a zero sum elects
                                 #   plus), and the entry of that sign with the largest magnitude is taken as it is.  It takes
@@ -213,7 +226,7 @@ MERGE_OPTION_RANGES = {"cutoff_pct": (0.0, 1.0), "cull_start_pct": (0.0, 1.0), "
                        "b": (0.0, 1e6)}
 OPERATORS = ("fourier", "addition", "task_addition", "fourier_legacy", "ties", "dare_ties", "dare_linear", "breadcrumbs", "breadcrumbs_ties",
              "model_stock", "nuslerp", "slerp", "sce", "della", "della_linear", "consensus_ta", "consensus_ties",
-             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs", "iso_c", "emr")
+             "karcher", "multislerp", "arcee_fusion", "nearswap", "pcb", "tsv", "widen", "cabs", "iso_c", "emr", "wudi")
 # The delta-merge operator families: ties, DARE, Model Breadcrumbs.  A family's keys are accepted with its operators only
 # (all of them but consensus_ta take `density`), seed and consensus_k stay ints (they must survive exactly), every
 # other value becomes a float.
@@ -249,6 +262,9 @@ ISO_OPTION_DEFAULTS = {"iso_lambda": 1.0, "iso_tol": 1e-4, "iso_max_iter": 40}
 ISO_MAX_S = 16384                                   # min(rows, cols) of a block tensor at most
 EMR_OPERATORS = ("emr",)                            # the elected unified model; it takes no weights
 EMR_OPTION_DEFAULTS = {"emr_lambda": 1.0}
+WUDI_OPERATORS = ("wudi",)
+WUDI_OPTION_DEFAULTS = {"wudi_iters": 300, "wudi_lr": 1e-5, "wudi_lambda": 1.0}
+WUDI_MAX_C = 32768                                  # columns of a block tensor at most: S is [C x C]
 TSV_MAX_VECTORS = 256                               # k * min(tsv_rank, rows, cols) at most: the width of the whitened panels
 
 
@@ -423,6 +439,16 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "della": "(it drops nothing at random)",
                            "consensus_ta": "(its masks are per task, computed by emr-task afterwards)",
                            "arcee_fusion": "(it merges several models by election)"}),
+    _OptionFamily(WUDI_OPERATORS, WUDI_OPTION_DEFAULTS,
+                  {"wudi_iters": ("int", 0, 2000), "wudi_lr": (0, 1, "(]"), "wudi_lambda": _LAMBDA},
+                  earlier={"ties": "(it trims nothing and optimises the merged delta against interference: wudi_lambda)",
+                           "dare_ties": "(it drops nothing at random)",
+                           "breadcrumbs": "(it trims nothing)",
+                           "model_stock": "(it weights by alpha and optimises the sum)",
+                           "sce": "(it selects nothing: every element is optimised)",
+                           "della": "(it drops nothing at random)",
+                           "consensus_ta": "(it masks nothing)",
+                           "arcee_fusion": "(it merges several models by minimising their interference)"}),
 )
 
 
@@ -627,6 +653,11 @@ class MergeConfig:
             if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
                 raise click.BadParameter(f"operator tsv needs finetune_merge alphas >= 0 with a sum > 0 (an alpha scales the "
                                          f"finetune's singular values; 0 leaves the finetune out), not {alphas}")
+        if operator in WUDI_OPERATORS:
+            alphas = [m.alpha for m in raw["finetune_merge"]]
+            if any(isinstance(a, bool) or not isinstance(a, (int, float)) or not (a >= 0) for a in alphas) or not (0 < sum(alphas) < float("inf")):
+                raise click.BadParameter(f"operator wudi needs finetune_merge alphas >= 0 with a sum > 0 (an alpha scales the "
+                                         f"task's weight in the objective and in the start; 0 leaves the finetune out), not {alphas}")
         if operator in FUSION_OPERATORS + EMR_OPERATORS:
             for m in raw["finetune_merge"]:
                 if isinstance(m.alpha, bool) or not isinstance(m.alpha, (int, float)) or m.alpha != 1:

@@ -936,6 +936,89 @@ int smhip_iso_gemm(smhip_ctx* ctx, const smhip_iso_gemm_desc* d, void* stream) {
     SM_FINISH(ctx, ctx->pipe.delta.iso_gemm_probe(*d));
 }
 
+size_t smhip_wudi_workspace(int rows, int cols) {
+    if (rows < 1 || cols < 1 || cols > SMHIP_WUDI_MAX_C) return 0;
+    return smhip::DeltaHost<SM_BACKEND>::wudi_layout(rows, cols).total;
+}
+
+int smhip_wudi_merge(smhip_ctx* ctx, const smhip_wudi_desc* d, void* out, float* delta_out, smhip_wudi_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (int rc = delta_tensor_check(ctx, "wudi_merge", d, out, delta_out, true, [&]() -> const char* {
+            if (!std::isfinite(d->lambda)) return "lambda is not finite";
+            if (!(d->lr > 0.0 && d->lr <= 1.0)) return "lr must be in (0, 1]";
+            if (d->iters < 0 || d->iters > SMHIP_WUDI_MAX_ITER) return "iters out of range (0..2000)";
+            for (int i = 0; i < d->k; ++i)
+                if (d->alpha[i] < 0.0) return "an alpha is negative";
+            return nullptr;
+        }))
+        return rc;
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("wudi_merge: ") + what); };
+    if (d->n > 0) {
+        if (d->rows < 1 || d->cols < 1 || (size_t)d->rows * (size_t)d->cols != d->n) return bad("rows and cols must be >= 1 and rows * cols == n");
+        if (d->cols > SMHIP_WUDI_MAX_C) return bad("cols exceeds 32768");
+        if (d->n / smhip::GEO_SEG_ELEMS > (size_t)1 << 30) return bad("tensor too large");
+        if (!d->workspace || (uintptr_t)d->workspace % 256 || d->workspace_bytes < smhip_wudi_workspace(d->rows, d->cols))
+            return bad("the workspace is null, not 256-byte aligned or too small (smhip_wudi_workspace)");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.wudi_merge(*d, out, delta_out, report));
+}
+
+int smhip_wudi_gemm(smhip_ctx* ctx, const smhip_wudi_gemm_desc* d, void* stream) {
+    SM_GUARD(ctx);
+    auto bad = [&](const char* what) { return ctx->pipe.fail(SMHIP_ERR_ARG, std::string("wudi_gemm: ") + what); };
+    if (!d) return bad("null descriptor");
+    if (d->kind < 0 || d->kind > 2) return bad("bad kind");
+    if (d->M < 1 || d->N < 1 || d->K < 1 || d->M > (1 << 24) || d->N > (1 << 24)) return bad("bad shape");
+    if (d->kind == 0 && d->M != d->N) return bad("bad shape (gram: M == N)");
+    const int gm = (d->M + 127) / 128, gn = (d->N + 127) / 128;
+    if ((long long)gm * gn > 0x7fffffffLL) return bad("bad shape");
+    using Span = std::pair<uintptr_t, uintptr_t>;
+    auto span = [](const void* p, size_t es, int rows, int ld, int cols) { return Span((uintptr_t)p, (uintptr_t)p + ((size_t)(rows - 1) * ld + cols) * es); };
+    std::vector<Span> ins, outs;
+    if (d->kind != 2) {
+        if (d->dtype < SMHIP_BF16 || d->dtype > SMHIP_F32) return bad("bad dtype");
+        const size_t es = d->dtype == SMHIP_F32 ? 4 : 2;
+        const int nr = d->kind == 0 ? d->K : d->M, nc = d->kind == 0 ? d->N : d->K;
+        if (!d->finetune || !d->base) return bad("null pointer");
+        if ((uintptr_t)d->finetune % es || (uintptr_t)d->base % es) return bad("a pointer is not aligned to its element size");
+        if (d->ld < nc) return bad("a pitch is shorter than its row");
+        ins.push_back(span(d->finetune, es, nr, d->ld, nc)); ins.push_back(span(d->base, es, nr, d->ld, nc));
+    }
+    if (d->kind == 0) {
+        if (!d->sh || !d->s) return bad("null pointer");
+        if ((uintptr_t)d->sh % 4 || (uintptr_t)d->s % 4) return bad("a pointer is not aligned to its element size");
+        outs.push_back(span(d->sh, 4, d->N, d->N, d->N)); outs.push_back(span(d->s, 4, d->N, d->N, d->N));
+    } else {
+        if (!d->b || !d->p) return bad("null pointer");
+        if ((uintptr_t)d->b % 4 || (uintptr_t)d->p % 4) return bad("a pointer is not aligned to its element size");
+        if (d->ldb < d->K) return bad("a pitch is shorter than its row");
+        ins.push_back(span(d->b, 4, d->N, d->ldb, d->K));
+        (d->kind == 1 ? outs : ins).push_back(span(d->p, 4, d->M, d->N, d->N));
+    }
+    if (d->kind == 2) {
+        if (!d->a || !d->m || !d->v || !d->x || !d->xn) return bad("null pointer");
+        if ((uintptr_t)d->a % 4 || (uintptr_t)d->m % 4 || (uintptr_t)d->v % 4 || (uintptr_t)d->x % 4 || (uintptr_t)d->xn % 4 || (uintptr_t)d->g % 4)
+            return bad("a pointer is not aligned to its element size");
+        if (d->lda < d->K || d->ldx < d->N) return bad("a pitch is shorter than its row");
+        if (d->t < 1 || d->t > SMHIP_WUDI_MAX_ITER) return bad("t out of range (1..2000)");
+        if (!(d->lr > 0.0 && d->lr <= 1.0)) return bad("lr must be in (0, 1]");
+        ins.push_back(span(d->a, 4, d->M, d->lda, d->K)); ins.push_back(span(d->x, 4, d->M, d->ldx, d->N));
+        outs.push_back(span(d->m, 4, d->M, d->N, d->N)); outs.push_back(span(d->v, 4, d->M, d->N, d->N));
+        outs.push_back(span(d->xn, 4, d->M, d->N, d->N));
+        if (d->g) outs.push_back(span(d->g, 4, d->M, d->N, d->N));
+    }
+    auto hits = [](const Span& x, const Span& y) { return x.first < y.second && y.first < x.second; };
+    for (size_t o = 0; o < outs.size(); ++o) {
+        for (const Span& in : ins)
+            if (hits(outs[o], in)) return bad("an output overlaps an operand");
+        for (size_t q = o + 1; q < outs.size(); ++q)
+            if (hits(outs[o], outs[q])) return bad("an output overlaps an operand");
+    }
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.wudi_gemm_probe(*d));
+}
+
 int smhip_exact_norm(smhip_ctx* ctx, const void* x, int dtype, size_t n, double* norm_out, void* stream) {
     SM_GUARD(ctx);
     if (!norm_out || (n > 0 && !x)) return ctx->pipe.fail(SMHIP_ERR_ARG, "bad argument");

@@ -35,6 +35,7 @@
 #include "sm_eig.hpp"
 #include "sm_fp8.hpp"
 #include "sm_mx4.hpp"
+#include "sm_wudi.hpp"
 
 namespace smhip {
 
@@ -1669,6 +1670,168 @@ class DeltaHost {
     }
     int iso_gemm_probe(const smhip_iso_gemm_desc& d) {
         iso_gemm(d.form, d.sym, d.a, d.lda, d.b, d.ldb, d.M, d.N, d.K, d.epilogue, d.ca, d.cb, d.e, d.lde, d.c, d.ldc);
+        be.sync(stream);
+        return SMHIP_OK;
+    }
+
+    // ---- WUDI-Merging (sm_wudi.hpp; smhip_wudi_merge).  The caller's workspace: S [C x C] | Sh, max(C C, R C) floats: the
+    // gradient of the two reported steps goes there | P, m, v and the two X of the iteration [R x C] | the partials of the
+    // ordered sums | 512 bytes: a flag word per entry and one for the sum, then n_i [16] and the two gradient sums. ----
+    struct WudiLayout {
+        size_t n, Sh, P, M, V, X0, X1, part, tail, total;
+    };
+    static WudiLayout wudi_layout(int rows, int cols) {
+        WudiLayout t;
+        t.n = (size_t)rows * cols;
+        const size_t cc = (size_t)cols * cols, nb = round_up(t.n * 4, 256);
+        t.Sh = round_up(cc * 4, 256);
+        t.P = t.Sh + round_up(std::max(cc, t.n) * 4, 256);
+        t.M = t.P + nb; t.V = t.M + nb; t.X0 = t.V + nb; t.X1 = t.X0 + nb;
+        t.part = t.X1 + nb;
+        t.tail = t.part + round_up((t.n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS * 8, 256);
+        t.total = t.tail + 512;
+        return t;
+    }
+    static void wudi_delta(WudiDelta& w, const void* ft, const void* base, int dtype, int ld, int nr, int nc) {
+        w.ft = ft; w.base = base; w.dtype = dtype; w.ld = ld; w.nr = nr; w.nc = nc;
+        w.vec = (aligned16(ft) && aligned16(base) && ld % (dtype == DT_F32 ? 4 : 8) == 0) ? 1 : 0;
+    }
+    // the launches: g holds the kernel's operands and planes, the shape and the grid are filled here
+    void wudi_launch(int kind, WudiGemmParams& g, int M, int N, int K) {
+        g.M = M; g.N = N; g.K = K;
+        g.avec = (aligned16(g.a) && g.lda % 4 == 0) ? 1 : 0; g.bvec = (aligned16(g.b) && g.ldb % 4 == 0) ? 1 : 0;
+        const int gm = (M + ISO_WG - 1) / ISO_WG;
+        g.gn = (N + ISO_WG - 1) / ISO_WG;
+        if (kind == WUDI_GRAM) be.template launch<KWudiGram>(g.gn * (g.gn + 1) / 2, ISO_THREADS, WUDI_LDS_FLOATS * 4, g, stream);
+        else if (kind == WUDI_RHS) be.template launch<KWudiRhs>(gm * g.gn, ISO_THREADS, WUDI_LDS_FLOATS * 4, g, stream);
+        else be.template launch<KWudiStep>(gm * g.gn, ISO_THREADS, WUDI_LDS_FLOATS * 4, g, stream);
+    }
+    // s_t and q_t of steps 1 .. iters (smhip_wudi_merge, step 6): one fp64 operation at a time
+    struct WudiSchedule {
+        double lr, b1t = 1.0, b2t = 1.0;
+        float c1, c2, st = 0.f, qt = 0.f;
+        explicit WudiSchedule(double lr_) : lr(lr_), c1((float)geo_dadd(1.0, -0.9)), c2((float)geo_dadd(1.0, -0.999)) {}
+        void next() {
+            b1t = geo_dmul(b1t, 0.9); b2t = geo_dmul(b2t, 0.999);
+            st = (float)geo_ddiv(lr, geo_dadd(1.0, -b1t));
+            qt = (float)geo_ddiv(1.0, geo_dsqrt(geo_dadd(1.0, -b2t)));
+        }
+        void fill(WudiGemmParams& g) const { g.c1 = c1; g.c2 = c2; g.st = st; g.qt = qt; }
+    };
+    int wudi_merge(const smhip_wudi_desc& d, void* out, float* delta_out, smhip_wudi_report* rep) {
+        smhip_wudi_report local;
+        smhip_wudi_report& R_ = rep ? *rep : local;
+        R_ = smhip_wudi_report{};
+        if (d.n == 0) return SMHIP_OK;
+        const WudiLayout t = wudi_layout(d.rows, d.cols);
+        const int R = d.rows, C = d.cols, k = d.k;
+        char* ws = (char*)d.workspace;
+        float* S = (float*)ws;
+        float* Sh = (float*)(ws + t.Sh);
+        float* P = (float*)(ws + t.P);
+        float* Mo = (float*)(ws + t.M);
+        float* Vo = (float*)(ws + t.V);
+        float* X = (float*)(ws + t.X0);
+        float* Xn = (float*)(ws + t.X1);
+        double* part = (double*)(ws + t.part);
+        uint32_t* flags = (uint32_t*)(ws + t.tail);                 // [i]: entry i (bit 0), [16]: iso_sum's
+        double* nsq = (double*)(ws + t.tail + 128);                 // [16]
+        double* res = nsq + TIES_MAX_MODELS;                        // [0]: sum g^2 of step 1, [1]: of the last step
+        be.memset(flags, 0, 512, stream);
+        R_.rows = R; R_.cols = C; R_.iterations = d.iters;
+
+        // 2: the norms, geo_gram over one entry at a time (its diagonal and nothing else)
+        const size_t nseg = (d.n + GEO_SEG_ELEMS - 1) / GEO_SEG_ELEMS;
+        for (int i = 0; i < k; ++i) {
+            TiesInputs in;
+            ties_inputs(in, 1, d.in_dtype, d.n, d.finetune + i, d.base + i, true);
+            gram_pass(in, false, GEO_SEG_ELEMS, nseg, part, flags + i, nsq + i);
+        }
+        uint32_t fl[TIES_MAX_MODELS + 1];
+        double nh[TIES_MAX_MODELS];
+        be.d2h(fl, flags, sizeof fl, stream);
+        be.d2h(nh, nsq, sizeof nh, stream);                         // the first synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        uint32_t bad = 0;
+        for (int i = 0; i < k; ++i) bad |= fl[i] ? 1u << i : 0u;
+        if (bad) return delta_nonfinite("wudi_merge", "finetune - base", k, bad);
+        // 3: the weights
+        for (int i = 0; i < k; ++i) {
+            R_.n[i] = nh[i];
+            if (d.alpha[i] == 0.0 || nh[i] == 0.0) continue;
+            R_.w[i] = (float)geo_ddiv(d.alpha[i], nh[i]);
+            R_.active[R_.k_active++] = i;
+        }
+        auto apply = [&](const float* x) {
+            IsoApplyParams a;
+            a.q = x; a.sigma = 1.f; a.lambda = (float)d.lambda; a.base_out = d.base_out; a.dtype = d.base_out_dtype;
+            a.out = out; a.delta_out = delta_out; a.n = d.n;
+            a.aligned = (aligned16(d.base_out) && aligned16(out) && aligned16(delta_out)) ? 1 : 0;
+            a.chunks = stream_chunks((d.n + 7) / 8, 256, 2, 8);
+            be.template launch<KIsoApply>(stream_grid((d.n + 7) / 8, 256, a.chunks), 256, 0, a, stream);
+        };
+        if (R_.k_active == 0) {
+            R_.zero = 1;
+            be.memset(X, 0, d.n * 4, stream);
+            apply(X);
+            be.sync(stream);
+            return SMHIP_OK;
+        }
+        // 4: S and P
+        for (int q = 0; q < R_.k_active; ++q) {
+            const int i = R_.active[q];
+            WudiGemmParams g{};
+            wudi_delta(g.d, d.finetune[i], d.base[i], d.in_dtype, C, R, C);
+            g.first = q == 0 ? 1 : 0; g.w = R_.w[i]; g.sh = Sh; g.s = S; g.ldo = C;
+            wudi_launch(WUDI_GRAM, g, C, C, R);
+            g.b = Sh; g.ldb = C; g.p = P; g.ldp = C;
+            wudi_launch(WUDI_RHS, g, R, C, C);
+        }
+        // 5: the start
+        IsoSumParams sp;
+        sp.t = X;
+        ties_inputs(sp.in, k, d.in_dtype, d.n, d.finetune, d.base, true);
+        for (int i = 0; i < TIES_MAX_MODELS; ++i) sp.alpha[i] = (float)d.alpha[i < k ? i : 0];
+        sp.flags = flags + TIES_MAX_MODELS;
+        sp.chunks = stream_chunks((d.n + 7) / 8, 256, 2, 8);
+        be.template launch<KIsoSum>(stream_grid((d.n + 7) / 8, 256, sp.chunks), 256, 0, sp, stream);
+        if (d.iters > 0) {
+            be.memset(Mo, 0, d.n * 4, stream);
+            be.memset(Vo, 0, d.n * 4, stream);
+        }
+        // 7: the iteration
+        WudiSchedule sched(d.lr);
+        for (int it = 1; it <= d.iters; ++it) {
+            sched.next();
+            const bool report = it == 1 || it == d.iters;
+            WudiGemmParams g{};
+            g.a = X; g.lda = C; g.b = S; g.ldb = C; g.p = P; g.m = Mo; g.v = Vo; g.x = X; g.ldx = C; g.xn = Xn; g.ldp = C;
+            g.g = report ? Sh : nullptr;
+            sched.fill(g);
+            wudi_launch(WUDI_STEP, g, R, C, C);
+            if (report) iso_reduce<KIsoNorm>(Sh, nullptr, d.n, 0, part, res + (it == 1 ? 0 : 1));
+            std::swap(X, Xn);
+        }
+        // 8: the output
+        apply(X);
+        double rh[2];
+        be.d2h(rh, res, sizeof rh, stream);                         // the second synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (d.iters > 0) { R_.grad_sq_first = rh[0]; R_.grad_sq_last = d.iters == 1 ? rh[0] : rh[1]; }
+        return SMHIP_OK;
+    }
+    int wudi_gemm_probe(const smhip_wudi_gemm_desc& d) {
+        WudiGemmParams g{};
+        if (d.kind == WUDI_GRAM) wudi_delta(g.d, d.finetune, d.base, d.dtype, d.ld, d.K, d.N);
+        if (d.kind == WUDI_RHS) wudi_delta(g.d, d.finetune, d.base, d.dtype, d.ld, d.M, d.K);
+        g.a = d.a; g.lda = d.lda; g.b = d.b; g.ldb = d.ldb; g.first = d.first ? 1 : 0; g.w = d.w;
+        g.sh = d.sh; g.s = d.s; g.ldo = d.N; g.p = d.p; g.m = d.m; g.v = d.v; g.x = d.x; g.ldx = d.ldx; g.xn = d.xn; g.g = d.g; g.ldp = d.N;
+        if (d.kind == WUDI_STEP) {
+            WudiSchedule sched(d.lr);
+            for (int it = 0; it < d.t; ++it) sched.next();
+            sched.fill(g);
+        }
+        wudi_launch(d.kind, g, d.kind == WUDI_GRAM ? d.N : d.M, d.N, d.K);
         be.sync(stream);
         return SMHIP_OK;
     }

@@ -342,6 +342,19 @@ class TsvReport:
 
 
 @dataclass
+class WudiReport:
+    R: int = 0                                                       # rows
+    C: int = 0                                                       # the rest
+    active: List[int] = field(default_factory=list)                  # the entries with alpha_i != 0 and n_i != 0
+    n: List[float] = field(default_factory=list)                     # n_i = ||d_i||_F^2 of every entry (fp64, ordered)
+    w: List[float] = field(default_factory=list)                     # w_i = fp32(alpha_i / n_i), 0 for an inactive entry
+    iterations: int = 0                                              # Adam steps taken
+    zero: bool = False                                               # no active entry: merged = +0
+    grad_sq_first: float = 0.0                                       # sum g^2 of step 1 (fp64, ordered)
+    grad_sq_last: float = 0.0                                        # ... of the last step
+
+
+@dataclass
 class IsoReport:
     rows: int = 0
     cols: int = 0
@@ -1680,6 +1693,103 @@ class Engine:
         d.ca, d.cb, d.c, d.ldc = float(ca), float(cb), store.data_ptr(), ldc
         self._call(self.lib.dll.smhip_iso_gemm(self.ctx.h, C.byref(d), self._stream()))
         return store[:, :N]
+
+    # -- WUDI-Merging (task-vector-guided Adam) ----------------------------------------------------
+    def wudi_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
+                   base_out: torch.Tensor, *, iters: int = 300, lr: float = 1e-5, lam: float = 1.0, layer_name: str = "",
+                   want_delta: bool = False):
+        """WUDI merge of one tensor with at least two dimensions, viewed as ``[shape[0], rest] = R x C``
+        (``smhip_wudi_merge``; the function is stated in include/shardmerge_hip.h): the merged task vector ``X`` that
+        minimises ``sum_i ||(X - d_i) d_i^T||_F^2 / ||d_i||_F^2`` over the deltas ``d_i = finetune_i - base_i``, found by
+        ``iters`` Adam steps at ``lr`` from the sum of the deltas times ``alpha_i`` - one fp32 MFMA product ``X S`` per
+        step, ``S`` and ``P`` built once from the 16-bit inputs - and added, times ``lam``, onto ``base_out`` in its
+        dtype.  Alphas >= 0; an entry with ``alpha_i == 0`` or a zero delta is left out.  ``C <= 32768``.  Returns (out,
+        WudiReport[, the fp32 merged task vector before ``lam``]).  A NaN or Inf in a delta raises ValueError naming
+        ``layer_name``."""
+        layer_name = layer_name or "layer"
+        if not math.isfinite(float(lam)):
+            raise ValueError(f"wudi_merge: lam {lam} is not finite")
+        if not (0.0 < float(lr) <= 1.0):
+            raise ValueError(f"wudi_merge: lr {lr} is not in (0, 1]")
+        if isinstance(iters, bool) or not isinstance(iters, int) or not (0 <= iters <= _lib.WUDI_MAX_ITER):
+            raise ValueError(f"wudi_merge: iters must be an integer in 0..{_lib.WUDI_MAX_ITER}, not {iters!r}")
+        if any(not (float(a) >= 0.0) for a in alphas):
+            raise ValueError(f"wudi_merge: the alphas {list(alphas)} must be >= 0")
+        if base_out.ndim < 2:
+            raise ValueError(f"wudi_merge: {layer_name} has shape {list(base_out.shape)}; at least two dimensions expected")
+        rows = int(base_out.shape[0])
+        cols = int(base_out.numel() // rows) if rows else 0
+        if cols > _lib.WUDI_MAX_C:                   # (before anything is staged)
+            raise ValueError(f"wudi_merge: {layer_name} has shape {list(base_out.shape)}: {cols} columns, at most {_lib.WUDI_MAX_C}")
+        desc, rep, k = _lib.WudiDesc(), _lib.WudiReport(), len(finetunes)
+        keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "wudi_merge")
+        desc.n = bo.numel()
+        desc.rows, desc.cols, desc.lam, desc.lr, desc.iters = rows, cols, float(lam), float(lr), iters
+        if desc.n:
+            ws = self._xl_workspace(int(self.lib.dll.smhip_wudi_workspace(rows, cols)))
+            desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
+        self._run_delta_merge(self.lib.dll.smhip_wudi_merge, desc, rep, out, delta, layer_name)
+        report = WudiReport(R=rows, C=cols, active=[int(rep.active[q]) for q in range(rep.k_active)],
+                            n=[float(rep.n[i]) for i in range(k)], w=[float(rep.w[i]) for i in range(k)],
+                            iterations=int(rep.iterations), zero=bool(rep.zero), grad_sq_first=float(rep.grad_sq_first),
+                            grad_sq_last=float(rep.grad_sq_last))
+        return (out, report, delta) if want_delta else (out, report)
+
+    def wudi_gemm(self, kind: int, *, finetune: Optional[torch.Tensor] = None, base: Optional[torch.Tensor] = None,
+                  a: Optional[torch.Tensor] = None, b: Optional[torch.Tensor] = None, w: float = 1.0,
+                  s: Optional[torch.Tensor] = None, p: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
+                  v: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None, t: int = 1, lr: float = 1e-5,
+                  want_g: bool = False):
+        """one of the three kernels of ``wudi_merge`` alone (``smhip_wudi_gemm``; tests and tools).  2-D tensors whose rows
+        are contiguous are used where they lie - offset and pitch included - when they are on the engine's device.
+        kind 0, ``wudi_gram``: ``finetune``, ``base`` [K, N] -> (Sh, S) = (w d^T d, Sh or s + Sh).
+        kind 1, ``wudi_rhs``: ``finetune``, ``base`` [M, K], ``b`` [N, K] fp32 -> P = d b^T, or p + d b^T.
+        kind 2, ``wudi_step``: ``a`` [M, K], ``b`` [N, K], the planes ``p``, ``m``, ``v`` [M, N] and ``x`` (default: a)
+        -> (m', v', X'[, g]) of step ``t`` at ``lr``."""
+        def place(q, dtype=None):
+            if q is None:
+                return None
+            if (dtype is not None and q.dtype != dtype) or q.device != self.device or q.ndim != 2 or (q.shape[1] > 1 and q.stride(1) != 1):
+                return self._dev(q, dtype)
+            return q
+        pitch = lambda q: int(q.stride(0)) if q.shape[0] > 1 else int(q.shape[1])
+        plane = lambda q: self._dev(q, torch.float32).clone()
+        d = _lib.WudiGemmDesc()
+        d.kind, d.w, d.t, d.lr = int(kind), float(w), int(t), float(lr)
+        d.first = 1 if (s is None if kind == _lib.WUDI_GRAM else p is None) else 0          # no plane to add to: the first task
+        if kind != _lib.WUDI_STEP:
+            ft, bs = place(finetune), place(base)
+            if ft.dtype != bs.dtype or pitch(ft) != pitch(bs):
+                raise ValueError("wudi_gemm: finetune and base must share dtype and pitch")
+            d.finetune, d.base, d.dtype, d.ld = ft.data_ptr(), bs.data_ptr(), _DTYPE_CODE[ft.dtype], pitch(ft)
+        if kind == _lib.WUDI_GRAM:
+            K, N = ft.shape
+            sh = torch.zeros((N, N), dtype=torch.float32, device=self.device)
+            so = plane(s) if s is not None else torch.zeros_like(sh)
+            d.M, d.N, d.K, d.sh, d.s = N, N, K, sh.data_ptr(), so.data_ptr()
+            self._call(self.lib.dll.smhip_wudi_gemm(self.ctx.h, C.byref(d), self._stream()))
+            return sh, so
+        bv = place(b, torch.float32)
+        N = int(bv.shape[0])
+        d.b, d.ldb = bv.data_ptr(), pitch(bv)
+        if kind == _lib.WUDI_RHS:
+            M, K = ft.shape
+            po = plane(p) if p is not None else torch.zeros((M, N), dtype=torch.float32, device=self.device)
+            d.M, d.N, d.K, d.p = M, N, K, po.data_ptr()
+            self._call(self.lib.dll.smhip_wudi_gemm(self.ctx.h, C.byref(d), self._stream()))
+            return po
+        av = place(a, torch.float32)
+        xv = place(x, torch.float32) if x is not None else av
+        M, K = av.shape
+        if tuple(xv.shape) != (M, N):
+            raise ValueError(f"wudi_gemm: x must be [{M}, {N}], not {list(xv.shape)}")
+        pv, mo, vo = plane(p), plane(m), plane(v)
+        xn = torch.zeros((M, N), dtype=torch.float32, device=self.device)
+        g = torch.zeros_like(xn) if want_g else None
+        d.M, d.N, d.K, d.a, d.lda, d.x, d.ldx = M, N, K, av.data_ptr(), pitch(av), xv.data_ptr(), pitch(xv)
+        d.p, d.m, d.v, d.xn, d.g = pv.data_ptr(), mo.data_ptr(), vo.data_ptr(), xn.data_ptr(), g.data_ptr() if want_g else None
+        self._call(self.lib.dll.smhip_wudi_gemm(self.ctx.h, C.byref(d), self._stream()))
+        return (mo, vo, xn, g) if want_g else (mo, vo, xn)
 
     # -- WIDEN (weight disentanglement) ----------------------------------------------------------
     def widen_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
