@@ -1621,6 +1621,63 @@ typedef struct {
 int smhip_mx4_dequant(smhip_ctx* ctx, const smhip_mx4_dequant_desc* desc, void* out, void* stream);
 int smhip_mx4_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int on_device, void* stream);
 
+/* ---- NVFP4: a tensor as E2M1 codes, two to a byte, one E4M3 scale per block of 16 consecutive elements of a row and
+ *      ONE fp32 scale for the whole tensor - the 4-bit form ModelOpt writes (X.weight as U8 [R][C / 2], X.weight_scale
+ *      as F8_E4M3 [R][C / 16], X.weight_scale_2 as one F32; AS RECALLED, NOT CHECKED: PAPERS.md).  A DATA TYPE like
+ *      block-scaled FP8 and MXFP4 above: smhip_nv4_dequant rebuilds the tensor that every operator then takes.  The
+ *      reference has no such type; this section IS its definition.  The encodings are those above: e2m1_to_f32 and the
+ *      rounding of f32_to_e2m1 (smhip_mx4_fn), e4m3_to_f32 and f32_to_e4m3 (smhip_fp8_fn).  fp32(.) is ONE correctly
+ *      rounded IEEE fp32 operation, denormals kept; nothing is fused, reassociated or replaced by a reciprocal.
+ *      THE LAYOUT.  Only tensors with cols % 16 == 0 are converted; block b of row r holds its columns 16 b ...  Element
+ *      2 j of a row goes to the LOW nibble of code byte j and element 2 j + 1 to the HIGH nibble, as in MXFP4.
+ *      QUANT, smhip_nv4_quant:
+ *        1. A = max |fp32(x)| over the TENSOR, after the exact promotion: an integer maximum of the magnitude bits,
+ *           exact and order-free.
+ *        2. g = max(fp32(A / 2688), 2^-126); 2688 = 6 * 448, the largest element times the largest block scale.
+ *        3. Per block of 16: a = max |fp32(x)|; t = fp32(fp32(a / 6) / g); sc = f32_to_e4m3(t) (it rounds to nearest
+ *           even, subnormals included, and saturates at 448); d = fp32(e4m3_to_f32(sc) * g).
+ *        4. Each element: if d == 0 the code is the sign bit with magnitude 0.  Otherwise q = fp32(|fp32(x)| / d) and the
+ *           code is the sign bit and q rounded to the nearest E2M1 magnitude, ties to the even mantissa, saturating at 6.
+ *           -0 keeps its sign.
+ *        5. The report, integers only: blocks; zero_blocks (a == 0); zero_scale_blocks (a != 0 but d == 0: the block
+ *           is so small against A that its scale underflows, and every code of it is 0); saturated, the elements with
+ *           q >= 7 (they are stored as 6; it happens where t is an E4M3 subnormal that rounds down); nonfinite, the
+ *           blocks that hold a NaN or an Inf.
+ *      A NaN or an Inf in the input fails the call with SMHIP_ERR_NONFINITE; the outputs are then unspecified.
+ *      The error, derived: the widest gap of the grid is 2, so |x - dq| <= d (up to the roundings of q and of the
+ *      product, a factor 1 + 2^-20) where the element did not saturate.
+ *      DEQUANT, smhip_nv4_dequant: d = fp32(e4m3_to_f32(sc) * g); w = round_to(out_dtype, fp32(e2m1_to_f32(code) * d)) -
+ *      two fp32 products, then one round-to-nearest-even cast into bf16, fp16 or fp32.  A NaN scale code (0x7F, 0xFF)
+ *      fails the call with SMHIP_ERR_NONFINITE; a g that is not finite and positive with SMHIP_ERR_ARG.
+ *      rows cols == 0: nothing is written, the report is zero and g is 2^-126.  SMHIP_ERR_ARG: a block other than 16,
+ *      cols % 16 != 0, a bad dtype, a null or misaligned pointer, an output that overlaps an input or another output, a
+ *      tensor too large.  With x / out, codes and scales 16-byte aligned everything moves in 16-byte accesses; anything
+ *      else goes element by element and gives the same bytes.  Both synchronise the stream once, at their end (the
+ *      counters and g / the flag word are read back); quant does not read the maximum back between its two kernels.
+ *      Profile names: "nv4_amax", "nv4_quant"; "nv4_dequant". ---- */
+#define SMHIP_NV4_BLOCK 16
+typedef struct {
+    const void* x; int dtype;               /* device, [rows][cols], SMHIP_BF16 / F16 / F32 */
+    size_t rows, cols;                      /* cols % 16 == 0 */
+    int block;                              /* SMHIP_NV4_BLOCK */
+} smhip_nv4_quant_desc;
+typedef struct {
+    uint64_t blocks, zero_blocks, zero_scale_blocks, saturated, nonfinite;
+} smhip_nv4_report;
+/* codes: device uint8 [rows][cols / 2].  scales: device E4M3 bytes [rows][cols / 16].  global_scale: HOST, g.
+ * report (optional): HOST. */
+int smhip_nv4_quant(smhip_ctx* ctx, const smhip_nv4_quant_desc* desc, uint8_t* codes, uint8_t* scales, float* global_scale,
+                    smhip_nv4_report* report, void* stream);
+typedef struct {
+    const uint8_t* codes; const uint8_t* scales; /* device, as smhip_nv4_quant writes them */
+    float global_scale;                     /* g: finite and positive */
+    size_t rows, cols;
+    int block;                              /* SMHIP_NV4_BLOCK */
+    int out_dtype;                          /* SMHIP_BF16 / F16 / F32 */
+} smhip_nv4_dequant_desc;
+/* out: device, out_dtype, [rows][cols]; it must not overlap an input */
+int smhip_nv4_dequant(smhip_ctx* ctx, const smhip_nv4_dequant_desc* desc, void* out, void* stream);
+
 /* ---- EMR-Merging (Huang et al., "EMR-Merging: Tuning-Free High-Performance Model Merging", NeurIPS 2024; as recalled:
  *      PAPERS.md): ONE unified task vector is ELECTED from the finetunes' deltas - per element the sign of their sum and
  *      the largest magnitude among the entries of that sign - and every task gets a 1-bit MASK (where its own delta

@@ -310,6 +310,57 @@ def dequantize_mxfp4_command(model: str, out_dir: Path, storage_dir: Path, dtype
     _mx4_command("dequantize-mxfp4", model, out_dir, storage_dir, None, dtype, device, verbose)
 
 
+def _nv4_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str, verbose: bool):
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.extract import parse_modules
+        from .merge.mx4 import format_table
+        from .merge.nv4 import run_nv4
+        result = asyncio.run(run_nv4(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device))
+    except Exception as exc:
+        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"model: {out_dir}")
+
+
+@cli.command("quantize-nvfp4")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the NVFP4 checkpoint is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--modules", type=str, default=None,
+              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
+                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def quantize_nvfp4_command(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool):
+    """MODEL as an NVFP4 checkpoint: E2M1 weights, two to a byte, one E4M3 scale per 16 elements of a row, one fp32 scale per tensor.
+
+    DIR receives the shards (X.weight as U8 [R, C / 2], X.weight_scale as F8_E4M3 [R, C / 16], X.weight_scale_2 as one
+    F32), model.safetensors.index.json and a config.json with the quantization_config block; it can be named as a
+    finetune_merge entry of `merge` in place of MODEL.  A weight whose row length is no multiple of 16 is copied as it is.
+    """
+    _nv4_command("quantize-nvfp4", model, out_dir, storage_dir, modules, "bf16", device, verbose)
+
+
+@cli.command("dequantize-nvfp4")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the NVFP4 tensors are written in")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def dequantize_nvfp4_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
+    """The NVFP4 checkpoint MODEL written out in 16 or 32 bits: code times its block's scale times the tensor's scale.
+
+    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
+    """
+    _nv4_command("dequantize-nvfp4", model, out_dir, storage_dir, None, dtype, device, verbose)
+
+
 @cli.command("emr-task")
 @click.argument("model", type=str)
 @click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")

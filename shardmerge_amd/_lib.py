@@ -459,6 +459,26 @@ class Mx4DequantDesc(C.Structure):
                 ("block", C.c_int), ("out_dtype", C.c_int)]
 
 
+NV4_BLOCK = 16                                      # elements of a scale block of smhip_nv4_quant / smhip_nv4_dequant
+
+
+class Nv4QuantDesc(C.Structure):
+    """smhip_nv4_quant_desc"""
+    _fields_ = [("x", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t), ("block", C.c_int)]
+
+
+class Nv4Report(C.Structure):
+    """smhip_nv4_report"""
+    _fields_ = [("blocks", C.c_uint64), ("zero_blocks", C.c_uint64), ("zero_scale_blocks", C.c_uint64),
+                ("saturated", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
+class Nv4DequantDesc(C.Structure):
+    """smhip_nv4_dequant_desc"""
+    _fields_ = [("codes", C.c_void_p), ("scales", C.c_void_p), ("global_scale", C.c_float), ("rows", C.c_size_t),
+                ("cols", C.c_size_t), ("block", C.c_int), ("out_dtype", C.c_int)]
+
+
 DELLA_MAX_COLS = 32768        # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -563,6 +583,8 @@ class SmhipLibrary:
         d.smhip_mx4_quant.argtypes = [P, C.POINTER(Mx4QuantDesc), P, P, C.POINTER(Mx4Report), P]
         d.smhip_mx4_dequant.argtypes = [P, C.POINTER(Mx4DequantDesc), P, P]
         d.smhip_mx4_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
+        d.smhip_nv4_quant.argtypes = [P, C.POINTER(Nv4QuantDesc), P, P, C.POINTER(C.c_float), C.POINTER(Nv4Report), P]
+        d.smhip_nv4_dequant.argtypes = [P, C.POINTER(Nv4DequantDesc), P, P]
         d.smhip_emr_merge.argtypes = [P, C.POINTER(EmrDesc), P, P, C.POINTER(EmrReport), P]
         d.smhip_emr_mask.argtypes = [P, C.POINTER(EmrMaskDesc), P, P, C.POINTER(EmrMaskReport), P]
         d.smhip_emr_apply.argtypes = [P, C.POINTER(EmrApplyDesc), P, P]

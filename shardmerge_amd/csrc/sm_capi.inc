@@ -794,6 +794,41 @@ int smhip_mx4_fn(smhip_ctx* ctx, int op, const void* x, void* y, size_t n, int o
     SM_FINISH(ctx, ctx->pipe.delta.mx4_fn(op, x, y, n, on_device != 0));
 }
 
+// what smhip_nv4_quant and smhip_nv4_dequant share on top of dpack_check: whole blocks of 16 along a row
+static int nv4_check(smhip_ctx* ctx, const char* op, int dtype, size_t rows, size_t cols, int block,
+                     std::initializer_list<dpack_span> ins, std::initializer_list<dpack_span> outs) {
+    if (block != SMHIP_NV4_BLOCK)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": block size " + std::to_string(block) + " is not 16");
+    if (cols % SMHIP_NV4_BLOCK)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + std::to_string(cols) + " columns are no multiple of 16");
+    return dpack_check(ctx, op, dtype, rows, cols, SMHIP_DPACK_ROW, ins, outs);
+}
+
+int smhip_nv4_quant(smhip_ctx* ctx, const smhip_nv4_quant_desc* d, uint8_t* codes, uint8_t* scales, float* global_scale,
+                    smhip_nv4_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "nv4_quant: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols;
+    if (int rc = nv4_check(ctx, "nv4_quant", d->dtype, d->rows, d->cols, d->block, {{d->x, n * es, es}},
+                           {{codes, n / 2, 1}, {scales, n / SMHIP_NV4_BLOCK, 1}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.nv4_quant(*d, codes, scales, global_scale, report));
+}
+
+int smhip_nv4_dequant(smhip_ctx* ctx, const smhip_nv4_dequant_desc* d, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "nv4_dequant: null descriptor");
+    if (!(d->global_scale > 0.0f) || std::isinf(d->global_scale))
+        return ctx->pipe.fail(SMHIP_ERR_ARG, "nv4_dequant: the tensor's scale " + std::to_string(d->global_scale) + " is not finite and positive");
+    const size_t es = d->out_dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols;
+    if (int rc = nv4_check(ctx, "nv4_dequant", d->out_dtype, d->rows, d->cols, d->block,
+                           {{d->codes, n / 2, 1}, {d->scales, n / SMHIP_NV4_BLOCK, 1}}, {{out, n * es, es}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.nv4_dequant(*d, out));
+}
+
 int smhip_emr_merge(smhip_ctx* ctx, const smhip_emr_desc* d, void* out, float* delta_out, smhip_emr_report* report,
                     void* stream) {
     SM_GUARD(ctx);

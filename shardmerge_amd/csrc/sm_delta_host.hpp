@@ -1,5 +1,5 @@
 // sm_delta_host.hpp - host paths of the delta operators: TIES, DARE, Breadcrumbs, the geometric and Karcher-mean
-// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack, block-scaled FP8, MXFP4 and EMR-Merging (sm_delta.hpp
+// merges, SCE, DELLA, Consensus, the pairwise fusion, PCB, TSV, WIDEN, CABS, Iso-C, the task-vector statistics, the low-rank extraction, the delta pack, block-scaled FP8, MXFP4, NVFP4 and EMR-Merging (sm_delta.hpp
 // and the operators' headers; the functions are stated in shardmerge_hip.h; arguments checked in sm_capi.inc).
 // DeltaHost<B> is a member of Pipeline<B> (sm_pipeline.hpp): it launches on the pipeline's backend and stream, reports
 // through its error string and owns the one workspace buffer the operators share - they never run at once.
@@ -35,6 +35,7 @@
 #include "sm_eig.hpp"
 #include "sm_fp8.hpp"
 #include "sm_mx4.hpp"
+#include "sm_nv4.hpp"
 #include "sm_wudi.hpp"
 
 namespace smhip {
@@ -2025,6 +2026,56 @@ class DeltaHost {
         } else if (n) {
             be.template launch<KMx4Fn>((int)((n + 255) / 256), 256, LDS_SCRATCH_FLOATS * 4, p, stream);
         }
+        return SMHIP_OK;
+    }
+
+    // ---- NVFP4 (sm_nv4.hpp; smhip_nv4_quant, smhip_nv4_dequant).  Quant: two kernels on the stream, the tensor's maximum
+    // and the quantiser that reads its word - no readback between them; the head (the word, g, the four counters) is read
+    // back once.  Dequant: one kernel, the flag word read back.  Workspace: Nv4Head alone ----
+    struct Nv4Head { unsigned long long counts[NV4_COUNTERS]; uint32_t amax; float global; uint32_t flags[2]; };
+    int nv4_quant(const smhip_nv4_quant_desc& d, uint8_t* codes, uint8_t* scales, float* global_scale, smhip_nv4_report* rep) {
+        const size_t n = d.rows * d.cols, nblk = n / NV4_BLOCK, npair = (nblk + 1) / 2;
+        if (rep) *rep = smhip_nv4_report{};
+        if (global_scale) *global_scale = u2f(NV4_MIN_GLOBAL);   // (what a tensor of zeros gets)
+        if (nblk == 0) return SMHIP_OK;
+        Nv4Head* w;
+        if (int rc = plain_workspace(w)) return rc;
+        Nv4AmaxParams a;
+        a.x = d.x; a.dtype = d.dtype; a.n = n; a.amax = &w->amax; a.vec = aligned16(d.x) ? 1 : 0;
+        a.chunks = stream_chunks(n / 8, NV4_THREADS, 2, 8);
+        be.template launch<KNv4Amax>(stream_grid(n / 8, NV4_THREADS, a.chunks), NV4_THREADS, (LDS_SCRATCH_FLOATS + 4) * 4, a, stream);
+        Nv4QuantParams p;
+        p.x = d.x; p.dtype = d.dtype; p.nblk = nblk; p.codes = codes; p.scale = scales; p.amax = &w->amax; p.global = &w->global;
+        p.counts = w->counts;
+        p.vec = (aligned16(d.x) && aligned16(codes) && aligned16(scales)) ? 1 : 0;
+        p.chunks = stream_chunks(npair, NV4_THREADS, 1, 8);
+        be.template launch<KNv4Quant>(stream_grid(npair, NV4_THREADS, p.chunks), NV4_THREADS, (LDS_SCRATCH_FLOATS + NV4_LDS_FLOATS) * 4, p, stream);
+        Nv4Head host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
+        if (global_scale) *global_scale = host.global;
+        if (rep) {
+            rep->blocks = nblk; rep->zero_blocks = host.counts[NV4_ZERO_BLOCKS]; rep->zero_scale_blocks = host.counts[NV4_ZERO_SCALE];
+            rep->saturated = host.counts[NV4_SATURATED]; rep->nonfinite = host.counts[NV4_NONFINITE];
+        }
+        if (host.amax >= 0x7f800000u) return fail(SMHIP_ERR_NONFINITE, "nv4_quant: NaN or Inf in the tensor");
+        return SMHIP_OK;
+    }
+    int nv4_dequant(const smhip_nv4_dequant_desc& d, void* out) {
+        const size_t nblk = d.rows * d.cols / NV4_BLOCK, npair = (nblk + 1) / 2;
+        if (nblk == 0) return SMHIP_OK;
+        Nv4Head* w;
+        if (int rc = plain_workspace(w)) return rc;
+        Nv4DequantParams p;
+        p.codes = d.codes; p.scale = d.scales; p.global = d.global_scale; p.nblk = nblk; p.out = out; p.out_dtype = d.out_dtype;
+        p.flags = w->flags;
+        p.vec = (aligned16(d.codes) && aligned16(d.scales) && aligned16(out)) ? 1 : 0;
+        p.chunks = stream_chunks(npair, NV4_THREADS, 1, 8);
+        be.template launch<KNv4Dequant>(stream_grid(npair, NV4_THREADS, p.chunks), NV4_THREADS, (LDS_SCRATCH_FLOATS + NV4_LDS_FLOATS) * 4, p, stream);
+        Nv4Head host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0] & NV4_FLAG_NAN_SCALE) return fail(SMHIP_ERR_NONFINITE, "nv4_dequant: a NaN scale code (0x7F or 0xFF) in the tensor");
         return SMHIP_OK;
     }
 

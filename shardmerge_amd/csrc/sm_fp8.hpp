@@ -21,41 +21,17 @@
 //   fp8_fn        the probe behind smhip_fp8_fn: the two conversions alone over a flat array.
 #pragma once
 #include "sm_delta.hpp"
+#include "sm_minifloat.hpp"
 
 namespace smhip {
 
 constexpr int FP8_BLOCK = 128;                    // rows and columns of a scale block
 constexpr int FP8_THREADS = 256;                  // work-group of fp8_quant: 16 octet columns x 16 rows, 8 times
-constexpr uint32_t FP8_MAX_KEY = 0x43e00000u;     // 448.0f, the largest finite E4M3 value
 constexpr uint32_t FP8_MIN_SCALE = 0x00800000u;   // 2^-126, the smallest normal fp32 value
 enum { FP8_ENCODE = 0, FP8_DECODE = 1 };
 enum { FP8_FLAG_NONFINITE = 1u, FP8_FLAG_NAN_CODE = 2u };
 
-// ---- the encoding: OCP E4M3 "fn" - bias 7, no infinities, NaN is S.1111.111, largest finite value 448 ----
-// exact.  A NaN code gives the quiet NaN torch's conversion gives (sign | 0x7ff00000)
-SM_HD float e4m3_to_f32(uint32_t code) {
-    const uint32_t s = (code & 0x80u) << 24, a = code & 0x7fu;
-    if (a == 0x7fu) return u2f(s | 0x7ff00000u);
-    if (a < 8u) {                                                   // subnormal: m 2^-9 (and the zeros)
-        const float v = (float)(int)a * 0.001953125f;
-        return u2f(s | f2u(v));
-    }
-    return u2f(s | ((a << 20) + 0x3c000000u));                      // exponent e - 7 + 127, three mantissa bits on top
-}
-// round to nearest even on the E4M3 grid, subnormals included; saturating: a |v| that rounds above 448 gives +-448, an
-// Inf too; NaN gives 0x7F
-SM_HD uint32_t f32_to_e4m3(float v) {
-    const uint32_t u = f2u(v), s = (u >> 24) & 0x80u;
-    uint32_t a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return 0x7fu;
-    if (a >= FP8_MAX_KEY) return s | 0x7eu;                         // [448, 464] rounds to 448; beyond it the clamp
-    if (a < 0x3c800000u) {                                          // |v| < 2^-6: the subnormal grid of step 2^-9.
-        // 2^14 has an ulp of 2^-9: ONE rounded addition leaves RNE(|v| 2^9) in the low mantissa bits (8: 2^-6 itself)
-        return s | (f2u(aten_fadd_(u2f(a), 16384.0f)) - 0x46800000u);
-    }
-    a += 0x7ffffu + ((a >> 20) & 1u);                               // RNE to three mantissa bits; a carry moves the exponent
-    return s | ((a >> 20) - 960u);                                  // (127 - 7) << 3
-}
+// (the encoding - e4m3_to_f32, f32_to_e4m3, FP8_MAX_KEY - is sm_minifloat.hpp's: NVFP4's block scales share it)
 
 // the scale of a block from its maximum's key a (a finite magnitude): max(a / 448, 2^-126), one rounded fp32 division
 SM_HD float fp8_scale_of(uint32_t a) {

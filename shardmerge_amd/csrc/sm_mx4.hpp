@@ -28,7 +28,7 @@
 // A pointer that is not 16-byte aligned sends a call element by element through the same conversions; the last,
 // partial round stores its scale bytes one by one where 16 do not fit.
 #pragma once
-#include "sm_common.hpp"
+#include "sm_minifloat.hpp"
 #include "sm_tag.hpp"
 
 namespace smhip {
@@ -41,29 +41,7 @@ enum { MX4_ZERO_BLOCKS = 0, MX4_SATURATED = 1, MX4_NONFINITE = 2, MX4_COUNTERS =
 enum { MX4_FLAG_NAN_SCALE = 1u };
 
 // ---- the encodings ----
-// E2M1: sign, two exponent bits of bias 1, one mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}; no NaN, no infinity.
-// exact; the bits are built from the three fields
-SM_HD uint32_t e2m1_bits(uint32_t code) {
-    const uint32_t s = (code & 8u) << 28, e = (code >> 1) & 3u, m = code & 1u;
-    return s | (e ? ((e + 126u) << 23) | (m << 22) : m * 0x3f000000u);
-}
-SM_HD float e2m1_to_f32(uint32_t code) { return u2f(e2m1_bits(code)); }
-// the code (0..7) of a magnitude given as non-negative fp32 bits, and whether it rounds above 6: round to nearest, ties
-// to the even mantissa.  From 1 up one integer addition rounds to one mantissa bit (a carry moves the exponent); below
-// 1 the grid is {0, 0.5, 1}: a tie at 0.25 goes to 0 and one at 0.75 to 1.  Everything from 7 up, Inf and NaN included,
-// is saturated to 6
-SM_HD uint32_t e2m1_of_bits(uint32_t a, uint32_t* sat) {
-    const uint32_t r = ((a + 0x1fffffu + ((a >> 22) & 1u)) >> 22) - 252u;        // (a >= 1.0: r >= 2)
-    const uint32_t low = (a > 0x3e800000u ? 1u : 0u) + (a >= 0x3f400000u ? 1u : 0u);
-    const uint32_t c = a < 0x3f800000u ? low : r;
-    *sat = c > 7u ? 1u : 0u;
-    return c > 7u ? 7u : c;
-}
-SM_HD uint32_t f32_to_e2m1(float v) {
-    uint32_t sat;
-    const uint32_t u = f2u(v);
-    return ((u >> 28) & 8u) | e2m1_of_bits(u & 0x7fffffffu, &sat);
-}
+// E2M1 (e2m1_bits, e2m1_to_f32, e2m1_of_bits, f32_to_e2m1) is sm_minifloat.hpp's: NVFP4's elements share it.
 // E8M0: 2^(code - 127); 0xFF is NaN.  Code 0 is 2^-127, an fp32 denormal
 SM_HD float e8m0_to_f32(uint32_t s) { return u2f(s == 0xffu ? 0x7fc00000u : (s ? s << 23 : 0x00400000u)); }
 // the scale code of a block from its maximum's magnitude bits: max(E - 2, 0) with E the biased exponent field, that is

@@ -205,6 +205,11 @@ def config_stamp(config: MergeConfig) -> str:
             if (ident := mx4_identity(Path(config.storage_path) / m.model)) is not None}   # an MXFP4 checkpoint's: its shard headers
     if mx4s:
         doc["mx4_models"] = mx4s
+    from .nv4model import nv4_identity
+    nv4s = {m.model: ident for m in config.finetune_merge
+            if (ident := nv4_identity(Path(config.storage_path) / m.model)) is not None}   # an NVFP4 checkpoint's: its shard headers
+    if nv4s:
+        doc["nv4_models"] = nv4s
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 

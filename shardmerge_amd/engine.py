@@ -294,6 +294,17 @@ class Mx4Report:
     nonfinite: int = 0                                               # blocks that hold a NaN or an Inf
 
 
+@dataclass
+class Nv4Report:
+    rows: int = 0
+    cols: int = 0
+    blocks: int = 0                                                  # scale blocks of 16 elements
+    zero_blocks: int = 0                                             # blocks of zeros
+    zero_scale_blocks: int = 0                                       # blocks that are not zero but whose scale underflows: zero codes
+    saturated: int = 0                                               # elements whose scaled magnitude is 7 or more (stored as 6)
+    nonfinite: int = 0                                               # blocks that hold a NaN or an Inf
+
+
 def _shape_rows(t: torch.Tensor) -> Tuple[int, int]:
     """the delta pack's view of a tensor: R = shape[0] rows of the rest; a 0-D or 1-D tensor is one row"""
     if t.ndim <= 1:
@@ -853,6 +864,65 @@ class Engine:
         if on_device and self.device.type != "cpu":
             torch.cuda.synchronize(self.device)
         return y.cpu()
+
+    # -- NVFP4 (E2M1 codes, two to a byte, one E4M3 scale per 16 elements of a row, one fp32 scale per tensor) --
+    def nv4_quant(self, x: torch.Tensor, *, layer_name: str = ""):
+        """A 2-D tensor with ``C % 16 == 0`` as NVFP4 (``smhip_nv4_quant``; the function is stated in
+        include/shardmerge_hip.h): the tensor's scale ``g = max(amax / 2688, 2^-126)``, per block of 16 elements of a
+        row the E4M3 scale ``e4m3(amax_block / 6 / g)`` and the E2M1 codes of ``x / (scale g)``, element ``2 j`` in the
+        low nibble of byte ``j``.  Returns ``(codes uint8 [R, C / 2], scales float8_e4m3fn [R, C / 16], global_scale - a
+        float32 CPU tensor of shape [] -, Nv4Report)``.  A NaN or Inf in ``x`` raises ValueError naming ``layer_name``."""
+        who = layer_name or "tensor"
+        if x.ndim != 2:
+            raise ValueError(f"nv4_quant: {who} is {list(x.shape)}; a 2-D tensor expected")
+        if x.dtype not in _DTYPE_CODE:
+            raise ValueError(f"nv4_quant: {who} is {x.dtype}; bf16, f16 or f32 expected")
+        rows, cols = x.shape
+        if cols % _lib.NV4_BLOCK:
+            raise ValueError(f"nv4_quant: {who} is {list(x.shape)}; its {cols} columns are no multiple of {_lib.NV4_BLOCK}")
+        xs = self._dev(x)
+        codes = torch.empty((rows, cols // 2), dtype=torch.uint8, device=self.device)
+        sc = torch.empty((rows, cols // _lib.NV4_BLOCK), dtype=torch.uint8, device=self.device)
+        desc = _lib.Nv4QuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, _lib.NV4_BLOCK)
+        rep, g = _lib.Nv4Report(), C.c_float()
+        self._mx4_check(self.lib.dll.smhip_nv4_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(), C.byref(g),
+                                                     C.byref(rep), self._stream()), "Non-finite value", layer_name)
+        report = Nv4Report(rows=rows, cols=cols, blocks=int(rep.blocks), zero_blocks=int(rep.zero_blocks),
+                           zero_scale_blocks=int(rep.zero_scale_blocks), saturated=int(rep.saturated), nonfinite=int(rep.nonfinite))
+        return codes, sc.view(torch.float8_e4m3fn), torch.tensor(g.value, dtype=torch.float32), report
+
+    def nv4_dequant(self, codes: torch.Tensor, scales: torch.Tensor, global_scale, dtype: torch.dtype = torch.bfloat16, *,
+                    out: Optional[torch.Tensor] = None, layer_name: str = "") -> torch.Tensor:
+        """the tensor an NVFP4 tensor stands for: ``e2m1_to_f32(code) * (e4m3_to_f32(scale) * global_scale)``, two fp32
+        products, then one rounding into ``dtype`` (``smhip_nv4_dequant``).  codes: uint8 [R, C / 2]; scales:
+        float8_e4m3fn (or its bytes as uint8) [R, C / 16]; global_scale: a float or a one-element tensor; out
+        (optional): a contiguous ``dtype`` [R, C] tensor on the engine's device that overlaps neither.  A NaN scale
+        code, or a global scale that is not finite and positive, raises ValueError naming ``layer_name``."""
+        who = layer_name or "tensor"
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"nv4_dequant: dtype of {who} is {dtype}; bf16, f16 or f32 expected")
+        if codes.dtype != torch.uint8 or codes.ndim != 2 or (2 * codes.shape[1]) % _lib.NV4_BLOCK:
+            raise ValueError(f"nv4_dequant: codes of {who} are {codes.dtype} {list(codes.shape)}; uint8 [R, C / 2] with "
+                             f"C a multiple of {_lib.NV4_BLOCK} expected")
+        rows, cols = codes.shape[0], 2 * codes.shape[1]
+        want = (rows, cols // _lib.NV4_BLOCK)
+        if scales.dtype not in (torch.float8_e4m3fn, torch.uint8) or tuple(scales.shape) != want:
+            raise ValueError(f"nv4_dequant: scales of {who} are {scales.dtype} {list(scales.shape)}; "
+                             f"float8_e4m3fn {list(want)} expected for codes {list(codes.shape)}")
+        if isinstance(global_scale, torch.Tensor):
+            if global_scale.numel() != 1:
+                raise ValueError(f"nv4_dequant: the global scale of {who} is {list(global_scale.shape)}; one value expected")
+            global_scale = float(global_scale.detach().float().cpu().reshape(()))
+        cs, sc = self._dev(codes), self._dev(scales.view(torch.uint8))
+        if out is None:
+            out = torch.empty((rows, cols), dtype=dtype, device=self.device)
+        elif out.dtype != dtype or tuple(out.shape) != (rows, cols) or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"nv4_dequant: out of {who} is {out.dtype} {list(out.shape)} on {out.device}; a contiguous "
+                             f"{dtype} {[rows, cols]} tensor on {self.device} expected")
+        desc = _lib.Nv4DequantDesc(cs.data_ptr(), sc.data_ptr(), global_scale, rows, cols, _lib.NV4_BLOCK, _DTYPE_CODE[dtype])
+        self._mx4_check(self.lib.dll.smhip_nv4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
+                        "NaN scale code", layer_name)
+        return out
 
     # -- EMR-Merging: the unified model, a task's mask and rescaler, the task's tensor --------------
     def emr_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], base_out: torch.Tensor, *,

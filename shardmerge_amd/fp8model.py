@@ -96,7 +96,11 @@ class Fp8Model:
 
 
 def fp8_model(uri: str, path: Path, weight_map: Dict[str, str]) -> Optional[Fp8Model]:
-    """the Fp8Model of a full model directory, None when no shard holds an F8_E4M3 tensor"""
+    """the Fp8Model of a full model directory, None when no shard holds an F8_E4M3 tensor - or when the directory is an
+    NVFP4 checkpoint (nv4model.py), whose block scales are F8_E4M3 tensors"""
+    from .nv4model import nv4_model
+    if nv4_model(uri, path, weight_map) is not None:
+        return None
     m = Fp8Model(uri, path, weight_map)
     return m if m.scale_keys else None
 

@@ -26,6 +26,7 @@ from .deltapack import DeltaPack, is_pack_dir
 from .emrpack import EmrPack, is_emr_dir
 from .fp8model import Fp8Model, fp8_model
 from .mx4model import Mx4Model, mx4_model
+from .nv4model import Nv4Model, nv4_model
 
 logger = logging.getLogger(__name__)
 
@@ -74,6 +75,7 @@ class LocalModelIndex:
         self.emrs: Dict[str, EmrPack] = {}             # EMR pack directories (emrpack.py), by model uri
         self.fp8s: Dict[str, Fp8Model] = {}            # block-scaled FP8 checkpoints (fp8model.py), by model uri
         self.mx4s: Dict[str, Mx4Model] = {}            # MXFP4 checkpoints (mx4model.py), by model uri
+        self.nv4s: Dict[str, Nv4Model] = {}            # NVFP4 checkpoints (nv4model.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -115,6 +117,12 @@ class LocalModelIndex:
             index = json.load(fh)
         self.model_indexes[model_uri] = index
         self._ordered_weights[model_uri] = order_weights(list(index["weight_map"].keys()))
+        nv4 = nv4_model(model_uri, self.storage_path / model_uri, index["weight_map"])
+        if nv4 is not None:
+            # an NVFP4 checkpoint: a config says so and its coded weights come with both scales; tested before FP8, which
+            # its F8_E4M3 block scales would otherwise claim
+            self.nv4s[model_uri] = nv4
+            logger.info(f"Model {model_uri}: NVFP4 checkpoint, {len(nv4.scale_keys)} two-level-scaled E2M1 tensors")
         fp8 = fp8_model(model_uri, self.storage_path / model_uri, index["weight_map"])
         if fp8 is not None:
             # a block-scaled FP8 checkpoint: a full model whose E4M3 tensors come with a scale tensor each
@@ -142,6 +150,10 @@ class LocalModelIndex:
     def fp8(self, model_uri: str) -> Optional[Fp8Model]:
         """the block-scaled FP8 checkpoint registered under this uri, None for anything else"""
         return self.fp8s.get(model_uri)
+
+    def nv4(self, model_uri: str) -> Optional[Nv4Model]:
+        """the NVFP4 checkpoint registered under this uri, None for anything else"""
+        return self.nv4s.get(model_uri)
 
     def mx4(self, model_uri: str) -> Optional[Mx4Model]:
         """the MXFP4 checkpoint registered under this uri, None for anything else"""
