@@ -1678,6 +1678,71 @@ typedef struct {
 /* out: device, out_dtype, [rows][cols]; it must not overlap an input */
 int smhip_nv4_dequant(smhip_ctx* ctx, const smhip_nv4_dequant_desc* desc, void* out, void* stream);
 
+/* ---- GPTQ-layout INT4: a Linear X with W [R = out][C = in] as group-quantised 4-bit integers in the tensor layout of
+ *      GPTQ checkpoints (AS RECALLED, NOT CHECKED: PAPERS.md), group size g = 32, 64 or 128 along the input dimension:
+ *        X.qweight I32 [C / 8][R]      word (j, o) = sum over e = 0..7 of q[o][8 j + e] << 4 e
+ *        X.scales  F16 [C / g][R]      s16 of group G = i / g and row o
+ *        X.qzeros  I32 [C / g][R / 8]  word (G, w) = sum over e of ((z[G][8 w + e] - 1) & 15) << 4 e - the v1 "minus
+ *                                      one" convention; the reader takes z = (stored + 1) & 15
+ *        X.g_idx   I32 [C]             i / g
+ *      and W[o][i] = s16[i / g][o] * (q[o][i] - z[i / g][o]).  The weight is stored TRANSPOSED and packed along the
+ *      input dimension, the zero-points along the output dimension.  A DATA TYPE like block-scaled FP8, MXFP4 and NVFP4
+ *      above; the reference has no such type and this section IS its definition.  fp32(.) is ONE correctly rounded IEEE
+ *      fp32 operation; nothing is fused, reassociated or replaced by a reciprocal; rint rounds to the nearest integer,
+ *      ties to even.  Only tensors with rows % 8 == 0 and cols % g == 0 are converted.
+ *      QUANT, smhip_gptq_quant, is ROUND TO NEAREST, asymmetric - NOT the GPTQ solver, which needs calibration data.
+ *      Per group G and row o, over the group's g elements after the exact promotion to fp32:
+ *        1. mn = min(min x, 0), mx = max(max x, 0): exact and order-free.
+ *        2. s = fp32(fp32(mx - mn) / 15).
+ *        3. s16 = s rounded to fp16 (nearest even), then clamped into [2^-24, 65504]: a group of zeros gets 2^-24 and
+ *           nothing divides by zero.
+ *        4. z = clamp(rint(fp32(fp32(0 - mn) / s16)), 0, 15).
+ *        5. q = clamp(t, 0, 15) with t = fp32(rint(fp32(x / s16)) + z).
+ *        6. The report, integers only: groups = R C / g; zero_groups (mn == mx == 0); scale_clamped (a group that is not
+ *           of zeros whose s16 a clamp moved); clipped, the ELEMENTS whose t left 0 .. 15; nonfinite, the groups that
+ *           hold a NaN or an Inf.
+ *      A NaN or an Inf in the input fails the call with SMHIP_ERR_NONFINITE; the outputs are then unspecified.  g_idx is
+ *      written as i / g.
+ *      DEQUANT, smhip_gptq_dequant: w = round_to(out_dtype, fp32(float(q - z) * s16)) - the difference is an exact
+ *      integer, one product (exact: 5 bits by 11), one round-to-nearest-even cast into bf16, fp16 or fp32.  It decodes
+ *      whatever zero-points are stored, so a symmetric checkpoint (z = 8, zero words 0x77777777) reads as well.  A g_idx
+ *      with g_idx[i] != i / g (act-order) fails the call with SMHIP_ERR_ARG, a NaN or Inf scale with
+ *      SMHIP_ERR_NONFINITE.
+ *      THE ERROR, derived, on the fp32 value dq = (q - z) s16, for s16 that no clamp moved.  Let t' = x / s16 exactly.
+ *      NOT CLIPPED (t in 0 .. 15): dq = rint(fp32(t')) s16 and |fp32(t') - t'| <= 2^-24 |t'| with |t'| < 16, so
+ *      |x - dq| <= s16 (1/2 + 2^-20).  CLIPPED: x lies in [mn, mx] and the grid spans [-z s16, (15 - z) s16].  Below,
+ *      z = rint(-mn / s16) where that is at most 15, so mn >= -(z + 1/2) s16; where it is clamped to 15, -mn <= 15 s gives
+ *      mn >= -15 s16 - 15 (s - s16).  Above, mx - (15 - z) s16 = (mn + z s16) + 15 (s - s16) <= s16 / 2 + 15 |s - s16|.
+ *      So |x - dq| <= s16 / 2 + 15 |s - s16|, and |s - s16| <= 2^-11 s16 where s16 is a normal fp16 number (half an
+ *      ulp): |x - dq| <= s16 (1/2 + 15 * 2^-11).  Where s16 is an fp16 subnormal |s - s16| <= 2^-25 instead.  Both
+ *      bounds take the roundings of mx - mn, of the division by 15 and of the quotient on top: a factor 1 + 2^-17.
+ *      Where the upper clamp moved s16 (s > 65504) a clipped element has no bound.
+ *      rows cols == 0: nothing is written and the report is zero.  SMHIP_ERR_ARG: a group size other than 32, 64 or 128,
+ *      rows % 8 != 0, cols % g != 0, a bad dtype, a null or misaligned pointer, an output that overlaps an input or
+ *      another output, a tensor too large.  With x / out and scales 16-byte aligned they move in 16-byte accesses;
+ *      anything else goes element by element and gives the same bytes.  Both synchronise the stream once, at their end
+ *      (the counters / the flag word are read back).  Profile names: "gptq_quant"; "gptq_dequant". ---- */
+typedef struct {
+    const void* x; int dtype;               /* device, [rows][cols], SMHIP_BF16 / F16 / F32 */
+    size_t rows, cols;                      /* rows % 8 == 0, cols % group_size == 0 */
+    int group_size;                         /* 32, 64 or 128 */
+} smhip_gptq_quant_desc;
+typedef struct {
+    uint64_t groups, zero_groups, scale_clamped, clipped, nonfinite;
+} smhip_gptq_report;
+/* qweight: device int32 [cols / 8][rows].  qzeros: device int32 [cols / g][rows / 8].  scales: device fp16 bits
+ * [cols / g][rows].  g_idx: device int32 [cols].  report (optional): HOST. */
+int smhip_gptq_quant(smhip_ctx* ctx, const smhip_gptq_quant_desc* desc, int32_t* qweight, int32_t* qzeros, uint16_t* scales,
+                     int32_t* g_idx, smhip_gptq_report* report, void* stream);
+typedef struct {
+    const int32_t* qweight; const int32_t* qzeros; const uint16_t* scales; const int32_t* g_idx;   /* device, as above */
+    size_t rows, cols;
+    int group_size;                         /* 32, 64 or 128 */
+    int out_dtype;                          /* SMHIP_BF16 / F16 / F32 */
+} smhip_gptq_dequant_desc;
+/* out: device, out_dtype, [rows][cols]; it must not overlap an input */
+int smhip_gptq_dequant(smhip_ctx* ctx, const smhip_gptq_dequant_desc* desc, void* out, void* stream);
+
 /* ---- EMR-Merging (Huang et al., "EMR-Merging: Tuning-Free High-Performance Model Merging", NeurIPS 2024; as recalled:
  *      PAPERS.md): ONE unified task vector is ELECTED from the finetunes' deltas - per element the sign of their sum and
  *      the largest magnitude among the entries of that sign - and every task gets a 1-bit MASK (where its own delta

@@ -361,6 +361,60 @@ def dequantize_nvfp4_command(model: str, out_dir: Path, storage_dir: Path, dtype
     _nv4_command("dequantize-nvfp4", model, out_dir, storage_dir, None, dtype, device, verbose)
 
 
+def _gptq_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str,
+                  verbose: bool, group_size: int = 128):
+    setup_logging(verbose)
+    from .constants import tune_hip_queues
+    tune_hip_queues()                   # before the first GPU call, as merge does
+    try:
+        from .merge.extract import parse_modules
+        from .merge.gptq import run_gptq
+        from .merge.mx4 import format_table
+        result = asyncio.run(run_gptq(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device, group_size))
+    except Exception as exc:
+        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
+        traceback.print_exc()
+        raise click.Abort()
+    click.echo(format_table(result))
+    click.echo(f"model: {out_dir}")
+
+
+@cli.command("quantize-gptq")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the GPTQ checkpoint is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--group-size", type=click.Choice(["32", "64", "128"]), default="128", help="Input columns that share a scale and a zero-point")
+@click.option("--modules", type=str, default=None,
+              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
+                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def quantize_gptq_command(model: str, out_dir: Path, storage_dir: Path, group_size: str, modules: Optional[str], device: str, verbose: bool):
+    """MODEL as a GPTQ-layout INT4 checkpoint, quantised by ROUND TO NEAREST (asymmetric) - not by the GPTQ solver.
+
+    DIR receives the shards (X.qweight as I32 [C / 8, R], X.qzeros as I32 [C / g, R / 8], X.scales as F16 [C / g, R] and
+    X.g_idx as I32 [C] in place of X.weight), model.safetensors.index.json and a config.json with the
+    quantization_config block; it can be named as a finetune_merge entry of `merge` in place of MODEL.  A weight whose
+    rows are no multiple of 8 or whose columns are no multiple of the group size is copied as it is.
+    """
+    _gptq_command("quantize-gptq", model, out_dir, storage_dir, modules, "bf16", device, verbose, int(group_size))
+
+
+@cli.command("dequantize-gptq")
+@click.argument("model", type=str)
+@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
+@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the GPTQ tensors are written in")
+@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
+@click.option("--verbose", is_flag=True, help="Enable verbose logging")
+def dequantize_gptq_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
+    """The GPTQ checkpoint MODEL written out in 16 or 32 bits: X.weight = (code - zero-point) times its group's scale.
+
+    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
+    """
+    _gptq_command("dequantize-gptq", model, out_dir, storage_dir, None, dtype, device, verbose)
+
+
 @cli.command("emr-task")
 @click.argument("model", type=str)
 @click.option("--base", required=True, type=str, help="The base model MODEL was finetuned from (under the storage directory)")

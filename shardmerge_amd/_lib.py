@@ -479,6 +479,26 @@ class Nv4DequantDesc(C.Structure):
                 ("cols", C.c_size_t), ("block", C.c_int), ("out_dtype", C.c_int)]
 
 
+GPTQ_GROUPS = (32, 64, 128)                         # the group sizes of smhip_gptq_quant / smhip_gptq_dequant
+
+
+class GptqQuantDesc(C.Structure):
+    """smhip_gptq_quant_desc"""
+    _fields_ = [("x", C.c_void_p), ("dtype", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t), ("group_size", C.c_int)]
+
+
+class GptqReport(C.Structure):
+    """smhip_gptq_report"""
+    _fields_ = [("groups", C.c_uint64), ("zero_groups", C.c_uint64), ("scale_clamped", C.c_uint64),
+                ("clipped", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
+class GptqDequantDesc(C.Structure):
+    """smhip_gptq_dequant_desc"""
+    _fields_ = [("qweight", C.c_void_p), ("qzeros", C.c_void_p), ("scales", C.c_void_p), ("g_idx", C.c_void_p),
+                ("rows", C.c_size_t), ("cols", C.c_size_t), ("group_size", C.c_int), ("out_dtype", C.c_int)]
+
+
 DELLA_MAX_COLS = 32768        # the longest row smhip_della_merge ranks (a row is sorted in LDS)
 
 
@@ -585,6 +605,8 @@ class SmhipLibrary:
         d.smhip_mx4_fn.argtypes = [P, I, P, P, C.c_size_t, I, P]
         d.smhip_nv4_quant.argtypes = [P, C.POINTER(Nv4QuantDesc), P, P, C.POINTER(C.c_float), C.POINTER(Nv4Report), P]
         d.smhip_nv4_dequant.argtypes = [P, C.POINTER(Nv4DequantDesc), P, P]
+        d.smhip_gptq_quant.argtypes = [P, C.POINTER(GptqQuantDesc), P, P, P, P, C.POINTER(GptqReport), P]
+        d.smhip_gptq_dequant.argtypes = [P, C.POINTER(GptqDequantDesc), P, P]
         d.smhip_emr_merge.argtypes = [P, C.POINTER(EmrDesc), P, P, C.POINTER(EmrReport), P]
         d.smhip_emr_mask.argtypes = [P, C.POINTER(EmrMaskDesc), P, P, C.POINTER(EmrMaskReport), P]
         d.smhip_emr_apply.argtypes = [P, C.POINTER(EmrApplyDesc), P, P]

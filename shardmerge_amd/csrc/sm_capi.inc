@@ -829,6 +829,42 @@ int smhip_nv4_dequant(smhip_ctx* ctx, const smhip_nv4_dequant_desc* d, void* out
     SM_FINISH(ctx, ctx->pipe.delta.nv4_dequant(*d, out));
 }
 
+// what smhip_gptq_quant and smhip_gptq_dequant share on top of dpack_check: the group size and the shape rule
+static int gptq_check(smhip_ctx* ctx, const char* op, int dtype, size_t rows, size_t cols, int g,
+                      std::initializer_list<dpack_span> ins, std::initializer_list<dpack_span> outs) {
+    if (g != 32 && g != 64 && g != 128)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": group size " + std::to_string(g) + " is not 32, 64 or 128");
+    if (rows % 8)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + std::to_string(rows) + " rows are no multiple of 8");
+    if (cols % (size_t)g)
+        return ctx->pipe.fail(SMHIP_ERR_ARG, std::string(op) + ": " + std::to_string(cols) + " columns are no multiple of the group size " + std::to_string(g));
+    return dpack_check(ctx, op, dtype, rows, cols, SMHIP_DPACK_ROW, ins, outs);
+}
+
+int smhip_gptq_quant(smhip_ctx* ctx, const smhip_gptq_quant_desc* d, int32_t* qweight, int32_t* qzeros, uint16_t* scales,
+                     int32_t* g_idx, smhip_gptq_report* report, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "gptq_quant: null descriptor");
+    const size_t es = d->dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols, ng = d->group_size > 0 ? n / (size_t)d->group_size : 0;
+    if (int rc = gptq_check(ctx, "gptq_quant", d->dtype, d->rows, d->cols, d->group_size, {{d->x, n * es, es}},
+                            {{qweight, n / 2, 4}, {qzeros, ng / 2, 4}, {scales, ng * 2, 2}, {g_idx, n ? d->cols * 4 : 0, 4}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.gptq_quant(*d, qweight, qzeros, scales, g_idx, report));
+}
+
+int smhip_gptq_dequant(smhip_ctx* ctx, const smhip_gptq_dequant_desc* d, void* out, void* stream) {
+    SM_GUARD(ctx);
+    if (!d) return ctx->pipe.fail(SMHIP_ERR_ARG, "gptq_dequant: null descriptor");
+    const size_t es = d->out_dtype == SMHIP_F32 ? 4 : 2, n = d->rows * d->cols, ng = d->group_size > 0 ? n / (size_t)d->group_size : 0;
+    if (int rc = gptq_check(ctx, "gptq_dequant", d->out_dtype, d->rows, d->cols, d->group_size,
+                            {{d->qweight, n / 2, 4}, {d->qzeros, ng / 2, 4}, {d->scales, ng * 2, 2}, {d->g_idx, n ? d->cols * 4 : 0, 4}},
+                            {{out, n * es, es}}))
+        return rc;
+    ctx->pipe.stream = stream;
+    SM_FINISH(ctx, ctx->pipe.delta.gptq_dequant(*d, out));
+}
+
 int smhip_emr_merge(smhip_ctx* ctx, const smhip_emr_desc* d, void* out, float* delta_out, smhip_emr_report* report,
                     void* stream) {
     SM_GUARD(ctx);

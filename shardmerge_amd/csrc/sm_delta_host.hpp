@@ -36,6 +36,7 @@
 #include "sm_fp8.hpp"
 #include "sm_mx4.hpp"
 #include "sm_nv4.hpp"
+#include "sm_gptq.hpp"
 #include "sm_wudi.hpp"
 
 namespace smhip {
@@ -2076,6 +2077,57 @@ class DeltaHost {
         be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
         if (!be.ok()) return SMHIP_OK;
         if (host.flags[0] & NV4_FLAG_NAN_SCALE) return fail(SMHIP_ERR_NONFINITE, "nv4_dequant: a NaN scale code (0x7F or 0xFF) in the tensor");
+        return SMHIP_OK;
+    }
+
+    // ---- GPTQ-layout INT4 (sm_gptq.hpp; smhip_gptq_quant, smhip_gptq_dequant).  One kernel each over the tiles of 64 rows
+    // by one group, `chunks` tiles per work-group; the head (the four counters / the flag word) is read back once.
+    // Workspace: GptqHead alone ----
+    struct GptqHead { unsigned long long counts[GPTQ_COUNTERS]; uint32_t flags[2]; };
+    static size_t gptq_tiles(size_t rows, size_t cols, int g) { return ((rows + GPTQ_ROWS - 1) / GPTQ_ROWS) * (cols / (size_t)g); }
+    int gptq_quant(const smhip_gptq_quant_desc& d, int32_t* qweight, int32_t* qzeros, uint16_t* scales, int32_t* g_idx,
+                   smhip_gptq_report* rep) {
+        if (rep) *rep = smhip_gptq_report{};
+        if (d.rows * d.cols == 0) return SMHIP_OK;
+        const size_t ntiles = gptq_tiles(d.rows, d.cols, d.group_size);
+        GptqHead* w;
+        if (int rc = plain_workspace(w)) return rc;
+        GptqQuantParams p;
+        p.x = d.x; p.dtype = d.dtype; p.R = d.rows; p.C = d.cols; p.g = d.group_size;
+        p.qweight = (uint32_t*)qweight; p.qzeros = (uint32_t*)qzeros; p.scales = scales; p.g_idx = (uint32_t*)g_idx;
+        p.counts = w->counts;
+        p.vec_x = aligned16(d.x) ? 1 : 0; p.vec_s = aligned16(scales) ? 1 : 0;
+        p.chunks = stream_chunks(ntiles, 1, 1, 8);
+        be.template launch<KGptqQuant>(stream_grid(ntiles, 1, p.chunks), GPTQ_THREADS, (LDS_SCRATCH_FLOATS + GPTQ_QUANT_LDS_FLOATS) * 4, p, stream);
+        GptqHead host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;                   // (reported by the caller as SMHIP_ERR_HIP; the report stays zero)
+        if (rep) {
+            rep->groups = d.rows * (d.cols / (size_t)d.group_size); rep->zero_groups = host.counts[GPTQ_ZERO_GROUPS];
+            rep->scale_clamped = host.counts[GPTQ_SCALE_CLAMPED]; rep->clipped = host.counts[GPTQ_CLIPPED];
+            rep->nonfinite = host.counts[GPTQ_NONFINITE];
+        }
+        if (host.counts[GPTQ_NONFINITE]) return fail(SMHIP_ERR_NONFINITE, "gptq_quant: NaN or Inf in the tensor");
+        return SMHIP_OK;
+    }
+    int gptq_dequant(const smhip_gptq_dequant_desc& d, void* out) {
+        if (d.rows * d.cols == 0) return SMHIP_OK;
+        const size_t ntiles = gptq_tiles(d.rows, d.cols, d.group_size);
+        GptqHead* w;
+        if (int rc = plain_workspace(w)) return rc;
+        GptqDequantParams p;
+        p.qweight = (const uint32_t*)d.qweight; p.qzeros = (const uint32_t*)d.qzeros; p.scales = d.scales; p.g_idx = (const uint32_t*)d.g_idx;
+        p.R = d.rows; p.C = d.cols; p.g = d.group_size; p.out = out; p.out_dtype = d.out_dtype;
+        p.vec = aligned16(out) ? 1 : 0;
+        p.flags = w->flags;
+        p.chunks = stream_chunks(ntiles, 1, 1, 8);
+        be.template launch<KGptqDequant>(stream_grid(ntiles, 1, p.chunks), GPTQ_THREADS, (LDS_SCRATCH_FLOATS + GPTQ_DEQUANT_LDS_FLOATS) * 4, p, stream);
+        GptqHead host;
+        be.d2h(&host, w, sizeof host, stream);           // the call's one synchronisation
+        if (!be.ok()) return SMHIP_OK;
+        if (host.flags[0] & GPTQ_FLAG_ACT_ORDER)
+            return fail(SMHIP_ERR_ARG, "gptq_dequant: g_idx is not i // group_size (act-order, desc_act, is not supported)");
+        if (host.flags[0] & GPTQ_FLAG_NONFINITE_SCALE) return fail(SMHIP_ERR_NONFINITE, "gptq_dequant: a NaN or Inf scale in the tensor");
         return SMHIP_OK;
     }
 

@@ -210,6 +210,11 @@ def config_stamp(config: MergeConfig) -> str:
             if (ident := nv4_identity(Path(config.storage_path) / m.model)) is not None}   # an NVFP4 checkpoint's: its shard headers
     if nv4s:
         doc["nv4_models"] = nv4s
+    from .gptqmodel import gptq_identity
+    gptqs = {m.model: ident for m in config.finetune_merge
+             if (ident := gptq_identity(Path(config.storage_path) / m.model)) is not None}   # a GPTQ checkpoint's: its shard headers
+    if gptqs:
+        doc["gptq_models"] = gptqs
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 

@@ -305,6 +305,18 @@ class Nv4Report:
     nonfinite: int = 0                                               # blocks that hold a NaN or an Inf
 
 
+@dataclass
+class GptqReport:
+    rows: int = 0
+    cols: int = 0
+    group_size: int = 0
+    groups: int = 0                                                  # (group, row) pairs: R C / g scales
+    zero_groups: int = 0                                             # groups of zeros
+    scale_clamped: int = 0                                           # groups, not of zeros, whose fp16 scale a clamp moved
+    clipped: int = 0                                                 # elements whose code left 0 .. 15 before the clamp
+    nonfinite: int = 0                                               # groups that hold a NaN or an Inf
+
+
 def _shape_rows(t: torch.Tensor) -> Tuple[int, int]:
     """the delta pack's view of a tensor: R = shape[0] rows of the rest; a 0-D or 1-D tensor is one row"""
     if t.ndim <= 1:
@@ -922,6 +934,77 @@ class Engine:
         desc = _lib.Nv4DequantDesc(cs.data_ptr(), sc.data_ptr(), global_scale, rows, cols, _lib.NV4_BLOCK, _DTYPE_CODE[dtype])
         self._mx4_check(self.lib.dll.smhip_nv4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
                         "NaN scale code", layer_name)
+        return out
+
+    # -- GPTQ-layout INT4 (qweight / qzeros / scales / g_idx: the weight transposed, packed along the input dimension) --
+    def gptq_quant(self, x: torch.Tensor, group_size: int = 128, *, layer_name: str = ""):
+        """A 2-D tensor ``W [R, C]`` with ``R % 8 == 0`` and ``C % group_size == 0`` as group-quantised INT4 in the GPTQ
+        tensor layout (``smhip_gptq_quant``; the function is stated in include/shardmerge_hip.h): round to nearest,
+        asymmetric, one fp16 scale and one zero-point per ``group_size`` input columns and output row - NOT the GPTQ
+        solver.  Returns ``(qweight int32 [C / 8, R], qzeros int32 [C / g, R / 8], scales float16 [C / g, R], g_idx int32
+        [C], GptqReport)``.  A NaN or Inf in ``x`` raises ValueError naming ``layer_name``."""
+        who = layer_name or "tensor"
+        if x.ndim != 2:
+            raise ValueError(f"gptq_quant: {who} is {list(x.shape)}; a 2-D tensor expected")
+        if x.dtype not in _DTYPE_CODE:
+            raise ValueError(f"gptq_quant: {who} is {x.dtype}; bf16, f16 or f32 expected")
+        if group_size not in _lib.GPTQ_GROUPS:
+            raise ValueError(f"gptq_quant: group size {group_size} for {who} is not one of {list(_lib.GPTQ_GROUPS)}")
+        rows, cols = x.shape
+        if rows % 8 or cols % group_size:
+            raise ValueError(f"gptq_quant: {who} is {list(x.shape)}; rows a multiple of 8 and columns a multiple of the "
+                             f"group size {group_size} expected")
+        xs = self._dev(x)
+        ng = cols // group_size
+        qweight = torch.empty((cols // 8, rows), dtype=torch.int32, device=self.device)
+        qzeros = torch.empty((ng, rows // 8), dtype=torch.int32, device=self.device)
+        scales = torch.empty((ng, rows), dtype=torch.float16, device=self.device)
+        g_idx = torch.empty((cols,), dtype=torch.int32, device=self.device)
+        desc = _lib.GptqQuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, group_size)
+        rep = _lib.GptqReport()
+        self._mx4_check(self.lib.dll.smhip_gptq_quant(self.ctx.h, C.byref(desc), qweight.data_ptr(), qzeros.data_ptr(),
+                                                      scales.data_ptr(), g_idx.data_ptr(), C.byref(rep), self._stream()),
+                        "Non-finite value", layer_name)
+        report = GptqReport(rows=rows, cols=cols, group_size=group_size, groups=int(rep.groups), zero_groups=int(rep.zero_groups),
+                            scale_clamped=int(rep.scale_clamped), clipped=int(rep.clipped), nonfinite=int(rep.nonfinite))
+        return qweight, qzeros, scales, g_idx, report
+
+    def gptq_dequant(self, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, g_idx: torch.Tensor,
+                     dtype: torch.dtype = torch.bfloat16, *, out: Optional[torch.Tensor] = None, layer_name: str = "") -> torch.Tensor:
+        """the tensor ``W [R, C]`` four GPTQ tensors stand for: ``(q - z) * scale``, the difference an exact integer, one
+        fp32 product, one rounding into ``dtype`` (``smhip_gptq_dequant``).  qweight: int32 [C / 8, R]; scales: float16
+        [C / g, R], which gives the group size g = 32, 64 or 128; qzeros: int32 [C / g, R / 8], stored minus one; g_idx:
+        int32 [C], which must be ``i // g`` (act-order is not supported); out (optional): a contiguous ``dtype`` [R, C]
+        tensor on the engine's device that overlaps none of them.  A wrong shape, an act-order g_idx and a NaN or Inf
+        scale raise ValueError naming ``layer_name``."""
+        who = layer_name or "tensor"
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"gptq_dequant: dtype of {who} is {dtype}; bf16, f16 or f32 expected")
+        if qweight.dtype != torch.int32 or qweight.ndim != 2 or qweight.shape[1] % 8:
+            raise ValueError(f"gptq_dequant: qweight of {who} is {qweight.dtype} {list(qweight.shape)}; int32 [C / 8, R] with "
+                             f"R a multiple of 8 expected")
+        cols, rows = 8 * qweight.shape[0], qweight.shape[1]
+        if scales.dtype != torch.float16 or scales.ndim != 2 or scales.shape[1] != rows or not scales.shape[0] \
+                or cols % scales.shape[0] or cols // scales.shape[0] not in _lib.GPTQ_GROUPS:
+            raise ValueError(f"gptq_dequant: scales of {who} are {scales.dtype} {list(scales.shape)}; float16 [C / g, {rows}] "
+                             f"with g one of {list(_lib.GPTQ_GROUPS)} expected for qweight {list(qweight.shape)}")
+        group_size = cols // scales.shape[0]
+        if qzeros.dtype != torch.int32 or tuple(qzeros.shape) != (cols // group_size, rows // 8):
+            raise ValueError(f"gptq_dequant: qzeros of {who} are {qzeros.dtype} {list(qzeros.shape)}; int32 "
+                             f"{[cols // group_size, rows // 8]} expected for qweight {list(qweight.shape)}")
+        if g_idx.dtype != torch.int32 or tuple(g_idx.shape) != (cols,):
+            raise ValueError(f"gptq_dequant: g_idx of {who} is {g_idx.dtype} {list(g_idx.shape)}; int32 {[cols]} expected "
+                             f"for qweight {list(qweight.shape)}")
+        qw, qz, sc, gi = self._dev(qweight), self._dev(qzeros), self._dev(scales), self._dev(g_idx)
+        if out is None:
+            out = torch.empty((rows, cols), dtype=dtype, device=self.device)
+        elif out.dtype != dtype or tuple(out.shape) != (rows, cols) or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"gptq_dequant: out of {who} is {out.dtype} {list(out.shape)} on {out.device}; a contiguous "
+                             f"{dtype} {[rows, cols]} tensor on {self.device} expected")
+        desc = _lib.GptqDequantDesc(qw.data_ptr(), qz.data_ptr(), sc.data_ptr(), gi.data_ptr(), rows, cols, group_size,
+                                    _DTYPE_CODE[dtype])
+        self._mx4_check(self.lib.dll.smhip_gptq_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
+                        "Non-finite scale", layer_name)
         return out
 
     # -- EMR-Merging: the unified model, a task's mask and rescaler, the task's tensor --------------

@@ -26,6 +26,7 @@ from .deltapack import DeltaPack, is_pack_dir
 from .emrpack import EmrPack, is_emr_dir
 from .fp8model import Fp8Model, fp8_model
 from .mx4model import Mx4Model, mx4_model
+from .gptqmodel import GptqModel, gptq_model
 from .nv4model import Nv4Model, nv4_model
 
 logger = logging.getLogger(__name__)
@@ -76,6 +77,7 @@ class LocalModelIndex:
         self.fp8s: Dict[str, Fp8Model] = {}            # block-scaled FP8 checkpoints (fp8model.py), by model uri
         self.mx4s: Dict[str, Mx4Model] = {}            # MXFP4 checkpoints (mx4model.py), by model uri
         self.nv4s: Dict[str, Nv4Model] = {}            # NVFP4 checkpoints (nv4model.py), by model uri
+        self.gptqs: Dict[str, GptqModel] = {}          # GPTQ-layout INT4 checkpoints (gptqmodel.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -133,6 +135,11 @@ class LocalModelIndex:
             # an MXFP4 checkpoint: config.json says so and its coded weights come with a scale tensor each
             self.mx4s[model_uri] = mx4
             logger.info(f"Model {model_uri}: MXFP4 checkpoint, {len(mx4.scale_keys)} micro-scaled E2M1 tensors")
+        gptq = gptq_model(model_uri, self.storage_path / model_uri, index["weight_map"])
+        if gptq is not None:
+            # a GPTQ checkpoint: config.json says so and a weight is stored as qweight, qzeros, scales and g_idx
+            self.gptqs[model_uri] = gptq
+            logger.info(f"Model {model_uri}: GPTQ checkpoint, {len(gptq.keys)} INT4 tensors in groups of {gptq.group_size}")
         logger.info(f"Model {model_uri}: {len(set(index['weight_map'].values()))} shards, {len(index['weight_map'])} tensors")
 
     def adapter(self, model_uri: str) -> Optional[LoraAdapter]:
@@ -154,6 +161,10 @@ class LocalModelIndex:
     def nv4(self, model_uri: str) -> Optional[Nv4Model]:
         """the NVFP4 checkpoint registered under this uri, None for anything else"""
         return self.nv4s.get(model_uri)
+
+    def gptq(self, model_uri: str) -> Optional[GptqModel]:
+        """the GPTQ-layout INT4 checkpoint registered under this uri, None for anything else"""
+        return self.gptqs.get(model_uri)
 
     def mx4(self, model_uri: str) -> Optional[Mx4Model]:
         """the MXFP4 checkpoint registered under this uri, None for anything else"""

@@ -50,7 +50,7 @@ class MergeTensorsBase(ABC):
         the planes and scale, the tensor the pack stores whole, or the base's tensor alone; for an EMR pack entry its
         base's and the unified model's tensor, the mask and the rescaler, the whole tensor, or the base's tensor alone;
         for an FP8 or an MXFP4 checkpoint entry the codes and their scale tensor, for an NVFP4 one the codes and both
-        scale tensors, or the tensor it keeps in 16 bits"""
+        scale tensors, for a GPTQ one the four tensors a weight is stored as, or the tensor it keeps in 16 bits"""
         pack = self.index_manager.pack(m.model)
         if pack is not None:
             t = pack.tensors.get(layer_name)
@@ -77,6 +77,9 @@ class MergeTensorsBase(ABC):
         nv4 = self.index_manager.nv4(m.model)
         if nv4 is not None and layer_name in nv4.scale_keys:
             return [(m.model, layer_name), (m.model, nv4.scale_keys[layer_name]), (m.model, nv4.global_keys[layer_name])]
+        gptq = self.index_manager.gptq(m.model)
+        if gptq is not None and layer_name in gptq.keys:
+            return [(m.model, key) for key in gptq.keys[layer_name]]
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return [(m.model, layer_name)]
@@ -97,7 +100,9 @@ class MergeTensorsBase(ABC):
         block-scaled FP8 checkpoint entry (fp8model.py) `Engine.fp8_dequant` of the codes and their scales into the
         dtype its base holds the tensor in; the tensors it keeps in 16 bits pass as they are.  For an MXFP4
         checkpoint entry (mx4model.py) `Engine.mx4_dequant` of the codes and their scales, likewise; for an NVFP4
-        checkpoint entry (nv4model.py) `Engine.nv4_dequant` of the codes, the block scales and the tensor's scale.
+        checkpoint entry (nv4model.py) `Engine.nv4_dequant` of the codes, the block scales and the tensor's scale; for
+        a GPTQ checkpoint entry (gptqmodel.py), which holds no `X.weight`, `Engine.gptq_dequant` of `X.qweight`,
+        `X.qzeros`, `X.scales` and `X.g_idx`.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
@@ -145,6 +150,11 @@ class MergeTensorsBase(ABC):
             scale_2 = await fetch(m.model, nv4.global_keys[layer_name])
             return self.engine(device).nv4_dequant(codes, scale, scale_2, self._fp8_out_dtype(m, layer_name, "NVFP4"),
                                                    layer_name=f"{m.model}: {layer_name}")
+        gptq = self.index_manager.gptq(m.model)
+        if gptq is not None and layer_name in gptq.keys:
+            qweight, qzeros, scales, g_idx = [await fetch(m.model, key) for key in gptq.keys[layer_name]]
+            return self.engine(device).gptq_dequant(qweight, qzeros, scales, g_idx, self._fp8_out_dtype(m, layer_name, "GPTQ"),
+                                                    layer_name=f"{m.model}: {layer_name}")
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return await fetch(m.model, layer_name)
@@ -219,6 +229,9 @@ class MergeTensorsBase(ABC):
             if self.index_manager.nv4(uri) is not None:
                 raise ValueError(f"{uri} is an NVFP4 checkpoint and cannot be {role}: write it out in 16 bits with "
                                  f"`dequantize-nvfp4 {uri} --out DIR` first and name that directory")
+            if self.index_manager.gptq(uri) is not None:
+                raise ValueError(f"{uri} is a GPTQ checkpoint and cannot be {role}: write it out in 16 bits with "
+                                 f"`dequantize-gptq {uri} --out DIR` first and name that directory")
         base_keys = self.index_manager.get_model_keys(cfg.output_base_model)
         for m in cfg.finetune_merge:
             adapter = self.index_manager.adapter(m.model)
@@ -258,6 +271,9 @@ class MergeTensorsBase(ABC):
             nv4 = self.index_manager.nv4(m.model)
             if nv4 is not None:
                 keys = keys - nv4.scale_names
+            gptq = self.index_manager.gptq(m.model)
+            if gptq is not None:
+                keys = gptq.model_keys(keys)            # (the four tensors of a weight stand for its X.weight)
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)
