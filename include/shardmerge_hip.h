@@ -1175,6 +1175,9 @@ typedef struct {
     double tol;                             /* (0, 1] */
     int max_iter;                           /* 0..200 */
     void* workspace; size_t workspace_bytes;
+    int gemm;                               /* SMHIP_ISO_GEMM_FP32 (0, a zero-initialised desc) | SMHIP_ISO_GEMM_BF16X3: every
+                                               gemm of step 4 is the split product stated at smhip_iso_gemm; the report's
+                                               e, steps, N and sigma_bar are then those of that product */
 } smhip_iso_desc;
 typedef struct {
     int s, L, transposed;
@@ -1191,7 +1194,37 @@ int smhip_iso_merge(smhip_ctx* ctx, const smhip_iso_desc* desc, void* out, float
  * form 0 (NT): c = ep(a b^T), a [M x K] pitch lda, b [N x K] pitch ldb; form 1 (NN): c = ep(a b), b [K x N].  sym (NT,
  * M == N, b^T the transpose of a's partner bit for bit - a == b, or a == b symmetric): m >= n computed and mirrored.
  * epilogue 0: acc; 1: fmaf(ca, acc, cb * e[m][n]); 2: fmaf(ca, e[m][n], acc); 3: fmaf(ca, e[m][n], cb * acc); e [M x N]
- * pitch lde.  c [M x N] pitch ldc may not overlap an input.  M, N, K >= 1. */
+ * pitch lde.  c [M x N] pitch ldc may not overlap an input.  M, N, K >= 1.
+ *
+ * gemm = SMHIP_ISO_GEMM_BF16X3 ("iso_gemm3_nt", "iso_gemm3_nn"): the same product on the bf16 MFMA, opt-in.
+ *   1. Split.  Every fp32 operand x becomes three bf16 pieces, each rounded to nearest even:
+ *        x0 = bf16(x);  x1 = bf16(x - float(x0));  x2 = bf16((x - float(x0)) - float(x1)).
+ *      With 2^e <= |x| < 2^(e+1), x is a multiple of 2^(e-23).  x0 keeps 8 significant bits, so r1 = x - x0 is a multiple
+ *      of 2^(e-23) with |r1| <= 2^(e-8), half a unit of x0's last place: at most 2^15 such multiples, 16 bits, and the
+ *      subtraction is exact in fp32.  x1 keeps 8 bits of r1 and its exponent is at most e - 8, so r2 = r1 - x1 is a
+ *      multiple of 2^(e-23) with |r2| <= 2^(e-16): at most 2^7 multiples, which 8 bits hold.  The second subtraction is
+ *      exact and x2 == r2: x0 + x1 + x2 == x exactly, 24 bits as 8 + 8 + 8 with signed pieces.  This needs every piece
+ *      to be a normal number and x0 not to round to infinity: a finite x with 2^-100 <= |x| < 2^127 (or x == 0).
+ *      Operands outside that range, NaN and Inf are the caller's problem; smhip_iso_merge scales X to Frobenius norm
+ *      1 and rejects non-finite deltas before any product.
+ *   2. Products.  Per k six of the nine piece products are kept: a0 b0, a0 b1, a1 b0, a1 b1, a0 b2, a2 b0.  Each is
+ *      8 x 8 bits and exact in fp32.  They are accumulated in fp32 over all k into one accumulator from +0.
+ *      Dropped: a1 b2, a2 b1, a2 b2.  |a1| <= 2^-8 |a| and |a2| <= 2^-16 |a| by the above, so the three amount to at most
+ *      (2^-24 + 2^-24 + 2^-32) |a| |b| < 2^-23 (1 + 2^-9) |a| |b| per k - the worst case, every piece at half a unit;
+ *      pieces with uniformly distributed low bits give about 2^-26 |a| |b| on average.
+ *   3. Order.  The emulator adds in ascending k and within a k in the order a2 b0, a0 b2, a1 b1, a1 b0, a0 b1, a0 b0
+ *      (the small terms first), one rounded fp32 addition each.  The device issues, per 16 k, one
+ *      v_mfma_f32_32x32x16_bf16 per term in that order; the order of addition inside one such instruction is not
+ *      documented and has not been measured, nor has its handling of denormal pieces.  The device is therefore NOT
+ *      required to equal the emulator bit for bit in this mode.  Both are held to
+ *        |C - C64| <= (6 K + 1) 2^-23 (|A| |B|)  per element before the epilogue, C64 the fp64 product of the fp32 inputs:
+ *      6 K additions at 2^-23 each (a truncating adder; round to nearest gives 2^-24, and the emulator's 6 K 2^-24 plus the
+ *      dropped K 2^-23 (1 + 2^-9) stay inside).
+ *   4. Epilogues, edges and the symmetric mode are iso_gemm's, except that inside a diagonal 128 x 128 tile (m, n) and
+ *      (n, m) add a0 b1 and a1 b0 in swapped order and may differ in the last bit: only m >= n is kept there and
+ *      mirrored, as the off-diagonal tiles are.  c == c^T bit for bit. */
+#define SMHIP_ISO_GEMM_FP32 0
+#define SMHIP_ISO_GEMM_BF16X3 1
 typedef struct {
     int form, sym, epilogue;
     int M, N, K;
@@ -1200,6 +1233,7 @@ typedef struct {
     const float* e; int lde;
     float ca, cb;
     float* c; int ldc;
+    int gemm;                               /* SMHIP_ISO_GEMM_FP32 (0) | SMHIP_ISO_GEMM_BF16X3 */
 } smhip_iso_gemm_desc;
 int smhip_iso_gemm(smhip_ctx* ctx, const smhip_iso_gemm_desc* desc, void* stream);
 

@@ -317,12 +317,15 @@ class TsvReport(C.Structure):
 ISO_MAX_S, ISO_MAX_ITER = 16384, 200               # SMHIP_ISO_MAX_S, SMHIP_ISO_MAX_ITER
 ISO_NT, ISO_NN = 0, 1                               # form of smhip_iso_gemm
 ISO_EP_PLAIN, ISO_EP_POLY, ISO_EP_AXPY, ISO_EP_CUBIC = range(4)
+ISO_GEMM_MODES = {"fp32": 0, "bf16x3": 1}          # SMHIP_ISO_GEMM_FP32, SMHIP_ISO_GEMM_BF16X3
 
 
 class IsoDesc(C.Structure):
-    """smhip_iso_desc: the leading fields of the delta merges, then the shape, lambda, tol, max_iter and the workspace"""
+    """smhip_iso_desc: the leading fields of the delta merges, then the shape, lambda, tol, max_iter, the workspace and the
+    gemm mode"""
     _fields_ = _DELTA_DESC_FIELDS[:8] + [("rows", C.c_int), ("cols", C.c_int), ("lam", C.c_double), ("tol", C.c_double),
-                                         ("max_iter", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                                         ("max_iter", C.c_int), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                                         ("gemm", C.c_int)]
 
 
 class IsoReport(C.Structure):
@@ -337,7 +340,7 @@ class IsoGemmDesc(C.Structure):
     """smhip_iso_gemm_desc"""
     _fields_ = [("form", C.c_int), ("sym", C.c_int), ("epilogue", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("e", C.c_void_p), ("lde", C.c_int),
-                ("ca", C.c_float), ("cb", C.c_float), ("c", C.c_void_p), ("ldc", C.c_int)]
+                ("ca", C.c_float), ("cb", C.c_float), ("c", C.c_void_p), ("ldc", C.c_int), ("gemm", C.c_int)]
 
 
 WUDI_MAX_C, WUDI_MAX_ITER = 32768, 2000            # SMHIP_WUDI_MAX_C, SMHIP_WUDI_MAX_ITER

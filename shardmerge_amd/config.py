@@ -173,6 +173,9 @@ reference's shard/config.py:24-126, so existing config files work unchanged.
       # iso_lambda: 1.0         #   scales the merged delta
       # iso_tol: 0.0001         #   0 < iso_tol <= 1: the iteration stops at ||X X^T - I||_F / sqrt(min(rows, cols)) <= iso_tol
       # iso_max_iter: 40        #   an integer in 0..200: steps at most (reaching it is reported, not an error)
+      # iso_gemm: fp32          #   fp32 | bf16x3: the iteration's products on the fp32 MFMA, or on the bf16 MFMA with every
+                                #   fp32 operand split into three bf16 pieces (six of the nine piece products, fp32 sums;
+                                #   about 2^-23 relative per product term, and not bit for bit the same on every path)
                                 # | wudi (WUDI-Merging, Cheng et al. 2025; no counterpart in the reference): per block
                                 #   matrix ([shape[0] x the rest]) the merged task vector X that minimises the interference
                                 #   sum_i ||(X - d_i) d_i^T||^2 / ||d_i||^2 between the tasks, the deltas d_i themselves
@@ -258,7 +261,8 @@ CABS_OPTION_DEFAULTS = {"cabs_n": 64, "cabs_m": 256, "cabs_conflict_aware": 1.0,
 CABS_GROUPS = (4, 8, 16, 32, 64, 128, 256, 512)     # cabs_m: a group is selected inside one work-group
 WIDEN_MAX_COLS = 65536                              # columns of a block tensor at most: the ranks are counted over all pairs
 ISO_OPERATORS = ("iso_c",)
-ISO_OPTION_DEFAULTS = {"iso_lambda": 1.0, "iso_tol": 1e-4, "iso_max_iter": 40}
+ISO_OPTION_DEFAULTS = {"iso_lambda": 1.0, "iso_tol": 1e-4, "iso_max_iter": 40, "iso_gemm": "fp32"}
+ISO_GEMMS = ("fp32", "bf16x3")                      # iso_gemm: the fp32 MFMA, or the bf16 MFMA on three-way split operands
 ISO_MAX_S = 16384                                   # min(rows, cols) of a block tensor at most
 EMR_OPERATORS = ("emr",)                            # the elected unified model; it takes no weights
 EMR_OPTION_DEFAULTS = {"emr_lambda": 1.0}
@@ -421,7 +425,7 @@ _OPTION_FAMILIES = (                                # in the order they were add
                            "arcee_fusion": "(it merges several models by n:m sparsification)"},
                   check=_cabs_n_of_m),
     _OptionFamily(ISO_OPERATORS, ISO_OPTION_DEFAULTS,
-                  {"iso_lambda": _LAMBDA, "iso_tol": (0, 1, "(]"), "iso_max_iter": ("int", 0, 200)},
+                  {"iso_lambda": _LAMBDA, "iso_tol": (0, 1, "(]"), "iso_max_iter": ("int", 0, 200), "iso_gemm": ("choice",) + ISO_GEMMS},
                   earlier={"ties": "(it trims nothing and flattens the spectrum of the summed delta: iso_lambda)",
                            "dare_ties": "(it drops nothing at random)",
                            "breadcrumbs": "(it trims nothing)",

@@ -966,6 +966,7 @@ int smhip_iso_merge(smhip_ctx* ctx, const smhip_iso_desc* d, void* out, float* d
             if (!std::isfinite(d->lambda)) return "lambda is not finite";
             if (!(d->tol > 0.0 && d->tol <= 1.0)) return "tol must be in (0, 1]";
             if (d->max_iter < 0 || d->max_iter > SMHIP_ISO_MAX_ITER) return "max_iter out of range (0..200)";
+            if (d->gemm != SMHIP_ISO_GEMM_FP32 && d->gemm != SMHIP_ISO_GEMM_BF16X3) return "bad gemm mode";
             return nullptr;
         }))
         return rc;
@@ -989,6 +990,7 @@ int smhip_iso_gemm(smhip_ctx* ctx, const smhip_iso_gemm_desc* d, void* stream) {
     if (d->epilogue < 0 || d->epilogue > 3) return bad("bad epilogue");
     if (d->M < 1 || d->N < 1 || d->K < 1 || d->M > (1 << 24) || d->N > (1 << 24)) return bad("bad shape");
     if (d->sym != 0 && d->sym != 1) return bad("sym must be 0 or 1");
+    if (d->gemm != SMHIP_ISO_GEMM_FP32 && d->gemm != SMHIP_ISO_GEMM_BF16X3) return bad("bad gemm mode");
     if (d->sym && (d->form != 0 || d->M != d->N)) return bad("sym needs the NT form and M == N");
     if (!d->a || !d->b || !d->c || (d->epilogue && !d->e)) return bad("null pointer");
     if ((uintptr_t)d->a % 4 || (uintptr_t)d->b % 4 || (uintptr_t)d->c % 4 || (uintptr_t)d->e % 4)

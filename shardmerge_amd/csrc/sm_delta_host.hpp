@@ -29,6 +29,7 @@
 #include "sm_widen.hpp"
 #include "sm_cabs.hpp"
 #include "sm_iso.hpp"
+#include "sm_iso3.hpp"
 #include "sm_dpack.hpp"
 #include "sm_emr.hpp"
 #include "sm_emr_fused.hpp"
@@ -1545,7 +1546,7 @@ class DeltaHost {
         return t;
     }
     void iso_gemm(int form, int sym, const float* a, int lda, const float* b, int ldb, int M, int N, int K, int ep, float ca,
-                  float cb, const float* e, int lde, float* c, int ldc) {
+                  float cb, const float* e, int lde, float* c, int ldc, int gemm = SMHIP_ISO_GEMM_FP32) {
         IsoGemmParams g;
         g.a = a; g.b = b; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
         g.avec = (aligned16(a) && lda % 4 == 0) ? 1 : 0; g.bvec = (aligned16(b) && ldb % 4 == 0) ? 1 : 0;
@@ -1553,6 +1554,11 @@ class DeltaHost {
         const int gm = (M + ISO_WG - 1) / ISO_WG;
         g.gn = (N + ISO_WG - 1) / ISO_WG;
         const int grid = sym ? gm * (gm + 1) / 2 : gm * g.gn;
+        if (gemm == SMHIP_ISO_GEMM_BF16X3) {                        // the three-way split on the bf16 MFMA (sm_iso3.hpp)
+            if (form == ISO_NT) be.template launch<KIsoGemm3NT>(grid, ISO_THREADS, ISO_GEMM3_LDS_BYTES, g, stream);
+            else be.template launch<KIsoGemm3NN>(grid, ISO_THREADS, ISO_GEMM3_LDS_BYTES, g, stream);
+            return;
+        }
         if (form == ISO_NT) be.template launch<KIsoGemmNT>(grid, ISO_THREADS, ISO_GEMM_LDS_FLOATS * 4, g, stream);
         else be.template launch<KIsoGemmNN>(grid, ISO_THREADS, ISO_GEMM_LDS_FLOATS * 4, g, stream);
     }
@@ -1633,7 +1639,7 @@ class DeltaHost {
         bool cubic = false;                                         // the quintic phase is over
         double prev = 0.0;
         for (;; ++it) {
-            iso_gemm(ISO_NT, 1, X, L, X, L, s, s, L, ISO_EP_PLAIN, 0.f, 0.f, nullptr, 0, G, s);
+            iso_gemm(ISO_NT, 1, X, L, X, L, s, s, L, ISO_EP_PLAIN, 0.f, 0.f, nullptr, 0, G, s, d.gemm);
             iso_reduce<KIsoResid>(G, nullptr, (size_t)s * s, s, part, res + 1);
             double rs = 0.0;
             be.d2h(&rs, res + 1, 8, stream);                        // the iteration's one synchronisation
@@ -1646,11 +1652,11 @@ class DeltaHost {
             if (!(e > ISO_QUINTIC_ABOVE) || (it > 0 && !(e < prev))) cubic = true;
             prev = e;
             if (!cubic) {
-                iso_gemm(ISO_NT, 1, G, s, G, s, s, s, s, ISO_EP_POLY, ISO_C5, ISO_B5, G, s, P, s);
-                iso_gemm(ISO_NN, 0, P, s, X, L, s, L, s, ISO_EP_AXPY, ISO_A5, 0.f, X, L, Xn, L);
+                iso_gemm(ISO_NT, 1, G, s, G, s, s, s, s, ISO_EP_POLY, ISO_C5, ISO_B5, G, s, P, s, d.gemm);
+                iso_gemm(ISO_NN, 0, P, s, X, L, s, L, s, ISO_EP_AXPY, ISO_A5, 0.f, X, L, Xn, L, d.gemm);
                 R_.steps[it] = 'q';
             } else {
-                iso_gemm(ISO_NN, 0, G, s, X, L, s, L, s, ISO_EP_CUBIC, ISO_A3, ISO_B3, X, L, Xn, L);
+                iso_gemm(ISO_NN, 0, G, s, X, L, s, L, s, ISO_EP_CUBIC, ISO_A3, ISO_B3, X, L, Xn, L, d.gemm);
                 R_.steps[it] = 'c';
             }
             std::swap(X, Xn);
@@ -1671,7 +1677,7 @@ class DeltaHost {
         return SMHIP_OK;
     }
     int iso_gemm_probe(const smhip_iso_gemm_desc& d) {
-        iso_gemm(d.form, d.sym, d.a, d.lda, d.b, d.ldb, d.M, d.N, d.K, d.epilogue, d.ca, d.cb, d.e, d.lde, d.c, d.ldc);
+        iso_gemm(d.form, d.sym, d.a, d.lda, d.b, d.ldb, d.M, d.N, d.K, d.epilogue, d.ca, d.cb, d.e, d.lde, d.c, d.ldc, d.gemm);
         be.sync(stream);
         return SMHIP_OK;
     }

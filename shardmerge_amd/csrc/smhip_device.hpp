@@ -138,15 +138,16 @@ __global__ void __launch_bounds__(K::max_threads, K::waves) sm_kernel(const type
 #define SM_SIDE_HEADER_26 "sm_wudi.hpp"          // WUDI-Merging: the three GEMMs (task-vector Gram, right-hand side, Adam step)
 #define SM_SIDE_HEADER_27 "sm_nv4.hpp"           // NVFP4 (E2M1 + E4M3 + fp32): the tensor's maximum, the quantiser, the dequantiser
 #define SM_SIDE_HEADER_28 "sm_gptq.hpp"          // GPTQ-layout INT4: the quantiser and the dequantiser, a transpose through LDS each
+#define SM_SIDE_HEADER_29 "sm_iso3.hpp"          // Iso-C: iso_gemm on the bf16 MFMA with three-way split fp32 operands
 // A new group: its SM_SIDE_HEADER_<g> and SM_SIDE_KERNELS_<g>, one more entry in SM_SIDE_KERNELS_ALL, and SM_SIDE_GROUPS
 // (the Makefile reads it).
-#define SM_SIDE_GROUPS 29
+#define SM_SIDE_GROUPS 30
 #define SM_SIDE_KERNELS_ALL(X)                                                                                       \
     SM_SIDE_KERNELS_0(X) SM_SIDE_KERNELS_1(X) SM_SIDE_KERNELS_2(X) SM_SIDE_KERNELS_3(X) SM_SIDE_KERNELS_4(X) SM_SIDE_KERNELS_5(X)     \
     SM_SIDE_KERNELS_6(X) SM_SIDE_KERNELS_7(X) SM_SIDE_KERNELS_8(X) SM_SIDE_KERNELS_9(X) SM_SIDE_KERNELS_10(X) SM_SIDE_KERNELS_11(X)   \
     SM_SIDE_KERNELS_12(X) SM_SIDE_KERNELS_13(X) SM_SIDE_KERNELS_14(X) SM_SIDE_KERNELS_15(X) SM_SIDE_KERNELS_16(X) SM_SIDE_KERNELS_17(X) \
     SM_SIDE_KERNELS_18(X) SM_SIDE_KERNELS_19(X) SM_SIDE_KERNELS_20(X) SM_SIDE_KERNELS_21(X) SM_SIDE_KERNELS_22(X) SM_SIDE_KERNELS_23(X) \
     SM_SIDE_KERNELS_24(X) SM_SIDE_KERNELS_25(X) SM_SIDE_KERNELS_26(X) SM_SIDE_KERNELS_27(X) \
-    SM_SIDE_KERNELS_28(X)
+    SM_SIDE_KERNELS_28(X) SM_SIDE_KERNELS_29(X)
 
 }  // namespace smhip

@@ -1786,15 +1786,18 @@ class Engine:
     # -- Iso-C (isotropic merging) ----------------------------------------------------------------
     def iso_merge(self, finetunes: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], alphas: Sequence[float],
                   base_out: torch.Tensor, *, lam: float = 1.0, tol: float = 1e-4, max_iter: int = 40,
-                  want_delta: bool = False, layer_name: str = ""):
+                  want_delta: bool = False, layer_name: str = "", gemm: str = "fp32"):
         """Iso-C merge of one tensor with at least two dimensions, viewed as ``[shape[0], rest]`` (``smhip_iso_merge``; the
         function is stated in include/shardmerge_hip.h): the sum ``T`` of the deltas ``finetune_i - base_i`` times
         ``alpha_i`` with its singular values replaced by their mean - ``mean(S) U V^T``, the polar factor of ``T`` by a
         Newton-Schulz iteration on fp32 MFMA that stops at ``||X X^T - I||_F / sqrt(s) <= tol`` or after ``max_iter``
-        steps (which is reported, not raised) - added, times ``lam``, onto ``base_out`` in its dtype.
+        steps (which is reported, not raised) - added, times ``lam``, onto ``base_out`` in its dtype.  ``gemm="bf16x3"``
+        runs every product of the iteration on the bf16 MFMA with three-way split operands (csrc/sm_iso3.hpp).
         ``min(rows, cols) <= 16384``.  Returns (out, IsoReport[, the fp32 merged delta before ``lam``]).  A NaN or Inf in
         a delta or in the sum raises ValueError naming ``layer_name``."""
         layer_name = layer_name or "layer"
+        if gemm not in _lib.ISO_GEMM_MODES:
+            raise ValueError(f"iso_merge: {layer_name}: gemm must be one of {' | '.join(_lib.ISO_GEMM_MODES)}, not {gemm!r}")
         if not math.isfinite(float(lam)):
             raise ValueError(f"iso_merge: lam {lam} is not finite")
         if not (0.0 < float(tol) <= 1.0):
@@ -1811,6 +1814,7 @@ class Engine:
         keep, bo, out, delta = self._stage_delta_merge(desc, finetunes, bases, alphas, base_out, layer_name, want_delta, "iso_merge")
         desc.n = bo.numel()
         desc.rows, desc.cols, desc.lam, desc.tol, desc.max_iter = rows, cols, float(lam), float(tol), max_iter
+        desc.gemm = _lib.ISO_GEMM_MODES[gemm]
         if desc.n:
             ws = self._xl_workspace(int(self.lib.dll.smhip_iso_workspace(rows, cols)))
             desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -1822,10 +1826,14 @@ class Engine:
         return (out, report, delta) if want_delta else (out, report)
 
     def iso_gemm(self, a: torch.Tensor, b: torch.Tensor, *, form: int = 0, sym: bool = False, epilogue: int = 0,
-                 ca: float = 0.0, cb: float = 0.0, e: Optional[torch.Tensor] = None, ldc: Optional[int] = None) -> torch.Tensor:
+                 ca: float = 0.0, cb: float = 0.0, e: Optional[torch.Tensor] = None, ldc: Optional[int] = None,
+                 gemm: str = "fp32", layer_name: str = "") -> torch.Tensor:
         """``iso_gemm`` alone (``smhip_iso_gemm``; tests and tools): ``ep(a b^T)`` (form 0, ``b [N, K]``) or ``ep(a b)``
         (form 1, ``b [K, N]``) for 2-D fp32 tensors whose rows are contiguous - views with an offset or a pitch are used
-        where they lie when they are on the engine's device.  Returns ``c [M, N]`` (a view of pitch ``ldc`` when given)."""
+        where they lie when they are on the engine's device.  ``gemm="bf16x3"``: the split product on the bf16 MFMA.
+        Returns ``c [M, N]`` (a view of pitch ``ldc`` when given)."""
+        if gemm not in _lib.ISO_GEMM_MODES:
+            raise ValueError(f"iso_gemm: {layer_name or 'layer'}: gemm must be one of {' | '.join(_lib.ISO_GEMM_MODES)}, not {gemm!r}")
         def place(t):
             if t is None:
                 return None
@@ -1843,7 +1851,7 @@ class Engine:
         d.a, d.lda, d.b, d.ldb = av.data_ptr(), pitch(av), bv.data_ptr(), pitch(bv)
         if ev is not None:
             d.e, d.lde = ev.data_ptr(), pitch(ev)
-        d.ca, d.cb, d.c, d.ldc = float(ca), float(cb), store.data_ptr(), ldc
+        d.ca, d.cb, d.c, d.ldc, d.gemm = float(ca), float(cb), store.data_ptr(), ldc, _lib.ISO_GEMM_MODES[gemm]
         self._call(self.lib.dll.smhip_iso_gemm(self.ctx.h, C.byref(d), self._stream()))
         return store[:, :N]
 

@@ -3,7 +3,8 @@ Task-Specific Subspaces", ICML 2025).  Every block tensor with at least two dime
 the deltas of the covering finetunes are summed with their alphas into one task matrix ``T = U S V^T`` whose spectrum is
 replaced by its mean: ``mean(S) U V^T`` is added, times ``iso_lambda``, onto output_base_model.  ``U V^T`` is the polar
 factor of ``T`` and ``mean(S) = <U V^T, T> / min(rows, cols)``, so no SVD is taken: a Newton-Schulz iteration on the
-fp32 MFMA GEMM of csrc/sm_iso.hpp stops at ``||X X^T - I||_F / sqrt(s) <= iso_tol`` or after ``iso_max_iter`` steps.  The
+fp32 MFMA GEMM of csrc/sm_iso.hpp stops at ``||X X^T - I||_F / sqrt(s) <= iso_tol`` or after ``iso_max_iter`` steps;
+``iso_gemm: bf16x3`` runs its products on the bf16 MFMA with three-way split operands (csrc/sm_iso3.hpp) instead.  The
 reference has no such operator; the function is defined in include/shardmerge_hip.h (``smhip_iso_merge``) and runs
 behind ``Engine.iso_merge``.
 
@@ -32,6 +33,7 @@ class IsoMerge(TiesMerge):
         super().__init__(config, index_manager=index_manager, engine=engine, **kwargs)
         opts = getattr(config, "merge_options", None) or {}
         self.iso_max_iter = int(opts.get("iso_max_iter", ISO_OPTION_DEFAULTS["iso_max_iter"]))      # exactly
+        self.iso_gemm = str(opts.get("iso_gemm", ISO_OPTION_DEFAULTS["iso_gemm"]))
 
     async def initialize(self):
         await super().initialize()
@@ -62,7 +64,7 @@ class IsoMerge(TiesMerge):
     def get_readme(self) -> str:
         return self._readme("Iso-C", f"Iso-C (isotropic merging: the summed delta's singular values replaced by their mean, by a "
                                      f"Newton-Schulz polar iteration), lambda {self.iso_lambda:g}, tol {self.iso_tol:g}, "
-                                     f"max_iter {self.iso_max_iter}; 1-D tensors: the normalised weighted mean of the deltas")
+                                     f"max_iter {self.iso_max_iter}, products {self.iso_gemm}; 1-D tensors: the normalised weighted mean of the deltas")
 
     def merge_block(self, eng, fts, bases, alphas, base_out, name: str):
         if base_out.ndim < 2:
@@ -70,7 +72,7 @@ class IsoMerge(TiesMerge):
                                   sign_election=False, key=tensor_key(0, name), stream_ids=list(range(len(fts))),
                                   layer_name=name)
         return eng.iso_merge(fts, bases, alphas, base_out, lam=self.iso_lambda, tol=self.iso_tol, max_iter=self.iso_max_iter,
-                             layer_name=name)
+                             layer_name=name, gemm=self.iso_gemm)
 
     def tensor_passes(self, k: int) -> int:
         # the k finetunes and their bases read once; base_out read and out written; the iteration's matrix products are
@@ -84,7 +86,7 @@ class IsoMerge(TiesMerge):
         if report.zero:
             logger.info(f"Merged {name}: {k} model(s), Iso-C: the summed delta is zero, the base is kept")
             return
-        logger.info(f"Merged {name}: {k} model(s), Iso-C lambda {self.iso_lambda:g} tol {self.iso_tol:g}: {report.s} x {report.L}"
+        logger.info(f"Merged {name}: {k} model(s), Iso-C lambda {self.iso_lambda:g} tol {self.iso_tol:g} products {self.iso_gemm}: {report.s} x {report.L}"
                     f"{' (transposed)' if report.transposed else ''}, steps {report.steps or '-'}, residual {report.e[-1]:.3g} "
                     f"{'converged' if report.converged else f'NOT converged after iso_max_iter = {self.iso_max_iter} steps'}, "
                     f"mean singular value {report.sigma_bar:.6g}")
