@@ -18,6 +18,7 @@ import click
 from .config import MergeConfig
 from .index import LocalModelIndex
 from .merge.fast_fourier import FourierMerge
+from .quantformat import formats
 
 logger = logging.getLogger(__name__)
 
@@ -211,208 +212,66 @@ def compress_delta_command(model: str, base: str, out_dir: Path, storage_dir: Pa
     click.echo(f"delta pack: {out_dir}")
 
 
-def _fp8_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str, verbose: bool):
+def _quant_command(fmt, verb: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str,
+                   verbose: bool, **options):
+    command = f"{verb}-{fmt.SUFFIX}"
     setup_logging(verbose)
     from .constants import tune_hip_queues
     tune_hip_queues()                   # before the first GPU call, as merge does
     try:
         from .merge.extract import parse_modules
-        from .merge.fp8 import format_table, run_fp8
-        result = asyncio.run(run_fp8(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device))
+        from .merge.quantize import format_table, run_conversion
+        result = asyncio.run(run_conversion(fmt, verb, model, out_dir, storage_dir, parse_modules(modules), dtype, device, **options))
     except Exception as exc:
         logging.error(f"Error during {command}: {exc}", exc_info=verbose)
         traceback.print_exc()
         raise click.Abort()
-    click.echo(format_table(result))
+    click.echo(format_table(fmt, result))
     click.echo(f"model: {out_dir}")
 
 
-@cli.command("quantize-fp8")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the FP8 checkpoint is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--modules", type=str, default=None,
-              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
-                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def quantize_fp8_command(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool):
-    """MODEL as a block-scaled FP8 checkpoint: E4M3 weights with one fp32 scale per 128 x 128 block.
-
-    DIR receives the shards (X.weight as F8_E4M3, X.weight_scale_inv as F32), model.safetensors.index.json and a
-    config.json with the quantization_config block; it can be named as a finetune_merge entry of `merge` in place of MODEL.
-    """
-    _fp8_command("quantize-fp8", model, out_dir, storage_dir, modules, "bf16", device, verbose)
+def _register(name: str, help_text: str, params, run):
+    """the command `name` with `params` in the order its --help lists them"""
+    for param in reversed(params):
+        run = param(run)
+    cli.command(name, help=help_text)(run)
 
 
-@cli.command("dequantize-fp8")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the FP8 tensors are written in")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def dequantize_fp8_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
-    """The block-scaled FP8 checkpoint MODEL written out in 16 or 32 bits: code times its block's scale, rounded once.
+def _register_format(fmt):
+    """`quantize-SUFFIX` and `dequantize-SUFFIX` of one checkpoint format (quantformat.py)"""
+    model = click.argument("model", type=str)
+    storage = click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
+    tail = [click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on"),
+            click.option("--verbose", is_flag=True, help="Enable verbose logging")]
+    extra = [click.option(f"--{key.replace('_', '-')}", type=click.Choice([str(c) for c in choices]), default=str(default), help=text)
+             for key, (choices, default, text) in fmt.OPTIONS.items()]
+    casts = {key: type(default) for key, (_, default, _) in fmt.OPTIONS.items()}
 
-    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
-    """
-    _fp8_command("dequantize-fp8", model, out_dir, storage_dir, None, dtype, device, verbose)
+    def quantize(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool, **options):
+        _quant_command(fmt, "quantize", model, out_dir, storage_dir, modules, "bf16", device, verbose,
+                       **{key: casts[key](value) for key, value in options.items()})
 
+    def dequantize(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
+        _quant_command(fmt, "dequantize", model, out_dir, storage_dir, None, dtype, device, verbose)
 
-def _mx4_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str, verbose: bool):
-    setup_logging(verbose)
-    from .constants import tune_hip_queues
-    tune_hip_queues()                   # before the first GPU call, as merge does
-    try:
-        from .merge.extract import parse_modules
-        from .merge.mx4 import format_table, run_mx4
-        result = asyncio.run(run_mx4(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device))
-    except Exception as exc:
-        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
-        traceback.print_exc()
-        raise click.Abort()
-    click.echo(format_table(result))
-    click.echo(f"model: {out_dir}")
-
-
-@cli.command("quantize-mxfp4")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the MXFP4 checkpoint is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--modules", type=str, default=None,
-              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
-                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def quantize_mxfp4_command(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool):
-    """MODEL as an MXFP4 checkpoint: E2M1 weights, two to a byte, with one E8M0 scale per 32 elements of a row.
-
-    DIR receives the shards (X.weight as U8 [R, C / 2], X.weight_scale as U8 [R, C / 32]), model.safetensors.index.json
-    and a config.json with the quantization_config block; it can be named as a finetune_merge entry of `merge` in place
-    of MODEL.  A weight whose row length is no multiple of 32 is copied as it is.
-    """
-    _mx4_command("quantize-mxfp4", model, out_dir, storage_dir, modules, "bf16", device, verbose)
+    _register(f"quantize-{fmt.SUFFIX}", fmt.QUANTIZE_HELP, [
+        model, click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path),
+                            help=f"Directory the {fmt.NAME} checkpoint is written to"),
+        storage, *extra,
+        click.option("--modules", type=str, default=None,
+                     help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
+                          "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied"),
+        *tail], quantize)
+    _register(f"dequantize-{fmt.SUFFIX}", fmt.DEQUANTIZE_HELP, [
+        model, click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path),
+                            help="Directory the 16- or 32-bit model is written to"),
+        storage, click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16",
+                              help=f"The dtype the {fmt.NAME} tensors are written in"),
+        *tail], dequantize)
 
 
-@cli.command("dequantize-mxfp4")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the MXFP4 tensors are written in")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def dequantize_mxfp4_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
-    """The MXFP4 checkpoint MODEL written out in 16 or 32 bits: code times its block's power-of-two scale.
-
-    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
-    """
-    _mx4_command("dequantize-mxfp4", model, out_dir, storage_dir, None, dtype, device, verbose)
-
-
-def _nv4_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str, verbose: bool):
-    setup_logging(verbose)
-    from .constants import tune_hip_queues
-    tune_hip_queues()                   # before the first GPU call, as merge does
-    try:
-        from .merge.extract import parse_modules
-        from .merge.mx4 import format_table
-        from .merge.nv4 import run_nv4
-        result = asyncio.run(run_nv4(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device))
-    except Exception as exc:
-        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
-        traceback.print_exc()
-        raise click.Abort()
-    click.echo(format_table(result))
-    click.echo(f"model: {out_dir}")
-
-
-@cli.command("quantize-nvfp4")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the NVFP4 checkpoint is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--modules", type=str, default=None,
-              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
-                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def quantize_nvfp4_command(model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], device: str, verbose: bool):
-    """MODEL as an NVFP4 checkpoint: E2M1 weights, two to a byte, one E4M3 scale per 16 elements of a row, one fp32 scale per tensor.
-
-    DIR receives the shards (X.weight as U8 [R, C / 2], X.weight_scale as F8_E4M3 [R, C / 16], X.weight_scale_2 as one
-    F32), model.safetensors.index.json and a config.json with the quantization_config block; it can be named as a
-    finetune_merge entry of `merge` in place of MODEL.  A weight whose row length is no multiple of 16 is copied as it is.
-    """
-    _nv4_command("quantize-nvfp4", model, out_dir, storage_dir, modules, "bf16", device, verbose)
-
-
-@cli.command("dequantize-nvfp4")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the NVFP4 tensors are written in")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def dequantize_nvfp4_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
-    """The NVFP4 checkpoint MODEL written out in 16 or 32 bits: code times its block's scale times the tensor's scale.
-
-    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
-    """
-    _nv4_command("dequantize-nvfp4", model, out_dir, storage_dir, None, dtype, device, verbose)
-
-
-def _gptq_command(command: str, model: str, out_dir: Path, storage_dir: Path, modules: Optional[str], dtype: str, device: str,
-                  verbose: bool, group_size: int = 128):
-    setup_logging(verbose)
-    from .constants import tune_hip_queues
-    tune_hip_queues()                   # before the first GPU call, as merge does
-    try:
-        from .merge.extract import parse_modules
-        from .merge.gptq import run_gptq
-        from .merge.mx4 import format_table
-        result = asyncio.run(run_gptq(command, model, out_dir, storage_dir, parse_modules(modules), dtype, device, group_size))
-    except Exception as exc:
-        logging.error(f"Error during {command}: {exc}", exc_info=verbose)
-        traceback.print_exc()
-        raise click.Abort()
-    click.echo(format_table(result))
-    click.echo(f"model: {out_dir}")
-
-
-@cli.command("quantize-gptq")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the GPTQ checkpoint is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--group-size", type=click.Choice(["32", "64", "128"]), default="128", help="Input columns that share a scale and a zero-point")
-@click.option("--modules", type=str, default=None,
-              help="Quantise the 2-D weights of the modules whose name ends in one of these, comma-separated "
-                   "(default: q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj); everything else is copied")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def quantize_gptq_command(model: str, out_dir: Path, storage_dir: Path, group_size: str, modules: Optional[str], device: str, verbose: bool):
-    """MODEL as a GPTQ-layout INT4 checkpoint, quantised by ROUND TO NEAREST (asymmetric) - not by the GPTQ solver.
-
-    DIR receives the shards (X.qweight as I32 [C / 8, R], X.qzeros as I32 [C / g, R / 8], X.scales as F16 [C / g, R] and
-    X.g_idx as I32 [C] in place of X.weight), model.safetensors.index.json and a config.json with the
-    quantization_config block; it can be named as a finetune_merge entry of `merge` in place of MODEL.  A weight whose
-    rows are no multiple of 8 or whose columns are no multiple of the group size is copied as it is.
-    """
-    _gptq_command("quantize-gptq", model, out_dir, storage_dir, modules, "bf16", device, verbose, int(group_size))
-
-
-@cli.command("dequantize-gptq")
-@click.argument("model", type=str)
-@click.option("--out", "out_dir", required=True, type=click.Path(path_type=Path), help="Directory the 16- or 32-bit model is written to")
-@click.option("--storage-dir", type=click.Path(path_type=Path), default=Path("storage"), help="Where MODEL lives")
-@click.option("--dtype", type=click.Choice(["bf16", "f16", "f32"]), default="bf16", help="The dtype the GPTQ tensors are written in")
-@click.option("--device", type=str, default="cuda", help="Device to perform tensor operations on")
-@click.option("--verbose", is_flag=True, help="Enable verbose logging")
-def dequantize_gptq_command(model: str, out_dir: Path, storage_dir: Path, dtype: str, device: str, verbose: bool):
-    """The GPTQ checkpoint MODEL written out in 16 or 32 bits: X.weight = (code - zero-point) times its group's scale.
-
-    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
-    """
-    _gptq_command("dequantize-gptq", model, out_dir, storage_dir, None, dtype, device, verbose)
+for _fmt in formats():
+    _register_format(_fmt)
 
 
 @cli.command("emr-task")

@@ -195,26 +195,11 @@ def config_stamp(config: MergeConfig) -> str:
             if is_emr_dir(Path(config.storage_path) / m.model)}            # an EMR pack's: its config and its tensors' header
     if emrs:
         doc["emr_packs"] = emrs
-    from .fp8model import fp8_identity
-    fp8s = {m.model: ident for m in config.finetune_merge
-            if (ident := fp8_identity(Path(config.storage_path) / m.model)) is not None}   # an FP8 checkpoint's: its shard headers
-    if fp8s:
-        doc["fp8_models"] = fp8s
-    from .mx4model import mx4_identity
-    mx4s = {m.model: ident for m in config.finetune_merge
-            if (ident := mx4_identity(Path(config.storage_path) / m.model)) is not None}   # an MXFP4 checkpoint's: its shard headers
-    if mx4s:
-        doc["mx4_models"] = mx4s
-    from .nv4model import nv4_identity
-    nv4s = {m.model: ident for m in config.finetune_merge
-            if (ident := nv4_identity(Path(config.storage_path) / m.model)) is not None}   # an NVFP4 checkpoint's: its shard headers
-    if nv4s:
-        doc["nv4_models"] = nv4s
-    from .gptqmodel import gptq_identity
-    gptqs = {m.model: ident for m in config.finetune_merge
-             if (ident := gptq_identity(Path(config.storage_path) / m.model)) is not None}   # a GPTQ checkpoint's: its shard headers
-    if gptqs:
-        doc["gptq_models"] = gptqs
+    from .quantformat import identity_of
+    for m in config.finetune_merge:         # a quantised checkpoint's: its shard headers, under its format's key
+        found = identity_of(Path(config.storage_path) / m.model)
+        if found is not None:
+            doc.setdefault(f"{found[0]}_models", {})[m.model] = found[1]
     return hashlib.sha256(json.dumps(doc, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 

@@ -799,7 +799,7 @@ class Engine:
     MX4_FNS = {"f32_to_e2m1": _lib.MX4_F32_TO_E2M1, "e2m1_to_f32": _lib.MX4_E2M1_TO_F32,
                "amax_to_e8m0": _lib.MX4_AMAX_TO_E8M0, "e8m0_to_f32": _lib.MX4_E8M0_TO_F32}
 
-    def _mx4_check(self, rc: int, what: str, layer_name: str):
+    def _quant_check(self, rc: int, what: str, layer_name: str):
         try:
             self.ctx.check(rc)
         except SmhipError as e:
@@ -828,7 +828,7 @@ class Engine:
         sc = torch.empty((rows, cols // _lib.MX4_BLOCK), dtype=torch.uint8, device=self.device)
         desc = _lib.Mx4QuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, _lib.MX4_BLOCK)
         rep = _lib.Mx4Report()
-        self._mx4_check(self.lib.dll.smhip_mx4_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(), C.byref(rep),
+        self._quant_check(self.lib.dll.smhip_mx4_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(), C.byref(rep),
                                                      self._stream()), "Non-finite value", layer_name)
         return codes, sc, Mx4Report(rows=rows, cols=cols, blocks=int(rep.blocks), zero_blocks=int(rep.zero_blocks),
                                     saturated=int(rep.saturated), nonfinite=int(rep.nonfinite))
@@ -857,7 +857,7 @@ class Engine:
             raise ValueError(f"mx4_dequant: out of {who} is {out.dtype} {list(out.shape)} on {out.device}; a contiguous "
                              f"{dtype} {[rows, cols]} tensor on {self.device} expected")
         desc = _lib.Mx4DequantDesc(cs.data_ptr(), sc.data_ptr(), rows, cols, _lib.MX4_BLOCK, _DTYPE_CODE[dtype])
-        self._mx4_check(self.lib.dll.smhip_mx4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
+        self._quant_check(self.lib.dll.smhip_mx4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
                         "NaN scale code", layer_name)
         return out
 
@@ -897,7 +897,7 @@ class Engine:
         sc = torch.empty((rows, cols // _lib.NV4_BLOCK), dtype=torch.uint8, device=self.device)
         desc = _lib.Nv4QuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, _lib.NV4_BLOCK)
         rep, g = _lib.Nv4Report(), C.c_float()
-        self._mx4_check(self.lib.dll.smhip_nv4_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(), C.byref(g),
+        self._quant_check(self.lib.dll.smhip_nv4_quant(self.ctx.h, C.byref(desc), codes.data_ptr(), sc.data_ptr(), C.byref(g),
                                                      C.byref(rep), self._stream()), "Non-finite value", layer_name)
         report = Nv4Report(rows=rows, cols=cols, blocks=int(rep.blocks), zero_blocks=int(rep.zero_blocks),
                            zero_scale_blocks=int(rep.zero_scale_blocks), saturated=int(rep.saturated), nonfinite=int(rep.nonfinite))
@@ -932,7 +932,7 @@ class Engine:
             raise ValueError(f"nv4_dequant: out of {who} is {out.dtype} {list(out.shape)} on {out.device}; a contiguous "
                              f"{dtype} {[rows, cols]} tensor on {self.device} expected")
         desc = _lib.Nv4DequantDesc(cs.data_ptr(), sc.data_ptr(), global_scale, rows, cols, _lib.NV4_BLOCK, _DTYPE_CODE[dtype])
-        self._mx4_check(self.lib.dll.smhip_nv4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
+        self._quant_check(self.lib.dll.smhip_nv4_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
                         "NaN scale code", layer_name)
         return out
 
@@ -962,7 +962,7 @@ class Engine:
         g_idx = torch.empty((cols,), dtype=torch.int32, device=self.device)
         desc = _lib.GptqQuantDesc(xs.data_ptr(), _DTYPE_CODE[xs.dtype], rows, cols, group_size)
         rep = _lib.GptqReport()
-        self._mx4_check(self.lib.dll.smhip_gptq_quant(self.ctx.h, C.byref(desc), qweight.data_ptr(), qzeros.data_ptr(),
+        self._quant_check(self.lib.dll.smhip_gptq_quant(self.ctx.h, C.byref(desc), qweight.data_ptr(), qzeros.data_ptr(),
                                                       scales.data_ptr(), g_idx.data_ptr(), C.byref(rep), self._stream()),
                         "Non-finite value", layer_name)
         report = GptqReport(rows=rows, cols=cols, group_size=group_size, groups=int(rep.groups), zero_groups=int(rep.zero_groups),
@@ -1003,7 +1003,7 @@ class Engine:
                              f"{dtype} {[rows, cols]} tensor on {self.device} expected")
         desc = _lib.GptqDequantDesc(qw.data_ptr(), qz.data_ptr(), sc.data_ptr(), gi.data_ptr(), rows, cols, group_size,
                                     _DTYPE_CODE[dtype])
-        self._mx4_check(self.lib.dll.smhip_gptq_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
+        self._quant_check(self.lib.dll.smhip_gptq_dequant(self.ctx.h, C.byref(desc), out.data_ptr(), self._stream()),
                         "Non-finite scale", layer_name)
         return out
 

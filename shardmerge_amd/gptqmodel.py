@@ -11,17 +11,16 @@ false, a ``checkpoint_format`` - where one is named - of ``gptq``, a ``group_siz
 ``X.qweight`` with its three companions in the dtypes and shapes above.  As a ``finetune_merge`` entry its tensor
 ``X.weight`` is ``Engine.gptq_dequant(X.qweight, X.qzeros, X.scales, X.g_idx, dtype of the base's X.weight)`` (the
 function is stated in include/shardmerge_hip.h, smhip_gptq_dequant).  ``python -m shard quantize-gptq`` writes one - by
-round to nearest, not by the GPTQ solver - and ``dequantize-gptq`` turns one back (merge/gptq.py).  Everything this
-module rejects is rejected before any output is written, and the message names the model and the tensor or field.
+round to nearest, not by the GPTQ solver; the four tensors take the place of a named module's ``X.weight`` with ``R % 8
+== 0`` and ``C % group_size == 0``, any other is copied - and ``dequantize-gptq`` turns one back (merge/quantize.py).
+Everything this module rejects is rejected before any output is written, and the message names the model and the
+tensor or field.
 """
 from __future__ import annotations
 
-import hashlib
-import json
-from pathlib import Path
-from typing import Dict, Optional, Tuple
+from typing import Dict
 
-from .adapter import FULL_INDEX, read_header
+from .quantformat import CONFIG_BLOCK, QuantModel, quant_blocks
 
 QUANT_METHOD = "gptq"
 GROUPS = (32, 64, 128)
@@ -34,54 +33,38 @@ class GptqModelError(ValueError):
     """a GPTQ checkpoint this build cannot read; the message names the model and the tensor or field"""
 
 
-def quantization_config(not_converted, group_size: int = 128) -> Dict:
-    """the ``quantization_config`` block of a checkpoint `quantize-gptq` writes"""
-    return {"quant_method": QUANT_METHOD, "bits": 4, "group_size": group_size, "desc_act": False, "sym": False,
-            "checkpoint_format": "gptq", "modules_to_not_convert": sorted(not_converted)}
-
-
-def quant_block(path: Path) -> Optional[Dict]:
-    try:
-        doc = json.loads((Path(path) / "config.json").read_bytes())
-    except (OSError, ValueError):
-        return None
-    qc = doc.get("quantization_config") if isinstance(doc, dict) else None
-    return qc if isinstance(qc, dict) else None
-
-
-def says_gptq(path: Path) -> bool:
-    qc = quant_block(path)
-    return qc is not None and qc.get("quant_method") == QUANT_METHOD
-
-
 def _is_quad(header: Dict, name: str) -> bool:
     return (name.endswith(QWEIGHT) and header[name]["dtype"] == "I32"
             and all(name[: -len(QWEIGHT)] + c in header for c in COMPANIONS))
 
 
-class GptqModel:
-    """the GPTQ tensors of the full model at `path`; `keys`: the name ``X.weight`` of the tensor they stand for -> the
-    names of (qweight, qzeros, scales, g_idx)"""
+class GptqModel(QuantModel):
+    """`keys`: the name ``X.weight`` of the tensor they stand for -> the names of (qweight, qzeros, scales, g_idx);
+    `group_size`: the checkpoint's"""
+    NAME, A_NAME, A_LABEL, KEY, SUFFIX, Error = "GPTQ", "a GPTQ", "a GPTQ", "gptq", "gptq", GptqModelError
+    EXPECTED = ("is no GPTQ checkpoint (quant_method 'gptq' in config.json and I32 qweight tensors with their qzeros, scales "
+                "and g_idx are expected)")
+    OPTIONS = {"group_size": (GROUPS, 128, "Input columns that share a scale and a zero-point")}
+    QUANTIZE_HELP = """MODEL as a GPTQ-layout INT4 checkpoint, quantised by ROUND TO NEAREST (asymmetric) - not by the GPTQ solver.
 
-    def __init__(self, uri: str, path: Path, weight_map: Dict[str, str]):
-        self.uri = uri
-        self.path = Path(path)
-        self.keys: Dict[str, Tuple[str, str, str, str]] = {}
-        self.group_size = 0
-        sha = hashlib.sha256()
-        header = {}
-        for shard in sorted(set(weight_map.values())):
-            raw, doc = read_header(self.path / shard)
-            sha.update(shard.encode() + b"\0" + raw)
-            header.update(doc)
-        header.pop("__metadata__", None)
-        self.header = header
-        self.identity = {"gptq_headers": sha.hexdigest()}      # offsets, shapes and metadata of every shard
-        self.claimed = says_gptq(self.path) and any(_is_quad(header, n) for n in header)
-        if not self.claimed:
-            return
-        qc = quant_block(self.path)
-        field = "config.json quantization_config"
+    DIR receives the shards (X.qweight as I32 [C / 8, R], X.qzeros as I32 [C / g, R / 8], X.scales as F16 [C / g, R] and
+    X.g_idx as I32 [C] in place of X.weight), model.safetensors.index.json and a config.json with the
+    quantization_config block; it can be named as a finetune_merge entry of `merge` in place of MODEL.  A weight whose
+    rows are no multiple of 8 or whose columns are no multiple of the group size is copied as it is.
+    """
+    DEQUANTIZE_HELP = """The GPTQ checkpoint MODEL written out in 16 or 32 bits: X.weight = (code - zero-point) times its group's scale.
+
+    DIR can be named wherever `merge` takes a full model: as base, output_base_model or a finetune_merge entry.
+    """
+
+    @classmethod
+    def says(cls, path, header) -> bool:
+        return (quant_blocks(path).get(CONFIG_BLOCK, {}).get("quant_method") == QUANT_METHOD
+                and any(_is_quad(header, n) for n in header))
+
+    def validate(self):
+        header, field = self.header, CONFIG_BLOCK
+        qc = quant_blocks(self.path)[field]
         if qc.get("bits") != 4:
             self._fail(f"{field}.bits {qc.get('bits')!r} is not 4")
         if qc.get("desc_act", False):
@@ -112,40 +95,39 @@ class GptqModel:
                 self._fail(f"tensor {stem + WEIGHT_SUFFIX} stands next to {name}")
             self.keys[stem + WEIGHT_SUFFIX] = (name,) + tuple(stem + c for c in COMPANIONS)
 
-    def _fail(self, what: str):
-        raise GptqModelError(f"GPTQ checkpoint {self.uri}: {what}")
-
-    @property
-    def stored_names(self):
-        """every stored tensor that belongs to a weight and is no tensor of the model"""
-        return {n for quad in self.keys.values() for n in quad}
-
-    def model_keys(self, keys):
-        """the tensor list of the model the checkpoint stands for: the four names of a weight are its ``X.weight``"""
-        return (set(keys) - self.stored_names) | set(self.keys)
-
-    def shape(self, name: str):
-        """the shape [R, C] of the tensor ``X.weight`` that `name` stands for"""
+    def shape(self, name):
         eighth, r = self.header[self.keys[name][0]]["shape"]
         return [int(r), 8 * int(eighth)]
 
+    def dequant(self, engine, tensors, dtype, layer_name):
+        return engine.gptq_dequant(*tensors, dtype, layer_name=layer_name)
 
-def gptq_model(uri: str, path: Path, weight_map: Dict[str, str]) -> Optional[GptqModel]:
-    """the GptqModel of a full model directory; None unless config.json says gptq and a shard holds the four tensors"""
-    if not says_gptq(path):
-        return None
-    m = GptqModel(uri, path, weight_map)
-    return m if m.claimed else None
+    def summary(self) -> str:
+        return f"GPTQ checkpoint, {len(self.keys)} INT4 tensors in groups of {self.group_size}"
 
+    @classmethod
+    def check_options(cls, command, group_size=128):
+        if group_size not in GROUPS:
+            raise ValueError(f"{command}: --group-size {group_size} is not one of {list(GROUPS)}")
 
-def gptq_identity(path: Path) -> Optional[Dict[str, str]]:
-    """what decides a GPTQ checkpoint's content for a resumed run: its shard headers; None for anything else"""
-    path = Path(path)
-    if not (path / FULL_INDEX).exists():
-        return None
-    try:
-        weight_map = json.loads((path / FULL_INDEX).read_bytes())["weight_map"]
-        m = gptq_model(str(path), path, weight_map)
-    except (OSError, ValueError, KeyError):
-        return None
-    return m.identity if m is not None else None
+    @classmethod
+    def fits(cls, shape, group_size=128) -> bool:
+        return shape[0] % 8 == 0 and shape[1] % group_size == 0
+
+    @classmethod
+    def unfit(cls, shape, group_size=128) -> str:
+        return f"{list(shape)} is not rows a multiple of 8 by columns a multiple of {group_size}"
+
+    @classmethod
+    def quant(cls, engine, tensor, layer_name, group_size=128):
+        stem = layer_name[: -len(WEIGHT_SUFFIX)]
+        *four, rep = engine.gptq_quant(tensor, group_size, layer_name=layer_name)
+        return ({stem + suffix: v.cpu() for suffix, v in zip((QWEIGHT,) + COMPANIONS, four)},
+                {"groups": rep.groups, "zero_groups": rep.zero_groups, "scale_clamped": rep.scale_clamped, "clipped": rep.clipped},
+                f"{rep.groups} groups of {group_size} ({rep.zero_groups} of zeros, {rep.scale_clamped} with a clamped scale), "
+                f"{rep.clipped} clipped, {rep.nonfinite} non-finite")
+
+    @classmethod
+    def quantization_config(cls, not_converted, group_size=128):
+        return {"quant_method": QUANT_METHOD, "bits": 4, "group_size": group_size, "desc_act": False, "sym": False,
+                "checkpoint_format": "gptq", "modules_to_not_convert": sorted(not_converted)}

@@ -24,10 +24,7 @@ from safetensors import safe_open
 from .adapter import ADAPTER_BIN, AdapterError, LoraAdapter, is_adapter_dir, is_bin_only_adapter_dir
 from .deltapack import DeltaPack, is_pack_dir
 from .emrpack import EmrPack, is_emr_dir
-from .fp8model import Fp8Model, fp8_model
-from .mx4model import Mx4Model, mx4_model
-from .gptqmodel import GptqModel, gptq_model
-from .nv4model import Nv4Model, nv4_model
+from .quantformat import QuantModel, claim
 
 logger = logging.getLogger(__name__)
 
@@ -74,10 +71,7 @@ class LocalModelIndex:
         self.adapters: Dict[str, LoraAdapter] = {}     # LoRA adapter directories (adapter.py), by model uri
         self.packs: Dict[str, DeltaPack] = {}          # delta pack directories (deltapack.py), by model uri
         self.emrs: Dict[str, EmrPack] = {}             # EMR pack directories (emrpack.py), by model uri
-        self.fp8s: Dict[str, Fp8Model] = {}            # block-scaled FP8 checkpoints (fp8model.py), by model uri
-        self.mx4s: Dict[str, Mx4Model] = {}            # MXFP4 checkpoints (mx4model.py), by model uri
-        self.nv4s: Dict[str, Nv4Model] = {}            # NVFP4 checkpoints (nv4model.py), by model uri
-        self.gptqs: Dict[str, GptqModel] = {}          # GPTQ-layout INT4 checkpoints (gptqmodel.py), by model uri
+        self.quants: Dict[str, QuantModel] = {}        # quantised checkpoints of any format (quantformat.py), by model uri
 
     async def add_model(self, model_uri: str, revision: str = "main"):
         if model_uri in self.model_indexes:
@@ -119,27 +113,11 @@ class LocalModelIndex:
             index = json.load(fh)
         self.model_indexes[model_uri] = index
         self._ordered_weights[model_uri] = order_weights(list(index["weight_map"].keys()))
-        nv4 = nv4_model(model_uri, self.storage_path / model_uri, index["weight_map"])
-        if nv4 is not None:
-            # an NVFP4 checkpoint: a config says so and its coded weights come with both scales; tested before FP8, which
-            # its F8_E4M3 block scales would otherwise claim
-            self.nv4s[model_uri] = nv4
-            logger.info(f"Model {model_uri}: NVFP4 checkpoint, {len(nv4.scale_keys)} two-level-scaled E2M1 tensors")
-        fp8 = fp8_model(model_uri, self.storage_path / model_uri, index["weight_map"])
-        if fp8 is not None:
-            # a block-scaled FP8 checkpoint: a full model whose E4M3 tensors come with a scale tensor each
-            self.fp8s[model_uri] = fp8
-            logger.info(f"Model {model_uri}: FP8 checkpoint, {len(fp8.scale_keys)} block-scaled E4M3 tensors")
-        mx4 = mx4_model(model_uri, self.storage_path / model_uri, index["weight_map"])
-        if mx4 is not None:
-            # an MXFP4 checkpoint: config.json says so and its coded weights come with a scale tensor each
-            self.mx4s[model_uri] = mx4
-            logger.info(f"Model {model_uri}: MXFP4 checkpoint, {len(mx4.scale_keys)} micro-scaled E2M1 tensors")
-        gptq = gptq_model(model_uri, self.storage_path / model_uri, index["weight_map"])
-        if gptq is not None:
-            # a GPTQ checkpoint: config.json says so and a weight is stored as qweight, qzeros, scales and g_idx
-            self.gptqs[model_uri] = gptq
-            logger.info(f"Model {model_uri}: GPTQ checkpoint, {len(gptq.keys)} INT4 tensors in groups of {gptq.group_size}")
+        quant = claim(model_uri, self.storage_path / model_uri, index["weight_map"])
+        if quant is not None:
+            # a quantised checkpoint: a full model some of whose weights are stored as codes with their scales
+            self.quants[model_uri] = quant
+            logger.info(f"Model {model_uri}: {quant.summary()}")
         logger.info(f"Model {model_uri}: {len(set(index['weight_map'].values()))} shards, {len(index['weight_map'])} tensors")
 
     def adapter(self, model_uri: str) -> Optional[LoraAdapter]:
@@ -154,21 +132,27 @@ class LocalModelIndex:
         """the EMR pack registered under this uri, None for anything else"""
         return self.emrs.get(model_uri)
 
-    def fp8(self, model_uri: str) -> Optional[Fp8Model]:
-        """the block-scaled FP8 checkpoint registered under this uri, None for anything else"""
-        return self.fp8s.get(model_uri)
+    def quant(self, model_uri: str, key: Optional[str] = None) -> Optional[QuantModel]:
+        """the quantised checkpoint registered under this uri - of the format with this KEY only, when one is given;
+        None for anything else"""
+        m = self.quants.get(model_uri)
+        return m if m is not None and key in (None, m.KEY) else None
 
-    def nv4(self, model_uri: str) -> Optional[Nv4Model]:
-        """the NVFP4 checkpoint registered under this uri, None for anything else"""
-        return self.nv4s.get(model_uri)
+    def fp8(self, model_uri: str) -> Optional[QuantModel]:
+        """the block-scaled FP8 checkpoint (fp8model.py) registered under this uri, None for anything else"""
+        return self.quant(model_uri, "fp8")
 
-    def gptq(self, model_uri: str) -> Optional[GptqModel]:
-        """the GPTQ-layout INT4 checkpoint registered under this uri, None for anything else"""
-        return self.gptqs.get(model_uri)
+    def mx4(self, model_uri: str) -> Optional[QuantModel]:
+        """the MXFP4 checkpoint (mx4model.py) registered under this uri, None for anything else"""
+        return self.quant(model_uri, "mx4")
 
-    def mx4(self, model_uri: str) -> Optional[Mx4Model]:
-        """the MXFP4 checkpoint registered under this uri, None for anything else"""
-        return self.mx4s.get(model_uri)
+    def nv4(self, model_uri: str) -> Optional[QuantModel]:
+        """the NVFP4 checkpoint (nv4model.py) registered under this uri, None for anything else"""
+        return self.quant(model_uri, "nv4")
+
+    def gptq(self, model_uri: str) -> Optional[QuantModel]:
+        """the GPTQ-layout INT4 checkpoint (gptqmodel.py) registered under this uri, None for anything else"""
+        return self.quant(model_uri, "gptq")
 
     def _require(self, model_uri: str, tensor_name: Optional[str] = None) -> Dict:
         if model_uri not in self.model_indexes:

@@ -49,8 +49,8 @@ class MergeTensorsBase(ABC):
         base's tensor and, when the adapter targets it, the two factors; for a delta pack entry its base's tensor and
         the planes and scale, the tensor the pack stores whole, or the base's tensor alone; for an EMR pack entry its
         base's and the unified model's tensor, the mask and the rescaler, the whole tensor, or the base's tensor alone;
-        for an FP8 or an MXFP4 checkpoint entry the codes and their scale tensor, for an NVFP4 one the codes and both
-        scale tensors, for a GPTQ one the four tensors a weight is stored as, or the tensor it keeps in 16 bits"""
+        for a quantised checkpoint entry (quantformat.py) the tensors a weight is stored as, or the tensor it keeps in
+        16 bits"""
         pack = self.index_manager.pack(m.model)
         if pack is not None:
             t = pack.tensors.get(layer_name)
@@ -68,18 +68,9 @@ class MergeTensorsBase(ABC):
             if t.kind == "full":
                 return [(m.model, t.full_key)]
             return [(m.base, layer_name), (emr.unified, layer_name), (m.model, t.mask_key), (m.model, t.scale_key)]
-        fp8 = self.index_manager.fp8(m.model)
-        if fp8 is not None and layer_name in fp8.scale_keys:
-            return [(m.model, layer_name), (m.model, fp8.scale_keys[layer_name])]
-        mx4 = self.index_manager.mx4(m.model)
-        if mx4 is not None and layer_name in mx4.scale_keys:
-            return [(m.model, layer_name), (m.model, mx4.scale_keys[layer_name])]
-        nv4 = self.index_manager.nv4(m.model)
-        if nv4 is not None and layer_name in nv4.scale_keys:
-            return [(m.model, layer_name), (m.model, nv4.scale_keys[layer_name]), (m.model, nv4.global_keys[layer_name])]
-        gptq = self.index_manager.gptq(m.model)
-        if gptq is not None and layer_name in gptq.keys:
-            return [(m.model, key) for key in gptq.keys[layer_name]]
+        quant = self.index_manager.quant(m.model)
+        if quant is not None and layer_name in quant.keys:
+            return [(m.model, key) for key in quant.keys[layer_name]]
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return [(m.model, layer_name)]
@@ -97,12 +88,8 @@ class MergeTensorsBase(ABC):
         pack entry (deltapack.py) `Engine.delta_apply` on the base tensor and the planes, the tensor the pack stores
         whole, or the base tensor itself where the pack holds nothing for it.  For an EMR pack entry (emrpack.py)
         `Engine.emr_apply` on the base tensor, the unified model's tensor, the mask and the rescaler, likewise.  For a
-        block-scaled FP8 checkpoint entry (fp8model.py) `Engine.fp8_dequant` of the codes and their scales into the
-        dtype its base holds the tensor in; the tensors it keeps in 16 bits pass as they are.  For an MXFP4
-        checkpoint entry (mx4model.py) `Engine.mx4_dequant` of the codes and their scales, likewise; for an NVFP4
-        checkpoint entry (nv4model.py) `Engine.nv4_dequant` of the codes, the block scales and the tensor's scale; for
-        a GPTQ checkpoint entry (gptqmodel.py), which holds no `X.weight`, `Engine.gptq_dequant` of `X.qweight`,
-        `X.qzeros`, `X.scales` and `X.g_idx`.
+        quantised checkpoint entry (quantformat.py) the format's `dequant` of the tensors the weight is stored as into
+        the dtype its base holds the tensor in; the tensors it keeps in 16 bits pass as they are.
         fetch: async (uri, tensor name) -> tensor, the caller's (caching) reader; default: `_fetch` on `device`."""
         if fetch is None:
             async def fetch(uri, tname):
@@ -131,30 +118,11 @@ class MergeTensorsBase(ABC):
             mask = await fetch(m.model, t.mask_key)
             scale = await fetch(m.model, t.scale_key)
             return self.engine(device).emr_apply(base, unified, mask, scale)
-        fp8 = self.index_manager.fp8(m.model)
-        if fp8 is not None and layer_name in fp8.scale_keys:
-            codes = await fetch(m.model, layer_name)
-            scale = await fetch(m.model, fp8.scale_keys[layer_name])
-            return self.engine(device).fp8_dequant(codes, scale, self._fp8_out_dtype(m, layer_name),
-                                                   name=f"{m.model}: {layer_name}")
-        mx4 = self.index_manager.mx4(m.model)
-        if mx4 is not None and layer_name in mx4.scale_keys:
-            codes = await fetch(m.model, layer_name)
-            scale = await fetch(m.model, mx4.scale_keys[layer_name])
-            return self.engine(device).mx4_dequant(codes, scale, self._fp8_out_dtype(m, layer_name, "MXFP4"),
-                                                   layer_name=f"{m.model}: {layer_name}")
-        nv4 = self.index_manager.nv4(m.model)
-        if nv4 is not None and layer_name in nv4.scale_keys:
-            codes = await fetch(m.model, layer_name)
-            scale = await fetch(m.model, nv4.scale_keys[layer_name])
-            scale_2 = await fetch(m.model, nv4.global_keys[layer_name])
-            return self.engine(device).nv4_dequant(codes, scale, scale_2, self._fp8_out_dtype(m, layer_name, "NVFP4"),
-                                                   layer_name=f"{m.model}: {layer_name}")
-        gptq = self.index_manager.gptq(m.model)
-        if gptq is not None and layer_name in gptq.keys:
-            qweight, qzeros, scales, g_idx = [await fetch(m.model, key) for key in gptq.keys[layer_name]]
-            return self.engine(device).gptq_dequant(qweight, qzeros, scales, g_idx, self._fp8_out_dtype(m, layer_name, "GPTQ"),
-                                                    layer_name=f"{m.model}: {layer_name}")
+        quant = self.index_manager.quant(m.model)
+        if quant is not None and layer_name in quant.keys:
+            stored = [await fetch(m.model, key) for key in quant.keys[layer_name]]
+            return quant.dequant(self.engine(device), stored, self._quant_out_dtype(m, layer_name, quant.NAME),
+                                 f"{m.model}: {layer_name}")
         adapter = self.index_manager.adapter(m.model)
         if adapter is None:
             return await fetch(m.model, layer_name)
@@ -175,11 +143,12 @@ class MergeTensorsBase(ABC):
             from ..adapter import AdapterError
             raise AdapterError(f"LoRA adapter {m.model}: tensor {layer_name} (DoRA): {e.message}") from e
 
-    def _fp8_out_dtype(self, m: MergeModel, layer_name: str, what: str = "FP8") -> torch.dtype:
-        """the dtype an FP8 or MXFP4 entry's tensor is dequantised into: the one its base holds the tensor in (shard headers)"""
+    def _quant_out_dtype(self, m: MergeModel, layer_name: str, what: str) -> torch.dtype:
+        """the dtype a quantised entry's tensor is dequantised into: the one its base holds the tensor in (shard headers);
+        what: the format's NAME"""
         from ..adapter import base_tensor_meta
         from ..stformat import ST_DTYPES
-        cache = self.__dict__.setdefault("_fp8_base_meta", {})
+        cache = self.__dict__.setdefault("_quant_base_meta", {})
         if m.base not in cache:
             cache[m.base] = base_tensor_meta(self.index_manager, m.base)
         dtype = ST_DTYPES.get(cache[m.base][layer_name][1])
@@ -218,20 +187,12 @@ class MergeTensorsBase(ABC):
         for m in cfg.finetune_merge:
             await self.index_manager.add_model(m.base)
             await self.index_manager.add_model(m.model)
-        # an FP8 checkpoint is read as a finetune only: the merge walks the output base's tensor list and writes its dtypes
+        # a quantised checkpoint is read as a finetune only: the merge walks the output base's tensor list and writes its dtypes
         for role, uri in [("output_base_model", cfg.output_base_model)] + [(f"the base of {m.model}", m.base) for m in cfg.finetune_merge]:
-            if self.index_manager.fp8(uri) is not None:
-                raise ValueError(f"{uri} is a block-scaled FP8 checkpoint and cannot be {role}: write it out in 16 bits with "
-                                 f"`dequantize-fp8 {uri} --out DIR` first and name that directory")
-            if self.index_manager.mx4(uri) is not None:
-                raise ValueError(f"{uri} is an MXFP4 checkpoint and cannot be {role}: write it out in 16 bits with "
-                                 f"`dequantize-mxfp4 {uri} --out DIR` first and name that directory")
-            if self.index_manager.nv4(uri) is not None:
-                raise ValueError(f"{uri} is an NVFP4 checkpoint and cannot be {role}: write it out in 16 bits with "
-                                 f"`dequantize-nvfp4 {uri} --out DIR` first and name that directory")
-            if self.index_manager.gptq(uri) is not None:
-                raise ValueError(f"{uri} is a GPTQ checkpoint and cannot be {role}: write it out in 16 bits with "
-                                 f"`dequantize-gptq {uri} --out DIR` first and name that directory")
+            quant = self.index_manager.quant(uri)
+            if quant is not None:
+                raise ValueError(f"{uri} is {quant.A_LABEL} checkpoint and cannot be {role}: write it out in 16 bits with "
+                                 f"`dequantize-{quant.SUFFIX} {uri} --out DIR` first and name that directory")
         base_keys = self.index_manager.get_model_keys(cfg.output_base_model)
         for m in cfg.finetune_merge:
             adapter = self.index_manager.adapter(m.model)
@@ -262,18 +223,9 @@ class MergeTensorsBase(ABC):
                 emr.check_against(m.base, base_tensor_meta(self.index_manager, m.base))
                 emr.check_against(emr.unified, base_tensor_meta(self.index_manager, emr.unified), what="unified model")
             keys = self.index_manager.get_model_keys(m.base if adapter is not None or pack is not None or emr is not None else m.model)
-            fp8 = self.index_manager.fp8(m.model)
-            if fp8 is not None:
-                keys = keys - fp8.scale_names                  # (the scale tensors belong to their weights)
-            mx4 = self.index_manager.mx4(m.model)
-            if mx4 is not None:
-                keys = keys - mx4.scale_names
-            nv4 = self.index_manager.nv4(m.model)
-            if nv4 is not None:
-                keys = keys - nv4.scale_names
-            gptq = self.index_manager.gptq(m.model)
-            if gptq is not None:
-                keys = gptq.model_keys(keys)            # (the four tensors of a weight stand for its X.weight)
+            quant = self.index_manager.quant(m.model)
+            if quant is not None:
+                keys = quant.model_keys(keys)           # (the tensors a weight is stored as stand for the weight)
             if keys != base_keys:
                 # (the reference means to raise this ValueError too but trips over a missing
                 # attribute first - SURVEY quirk Q9; the intended error is raised here)
